@@ -66,6 +66,39 @@ def make_inputs(kw, B, device, seed, module):
     return dict(x0=x0, sigma=sigma, x=x, text=text, um=ones, vm=ones, extra=extra)
 
 
+DUMP_BYTES = 64_000_000                                      # cap of --dump-outputs, npy headers included
+
+
+def step_outputs(loss, model):
+    """What a caller of the timed step receives, copied to the host as float32: the loss it returns and every parameter's gradient."""
+    out = {"loss": loss["loss"].detach().float().cpu()}
+    for n, p in model.named_parameters():
+        if p.grad is not None:
+            out["grad." + n] = p.grad.detach().float().cpu()
+    return out
+
+
+def dump_outputs(outs, path):
+    """One DIR/<name>.npy per output.  Above DUMP_BYTES every array keeps the same share of its elements (flattened), at positions drawn
+    from a generator seeded by the array's name: the same positions in every run, so two builds compare element for element."""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 4 * sum(t.numel() for t in outs.values())
+    frac = min(1.0, (DUMP_BYTES - 256 * len(outs)) / max(total, 1))
+    written = 0
+    for name, t in outs.items():
+        k = max(1, int(t.numel() * frac))
+        if k < t.numel():
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(zlib.crc32(name.encode()))
+                                 )[:k].sort().values
+            t = t.flatten()[idx]
+        np.save(os.path.join(path, name + ".npy"), t.numpy())
+        written += 4 * t.numel()
+    print(f"[bench] --dump-outputs: {len(outs)} arrays, {written / 1e6:.1f} MB of float32 in {path}"
+          + (f" (a seeded {frac:.3f} sample of {total / 1e6:.1f} MB)" if frac < 1.0 else ""), file=sys.stderr, flush=True)
+
+
 def conv_flops(info):
     """Algorithmic FLOPs of one conv / dgrad / wgrad launch from the REALISED per-expert row counts."""
     per_px = 2.0 * info["HW"] * info["O"] * info["I"]
@@ -372,7 +405,12 @@ def main():
     ap.add_argument("--single-graph", action="store_true", help="capture the step as ONE hipGraph instead of the seven staged graphs (A/B)")
     ap.add_argument("--sync-each-step", action="store_true", help="diagnostic: synchronize after every step (the host never runs ahead of the GPU)")
     ap.add_argument("--no-graph", action="store_true", help="issue every launch from Python instead of replaying the captured hipGraph")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed (loss, every parameter gradient) as DIR/<name>.npy, float32, "
+                         "at most 64 MB in all (beyond that a fixed, seeded sample of each array)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -493,6 +531,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     ms = 1e3 * dt / args.steps
+    if args.dump_outputs and rank == 0:                      # before any further step overwrites the last timed step's results
+        dump_outputs(step_outputs(loss, model), args.dump_outputs)
     stage_ms = None
     if not args.no_graph and graphed is not None and hasattr(graphed, "stage_times"):
         graphed.timing = True                                # one extra, untimed step with HIP events between the staged graphs

@@ -53,10 +53,10 @@ def _noise(x: Tensor) -> Tensor:
 # L0: magnitude-preserving primitives            models/model_internals.py
 # --------------------------------------------------------------------------
 def normalize(x: Tensor, dim: Optional[Sequence[int]] = None, eps: float = 1e-4) -> Tensor:
-    """x / (eps + ||x||_2 * sqrt(n_norm / n_x)); norm in fp32 (model_internals.py:8-30)."""
+    """x / (eps + ||x||_2 * sqrt(n_norm / n_x)); norm in fp32, fp64 for fp64 inputs (model_internals.py:8-30)."""
     if dim is None:
         dim = list(range(1, x.ndim))
-    n = torch.linalg.vector_norm(x, dim=list(dim), keepdim=True, dtype=torch.float32)
+    n = torch.linalg.vector_norm(x, dim=list(dim), keepdim=True, dtype=torch.promote_types(x.dtype, torch.float32))
     n = eps + n * math.sqrt(n.numel() / x.numel())
     return x / n.to(x.dtype)
 
@@ -112,8 +112,8 @@ def mp_fourier(x: Tensor, freqs: Tensor, phases: Tensor) -> Tensor:
 
 def mp_weight(w: Tensor, gain=1.0) -> Tensor:
     """Effective weight of an MP_Conv: normalize(w) * gain / sqrt(fan_in)
-    (model_internals.py:258-259)."""
-    w = normalize(w.float())
+    (model_internals.py:258-259).  fp32, fp64 for fp64 weights."""
+    w = normalize(w.to(torch.promote_types(w.dtype, torch.float32)))
     return w * (gain / math.sqrt(w[0].numel()))
 
 

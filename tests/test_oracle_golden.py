@@ -230,16 +230,19 @@ def test_round4_boundary_cases():
     general normalize / mp_cat arguments, strided MP_Conv."""
     import os
     g = torch.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "round4.pt"), weights_only=False)
+    # The oracle runs this case in fp64: the stored fp32 output (~40 layers, |out| up to 542) carries its own summation-order rounding,
+    # 1.28e-4 beyond rtol * |ref| at its worst element against the exact value, and an fp32 oracle adds the rounding of whichever CPU
+    # kernels run the test.  In fp64 only the fixture's fixed rounding is left, the same on every machine.
     c = g["unet_expert_64x128"]
-    P = {k: v.clone().requires_grad_(True) for k, v in c["state"].items()}
-    x = c["x"].clone().requires_grad_(True)
-    out = O.unet_expert(P, "", x, c["te"], c["text"])
-    assert out.shape == (1, 4, 64, 128)
-    close(out, c["out"], rtol=1e-4, atol=1e-4)
-    out.backward(c["grad_out"])
-    close_scaled(x.grad, c["x_grad"])
+    P = {k: v.double().requires_grad_(True) for k, v in c["state"].items()}
+    x = c["x"].double().requires_grad_(True)
+    out = O.unet_expert(P, "", x, c["te"].double(), c["text"].double())
+    assert out.shape == (1, 4, 64, 128) and out.dtype == torch.float64
+    close(out, c["out"].double(), rtol=1e-4, atol=2e-4)
+    out.backward(c["grad_out"].double())
+    close_scaled(x.grad, c["x_grad"].double())
     for n, gref in c["param_grads"].items():
-        close_scaled(P[n].grad, gref)
+        close_scaled(P[n].grad, gref.double())
     c = g["unet_expert_half"]
     close(O.unet_expert(c["state"], "", c["x"], c["te"], c["text"]), c["out_fp32"], rtol=1e-4, atol=1e-4)
     c = g["pos_encoding"]
