@@ -889,8 +889,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_merged_kernel(bf16* dq, bf16*
 }
 
 static inline bool attn_mfma_ok(int H, const void* a, const void* b2, const void* c2, const void* d2) {
-  static const bool off = getenv("HDMOE_ATTN_VALU") != nullptr;
-  return !off && H >= 1 && H <= 4096 && (((uintptr_t)a | (uintptr_t)b2 | (uintptr_t)c2 | (uintptr_t)d2) & 7) == 0;
+  return H >= 1 && H <= 4096 && (((uintptr_t)a | (uintptr_t)b2 | (uintptr_t)c2 | (uintptr_t)d2) & 7) == 0;
 }
 
 static int attn_force_slow() {                                // (tests: the online-maximum sweep of the forward kernel for every block)

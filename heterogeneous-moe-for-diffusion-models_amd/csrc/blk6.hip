@@ -17,7 +17,6 @@
 //
 // Domain: bf16, W in {16, 32}, H a multiple of 256 / W, square odd k in {3, 5, 7} with "same" padding, Ca % 32 == 0, Cm in {32, 64},
 // Cb % 32 == 0.  Everything else returns 1 (the caller runs the layers one by one).
-#include <stdlib.h>
 #include <type_traits>
 #include "common.h"
 #include "conv_args.h"
@@ -38,8 +37,7 @@ constexpr int B6_EB = 256;                    // bytes of LDS behind the weight 
 
 int blk6_plan(const void* x, const void* wa, const void* wb, void* y, const void* res, const int* seg, int ngroups, long wa_stride,
               long wb_stride, int N, int H, int W, int Ca, int Cm, int Cb, const int* ks, B6Plan& plan) {
-  static const bool off = getenv("HDMOE_BLK6") && atoi(getenv("HDMOE_BLK6")) == 0;
-  if (off || !(W == 16 || W == 32) || Ca % 32 || Cb % 32 || !(Cm == 32 || Cm == 64) || ngroups < 1 || ngroups > HDMOE_MAX_GROUPS) return 1;
+  if (!(W == 16 || W == 32) || Ca % 32 || Cb % 32 || !(Cm == 32 || Cm == 64) || ngroups < 1 || ngroups > HDMOE_MAX_GROUPS) return 1;
   int maxk = 0;
   for (int g = 0; g < ngroups; ++g) {
     if (ks[g] != 3 && ks[g] != 5 && ks[g] != 7) return 1;
@@ -59,8 +57,6 @@ int blk6_plan(const void* x, const void* wa, const void* wb, void* y, const void
     for (int k = i; k > 0 && a.ks[a.order[k]] > a.ks[a.order[k - 1]]; --k) { const int t = a.order[k]; a.order[k] = a.order[k - 1]; a.order[k - 1] = t; }
   const int NTM = Cm / 32, NTB = Cb % 64 == 0 ? 2 : 1;
   const int nbmax = 32 * (NTM > NTB ? NTM : NTB);
-  static const int force_t = getenv("HDMOE_B6_T") ? atoi(getenv("HDMOE_B6_T")) : 0;
-  static const int force_nw = getenv("HDMOE_B6_NW") ? atoi(getenv("HDMOE_B6_NW")) : 0;
   // Geometry candidates, best first: 4-wave workgroups, two per CU (<= 80 KB of LDS each, one x buffer, conv A over <= 12 blocks), on
   // the 256-pixel tile or -- 64-channel layers, whose intermediate image is twice as large -- on a 128-pixel tile; else one 8-wave
   // workgroup per CU with two x buffers.
@@ -68,7 +64,6 @@ int blk6_plan(const void* x, const void* wa, const void* wb, void* y, const void
   const Cand cands[3] = {{4, 256 / W}, {8, 256 / W}, {4, 128 / W}};     // (128-pixel tiles measured slower than the 8-wave form: last resort)
   bool found = false;
   for (const Cand& cd : cands) {
-    if ((force_nw == 4 || force_nw == 8) && cd.nw != force_nw) continue;
     const int th = cd.th;
     if (th < 4 || H % th || (th * W) % 32) continue;
     if (cd.nw == 4 && (th * W == 128) && NTM != 2) continue;
@@ -87,7 +82,6 @@ int blk6_plan(const void* x, const void* wa, const void* wb, void* y, const void
       for (int g = 0; g < ngroups; ++g) stages += (ks[g] * ks[g] + t - 1) / t;
       if (stages <= best_stages) { best_stages = stages; best = t; }
     }
-    if (force_t >= 2 && force_t <= 9 && force_t * (nbmax / 16) <= 40 && fixed + 2 * force_t * nbmax * 64 <= cap) best = force_t;
     if (!best) continue;
     a.TH = th; a.tpi = H / th; a.xb_bytes = xb; a.hb_plane = hbp; a.T = best; a.wb_bytes = best * nbmax * 64; a.nxp = xb / 1024 / cd.nw;
     plan.NW = cd.nw;
@@ -99,15 +93,11 @@ int blk6_plan(const void* x, const void* wa, const void* wb, void* y, const void
   auto recip = [](int d) { return d == 1 ? 0xFFFFFFFFu : (unsigned)((1ull << 32) / (unsigned)d + 1); };
   a.m_tpi = recip(a.tpi); a.m_T = recip(a.T);
   const long units = (long)N * a.tpi;
-  static const int gcap_env = getenv("HDMOE_B6_G") ? atoi(getenv("HDMOE_B6_G")) : 0;
-  const long gcap = gcap_env > 0 ? gcap_env : (plan.NW == 4 ? 512 : 256);
+  const long gcap = plan.NW == 4 ? 512 : 256;
   plan.G = (unsigned)(units < gcap ? units : gcap);
   plan.NTM = NTM; plan.NTB = NTB;
   a.stamps = (unsigned long long*)g_b6_stamps;
-  static const int dbg = getenv("HDMOE_B6_DBG") ? atoi(getenv("HDMOE_B6_DBG")) : 0;
-  a.dbg = dbg;
-  static const int desync = getenv("HDMOE_B6_DESYNC") ? atoi(getenv("HDMOE_B6_DESYNC")) : 0;
-  a.desync = desync;
+  a.dbg = 0;
   return 0;
 }
 

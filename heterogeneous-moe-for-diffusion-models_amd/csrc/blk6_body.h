@@ -34,8 +34,8 @@ struct B6Args {
   float* de;                          // mode 1: [N][Cm] += sum over pixels of d(mid)/d(e)
   const unsigned long long* seed_dev; unsigned seed_lo, seed_hi; float p;
   unsigned long long* stamps;         // development: s_memtime stamps of workgroup 0 ([wave][64] slots), or null
-  int dbg;                            // development ablations: 1 no MFMA loops, 2 no DMA inside the loops, 4 no global stores, 8 no middle op
-  int desync;                         // 4-wave variant: how the two workgroups of a CU are kept out of phase (0 off, 1 priority by parity, 2 priority by grid half, 3 / 4: start delay)
+  int dbg;                            // always 0 (blk6_plan).  The tests on it stay: without them the 4-wave variants' register allocation
+                                      // grows past 256 VGPRs and spills to scratch
 };
 
 struct B6Unit { int g, ks, n, ty0, rend; };     // (everything else follows from ks: kept out of the record, scalar registers are scarce here)
@@ -76,14 +76,6 @@ DEVI void blk6_body(const B6Args& a, const int bid, const int G) {
     }
   };
   stamp(1);
-  if (NW == 4) {
-    // Two workgroups share a CU.  Left alone they run in lockstep -- same program, same unit sizes: both in their MFMA stages, then both
-    // in their middle ops -- and nothing overlaps.  A priority difference breaks the tie: the favoured workgroup takes the matrix pipe,
-    // the other one falls half a unit behind and from then on computes while its partner stores, and vice versa.
-    const bool second = (a.desync == 1 || a.desync == 3) ? (bid & 1) : (bid >= (G >> 1));
-    if ((a.desync == 1 || a.desync == 2) && second) __builtin_amdgcn_s_setprio(1);
-    if ((a.desync == 3 || a.desync == 4) && second) { for (int i = 0; i < 64; ++i) __builtin_amdgcn_s_sleep(100); }
-  }
   // ---- unit list (as conv6_body.h): groups in descending kernel size; a unit = one TH x W tile of one routed row
   const int oi_l = lane & 7;
   int v_g = 0, v_ks = 0;

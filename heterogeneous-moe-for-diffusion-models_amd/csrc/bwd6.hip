@@ -5,7 +5,6 @@
 // side by side in one grid about the longer of the two.  A fork onto a second stream inside the graph would also overlap them, but a
 // hipGraph with internal branches no longer runs concurrently with the other branch's graph (measured: the ViT backward graph then
 // waits for the whole U-Net backward graph).
-#include <stdlib.h>
 #include "common.h"
 #include "conv_args.h"
 #include "conv6_common.h"
@@ -47,12 +46,11 @@ __global__ __launch_bounds__(512) void bwd7_kernel(C7Args c, W6Args a3, W6Args a
   if (b < G7) { conv7_body<CO, KMASK, TWS == 4>(c, b, G7); return; }
   int r = b - G7;
   if (TWS == 5 && OT == 0) {                                 // 32 x 32 maps: the streaming weight-gradient programs (output chunks of 32)
-    const int icw = a3.icw > 0 ? a3.icw : 1;
-    const int nbx3 = a3.Cin / (32 * icw), nby3 = a3.Cout / (32 * a3.ocw), n3 = nbx3 * nby3 * a3.chunks;
+    const int nbx3 = a3.Cin / (32 * a3.icw), nby3 = a3.Cout / (32 * a3.ocw), n3 = nbx3 * nby3 * a3.chunks;
     if (r < n3) {                                            // 3x3 class: wgrad8, icw x ocw channel chunks per workgroup
       const int bx = r % nbx3; r /= nbx3;
       const int by = r % nby3, z = r / nby3, pairs = a3.icw * a3.ocw;
-      if (pairs == 0) wgrad7_body<3>(a3, bx, by, z);         // (HDMOE_WGRAD8=0)
+      if (pairs == 0) wgrad7_body<3>(a3, bx, by, z);         // (never taken: icw >= 1; kept because removing it changes the kernel's register allocation)
       else if (pairs == 4) wgrad8_body3<4, 8>(a3, bx, by, z);
       else if (pairs == 2) wgrad8_body3<2, 8>(a3, bx, by, z);
       else wgrad8_body3<2, 16>(a3, bx, by, z);
@@ -61,7 +59,7 @@ __global__ __launch_bounds__(512) void bwd7_kernel(C7Args c, W6Args a3, W6Args a
     r -= n3;
     const int bx = r % ibs; r /= ibs;
     wgrad7_body<5>(a5, bx, r % obs, r / obs);
-  } else if (OT > 0) {
+  } else if (OT > 0) {                                       // 16 x 16 maps: the wgrad6 programs
     const int bx = r % ibs; r /= ibs;
     const int by = r % obs;
     const int z = r / obs;
@@ -77,7 +75,7 @@ void launch_bwd7(const C7Plan& cp, const W6DualPlan& wp, hipStream_t stream) {
   const size_t lds = cp.lds > wp.lds ? cp.lds : wp.lds;
   const int obs = OT == 0 ? wp.c[0].Cout / 32 : wp.obs;      // OT == 0: wgrad7 / wgrad8 (output chunks of 32)
   unsigned nw = (unsigned)(wp.ibs * obs * (wp.c[0].chunks + wp.c[1].chunks));
-  if (OT == 0) nw = (unsigned)((wp.c[0].Cin / (32 * (wp.c[0].icw > 0 ? wp.c[0].icw : 1))) * (wp.c[0].Cout / (32 * wp.c[0].ocw)) * wp.c[0].chunks + wp.ibs * obs * wp.c[1].chunks);
+  if (OT == 0) nw = (unsigned)((wp.c[0].Cin / (32 * wp.c[0].icw)) * (wp.c[0].Cout / (32 * wp.c[0].ocw)) * wp.c[0].chunks + wp.ibs * obs * wp.c[1].chunks);
   hipLaunchKernelGGL((bwd7_kernel<CO, KMASK, TWS, OT>), dim3(cp.G + nw), dim3(512), lds, stream, cp.a, wp.c[0], wp.c[1], (int)cp.G, wp.ibs, obs);
 }
 
@@ -108,8 +106,7 @@ extern "C" {
 int hdmoe_conv_bwd6s(const void* x, const void* dy, const void* wd, void* dx, float* const* G, const int* seg, int ngroups, long wd_stride,
                      long wd_plane, int N, int H, int W, int Cin, int Cout, const int* kh, const int* kw, const int* pt, const int* pl,
                      float alpha, void* ws, long ws_bytes, const float* in_scale, const float* in_shift, int in_relu, int hi_only, hipStream_t stream) {
-  static const bool off = getenv("HDMOE_BWD6") && atoi(getenv("HDMOE_BWD6")) == 0;
-  if (off || !dx || !wd || ngroups < 1 || ngroups > HDMOE_MAX_GROUPS || Cout % 16) return 1;
+  if (!dx || !wd || ngroups < 1 || ngroups > HDMOE_MAX_GROUPS || Cout % 16) return 1;
   W6DualPlan wp;
   if (wgrad6_plan_split(x, dy, G, seg, ngroups, N, H, W, Cin, Cout, kh, kw, pt, pl, ws, ws_bytes, wp)) return 1;
   if ((in_scale == nullptr) != (in_shift == nullptr) || (in_scale && (ngroups != 1 || seg))) return HDMOE_EINVAL;
@@ -138,8 +135,7 @@ int hdmoe_conv_bwd6s(const void* x, const void* dy, const void* wd, void* dx, fl
 int hdmoe_conv_bwd6(const void* x, const void* dy, const void* wd, void* dx, float* const* G, const int* seg, int ngroups, long wd_stride,
                     int N, int H, int W, int Cin, int Cout, const int* kh, const int* kw, const int* pt, const int* pl, float alpha,
                     void* ws, long ws_bytes, int dtype, hipStream_t stream) {
-  static const bool off = getenv("HDMOE_BWD6") && atoi(getenv("HDMOE_BWD6")) == 0;
-  if (off || dtype != HDMOE_BF16 || !dx || !wd || ngroups < 1 || ngroups > HDMOE_MAX_GROUPS || Cout % 16) return 1;
+  if (dtype != HDMOE_BF16 || !dx || !wd || ngroups < 1 || ngroups > HDMOE_MAX_GROUPS || Cout % 16) return 1;
   W6DualPlan wp;
   if (wgrad6_plan_dual(x, dy, G, seg, ngroups, N, H, W, Cin, Cout, kh, kw, pt, pl, ws, ws_bytes, dtype, wp)) return 1;
   ConvArgs c;                                              // the dgrad as a forward conv over dy
@@ -152,11 +148,10 @@ int hdmoe_conv_bwd6(const void* x, const void* dy, const void* wd, void* dx, flo
   }
   {
     C7Plan cp7;                                            // 32 x 32 maps: the streaming kernel as the dgrad program (wgrad6 handles 3x3 / 5x5 only)
-    static const bool w7 = !(getenv("HDMOE_WGRAD7") && atoi(getenv("HDMOE_WGRAD7")) == 0);
     if (!conv7_plan(c, dtype, cp7) && cp7.kmask == 3 && (cp7.w16 != 0) == (wp.TWS == 4)) {
 #define BWD7_GO(Co)                                                                              \
   do {                                                                                           \
-    if (wp.TWS == 5) { if (w7) launch_bwd7<Co, 3, 5, 0>(cp7, wp, stream); else if (wp.OT == 2) launch_bwd7<Co, 3, 5, 2>(cp7, wp, stream); else launch_bwd7<Co, 3, 5, 1>(cp7, wp, stream); } \
+    if (wp.TWS == 5) launch_bwd7<Co, 3, 5, 0>(cp7, wp, stream);                                                               \
     else { if (wp.OT == 2) launch_bwd7<Co, 3, 4, 2>(cp7, wp, stream); else launch_bwd7<Co, 3, 4, 1>(cp7, wp, stream); }            \
   } while (0)
       if (cp7.CO == 2) BWD7_GO(2); else BWD7_GO(1);

@@ -16,7 +16,6 @@
 //   conv_wgrad2_kernel            pixel tile + halo in LDS, taps owned per wave, transposing LDS reads (bf16), one fp32 atomic
 //                                 flush per workgroup into a [tap][O][I] slab (contiguous I: full-rate atomic shape,
 //                                 MI355X_MICROARCH "Global float atomics"); conv_wgrad_kernel for stride > 1
-#include <stdlib.h>
 #include "common.h"
 #include "conv_args.h"
 #include "hdmoe.h"
@@ -1444,16 +1443,13 @@ int hdmoe_conv_wgrad(const void* x, const void* dy, float* const* G, const int* 
         // once.  bf16 units are short and the flush dominates: fewer, longer workgroups measured best (launch_table sweeps).
         long upw;
         if (esz == 4) {
-            static const long f32_parts = getenv("HDMOE_WG_PARTS_F32") ? atol(getenv("HDMOE_WG_PARTS_F32")) : 512;
-            long parts = f32_parts / ((long)ibs * obs); if (parts < 8) parts = 8;
+            long parts = 512 / ((long)ibs * obs); if (parts < 8) parts = 8;
             const long class_units = (units_l * gm.ngr + ngroups - 1) / ngroups;   // assume balanced routing
             upw = (class_units + parts - 1) / parts;
         } else {
-            static const long bf16_parts = getenv("HDMOE_WG_PARTS") ? atol(getenv("HDMOE_WG_PARTS")) : 384;
             // classes with more than 9 taps flush (taps x 64 x 32) floats per workgroup: fewer, longer workgroups (bench sweep:
             // 384 -> 256 partitions = -0.7 ms/step at B = 256)
-            static const long bf16_parts_big = getenv("HDMOE_WG_PARTS_BIG") ? atol(getenv("HDMOE_WG_PARTS_BIG")) : 256;
-            long parts = (taps > 9 ? bf16_parts_big : bf16_parts) / ((long)ibs * obs); if (parts < 8) parts = 8;
+            long parts = (taps > 9 ? 256 : 384) / ((long)ibs * obs); if (parts < 8) parts = 8;
             upw = (units_l + parts - 1) / parts;
         }
         if (upw < 1) upw = 1;

@@ -14,7 +14,6 @@
 //   * MFMA 32x32x16 bf16 with A = weights, B = pixels: an accumulator lane owns one pixel and 4 consecutive channels per register
 //     quad; the epilogue pairs quads across the two half-waves with v_permlane32_swap (T21) and stores 16 bytes per lane.
 // Domain (everything else stays on conv.hip): stride 1, square k in {3,5,7}, Cin % 32 == 0, Cout % 32 == 0, W == 16 or W % 32 == 0.
-#include <stdlib.h>
 #include "conv_args.h"
 #include "conv6_common.h"
 #include "hdmoe.h"
@@ -36,8 +35,6 @@ void* hdmoe_debug_stamp_buffer() { return g_c6_stamps; }      // (shared with co
 
 // Launch geometry of conv6 for one layer (shared with the fused backward launch of bwd6.hip).  0 = planned, 1 = outside the domain.
 int conv6_plan(const ConvArgs& c, int dtype, C6Plan& plan) {
-  static const bool off = getenv("HDMOE_CONV6") && atoi(getenv("HDMOE_CONV6")) == 0;
-  if (off) return 1;
   if (dtype != HDMOE_BF16 || c.stride != 1 || c.ones || c.Cphys != c.Cin || c.Ipad != c.Cin || c.Cin % 32 || c.Cout % 32 || c.Cstore != c.Cout) return 1;
   if (c.Ho != c.H || c.Wo != c.W || !(c.W == 16 || c.W % 32 == 0) || c.H < 8) return 1;
   int maxk = 0, mink = 99;
@@ -56,9 +53,7 @@ int conv6_plan(const ConvArgs& c, int dtype, C6Plan& plan) {
   a.x = c.x; a.w = c.w; a.y = c.y; a.res = c.res; a.seg = c.seg; a.wstride = c.wstride;
   a.N = c.N; a.H = c.H; a.W = c.W; a.Cin = c.Cin; a.Cout = c.Cout; a.ngroups = c.ngroups; a.alpha = c.alpha; a.beta = c.beta;
   a.xbytes = (int)xbytes; a.wbytes = (int)wbytes;
-  static const int dbg = getenv("HDMOE_C6_DBG") ? atoi(getenv("HDMOE_C6_DBG")) : 0;
-  a.dbg = dbg;
-  a.stamps = (unsigned long long*)g_c6_stamps;
+  a.dbg = 0; a.stamps = (unsigned long long*)g_c6_stamps;
   a.w_rowpitch = c.Cin; a.w_tapstride = c.Cout * c.Cin; a.gbias = nullptr;
   a.film_e = nullptr; a.film_h = nullptr; a.film_seed_dev = nullptr; a.film_seed_lo = 0; a.film_seed_hi = 0; a.film_p = 0.f;
   for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) { a.ks[g] = c.kh[g]; a.pt[g] = c.pt[g]; a.pl[g] = c.pl[g]; a.order[g] = g; }
@@ -72,14 +67,8 @@ int conv6_plan(const ConvArgs& c, int dtype, C6Plan& plan) {
   const int ppt = ((a.TH + maxk - 1) * (a.TW + maxk - 1) + 15) / 16;
   if (ppt > 34) return 1;
   const long tiles = (long)c.N * a.tpi;
-  static const int force_mt = getenv("HDMOE_C6_MT") ? atoi(getenv("HDMOE_C6_MT")) : 0;
-  static const int force_t = getenv("HDMOE_C6_T") ? atoi(getenv("HDMOE_C6_T")) : 0;
-  static const int wg2_env = getenv("HDMOE_C6_WG2") ? atoi(getenv("HDMOE_C6_WG2")) : 0;
-  const bool wg2 = wg2_env && NT == 1;                       // two co-resident workgroups per CU (<1,1> needs 105 VGPRs: 4 waves / SIMD fit)
-  const int LDS_CAP = wg2 ? 80 * 1024 : 160 * 1024;
+  const int LDS_CAP = 160 * 1024;
   int MT = (tiles * a.nblk >= 4 * 256) ? 2 : 1;             // 512-pixel units only when every CU still gets >= 2 of them
-  if (wg2) MT = 1;
-  if (force_mt) MT = force_mt;
   int T = 0;
   for (; MT >= 1; --MT) {
     a.hb_bytes = C6_NW * ((MT * ppt + C6_NW - 1) / C6_NW) * 1024;   // every wave owns the same number of 1-KB pieces
@@ -94,7 +83,6 @@ int conv6_plan(const ConvArgs& c, int dtype, C6Plan& plan) {
     if (best) { T = best; break; }
   }
   if (!T) return 1;
-  if (force_t) T = force_t;
   a.T = T; a.wb_bytes = T * NB * 64;
   auto recip = [](int d) { return (unsigned)((1ull << 32) / (unsigned)d + 1); };
   a.m_nblk = a.nblk == 1 ? 0xFFFFFFFFu : recip(a.nblk); a.m_T = recip(T); a.m_tpi = a.tpi == 1 ? 0xFFFFFFFFu : recip(a.tpi);
@@ -103,8 +91,7 @@ int conv6_plan(const ConvArgs& c, int dtype, C6Plan& plan) {
   if (lds > (size_t)LDS_CAP || T * (NB / 16) > 40) return 1;
   long ub = (tiles + MT - 1) / MT + c.ngroups;
   ub *= a.nblk;
-  static const long gcap_env = getenv("HDMOE_C6_G") ? atol(getenv("HDMOE_C6_G")) : 0;       // (A/B aid: fewer persistent workgroups leave CUs to the other branches)
-  const long gcap = wg2 ? 512 : (gcap_env > 0 ? gcap_env : 256);
+  const long gcap = 256;
   plan.G = (unsigned)(ub < gcap ? ub : gcap);
   plan.MT = MT; plan.NT = NT; plan.lds = lds;
   return 0;

@@ -207,7 +207,6 @@ DEVI void conv6_body(const C6Args& a, const int bid, const int G) {
         hmode = 2; nh = hpieces(nu.ppt);
         stamp(6);
       }
-      if (a.dbg & 2) nh = 0;
       const int hbn = HB0 + (par ^ 1) * a.hb_bytes;
       int ky = 0, kx = 0;                                           // tap cursor, carried across the chunk's stages
       for (int tg = 0; tg < cur.ntg; ++tg) {
@@ -223,7 +222,6 @@ DEVI void conv6_body(const C6Args& a, const int bid, const int G) {
         if (tg + 1 < cur.ntg) { nsb = stage_base(wbase_cur, c, t0 + a.T); nwp = wpieces(min(a.T, cur.ntaps - t0 - a.T)); }
         else if (!last_chunk) { nsb = stage_base(wbase_cur, c + 1, 0); nwp = wpieces(min(a.T, cur.ntaps)); }
         else if (has_next) { nsb = stage_base(wbase_nxt, 0, 0); nwp = wpieces(min(a.T, nu.ntaps)); }
-        if (a.dbg & 2) nwp = 0;
         const int nhs = tg == 0 ? nh : 0;                           // halo pieces ride on the chunk's first stage
         // per-tap side work (k compile-time): weight piece k of the next stage, halo piece k of the next chunk / unit
         auto side = [&](int k) {
@@ -283,101 +281,94 @@ DEVI void conv6_body(const C6Args& a, const int bid, const int G) {
 #pragma unroll
           for (int q = 0; q < SPT; ++q) side(SPT * tl + q);
         };
-        if (!(a.dbg & 1)) {
-          load_tap(fxa, fwa, 0);
+        load_tap(fxa, fwa, 0);
 #pragma unroll
-          for (int tl = 0; tl < C6_MAXT; ++tl) {                    // fully unrolled: tl (and with it every DMA / plan index) is static
-            if (tl < ntl) {
-              if (tl & 1) step(fxb, fwb, fxa, fwa, tl); else step(fxa, fwa, fxb, fwb, tl);
-            } else {
+        for (int tl = 0; tl < C6_MAXT; ++tl) {                    // fully unrolled: tl (and with it every DMA / plan index) is static
+          if (tl < ntl) {
+            if (tl & 1) step(fxb, fwb, fxa, fwa, tl); else step(fxa, fwa, fxb, fwb, tl);
+          } else {
 #pragma unroll
-              for (int q = 0; q < SPT; ++q) side(SPT * tl + q);     // side work left over when the stage has fewer taps than pieces
-            }
+            for (int q = 0; q < SPT; ++q) side(SPT * tl + q);     // side work left over when the stage has fewer taps than pieces
           }
-          // undo the cursor's run-ahead (load_tap advanced it once more than there were taps)
-          if (kx == 0) { kx = cur.ks - 1; --ky; } else --kx;
-        } else {
-#pragma unroll
-          for (int k = 0; k < SPT * C6_MAXT; ++k) side(k);
         }
+        // undo the cursor's run-ahead (load_tap advanced it once more than there were taps)
+        if (kx == 0) { kx = cur.ks - 1; --ky; } else --kx;
         sp ^= 1;
       }
       par ^= 1;
     }
     // ---- epilogue: y = alpha * acc + beta * res, 16-byte stores (two register quads paired across the half-waves)
     stamp(10);
-    if (!(a.dbg & 4)) {
-      bf16* Y = (bf16*)a.y;
-      const bf16* R = (const bf16*)a.res;
-      const int n = (MT == 2 && tile_w) ? cur.n[MT - 1] : cur.n[0];
-      const int ty0 = (MT == 2 && tile_w) ? cur.ty0[MT - 1] : cur.ty0[0];
-      const int tx0 = (MT == 2 && tile_w) ? cur.tx0[MT - 1] : cur.tx0[0];
-      const bool tv = (MT == 2 && tile_w) ? cur.valid[MT - 1] : cur.valid[0];
+    bf16* Y = (bf16*)a.y;
+    const bf16* R = (const bf16*)a.res;
+    const int n = (MT == 2 && tile_w) ? cur.n[MT - 1] : cur.n[0];
+    const int ty0 = (MT == 2 && tile_w) ? cur.ty0[MT - 1] : cur.ty0[0];
+    const int tx0 = (MT == 2 && tile_w) ? cur.tx0[MT - 1] : cur.tx0[0];
+    const bool tv = (MT == 2 && tile_w) ? cur.valid[MT - 1] : cur.valid[0];
 #pragma unroll
-      for (int m = 0; m < MB; ++m) {
-        const int q = ((mb0 + m) & 7) * 32 + r;
-        const int yy = ty0 + (q >> a.tws), xx = tx0 + (q & (a.TW - 1));
-        const bool ok = tv && yy < a.H && xx < a.W;
-        const long pix = (((long)n * a.H + yy) * a.W + xx) * a.Cout + cur.nbk * NB;
+    for (int m = 0; m < MB; ++m) {
+      const int q = ((mb0 + m) & 7) * 32 + r;
+      const int yy = ty0 + (q >> a.tws), xx = tx0 + (q & (a.TW - 1));
+      const bool ok = tv && yy < a.H && xx < a.W;
+      const long pix = (((long)n * a.H + yy) * a.W + xx) * a.Cout + cur.nbk * NB;
 #pragma unroll
-        for (int b = 0; b < NT; ++b)
+      for (int b = 0; b < NT; ++b)
 #pragma unroll
-          for (int p = 0; p < 2; ++p) {
-            // quads 2p (channels 16p + 4h ..) and 2p+1 (channels 16p + 8 + 4h ..) of this lane
-            float v[8];
-            if (a.gbias && ok) {                                    // per-expert bias map (the folded ones channel), inside the alpha scale
-              const float* gb = a.gbias + (((long)cur.g * a.H + yy) * a.W + xx) * a.Cout + cur.nbk * NB + 32 * b + 16 * p + 4 * h;
-              const float4 g0 = *reinterpret_cast<const float4*>(gb), g1 = *reinterpret_cast<const float4*>(gb + 8);
-              v[0] = a.alpha * (acc[m][b][8 * p] + g0.x); v[1] = a.alpha * (acc[m][b][8 * p + 1] + g0.y);
-              v[2] = a.alpha * (acc[m][b][8 * p + 2] + g0.z); v[3] = a.alpha * (acc[m][b][8 * p + 3] + g0.w);
-              v[4] = a.alpha * (acc[m][b][8 * p + 4] + g1.x); v[5] = a.alpha * (acc[m][b][8 * p + 5] + g1.y);
-              v[6] = a.alpha * (acc[m][b][8 * p + 6] + g1.z); v[7] = a.alpha * (acc[m][b][8 * p + 7] + g1.w);
-            } else {
+        for (int p = 0; p < 2; ++p) {
+          // quads 2p (channels 16p + 4h ..) and 2p+1 (channels 16p + 8 + 4h ..) of this lane
+          float v[8];
+          if (a.gbias && ok) {                                    // per-expert bias map (the folded ones channel), inside the alpha scale
+            const float* gb = a.gbias + (((long)cur.g * a.H + yy) * a.W + xx) * a.Cout + cur.nbk * NB + 32 * b + 16 * p + 4 * h;
+            const float4 g0 = *reinterpret_cast<const float4*>(gb), g1 = *reinterpret_cast<const float4*>(gb + 8);
+            v[0] = a.alpha * (acc[m][b][8 * p] + g0.x); v[1] = a.alpha * (acc[m][b][8 * p + 1] + g0.y);
+            v[2] = a.alpha * (acc[m][b][8 * p + 2] + g0.z); v[3] = a.alpha * (acc[m][b][8 * p + 3] + g0.w);
+            v[4] = a.alpha * (acc[m][b][8 * p + 4] + g1.x); v[5] = a.alpha * (acc[m][b][8 * p + 5] + g1.y);
+            v[6] = a.alpha * (acc[m][b][8 * p + 6] + g1.z); v[7] = a.alpha * (acc[m][b][8 * p + 7] + g1.w);
+          } else {
 #pragma unroll
-              for (int e = 0; e < 8; ++e) v[e] = a.alpha * acc[m][b][8 * p + e];
-            }
-            if (R && ok) {                                          // residual added in fp32, before the one rounding to bf16
-              const long o0 = pix + 32 * b + 16 * p + 4 * h;
-              const bf16x4 r0 = *reinterpret_cast<const bf16x4*>(R + o0);
-              const bf16x4 r1 = *reinterpret_cast<const bf16x4*>(R + o0 + 8);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) { v[e] += a.beta * (float)r0[e]; v[4 + e] += a.beta * (float)r1[e]; }
-            }
-            typedef __attribute__((ext_vector_type(2))) __bf16 bf2;
-            typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-            const unsigned A0 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[0], (bf16)v[1]}), A1 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[2], (bf16)v[3]});
-            const unsigned B0 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[4], (bf16)v[5]}), B1 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[6], (bf16)v[7]});
-            // after the swap the lower half-wave holds channels 16p .. 16p+7 of its pixel, the upper half 16p+8 .. 16p+15
-            const u32x2 s0 = __builtin_amdgcn_permlane32_swap(A0, B0, false, false);
-            const u32x2 s1 = __builtin_amdgcn_permlane32_swap(A1, B1, false, false);
-            if (ok) *reinterpret_cast<uint4*>(Y + pix + 32 * b + 16 * p + 8 * h) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
-            if (FILM && a.film_e && ok) {
-              // FiLM + mp_silu + dropout of the 8 channels this lane just stored (from the bf16-ROUNDED values, as the separate pass reads them)
-              const long eo = pix + 32 * b + 16 * p + 8 * h;                  // element index of the first of the 8 channels
-              const int c0 = cur.nbk * NB + 32 * b + 16 * p + 8 * h;
-              const unsigned pk[4] = {s0[0], s1[0], s0[1], s1[1]};
-              uint32_t r4[8];
-              if (a.film_p > 0.f) {
-                const long q0 = eo >> 2;
-                philox((uint32_t)q0, (uint32_t)(q0 >> 32), film_lo, film_hi, r4);
-                philox((uint32_t)(q0 + 1), (uint32_t)((q0 + 1) >> 32), film_lo, film_hi, r4 + 4);
-              }
-              unsigned ho[4];
-#pragma unroll
-              for (int j2 = 0; j2 < 4; ++j2) {
-                const bf2 yv = __builtin_bit_cast(bf2, pk[j2]);
-                float f0 = mp_silu_f((float)yv[0] * a.film_e[(long)n * a.Cout + c0 + 2 * j2]);
-                float f1 = mp_silu_f((float)yv[1] * a.film_e[(long)n * a.Cout + c0 + 2 * j2 + 1]);
-                if (a.film_p > 0.f) {
-                  f0 = u01(r4[2 * j2]) >= a.film_p ? f0 * film_inv : 0.f;
-                  f1 = u01(r4[2 * j2 + 1]) >= a.film_p ? f1 * film_inv : 0.f;
-                }
-                ho[j2] = __builtin_bit_cast(unsigned, (bf2){(bf16)f0, (bf16)f1});
-              }
-              *reinterpret_cast<uint4*>(reinterpret_cast<bf16*>(a.film_h) + eo) = make_uint4(ho[0], ho[1], ho[2], ho[3]);
-            }
+            for (int e = 0; e < 8; ++e) v[e] = a.alpha * acc[m][b][8 * p + e];
           }
-      }
+          if (R && ok) {                                          // residual added in fp32, before the one rounding to bf16
+            const long o0 = pix + 32 * b + 16 * p + 4 * h;
+            const bf16x4 r0 = *reinterpret_cast<const bf16x4*>(R + o0);
+            const bf16x4 r1 = *reinterpret_cast<const bf16x4*>(R + o0 + 8);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { v[e] += a.beta * (float)r0[e]; v[4 + e] += a.beta * (float)r1[e]; }
+          }
+          typedef __attribute__((ext_vector_type(2))) __bf16 bf2;
+          typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
+          const unsigned A0 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[0], (bf16)v[1]}), A1 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[2], (bf16)v[3]});
+          const unsigned B0 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[4], (bf16)v[5]}), B1 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[6], (bf16)v[7]});
+          // after the swap the lower half-wave holds channels 16p .. 16p+7 of its pixel, the upper half 16p+8 .. 16p+15
+          const u32x2 s0 = __builtin_amdgcn_permlane32_swap(A0, B0, false, false);
+          const u32x2 s1 = __builtin_amdgcn_permlane32_swap(A1, B1, false, false);
+          if (ok) *reinterpret_cast<uint4*>(Y + pix + 32 * b + 16 * p + 8 * h) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+          if (FILM && a.film_e && ok) {
+            // FiLM + mp_silu + dropout of the 8 channels this lane just stored (from the bf16-ROUNDED values, as the separate pass reads them)
+            const long eo = pix + 32 * b + 16 * p + 8 * h;                  // element index of the first of the 8 channels
+            const int c0 = cur.nbk * NB + 32 * b + 16 * p + 8 * h;
+            const unsigned pk[4] = {s0[0], s1[0], s0[1], s1[1]};
+            uint32_t r4[8];
+            if (a.film_p > 0.f) {
+              const long q0 = eo >> 2;
+              philox((uint32_t)q0, (uint32_t)(q0 >> 32), film_lo, film_hi, r4);
+              philox((uint32_t)(q0 + 1), (uint32_t)((q0 + 1) >> 32), film_lo, film_hi, r4 + 4);
+            }
+            unsigned ho[4];
+#pragma unroll
+            for (int j2 = 0; j2 < 4; ++j2) {
+              const bf2 yv = __builtin_bit_cast(bf2, pk[j2]);
+              float f0 = mp_silu_f((float)yv[0] * a.film_e[(long)n * a.Cout + c0 + 2 * j2]);
+              float f1 = mp_silu_f((float)yv[1] * a.film_e[(long)n * a.Cout + c0 + 2 * j2 + 1]);
+              if (a.film_p > 0.f) {
+                f0 = u01(r4[2 * j2]) >= a.film_p ? f0 * film_inv : 0.f;
+                f1 = u01(r4[2 * j2 + 1]) >= a.film_p ? f1 * film_inv : 0.f;
+              }
+              ho[j2] = __builtin_bit_cast(unsigned, (bf2){(bf16)f0, (bf16)f1});
+            }
+            *reinterpret_cast<uint4*>(reinterpret_cast<bf16*>(a.film_h) + eo) = make_uint4(ho[0], ho[1], ho[2], ho[3]);
+          }
+        }
     }
     stamp(11);
     if (!has_next) break;

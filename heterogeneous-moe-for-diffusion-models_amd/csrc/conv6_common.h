@@ -23,7 +23,7 @@ struct C6Args {
                                       // larger values read a [tap][rows][pitch] image with more channels / rows than this conv uses
                                       // (the ones-channel layer of Unet_expert: hdmoe_conv6_ones_fwd / _bwd)
   const float* gbias;                 // optional fp32 [group][H][W][Cout]: y = alpha * (acc + gbias[g][yy][xx][:]) + beta * res
-  int dbg;                            // development ablations: 1 skip the MFMA loop, 2 skip the in-loop DMA, 4 skip the stores
+  int dbg;                            // always 0.  conv6s_body.h keeps its tests on it: without them the split kernel needs one VGPR more
   unsigned long long* stamps;         // development: s_memtime stamps of workgroup 0 ([wave][64] slots), or null
   // fused FiLM epilogue (Unet_block, reference model_components.py:242-246): besides y the kernel writes
   // film_h = dropout_p(mp_silu(y * film_e[n][c])) -- the same arithmetic and the same Philox bits as film_silu_fwd_vec_kernel

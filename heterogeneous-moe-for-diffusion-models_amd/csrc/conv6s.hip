@@ -16,7 +16,6 @@
 //   * fp32 epilogue (16-byte stores straight from the accumulator quads), optionally accumulating per-sample sum / sum of squares
 //     for the GroupNorm that follows.
 // Domain: 3x3 kernels, stride 1, Cin % 32 == 0, Cout % 32 == 0, W == 16 or W % 32 == 0 (the trunk and its dgrad); else conv.hip.
-#include <stdlib.h>
 #include "conv_args.h"
 #include "conv6_common.h"
 #include "hdmoe.h"
@@ -24,17 +23,15 @@
 
 namespace {
 
-template <int NT, bool P3>
-__global__ __launch_bounds__(64 * C6_NW) void conv6_split_kernel(C6SArgs sa) {
-  conv6s_body<NT, P3>(sa, blockIdx.x, gridDim.x);
+template <int NT>
+__global__ __launch_bounds__(64 * C6_NW) void conv6_split_kernel(C6SArgs sa) {   // the stand-alone forward: always the P3 plan
+  conv6s_body<NT, true>(sa, blockIdx.x, gridDim.x);
 }
 
 }  // namespace
 
 // x, y (and res) fp32; w = bf16 [hi | lo][g][tap][Cout][Cin] with `wplane_elems` elements between the two planes
 int conv6s_plan(const ConvArgs& c, long wplane_elems, const ConvFuse* fuse, C6SPlan& plan, bool p3) {
-  static const bool off = getenv("HDMOE_CONV6") && atoi(getenv("HDMOE_CONV6")) == 0;
-  if (off) return 1;
   if (c.stride != 1 || c.ones || c.Cphys != c.Cin || c.Ipad != c.Cin || c.Cin % 32 || c.Cout % 32 || c.Cstore != c.Cout) return 1;
   if (c.Ho != c.H || c.Wo != c.W || !(c.W == 16 || c.W % 32 == 0) || c.H < 8) return 1;
   for (int g = 0; g < c.ngroups; ++g) if (c.kh[g] != 3 || c.kw[g] != 3) return 1;
@@ -46,8 +43,7 @@ int conv6s_plan(const ConvArgs& c, long wplane_elems, const ConvFuse* fuse, C6SP
   C6Args& a = sa.c;
   a.x = c.x; a.w = c.w; a.y = c.y; a.res = c.res; a.seg = c.seg; a.wstride = c.wstride;
   a.N = c.N; a.H = c.H; a.W = c.W; a.Cin = c.Cin; a.Cout = c.Cout; a.ngroups = c.ngroups; a.alpha = c.alpha; a.beta = c.beta;
-  static const int dbg = getenv("HDMOE_C6S_DBG") ? atoi(getenv("HDMOE_C6S_DBG")) : 0;   // development ablations (conv6s_body.h): 1 no MFMA, 2 no in-loop DMA, 4 no stores, 8 no halo conversion
-  a.xbytes = (int)xbytes; a.wbytes = (int)wbytes; a.dbg = dbg; a.stamps = nullptr;
+  a.xbytes = (int)xbytes; a.wbytes = (int)wbytes; a.dbg = 0; a.stamps = nullptr;
   for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) { a.ks[g] = c.kh[g]; a.pt[g] = c.pt[g]; a.pl[g] = c.pl[g]; a.order[g] = g; }
   a.TW = c.W >= 32 ? 32 : 16; a.tws = a.TW == 32 ? 5 : 4; a.TH = 256 / a.TW;
   a.tiles_x = c.W / a.TW;
@@ -74,40 +70,29 @@ int conv6s_plan(const ConvArgs& c, long wplane_elems, const ConvFuse* fuse, C6SP
   sa.in_scale = fuse ? fuse->in_scale : nullptr; sa.in_shift = fuse ? fuse->in_shift : nullptr; sa.in_relu = fuse ? fuse->in_relu : 0;
   sa.stats = fuse ? fuse->stats : nullptr;
   sa.nprod = 3;
-  {
-    static const bool drain = getenv("HDMOE_C6S_COUNTED") && atoi(getenv("HDMOE_C6S_COUNTED")) == 0;   // 0: plain stores, full drain (A/B)
-    const long yb = (long)c.N * c.H * c.W * c.Cout * 4;
-    a.ybytes = (yb < (1l << 32) && !drain) ? (unsigned)yb : 0u;
-  }
+  const long ybytes = (long)c.N * c.H * c.W * c.Cout * 4;
+  a.ybytes = ybytes < (1l << 32) ? (unsigned)ybytes : 0u;
   const size_t lds = 2 * (size_t)a.hb_bytes + 2 * (size_t)a.wb_bytes + tab_bytes;
   const long tiles = (long)c.N * a.tpi;
   long ub = ((tiles + 1) / 2 + c.ngroups) * a.nblk;
   // 224, not 256, persistent workgroups: one of these takes a CU's whole register file, so on a full grid NOTHING of the other branches
   // can start until it ends; leaving 32 CUs free lets their small kernels through (16.17 -> 16.00 ms/step, three same-box pairs;
   // 192 / 208: 16.04 / 16.08, 128: 16.27)
-  static const long gcap = getenv("HDMOE_C6S_G") ? atol(getenv("HDMOE_C6S_G")) : 224;
+  const long gcap = 224;
   plan.G = (unsigned)(ub < gcap ? ub : gcap);
   plan.NT = NT; plan.lds = lds;
   return 0;
 }
 
 int conv6_split_try_launch(const ConvArgs& c, long wplane_elems, const ConvFuse* fuse, hipStream_t stream) {
-  static const bool p3 = !(getenv("HDMOE_C6S_P3") && atoi(getenv("HDMOE_C6S_P3")) == 0);   // 0: the three products as separate passes (A/B)
   C6SPlan plan;
-  if (conv6s_plan(c, wplane_elems, fuse, plan, p3)) return 1;
+  if (conv6s_plan(c, wplane_elems, fuse, plan, true)) return 1;
   static unsigned long long attr_set = 0;
   if (hdmoe_first_on_device(attr_set)) {
-    (void)hipFuncSetAttribute((const void*)conv6_split_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv6_split_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv6_split_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)conv6_split_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)conv6_split_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)conv6_split_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   }
-  if (p3) {
-    if (plan.NT == 2) hipLaunchKernelGGL((conv6_split_kernel<2, true>), dim3(plan.G), dim3(64 * C6_NW), plan.lds, stream, plan.sa);
-    else hipLaunchKernelGGL((conv6_split_kernel<1, true>), dim3(plan.G), dim3(64 * C6_NW), plan.lds, stream, plan.sa);
-  } else {
-    if (plan.NT == 2) hipLaunchKernelGGL((conv6_split_kernel<2, false>), dim3(plan.G), dim3(64 * C6_NW), plan.lds, stream, plan.sa);
-    else hipLaunchKernelGGL((conv6_split_kernel<1, false>), dim3(plan.G), dim3(64 * C6_NW), plan.lds, stream, plan.sa);
-  }
+  if (plan.NT == 2) hipLaunchKernelGGL((conv6_split_kernel<2>), dim3(plan.G), dim3(64 * C6_NW), plan.lds, stream, plan.sa);
+  else hipLaunchKernelGGL((conv6_split_kernel<1>), dim3(plan.G), dim3(64 * C6_NW), plan.lds, stream, plan.sa);
   return hdmoe_launch_status();
 }

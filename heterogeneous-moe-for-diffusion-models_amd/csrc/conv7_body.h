@@ -32,7 +32,8 @@ struct C7Args {
   int ks[HDMOE_MAX_GROUPS], order[HDMOE_MAX_GROUPS];   // kernel size per group; groups in descending kernel size
   float alpha, beta;
   int xbytes, wbytes;
-  int dbg;                             // development ablations: 1 skip the MFMAs, 2 skip the tile DMA of later units, 4 skip the stores
+  int dbg;                             // always 0 (conv7_plan).  The tests on it stay: they split the MFMA loop, the interleave hints and the
+                                       // epilogue into separate blocks, and without them the compiler schedules conv7 differently (more VGPRs)
   unsigned long long* stamps;          // development: s_memtime stamps of workgroup 0 ([wave][64] slots; hdmoe_conv6_debug_stamps), or null
 };
 

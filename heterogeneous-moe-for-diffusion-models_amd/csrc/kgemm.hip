@@ -6,7 +6,6 @@
 // LDS): a workgroup owns 32 rows, its eight waves split K in 64-element chunks (a lane reads 64 contiguous bytes of its row per
 // chunk = four k-steps; the k <-> MFMA-slot assignment is arbitrary as long as both operands use the same one), and the partial
 // sums meet in LDS in a fixed order (deterministic forward).
-#include <stdlib.h>
 #include "common.h"
 #include "conv_args.h"
 #include "hdmoe.h"
@@ -78,9 +77,8 @@ __global__ __launch_bounds__(512) void kgemm_kernel(KArgs a) {
 
 // Returns HDMOE_OK after launching, a negative status on a launch error, or 1 when the layer is outside this file's domain.
 int kgemm_try_launch(const ConvArgs& a, int dtype, hipStream_t stream) {
-  static const bool off = getenv("HDMOE_KGEMM") && atoi(getenv("HDMOE_KGEMM")) == 0;
-  if (off || dtype != HDMOE_BF16 || a.ngroups != 1 || a.seg || a.stride != 1 || a.ones || a.kh[0] != 1 || a.kw[0] != 1 || a.pt[0] || a.pl[0]) return 1;
-  static const int mink = getenv("HDMOE_KGEMM_MINK") ? atoi(getenv("HDMOE_KGEMM_MINK")) : 512;   // (768: the text projections of the fusion cross-attention, 37 + 31 -> ~2 x 12 us on the serial stage; same-box step -0.1 ms)
+  if (dtype != HDMOE_BF16 || a.ngroups != 1 || a.seg || a.stride != 1 || a.ones || a.kh[0] != 1 || a.kw[0] != 1 || a.pt[0] || a.pl[0]) return 1;
+  constexpr int mink = 512;   // (768: the text projections of the fusion cross-attention, 37 + 31 -> ~2 x 12 us on the serial stage; same-box step -0.1 ms)
   if (a.Cin != a.Cphys || a.Ipad != a.Cin || a.Cin % 64 || a.Cin < mink || a.Cout != a.Cstore || a.Cout % 32 || a.Cout > 64) return 1;
   if (a.Ho != a.H || a.Wo != a.W || (((uintptr_t)a.x | (uintptr_t)a.w) & 15)) return 1;
   KArgs k;

@@ -11,7 +11,6 @@
 // The four waves of a workgroup split the workgroup's slice range, add their accumulators through LDS and flush one [32*OT][32*IT]
 // tile with float atomics (the slab is shared with the other position partitions, as in conv_wgrad2).
 // Domain: Cin % 32 == 0, Cout % 32 == 0, no constant-one input channel; everything else stays with conv.hip.
-#include <stdlib.h>
 #include "common.h"
 #include "conv_args.h"
 #include "hdmoe.h"
@@ -380,8 +379,7 @@ __global__ __launch_bounds__(256) void towg_bf16_kernel(TowgArgs a) {
 // k x k bf16 weight gradient for Cout <= 4 (k = 1 or 3, one expert, stride 1, "same" geometry): G [tap][Cout][Cin] += .  Same return convention.
 int towg_try_launch(const void* x, const void* dy, float* G, int N, int H, int W, int Cin, int Cout, int k, int pt, int pl, int dtype,
                     hipStream_t stream) {
-  static const bool off = getenv("HDMOE_TOWG") && atoi(getenv("HDMOE_TOWG")) == 0;
-  if (off || dtype != HDMOE_BF16 || Cout < 1 || Cout > 4 || Cin % 32 || (k != 1 && k != 3) || pt != (k - 1) / 2 || pl != (k - 1) / 2) return 1;
+  if (dtype != HDMOE_BF16 || Cout < 1 || Cout > 4 || Cin % 32 || (k != 1 && k != 3) || pt != (k - 1) / 2 || pl != (k - 1) / 2) return 1;
   if (!x || !dy || !G || ((uintptr_t)x & 3)) return 1;
   TowgArgs a;
   a.x = (const bf16*)x; a.dy = (const bf16*)dy; a.G = G; a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.pad = (k - 1) / 2;
@@ -413,8 +411,7 @@ int towg_try_launch(const void* x, const void* dy, float* G, int N, int H, int W
 // k x k fp32 layer with taps * Cin <= 64 (one expert, stride 1, "same" geometry): G [tap][Cout][Cin] += .  Same return convention.
 int swg_try_launch(const void* x, const void* dy, float* G, int N, int H, int W, int Cin, int Cout, int k, int pt, int pl, int dtype,
                    hipStream_t stream) {
-  static const bool off = getenv("HDMOE_SWG") && atoi(getenv("HDMOE_SWG")) == 0;
-  if (off || dtype != HDMOE_F32 || Cout % 32 || k * k * Cin > 64 || !x || !dy || !G || (long)N * H * W >= (1l << 31)) return 1;
+  if (dtype != HDMOE_F32 || Cout % 32 || k * k * Cin > 64 || !x || !dy || !G || (long)N * H * W >= (1l << 31)) return 1;
   SwgArgs a;
   a.x = (const float*)x; a.dy = (const float*)dy; a.G = G; a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.k = k; a.pt = pt; a.pl = pl;
   const long total = (long)N * H * W;
@@ -431,8 +428,7 @@ int swg_try_launch(const void* x, const void* dy, float* G, int N, int H, int W,
 // Returns HDMOE_OK after launching, a negative status on a launch error, or 1 when the layer is outside this file's domain.
 int lwg_try_launch(const void* x, const void* dy, float* const* G, const int* seg, int ngroups, int N, long HW, int Cin, int Cout,
                    int dtype, hipStream_t stream) {
-  static const bool off = getenv("HDMOE_LWG") && atoi(getenv("HDMOE_LWG")) == 0;
-  if (off || Cin % 32 || Cout % 32 || (dtype != HDMOE_BF16 && dtype != HDMOE_F32)) return 1;
+  if (Cin % 32 || Cout % 32 || (dtype != HDMOE_BF16 && dtype != HDMOE_F32)) return 1;
   if (((uintptr_t)x | (uintptr_t)dy) & 15) return 1;
   LwgArgs a;
   a.x = x; a.dy = dy; a.seg = seg; a.ngroups = ngroups; a.N = N; a.HW = HW; a.I = Cin; a.O = Cout;

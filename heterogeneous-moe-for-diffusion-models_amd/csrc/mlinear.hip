@@ -7,7 +7,6 @@
 //   dx[r][i]   = sum_l sum_o dy_l[r][o] * W_l,g(r)[o][i]     (also the sum over the layers that autograd would do with L - 1 adds)
 //   dW_l,g[o][i] += sum_{r in g} dy_l[r][o] * x[r][i]        (one owner thread per element: no atomics, deterministic)
 // fp32 FMA code on purpose: the whole family is ~100 MFLOP per step and lives on the fp32 vector path.
-#include <stdlib.h>
 #include "common.h"
 #include "conv_args.h"
 #include "hdmoe.h"
@@ -215,8 +214,7 @@ static bool ml_fill(MLArgs& a, const void* x, const int* seg, const float* const
 // Grouped fp32 linear with 256 <= I <= 1024 on one-position rows (H = W = 1): see glin_f32_kernel.  Same return convention as the other
 // *_try_launch helpers (1 = outside the domain).
 int glin_try_launch(const ConvArgs& c, int dtype, hipStream_t stream) {
-  static const bool off = getenv("HDMOE_GLIN") && atoi(getenv("HDMOE_GLIN")) == 0;
-  if (off || dtype != HDMOE_F32 || c.stride != 1 || c.ones || c.H != 1 || c.W != 1 || c.Ho != 1 || c.Wo != 1 || c.Cin != c.Cphys) return 1;
+  if (dtype != HDMOE_F32 || c.stride != 1 || c.ones || c.H != 1 || c.W != 1 || c.Ho != 1 || c.Wo != 1 || c.Cin != c.Cphys) return 1;
   if (c.Cin < 256 || c.Cin > 1024 || c.Cin % 4 || c.Ipad % 4 || c.Cout != c.Cstore || c.N < 1) return 1;
   for (int g = 0; g < c.ngroups; ++g) if (c.kh[g] != 1 || c.kw[g] != 1 || c.pt[g] || c.pl[g]) return 1;
   if (((uintptr_t)c.x | (uintptr_t)c.w) & 15) return 1;

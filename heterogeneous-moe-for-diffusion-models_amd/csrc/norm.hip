@@ -2,7 +2,6 @@
 //   pixel-norm  : normalize(x, dim=[1])            reference models/model_internals.py:8-30, model_components.py:238
 //   GroupNorm   : nn.GroupNorm(G, C) (+ReLU / +mp_silu fused)   model_components.py:102-109, :491, :530
 //   LayerNorm   : nn.LayerNorm(C)                  model_components.py:495-496, :645
-#include <stdlib.h>
 #include "common.h"
 #include "hdmoe.h"
 
@@ -528,10 +527,6 @@ template <> struct VecW<bf16, 4> {
     *reinterpret_cast<bf16x4*>(p) = v;
   }
 };
-template <> struct VecW<float, 8> {                          // two 16-byte accesses
-  static DEVI void load(float* f, const float* p) { vload<float>(f, p); vload<float>(f + 4, p + 4); }
-  static DEVI void store(float* p, const float* f) { vstore<float>(p, f); vstore<float>(p + 4, f + 4); }
-};
 template <typename T, typename TD = T, int WV = VT<T>::W>
 __global__ __launch_bounds__(512) void groupnorm_bwd_stats_vec_kernel(float* s1, float* s2, float* dgamma, float* dbeta, const TD* dy,
                                                                      const T* x, const float* gamma, const float* beta, const float* mean,
@@ -858,8 +853,7 @@ static int groupnorm_bwd_impl(void* dx, float* dgamma, float* dbeta, float* ws, 
     // 512, not 2048 blocks: this pass belongs to the router trunks' backward, which has slack, and a chip-filling grid of it holds up the
     // expert branch's kernels on the critical stream (same-box A/B 2048 -> 512: 15.52 -> 15.40 ms/step; the reverse experiment, four
     // row-range blocks per sample in the statistics pass, cost +0.4 ms)
-    static const long gcap = getenv("HDMOE_GNB_GRID") ? atol(getenv("HDMOE_GNB_GRID")) : 512;
-    unsigned gb = grid_for(nvec); if (gb > gcap) gb = (unsigned)gcap;
+    unsigned gb = grid_for(nvec); if (gb > 512) gb = 512;
     hipLaunchKernelGGL(groupnorm_bwd_apply_vec_kernel<T>, dim3(gb), dim3(TPB), 0, stream, (T*)dx, (const T*)dy, (const T*)x,
                        gamma, beta, mean, rstd, s1, s2, S, C, G, act, nvec, dyb, dybs);
     return hdmoe_launch_status();
@@ -898,25 +892,16 @@ int hdmoe_groupnorm_bwd_split(void* dx, float* dgamma, float* dbeta, float* ws, 
 int hdmoe_gn1t_bwd(void* dx, float* dgamma, float* dbeta, float* ws, const void* dz, const float* g, float gscale, const float* x, const float* gamma,
                    const float* beta, const float* mean, const float* rstd, int N, long S, int C, hipStream_t stream) {
   if (!dx || !dgamma || !dbeta || !ws || !x || (!dz && !g) || gn_check(N, C, 1)) return HDMOE_EINVAL;
-  // 8 channels per thread (16-byte accesses to the bf16 tensors, two per fp32 vector) or 4 (HDMOE_GN1T_W=4: 8-byte bf16 accesses)
-  static const int wsel = getenv("HDMOE_GN1T_W") ? atoi(getenv("HDMOE_GN1T_W")) : 4;   // (measured: 171 vs 214 us for stats + apply at C = 128, 13.58 vs 13.93 ms/step)
-  const int Wv = (wsel == 4 || C % 8 || 512 % (C / 8)) ? 4 : 8;
-  if (C % Wv || C / Wv > 512 || 512 % (C / Wv) || ((uintptr_t)x & 15) || ((uintptr_t)dx & 15) || ((uintptr_t)dz & 15)) return HDMOE_EINVAL;
-  const long nvec = (long)N * S * C / Wv;
+  // 4 channels per thread: 8-byte accesses to the bf16 tensors (measured against 8 channels with 16-byte accesses: 171 vs 214 us for stats
+  // + apply at C = 128, 13.58 vs 13.93 ms/step)
+  if (C % 4 || C / 4 > 512 || 512 % (C / 4) || ((uintptr_t)x & 15) || ((uintptr_t)dx & 15) || ((uintptr_t)dz & 15)) return HDMOE_EINVAL;
+  const long nvec = (long)N * S * C / 4;
   float* s1 = ws; float* s2 = ws + N;
-  static const long gcap = getenv("HDMOE_GNB_GRID") ? atol(getenv("HDMOE_GNB_GRID")) : 512;
-  unsigned gb = grid_for(nvec); if (gb > gcap) gb = (unsigned)gcap;
-  if (Wv == 8) {
-    hipLaunchKernelGGL((groupnorm_bwd_stats_vec_kernel<float, bf16, 8>), dim3(N, 1), dim3(512), 0, stream, s1, s2, dgamma, dbeta, (const bf16*)dz, x, gamma, beta,
-                       mean, rstd, S, C, 1, 1, 1, dz ? nullptr : g, gscale);
-    hipLaunchKernelGGL((groupnorm_bwd_apply_vec_kernel<float, bf16, 8>), dim3(gb), dim3(TPB), 0, stream, (bf16*)dx, (const bf16*)dz, x, gamma, beta, mean, rstd,
-                       s1, s2, S, C, 1, 1, nvec, dz ? nullptr : g, gscale);
-  } else {
-    hipLaunchKernelGGL((groupnorm_bwd_stats_vec_kernel<float, bf16, 4>), dim3(N, 1), dim3(512), 0, stream, s1, s2, dgamma, dbeta, (const bf16*)dz, x, gamma, beta,
-                       mean, rstd, S, C, 1, 1, 1, dz ? nullptr : g, gscale);
-    hipLaunchKernelGGL((groupnorm_bwd_apply_vec_kernel<float, bf16, 4>), dim3(gb), dim3(TPB), 0, stream, (bf16*)dx, (const bf16*)dz, x, gamma, beta, mean, rstd,
-                       s1, s2, S, C, 1, 1, nvec, dz ? nullptr : g, gscale);
-  }
+  unsigned gb = grid_for(nvec); if (gb > 512) gb = 512;      // (as in groupnorm_bwd_impl)
+  hipLaunchKernelGGL((groupnorm_bwd_stats_vec_kernel<float, bf16, 4>), dim3(N, 1), dim3(512), 0, stream, s1, s2, dgamma, dbeta, (const bf16*)dz, x, gamma, beta,
+                     mean, rstd, S, C, 1, 1, 1, dz ? nullptr : g, gscale);
+  hipLaunchKernelGGL((groupnorm_bwd_apply_vec_kernel<float, bf16, 4>), dim3(gb), dim3(TPB), 0, stream, (bf16*)dx, (const bf16*)dz, x, gamma, beta, mean, rstd,
+                     s1, s2, S, C, 1, 1, nvec, dz ? nullptr : g, gscale);
   return hdmoe_launch_status();
 }
 /* out (bf16 [N][S][C]) = relu(y * scale[n][c] + shift[n][c])  (scale == null: out = bf16(y)); C % 8 == 0 */

@@ -9,7 +9,6 @@
 //             33rd column is simply never fetched) and the map added inside the alpha scale of the epilogue;
 //   backward: dx = conv6 over dy with the flipped image (its 33rd row per tap skipped through the tap stride), dW[:, :32] by wgrad6
 //             into compact slabs, dW[:, 32] from per-expert pixel sums of dy; one scatter launch adds both into the bank's [tap][O][33] slab.
-#include <stdlib.h>
 #include "common.h"
 #include "conv_args.h"
 #include "conv6_common.h"
@@ -134,10 +133,9 @@ extern "C" {
  * [ngroups][H][W][O] fp32 (written here).  Returns 1 without launching outside the domain (bf16, conv6's shapes). */
 int hdmoe_conv6_ones_fwd(const void* x, const void* wf, void* y, float* gbias, float alpha, const int* seg, int ngroups, long wstride,
                          int N, int H, int W, int C, int O, int Ipad, const int* kh, int dtype, hipStream_t stream) {
-  static const bool off = getenv("HDMOE_ONES6") && atoi(getenv("HDMOE_ONES6")) == 0;
   if (!x || !wf || !y || !gbias || N < 0) return HDMOE_EINVAL;
   OnesGeo geo;
-  if (off || dtype != HDMOE_BF16 || !ones_domain(ngroups, H, W, C, O, Ipad, kh, geo) || (((uintptr_t)gbias) & 15)) return 1;
+  if (dtype != HDMOE_BF16 || !ones_domain(ngroups, H, W, C, O, Ipad, kh, geo) || (((uintptr_t)gbias) & 15)) return 1;
   if (N == 0) return HDMOE_OK;
   ConvArgs c;
   c.x = x; c.w = wf; c.y = y; c.res = nullptr; c.seg = seg; c.wstride = wstride;
@@ -158,10 +156,9 @@ int hdmoe_conv6_ones_fwd(const void* x, const void* wf, void* y, float* gbias, f
 int hdmoe_conv6_ones_bwd(const void* x, const void* dy, const void* wd, void* dx, float* const* G33, float* S, float* const* G32, const int* seg,
                          int ngroups, long wdstride, int N, int H, int W, int C, int O, int Opad, const int* kh, float alpha, void* ws, long ws_bytes,
                          int dtype, hipStream_t stream) {
-  static const bool off = getenv("HDMOE_ONES6") && atoi(getenv("HDMOE_ONES6")) == 0;
   if (!x || !dy || !G33 || !S || !G32 || N < 0) return HDMOE_EINVAL;
   OnesGeo geo;
-  if (off || dtype != HDMOE_BF16 || !ones_domain(ngroups, H, W, C, O, C + 8, kh, geo) || Opad % 8 || Opad < O) return 1;
+  if (dtype != HDMOE_BF16 || !ones_domain(ngroups, H, W, C, O, C + 8, kh, geo) || Opad % 8 || Opad < O) return 1;
   int k2[HDMOE_MAX_GROUPS], pd[HDMOE_MAX_GROUPS];
   for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) { k2[g] = geo.ks[g]; pd[g] = (geo.ks[g] - 1) / 2; }
   const long kib = hdmoe_conv_wgrad6_ws_kib(ngroups, N, H, W, C, O, k2, k2, dtype);

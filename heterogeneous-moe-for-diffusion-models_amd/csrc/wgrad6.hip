@@ -16,7 +16,6 @@
 //   * results leave as plain 128-byte-run stores into a per-(expert, pixel-partition) partial slab; wgrad6_reduce_kernel sums the
 //     partitions into the bank's [tap][O][I] gradient slab in a fixed order (deterministic; float atomics ran at ~1.3 TB/s).
 // Domain: bf16, stride 1, square k in {3, 5}, Cin % 32 == 0, Cout % 32 == 0, W == 16 or W % 32 == 0; everything else: conv.hip.
-#include <stdlib.h>
 #include "common.h"
 #include "conv_args.h"
 #include "hdmoe.h"
@@ -120,14 +119,13 @@ __global__ __launch_bounds__(256) void wgrad6_reduce_multi_kernel(W6RBatch b) {
 // bf16 layers on 32 x 32 maps run the wgrad8 program (wgrad8_body.h) in the fused backward launch: 2 x 2 chunks per workgroup where the layer
 // has them, so a slot has a quarter of the workgroups and the class gets four times the slots for the same number of workgroups.
 int w6_wgs_per_slot(int H, int W, int Cin, int Cout, int ks, int dtype, int* icw, int* ocw) {
-  static const bool w8 = !(getenv("HDMOE_WGRAD8") && atoi(getenv("HDMOE_WGRAD8")) == 0);
   const int OT = Cout % 64 == 0 ? 2 : 1;
   int ic = 1, oc = 1, n = (Cin / 32) * (Cout / (32 * OT));
-  if (w8 && dtype == HDMOE_BF16 && ks == 3 && H == 32 && W == 32) {
+  if (dtype == HDMOE_BF16 && ks == 3 && H == 32 && W == 32) {
     ic = Cin % 64 == 0 ? 2 : 1; oc = Cout % 64 == 0 ? 2 : 1;
     n = (Cin / 32 / ic) * (Cout / 32 / oc);
   }
-  if (icw) *icw = w8 ? ic : 0;                               // 0: the wgrad7 program (one chunk pair per workgroup) for this class
+  if (icw) *icw = ic;
   if (ocw) *ocw = oc;
   return n;
 }
@@ -138,21 +136,17 @@ void w6_partition(long units_l, int ngr, int ngroups, int wgs, int& upw, int& sl
   // [tap][O][I] fp32 slab, at 256 a 64->64 layer moved 71 MB of partials for 2 x 17 MB of operands, and in the fused backward launch
   // the 256 conv workgroups fill the chip anyway (same-box A/B 256 -> 128: 16.58 -> 16.15 ms/step).  The fp32 router layers
   // measure the same (16.15-16.2 with 128, 16.25-16.4 with 256 or 512).
-  static const long target_bf = getenv("HDMOE_W6_PARTS") ? atol(getenv("HDMOE_W6_PARTS")) : 128;
-  static const long target_sp = getenv("HDMOE_W6_PARTS_SPLIT") ? atol(getenv("HDMOE_W6_PARTS_SPLIT")) : 128;
-  long parts = (split ? target_sp : target_bf) / ((long)ibs * obs);
+  const long target = 128;
+  long parts = target / ((long)ibs * obs);
   // Two kernel-size classes in one launch (3x3 and 5x5 experts): the workgroups are shared out by WORK (taps x rows), not evenly -- with 128 + 128
-  // the 3x3 class finished in a third of the 5x5 class's time and its CUs idled (round 4; HDMOE_W6_BALANCE=0: the even split)
-  static const bool balance = !(getenv("HDMOE_W6_BALANCE") && atoi(getenv("HDMOE_W6_BALANCE")) == 0);
-  // One class alone (the router-trunk layers in bf16-operand mode).  HDMOE_W6_PARTS_SINGLE=256 makes the launch itself 20 % faster on the trunk
-  // shapes (B = 256: 128 -> 128 233 -> 184 us, 64 -> 128 120 -> 92, 32 -> 64 44 -> 38) but the replayed step 0.05 ms SLOWER on the same box: the
-  // router's backward runs beside the U-Net bank's backward, which is the critical path, and more workgroups take CUs from it.  Default: as before.
-  static const long target_one = getenv("HDMOE_W6_PARTS_SINGLE") ? atol(getenv("HDMOE_W6_PARTS_SINGLE")) : target_bf;
-  if (!split && ngr == ngroups) parts = target_one / ((long)ibs * obs);
-  if (balance && !split && kh && ngr < ngroups) {
+  // the 3x3 class finished in a third of the 5x5 class's time and its CUs idled (round 4).  One class alone (the router-trunk layers in
+  // bf16-operand mode) keeps 128: 256 made the launch itself 20 % faster on the trunk shapes (B = 256: 128 -> 128 233 -> 184 us, 64 -> 128
+  // 120 -> 92, 32 -> 64 44 -> 38) but the replayed step 0.05 ms SLOWER on the same box: the router's backward runs beside the U-Net bank's
+  // backward, which is the critical path, and more workgroups take CUs from it.
+  if (!split && kh && ngr < ngroups) {
     long wsum = 0;
     for (int g = 0; g < ngroups; ++g) wsum += (long)kh[g] * kh[g];
-    parts = 2 * target_bf * ((long)ngr * ks * ks) / wsum / ((long)ibs * obs);
+    parts = 2 * target * ((long)ngr * ks * ks) / wsum / ((long)ibs * obs);
   }
   if (parts < 1) parts = 1;
   const long class_units = (units_l * ngr + ngroups - 1) / ngroups;
@@ -208,8 +202,7 @@ int hdmoe_conv_wgrad6_ws_kib(int ngroups, int N, int H, int W, int Cin, int Cout
 // 0 = planned, 1 = not applicable (the caller takes hdmoe_conv_wgrad6 / hdmoe_conv_wgrad).
 int wgrad6_plan_dual(const void* x, const void* dy, float* const* G, const int* seg, int ngroups, int N, int H, int W, int Cin, int Cout,
                      const int* kh, const int* kw, const int* pt, const int* pl, void* ws, long ws_bytes, int dtype, W6DualPlan& p) {
-  static const bool off = (getenv("HDMOE_WGRAD6") && atoi(getenv("HDMOE_WGRAD6")) == 0) || (getenv("HDMOE_W6_DUAL") && atoi(getenv("HDMOE_W6_DUAL")) == 0);
-  if (off || dtype != HDMOE_BF16) return 1;
+  if (dtype != HDMOE_BF16) return 1;
   const long need1 = 1024l * hdmoe_conv_wgrad6_ws_kib(ngroups, N, H, W, Cin, Cout, kh, kw, dtype);
   if (need1 == 0 || !ws || ws_bytes < 2 * need1 || !x || !dy || !G || N == 0) return 1;
   if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)ws) & 15) return 1;
@@ -251,8 +244,6 @@ int wgrad6_plan_dual(const void* x, const void* dy, float* const* G, const int* 
 // Launch geometry of the deferred split-bf16 (fp32 tensors, 3x3 only) weight gradient of one layer.  0 = planned, 1 = not applicable.
 int wgrad6_plan_split(const void* x, const void* dy, float* const* G, const int* seg, int ngroups, int N, int H, int W, int Cin, int Cout,
                       const int* kh, const int* kw, const int* pt, const int* pl, void* ws, long ws_bytes, W6DualPlan& p) {
-  static const bool off = getenv("HDMOE_WGRAD6") && atoi(getenv("HDMOE_WGRAD6")) == 0;
-  if (off) return 1;
   const long need1 = 1024l * hdmoe_conv_wgrad6_ws_kib(ngroups, N, H, W, Cin, Cout, kh, kw, HDMOE_F32S);
   if (need1 == 0 || !ws || ws_bytes < 2 * need1 || !x || !dy || !G || N == 0) return 1;
   if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)ws) & 15) return 1;
@@ -287,8 +278,6 @@ extern "C" {
 int hdmoe_conv_wgrad6(const void* x, const void* dy, float* const* G, const int* seg, int ngroups, int N, int H, int W, int Cin,
                       int Cout, const int* kh, const int* kw, const int* pt, const int* pl, void* ws, long ws_bytes, int dtype,
                       int defer, hipStream_t stream) {
-  static const bool off = getenv("HDMOE_WGRAD6") && atoi(getenv("HDMOE_WGRAD6")) == 0;
-  if (off) return 1;
   // defer != 0: no reduction here (hdmoe_conv_wgrad6_reduce_batch does it later); the kernel-size classes then need their own
   // workspace regions, laid out one after the other (each `need` bytes at most)
   const long need1 = 1024l * hdmoe_conv_wgrad6_ws_kib(ngroups, N, H, W, Cin, Cout, kh, kw, dtype);

@@ -9,7 +9,7 @@ When do the collectives go out?  Almost every gradient of this path is written s
 weight bank's finish launch, the norm / bias / table backward kernels) and never passes through an AccumulateGrad node, so
 autograd hooks cannot tell when a bucket is complete.  Completion is known structurally instead:
   * default (multi-stream step): the parameters are bucketed by the SECTION of the staged step (hdmoe_hip/graph.py) whose backward
-    finishes them, in the order the sections complete: the U-Net bank's backward runs as four sections (graph.Stager.SPLIT_UNET_BWD) --
+    finishes them, in the order the sections complete: the U-Net bank's backward runs as four sections (graph.Stager, SPLIT_UNET_BWD) --
     "unet_s3" (full-resolution decoder entries + output conv), "unet_s2" (decoder below), "unet_s1" (encoder below), then "vit" (ViT
     router + experts), "unet_s0" (full-resolution encoder entries, the embedding layers of every block, the U-Net router) and "rest" (stem,
     fusion, head, preconditioning).  ``staged_hooks(staged)`` gives StagedStep one hook per section; each runs right after that section's

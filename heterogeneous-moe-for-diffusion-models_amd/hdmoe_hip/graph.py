@@ -19,10 +19,7 @@ def _capture_mode() -> str:
     """Error mode of the stream captures.  With a process group alive (RCCL's watchdog thread polls events from its own thread)
     a 'global' capture would turn that polling into a capture error; 'thread_local' restricts the check to the capturing thread.
     The step allocates nothing new after its warm-up runs, so the laxer mode hides nothing."""
-    import os
     import torch.distributed as dist
-    if os.environ.get("HDMOE_CAPTURE_MODE"):                      # (A/B aid)
-        return os.environ["HDMOE_CAPTURE_MODE"]
     return "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
 
 
@@ -95,32 +92,27 @@ class Stager:
     """Stage bookkeeping shared by the eager warm-up runs and the capture run of a StagedStep.  Model code talks to it through
     ``graph.current()``: ``cut(stage, **tensors_by_producer_stage)`` at a boundary, ``backward(loss)`` instead of loss.backward()."""
 
-    KIND = {"pre": "main", "ur": "r", "unet": "u", "vit": "v", "post": "main", "ucomb_bwd": "u", "ur_bwd": "r", "unet_bwd": "u", "vit_bwd": "v",
+    # The router FORWARD of the U-Net branch is on the critical path (the bank cannot start before the routing weights exist): it runs
+    # on the bank's own stream; only its backward, which has slack, uses the third stream.
+    KIND = {"pre": "main", "ur": "u", "unet": "u", "vit": "v", "post": "main", "ucomb_bwd": "u", "ur_bwd": "r", "unet_bwd": "u", "vit_bwd": "v",
             "pre_bwd": "main", "unet_bwd2": "u", "unet_bwd1": "u", "unet_bwd0": "u", "vcomb_bwd": "v", "vr_bwd": "main"}
-    # SPLIT_VROUTER (round 4): with the U-Net bank's backward down to ~6 ms the ViT section became the LAST one to finish (stage_ms: vit_bwd
+    # SPLIT_VROUTER, the ViT router's backward as its own section (round 4, always on): with the U-Net bank's backward down to ~6 ms the ViT section became the LAST one to finish (stage_ms: vit_bwd
     # 6.2 -> 12.8 ms, unet_bwd0 ends at 12.4): its stream runs the ViT bank's backward (~170 small launches) and then the ViT router's trunk
     # backward (the heavy part) one after the other.  The router's backward needs only the gradient of the routing weights, which the
     # combine backward -- the section's first kernel -- produces: same cut as for the U-Net router (`vcomb_bwd` on the ViT stream, then
-    # `vr_bwd` beside `vit_bwd`).  The forward stays one graph.  HDMOE_VR_STREAM: the stream of `vr_bwd`.  Same box, ms/step, with the stream
+    # `vr_bwd` beside `vit_bwd`).  The forward stays one graph.  The stream of `vr_bwd`, same box, ms/step, with the stream
     # priorities of the time: no split 13.39; "r" (behind the U-Net router's backward) 13.13; "main" (idle between `post` and `pre_bwd`) 13.32;
     # "r2" (a fifth stream of our own) 17.9 -- see the note on hardware queues below.  Without priorities (the default now, see StagedStep):
     # "main" 13.02, "r" 13.62.
-    SPLIT_VROUTER = __import__("os").environ.get("HDMOE_SPLIT_VROUTER", "1") != "0"
-    KIND["vr_bwd"] = __import__("os").environ.get("HDMOE_VR_STREAM", "main")
-    # SPLIT_UNET_BWD (round 4): the U-Net bank's backward as up to FOUR sections on its stream -- decoder at full resolution (+ output conv),
+    # SPLIT_UNET_BWD (round 4, always on): the U-Net bank's backward as up to FOUR sections on its stream -- decoder at full resolution (+ output conv),
     # decoder below, encoder below, encoder at full resolution (+ embeddings) -- cut with detached leaves inside the forward graph
     # (models/model_components.py unet_expert_bank_forward).  Each section finishes its own weight gradients (bank.finish_stage), so its
     # gradient bucket can go to RCCL while the later sections still run (hdmoe_hip/dp.py); single-process jobs just replay four graphs.
-    SPLIT_UNET_BWD = __import__("os").environ.get("HDMOE_SPLIT_UNET_BWD", "1") != "0"
     # SPLIT_ROUTER: the U-Net branch is the longer one, and its router's backward (2.2 ms of kernels) needs nothing from the bank's
     # backward but the gradient of the routing weights, which the bank's FIRST backward kernel (the combine) produces.  The router
     # therefore gets its own stream and graphs (`ur`, `ur_bwd`), and the combine backward its own small graph (`ucomb_bwd`) so that
-    # `ur_bwd` can start right after it, beside the bank backward.
-    SPLIT_ROUTER = __import__("os").environ.get("HDMOE_SPLIT_ROUTER", "1") != "0"
-    # The router FORWARD of the U-Net branch is on the critical path (the bank cannot start before the routing weights exist): it runs
-    # on the bank's own (prioritised) stream; only its backward, which has slack, uses the third stream.
-    if __import__("os").environ.get("HDMOE_UR_ON_U", "1") != "0":
-        KIND["ur"] = "u"
+    # `ur_bwd` can start right after it, beside the bank backward.  (Tests set it False to compare against the seven-graph form.)
+    SPLIT_ROUTER = True
 
     def __init__(self, device, streams, pools):
         self.device, self.streams, self.pools = device, streams, pools
@@ -232,44 +224,37 @@ def backward(loss):
         loss.backward()
 
 
-# Timing experiments only (tools/): sections listed in HDMOE_SKIP_STAGE are dropped from the replay -- the step's results
-# are then WRONG.  Read once at import; a left-over setting is announced loudly instead of silently corrupting a training run.
-SKIP_STAGES = tuple(s_ for s_ in __import__("os").environ.get("HDMOE_SKIP_STAGE", "").split(",") if s_)
-if SKIP_STAGES:
-    import warnings as _warnings
-    _warnings.warn(f"hdmoe_hip.graph: HDMOE_SKIP_STAGE={','.join(SKIP_STAGES)} drops these sections from every StagedStep replay -- gradients and "
-                   "loss are WRONG; this switch is for timing experiments only", RuntimeWarning)
-
-
 class StagedStep:
-    """Drop-in for GraphedStep when ``step_fn`` runs the banked HDMOEM path and calls ``graph.backward(loss)``."""
+    """Drop-in for GraphedStep when ``step_fn`` runs the banked HDMOEM path and calls ``graph.backward(loss)``.
+
+    Two keyword arguments exist for timing / race experiments only (tools/replay_race.py): ``priorities=True`` gives the U-Net and main
+    streams the higher priority (see the note in __init__), ``skip`` names sections that every replay drops -- the step's results are
+    then WRONG."""
 
     ORDER = ["pre", "unet", "vit", "post", "unet_bwd", "vit_bwd", "pre_bwd"]
     ORDER_R = ["pre", "ur", "unet", "vit", "post", "ucomb_bwd", "unet_bwd", "ur_bwd", "vit_bwd", "pre_bwd"]
 
-    def __init__(self, step_fn, device, warmup: int = 3):
+    def __init__(self, step_fn, device, warmup: int = 3, *, priorities: bool = False, skip=()):
         self.device = torch.device(device)
+        self.skip = tuple(skip)
         # the U-Net branch is the longer one (the ViT branch has ~2.5 ms of slack in the backward): its stream gets the higher priority
         # ... but only in a single-process job.  Measured with a one-rank RCCL group (bench.py HDMOE_BENCH_FORCE_DIST=1): as soon as the
         # process owns one more stream (RCCL's) next to prioritised ones, whole stages run 1.5-2x longer (17.3 -> 22.5 ms/step; a fifth
         # stream of our own did the same); with equal priorities the extra stream costs ~0.2 ms (17.2 vs 17.0 ms/step including the
-        # all-reduces).  So: priorities only when no process group exists.  How ROCclr maps streams onto its hardware queues
+        # all-reduces).  How ROCclr maps streams onto its hardware queues
         # (GPU_MAX_HW_QUEUES, default 4 per priority level) decides whether two of our streams end up sharing a queue and whole
         # stages serialise: measured under the one-rank RCCL group 4 queues 17.2, 8 queues 17.4, 6 queues 20.4 ms/step; without a group
         # and without priorities 4 queues 18.0, 8 queues 17.6; a ONE-graph replay with an internal fork (the sampler) is 20 % slower
         # with 8 queues than with 4.  The default (4) is the best setting for every configuration the code itself selects.
-        # ROUND 4: stream priorities are OFF by default.  With prioritised streams, replays launched back to back (the host a replay ahead of the
-        # device -- what a training loop and bench.py do) showed a transient: in 2-6 % of the replays the router logits of the LOW-priority branch
+        # ROUND 4: stream priorities are OFF unless `priorities=True` (tools/replay_race.py).  With prioritised streams, replays launched
+        # back to back (the host a replay ahead of the device -- what a training loop and bench.py do) showed a transient: in 2-6 % of the replays the router logits of the LOW-priority branch
         # came out with a bf16-sized error (5e-3 .. 3e-2 against 8e-5), gone in the next replay (tools/replay_race.py: 51 outliers in 900 bursts of
         # three replays; 0 in 1800 bursts without priorities, 0 with a synchronize between the replays; it survives dropping every backward section
         # from the replay, so it sits between `pre` / the forward branches of neighbouring replays).  The event dependencies are the same either
         # way; which wait the prioritised queues do not honour was not isolated.  Without priorities the schedule needs `vr_bwd` on the `main`
         # stream to keep the step time (12.98 prioritised, 13.02 equal priorities + vr_bwd on main, 13.62 equal priorities + vr_bwd behind ur_bwd).
-        pmode = os.environ.get("HDMOE_STREAM_PRIO", "0")
-        use_prio = pmode == "1"
-        prio = {"main": -1, "u": -1, "v": 0, "r": 0} if use_prio else {"main": 0, "u": 0, "v": 0, "r": 0}
-        names = ("main", "u", "v", "r") + (("r2",) if Stager.KIND["vr_bwd"] == "r2" else ())
-        prio["r2"] = 0
+        prio = {"main": -1, "u": -1, "v": 0, "r": 0} if priorities else {"main": 0, "u": 0, "v": 0, "r": 0}
+        names = ("main", "u", "v", "r")
         self.streams = {k: torch.cuda.Stream(device=self.device, priority=prio[k]) for k in names}
         self.pools = {k: torch.cuda.graph_pool_handle() for k in names}
         cur = torch.cuda.current_stream(self.device)
@@ -283,7 +268,7 @@ class StagedStep:
         with no_gc():
             st = self._run(step_fn, capture=True)
         core = [n for n in st.order if n not in ("unet_bwd2", "unet_bwd1", "unet_bwd0", "vcomb_bwd", "vr_bwd")]
-        self.split_vr = "vr_bwd" in st.order                      # the ViT router's backward as its own section (Stager.SPLIT_VROUTER)
+        self.split_vr = "vr_bwd" in st.order                      # the ViT router's backward as its own section (SPLIT_VROUTER above)
         if core not in (self.ORDER, self.ORDER_R):
             raise RuntimeError(f"staged step: unexpected stage sequence {st.order}")
         self.split_router = core == self.ORDER_R
@@ -315,7 +300,7 @@ class StagedStep:
         cur = torch.cuda.current_stream(self.device)
         ev = self._events = {} if self.timing else None
 
-        skip = SKIP_STAGES
+        skip = self.skip
 
         def run(name, stream):
             if name in skip:

@@ -58,9 +58,8 @@ def _next_seed() -> int:
 _step_counters = {}
 
 # Independent, launch-latency-bound branches of the model (the ViT experts) run on side streams beside the main stream's
-# large launches; HDMOE_SIDE_STREAMS=0 serialises everything on the caller's stream.
-import os as _os
-SIDE_STREAMS = _os.environ.get("HDMOE_SIDE_STREAMS", "1") != "0"
+# large launches; False serialises everything on the caller's stream.
+SIDE_STREAMS = True
 _side_pool = {}
 
 
@@ -203,12 +202,11 @@ _w6_ws = {}
 # Small learnable tensors (norm affines, biases, rel_pos_bias, alpha_txt): when the parameter already owns a gradient buffer (the
 # flat DP buckets, or a .grad kept from the previous step) the backward kernels -- which accumulate anyway -- add straight into it
 # and hand autograd None.  That is what the weight bank does for the conv weights; per step it removes a zero-fill and an
-# AccumulateGrad add per parameter (~300 launches of ~5 us that the host enqueues one by one).  HDMOE_DIRECT_PARAM_GRADS=0: off.
-DIRECT_PARAM_GRADS = _os.environ.get("HDMOE_DIRECT_PARAM_GRADS", "1") != "0"
+# AccumulateGrad add per parameter (~300 launches of ~5 us that the host enqueues one by one).
 
 
 def _direct(p) -> bool:
-    return (DIRECT_PARAM_GRADS and p is not None and p.is_leaf and p.requires_grad and p.grad is not None
+    return (p is not None and p.is_leaf and p.requires_grad and p.grad is not None
             and p.grad.dtype == torch.float32 and p.grad.is_contiguous() and p.grad.shape == p.shape)
 
 
@@ -242,7 +240,6 @@ class _ZeroPool:
 
 
 _zero_pools = {}
-ZERO_POOL = _os.environ.get("HDMOE_ZERO_POOL", "1") != "0"
 
 
 def zero_pool_reset(device) -> None:
@@ -255,7 +252,7 @@ def _zeros(shape, dtype, device, pool_ok: bool = True) -> Tensor:
     """torch.zeros for accumulate-into scratch / non-leaf gradients, served from the per-step zero pool when possible
     (``pool_ok=False``: the buffer may become a leaf's .grad -- autograd adopts incoming gradients -- and must own its memory)."""
     device = torch.device(device)
-    if pool_ok and ZERO_POOL and device.type == "cuda":
+    if pool_ok and device.type == "cuda":
         pool = _zero_pools.get(device)
         if pool is None:
             if torch.cuda.is_current_stream_capturing():
@@ -301,12 +298,12 @@ def fanout(x: Tensor, n: int, scales=None):
 class _W6Arena:
     """Workspace of the DEFERRED wgrad6 reductions: every k x k layer of the weight bank keeps its partial slabs until the end of the
     backward pass, where one batched launch per 16 layers sums them (WeightBank._finish).  One bump-allocated buffer per device,
-    rewound at the start of a step.  It starts at HDMOE_W6_ARENA_MB (default 1024) and is re-sized to the step's high-water mark at the
+    rewound at the start of a step.  It starts at W6_ARENA_MB and is re-sized to the step's high-water mark at the
     next rewind outside a graph capture: a layer that does not fit meanwhile takes the non-deferred path (its own cached workspace)."""
 
     def __init__(self, device):
         self.device = device
-        self.buf = torch.empty(int(_os.environ.get("HDMOE_W6_ARENA_MB", "1024")) << 18, dtype=torch.float32, device=device)
+        self.buf = torch.empty(W6_ARENA_MB << 18, dtype=torch.float32, device=device)
         self.off = 0
         self.want = 0                                        # floats the current step would have needed
         self.captured = False                                # a hipGraph capture handed out slices of the CURRENT buffer
@@ -320,8 +317,8 @@ class _W6Arena:
                 # the captured step would bake the slower non-deferred path in: say how to avoid it instead of degrading silently
                 import warnings
                 warnings.warn(f"hdmoe_hip: the deferred weight-gradient arena ({self.buf.numel() * 4 >> 20} MB) is too small for this step and cannot "
-                              f"grow inside a hipGraph capture; run one eager step before capturing or set HDMOE_W6_ARENA_MB >= "
-                              f"{(self.want * 5 >> 20) + 1}", RuntimeWarning, stacklevel=3)
+                              f"grow inside a hipGraph capture; run one eager step before capturing (this step needs >= "
+                              f"{(self.want * 5 >> 20) + 1} MB)", RuntimeWarning, stacklevel=3)
             return None
         self.off = start + nfloats
         if torch.cuda.is_current_stream_capturing():
@@ -342,8 +339,7 @@ class _W6Arena:
 
 
 _w6_arenas = {}
-W6_DEFER = _os.environ.get("HDMOE_W6_DEFER", "1") != "0"
-BWD6 = _os.environ.get("HDMOE_BWD6", "1") != "0"          # dgrad + wgrad of a k x k expert layer in one launch (csrc/bwd6.hip)
+W6_ARENA_MB = 1024                                         # initial size of the deferred weight-gradient arena
 
 
 def w6_arena_reset(device) -> None:
@@ -372,7 +368,7 @@ def _wgrad(info, x, dy, Gs, seg, G, N, H, W, Ho, Wo, I, Cphys, O, ones, khs, kws
         dtc = F32S if split else _dt(x)
         kib = lib().hdmoe_conv_wgrad6_ws_kib(G, N, H, W, I, O, ctypes.cast(_int_array(khs), ctypes.c_void_p),
                                              ctypes.cast(_int_array(kws), ctypes.c_void_p), dtc)
-        if kib > 0 and bank is not None and W6_DEFER and _prof_ok():
+        if kib > 0 and bank is not None and _prof_ok():
             # weight-bank layer: the partial slabs stay in the arena, the bank sums all layers' partials in one batched launch
             ws = _w6_arena_take(x.device, 2 * kib * 256)
             if ws is not None:
@@ -483,7 +479,7 @@ class _MPConvFn(torch.autograd.Function):
         need_gain = gains is not None and any(nig[4 + G + g] for g in range(G))
         need_w = any(nig[4 + g] for g in range(G)) or need_gain
         fused = False
-        if (nig[0] and need_w and ctx.ent is not None and BWD6 and W6_DEFER and _prof_ok() and x.dtype == torch.bfloat16 and not split
+        if (nig[0] and need_w and ctx.ent is not None and _prof_ok() and x.dtype == torch.bfloat16 and not split
                 and not ones and Ho == H and Wo == W and Cphys == I and set(khs) == {3, 5} and khs == kws):
             # input gradient + (deferred) weight gradient of a 3x3 / 5x5 expert layer in one launch (csrc/bwd6.hip)
             from ._lib import lib, _int_array
@@ -504,7 +500,7 @@ class _MPConvFn(torch.autograd.Function):
                     STATS["bwd6"] += 1
                 else:
                     dx = None
-        if (nig[0] and need_w and ctx.ent is not None and BWD6 and W6_DEFER and _prof_ok() and split and not ones and Ho == H and Wo == W
+        if (nig[0] and need_w and ctx.ent is not None and _prof_ok() and split and not ones and Ho == H and Wo == W
                 and Cphys == I and set(khs) == {3} and khs == kws):
             # the same for a router-trunk layer (fp32 tensors, split-bf16 arithmetic)
             from ._lib import lib, _int_array
@@ -640,9 +636,6 @@ def mp_conv_strided(x: Tensor, w: Tensor, gain: float, stride: int, training: bo
 
 _PRECOMP = None                           # output tensor a fused launch has already produced for the NEXT _MPConvFn.forward (ops.unet_block_fused)
 F32S = 2                                  # C-ABI dtype code: fp32 tensors, split-bf16 arithmetic (include/hdmoe.h HDMOE_F32S)
-# The fp32 router trunks run on the bf16 matrix pipe as split-bf16 (3 MFMAs per product, ~1e-5 relative): HDMOE_ROUTER_SPLIT=0
-# keeps them on the fp32-input MFMA kernels.
-ROUTER_SPLIT = _os.environ.get("HDMOE_ROUTER_SPLIT", "1") != "0" and _os.environ.get("HDMOE_CONV6", "1") != "0"   # (the split kernels are conv6's)
 
 
 def _split_ok(x4: Tensor, ws, ones: bool) -> bool:
@@ -741,7 +734,7 @@ def multi_linear(x: Tensor, layers, gain: float, *, seg: Optional[Tensor] = None
     L = len(layers)
     bank = _bank.ACTIVE
     ents = None
-    if bank is not None and 1 <= L <= 16 and x.ndim == 2 and x.shape[1] <= 256 and x.dtype == torch.float32 and MULTI_LINEAR:
+    if bank is not None and 1 <= L <= 16 and x.ndim == 2 and x.shape[1] <= 256 and x.dtype == torch.float32:
         ents = [bank.lookup(ws, torch.float32, float(gain), 1.0, True) for ws in layers]
         ok = all(e is not None for e in ents) and len({(e.I, e.Ipad, len(e.params)) for e in ents if e is not None}) == 1
         if ok and all(e.khs == [1] * len(e.params) for e in ents) and (seg is not None or len(ents[0].params) == 1):
@@ -750,8 +743,6 @@ def multi_linear(x: Tensor, layers, gain: float, *, seg: Optional[Tensor] = None
     outs = [mp_conv(x, ws if seg is not None else ws[0], gain, seg=seg, training=training) for ws in layers]
     return [affine(o, 1.0, c) for o in outs] if c != 0.0 else outs
 
-
-MULTI_LINEAR = _os.environ.get("HDMOE_MULTI_LINEAR", "1") != "0"
 
 
 class _PatchLinearFn(torch.autograd.Function):
@@ -1064,8 +1055,8 @@ class _FilmReq:
 
 
 _FILM_REQ = None                                        # set around the mp_conv call of ops.mp_conv_film
-CONV_FILM = _os.environ.get("HDMOE_CONV_FILM", "1") != "0"
-CONV_FILM_TRAIN = _os.environ.get("HDMOE_CONV_FILM", "1") == "2"
+CONV_FILM = True                                        # False: always the separate FiLM pass
+CONV_FILM_TRAIN = False                                 # True: the fused FiLM epilogue with dropout too
 
 
 class _FilmDoneFn(torch.autograd.Function):
@@ -1089,7 +1080,7 @@ def mp_conv_film(x: Tensor, weights, gain, emb: Tensor, p: float, training: bool
     global _FILM_REQ
     p = float(p) if training else 0.0
     C = int((weights[0] if isinstance(weights, (list, tuple)) else weights).shape[0])
-    # Only without dropout (eval / sampling), unless forced (HDMOE_CONV_FILM=2): drawing the Philox bits in the conv epilogue -- 8 waves per CU,
+    # Only without dropout (eval / sampling), unless forced (CONV_FILM_TRAIN): drawing the Philox bits in the conv epilogue -- 8 waves per CU,
     # on every unit's critical path -- costs more than the whole separate pass (measured: conv6<2,1> 44 -> 85 us against a 22-us film kernel).
     ok = (CONV_FILM and (p == 0.0 or CONV_FILM_TRAIN) and x.dtype == torch.bfloat16 and x.ndim == 4 and C % 8 == 0 and 256 % (C // 8) == 0
           and _bank.ACTIVE is not None)
@@ -1106,17 +1097,16 @@ def mp_conv_film(x: Tensor, weights, gain, emb: Tensor, p: float, training: bool
     return _FilmSiluFn.apply(y, req.emb, p, req.seed)
 
 
-ONES6 = _os.environ.get("HDMOE_ONES6", "1") != "0"          # the 33-channel first conv of Unet_expert on conv6 / wgrad6 (csrc/ones6.hip)
-BLK6 = _os.environ.get("HDMOE_BLK6", "1") != "0"
+ONES6 = True                                                # the 33-channel first conv of Unet_expert on conv6 / wgrad6 (csrc/ones6.hip)
+BLK6 = True
 # Which blocks take the fused launch.  Measured per layer shape (tools/blk6_bench.py, graph replay, N = 512 rows, experts [3,3,5,5],
 # dropout 0.2; fused vs conv6 + film_silu + conv6): 32 -> 32 at 32x32 108 vs 117 us, 64 -> 32 140 vs 142, 32 -> 32 at 16x16 33 vs 42; but
 # 64 -> 64 at 16x16 76 vs 73, 128 -> 64 98 vs 93, 64 -> 64 at 32x32 306 vs 280: with 64 output channels the unit's phases (conv A, middle op,
 # conv B) run one after the other in a single 8-wave workgroup and the halo recompute is not paid back.  "c32": 32-channel blocks only.
 # Round 4: on 32 x 32 maps with enough routed rows the whole-image streaming kernel (csrc/conv7.hip) runs the two convs + the FiLM pass in
 # 2 x 27 + 19 us against the fused launch's 97-108 us, so "c32" leaves those blocks to it (same box: 14.00 -> 13.72 ms / step).
-BLK6_SCOPE = _os.environ.get("HDMOE_BLK6_SCOPE", "c32")
-CONV7 = _os.environ.get("HDMOE_CONV7", "1") != "0"
-C7_MINN = int(_os.environ.get("HDMOE_C7_MINN", "192"))
+BLK6_SCOPE = "c32"
+C7_MINN = 192                                               # conv7's least number of images (C7_MIN_IMAGES in csrc/conv7.hip)
 
 
 def unet_block_fused(h: Tensor, res: Optional[Tensor], w1s, w2s, gain1: float, gain2: float, emb: Tensor, p: float, training: bool,
@@ -1141,7 +1131,7 @@ def unet_block_fused(h: Tensor, res: Optional[Tensor], w1s, w2s, gain1: float, g
     C = ent1.O
     if ent1.I != Cin or ent2.I != C or ent2.O != C or (seg is None and len(w1s) != 1):
         return None
-    if BLK6_SCOPE == "c32" and (C != 32 or (CONV7 and H == 32 and W == 32 and N >= C7_MINN)):
+    if BLK6_SCOPE == "c32" and (C != 32 or (H == 32 and W == 32 and N >= C7_MINN)):
         return None
     p = float(p) if training else 0.0
     e32 = _f32(emb)
@@ -1873,13 +1863,11 @@ def group_norm(x: Tensor, gamma: Tensor, beta: Tensor, groups: int, act: int = A
     return _GroupNormFn.apply(x, gamma, beta, int(groups), int(act), float(eps))
 
 
-TRUNK_FUSED = _os.environ.get("HDMOE_TRUNK_FUSED", "1") != "0"
+TRUNK_FUSED = True
 # bf16 compute mode only (the split kernels): the router trunks' BACKWARD (input + weight gradients of their convs) uses the hi halves of
 # the split operands only -- bf16 operands, fp32 accumulation, one MFMA per product instead of three.  Bit-exact routing indices need
-# the fp32-equivalent FORWARD (three products); gradients carry the bf16 mode's tolerance like every expert layer.  0: three products.
-TRUNK_BWD_BF16 = _os.environ.get("HDMOE_TRUNK_BWD_BF16", "1") != "0"
-# ... and, in that mode, as plain bf16 layers on the streaming kernels (round 4; 0: the split kernels' hi-only path, csrc/bwd6.hip bwd6s)
-TRUNK_BWD7 = _os.environ.get("HDMOE_TRUNK_BWD7", "1") != "0"
+# the fp32-equivalent FORWARD (three products); gradients carry the bf16 mode's tolerance like every expert layer.  False: three products.
+TRUNK_BWD_BF16 = True
 
 
 class _TrunkFn(torch.autograd.Function):
@@ -1944,7 +1932,7 @@ class _TrunkFn(torch.autograd.Function):
         # wgrad7_body.h) -- the GroupNorm backward writes dy_l in bf16, a small pass materialises the conv input relu(gn(y_{l-1})) in bf16
         # (the forward never stores it), and the fused dgrad + weight-gradient launch reads both by LDS-DMA.  Same arithmetic as the hi-only
         # split path (bf16 operands, fp32 accumulation) except that the input gradient between two layers is stored in bf16.
-        use7 = (TRUNK_BWD7 and TRUNK_BWD_BF16 and CONV7 and H == 32 and W == 32 and N >= C7_MINN
+        use7 = (TRUNK_BWD_BF16 and H == 32 and W == 32 and N >= C7_MINN
                 and all(int(tensors[3 * l].shape[0]) % 32 == 0 and int(tensors[3 * l].shape[1]) % 32 == 0 for l in range(3)))
         for l in (2, 1, 0):
             w, gamma, beta = tensors[3 * l:3 * l + 3]
@@ -2009,7 +1997,7 @@ class _TrunkFn(torch.autograd.Function):
 def trunk_ok(x: Tensor, convs) -> bool:
     """Can Router.hard_route take the fused path?  bf16 compute mode with split-bf16 trunks, every conv a ready weight-bank entry inside the
     split kernels' domain, and the deferred weight-gradient path on."""
-    if not (TRUNK_FUSED and ROUTER_SPLIT and BWD6 and W6_DEFER and _prof_ok() and _bank.ACTIVE is not None):
+    if not (TRUNK_FUSED and _prof_ok() and _bank.ACTIVE is not None):
         return False
     if x.dtype != torch.float32 or x.ndim != 4:
         return False

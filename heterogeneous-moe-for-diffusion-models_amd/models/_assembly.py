@@ -24,8 +24,8 @@ Tensor = torch.Tensor
 
 
 # ViT experts as one routed bank over ragged token rows (one launch per layer for all experts; csrc/ragged.hip).
-# HDMOE_VIT_BANK=0: every expert on the whole batch on its own side stream (the round-1 path, kept for A/B timing).
-VIT_BANK = __import__("os").environ.get("HDMOE_VIT_BANK", "1") != "0"
+# False: every expert on the whole batch on its own side stream (the round-1 path; tests compare the two).
+VIT_BANK = True
 
 
 def _dispatch_nhwc(x: Tensor, experts: nn.ModuleList, out_router: Tensor, time_emb: Tensor, text2d: Optional[Tensor],
@@ -234,7 +234,7 @@ class _HDMOEMBase(nn.Module):
                 (te_r, te_b), (in_r, in_b) = ops.fanout(te_u, 2), ops.fanout(in_u, 2)
                 w_unet, p_unet, raw_unet, _ = self.Unet_router._fwd(in_r, te_r, Unet_router_mask, zeta)
                 out_u = _dispatch_nhwc(ops.cast(in_b, cdt), self.Unet_experts, w_unet, te_b, text2d, kcap=self.top_k)
-            split_vr = st.SPLIT_ROUTER and st.SPLIT_VROUTER
+            split_vr = st.SPLIT_ROUTER
             te_v, in_v = st.cut("vit", pre=(te, in_vit))
             if split_vr:
                 # one forward graph, three backward sections (hdmoe_hip/graph.py SPLIT_VROUTER): the router sees its own leaves of the stem

@@ -81,7 +81,7 @@ class Router(nn.Module):
         # keep the exact fp32-input MFMA -- the trunk's GroupNorm + ReLU turns even 1e-5 perturbations into mask flips that show
         # in the trunk gradients at the fp32 tests' 3e-4 tolerance.
         import hdmoe_hip
-        split = ops.ROUTER_SPLIT and hdmoe_hip.compute_dtype() == torch.bfloat16
+        split = hdmoe_hip.compute_dtype() == torch.bfloat16
         pooled = None
         convs = [hr[0].weights, hr[3].weights, hr[6].weights]
         if split and ops.trunk_ok(x, convs):
@@ -226,7 +226,7 @@ def unet_expert_bank_forward(experts: Sequence["Unet_expert"], x: Tensor, time_e
     skips = []
     bi = 0
     top = next(iter(e0.encoders.keys())).split("_")[0]          # "32x32": the full-resolution level
-    cut_on = stager is not None and getattr(stager, "SPLIT_UNET_BWD", False) and len(e0.block_channels) > 1
+    cut_on = stager is not None and len(e0.block_channels) > 1
 
     def cut(k):
         # boundary k between two backward sections: everything alive here becomes a leaf (tensors that already are leaves stay)

@@ -156,7 +156,7 @@ def timeit(N, R, Cin, Cout, ks, iters=20):
 
 
 def time_wgrad(N, R, Cin, Cout, ks, iters=10):
-    """Kernel time of the weight gradient (graph replay): wgrad6 + reduce vs the general kernel (HDMOE_WGRAD6=0 in another process)."""
+    """Kernel time of the weight gradient (graph replay): wgrad6 + reduce (the general kernel: a checkout without wgrad6, tools/ab_trees.sh)."""
     from hdmoe_hip._lib import call
     x = torch.randn(N, R, R, Cin, device=dev).bfloat16()
     dy = torch.randn(N, R, R, Cout, device=dev).bfloat16()

@@ -1,5 +1,5 @@
 """Isolated timing (graph replay) of the router-trunk GroupNorm backward with bf16 gradient tensors (hdmoe_gn1t_bwd) and of the bf16 activation
-pass (hdmoe_gn1t_act) at the BASELINE configs[1] trunk shapes.   [HDMOE_GN1T_W=4|8] [HDMOE_GNB_GRID=n] python tools/gn1t_bench.py"""
+pass (hdmoe_gn1t_act) at the BASELINE configs[1] trunk shapes.   python tools/gn1t_bench.py  (variants: tools/ab_trees.sh on two checkouts)"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "heterogeneous-moe-for-diffusion-models_amd"), ROOT]

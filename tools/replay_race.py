@@ -1,9 +1,13 @@
 """Race detector for the staged replay when the host runs ahead of the device: the setup of tests/test_bench_path_parity.py (wide_config1, bf16, train
 mode, p = 0 -- deterministic), `bursts` times `burst` replays back to back, after each burst the error of the router logits against the reference fixture
-(8.5e-5 / 4.6e-5 when all is well).  This is how the transient under prioritised streams was found and localised (hdmoe_hip/graph.py StagedStep, with
-HDMOE_STREAM_PRIO=1 and HDMOE_SKIP_STAGE=...).  usage: replay_race.py [eager tests first 0|1] [burst 3] [bursts 150]"""
+(8.5e-5 / 4.6e-5 when all is well).  This is how the transient under prioritised streams was found and localised (hdmoe_hip/graph.py StagedStep,
+priorities=True, skip=(sections)).  usage: replay_race.py [eager tests first 0|1] [burst 3] [bursts 150] [--prio] [--skip=stage,stage,...]"""
 import os
 import sys
+
+prio = "--prio" in sys.argv
+skip = tuple(s_ for a_ in sys.argv if a_.startswith("--skip=") for s_ in a_[len("--skip="):].split(",") if s_)
+sys.argv = [a_ for a_ in sys.argv if a_ != "--prio" and not a_.startswith("--skip=")]
 
 import torch
 
@@ -40,7 +44,7 @@ def fwd_bwd():
     return loss["loss"].detach()
 
 
-staged = hgraph.StagedStep(fwd_bwd, "cuda", warmup=2)
+staged = hgraph.StagedStep(fwd_bwd, "cuda", warmup=2, priorities=prio, skip=skip)
 errs = []
 burst = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 for it in range(int(sys.argv[3]) if len(sys.argv) > 3 else 12):

@@ -1,6 +1,6 @@
 """Evidence for the router-trunk backward precision default: the same 300-step training run at BASELINE configs[1]
 (model_config1, 4x32x32 latents, 4 experts top-2, B = 256, bf16 experts, train mode, reference optimizer groups / LRs) twice from the
-same seeds -- trunk backward with bf16 operands (HDMOE_TRUNK_BWD_BF16=1, one MFMA per product) vs the three-product fp32-equivalent
+same seeds -- trunk backward with bf16 operands (ops.TRUNK_BWD_BF16 = True, one MFMA per product) vs the three-product fp32-equivalent
 arithmetic -- logging loss, denoising loss, router entropy and expert usage.  Writes a JSON with both curves.
 
     python tools/trunk_precision_run.py profiles/r03_trunk_bwd_precision.json [steps]
