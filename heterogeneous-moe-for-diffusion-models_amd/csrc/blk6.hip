@@ -1,8 +1,6 @@
 // K3 + K4 fused: the main branch of a Unet_block as ONE persistent launch for all experts of a layer (reference
 // models/model_components.py:240-253):
-//     conv_res1 (k x k) -> * (1 + emb_layer(e) * gain) -> mp_silu -> F.dropout -> conv_res2 (k x k) -> mp_sum with the residual
-// and, with the flipped weight images, its input-gradient chain
-//     dgrad(conv_res2) -> dropout / mp_silu / FiLM backward -> dgrad(conv_res1).
+//     conv_res1 (k x k) -> * (1 + emb_layer(e) * gain) -> mp_silu -> F.dropout -> conv_res2 (k x k) -> mp_sum with the residual.
 //
 // Why: at this model's widths (32 / 64 channels on 32x32 / 16x16 latents) a k x k layer is 10-20 GFLOP and 67 MB -- below the bf16 ridge and
 // a handful of work units per CU, so the three launches of a block (conv6, film_silu, conv6) are dominated by their fixed costs and by the
@@ -26,9 +24,9 @@
 
 namespace {
 
-template <int NW, int NTM, int NTB, int MODE>
+template <int NW, int NTM, int NTB>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void blk6_kernel(B6Args a) {
-  blk6_body<NW, NTM, NTB, MODE>(a, blockIdx.x, gridDim.x);
+  blk6_body<NW, NTM, NTB>(a, blockIdx.x, gridDim.x);
 }
 
 struct B6Plan { B6Args a; int NW, NTM, NTB; unsigned G; size_t lds; };
@@ -101,15 +99,14 @@ int blk6_plan(const void* x, const void* wa, const void* wb, void* y, const void
   return 0;
 }
 
-template <int MODE>
 int blk6_launch(const B6Plan& plan, hipStream_t stream) {
   static unsigned long long attr_set = 0;
   if (hdmoe_first_on_device(attr_set)) {
-#define B6_ATTR(W, M, B, L) (void)hipFuncSetAttribute((const void*)blk6_kernel<W, M, B, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, L * 1024)
+#define B6_ATTR(W, M, B, L) (void)hipFuncSetAttribute((const void*)blk6_kernel<W, M, B>, hipFuncAttributeMaxDynamicSharedMemorySize, L * 1024)
     B6_ATTR(8, 1, 1, 160); B6_ATTR(8, 1, 2, 160); B6_ATTR(8, 2, 1, 160); B6_ATTR(8, 2, 2, 160);
     B6_ATTR(4, 1, 1, 80); B6_ATTR(4, 1, 2, 80); B6_ATTR(4, 2, 1, 80); B6_ATTR(4, 2, 2, 80);
   }
-#define B6_LAUNCH(W, M, B) hipLaunchKernelGGL((blk6_kernel<W, M, B, MODE>), dim3(plan.G), dim3(64 * W), plan.lds, stream, plan.a)
+#define B6_LAUNCH(W, M, B) hipLaunchKernelGGL((blk6_kernel<W, M, B>), dim3(plan.G), dim3(64 * W), plan.lds, stream, plan.a)
 #define B6_GO(W)                                                                                  \
   do {                                                                                            \
     if (plan.NTM == 2) { if (plan.NTB == 2) B6_LAUNCH(W, 2, 2); else B6_LAUNCH(W, 2, 1); }       \
@@ -147,28 +144,7 @@ int hdmoe_unet_block_fwd(const void* x, const void* w1, const void* w2, void* u,
   B6Args& a = plan.a;
   a.alpha = alpha; a.beta = beta; a.alpha_mid = 1.f; a.mode = 0; a.e = e; a.u = u; a.hmid = h; a.de = nullptr;
   a.seed_dev = seed_dev; a.seed_lo = (unsigned)seed; a.seed_hi = (unsigned)(seed >> 32); a.p = p;
-  return blk6_launch<0>(plan, stream);
-}
-
-/* Input-gradient chain of the same branch:
- *   dh = dgrad(dy, wd2)  (never written),   du = dropout / mp_silu / FiLM backward of dh   [N][H][W][C] (written: conv_res1's weight gradient),
- *   de [N][C] += sum_pixels d/de,           dx = alpha * dgrad(du, wd1)                    [N][H][W][Cin]
- * wd2 [g][tap][C][C], wd1 [g][tap][Cin][C]: flipped dgrad weight images; u: the pre-activation saved by the forward.  The two weight
- * gradients (x with du, h with dy) stay with hdmoe_conv_wgrad6. */
-int hdmoe_unet_block_bwd(const void* dy, const void* wd2, const void* wd1, const void* u, void* du, void* dx, float* de, const float* e,
-                         unsigned long long seed, const unsigned long long* seed_dev, float p, float alpha, float alpha_mid, const int* seg,
-                         int ngroups, long wd2stride, long wd1stride, int N, int H, int W, int Cin, int C, const int* kh, int dtype,
-                         hipStream_t stream) {
-  if (!dy || !wd2 || !wd1 || !u || !du || !dx || !e || N < 0 || p < 0.f || p >= 1.f) return HDMOE_EINVAL;
-  if (dtype != HDMOE_BF16) return 1;
-  if (((uintptr_t)u | (uintptr_t)du) & 15) return 1;
-  if (N == 0) return HDMOE_OK;
-  B6Plan plan;
-  if (blk6_plan(dy, wd2, wd1, dx, nullptr, seg, ngroups, wd2stride, wd1stride, N, H, W, C, C, Cin, kh, plan)) return 1;
-  B6Args& a = plan.a;
-  a.alpha = alpha; a.beta = 0.f; a.alpha_mid = alpha_mid; a.mode = 1; a.e = e; a.u = const_cast<void*>(u); a.hmid = du; a.de = de;
-  a.seed_dev = seed_dev; a.seed_lo = (unsigned)seed; a.seed_hi = (unsigned)(seed >> 32); a.p = p;
-  return blk6_launch<1>(plan, stream);
+  return blk6_launch(plan, stream);
 }
 
 }  // extern "C"

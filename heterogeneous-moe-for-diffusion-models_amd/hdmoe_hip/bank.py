@@ -285,9 +285,12 @@ class WeightBank:
             self._cb_queued = True
             torch.autograd.Variable._execution_engine.queue_callback(self._finish)
 
-    def defer_w6(self, Gs, seg, ws, dims):
-        """A k x k layer left its partial weight-gradient slabs in `ws` (ops._wgrad): summed in _finish / finish_stage."""
-        self._w6_pending.append((Gs, seg, ws, dims, STAGE if DEFER_FINISH else None))
+    def defer_w6(self, Gs, seg, ws, G, N, H, W, I, O, dtc, khs, ent: Optional[Entry] = None):
+        """A k x k layer (G groups of N images, H x W, I -> O channels, dtype code ``dtc``, kernel sizes ``khs``) left its partial
+        weight-gradient slabs for ``Gs`` in ``ws``: summed in _finish / finish_stage.  ``ent``: also `note_backward(ent)`."""
+        self._w6_pending.append((list(Gs), seg, ws, w6_record(G, N, H, W, I, O, dtc, khs), STAGE if DEFER_FINISH else None))
+        if ent is not None:
+            self.note_backward(ent)
 
     def _reduce_w6(self, stage):
         pend = [it for it in getattr(self, "_w6_pending", []) if stage is None or it[4] == stage]
@@ -296,7 +299,7 @@ class WeightBank:
         self._w6_pending = [it for it in self._w6_pending if not (stage is None or it[4] == stage)]
         Gflat, segs, wss, dims = [], [], [], []                # one launch per 16 (layer, kernel-size class) items
         for Gs, seg, ws, d, _ in pend:
-            Gflat += list(Gs) + [None] * (8 - len(Gs))
+            Gflat += Gs + [None] * (8 - len(Gs))
             segs.append(seg); wss.append(ws); dims += d
         call("hdmoe_conv_wgrad6_reduce_batch", Gflat, segs, wss, dims, len(pend))
 
@@ -335,6 +338,11 @@ class WeightBank:
                 call("hdmoe_wbank_bwd", self._descs, rows, rows.shape[0])
             return
         call("hdmoe_wbank_bwd", self._descs, self._rows, self._nrows)
+
+
+def w6_record(G, N, H, W, I, O, dtc, khs) -> List[int]:
+    """The 16-int layer record of hdmoe_conv_wgrad6_reduce_batch: {G, N, H, W, I, O, dtype, 0, kh[0..7]}."""
+    return [G, N, H, W, I, O, dtc, 0] + [int(k) for k in khs] + [0] * (8 - len(khs))
 
 
 def bank_for(module: torch.nn.Module) -> WeightBank:

@@ -7,6 +7,7 @@ token ``(N, S, C)`` or matrix ``(M, C)`` -- in float32 or bfloat16.  "Vector pat
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import List, Optional, Sequence
 
@@ -14,7 +15,7 @@ import torch
 
 from . import bank as _bank
 from ._lib import dtype_code_cast  # noqa: F401
-from ._lib import call, dtype_code
+from ._lib import _int_array, call, dtype_code, lib
 
 Tensor = torch.Tensor
 
@@ -197,8 +198,6 @@ def _kernel_hw(w: Tensor):
     raise ValueError(f"weight must be 2-D or 4-D, got {tuple(w.shape)}")
 
 
-_w6_ws = {}
-
 # Small learnable tensors (norm affines, biases, rel_pos_bias, alpha_txt): when the parameter already owns a gradient buffer (the
 # flat DP buckets, or a .grad kept from the previous step) the backward kernels -- which accumulate anyway -- add straight into it
 # and hand autograd None.  That is what the weight bank does for the conv weights; per step it removes a zero-fill and an
@@ -348,14 +347,57 @@ def w6_arena_reset(device) -> None:
         a.rewind()
 
 
-def _w6_arena_take(device, nfloats):
-    device = torch.device(device)
-    a = _w6_arenas.get(device)
-    if a is None:
-        if torch.cuda.is_current_stream_capturing():
+_w6_ws = {}
+
+
+def _w6_kib(G, N, H, W, I, O, khs, kws, dtc) -> int:
+    """KiB of partial weight-gradient slabs a wgrad6-reduced launch of this layer needs (csrc/wgrad6.hip); 0 outside its domain."""
+    return lib().hdmoe_conv_wgrad6_ws_kib(G, N, H, W, I, O, ctypes.cast(_int_array(khs), ctypes.c_void_p),
+                                          ctypes.cast(_int_array(kws), ctypes.c_void_p), dtc)
+
+
+def _w6_workspace(policy, device, kib):
+    """fp32 workspace of a wgrad6-reduced launch that needs ``kib`` KiB (none when kib == 0):
+      "arena"  -- 2 * kib KiB of the deferred arena (the partial slabs stay there for the bank's batched reduction), else None;
+      "stream" -- the per-(device, stream) cached buffer of an in-launch reduction (branches on different streams run concurrently;
+                  grown outside graph capture, i.e. in the warm-up steps);
+      "own"    -- the arena, else a buffer of its own outside a graph capture (the arena grows at the next step), else RuntimeError."""
+    if policy == "stream":
+        if kib <= 0:
             return None
-        a = _w6_arenas[device] = _W6Arena(device)
-    return a.take(nfloats)
+        key = (device, torch.cuda.current_stream().stream_id)
+        ws = _w6_ws.get(key)
+        if ws is None or ws.numel() < kib * 256:
+            ws = _w6_ws[key] = torch.empty(kib * 256, dtype=torch.float32, device=device)
+        return ws
+    ws = None
+    if kib > 0:
+        arena = _w6_arenas.get(device)
+        if arena is None and not torch.cuda.is_current_stream_capturing():
+            arena = _w6_arenas[device] = _W6Arena(device)
+        ws = arena.take(2 * kib * 256) if arena is not None else None
+    if ws is None and policy == "own":
+        if kib > 0 and not torch.cuda.is_current_stream_capturing():
+            return torch.empty(2 * kib * 256, dtype=torch.float32, device=device)
+        raise RuntimeError("router trunk backward: no weight-gradient workspace (arena exhausted inside a graph capture)")
+    return ws
+
+
+def _fused_bwd(bank, ent, label, name, x, dy, wd, dx, mid, ws, tail, defer, stats) -> bool:
+    """One launch for the input gradient (into ``dx``) and the weight gradient of weight-bank layer ``ent``:
+    ``name(x, dy, wd, dx, ent.G, *mid, ws, ws bytes, *tail)``.  On success ``defer`` = (seg, G, N, H, W, I, O, dtype code, khs)
+    leaves the partial slabs in ``ws`` to the bank's batched reduction, the layer is noted for the bank's finish and the ``stats``
+    keys are counted.  False: the layer is outside the launch's domain (nothing was launched)."""
+    if _timed("fused", label, name, x, dy, wd, dx, list(ent.G), *mid, ws, ws.numel() * 4, *tail) != 0:
+        return False
+    if defer is not None:
+        seg, *shape = defer
+        bank.defer_w6(ent.G, seg, ws, *shape, ent=ent)
+    else:
+        bank.note_backward(ent)
+    for k in stats:
+        STATS[k] += 1
+    return True
 
 
 def _wgrad(info, x, dy, Gs, seg, G, N, H, W, Ho, Wo, I, Cphys, O, ones, khs, kws, pts, split=False, bank=None):
@@ -363,26 +405,18 @@ def _wgrad(info, x, dy, Gs, seg, G, N, H, W, Ho, Wo, I, Cphys, O, ones, khs, kws
     split-bf16 mode (the router trunks) -- take the atomic-free kernel (csrc/wgrad6.hip) with a cached workspace; everything else
     the general kernel."""
     if (x.dtype == torch.bfloat16 or split) and not ones and Ho == H and Wo == W and Cphys == I:
-        from ._lib import lib, _int_array
-        import ctypes
         dtc = F32S if split else _dt(x)
-        kib = lib().hdmoe_conv_wgrad6_ws_kib(G, N, H, W, I, O, ctypes.cast(_int_array(khs), ctypes.c_void_p),
-                                             ctypes.cast(_int_array(kws), ctypes.c_void_p), dtc)
-        if kib > 0 and bank is not None and _prof_ok():
-            # weight-bank layer: the partial slabs stay in the arena, the bank sums all layers' partials in one batched launch
-            ws = _w6_arena_take(x.device, 2 * kib * 256)
-            if ws is not None:
-                if _timed("conv_wgrad", dict(info, dtype="split_bf16" if split else info.get("dtype"), wgrad_name="wgrad6_kernel<split> (deferred reduce)" if split else "wgrad6_kernel (deferred reduce)"),
-                          "hdmoe_conv_wgrad6", x, dy, Gs, seg, G, N, H, W, I, O, khs, kws, pts, pts, ws, ws.numel() * 4, dtc, 1) == 0:
-                    bank.defer_w6(list(Gs), seg, ws, [G, N, H, W, I, O, dtc, 0] + [int(k) for k in khs] + [0] * (8 - len(khs)))
-                    STATS["w6_defer"] += 1
-                    return
-        if kib > 0:
-            key = (x.device, torch.cuda.current_stream().stream_id)       # branches on different streams run concurrently
-            ws = _w6_ws.get(key)
-            if ws is None or ws.numel() < kib * 256:
-                ws = torch.empty(kib * 256, dtype=torch.float32, device=x.device)      # fp32 words; grown outside graph capture (warm-up steps)
-                _w6_ws[key] = ws
+        kib = _w6_kib(G, N, H, W, I, O, khs, kws, dtc)
+        # weight-bank layer: the partial slabs stay in the arena, the bank sums all layers' partials in one batched launch
+        ws = _w6_workspace("arena", x.device, kib) if bank is not None and _prof_ok() else None
+        if ws is not None:
+            if _timed("conv_wgrad", dict(info, dtype="split_bf16" if split else info.get("dtype"), wgrad_name="wgrad6_kernel<split> (deferred reduce)" if split else "wgrad6_kernel (deferred reduce)"),
+                      "hdmoe_conv_wgrad6", x, dy, Gs, seg, G, N, H, W, I, O, khs, kws, pts, pts, ws, ws.numel() * 4, dtc, 1) == 0:
+                bank.defer_w6(Gs, seg, ws, G, N, H, W, I, O, dtc, khs)
+                STATS["w6_defer"] += 1
+                return
+        ws = _w6_workspace("stream", x.device, kib)
+        if ws is not None:
             if split:
                 info = dict(info, dtype="split_bf16")
             if _timed("conv_wgrad", info, "hdmoe_conv_wgrad6", x, dy, Gs, seg, G, N, H, W, I, O, khs, kws, pts, pts, ws, ws.numel() * 4, dtc, 0) == 0:
@@ -478,75 +512,43 @@ class _MPConvFn(torch.autograd.Function):
         nig = ctx.needs_input_grad
         need_gain = gains is not None and any(nig[4 + G + g] for g in range(G))
         need_w = any(nig[4 + g] for g in range(G)) or need_gain
-        fused = False
-        if (nig[0] and need_w and ctx.ent is not None and _prof_ok() and x.dtype == torch.bfloat16 and not split
-                and not ones and Ho == H and Wo == W and Cphys == I and set(khs) == {3, 5} and khs == kws):
-            # input gradient + (deferred) weight gradient of a 3x3 / 5x5 expert layer in one launch (csrc/bwd6.hip)
-            from ._lib import lib, _int_array
-            import ctypes
-            kib = lib().hdmoe_conv_wgrad6_ws_kib(G, N, H, W, I, O, ctypes.cast(_int_array(khs), ctypes.c_void_p),
-                                                 ctypes.cast(_int_array(kws), ctypes.c_void_p), _dt(x))
-            ws = _w6_arena_take(x.device, 2 * kib * 256) if kib > 0 else None
+        Opad = (O + 15) // 16 * 16
+        wdstride = max(a * b for a, b in zip(khs, kws)) * I * Opad
+        ent, fused = ctx.ent, False
+        if need_w and ent is not None:
+            # the input gradient and the weight gradient of a weight-bank layer in one launch (a launch outside its domain returns non-zero:
+            # the layer then takes the general path below)
+            conv6 = nig[0] and _prof_ok() and not ones and Ho == H and Wo == W and Cphys == I and khs == kws
+            if conv6 and not split and x.dtype == torch.bfloat16 and set(khs) == {3, 5}:
+                fast, dtc, policy = "bwd6", _dt(x), "arena"           # 3x3 / 5x5 expert layer, deferred weight gradient (csrc/bwd6.hip)
+            elif conv6 and split and set(khs) == {3}:
+                fast, dtc, policy = "bwd6s", F32S, "arena"            # the same for a router-trunk layer (fp32 tensors, split-bf16 arithmetic)
+            elif ctx.ones6:
+                # the ones-channel layer: dgrad on conv6, weight gradient on wgrad6 + pixel sums of dy (csrc/ones6.hip)
+                fast, dtc, policy = "ones6", _dt(x), "stream"
+            else:
+                fast = None
+            ws = _w6_workspace(policy, x.device, _w6_kib(G, N, H, W, Cphys, O, khs, kws, dtc)) if fast else None
             if ws is not None:
-                dx = torch.empty_like(x)
-                Opad = (O + 15) // 16 * 16
-                wdstride = max(a * b for a, b in zip(khs, kws)) * I * Opad
-                if _timed("fused", dict(name="bwd6_kernel", dtype="bfloat16", seg=seg, N=N, HW=H * W, O=O, I=I, taps=[a * b for a, b in zip(khs, kws)], mult=2.0),
-                          "hdmoe_conv_bwd6", x, dy, ctx.wd, dx, list(ctx.ent.G), seg, G, wdstride, N, H, W, I, O, khs, kws, pts, pts, alpha,
-                          ws, ws.numel() * 4, _dt(x)) == 0:
-                    ctx.bank.defer_w6(list(ctx.ent.G), seg, ws, [G, N, H, W, I, O, _dt(x), 0] + [int(k) for k in khs] + [0] * (8 - len(khs)))
-                    ctx.bank.note_backward(ctx.ent)
-                    fused = True
-                    STATS["bwd6"] += 1
+                info = dict(seg=seg, N=N, HW=H * W, O=O, I=Cphys, taps=[a * b for a, b in zip(khs, kws)], mult=2.0 if nig[0] else 1.0)
+                defer, stats = (seg, G, N, H, W, I, O, dtc, khs), (fast,)
+                if fast == "bwd6":
+                    label = dict(name="bwd6_kernel", dtype="bfloat16", **info)
+                    name, mid, tail = "hdmoe_conv_bwd6", (seg, G, wdstride, N, H, W, I, O, khs, kws, pts, pts, alpha), (dtc,)
+                elif fast == "bwd6s":
+                    label = dict(name="bwd6s_kernel", dtype="bfloat16" if TRUNK_BWD_BF16 else "split_bf16", **info)
+                    name, mid = "hdmoe_conv_bwd6s", (seg, G, wdstride, G * wdstride, N, H, W, I, O, khs, kws, pts, pts, alpha)
+                    tail = (None, None, 0, 1 if TRUNK_BWD_BF16 else 0)
                 else:
-                    dx = None
-        if (nig[0] and need_w and ctx.ent is not None and _prof_ok() and split and not ones and Ho == H and Wo == W
-                and Cphys == I and set(khs) == {3} and khs == kws):
-            # the same for a router-trunk layer (fp32 tensors, split-bf16 arithmetic)
-            from ._lib import lib, _int_array
-            import ctypes
-            kib = lib().hdmoe_conv_wgrad6_ws_kib(G, N, H, W, I, O, ctypes.cast(_int_array(khs), ctypes.c_void_p),
-                                                 ctypes.cast(_int_array(kws), ctypes.c_void_p), F32S)
-            ws = _w6_arena_take(x.device, 2 * kib * 256) if kib > 0 else None
-            if ws is not None:
-                dx = torch.empty_like(x)
-                Opad = (O + 15) // 16 * 16
-                wdstride = 9 * I * Opad
-                if _timed("fused", dict(name="bwd6s_kernel", dtype="bfloat16" if TRUNK_BWD_BF16 else "split_bf16", seg=seg, N=N, HW=H * W, O=O, I=I, taps=[9] * G, mult=2.0),
-                          "hdmoe_conv_bwd6s", x, dy, ctx.wd, dx, list(ctx.ent.G), seg, G, wdstride, G * wdstride, N, H, W, I, O, khs, kws, pts, pts,
-                          alpha, ws, ws.numel() * 4, None, None, 0, 1 if TRUNK_BWD_BF16 else 0) == 0:
-                    ctx.bank.defer_w6(list(ctx.ent.G), seg, ws, [G, N, H, W, I, O, F32S, 0] + [int(k) for k in khs] + [0] * (8 - len(khs)))
-                    ctx.bank.note_backward(ctx.ent)
-                    fused = True
-                    STATS["bwd6s"] += 1
-                else:
-                    dx = None
-        if ctx.ones6 and need_w and ctx.ent is not None:
-            # the ones-channel layer: dgrad on conv6, weight gradient on wgrad6 + pixel sums of dy (csrc/ones6.hip)
-            from ._lib import lib, _int_array
-            import ctypes
-            kib = lib().hdmoe_conv_wgrad6_ws_kib(G, N, H, W, Cphys, O, ctypes.cast(_int_array(khs), ctypes.c_void_p),
-                                                 ctypes.cast(_int_array(kws), ctypes.c_void_p), _dt(x))
-            if kib > 0:
-                key = (x.device, torch.cuda.current_stream().stream_id)
-                ws = _w6_ws.get(key)
-                if ws is None or ws.numel() < kib * 256:
-                    ws = torch.empty(kib * 256, dtype=torch.float32, device=x.device)
-                    _w6_ws[key] = ws
-                S = torch.empty((G, H, W, O), dtype=torch.float32, device=x.device)
-                g32 = [_zeros((kh * kw, O, Cphys), torch.float32, x.device) for kh, kw in zip(khs, kws)]
+                    label = dict(name="conv6 dgrad + wgrad6 (ones-channel layer)", dtype="bfloat16", **info)
+                    S = torch.empty((G, H, W, O), dtype=torch.float32, device=x.device)
+                    g32 = [_zeros((kh * kw, O, Cphys), torch.float32, x.device) for kh, kw in zip(khs, kws)]
+                    name, mid, tail = "hdmoe_conv6_ones_bwd", (S, g32, seg, G, wdstride, N, H, W, Cphys, O, Opad, khs, alpha), (dtc,)
+                    defer, stats = None, ()                   # (reduced inside the launch, into the bank's slabs)
                 dxo = torch.empty_like(x) if nig[0] else None
-                Opad = (O + 15) // 16 * 16
-                wdstride = max(a * b for a, b in zip(khs, kws)) * I * Opad
-                if _timed("fused", dict(name="conv6 dgrad + wgrad6 (ones-channel layer)", dtype="bfloat16", seg=seg, N=N, HW=H * W, O=O, I=Cphys, taps=[a * b for a, b in zip(khs, kws)], mult=2.0 if nig[0] else 1.0),
-                          "hdmoe_conv6_ones_bwd", x, dy, ctx.wd, dxo, list(ctx.ent.G), S, g32, seg, G, wdstride, N, H, W, Cphys, O, Opad, khs, alpha,
-                          ws, ws.numel() * 4, _dt(x)) == 0:
-                    dx = dxo
-                    ctx.bank.note_backward(ctx.ent)
-                    fused = True
+                fused = _fused_bwd(ctx.bank, ent, label, name, x, dy, ctx.wd, dxo, mid, ws, tail, defer, stats)
+                dx = dxo if fused else None
         if nig[0] and not fused:
-            Opad = (O + 15) // 16 * 16
-            wdstride = max(a * b for a, b in zip(khs, kws)) * I * Opad
             wd = ctx.wd
             dx = torch.empty_like(x)
             pt_d = [kh - 1 - p for kh, p in zip(khs, pts)]
@@ -1881,7 +1883,6 @@ class _TrunkFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, ents, bank, eps, *tensors):
-        from ._lib import lib
         x = _c(x)
         N, H, W, _ = x.shape
         S = H * W
@@ -1917,8 +1918,6 @@ class _TrunkFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from ._lib import lib, _int_array
-        import ctypes
         x, *rest = ctx.saved_tensors
         saved, tensors = rest[:15], rest[15:]
         N, H, W, _ = x.shape
@@ -1926,7 +1925,6 @@ class _TrunkFn(torch.autograd.Function):
         ents, bank = ctx.ents, ctx.bank
         params = [t for l in range(3) for t in tensors[3 * l + 1:3 * l + 3]]
         bufs, ret = _param_grads(params)
-        k3 = ctypes.cast(_int_array([3]), ctypes.c_void_p)
         da = None
         # bf16-operand mode on 32 x 32 maps with enough samples: the trunk backward as PLAIN bf16 layers on the streaming kernels (csrc/conv7_body.h,
         # wgrad7_body.h) -- the GroupNorm backward writes dy_l in bf16, a small pass materialises the conv input relu(gn(y_{l-1})) in bf16
@@ -1949,21 +1947,12 @@ class _TrunkFn(torch.autograd.Function):
                      1.0 / S if l == 2 else 1.0, y, gamma, beta, mean, rstd, N, S, O)
                 a_in = torch.empty(xin.shape, dtype=torch.bfloat16, device=x.device)
                 call("hdmoe_gn1t_act", a_in, xin, isc, ish, N, S, I)
-                kib = lib().hdmoe_conv_wgrad6_ws_kib(1, N, H, W, I, O, k3, k3, 1)
-                arena = _w6_arena_take(x.device, 2 * kib * 256) if kib > 0 else None
-                if arena is None and kib > 0 and not torch.cuda.is_current_stream_capturing():
-                    arena = torch.empty(2 * kib * 256, dtype=torch.float32, device=x.device)
-                if arena is None:
-                    raise RuntimeError("router trunk backward: no weight-gradient workspace (arena exhausted inside a graph capture)")
+                arena = _w6_workspace("own", x.device, _w6_kib(1, N, H, W, I, O, [3], [3], 1))
                 da = torch.empty(xin.shape, dtype=torch.bfloat16, device=x.device)
-                if _timed("fused", dict(name="bwd7_trunk_kernel", dtype="bfloat16", seg=None, N=N, HW=S, O=O, I=I, taps=[9], mult=2.0),
-                          "hdmoe_conv_bwd6", a_in, dyb, ent.wd, da, list(ent.G), None, 1, wdstride, N, H, W, I, O, [3], [3], [1], [1], 1.0,
-                          arena, arena.numel() * 4, 1) != 0:
+                if not _fused_bwd(bank, ent, dict(name="bwd7_trunk_kernel", dtype="bfloat16", seg=None, N=N, HW=S, O=O, I=I, taps=[9], mult=2.0),
+                                  "hdmoe_conv_bwd6", a_in, dyb, ent.wd, da, (None, 1, wdstride, N, H, W, I, O, [3], [3], [1], [1], 1.0), arena, (1,),
+                                  (None, 1, N, H, W, I, O, 1, [3]), ("trunk_bwd", "trunk_bwd7")):
                     raise RuntimeError("router trunk backward: layer outside the streaming backward kernels' domain")
-                bank.defer_w6(list(ent.G), None, arena, [1, N, H, W, I, O, 1, 0, 3, 0, 0, 0, 0, 0, 0, 0])
-                bank.note_backward(ent)
-                STATS["trunk_bwd"] += 1
-                STATS["trunk_bwd7"] += 1
                 if l == 0:                                     # the stem features are fp32: so is their gradient
                     da32 = torch.empty(xin.shape, dtype=torch.float32, device=x.device)
                     call("hdmoe_cast", da32, da, da.numel(), 1, 0)
@@ -1974,20 +1963,12 @@ class _TrunkFn(torch.autograd.Function):
                 call("hdmoe_groupnorm_bwd_bcast", dy, bufs[2 * l], bufs[2 * l + 1], ws, _f32(g), 1.0 / S, y, gamma, beta, mean, rstd, N, S, O, 1, ACT_RELU, 0)
             else:
                 call("hdmoe_groupnorm_bwd", dy, bufs[2 * l], bufs[2 * l + 1], ws, da, y, gamma, beta, mean, rstd, N, S, O, 1, ACT_RELU, 0)
-            kib = lib().hdmoe_conv_wgrad6_ws_kib(1, N, H, W, I, O, k3, k3, F32S)
-            arena = _w6_arena_take(x.device, 2 * kib * 256) if kib > 0 else None
-            if arena is None and kib > 0 and not torch.cuda.is_current_stream_capturing():
-                arena = torch.empty(2 * kib * 256, dtype=torch.float32, device=x.device)      # arena exhausted (it grows at the next step): own slabs
-            if arena is None:
-                raise RuntimeError("router trunk backward: no weight-gradient workspace (arena exhausted inside a graph capture)")
+            arena = _w6_workspace("own", x.device, _w6_kib(1, N, H, W, I, O, [3], [3], F32S))
             da = torch.empty_like(xin)
-            if _timed("fused", dict(name="bwd6s_kernel", dtype="bfloat16" if TRUNK_BWD_BF16 else "split_bf16", seg=None, N=N, HW=S, O=O, I=I, taps=[9], mult=2.0),
-                      "hdmoe_conv_bwd6s", xin, dy, ent.wd, da, list(ent.G), None, 1, wdstride, wdstride, N, H, W, I, O, [3], [3], [1], [1], 1.0,
-                      arena, arena.numel() * 4, isc, ish, 1, 1 if TRUNK_BWD_BF16 else 0) != 0:
+            if not _fused_bwd(bank, ent, dict(name="bwd6s_kernel", dtype="bfloat16" if TRUNK_BWD_BF16 else "split_bf16", seg=None, N=N, HW=S, O=O, I=I, taps=[9], mult=2.0),
+                              "hdmoe_conv_bwd6s", xin, dy, ent.wd, da, (None, 1, wdstride, wdstride, N, H, W, I, O, [3], [3], [1], [1], 1.0), arena,
+                              (isc, ish, 1, 1 if TRUNK_BWD_BF16 else 0), (None, 1, N, H, W, I, O, F32S, [3]), ("trunk_bwd",)):
                 raise RuntimeError("router trunk backward: layer outside the fused backward kernel's domain")
-            bank.defer_w6(list(ent.G), None, arena, [1, N, H, W, I, O, F32S, 0, 3, 0, 0, 0, 0, 0, 0, 0])
-            bank.note_backward(ent)
-            STATS["trunk_bwd"] += 1
         out = [da, None, None, None]
         for l in range(3):
             out += [None, ret[2 * l], ret[2 * l + 1]]

@@ -325,22 +325,15 @@ int hdmoe_conv6_ones_bwd(const void* x, const void* dy, const void* wd, void* dx
                          int dtype, HS stream);
 
 /* ---- K3+K4 fused: Unet_block main branch as one persistent launch (csrc/blk6.hip; reference models/model_components.py:240-253) ----
- * forward:  u = conv(x, w1); h = dropout_p(mp_silu(u * e[n][c])); y = alpha * conv(h, w2) + beta * res   (u, h, y written; the
- *           activation tile stays in LDS between the two convs).  x [N][H][W][Cin], u / h / y / res [N][H][W][C] bf16, e fp32 [N][C];
- *           w1 [g][tap][C][Cin], w2 [g][tap][C][C] forward weight images; kh: per-expert square kernel size, "same" padding.
- * backward: dh = alpha_mid * dgrad(dy, wd2) (stays in LDS); du = dropout / mp_silu / FiLM backward (written); de [N][C] += ...;
- *           dx = alpha * dgrad(du, wd1).  wd2 [g][tap][C][C], wd1 [g][tap][Cin][C] flipped dgrad images; u from the forward.
- * Both return 1 without launching outside the kernel's domain (bf16, W in {16, 32}, H % (256 / W) == 0, k in {3, 5, 7},
- * Cin % 32 == 0, C in {32, 64}). */
+ * u = conv(x, w1); h = dropout_p(mp_silu(u * e[n][c])); y = alpha * conv(h, w2) + beta * res   (u, h, y written; the activation tile
+ * stays in LDS between the two convs).  x [N][H][W][Cin], u / h / y / res [N][H][W][C] bf16, e fp32 [N][C]; w1 [g][tap][C][Cin],
+ * w2 [g][tap][C][C] forward weight images; kh: per-expert square kernel size, "same" padding.  Returns 1 without launching outside
+ * the kernel's domain (bf16, W in {16, 32}, H % (256 / W) == 0, k in {3, 5, 7}, Cin % 32 == 0, C in {32, 64}). */
 int hdmoe_unet_block_fwd(const void* x, const void* w1, const void* w2, void* u, void* h, void* y, const void* res, const float* e,
                          unsigned long long seed, const unsigned long long* seed_dev, float p, float alpha, float beta, const int* seg,
                          int ngroups, long w1stride, long w2stride, int N, int H, int W, int Cin, int C, const int* kh, int dtype,
                          HS stream);
 int hdmoe_blk6_debug_stamps(void* buf);   /* development: 8 x 64 u64 device buffer for workgroup 0's in-kernel time stamps, or NULL */
-int hdmoe_unet_block_bwd(const void* dy, const void* wd2, const void* wd1, const void* u, void* du, void* dx, float* de, const float* e,
-                         unsigned long long seed, const unsigned long long* seed_dev, float p, float alpha, float alpha_mid, const int* seg,
-                         int ngroups, long wd2stride, long wd1stride, int N, int H, int W, int Cin, int C, const int* kh, int dtype,
-                         HS stream);
 
 /* ---- N3: fused multi-tensor clip_grad_norm_ + AdamW  (Utils/training.py:55-65,195-197) ----------------------------------- */
 /* descs: device array of {p, g, m, v, step, use addresses, numel, group} (hdmoe_opt_desc_bytes() bytes each); chunks: device int32 pairs

@@ -144,7 +144,7 @@ def test_bank_path_third_step_matches_the_reference(golden_wide, mode, dtype, tr
         if dtype == torch.bfloat16:                            # the kernels bench.py times ran in THIS step
             assert ops.STATS["trunk"] == 2 and ops.STATS["trunk_bwd"] == 6, dict(ops.STATS)
             if g["cfg_id"] in (1, 2):                          # 3x3 / 5x5 experts: fused dgrad + wgrad launches (7x7 layers take the separate kernels)
-                assert ops.STATS["bwd6"] + ops.STATS["blk_bwd"] >= 20, dict(ops.STATS)
+                assert ops.STATS["bwd6"] >= 20, dict(ops.STATS)
         loss_tol = 1e-3 if dtype == torch.float32 else LOSS_TOL_BF16
         torch.testing.assert_close(loss["loss"].detach().cpu(), g["loss"]["loss"], rtol=loss_tol, atol=1e-4)
         pg = {n: p.grad for n, p in model.named_parameters()}
@@ -196,7 +196,7 @@ def test_staged_train_mode_replay_matches_the_reference(golden_wide, split_route
         assert staged.split_router == split_router
         assert ops.STATS["trunk"] >= 4, dict(ops.STATS)            # warm-up step 2 and the capture ran the fused paths
         if g["cfg_id"] in (1, 2):
-            assert ops.STATS["bwd6"] + ops.STATS["blk_bwd"] >= 20, dict(ops.STATS)
+            assert ops.STATS["bwd6"] >= 20, dict(ops.STATS)
         for _ in range(3):
             l_g = staged()
         torch.cuda.synchronize()

@@ -1346,10 +1346,13 @@ def test_fused_router_trunk_matches_the_layer_by_layer_path(N, H, C, k, bwd_bf16
             sl = slice(1, 3) if mode == "fused_sub" else slice(None)
             wbank.bank_for(r).begin_step(False)
             xx = x[sl].clone().requires_grad_(True)
+            bwd6s = ops.STATS["bwd6s"]
             sw, gp, lg = r(x=xx, time_emb=te[sl], zeta=0.0)
             ((gp ** 2).sum() + (sw * 0.37).sum() + lg.sum() * 0.01).backward()
             wbank.deactivate()
             torch.cuda.synchronize()
+            if mode == "layers":                                   # each of the three convs: dgrad + deferred weight gradient in one launch
+                layers_bwd6s = ops.STATS["bwd6s"] - bwd6s
             res[mode] = (lg.detach().clone(), xx.grad.clone(), {n: p.grad.clone() for n, p in r.named_parameters() if p.grad is not None})
             r.zero_grad(set_to_none=False)
     finally:
@@ -1357,6 +1360,7 @@ def test_fused_router_trunk_matches_the_layer_by_layer_path(N, H, C, k, bwd_bf16
         ops.TRUNK_BWD_BF16 = prev_bwd
         hdmoe_hip.set_compute_dtype(prev)
     assert all(e.ready for e in r._hdmoe_bank.entries.values())
+    assert layers_bwd6s == 3, dict(ops.STATS)
     if N >= 192 and H == 32:                                       # the trunk backward ran as bf16 layers on the streaming kernels (csrc/conv7_body.h, wgrad7_body.h)
         assert ops.STATS["trunk_bwd7"] >= 3, dict(ops.STATS)
     (l0, dx0, pg0), (l1, dx1, pg1), (l2, _, _) = res["layers"], res["fused"], res["fused_sub"]

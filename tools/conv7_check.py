@@ -29,6 +29,7 @@ if "--time" in sys.argv and not any(f in sys.argv for f in ("--check-bwd", "--ti
 def _bwd_setup(N, R, Cin, Cout, ks, split, seed):
     import torch
     from hdmoe_hip._lib import call, lib, _int_array
+    from hdmoe_hip.bank import w6_record
     import ctypes
     dev = "cuda"
     g = torch.Generator().manual_seed(seed)
@@ -54,7 +55,7 @@ def _bwd_setup(N, R, Cin, Cout, ks, split, seed):
     dx = torch.empty_like(xd)
     pts = [(k - 1) // 2 for k in ks]
     args = (xd, dyd, wd, dx, Gs, segd, E, wdstride, N, R, R, I, O, list(ks), list(ks), pts, pts, 1.0, wsb, wsb.numel() * 4, 1)
-    dims = [E, N, R, R, I, O, 1, 0] + list(ks) + [0] * (8 - E)
+    dims = w6_record(E, N, R, R, I, O, 1, ks)
     return x, dy, ws, seg, Gs, dx, segd, wsb, args, dims
 
 
