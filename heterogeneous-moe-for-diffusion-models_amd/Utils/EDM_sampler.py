@@ -6,7 +6,14 @@ the denoiser call is sync-free (device-side dispatch plan, no ``mask.any()``).  
 both evaluations, the Euler step and the 2nd-order correction, sigma taken from a device-side copy of the schedule -- is one captured
 hipGraph replayed N - 1 times (plus one for the last, Euler-only stage): no host arithmetic between evaluations.  With churn the
 evaluation alone is captured, as before.
+
+Extensions over the reference, all opt-in (``sample()`` keywords; with their defaults every path computes what it did without them):
+image-to-image from ``init_latents`` part-way down the schedule (``strength``), inpainting (``inpaint_mask``: the known region is put back on
+its probability-flow path ``x0 + sigma * noise`` by the epilogue of the update kernels), and expert steering (``Unet_router_mask`` /
+``Vit_router_mask``, also on ``denoise()``).
 """
+import math
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -41,11 +48,18 @@ class EDM_Sampler:
         self._skey = None
 
     # reference Utils/EDM_sampler.py:35-70
-    def denoise(self, x, sigma, text_emb, transition_mean, softness, uncond_text_emb=None):
+    def denoise(self, x, sigma, text_emb, transition_mean, softness, uncond_text_emb=None, Unet_router_mask=None, Vit_router_mask=None):
+        """One (guided) denoiser evaluation.  Router masks: (B, E) or (E,) with {0, 1} entries, None = every expert allowed (the reference)."""
+        um = self._router_mask(Unet_router_mask, "Unet_router_mask", x.shape[0])
+        vm = self._router_mask(Vit_router_mask, "Vit_router_mask", x.shape[0])
+        return self._denoise(x, sigma, text_emb, transition_mean, softness, uncond_text_emb, self._dev_mask(um, x), self._dev_mask(vm, x))
+
+    def _denoise(self, x, sigma, text_emb, transition_mean, softness, uncond_text_emb, um=None, vm=None):
+        """denoise() on validated device masks (or None): no host read, so it can run under stream capture."""
         bs = x.shape[0]
         num_experts = self.model.num_experts
-        Unet_router_mask = torch.ones((bs, num_experts), device=x.device)
-        vit_router_mask = torch.ones((bs, num_experts), device=x.device)
+        Unet_router_mask = torch.ones((bs, num_experts), device=x.device) if um is None else um
+        vit_router_mask = torch.ones((bs, num_experts), device=x.device) if vm is None else vm
         kw = dict(x=x, sigma=sigma, Unet_router_mask=Unet_router_mask, Vit_router_mask=vit_router_mask, zeta=0,
                   transition_point=transition_mean, softness=softness)
         D_x = self.model(text_emb=text_emb, **kw)["denoised"].to(self.dtype)
@@ -56,26 +70,85 @@ class EDM_Sampler:
         # ref.lerp(D, g) = (1-g)*ref + g*D
         return ops.axpby(ref_D_x, D_x, 1.0 - self.guide, self.guide)
 
+    # ---- argument checks of the extensions: ValueError naming the argument, before any device work ------------------------------------
+    def _router_mask(self, m, name, bs):
+        """Checked router mask as a float32 (B, E) tensor on m's device, or None.  A row without an allowed expert is refused: the gate
+        would give NaN probabilities for it and silently drop the expert output."""
+        if m is None:
+            return None
+        E = self.model.num_experts
+        if not isinstance(m, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor of shape ({bs}, {E}) or ({E},)")
+        if m.ndim not in (1, 2) or m.shape[-1] != E or (m.ndim == 2 and m.shape[0] != bs):
+            raise ValueError(f"{name} must have shape ({bs}, {E}) or ({E},), got {tuple(m.shape)}")
+        if m.is_complex():
+            raise ValueError(f"{name} must be real with {{0, 1}} entries, got {m.dtype}")
+        h = m.detach().to("cpu", torch.float64)
+        if not bool(((h == 0) | (h == 1)).all()):
+            raise ValueError(f"{name} entries must be 0 or 1")
+        if bool((h.sum(-1) == 0).any()):
+            raise ValueError(f"{name} has a row with no allowed expert")
+        return m.detach().to(torch.float32).expand(bs, E)
+
+    @staticmethod
+    def _dev_mask(m, like):
+        return None if m is None else m.to(like.device).contiguous()
+
+    def _check_conditioning(self, noise, init_latents, strength, inpaint_mask):
+        try:
+            strength = float(strength)
+        except (TypeError, ValueError):
+            raise ValueError(f"strength must be a number in (0, 1], got {strength!r}") from None
+        if not 0.0 < strength <= 1.0:
+            raise ValueError(f"strength must be in (0, 1], got {strength}")
+        if init_latents is not None:
+            if not isinstance(init_latents, torch.Tensor) or not init_latents.is_floating_point():
+                raise ValueError("init_latents must be a floating-point tensor")
+            if tuple(init_latents.shape) != tuple(noise.shape):
+                raise ValueError(f"init_latents must have the shape of noise {tuple(noise.shape)}, got {tuple(init_latents.shape)}")
+        elif strength < 1.0:
+            raise ValueError(f"strength < 1 (got {strength}) needs init_latents")
+        if inpaint_mask is not None:
+            if init_latents is None:
+                raise ValueError("inpaint_mask needs init_latents (the content of the known region)")
+            if not isinstance(inpaint_mask, torch.Tensor) or inpaint_mask.dtype != torch.float32:
+                raise ValueError(f"inpaint_mask must be a float32 tensor, got {getattr(inpaint_mask, 'dtype', type(inpaint_mask))}")
+            if inpaint_mask.ndim != 4:
+                raise ValueError(f"inpaint_mask must be 4-D, got shape {tuple(inpaint_mask.shape)}")
+            try:
+                ok = torch.broadcast_shapes(inpaint_mask.shape, noise.shape) == noise.shape
+            except RuntimeError:
+                ok = False
+            if not ok:
+                raise ValueError(f"inpaint_mask of shape {tuple(inpaint_mask.shape)} does not broadcast to noise {tuple(noise.shape)}")
+            lo, hi = (float(v) for v in torch.aminmax(inpaint_mask.detach()))
+            if not (0.0 <= lo and hi <= 1.0):
+                raise ValueError(f"inpaint_mask values must lie in [0, 1], got [{lo}, {hi}]")
+        return strength
+
     # ---- hipGraph path ---------------------------------------------------------------------------------------------
-    def _denoise_graphed(self, x, t, text_emb, transition_mean, softness, uncond_text_emb):
+    def _denoise_graphed(self, x, t, text_emb, transition_mean, softness, uncond_text_emb, um=None, vm=None):
         key = (tuple(x.shape), x.dtype, tuple(text_emb.shape), float(transition_mean), float(softness),
-               None if uncond_text_emb is None else tuple(uncond_text_emb.shape))
+               None if uncond_text_emb is None else tuple(uncond_text_emb.shape),
+               None if um is None else tuple(um.shape), None if vm is None else tuple(vm.shape))
         if self._graph is None or self._gkey != key:
             self._sx = torch.empty_like(x)
             self._ssig = torch.zeros((), dtype=self.dtype, device=x.device)
             self._stext = text_emb.clone()
             self._sunc = None if uncond_text_emb is None else uncond_text_emb.clone()
+            self._sum = None if um is None else um.clone()
+            self._svm = None if vm is None else vm.clone()
             self._sx.copy_(x)
             self._ssig.fill_(max(float(t), 1e-3))
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):                     # warm-up: registers the weight bank, sizes the allocator pool
                 for _ in range(3):
-                    self.denoise(self._sx, self._ssig, self._stext, transition_mean, softness, self._sunc)
+                    self._denoise(self._sx, self._ssig, self._stext, transition_mean, softness, self._sunc, self._sum, self._svm)
             torch.cuda.current_stream().wait_stream(side)
             self._graph = torch.cuda.CUDAGraph()
             with hgraph.no_gc(), torch.cuda.graph(self._graph):
-                self._sout = self.denoise(self._sx, self._ssig, self._stext, transition_mean, softness, self._sunc)
+                self._sout = self._denoise(self._sx, self._ssig, self._stext, transition_mean, softness, self._sunc, self._sum, self._svm)
             self._gkey = key
         # every replay input is refreshed: a later sample() with another prompt of the same shape must not see the captured one
         self._sx.copy_(x)
@@ -83,35 +156,43 @@ class EDM_Sampler:
         self._stext.copy_(text_emb)
         if self._sunc is not None:
             self._sunc.copy_(uncond_text_emb)
+        if self._sum is not None:
+            self._sum.copy_(um)
+        if self._svm is not None:
+            self._svm.copy_(vm)
         self._graph.replay()
         return self._sout.clone()
 
     # ---- fused solver stage (reference :90-107 without churn) ----------------------------------------------------------
-    def _stage_state(self, x, text_emb, transition_mean, softness, uncond_text_emb):
-        """Static buffers of the device-side solver: latents, sigma schedule (float64, as the host computes it), stage index; with
-        use_graph also the two captured graphs (a full Heun stage, and the last Euler-only stage).  The SAME stage function runs
-        eagerly (use_graph=False) and under capture, so the two trajectories are bit-identical."""
+    def _stage_state(self, x, text_emb, transition_mean, softness, uncond_text_emb, known=None, um=None, vm=None):
+        """Static buffers of the device-side solver: latents, sigma schedule (float64, as the host computes it), stage index, and when given
+        the known-region operands (x0, noise, expanded mask) and the router masks; with use_graph also the two captured graphs (a full Heun
+        stage, and the last Euler-only stage).  The SAME stage function runs eagerly (use_graph=False) and under capture, so the two
+        trajectories are bit-identical.  The key holds what changes the captured structure (which optional operands exist, their shapes),
+        never their values: sample() refreshes every buffer, and the stage index is read on the device, so any strength shares one capture."""
         key = (tuple(x.shape), tuple(text_emb.shape), float(transition_mean), float(softness), self.num_steps, bool(self.use_graph),
-               None if uncond_text_emb is None else tuple(uncond_text_emb.shape))
+               None if uncond_text_emb is None else tuple(uncond_text_emb.shape), known is not None,
+               None if um is None else tuple(um.shape), None if vm is None else tuple(vm.shape))
         if self._stage is not None and self._skey == key:
             return self._stage
         dev = x.device
         st = dict(x=torch.empty_like(x), xn=torch.empty_like(x), sig=torch.ones((), dtype=torch.float32, device=dev),
                   t=torch.ones(self.num_steps + 1, dtype=torch.float64, device=dev), idx=torch.zeros(1, dtype=torch.int32, device=dev),
-                  text=text_emb.clone(), unc=None if uncond_text_emb is None else uncond_text_emb.clone())
+                  text=text_emb.clone(), unc=None if uncond_text_emb is None else uncond_text_emb.clone(),
+                  known=None if known is None else tuple(k.clone() for k in known),
+                  um=None if um is None else um.clone(), vm=None if vm is None else vm.clone())
         st["x"].copy_(x)
-        n = x.numel()
 
         def stage(last: bool):
             ops.call("hdmoe_sched_pick", st["sig"], st["t"], st["idx"], 0)
-            den = self.denoise(st["x"], st["sig"], st["text"], transition_mean, softness, st["unc"])
+            den = self._denoise(st["x"], st["sig"], st["text"], transition_mean, softness, st["unc"], st["um"], st["vm"])
             if last:
-                ops.call("hdmoe_heun_euler", st["x"], st["x"], den, st["t"], st["idx"], n)
+                ops.heun_euler(st["x"], st["x"], den, st["t"], st["idx"], st["known"])
             else:
-                ops.call("hdmoe_heun_euler", st["xn"], st["x"], den, st["t"], st["idx"], n)
+                ops.heun_euler(st["xn"], st["x"], den, st["t"], st["idx"], st["known"])
                 ops.call("hdmoe_sched_pick", st["sig"], st["t"], st["idx"], 1)
-                den2 = self.denoise(st["xn"], st["sig"], st["text"], transition_mean, softness, st["unc"])
-                ops.call("hdmoe_heun_correct", st["x"], st["x"], den, st["xn"], den2, st["t"], st["idx"], n)
+                den2 = self._denoise(st["xn"], st["sig"], st["text"], transition_mean, softness, st["unc"], st["um"], st["vm"])
+                ops.heun_correct(st["x"], st["x"], den, st["xn"], den2, st["t"], st["idx"], st["known"])
             ops.call("hdmoe_idx_advance", st["idx"])
 
         st["stage"] = stage
@@ -133,11 +214,11 @@ class EDM_Sampler:
         self._stage, self._skey = st, key
         return st
 
-    def _eval(self, x, t, text_emb, transition_mean, softness, uncond_text_emb):
+    def _eval(self, x, t, text_emb, transition_mean, softness, uncond_text_emb, um=None, vm=None):
         if self.use_graph:
-            return self._denoise_graphed(x, t, text_emb, transition_mean, softness, uncond_text_emb)
+            return self._denoise_graphed(x, t, text_emb, transition_mean, softness, uncond_text_emb, um, vm)
         sig = torch.tensor(t, dtype=self.dtype, device=x.device)
-        return self.denoise(x, sig, text_emb, transition_mean, softness, uncond_text_emb)
+        return self._denoise(x, sig, text_emb, transition_mean, softness, uncond_text_emb, um, vm)
 
     def t_schedule(self, device):
         """Karras rho schedule with the appended 0 (reference :80-87), computed on the host in float64."""
@@ -148,7 +229,26 @@ class EDM_Sampler:
 
     @torch.no_grad()
     def sample(self, noise: torch.Tensor, text_emb: torch.Tensor, transition_mean: float, softness: float,
-               uncond_text_emb: torch.Tensor = None) -> torch.Tensor:
+               uncond_text_emb: torch.Tensor = None, *, init_latents: torch.Tensor = None, strength: float = 1.0,
+               inpaint_mask: torch.Tensor = None, Unet_router_mask: torch.Tensor = None, Vit_router_mask: torch.Tensor = None) -> torch.Tensor:
+        """Heun solve of the probability-flow ODE over t = t_schedule() (N = num_solve_steps, t[N] = 0).
+
+        Keywords beyond the reference (every default reproduces the plain sampler):
+          strength:       in (0, 1]; the solver runs the last n_run = ceil(strength * N) stages, i0 = N - n_run ... N - 1, i.e. 2 n_run - 1
+                          evaluations per network.  Below 1 it needs init_latents.
+          init_latents:   x0, the shape of noise.  Start x = x0 + t[i0] * noise (image-to-image); without it x = t[i0] * noise.  This holds
+                          under the inpainting mask too: whatever x0 holds in the hole enters at 1 / t[i0] of the noise scale (zero the hole
+                          to avoid that).
+          inpaint_mask:   m, float32 in [0, 1] (1 = keep), any 4-D shape broadcasting to noise; needs init_latents.  Wherever a stage
+                          produces latents at sigma = t[i+1] (the Euler predictor, the Heun-corrected output, the last Euler-only output):
+                          x <- m (x0 + sigma noise) + (1 - m) x, so where m = 1 the output is x0 exactly.  Soft masks blend.
+          Unet_router_mask / Vit_router_mask:  (B, E) or (E,) with {0, 1} entries, passed to the model and the guide network; None = all
+                          experts.  A row with no allowed expert is refused.
+        Argument errors raise ValueError (naming the argument) before any device work."""
+        strength = self._check_conditioning(noise, init_latents, strength, inpaint_mask)
+        bs = noise.shape[0]
+        um = self._router_mask(Unet_router_mask, "Unet_router_mask", bs)
+        vm = self._router_mask(Vit_router_mask, "Vit_router_mask", bs)
         device = noise.device
         if self.use_graph:
             # the captured evaluation holds no weight-prepare launch when the images were current at capture time: refresh them here,
@@ -157,27 +257,43 @@ class EDM_Sampler:
             for m_ in {id(self.model): self.model, id(self.gnet): self.gnet}.values():
                 if isinstance(m_, nn.Module) and getattr(m_, "_hdmoe_bank", None) is not None:
                     m_._hdmoe_bank.refresh_eval()
+        N = self.num_steps
+        i0 = N - math.ceil(strength * N)
         t_steps = self.t_schedule(device)
-        x_next = ops.axpby(noise.to(self.dtype), None, float(t_steps[0]), 0.0)
+        um, vm = self._dev_mask(um, noise), self._dev_mask(vm, noise)
+        known = None
+        if init_latents is None:
+            x_next = ops.axpby(noise.to(self.dtype), None, float(t_steps[i0]), 0.0)
+        else:
+            lat = noise.to(self.dtype).contiguous()
+            x0 = init_latents.to(device=device, dtype=self.dtype).contiguous()
+            x_next = ops.axpby(x0, lat, 1.0, float(t_steps[i0]))
+            if inpaint_mask is not None:                      # expanded once per call: the kernels read a mask of the latents' size
+                known = (x0, lat, inpaint_mask.to(device).expand(noise.shape).contiguous())
         self.fused_heun = bool(self.s_churn <= 0 and self.dtype == torch.float32 and noise.is_cuda and self.num_steps >= 2)
         if self.fused_heun:
             # no churn: the whole solver runs from a device-side schedule (fused Euler / Heun-correction kernels, no host arithmetic between
             # the evaluations); with use_graph each stage is one hipGraph replay
-            st = self._stage_state(x_next, text_emb, transition_mean, softness, uncond_text_emb)
+            st = self._stage_state(x_next, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm)
             st["x"].copy_(x_next)
             st["text"].copy_(text_emb)
             if st["unc"] is not None:
                 st["unc"].copy_(uncond_text_emb)
+            for buf, src in zip(st["known"] or (), known or ()):
+                buf.copy_(src)
+            for name, src in (("um", um), ("vm", vm)):
+                if st[name] is not None:
+                    st[name].copy_(src)
             st["t"].copy_(torch.from_numpy(t_steps))
-            st["idx"].zero_()
-            for i in range(self.num_steps):
-                last = i == self.num_steps - 1
+            st["idx"].fill_(i0)
+            for i in range(i0, N):
+                last = i == N - 1
                 if self.use_graph:
                     (st["g_last"] if last else st["g_heun"]).replay()
                 else:
                     st["stage"](last)
             return st["x"].clone()
-        for i in range(self.num_steps):
+        for i in range(i0, N):
             t_cur, t_next = float(t_steps[i]), float(t_steps[i + 1])
             x_cur = x_next
             gamma = min(self.s_churn / self.num_steps, np.sqrt(2) - 1) if (self.s_churn > 0 and self.s_min <= t_cur <= self.s_max) else 0
@@ -185,14 +301,18 @@ class EDM_Sampler:
             x_hat = x_cur
             if gamma > 0:
                 x_hat = ops.axpby(x_cur, ops.randn_like(x_cur, 1.0), 1.0, float(np.sqrt(t_hat ** 2 - t_cur ** 2) * self.s_noise))
-            denoised = self._eval(x_hat, t_hat, text_emb, transition_mean, softness, uncond_text_emb)
+            denoised = self._eval(x_hat, t_hat, text_emb, transition_mean, softness, uncond_text_emb, um, vm)
             # d_cur = (x_hat - denoised)/t_hat ; x_next = x_hat + (t_next - t_hat) * d_cur
             h = (t_next - t_hat)
             x_next = ops.axpby(x_hat, denoised, 1.0 + h / t_hat, -h / t_hat)
+            if known is not None:
+                ops.known_blend_(x_next, *known, t_next)
             if i < self.num_steps - 1:
-                den2 = self._eval(x_next, t_next, text_emb, transition_mean, softness, uncond_text_emb)
+                den2 = self._eval(x_next, t_next, text_emb, transition_mean, softness, uncond_text_emb, um, vm)
                 # x_next = x_hat + h * (0.5*d_cur + 0.5*d_prime),  d_prime = (x_next - den2)/t_next
                 d_cur_term = ops.axpby(x_hat, denoised, 1.0 + 0.5 * h / t_hat, -0.5 * h / t_hat)     # x_hat + 0.5 h d_cur
                 d_pr = ops.axpby(x_next, den2, 0.5 * h / t_next, -0.5 * h / t_next)                  # 0.5 h d_prime
                 x_next = ops.axpby(d_cur_term, d_pr, 1.0, 1.0)
+                if known is not None:
+                    ops.known_blend_(x_next, *known, t_next)
         return x_next

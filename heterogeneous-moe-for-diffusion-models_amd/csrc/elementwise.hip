@@ -52,22 +52,78 @@ __global__ void sched_pick_kernel(float* sigma, const double* t, const int* idx,
 __global__ void idx_advance_kernel(int* idx) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *idx += 1;
 }
-// x_next = x_hat + (t_next - t_hat) * (x_hat - denoised) / t_hat
-__global__ void heun_euler_kernel(float* xn, const float* xh, const float* den, const double* t, const int* idx, long n) {
+// W fp32 elements per thread: 16-byte loads / stores when W == 4 (the launcher checks n % 4 and the alignment), scalar otherwise
+template <int W> DEVI void ldw(float* f, const float* p) {
+  if constexpr (W == 4) vload<float>(f, p); else f[0] = *p;
+}
+template <int W> DEVI void stw(float* p, const float* f) {
+  if constexpr (W == 4) vstore<float>(p, f); else *p = f[0];
+}
+// Known region (inpainting) on its probability-flow path at sigma = s: x <- m (x0 + s noise) + (1 - m) x.  Evaluated in exactly this form
+// (not as a lerp) so that m = 1 at s = 0 gives x0 and m = 0 gives x bit-for-bit.  Epilogue of the stage kernels, and the host-loop form.
+template <int W> DEVI void known_blend_w(float* x, const float* x0, const float* nz, const float* m, float s, long off) {
+#pragma clang fp contract(off)
+  float a[W], z[W], k[W];
+  ldw<W>(a, x0 + off); ldw<W>(z, nz + off); ldw<W>(k, m + off);
+#pragma unroll
+  for (int j = 0; j < W; ++j) x[j] = k[j] * (a[j] + s * z[j]) + (1.f - k[j]) * x[j];
+}
+// The update arithmetic is spelled out with contraction off, in the roundings of the earlier scalar kernels (euler: two products, one sum;
+// correct: u = fma(a1, x_hat, b1 den), v = a2 x_next + b2 den2 unfused, u + v), so the result does not depend on how the compiler fuses it.
+// x_next = x_hat + (t_next - t_hat) * (x_hat - denoised) / t_hat;  with x0 / nz / m (all or none): the known-region blend at t_next
+template <int W>
+__global__ void heun_euler_kernel(float* xn, const float* xh, const float* den, const double* t, const int* idx, long nv,
+                                  const float* x0, const float* nz, const float* m) {
+#pragma clang fp contract(off)
   const int i = *idx;
   const double th = t[i], h = t[i + 1] - th;
-  const float a = (float)(1.0 + h / th), b = (float)(-h / th);
-  GRID_STRIDE(e, n) xn[e] = a * xh[e] + b * den[e];
+  const float a = (float)(1.0 + h / th), b = (float)(-h / th), s = (float)t[i + 1];
+  GRID_STRIDE(v, nv) {
+    float p[W], d[W];
+    ldw<W>(p, xh + v * W); ldw<W>(d, den + v * W);
+#pragma unroll
+    for (int j = 0; j < W; ++j) p[j] = a * p[j] + b * d[j];
+    if (m) known_blend_w<W>(p, x0, nz, m, s, v * W);
+    stw<W>(xn + v * W, p);
+  }
 }
-// x_out = x_hat + h * (0.5 * (x_hat - denoised) / t_hat + 0.5 * (x_next - denoised') / t_next)
-__global__ void heun_correct_kernel(float* out, const float* xh, const float* den, const float* xn, const float* den2, const double* t, const int* idx, long n) {
+// x_out = x_hat + h * (0.5 * (x_hat - denoised) / t_hat + 0.5 * (x_next - denoised') / t_next);  x0 / nz / m: as heun_euler_kernel
+template <int W>
+__global__ void heun_correct_kernel(float* out, const float* xh, const float* den, const float* xn, const float* den2, const double* t, const int* idx,
+                                    long nv, const float* x0, const float* nz, const float* m) {
+#pragma clang fp contract(off)
   const int i = *idx;
   const double th = t[i], tn = t[i + 1], h = tn - th;
   const float a1 = (float)(1.0 + 0.5 * h / th), b1 = (float)(-0.5 * h / th), a2 = (float)(0.5 * h / tn), b2 = (float)(-0.5 * h / tn);
+  const float s = (float)tn;
+  GRID_STRIDE(v, nv) {
+    float p[W], d[W], q[W], d2[W];
+    ldw<W>(p, xh + v * W); ldw<W>(d, den + v * W); ldw<W>(q, xn + v * W); ldw<W>(d2, den2 + v * W);
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      const float u = __builtin_fmaf(a1, p[j], b1 * d[j]);
+      const float w = a2 * q[j] + b2 * d2[j];
+      p[j] = u + w;
+    }
+    if (m) known_blend_w<W>(p, x0, nz, m, s, v * W);
+    stw<W>(out + v * W, p);
+  }
+}
+// host-scalar form of the blend (host-driven sampler loop: churn or non-fp32 latents); x, x0, nz in T, m fp32
+template <typename T>
+__global__ void known_blend_kernel(T* x, const T* x0, const T* nz, const float* m, float s, long n) {
+#pragma clang fp contract(off)
   GRID_STRIDE(e, n) {
-    const float u = a1 * xh[e] + b1 * den[e];
-    const float v = a2 * xn[e] + b2 * den2[e];
-    out[e] = u + v;
+    const float k = m[e];
+    x[e] = from_f<T>(k * (to_f(x0[e]) + s * to_f(nz[e])) + (1.f - k) * to_f(x[e]));
+  }
+}
+__global__ void known_blend_f4_kernel(float* x, const float* x0, const float* nz, const float* m, float s, long nv) {
+  GRID_STRIDE(v, nv) {
+    float p[4];
+    ldw<4>(p, x + v * 4);
+    known_blend_w<4>(p, x0, nz, m, s, v * 4);
+    stw<4>(x + v * 4, p);
   }
 }
 struct FirTaps { float k[8]; };
@@ -1008,16 +1064,35 @@ int hdmoe_idx_advance(int* idx, hipStream_t stream) {
   hipLaunchKernelGGL(idx_advance_kernel, dim3(1), dim3(64), 0, stream, idx);
   return hdmoe_launch_status();
 }
-int hdmoe_heun_euler(float* xn, const float* xh, const float* den, const double* t, const int* idx, long n, hipStream_t stream) {
-  if (!xn || !xh || !den || !t || !idx) return HDMOE_EINVAL;
-  L1D(heun_euler_kernel, n, xn, xh, den, t, idx, n);
+// known-region operand block (x0, noise, mask): all NULL (no blend) or all set; the 16-byte path when every pointer allows it
+static inline int known_block(const float* x0, const float* noise, const float* mask) {
+  return (x0 == nullptr && noise == nullptr && mask == nullptr) ? 0 : (x0 && noise && mask) ? 1 : -1;
+}
+int hdmoe_heun_euler(float* xn, const float* xh, const float* den, const double* t, const int* idx, long n,
+                     const float* x0, const float* noise, const float* mask, hipStream_t stream) {
+  if (!xn || !xh || !den || !t || !idx || n < 0 || known_block(x0, noise, mask) < 0) return HDMOE_EINVAL;
+  if (n % 4 == 0 && al16(xn) && al16(xh) && al16(den) && al16(x0) && al16(noise) && al16(mask))
+    L1D(heun_euler_kernel<4>, n / 4, xn, xh, den, t, idx, n / 4, x0, noise, mask);
+  else
+    L1D(heun_euler_kernel<1>, n, xn, xh, den, t, idx, n, x0, noise, mask);
   return hdmoe_launch_status();
 }
 int hdmoe_heun_correct(float* out, const float* xh, const float* den, const float* xn, const float* den2, const double* t, const int* idx, long n,
-                       hipStream_t stream) {
-  if (!out || !xh || !den || !xn || !den2 || !t || !idx) return HDMOE_EINVAL;
-  L1D(heun_correct_kernel, n, out, xh, den, xn, den2, t, idx, n);
+                       const float* x0, const float* noise, const float* mask, hipStream_t stream) {
+  if (!out || !xh || !den || !xn || !den2 || !t || !idx || n < 0 || known_block(x0, noise, mask) < 0) return HDMOE_EINVAL;
+  if (n % 4 == 0 && al16(out) && al16(xh) && al16(den) && al16(xn) && al16(den2) && al16(x0) && al16(noise) && al16(mask))
+    L1D(heun_correct_kernel<4>, n / 4, out, xh, den, xn, den2, t, idx, n / 4, x0, noise, mask);
+  else
+    L1D(heun_correct_kernel<1>, n, out, xh, den, xn, den2, t, idx, n, x0, noise, mask);
   return hdmoe_launch_status();
+}
+int hdmoe_known_blend(void* x, const void* x0, const void* noise, const float* mask, float s, long n, int dtype, hipStream_t stream) {
+  if (!x || !x0 || !noise || !mask || n < 0) return HDMOE_EINVAL;
+  if (dtype == HDMOE_F32 && n % 4 == 0 && al16(x) && al16(x0) && al16(noise) && al16(mask)) {
+    L1D(known_blend_f4_kernel, n / 4, (float*)x, (const float*)x0, (const float*)noise, mask, s, n / 4);
+    return hdmoe_launch_status();
+  }
+  DT_SWITCH(dtype, L1D(known_blend_kernel<T>, n, (T*)x, (const T*)x0, (const T*)noise, mask, s, n))
 }
 int hdmoe_exp_rate(float* out, int blocks, int iters, hipStream_t stream) {
   if (!out || blocks < 1 || iters < 1) return HDMOE_EINVAL;

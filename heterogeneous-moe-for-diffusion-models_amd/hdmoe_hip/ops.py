@@ -888,6 +888,27 @@ def axpby(x: Tensor, y: Optional[Tensor], a: float, b: float = 0.0) -> Tensor:
     return _AxpbyFn.apply(x, y, float(a), float(b))
 
 
+# ---- EDM sampler stage (fp32 latents, schedule t and stage index idx on the device; see include/hdmoe.h).  `known` = (x0, noise, mask) of
+# the inpainting blend epilogue, or None.  Written into preallocated buffers so that the calls can be captured.
+def heun_euler(xn: Tensor, xh: Tensor, den: Tensor, t: Tensor, idx: Tensor, known: Optional[Sequence[Tensor]] = None) -> None:
+    x0, nz, m = known if known is not None else (None, None, None)
+    call("hdmoe_heun_euler", xn, xh, den, t, idx, xn.numel(), x0, nz, m)
+
+
+def heun_correct(out: Tensor, xh: Tensor, den: Tensor, xn: Tensor, den2: Tensor, t: Tensor, idx: Tensor,
+                 known: Optional[Sequence[Tensor]] = None) -> None:
+    x0, nz, m = known if known is not None else (None, None, None)
+    call("hdmoe_heun_correct", out, xh, den, xn, den2, t, idx, out.numel(), x0, nz, m)
+
+
+def known_blend_(x: Tensor, x0: Tensor, noise: Tensor, mask: Tensor, s: float) -> Tensor:
+    """In place: x <- mask (x0 + s noise) + (1 - mask) x; x, x0, noise contiguous of one dtype, mask fp32, all of x's size."""
+    assert x.is_contiguous() and x0.is_contiguous() and noise.is_contiguous() and mask.is_contiguous()
+    assert x0.dtype == noise.dtype == x.dtype and mask.dtype == torch.float32 and x0.numel() == noise.numel() == mask.numel() == x.numel()
+    call("hdmoe_known_blend", x, x0, noise, mask, float(s), x.numel(), _dt(x))
+    return x
+
+
 def mp_sum(a: Tensor, b: Tensor, t: float = 0.5) -> Tensor:
     """lerp(a,b,t)/sqrt((1-t)^2+t^2) (model_internals.py:50-66)."""
     n = math.sqrt((1.0 - t) ** 2 + t ** 2)

@@ -125,11 +125,18 @@ int hdmoe_affine(void* out, const void* x, float a, float c, long n, int dtype, 
 int hdmoe_mul(void* out, const void* x, const void* y, long n, int dtype, HS stream);
 /* One Heun stage of the EDM sampler with the sigma schedule on the device (reference Utils/EDM_sampler.py:90-107): t = float64 [N + 1] device
  * array, idx = device int32 stage counter.  sched_pick: *sigma = t[*idx + off];  heun_euler: x_next = x_hat + (t[i+1] - t[i]) (x_hat - den) / t[i];
- * heun_correct: out = x_hat + h (0.5 (x_hat - den) / t[i] + 0.5 (x_next - den2) / t[i+1]);  idx_advance: *idx += 1.  fp32 latents of n elements. */
+ * heun_correct: out = x_hat + h (0.5 (x_hat - den) / t[i] + 0.5 (x_next - den2) / t[i+1]);  idx_advance: *idx += 1.  fp32 latents of n elements.
+ * Known region (inpainting): x0, noise, mask = fp32 arrays of n elements each, either all NULL (exactly the update above) or all set, in which
+ * case heun_euler / heun_correct end with the epilogue  x <- mask (x0 + s noise) + (1 - mask) x  at s = (float) t[i+1], in that form
+ * (mask = 1 at s = 0 returns x0, mask = 0 returns x, bit-for-bit).  In-place calls (out == x_hat) are allowed.
+ * known_blend: the same blend with a host scalar s, in place on x (x, x0, noise in dtype; mask fp32): the host-driven sampler loop. */
 int hdmoe_sched_pick(float* sigma, const double* t, const int* idx, int off, HS stream);
 int hdmoe_idx_advance(int* idx, HS stream);
-int hdmoe_heun_euler(float* xn, const float* xh, const float* den, const double* t, const int* idx, long n, HS stream);
-int hdmoe_heun_correct(float* out, const float* xh, const float* den, const float* xn, const float* den2, const double* t, const int* idx, long n, HS stream);
+int hdmoe_heun_euler(float* xn, const float* xh, const float* den, const double* t, const int* idx, long n,
+                     const float* x0, const float* noise, const float* mask, HS stream);
+int hdmoe_heun_correct(float* out, const float* xh, const float* den, const float* xn, const float* den2, const double* t, const int* idx, long n,
+                       const float* x0, const float* noise, const float* mask, HS stream);
+int hdmoe_known_blend(void* x, const void* x0, const void* noise, const float* mask, float s, long n, int dtype, HS stream);
 /* Measurement aid: `blocks` x 256 threads, 8 x `iters` dependent v_exp_f32 per thread (out: blocks * 256 floats).  bench.py times it to state the
  * transcendental issue rate the attention kernels (reference models/model_internals.py:374-404: one exp per score) are bounded by. */
 int hdmoe_exp_rate(float* out, int blocks, int iters, HS stream);
