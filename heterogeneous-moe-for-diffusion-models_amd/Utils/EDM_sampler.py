@@ -7,6 +7,10 @@ both evaluations, the Euler step and the 2nd-order correction, sigma taken from 
 hipGraph replayed N - 1 times (plus one for the last, Euler-only stage): no host arithmetic between evaluations.  With churn the
 evaluation alone is captured, as before.
 
+``solver="dpmpp_2m"`` (extension) replaces Heun by the DPM-Solver++(2M) multistep solver: one evaluation per stage, the previous stage's
+denoiser output standing in for the second one (N evaluations for N stages instead of 2N - 1).  Its fp32 stage is one evaluation plus the
+fused ``hdmoe_dpm2m_step`` update; with ``use_graph`` ONE captured graph is replayed once per stage.  Other latent dtypes run a host-driven loop.
+
 Extensions over the reference, all opt-in (``sample()`` keywords; with their defaults every path computes what it did without them):
 image-to-image from ``init_latents`` part-way down the schedule (``strength``), inpainting (``inpaint_mask``: the known region is put back on
 its probability-flow path ``x0 + sigma * noise`` by the epilogue of the update kernels), and expert steering (``Unet_router_mask`` /
@@ -21,11 +25,17 @@ import torch.nn as nn
 from hdmoe_hip import graph as hgraph
 from hdmoe_hip import ops
 
+SOLVERS = ("heun", "dpmpp_2m")
+
 
 class EDM_Sampler:
     def __init__(self, model: nn.Module, Guide_net: nn.Module, num_solve_steps: int = 32, sigma_min: float = 0.002,
                  sigma_max: float = 80, rho: int = 7, S_churn: float = 0.0, S_min: float = 0.0, S_max: float = float("inf"),
-                 S_noise: float = 1.0, guidance: float = 1.0, dtype=torch.float32, use_graph: bool = False):
+                 S_noise: float = 1.0, guidance: float = 1.0, dtype=torch.float32, use_graph: bool = False, solver: str = "heun"):
+        if not isinstance(solver, str) or solver not in SOLVERS:
+            raise ValueError(f"solver must be one of {', '.join(map(repr, SOLVERS))}, got {solver!r}")
+        if solver == "dpmpp_2m" and S_churn > 0:
+            raise ValueError(f"solver='dpmpp_2m' does not take S_churn > 0 (got {S_churn}): churn is defined for solver='heun' only")
         self.model = model
         self.gnet = Guide_net
         self.num_steps = num_solve_steps
@@ -39,11 +49,15 @@ class EDM_Sampler:
         self.guide = guidance
         self.dtype = dtype
         self.use_graph = use_graph          # extension over the reference: hipGraph replay of the denoiser evaluation
+        self.solver = solver                # extension over the reference: "dpmpp_2m" = DPM-Solver++(2M), one evaluation per stage
         self._graph = None
         self._gkey = None
         # no churn, fp32 latents: a solver stage = both denoiser evaluations + the fused Euler / Heun-correction kernels with sigma read from a
         # device-side schedule; with use_graph it is ONE captured graph, replayed N - 1 times, plus one graph for the last (Euler-only) stage
         self.fused_heun = False
+        # solver="dpmpp_2m", fp32 latents: a stage = one evaluation + the fused multistep update (hdmoe_dpm2m_step); with use_graph ONE
+        # captured graph serves every stage, the last one and the first (no history) included: the kernel picks the order on the device
+        self.fused_dpm = False
         self._stage = None
         self._skey = None
 
@@ -170,7 +184,7 @@ class EDM_Sampler:
         stage, and the last Euler-only stage).  The SAME stage function runs eagerly (use_graph=False) and under capture, so the two
         trajectories are bit-identical.  The key holds what changes the captured structure (which optional operands exist, their shapes),
         never their values: sample() refreshes every buffer, and the stage index is read on the device, so any strength shares one capture."""
-        key = (tuple(x.shape), tuple(text_emb.shape), float(transition_mean), float(softness), self.num_steps, bool(self.use_graph),
+        key = (self.solver, tuple(x.shape), tuple(text_emb.shape), float(transition_mean), float(softness), self.num_steps, bool(self.use_graph),
                None if uncond_text_emb is None else tuple(uncond_text_emb.shape), known is not None,
                None if um is None else tuple(um.shape), None if vm is None else tuple(vm.shape))
         if self._stage is not None and self._skey == key:
@@ -182,6 +196,8 @@ class EDM_Sampler:
                   known=None if known is None else tuple(k.clone() for k in known),
                   um=None if um is None else um.clone(), vm=None if vm is None else vm.clone())
         st["x"].copy_(x)
+        if self.solver == "dpmpp_2m":
+            return self._dpm_stage_state(st, key, transition_mean, softness)
 
         def stage(last: bool):
             ops.call("hdmoe_sched_pick", st["sig"], st["t"], st["idx"], 0)
@@ -214,6 +230,56 @@ class EDM_Sampler:
         self._stage, self._skey = st, key
         return st
 
+    def _dpm_stage_state(self, st, key, transition_mean, softness):
+        """_stage_state for solver="dpmpp_2m": adds den_prev (the previous stage's denoiser output, read and overwritten element by element
+        by the step kernel) and the device int32 i0 (first stage run).  The step kernel takes the order (first at i0, multistep after, D at
+        t[i+1] = 0) from idx, i0 and t on the device, so with use_graph ONE capture serves every stage of every strength."""
+        del st["xn"]                                          # Heun's predictor buffer
+        st["den_prev"] = torch.zeros_like(st["x"])
+        st["i0"] = torch.zeros(1, dtype=torch.int32, device=st["x"].device)
+
+        def stage():
+            ops.call("hdmoe_sched_pick", st["sig"], st["t"], st["idx"], 0)
+            den = self._denoise(st["x"], st["sig"], st["text"], transition_mean, softness, st["unc"], st["um"], st["vm"])
+            ops.dpm2m_step(st["x"], st["x"], den, st["den_prev"], st["t"], st["idx"], st["i0"], st["known"])
+            ops.call("hdmoe_idx_advance", st["idx"])
+
+        st["stage"] = stage
+        if self.use_graph:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):                     # warm-up: registers the weight bank, sizes the allocator pool
+                st["idx"].zero_()
+                st["i0"].zero_()
+                for _ in range(2):
+                    stage()
+            torch.cuda.current_stream().wait_stream(side)
+            st["g_dpm"] = torch.cuda.CUDAGraph()
+            with hgraph.no_gc(), torch.cuda.graph(st["g_dpm"]):
+                stage()
+        self._stage, self._skey = st, key
+        return st
+
+    def _dpm_host_loop(self, x, t_steps, i0, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm):
+        """solver="dpmpp_2m" for latents the fused stage does not take (non-fp32 dtype): the rule of sample() with host coefficients."""
+        N = self.num_steps
+        den_prev = None
+        for i in range(i0, N):
+            t_cur, t_next = float(t_steps[i]), float(t_steps[i + 1])
+            den = self._eval(x, t_cur, text_emb, transition_mean, softness, uncond_text_emb, um, vm)
+            a = t_next / t_cur
+            if t_next == 0:
+                x = den.clone()
+            elif i == i0:
+                x = ops.axpby(x, den, a, 1.0 - a)
+            else:
+                hr = 0.5 * math.log(t_cur / t_next) / math.log(float(t_steps[i - 1]) / t_cur)      # 1 / (2 r)
+                x = ops.axpby(x, ops.axpby(den, den_prev, 1.0 + hr, -hr), a, 1.0 - a)
+            if known is not None:
+                ops.known_blend_(x, *known, t_next)
+            den_prev = den
+        return x
+
     def _eval(self, x, t, text_emb, transition_mean, softness, uncond_text_emb, um=None, vm=None):
         if self.use_graph:
             return self._denoise_graphed(x, t, text_emb, transition_mean, softness, uncond_text_emb, um, vm)
@@ -231,16 +297,24 @@ class EDM_Sampler:
     def sample(self, noise: torch.Tensor, text_emb: torch.Tensor, transition_mean: float, softness: float,
                uncond_text_emb: torch.Tensor = None, *, init_latents: torch.Tensor = None, strength: float = 1.0,
                inpaint_mask: torch.Tensor = None, Unet_router_mask: torch.Tensor = None, Vit_router_mask: torch.Tensor = None) -> torch.Tensor:
-        """Heun solve of the probability-flow ODE over t = t_schedule() (N = num_solve_steps, t[N] = 0).
+        """Solve of the probability-flow ODE over t = t_schedule() (N = num_solve_steps, t[N] = 0): Heun (solver="heun", the reference),
+        or DPM-Solver++(2M) (solver="dpmpp_2m", one evaluation per stage).
+
+        solver="dpmpp_2m" runs, for i = i0 ... N - 1, with D_i the (guided) denoiser output at t[i] and a = t[i+1] / t[i]:
+            t[i+1] == 0:  x = D_i                                       (last stage)
+            i == i0:      x = a x + (1 - a) D_i                         (no history yet: first order)
+            otherwise:    x = a x + (1 - a) ((1 + 1/(2r)) D_i - 1/(2r) D_{i-1}),   r = log(t[i-1] / t[i]) / log(t[i] / t[i+1])
+        then the inpainting blend below at sigma = t[i+1], and D_{i-1} <- D_i: n_run evaluations per network.  It takes every keyword below.
 
         Keywords beyond the reference (every default reproduces the plain sampler):
           strength:       in (0, 1]; the solver runs the last n_run = ceil(strength * N) stages, i0 = N - n_run ... N - 1, i.e. 2 n_run - 1
-                          evaluations per network.  Below 1 it needs init_latents.
+                          evaluations per network with Heun, n_run with DPM-Solver++(2M).  Below 1 it needs init_latents.
           init_latents:   x0, the shape of noise.  Start x = x0 + t[i0] * noise (image-to-image); without it x = t[i0] * noise.  This holds
                           under the inpainting mask too: whatever x0 holds in the hole enters at 1 / t[i0] of the noise scale (zero the hole
                           to avoid that).
           inpaint_mask:   m, float32 in [0, 1] (1 = keep), any 4-D shape broadcasting to noise; needs init_latents.  Wherever a stage
-                          produces latents at sigma = t[i+1] (the Euler predictor, the Heun-corrected output, the last Euler-only output):
+                          produces latents at sigma = t[i+1] (the Euler predictor, the Heun-corrected output, the last Euler-only output, each
+                          DPM-Solver++(2M) update):
                           x <- m (x0 + sigma noise) + (1 - m) x, so where m = 1 the output is x0 exactly.  Soft masks blend.
           Unet_router_mask / Vit_router_mask:  (B, E) or (E,) with {0, 1} entries, passed to the model and the guide network; None = all
                           experts.  A row with no allowed expert is refused.
@@ -270,10 +344,12 @@ class EDM_Sampler:
             x_next = ops.axpby(x0, lat, 1.0, float(t_steps[i0]))
             if inpaint_mask is not None:                      # expanded once per call: the kernels read a mask of the latents' size
                 known = (x0, lat, inpaint_mask.to(device).expand(noise.shape).contiguous())
-        self.fused_heun = bool(self.s_churn <= 0 and self.dtype == torch.float32 and noise.is_cuda and self.num_steps >= 2)
-        if self.fused_heun:
-            # no churn: the whole solver runs from a device-side schedule (fused Euler / Heun-correction kernels, no host arithmetic between
-            # the evaluations); with use_graph each stage is one hipGraph replay
+        fused = bool(self.s_churn <= 0 and self.dtype == torch.float32 and noise.is_cuda and self.num_steps >= 2)
+        self.fused_heun = fused and self.solver == "heun"
+        self.fused_dpm = fused and self.solver == "dpmpp_2m"
+        if fused:
+            # no churn: the whole solver runs from a device-side schedule (fused Euler / Heun-correction kernels, or the DPM-Solver++(2M) step
+            # kernel, no host arithmetic between the evaluations); with use_graph each stage is one hipGraph replay
             st = self._stage_state(x_next, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm)
             st["x"].copy_(x_next)
             st["text"].copy_(text_emb)
@@ -286,6 +362,14 @@ class EDM_Sampler:
                     st[name].copy_(src)
             st["t"].copy_(torch.from_numpy(t_steps))
             st["idx"].fill_(i0)
+            if self.fused_dpm:
+                st["i0"].fill_(i0)
+                for i in range(i0, N):
+                    if self.use_graph:
+                        st["g_dpm"].replay()
+                    else:
+                        st["stage"]()
+                return st["x"].clone()
             for i in range(i0, N):
                 last = i == N - 1
                 if self.use_graph:
@@ -293,6 +377,8 @@ class EDM_Sampler:
                 else:
                     st["stage"](last)
             return st["x"].clone()
+        if self.solver == "dpmpp_2m":
+            return self._dpm_host_loop(x_next, t_steps, i0, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm)
         for i in range(i0, N):
             t_cur, t_next = float(t_steps[i]), float(t_steps[i + 1])
             x_cur = x_next

@@ -109,6 +109,47 @@ __global__ void heun_correct_kernel(float* out, const float* xh, const float* de
     stw<W>(out + v * W, p);
   }
 }
+// One DPM-Solver++(2M) stage (multistep, data prediction) on the same device schedule, one evaluation per stage: i = *idx, a = t[i+1] / t[i];
+//   t[i+1] == 0:  x_out = den                                           (last stage)
+//   i == *i0:     x_out = a x + (1 - a) den                             (no history yet: first order)
+//   otherwise:    x_out = a x + (1 - a) ((1 + 1/(2r)) den - 1/(2r) den_prev),  r = log(t[i-1] / t[i]) / log(t[i] / t[i+1])
+// then the known-region blend at s = t[i+1] (x0 / nz / m: as heun_euler_kernel), and den_prev <- den, each thread on its own elements (so a
+// captured graph needs no ping-pong buffers).  Roundings, contraction off: a, b = 1 - a, w1 = 1 + 1/(2r), w0 = 1/(2r) are computed in double
+// and rounded to float once; u = w1 den - w0 den_prev (two products, one difference), x_out = a x + b u (two products, one sum); first order
+// a x + b den.  den_prev is read only by the second-order branch, x not at all by the last stage.
+template <int W>
+__global__ void dpm2m_step_kernel(float* xo, const float* x, const float* den, float* dp, const double* t, const int* idx, const int* i0, long nv,
+                                  const float* x0, const float* nz, const float* m) {
+#pragma clang fp contract(off)
+  const int i = *idx;
+  const double ti = t[i], tn = t[i + 1];
+  const int order = tn == 0.0 ? 0 : (i <= *i0 ? 1 : 2);       // <=, not ==: an idx below i0 never reads t[i - 1]
+  const double ad = tn / ti, hr = order == 2 ? 0.5 * log(ti / tn) / log(t[i - 1] / ti) : 0.0;
+  const float a = (float)ad, b = (float)(1.0 - ad), w1 = (float)(1.0 + hr), w0 = (float)hr, s = (float)tn;
+  GRID_STRIDE(v, nv) {
+    float p[W], d[W];
+    ldw<W>(d, den + v * W);
+    if (order == 0) {
+#pragma unroll
+      for (int j = 0; j < W; ++j) p[j] = d[j];
+    } else if (order == 1) {
+      ldw<W>(p, x + v * W);
+#pragma unroll
+      for (int j = 0; j < W; ++j) p[j] = a * p[j] + b * d[j];
+    } else {
+      float q[W];
+      ldw<W>(p, x + v * W); ldw<W>(q, dp + v * W);
+#pragma unroll
+      for (int j = 0; j < W; ++j) {
+        const float u = w1 * d[j] - w0 * q[j];
+        p[j] = a * p[j] + b * u;
+      }
+    }
+    if (m) known_blend_w<W>(p, x0, nz, m, s, v * W);
+    stw<W>(dp + v * W, d);
+    stw<W>(xo + v * W, p);
+  }
+}
 // host-scalar form of the blend (host-driven sampler loop: churn or non-fp32 latents); x, x0, nz in T, m fp32
 template <typename T>
 __global__ void known_blend_kernel(T* x, const T* x0, const T* nz, const float* m, float s, long n) {
@@ -1084,6 +1125,21 @@ int hdmoe_heun_correct(float* out, const float* xh, const float* den, const floa
     L1D(heun_correct_kernel<4>, n / 4, out, xh, den, xn, den2, t, idx, n / 4, x0, noise, mask);
   else
     L1D(heun_correct_kernel<1>, n, out, xh, den, xn, den2, t, idx, n, x0, noise, mask);
+  return hdmoe_launch_status();
+}
+// do the n-float ranges at p and q share an element
+static inline bool overlap(const float* p, const float* q, long n) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q, bytes = (uintptr_t)n * sizeof(float);
+  return n > 0 && a < b + bytes && b < a + bytes;
+}
+int hdmoe_dpm2m_step(float* x_out, const float* x, const float* den, float* den_prev, const double* t, const int* idx, const int* i0, long n,
+                     const float* x0, const float* noise, const float* mask, hipStream_t stream) {
+  if (!x_out || !x || !den || !den_prev || !t || !idx || !i0 || n < 0 || known_block(x0, noise, mask) < 0) return HDMOE_EINVAL;
+  if (overlap(den_prev, den, n) || overlap(den_prev, x, n) || overlap(den_prev, x_out, n)) return HDMOE_EINVAL;
+  if (n % 4 == 0 && al16(x_out) && al16(x) && al16(den) && al16(den_prev) && al16(x0) && al16(noise) && al16(mask))
+    L1D(dpm2m_step_kernel<4>, n / 4, x_out, x, den, den_prev, t, idx, i0, n / 4, x0, noise, mask);
+  else
+    L1D(dpm2m_step_kernel<1>, n, x_out, x, den, den_prev, t, idx, i0, n, x0, noise, mask);
   return hdmoe_launch_status();
 }
 int hdmoe_known_blend(void* x, const void* x0, const void* noise, const float* mask, float s, long n, int dtype, hipStream_t stream) {

@@ -901,6 +901,13 @@ def heun_correct(out: Tensor, xh: Tensor, den: Tensor, xn: Tensor, den2: Tensor,
     call("hdmoe_heun_correct", out, xh, den, xn, den2, t, idx, out.numel(), x0, nz, m)
 
 
+def dpm2m_step(out: Tensor, x: Tensor, den: Tensor, den_prev: Tensor, t: Tensor, idx: Tensor, i0: Tensor,
+               known: Optional[Sequence[Tensor]] = None) -> None:
+    """One DPM-Solver++(2M) stage into out (out may be x); reads den_prev, then stores den into it.  i0 = device int32 first stage."""
+    x0, nz, m = known if known is not None else (None, None, None)
+    call("hdmoe_dpm2m_step", out, x, den, den_prev, t, idx, i0, out.numel(), x0, nz, m)
+
+
 def known_blend_(x: Tensor, x0: Tensor, noise: Tensor, mask: Tensor, s: float) -> Tensor:
     """In place: x <- mask (x0 + s noise) + (1 - mask) x; x, x0, noise contiguous of one dtype, mask fp32, all of x's size."""
     assert x.is_contiguous() and x0.is_contiguous() and noise.is_contiguous() and mask.is_contiguous()

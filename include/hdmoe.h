@@ -129,7 +129,12 @@ int hdmoe_mul(void* out, const void* x, const void* y, long n, int dtype, HS str
  * Known region (inpainting): x0, noise, mask = fp32 arrays of n elements each, either all NULL (exactly the update above) or all set, in which
  * case heun_euler / heun_correct end with the epilogue  x <- mask (x0 + s noise) + (1 - mask) x  at s = (float) t[i+1], in that form
  * (mask = 1 at s = 0 returns x0, mask = 0 returns x, bit-for-bit).  In-place calls (out == x_hat) are allowed.
- * known_blend: the same blend with a host scalar s, in place on x (x, x0, noise in dtype; mask fp32): the host-driven sampler loop. */
+ * known_blend: the same blend with a host scalar s, in place on x (x, x0, noise in dtype; mask fp32): the host-driven sampler loop.
+ * dpm2m_step: one DPM-Solver++(2M) stage (one evaluation per stage; i = *idx, i0 = *i0 = the first stage run, a = t[i+1] / t[i]):
+ * t[i+1] == 0: x_out = den;  i == i0: x_out = a x + (1 - a) den;  else, with r = log(t[i-1] / t[i]) / log(t[i] / t[i+1]),
+ * x_out = a x + (1 - a) ((1 + 1/(2r)) den - 1/(2r) den_prev);  then the known-region epilogue as above (all NULL or all set), and
+ * den_prev <- den in the same pass (den_prev is read before it is written, element by element).  x_out == x is allowed; den_prev must
+ * not overlap x_out, x or den.  HDMOE_EINVAL for a NULL required pointer, n < 0, a partial known block or an overlapping den_prev. */
 int hdmoe_sched_pick(float* sigma, const double* t, const int* idx, int off, HS stream);
 int hdmoe_idx_advance(int* idx, HS stream);
 int hdmoe_heun_euler(float* xn, const float* xh, const float* den, const double* t, const int* idx, long n,
@@ -137,6 +142,8 @@ int hdmoe_heun_euler(float* xn, const float* xh, const float* den, const double*
 int hdmoe_heun_correct(float* out, const float* xh, const float* den, const float* xn, const float* den2, const double* t, const int* idx, long n,
                        const float* x0, const float* noise, const float* mask, HS stream);
 int hdmoe_known_blend(void* x, const void* x0, const void* noise, const float* mask, float s, long n, int dtype, HS stream);
+int hdmoe_dpm2m_step(float* x_out, const float* x, const float* den, float* den_prev, const double* t, const int* idx, const int* i0, long n,
+                     const float* x0, const float* noise, const float* mask, HS stream);
 /* Measurement aid: `blocks` x 256 threads, 8 x `iters` dependent v_exp_f32 per thread (out: blocks * 256 floats).  bench.py times it to state the
  * transcendental issue rate the attention kernels (reference models/model_internals.py:374-404: one exp per score) are bounded by. */
 int hdmoe_exp_rate(float* out, int blocks, int iters, HS stream);
