@@ -50,16 +50,16 @@ class EDM_Sampler:
         self.dtype = dtype
         self.use_graph = use_graph          # extension over the reference: hipGraph replay of the denoiser evaluation
         self.solver = solver                # extension over the reference: "dpmpp_2m" = DPM-Solver++(2M), one evaluation per stage
-        self._graph = None
-        self._gkey = None
         # no churn, fp32 latents: a solver stage = both denoiser evaluations + the fused Euler / Heun-correction kernels with sigma read from a
         # device-side schedule; with use_graph it is ONE captured graph, replayed N - 1 times, plus one graph for the last (Euler-only) stage
         self.fused_heun = False
         # solver="dpmpp_2m", fp32 latents: a stage = one evaluation + the fused multistep update (hdmoe_dpm2m_step); with use_graph ONE
         # captured graph serves every stage, the last one and the first (no history) included: the kernel picks the order on the device
         self.fused_dpm = False
+        # _stage_state() of the captured evaluation ("eval") and of the fused solver stage ("heun" / "dpm"): buffers, stage functions,
+        # graphs and the key they were built for
+        self._graph = None
         self._stage = None
-        self._skey = None
 
     # reference Utils/EDM_sampler.py:35-70
     def denoise(self, x, sigma, text_emb, transition_mean, softness, uncond_text_emb=None, Unet_router_mask=None, Vit_router_mask=None):
@@ -140,125 +140,103 @@ class EDM_Sampler:
                 raise ValueError(f"inpaint_mask values must lie in [0, 1], got [{lo}, {hi}]")
         return strength
 
-    # ---- hipGraph path ---------------------------------------------------------------------------------------------
-    def _denoise_graphed(self, x, t, text_emb, transition_mean, softness, uncond_text_emb, um=None, vm=None):
-        key = (tuple(x.shape), x.dtype, tuple(text_emb.shape), float(transition_mean), float(softness),
-               None if uncond_text_emb is None else tuple(uncond_text_emb.shape),
-               None if um is None else tuple(um.shape), None if vm is None else tuple(vm.shape))
-        if self._graph is None or self._gkey != key:
-            self._sx = torch.empty_like(x)
-            self._ssig = torch.zeros((), dtype=self.dtype, device=x.device)
-            self._stext = text_emb.clone()
-            self._sunc = None if uncond_text_emb is None else uncond_text_emb.clone()
-            self._sum = None if um is None else um.clone()
-            self._svm = None if vm is None else vm.clone()
-            self._sx.copy_(x)
-            self._ssig.fill_(max(float(t), 1e-3))
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):                     # warm-up: registers the weight bank, sizes the allocator pool
-                for _ in range(3):
-                    self._denoise(self._sx, self._ssig, self._stext, transition_mean, softness, self._sunc, self._sum, self._svm)
-            torch.cuda.current_stream().wait_stream(side)
-            self._graph = torch.cuda.CUDAGraph()
-            with hgraph.no_gc(), torch.cuda.graph(self._graph):
-                self._sout = self._denoise(self._sx, self._ssig, self._stext, transition_mean, softness, self._sunc, self._sum, self._svm)
-            self._gkey = key
-        # every replay input is refreshed: a later sample() with another prompt of the same shape must not see the captured one
-        self._sx.copy_(x)
-        self._ssig.fill_(float(t))
-        self._stext.copy_(text_emb)
-        if self._sunc is not None:
-            self._sunc.copy_(uncond_text_emb)
-        if self._sum is not None:
-            self._sum.copy_(um)
-        if self._svm is not None:
-            self._svm.copy_(vm)
-        self._graph.replay()
-        return self._sout.clone()
-
-    # ---- fused solver stage (reference :90-107 without churn) ----------------------------------------------------------
-    def _stage_state(self, x, text_emb, transition_mean, softness, uncond_text_emb, known=None, um=None, vm=None):
-        """Static buffers of the device-side solver: latents, sigma schedule (float64, as the host computes it), stage index, and when given
-        the known-region operands (x0, noise, expanded mask) and the router masks; with use_graph also the two captured graphs (a full Heun
-        stage, and the last Euler-only stage).  The SAME stage function runs eagerly (use_graph=False) and under capture, so the two
-        trajectories are bit-identical.  The key holds what changes the captured structure (which optional operands exist, their shapes),
-        never their values: sample() refreshes every buffer, and the stage index is read on the device, so any strength shares one capture."""
-        key = (self.solver, tuple(x.shape), tuple(text_emb.shape), float(transition_mean), float(softness), self.num_steps, bool(self.use_graph),
-               None if uncond_text_emb is None else tuple(uncond_text_emb.shape), known is not None,
-               None if um is None else tuple(um.shape), None if vm is None else tuple(vm.shape))
-        if self._stage is not None and self._skey == key:
-            return self._stage
+    # ---- static state and hipGraph capture: fused solver stages (reference :90-107 without churn), the captured evaluation ----------------
+    def _stage_state(self, kind, x, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm):
+        """Static buffers, stage functions and (use_graph) captured graphs of one kind:
+          "eval": one guided evaluation of x at sig into out (the host loops' evaluation with use_graph);
+          "heun": a full Heun stage and the last, Euler-only stage; "dpm": one DPM-Solver++(2M) stage (den_prev: the previous stage's
+                  denoiser output, read and overwritten element by element by the step kernel; i0: the first stage run).
+        The stage kinds take sigma from the schedule t (float64, as the host computes it) at the device stage index idx, and the kernels pick
+        the order on the device, so any strength shares one capture.  The SAME stage function runs eagerly and under capture: the two
+        trajectories are bit-identical.  The key holds everything a capture bakes in -- shapes, which optional operands exist, and what
+        _denoise reads on the host (guide, the two modules) -- never buffer values: every input is refreshed before each run."""
+        shape = lambda a: None if a is None else tuple(a.shape)
+        key = (kind, self.solver, shape(x), x.dtype, shape(text_emb), shape(uncond_text_emb), float(transition_mean), float(softness),
+               self.num_steps, bool(self.use_graph), None if known is None else tuple(map(shape, known)), shape(um), shape(vm),
+               float(self.guide), id(self.model), id(self.gnet))
+        slot = "_graph" if kind == "eval" else "_stage"          # one cached state for the evaluation, one for the solver stage
+        st = getattr(self, slot)
+        if st is not None and st["key"] == key:
+            return st
         dev = x.device
-        st = dict(x=torch.empty_like(x), xn=torch.empty_like(x), sig=torch.ones((), dtype=torch.float32, device=dev),
-                  t=torch.ones(self.num_steps + 1, dtype=torch.float64, device=dev), idx=torch.zeros(1, dtype=torch.int32, device=dev),
-                  text=text_emb.clone(), unc=None if uncond_text_emb is None else uncond_text_emb.clone(),
-                  known=None if known is None else tuple(k.clone() for k in known),
-                  um=None if um is None else um.clone(), vm=None if vm is None else vm.clone())
-        st["x"].copy_(x)
-        if self.solver == "dpmpp_2m":
-            return self._dpm_stage_state(st, key, transition_mean, softness)
+        opt = lambda a: None if a is None else torch.empty_like(a)
+        # mods: held so that their ids, in the key, cannot be reused by other modules while this capture lives
+        st = dict(key=key, x=torch.empty_like(x), sig=torch.ones((), dtype=self.dtype, device=dev), text=torch.empty_like(text_emb),
+                  unc=opt(uncond_text_emb), known=None if known is None else tuple(map(torch.empty_like, known)), um=opt(um), vm=opt(vm),
+                  mods=(self.model, self.gnet))
+        self._refresh(st, x, text_emb, uncond_text_emb, known, um, vm)
 
-        def stage(last: bool):
-            ops.call("hdmoe_sched_pick", st["sig"], st["t"], st["idx"], 0)
-            den = self._denoise(st["x"], st["sig"], st["text"], transition_mean, softness, st["unc"], st["um"], st["vm"])
+        def den(x_):
+            return self._denoise(x_, st["sig"], st["text"], transition_mean, softness, st["unc"], st["um"], st["vm"])
+
+        def pick(j):                                          # sig = t[idx + j]
+            ops.call("hdmoe_sched_pick", st["sig"], st["t"], st["idx"], j)
+
+        def heun(last: bool):
+            pick(0)
+            d = den(st["x"])
             if last:
-                ops.heun_euler(st["x"], st["x"], den, st["t"], st["idx"], st["known"])
+                ops.heun_euler(st["x"], st["x"], d, st["t"], st["idx"], st["known"])
             else:
-                ops.heun_euler(st["xn"], st["x"], den, st["t"], st["idx"], st["known"])
-                ops.call("hdmoe_sched_pick", st["sig"], st["t"], st["idx"], 1)
-                den2 = self._denoise(st["xn"], st["sig"], st["text"], transition_mean, softness, st["unc"], st["um"], st["vm"])
-                ops.heun_correct(st["x"], st["x"], den, st["xn"], den2, st["t"], st["idx"], st["known"])
+                ops.heun_euler(st["xn"], st["x"], d, st["t"], st["idx"], st["known"])
+                pick(1)
+                ops.heun_correct(st["x"], st["x"], d, st["xn"], den(st["xn"]), st["t"], st["idx"], st["known"])
             ops.call("hdmoe_idx_advance", st["idx"])
 
-        st["stage"] = stage
-        if self.use_graph:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):                     # warm-up: registers the weight bank, sizes the allocator pool
-                for _ in range(2):
-                    st["idx"].zero_()
-                    stage(False)
-            torch.cuda.current_stream().wait_stream(side)
-            st["g_heun"], st["g_last"] = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            st["idx"].zero_()
-            with hgraph.no_gc():
-                with torch.cuda.graph(st["g_heun"]):
-                    stage(False)
-                with torch.cuda.graph(st["g_last"], pool=st["g_heun"].pool()):
-                    stage(True)
-        self._stage, self._skey = st, key
-        return st
-
-    def _dpm_stage_state(self, st, key, transition_mean, softness):
-        """_stage_state for solver="dpmpp_2m": adds den_prev (the previous stage's denoiser output, read and overwritten element by element
-        by the step kernel) and the device int32 i0 (first stage run).  The step kernel takes the order (first at i0, multistep after, D at
-        t[i+1] = 0) from idx, i0 and t on the device, so with use_graph ONE capture serves every stage of every strength."""
-        del st["xn"]                                          # Heun's predictor buffer
-        st["den_prev"] = torch.zeros_like(st["x"])
-        st["i0"] = torch.zeros(1, dtype=torch.int32, device=st["x"].device)
-
-        def stage():
-            ops.call("hdmoe_sched_pick", st["sig"], st["t"], st["idx"], 0)
-            den = self._denoise(st["x"], st["sig"], st["text"], transition_mean, softness, st["unc"], st["um"], st["vm"])
-            ops.dpm2m_step(st["x"], st["x"], den, st["den_prev"], st["t"], st["idx"], st["i0"], st["known"])
+        def dpm():
+            pick(0)
+            ops.dpm2m_step(st["x"], st["x"], den(st["x"]), st["den_prev"], st["t"], st["idx"], st["i0"], st["known"])
             ops.call("hdmoe_idx_advance", st["idx"])
 
-        st["stage"] = stage
-        if self.use_graph:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):                     # warm-up: registers the weight bank, sizes the allocator pool
-                st["idx"].zero_()
-                st["i0"].zero_()
-                for _ in range(2):
-                    stage()
-            torch.cuda.current_stream().wait_stream(side)
-            st["g_dpm"] = torch.cuda.CUDAGraph()
-            with hgraph.no_gc(), torch.cuda.graph(st["g_dpm"]):
-                stage()
-        self._stage, self._skey = st, key
+        def evaluate():
+            st["out"] = den(st["x"])
+
+        if kind != "eval":
+            st.update(t=torch.ones(self.num_steps + 1, dtype=torch.float64, device=dev), idx=torch.zeros(1, dtype=torch.int32, device=dev))
+        if kind == "heun":
+            st["xn"] = torch.empty_like(x)                    # the Euler predictor
+        if kind == "dpm":
+            st.update(den_prev=torch.zeros_like(x), i0=torch.zeros(1, dtype=torch.int32, device=dev))
+        st["fns"] = {"eval": [evaluate], "heun": [lambda: heun(False), lambda: heun(True)], "dpm": [dpm]}[kind]
+        st["g_" + kind] = self._capture(st, warmup=3 if kind == "eval" else 2) if self.use_graph else []
+        setattr(self, slot, st)
         return st
+
+    @staticmethod
+    def _capture(st, warmup):
+        """One graph per stage function of st, all in one memory pool, after `warmup` runs of the first on a side stream (they register the
+        weight bank and size the allocator pool).  The device stage indices restart at 0 before every run."""
+        def restart():
+            for k in ("idx", "i0"):
+                if k in st:
+                    st[k].zero_()
+
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                restart()
+                st["fns"][0]()
+        torch.cuda.current_stream().wait_stream(side)
+        restart()
+        graphs = []
+        with hgraph.no_gc():
+            for fn in st["fns"]:
+                graphs.append(torch.cuda.CUDAGraph())
+                with torch.cuda.graph(graphs[-1], pool=graphs[0].pool() if len(graphs) > 1 else None):
+                    fn()
+        return graphs
+
+    @staticmethod
+    def _refresh(st, x, text_emb, uncond_text_emb, known, um, vm):
+        """Every input into the static buffers: a later sample() with another prompt of the same shape must not see the captured one."""
+        st["x"].copy_(x)
+        st["text"].copy_(text_emb)
+        for name, src in (("unc", uncond_text_emb), ("um", um), ("vm", vm)):
+            if st[name] is not None:
+                st[name].copy_(src)
+        for buf, src in zip(st["known"] or (), known or ()):
+            buf.copy_(src)
 
     def _dpm_host_loop(self, x, t_steps, i0, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm):
         """solver="dpmpp_2m" for latents the fused stage does not take (non-fp32 dtype): the rule of sample() with host coefficients."""
@@ -281,10 +259,14 @@ class EDM_Sampler:
         return x
 
     def _eval(self, x, t, text_emb, transition_mean, softness, uncond_text_emb, um=None, vm=None):
-        if self.use_graph:
-            return self._denoise_graphed(x, t, text_emb, transition_mean, softness, uncond_text_emb, um, vm)
-        sig = torch.tensor(t, dtype=self.dtype, device=x.device)
-        return self._denoise(x, sig, text_emb, transition_mean, softness, uncond_text_emb, um, vm)
+        if not self.use_graph:
+            sig = torch.tensor(t, dtype=self.dtype, device=x.device)
+            return self._denoise(x, sig, text_emb, transition_mean, softness, uncond_text_emb, um, vm)
+        st = self._stage_state("eval", x, text_emb, transition_mean, softness, uncond_text_emb, None, um, vm)
+        self._refresh(st, x, text_emb, uncond_text_emb, None, um, vm)
+        st["sig"].fill_(float(t))
+        st["g_eval"][0].replay()
+        return st["out"].clone()
 
     def t_schedule(self, device):
         """Karras rho schedule with the appended 0 (reference :80-87), computed on the host in float64."""
@@ -350,32 +332,16 @@ class EDM_Sampler:
         if fused:
             # no churn: the whole solver runs from a device-side schedule (fused Euler / Heun-correction kernels, or the DPM-Solver++(2M) step
             # kernel, no host arithmetic between the evaluations); with use_graph each stage is one hipGraph replay
-            st = self._stage_state(x_next, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm)
-            st["x"].copy_(x_next)
-            st["text"].copy_(text_emb)
-            if st["unc"] is not None:
-                st["unc"].copy_(uncond_text_emb)
-            for buf, src in zip(st["known"] or (), known or ()):
-                buf.copy_(src)
-            for name, src in (("um", um), ("vm", vm)):
-                if st[name] is not None:
-                    st[name].copy_(src)
+            kind = "heun" if self.fused_heun else "dpm"
+            st = self._stage_state(kind, x_next, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm)
+            self._refresh(st, x_next, text_emb, uncond_text_emb, known, um, vm)
             st["t"].copy_(torch.from_numpy(t_steps))
             st["idx"].fill_(i0)
             if self.fused_dpm:
                 st["i0"].fill_(i0)
-                for i in range(i0, N):
-                    if self.use_graph:
-                        st["g_dpm"].replay()
-                    else:
-                        st["stage"]()
-                return st["x"].clone()
+            runs = [g.replay for g in st["g_" + kind]] or st["fns"]
             for i in range(i0, N):
-                last = i == N - 1
-                if self.use_graph:
-                    (st["g_last"] if last else st["g_heun"]).replay()
-                else:
-                    st["stage"](last)
+                runs[-1 if i == N - 1 else 0]()               # Heun: the Euler-only stage last; DPM: its one stage throughout
             return st["x"].clone()
         if self.solver == "dpmpp_2m":
             return self._dpm_host_loop(x_next, t_steps, i0, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm)

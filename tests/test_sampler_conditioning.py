@@ -348,3 +348,29 @@ def test_router_mask_sampling_eager_vs_graph(real_model):
         EDM_Sampler(m, gn, num_solve_steps=3, guidance=2.0, S_churn=churn).sample(noise, text, -1.2, 1.6, Unet_router_mask=um)
         for net in (m, gn):
             assert net.masks and all(torch.equal(u, um.expand(2, -1)) and bool((v == 1).all()) for u, v in net.masks)
+
+
+@gpu
+@pytest.mark.parametrize("solver,churn", [("heun", 0.0), ("dpmpp_2m", 0.0), ("heun", 1.0)], ids=["heun", "dpmpp_2m", "churn_eval"])
+def test_capture_follows_guide_and_model(_gpu, solver, churn):
+    """A captured sampler recaptures when guide or the model changes between sample() calls: each output equals a fresh eager sampler's.
+    churn_eval: S_churn > 0 with S_max = 0 takes the host loop through the captured evaluation, without noise."""
+    gen = torch.Generator(device=DEV).manual_seed(8)
+    noise = torch.randn(2, 4, 8, 8, device=DEV, generator=gen)
+    text = torch.randn(2, 5, 16, device=DEV, generator=gen)
+    gnet = _MockDenoiser(0.5).to(DEV)
+    kw = dict(num_solve_steps=4, S_churn=churn, S_max=0.0, solver=solver)
+    graphed = EDM_Sampler(_MockDenoiser(0.9).to(DEV), gnet, use_graph=True, **kw)
+
+    def check(tag):
+        out = graphed.sample(noise, text, -1.2, 1.6)
+        eager = EDM_Sampler(graphed.model, gnet, guidance=graphed.guide, **kw).sample(noise, text, -1.2, 1.6)
+        assert (graphed.fused_heun or graphed.fused_dpm) == (churn == 0.0), tag
+        assert torch.equal(out, eager), f"{tag}: the replay differs from eager sampling"
+
+    check("first capture")
+    for guide in (2.5, 1.0):
+        graphed.guide = guide
+        check(f"guide {guide}")
+    graphed.model = _MockDenoiser(0.7).to(DEV)
+    check("new model")
