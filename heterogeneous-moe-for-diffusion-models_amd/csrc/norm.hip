@@ -716,9 +716,13 @@ constexpr int GN1_POOL_THREADS = 1024;                          // one block per
 // ws != null: the statistics of y come as the producing conv's partial slots (the gn1_finalize step folded in: a launch less in the
 // router's serial chain -- where a tiny kernel queues behind the other branch's persistent conv); scale / shift / mean / rstd are
 // then OUTPUTS (kept for the backward).
+// PQ (with ws): also pcnt[n][c] = the number of positions where the ReLU is open and qsum[n][c] = the sum of xh = (y - mean) * rstd over
+// them -- everything the backward's statistics of this layer need, since its incoming gradient is g[n][c] / S at every position.  The mask
+// is the backward's expression (act_grad_f of (y - mean) * rstd * gamma + beta), not y * scale + shift, so the two agree bit for bit.
+template <bool PQ>
 __global__ __launch_bounds__(GN1_POOL_THREADS) void gn1_relu_mean_kernel(float* out, const float* y, float* scale, float* shift, long S, int C,
                                                                        const float* ws, const float* gamma, const float* beta, float* mean,
-                                                                       float* rstd, int slots, float inv_count, float eps) {
+                                                                       float* rstd, int slots, float inv_count, float eps, float* pcnt, float* qsum) {
   extern __shared__ float part[];                              // [threads / C4][C]
   __shared__ float smr[2];
   const int n = blockIdx.x, C4 = C / 4, rows = GN1_POOL_THREADS / C4;
@@ -748,15 +752,31 @@ __global__ __launch_bounds__(GN1_POOL_THREADS) void gn1_relu_mean_kernel(float* 
       shift[(long)n * C + c] = beta[c] - smr[0] * g;
     }
   }
-  f4 acc = (f4)(0.f);
+  f4 acc = (f4)(0.f), pc = (f4)(0.f), qc = (f4)(0.f);
   if (rw < rows) {
-    f4 sc, sh;
+    f4 sc, sh, gm, bt;
+    float m = 0.f, rs = 0.f;
     if (ws) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) { const float g = gamma[4 * cq + e] * smr[1]; sc[e] = g; sh[e] = beta[4 * cq + e] - smr[0] * g; }
     } else {
       sc = *reinterpret_cast<const f4*>(scale + (long)n * C + 4 * cq); sh = *reinterpret_cast<const f4*>(shift + (long)n * C + 4 * cq);
     }
+    if (PQ) {
+      m = smr[0]; rs = smr[1];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { gm[e] = gamma[4 * cq + e]; bt[e] = beta[4 * cq + e]; }
+    }
+    // the ReLU-open count and sum of xh of one loaded vector (PQ only)
+    auto pq = [&](const f4& v) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float xh = (v[e] - m) * rs;
+        const bool open = act_grad_f(xh * gm[e] + bt[e], 1) > 0.f;
+        pc[e] += open ? 1.f : 0.f;
+        qc[e] += open ? xh : 0.f;
+      }
+    };
     const float* yp = y + (long)n * S * C + 4 * cq;
     long s2 = rw;
     for (; s2 + 3 * rows < S; s2 += 4 * rows) {                 // four independent 16-byte loads in flight per thread (one block per sample:
@@ -764,14 +784,17 @@ __global__ __launch_bounds__(GN1_POOL_THREADS) void gn1_relu_mean_kernel(float* 
 #pragma unroll
       for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f4*>(yp + (s2 + (long)u * rows) * C);
 #pragma unroll
-      for (int u = 0; u < 4; ++u)
+      for (int u = 0; u < 4; ++u) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[e] += fmaxf(v[u][e] * sc[e] + sh[e], 0.f);
+        if (PQ) pq(v[u]);
+      }
     }
     for (; s2 < S; s2 += rows) {
       const f4 v = *reinterpret_cast<const f4*>(yp + s2 * C);
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc[e] += fmaxf(v[e] * sc[e] + sh[e], 0.f);
+      if (PQ) pq(v);
     }
     *reinterpret_cast<f4*>(part + (long)rw * C + 4 * cq) = acc;
   }
@@ -781,7 +804,229 @@ __global__ __launch_bounds__(GN1_POOL_THREADS) void gn1_relu_mean_kernel(float* 
     for (int k = 0; k < rows; ++k) t += part[(long)k * C + c];
     out[(long)n * C + c] = t / (float)S;
   }
+  if (PQ) {                                                    // the same fixed-order reduction for the two extra sums
+#pragma unroll
+    for (int k2 = 0; k2 < 2; ++k2) {
+      __syncthreads();
+      if (rw < rows) *reinterpret_cast<f4*>(part + (long)rw * C + 4 * cq) = k2 ? qc : pc;
+      __syncthreads();
+      for (int c = threadIdx.x; c < C; c += GN1_POOL_THREADS) {
+        float t = 0.f;
+        for (int k = 0; k < rows; ++k) t += part[(long)k * C + c];
+        (k2 ? qsum : pcnt)[(long)n * C + c] = t;
+      }
+    }
+  }
 }
+
+// ---- router-trunk GroupNorm(1, C) + ReLU backward with bf16 gradients (ops._TrunkFn.backward on the streaming bf16 kernels).  Per layer
+// at most two launches: gn1t_stats_kernel (none for the pooled last layer, whose sums come from the forward's pcnt / qsum) and
+// gn1t_apply_kernel, which writes both bf16 operands of the conv's backward.  Every sum runs in an order fixed by S and C alone -- never by
+// the other samples of the batch -- and none uses a float atomic.  8 channels per thread: 16-byte accesses to every tensor.
+constexpr int GN1T_THREADS = 256;
+DEVI float wave_sum(float v) {                                 // fixed-shape shuffle tree; the total lands in lane 0
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+  return v;
+}
+// grid (N, parts): block (n, p) takes the rows [p * rpp, (p + 1) * rpp) of sample n; thread t the channels 8 (t % cv) .. + 7 of the rows
+// t / cv + k * R (R = 256 / cv; threads past R * cv idle).  Writes ws[n][p][2] = the (s1, s2) partials, s1 = sum dz' gamma, s2 = sum dz' gamma xh,
+// and wsc[k][c][n * parts + p] (k = 0: dgamma = sum dz' xh, k = 1: dbeta = sum dz'), channel-major so that the reduction reads them contiguously.
+__global__ __launch_bounds__(GN1T_THREADS) void gn1t_stats_kernel(float* ws, float* wsc, const bf16* dz, const float* x, const float* gamma,
+                                                                const float* beta, const float* mean, const float* rstd, long S, int C, int parts, long NP) {
+  __shared__ float lds[2][GN1T_THREADS * 8];                    // [R][C] per-thread channel partials (R * C <= 2048)
+  __shared__ float red[2][GN1T_THREADS / 64];
+  const int n = blockIdx.x, p = blockIdx.y, cv = C / 8, R = GN1T_THREADS / cv;
+  const int c0 = ((int)threadIdx.x % cv) * 8, rt = (int)threadIdx.x / cv;
+  const long rpp = (S + parts - 1) / parts;
+  const long r0 = min((long)p * rpp, S), r1 = min(r0 + rpp, S);
+  const float m = mean[n], rs = rstd[n];
+  float gm[8], bt[8], dg[8], db[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { gm[j] = gamma[c0 + j]; bt[j] = beta[c0 + j]; dg[j] = 0.f; db[j] = 0.f; }
+  float a1 = 0.f, a2 = 0.f;
+  auto acc = [&](const float* f, const float* d) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float xh = (f[j] - m) * rs;
+      const float dzz = d[j] * act_grad_f(xh * gm[j] + bt[j], 1);
+      a1 += dzz * gm[j]; a2 += dzz * gm[j] * xh;
+      dg[j] += dzz * xh; db[j] += dzz;
+    }
+  };
+  if (rt < R) {
+    const float* xp = x + (long)n * S * C + c0;
+    const bf16* dp = dz + (long)n * S * C + c0;
+    long r = r0 + rt;
+    for (; r + R < r1; r += 2 * R) {                            // two rows' loads (six 16-byte accesses) in flight per thread
+      float f0[8], f1[8], d0[8], d1[8];
+      vload<float>(f0, xp + r * C); vload<float>(f0 + 4, xp + r * C + 4); vload<bf16>(d0, dp + r * C);
+      vload<float>(f1, xp + (r + R) * C); vload<float>(f1 + 4, xp + (r + R) * C + 4); vload<bf16>(d1, dp + (r + R) * C);
+      acc(f0, d0); acc(f1, d1);
+    }
+    if (r < r1) {
+      float f0[8], d0[8];
+      vload<float>(f0, xp + r * C); vload<float>(f0 + 4, xp + r * C + 4); vload<bf16>(d0, dp + r * C);
+      acc(f0, d0);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { lds[0][rt * C + c0 + j] = dg[j]; lds[1][rt * C + c0 + j] = db[j]; }
+  }
+  a1 = wave_sum(a1); a2 = wave_sum(a2);
+  const int wv = threadIdx.x / 64;
+  if (threadIdx.x % 64 == 0) { red[0][wv] = a1; red[1][wv] = a2; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float u = 0.f, w = 0.f;
+#pragma unroll
+    for (int k = 0; k < GN1T_THREADS / 64; ++k) { u += red[0][k]; w += red[1][k]; }
+    ws[((long)n * parts + p) * 2] = u; ws[((long)n * parts + p) * 2 + 1] = w;
+  }
+  for (int c = threadIdx.x; c < C; c += GN1T_THREADS) {
+    float tg = 0.f, tb = 0.f;
+    for (int k = 0; k < R; ++k) { tg += lds[0][k * C + c]; tb += lds[1][k * C + c]; }
+    wsc[(long)c * NP + (long)n * parts + p] = tg; wsc[((long)C + c) * NP + (long)n * parts + p] = tb;
+  }
+}
+// grid: N * P2 row-range blocks, then ceil(C / 4) channel blocks.
+// Row-range block (n, p) first forms s1 / s2 of sample n: the sum of its `parts` statistics slots (dz given) or, for the pooled layer (g
+// given: the incoming gradient is g[n][c] * gscale at every position), s1 = sum_c g gscale gamma pcnt[n][c] and s2 = the same with qsum.
+// Every block of the sample runs the same code in the same order and gets the same bits.  Then, over its rows:
+//   dx[n][s][c] = bf16(rstd (dz' gamma - (s1 + xh s2) / (S C))),  dz' = dz relu'(xh gamma + beta),  xh = (x - mean) rstd
+//   a[n][s][i]  = bf16(relu(xin * scale[n][i] + shift[n][i]))     (scale == null: bf16(xin))  -- gn1t_act_kernel's arithmetic
+// Channel block b: channels 4 b .. 4 b + 3, one wave each: dgamma[c] += the sum over (n, p) of the slots (or of g gscale qsum), dbeta likewise.
+__global__ __launch_bounds__(GN1T_THREADS) void gn1t_apply_kernel(bf16* dx, bf16* a, float* dgamma, float* dbeta, const float* ws, const float* wsc,
+                                                                int parts, const bf16* dz, const float* g, float gscale, const float* pcnt,
+                                                                const float* qsum, const float* x, const float* gamma, const float* beta,
+                                                                const float* mean, const float* rstd, const float* xin, const float* scale,
+                                                                const float* shift, int N, long S, int C, int CI, int P2) {
+  const int nrb = N * P2, lane = threadIdx.x % 64, wv = threadIdx.x / 64;
+  if ((int)blockIdx.x >= nrb) {
+    const int c = ((int)blockIdx.x - nrb) * (GN1T_THREADS / 64) + wv;
+    if (c >= C) return;
+    float sg = 0.f, sb = 0.f;
+    if (g) {
+      for (int i = lane; i < N; i += 64) {
+        const float gs = g[(long)i * C + c] * gscale;
+        sg += gs * qsum[(long)i * C + c]; sb += gs * pcnt[(long)i * C + c];
+      }
+    } else {
+      const long NP = (long)N * parts;
+      const float* pg = wsc + (long)c * NP;
+      const float* pb = wsc + ((long)C + c) * NP;
+#pragma unroll 4
+      for (long i = lane; i < NP; i += 64) { sg += pg[i]; sb += pb[i]; }
+    }
+    sg = wave_sum(sg); sb = wave_sum(sb);
+    if (lane == 0) { dgamma[c] += sg; dbeta[c] += sb; }
+    return;
+  }
+  __shared__ float red[2][GN1T_THREADS / 64];
+  __shared__ float su[2];
+  const int n = blockIdx.x / P2, p = blockIdx.x % P2;
+  if (g) {
+    float u = 0.f, w = 0.f;
+    for (int c = threadIdx.x; c < C; c += GN1T_THREADS) {
+      const float gg = g[(long)n * C + c] * gscale * gamma[c];
+      u += gg * pcnt[(long)n * C + c]; w += gg * qsum[(long)n * C + c];
+    }
+    u = wave_sum(u); w = wave_sum(w);
+    if (lane == 0) { red[0][wv] = u; red[1][wv] = w; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      u = 0.f; w = 0.f;
+#pragma unroll
+      for (int k = 0; k < GN1T_THREADS / 64; ++k) { u += red[0][k]; w += red[1][k]; }
+      su[0] = u; su[1] = w;
+    }
+  } else if (threadIdx.x == 0) {
+    float u = 0.f, w = 0.f;
+    for (int k = 0; k < parts; ++k) { u += ws[((long)n * parts + k) * 2]; w += ws[((long)n * parts + k) * 2 + 1]; }
+    su[0] = u; su[1] = w;
+  }
+  __syncthreads();
+  const long rpp = (S + P2 - 1) / P2;
+  const long r0 = min((long)p * rpp, S), r1 = min(r0 + rpp, S);
+  {                                                             // dx
+    const int cv = C / 8, R = GN1T_THREADS / cv;
+    const int c0 = ((int)threadIdx.x % cv) * 8, rt = (int)threadIdx.x / cv;
+    const float m = mean[n], rs = rstd[n], u = su[0], w = su[1], invm = 1.f / (float)(S * C);
+    float gm[8], bt[8], gd[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { gm[j] = gamma[c0 + j]; bt[j] = beta[c0 + j]; gd[j] = g ? g[(long)n * C + c0 + j] * gscale : 0.f; }
+    auto out = [&](float* f, const float* d) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float xh = (f[j] - m) * rs;
+        const float dzz = d[j] * act_grad_f(xh * gm[j] + bt[j], 1);
+        f[j] = rs * (dzz * gm[j] - invm * (u + xh * w));
+      }
+    };
+    if (rt < R) {
+      const float* xp = x + (long)n * S * C + c0;
+      const bf16* dp = dz ? dz + (long)n * S * C + c0 : nullptr;
+      bf16* op = dx + (long)n * S * C + c0;
+      long r = r0 + rt;
+      for (; r + R < r1; r += 2 * R) {
+        float f0[8], f1[8], d0[8], d1[8];
+        vload<float>(f0, xp + r * C); vload<float>(f0 + 4, xp + r * C + 4);
+        vload<float>(f1, xp + (r + R) * C); vload<float>(f1 + 4, xp + (r + R) * C + 4);
+        if (dp) { vload<bf16>(d0, dp + r * C); vload<bf16>(d1, dp + (r + R) * C); }
+        else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) { d0[j] = gd[j]; d1[j] = gd[j]; }
+        }
+        out(f0, d0); out(f1, d1);
+        vstore<bf16>(op + r * C, f0); vstore<bf16>(op + (r + R) * C, f1);
+      }
+      if (r < r1) {
+        float f0[8], d0[8];
+        vload<float>(f0, xp + r * C); vload<float>(f0 + 4, xp + r * C + 4);
+        if (dp) vload<bf16>(d0, dp + r * C);
+        else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) d0[j] = gd[j];
+        }
+        out(f0, d0);
+        vstore<bf16>(op + r * C, f0);
+      }
+    }
+  }
+  {                                                             // a
+    const int cv = CI / 8, R = GN1T_THREADS / cv;
+    const int c0 = ((int)threadIdx.x % cv) * 8, rt = (int)threadIdx.x / cv;
+    float sc[8], sh[8];
+    if (scale) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { sc[j] = scale[(long)n * CI + c0 + j]; sh[j] = shift[(long)n * CI + c0 + j]; }
+    }
+    auto act = [&](float* f) {
+      if (scale) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] = fmaxf(f[j] * sc[j] + sh[j], 0.f);
+      }
+    };
+    if (rt < R) {
+      const float* ip = xin + (long)n * S * CI + c0;
+      bf16* op = a + (long)n * S * CI + c0;
+      long r = r0 + rt;
+      for (; r + R < r1; r += 2 * R) {
+        float f0[8], f1[8];
+        vload<float>(f0, ip + r * CI); vload<float>(f0 + 4, ip + r * CI + 4);
+        vload<float>(f1, ip + (r + R) * CI); vload<float>(f1 + 4, ip + (r + R) * CI + 4);
+        act(f0); act(f1);
+        vstore<bf16>(op + r * CI, f0); vstore<bf16>(op + (r + R) * CI, f1);
+      }
+      if (r < r1) {
+        float f0[8];
+        vload<float>(f0, ip + r * CI); vload<float>(f0 + 4, ip + r * CI + 4);
+        act(f0);
+        vstore<bf16>(op + r * CI, f0);
+      }
+    }
+  }
+}
+static inline int gn1t_parts(long S) { const long p = S / 128; return (int)(p < 1 ? 1 : (p > 16 ? 16 : p)); }
 }  // namespace
 
 extern "C" {
@@ -912,6 +1157,43 @@ int hdmoe_gn1t_act(void* out, const float* y, const float* scale, const float* s
   hipLaunchKernelGGL(gn1t_act_kernel, dim3(gb), dim3(TPB), 0, stream, (bf16*)out, y, scale, shift, S, C, nvec);
   return hdmoe_launch_status();
 }
+/* Floats of the statistics workspace of hdmoe_gn1t_stats: 2 N parts (s1 / s2 slots) + 2 C N parts (per-channel slots); parts a function of S. */
+int hdmoe_gn1t_stats_floats(int N, long S, int C) {
+  const long f = 2L * N * gn1t_parts(S) * (1 + (long)C);
+  return f > 0x7fffffffL ? -1 : (int)f;
+}
+/* Router-trunk backward, bf16 mode, layers whose gradient dz (bf16 [N][S][C]) comes from the next conv: the GroupNorm(1, C) + ReLU backward sums
+ * of every (sample, row range) into fixed slots of ws (hdmoe_gn1t_stats_floats floats).  x = the conv output y (fp32).  C % 8 == 0, C <= 2048. */
+int hdmoe_gn1t_stats(float* ws, const void* dz, const float* x, const float* gamma, const float* beta, const float* mean, const float* rstd, int N,
+                     long S, int C, hipStream_t stream) {
+  if (!ws || !dz || !x || !gamma || !beta || !mean || !rstd || N < 1 || S < 1 || C < 8 || C % 8 || C > 2048 || !al16(dz) || !al16(x)) return HDMOE_EINVAL;
+  const int parts = gn1t_parts(S);
+  const long NP = (long)N * parts;
+  hipLaunchKernelGGL(gn1t_stats_kernel, dim3(N, parts), dim3(GN1T_THREADS), 0, stream, ws, ws + 2 * NP, (const bf16*)dz, x, gamma, beta, mean, rstd,
+                     S, C, parts, NP);
+  return hdmoe_launch_status();
+}
+/* ... and in one launch both bf16 operands of that layer's conv backward: dx = the GroupNorm(1, C) + ReLU input gradient (from dz and ws of
+ * hdmoe_gn1t_stats, or -- dz == null, the pooled last layer -- from g[n][c] * gscale at every position and the forward's pcnt / qsum) and
+ * a = relu(xin * scale[n][i] + shift[n][i]) ([N][S][CI]; scale == null: bf16(xin)), bit for bit what hdmoe_gn1t_act writes.  dgamma / dbeta
+ * accumulate.  C, CI % 8 == 0 and <= 2048. */
+int hdmoe_gn1t_apply(void* dx, void* a, float* dgamma, float* dbeta, const float* ws, const void* dz, const float* g, float gscale, const float* pcnt,
+                     const float* qsum, const float* x, const float* gamma, const float* beta, const float* mean, const float* rstd, const float* xin,
+                     const float* scale, const float* shift, int N, long S, int C, int CI, hipStream_t stream) {
+  if (!dx || !a || !dgamma || !dbeta || !x || !gamma || !beta || !mean || !rstd || !xin || (scale == nullptr) != (shift == nullptr)) return HDMOE_EINVAL;
+  if (dz ? !ws : (!g || !pcnt || !qsum)) return HDMOE_EINVAL;
+  if (N < 1 || S < 1 || C < 8 || C % 8 || C > 2048 || CI < 8 || CI % 8 || CI > 2048 || !al16(dx) || !al16(a) || !al16(dz) || !al16(x) || !al16(xin))
+    return HDMOE_EINVAL;
+  int P2 = (2048 + N - 1) / N;                                  // row ranges per sample: ~2048 row-range blocks (the results do not depend on it)
+  if (P2 > S / 16) P2 = (int)(S / 16);
+  if (P2 < 1) P2 = 1;
+  const int parts = gn1t_parts(S);
+  const long NP = (long)N * parts;
+  const unsigned grid = (unsigned)(N * P2 + (C + GN1T_THREADS / 64 - 1) / (GN1T_THREADS / 64));
+  hipLaunchKernelGGL(gn1t_apply_kernel, dim3(grid), dim3(GN1T_THREADS), 0, stream, (bf16*)dx, (bf16*)a, dgamma, dbeta, ws, dz ? ws + 2 * NP : nullptr,
+                     parts, (const bf16*)dz, g, gscale, pcnt, qsum, x, gamma, beta, mean, rstd, xin, scale, shift, N, S, C, CI, P2);
+  return hdmoe_launch_status();
+}
 int hdmoe_layernorm_fwd(void* y, float* mean, float* rstd, const void* x, const float* gamma, const float* beta, long rows,
                         int C, float eps, int dtype, hipStream_t stream) {
   DT_SWITCH(dtype, if (row_vec_ok<T>(C, y, x, nullptr, nullptr)) {
@@ -951,8 +1233,9 @@ int hdmoe_gn1_finalize(float* scale, float* shift, float* mean, float* rstd, con
 int hdmoe_gn1_relu_mean(float* out, const float* y, const float* scale, const float* shift, int N, long S, int C, hipStream_t stream) {
   if (!out || !y || !scale || !shift || N < 1 || S < 1 || C < 4 || C % 4 || C > 1024) return HDMOE_EINVAL;
   const int rows = GN1_POOL_THREADS / (C / 4);
-  hipLaunchKernelGGL(gn1_relu_mean_kernel, dim3(N), dim3(GN1_POOL_THREADS), (size_t)rows * C * sizeof(float), stream, out, y, (float*)scale, (float*)shift,
-                     S, C, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr, 0, 0.f, 0.f);
+  hipLaunchKernelGGL(gn1_relu_mean_kernel<false>, dim3(N), dim3(GN1_POOL_THREADS), (size_t)rows * C * sizeof(float), stream, out, y, (float*)scale,
+                     (float*)shift, S, C, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr, 0, 0.f, 0.f,
+                     (float*)nullptr, (float*)nullptr);
   return hdmoe_launch_status();
 }
 /* hdmoe_gn1_finalize + hdmoe_gn1_relu_mean in one launch: statistics from the conv's partial slots ws [N][slots][2]; scale / shift [N][C] and
@@ -962,8 +1245,20 @@ int hdmoe_gn1_finalize_relu_mean(float* out, float* scale, float* shift, float* 
   if (!out || !y || !scale || !shift || !mean || !rstd || !ws || !gamma || !beta || N < 1 || slots < 1 || S < 1 || C < 4 || C % 4 || C > 1024)
     return HDMOE_EINVAL;
   const int rows = GN1_POOL_THREADS / (C / 4);
-  hipLaunchKernelGGL(gn1_relu_mean_kernel, dim3(N), dim3(GN1_POOL_THREADS), (size_t)rows * C * sizeof(float), stream, out, y, scale, shift, S, C, ws,
-                     gamma, beta, mean, rstd, slots, 1.f / ((float)S * (float)C), eps);
+  hipLaunchKernelGGL(gn1_relu_mean_kernel<false>, dim3(N), dim3(GN1_POOL_THREADS), (size_t)rows * C * sizeof(float), stream, out, y, scale, shift, S, C, ws,
+                     gamma, beta, mean, rstd, slots, 1.f / ((float)S * (float)C), eps, (float*)nullptr, (float*)nullptr);
+  return hdmoe_launch_status();
+}
+/* The same, and pcnt / qsum [N][C] (fp32): per channel, the number of positions where the ReLU is open and the sum of the normalised value
+ * (y - mean) * rstd over them -- the statistics hdmoe_gn1t_apply derives this layer's backward sums from when its gradient comes from the pool. */
+int hdmoe_gn1_finalize_relu_mean_pq(float* out, float* scale, float* shift, float* mean, float* rstd, float* pcnt, float* qsum, const float* y,
+                                    const float* ws, const float* gamma, const float* beta, int N, int slots, long S, int C, float eps, hipStream_t stream) {
+  if (!out || !y || !scale || !shift || !mean || !rstd || !pcnt || !qsum || !ws || !gamma || !beta || N < 1 || slots < 1 || S < 1 || C < 4 || C % 4 ||
+      C > 1024)
+    return HDMOE_EINVAL;
+  const int rows = GN1_POOL_THREADS / (C / 4);
+  hipLaunchKernelGGL(gn1_relu_mean_kernel<true>, dim3(N), dim3(GN1_POOL_THREADS), (size_t)rows * C * sizeof(float), stream, out, y, scale, shift, S, C, ws,
+                     gamma, beta, mean, rstd, slots, 1.f / ((float)S * (float)C), eps, pcnt, qsum);
   return hdmoe_launch_status();
 }
 

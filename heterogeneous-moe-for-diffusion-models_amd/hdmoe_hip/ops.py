@@ -1910,12 +1910,19 @@ class _TrunkFn(torch.autograd.Function):
     The normalised activations are never written.  ``tensors`` = (weight, gamma, beta) x 3; ``ents`` the ready weight-bank entries."""
 
     @staticmethod
-    def forward(ctx, x, ents, bank, eps, *tensors):
+    def forward(ctx, x, ents, bank, eps, grad, *tensors):
         x = _c(x)
         N, H, W, _ = x.shape
         S = H * W
         inp, sc, sh = x, None, None
         saved = []
+        # the backward takes the bf16 streaming path: the last layer's backward sums then come from two (N, C) statistics of this forward.
+        # `grad`: grad mode was on at the call and something requires a gradient (inside forward() grad mode is always off, and
+        # ctx.needs_input_grad says nothing about a no_grad caller)
+        pq = (None, None)
+        if grad and _trunk_use7(N, H, W, tensors):
+            C3 = int(tensors[6].shape[0])
+            pq = (torch.empty((N, C3), dtype=torch.float32, device=x.device), torch.empty((N, C3), dtype=torch.float32, device=x.device))
         for l in range(3):
             w, gamma, beta = tensors[3 * l:3 * l + 3]
             O, I = int(w.shape[0]), int(w.shape[1])
@@ -1936,10 +1943,13 @@ class _TrunkFn(torch.autograd.Function):
                 call("hdmoe_gn1_finalize", sc, sh, mean, rstd, ws, gamma, beta, N, slots, O, S * O, eps[l])
             else:                                               # last layer: statistics -> scale / shift inside the pooled read's launch
                 out = torch.empty((N, O), dtype=torch.float32, device=x.device)
-                call("hdmoe_gn1_finalize_relu_mean", out, sc, sh, mean, rstd, y, ws, gamma, beta, N, slots, S, O, eps[l])
+                if pq[0] is not None:
+                    call("hdmoe_gn1_finalize_relu_mean_pq", out, sc, sh, mean, rstd, *pq, y, ws, gamma, beta, N, slots, S, O, eps[l])
+                else:
+                    call("hdmoe_gn1_finalize_relu_mean", out, sc, sh, mean, rstd, y, ws, gamma, beta, N, slots, S, O, eps[l])
             saved += [y, sc, sh, mean, rstd]
             inp = y
-        ctx.save_for_backward(x, *saved, *tensors)
+        ctx.save_for_backward(x, *saved, *pq, *tensors)
         ctx.ents, ctx.bank = ents, bank
         STATS["trunk"] += 1
         return out
@@ -1947,7 +1957,7 @@ class _TrunkFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, *rest = ctx.saved_tensors
-        saved, tensors = rest[:15], rest[15:]
+        saved, (pcnt, qsum), tensors = rest[:15], rest[15:17], rest[17:]
         N, H, W, _ = x.shape
         S = H * W
         ents, bank = ctx.ents, ctx.bank
@@ -1955,11 +1965,11 @@ class _TrunkFn(torch.autograd.Function):
         bufs, ret = _param_grads(params)
         da = None
         # bf16-operand mode on 32 x 32 maps with enough samples: the trunk backward as PLAIN bf16 layers on the streaming kernels (csrc/conv7_body.h,
-        # wgrad7_body.h) -- the GroupNorm backward writes dy_l in bf16, a small pass materialises the conv input relu(gn(y_{l-1})) in bf16
-        # (the forward never stores it), and the fused dgrad + weight-gradient launch reads both by LDS-DMA.  Same arithmetic as the hi-only
+        # wgrad7_body.h) -- the GroupNorm backward writes dy_l in bf16 and, in the same launch, materialises the conv input relu(gn(y_{l-1}))
+        # in bf16 (the forward never stores it), and the fused dgrad + weight-gradient launch reads both by LDS-DMA.  Same arithmetic as the hi-only
         # split path (bf16 operands, fp32 accumulation) except that the input gradient between two layers is stored in bf16.
-        use7 = (TRUNK_BWD_BF16 and H == 32 and W == 32 and N >= C7_MINN
-                and all(int(tensors[3 * l].shape[0]) % 32 == 0 and int(tensors[3 * l].shape[1]) % 32 == 0 for l in range(3)))
+        use7 = _trunk_use7(N, H, W, tensors)
+        assert not use7 or pcnt is not None
         for l in (2, 1, 0):
             w, gamma, beta = tensors[3 * l:3 * l + 3]
             y, sc, sh, mean, rstd = saved[5 * l:5 * l + 5]
@@ -1968,13 +1978,19 @@ class _TrunkFn(torch.autograd.Function):
             xin = x if l == 0 else saved[5 * (l - 1)]
             isc, ish = (None, None) if l == 0 else (saved[5 * (l - 1) + 1], saved[5 * (l - 1) + 2])
             wdstride = 9 * I * ((O + 15) // 16 * 16)
-            ws = torch.empty(2 * N, dtype=torch.float32, device=x.device)
             if use7:
+                # GroupNorm + ReLU backward -> dy_l and relu(gn(y_{l-1})) -> the conv input, both bf16, in one launch (csrc/norm.hip
+                # gn1t_apply_kernel); its sums come from a statistics launch over (y_l, da), or for the pooled last layer from the forward's
+                # pcnt / qsum -- fixed summation orders, no float atomics
                 dyb = torch.empty(y.shape, dtype=torch.bfloat16, device=x.device)
-                call("hdmoe_gn1t_bwd", dyb, bufs[2 * l], bufs[2 * l + 1], ws, None if l == 2 else da, _f32(g) if l == 2 else None,
-                     1.0 / S if l == 2 else 1.0, y, gamma, beta, mean, rstd, N, S, O)
                 a_in = torch.empty(xin.shape, dtype=torch.bfloat16, device=x.device)
-                call("hdmoe_gn1t_act", a_in, xin, isc, ish, N, S, I)
+                stw = None
+                if l < 2:
+                    stw = torch.empty(lib().hdmoe_gn1t_stats_floats(N, S, O), dtype=torch.float32, device=x.device)
+                    call("hdmoe_gn1t_stats", stw, da, y, gamma, beta, mean, rstd, N, S, O)
+                call("hdmoe_gn1t_apply", dyb, a_in, bufs[2 * l], bufs[2 * l + 1], stw, None if l == 2 else da, _f32(g) if l == 2 else None,
+                     1.0 / S if l == 2 else 1.0, pcnt if l == 2 else None, qsum if l == 2 else None, y, gamma, beta, mean, rstd,
+                     xin, isc, ish, N, S, O, I)
                 arena = _w6_workspace("own", x.device, _w6_kib(1, N, H, W, I, O, [3], [3], 1))
                 da = torch.empty(xin.shape, dtype=torch.bfloat16, device=x.device)
                 if not _fused_bwd(bank, ent, dict(name="bwd7_trunk_kernel", dtype="bfloat16", seg=None, N=N, HW=S, O=O, I=I, taps=[9], mult=2.0),
@@ -1987,6 +2003,7 @@ class _TrunkFn(torch.autograd.Function):
                     da = da32
                 continue
             dy = torch.empty_like(y)
+            ws = torch.empty(2 * N, dtype=torch.float32, device=x.device)
             if l == 2:      # d(mean over S of a_3): g[n][c] / S at every position, read from the (N, C) tensor (no materialised broadcast)
                 call("hdmoe_groupnorm_bwd_bcast", dy, bufs[2 * l], bufs[2 * l + 1], ws, _f32(g), 1.0 / S, y, gamma, beta, mean, rstd, N, S, O, 1, ACT_RELU, 0)
             else:
@@ -1997,10 +2014,16 @@ class _TrunkFn(torch.autograd.Function):
                               "hdmoe_conv_bwd6s", xin, dy, ent.wd, da, (None, 1, wdstride, wdstride, N, H, W, I, O, [3], [3], [1], [1], 1.0), arena,
                               (isc, ish, 1, 1 if TRUNK_BWD_BF16 else 0), (None, 1, N, H, W, I, O, F32S, [3]), ("trunk_bwd",)):
                 raise RuntimeError("router trunk backward: layer outside the fused backward kernel's domain")
-        out = [da, None, None, None]
+        out = [da, None, None, None, None]
         for l in range(3):
             out += [None, ret[2 * l], ret[2 * l + 1]]
         return tuple(out)
+
+
+def _trunk_use7(N: int, H: int, W: int, tensors) -> bool:
+    """Does _TrunkFn's backward run as plain bf16 layers on the streaming kernels (32 x 32 maps, enough samples, widths % 32)?"""
+    return (TRUNK_BWD_BF16 and H == 32 and W == 32 and N >= C7_MINN
+            and all(int(tensors[3 * l].shape[0]) % 32 == 0 and int(tensors[3 * l].shape[1]) % 32 == 0 for l in range(3)))
 
 
 def trunk_ok(x: Tensor, convs) -> bool:
@@ -2033,7 +2056,8 @@ def router_trunk(x: Tensor, convs, norms) -> Optional[Tensor]:
     tensors = []
     for w, nm in zip(convs, norms):
         tensors += [w, nm.weight, nm.bias]
-    return _TrunkFn.apply(x, ents, _bank.ACTIVE, [float(nm.eps) for nm in norms], *tensors)
+    grad = torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in tensors))
+    return _TrunkFn.apply(x, ents, _bank.ACTIVE, [float(nm.eps) for nm in norms], grad, *tensors)
 
 
 class _LayerNormFn(torch.autograd.Function):

@@ -105,6 +105,9 @@ int hdmoe_gn1_finalize(float* scale, float* shift, float* mean, float* rstd, con
 int hdmoe_gn1_relu_mean(float* out, const float* y, const float* scale, const float* shift, int N, long S, int C, HS stream);
 int hdmoe_gn1_finalize_relu_mean(float* out, float* scale, float* shift, float* mean, float* rstd, const float* y, const float* ws,
                                  const float* gamma, const float* beta, int N, int slots, long S, int C, float eps, HS stream);   /* the two above in one launch */
+int hdmoe_gn1_finalize_relu_mean_pq(float* out, float* scale, float* shift, float* mean, float* rstd, float* pcnt, float* qsum, const float* y,
+                                    const float* ws, const float* gamma, const float* beta, int N, int slots, long S, int C, float eps, HS stream);
+    /* the same, and pcnt / qsum [N][C]: the count of positions where the ReLU is open and the sum of (y - mean) * rstd over them (for hdmoe_gn1t_apply) */
 int hdmoe_conv_wgrad6_reduce_batch(float* const* G, const int* const* seg, float* const* ws, const int* dims, int n, HS stream);
 
 /* development hook of the conv6 kernels: `buf` = device array of 8 x 64 uint64 receiving workgroup 0's in-kernel clock stamps
@@ -233,6 +236,16 @@ int hdmoe_groupnorm_bwd_split(void* dx, float* dgamma, float* dbeta, float* ws, 
 int hdmoe_gn1t_bwd(void* dx, float* dgamma, float* dbeta, float* ws, const void* dz, const float* g, float gscale, const float* x, const float* gamma,
                    const float* beta, const float* mean, const float* rstd, int N, long S, int C, HS stream);
 int hdmoe_gn1t_act(void* out, const float* y, const float* scale, const float* shift, int N, long S, int C, HS stream);
+/* The same backward in at most two launches per layer, with every sum in a fixed order that does not depend on the rest of the batch and no
+ * float atomics.  gn1t_stats: from dz (bf16 [N][S][C]) the per-(sample, row range) sums into ws (gn1t_stats_floats floats).  gn1t_apply: dx (bf16)
+ * from dz and ws, or (dz == null) from g[n][c] * gscale at every position and the forward's pcnt / qsum (hdmoe_gn1_finalize_relu_mean_pq);
+ * in the same launch a = gn1t_act(xin, scale, shift) ([N][S][CI], bit-identical); dgamma / dbeta accumulate.  C, CI % 8 == 0, <= 2048. */
+int hdmoe_gn1t_stats_floats(int N, long S, int C);
+int hdmoe_gn1t_stats(float* ws, const void* dz, const float* x, const float* gamma, const float* beta, const float* mean, const float* rstd, int N,
+                     long S, int C, HS stream);
+int hdmoe_gn1t_apply(void* dx, void* a, float* dgamma, float* dbeta, const float* ws, const void* dz, const float* g, float gscale, const float* pcnt,
+                     const float* qsum, const float* x, const float* gamma, const float* beta, const float* mean, const float* rstd, const float* xin,
+                     const float* scale, const float* shift, int N, long S, int C, int CI, HS stream);
 int hdmoe_layernorm_fwd(void* y, float* mean, float* rstd, const void* x, const float* gamma, const float* beta, long rows,
                         int C, float eps, int dtype, HS stream);
 int hdmoe_layernorm_bwd(void* dx, float* dgamma, float* dbeta, const void* dy, const void* x, const float* gamma,
