@@ -112,6 +112,7 @@ int blk6_launch(const B6Plan& plan, hipStream_t stream) {
     if (plan.NTM == 2) { if (plan.NTB == 2) B6_LAUNCH(W, 2, 2); else B6_LAUNCH(W, 2, 1); }       \
     else { if (plan.NTB == 2) B6_LAUNCH(W, 1, 2); else B6_LAUNCH(W, 1, 1); }                     \
   } while (0)
+  hdmoe_count_selection(HDMOE_SEL_BLK6);
   if (plan.NW == 4) B6_GO(4); else B6_GO(8);
   return hdmoe_launch_status();
 }

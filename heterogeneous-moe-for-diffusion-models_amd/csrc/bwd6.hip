@@ -120,6 +120,7 @@ int hdmoe_conv_bwd6s(const void* x, const void* dy, const void* wd, void* dx, fl
   C6SPlan cp;
   if (conv6s_plan(c, wd_plane, nullptr, cp)) return 1;
   cp.sa.nprod = hi_only ? 1 : 3;
+  hdmoe_count_selection(HDMOE_SEL_BWD6S);
 #define BWD6S_GO(Nt)                                                                             \
   do {                                                                                           \
     if (wp.TWS == 5) { if (wp.OT == 2) launch_bwd6s<Nt, 5, 2>(cp, wp, stream); else launch_bwd6s<Nt, 5, 1>(cp, wp, stream); } \
@@ -154,12 +155,24 @@ int hdmoe_conv_bwd6(const void* x, const void* dy, const void* wd, void* dx, flo
     if (wp.TWS == 5) launch_bwd7<Co, 3, 5, 0>(cp7, wp, stream);                                                               \
     else { if (wp.OT == 2) launch_bwd7<Co, 3, 4, 2>(cp7, wp, stream); else launch_bwd7<Co, 3, 4, 1>(cp7, wp, stream); }            \
   } while (0)
+      if (wp.TWS == 5) {
+        hdmoe_count_selection(HDMOE_SEL_BWD7_32);
+        if (wp.c[0].chunks) {
+          hdmoe_count_selection(HDMOE_SEL_BWD7_32_WGRAD8);
+          hdmoe_count_selection(wp.c[0].icw == 2 ? (wp.c[0].ocw == 2 ? HDMOE_SEL_WGRAD8_C22 : HDMOE_SEL_WGRAD8_C21)
+                                                 : (wp.c[0].ocw == 2 ? HDMOE_SEL_WGRAD8_C12 : HDMOE_SEL_WGRAD8_C11));
+        }
+        if (wp.c[1].chunks) hdmoe_count_selection(HDMOE_SEL_BWD7_32_WGRAD7);
+      } else {
+        hdmoe_count_selection(wp.OT == 2 ? HDMOE_SEL_BWD7_16_OT2 : HDMOE_SEL_BWD7_16_OT1);
+      }
       if (cp7.CO == 2) BWD7_GO(2); else BWD7_GO(1);
       return hdmoe_launch_status();
     }
   }
   C6Plan cp;
   if (conv6_plan(c, dtype, cp)) return 1;
+  hdmoe_count_selection(HDMOE_SEL_BWD6);
 #define BWD6_GO(M, Nt)                                                                           \
   do {                                                                                           \
     if (wp.TWS == 5) { if (wp.OT == 2) launch_bwd6<M, Nt, 5, 2>(cp, wp, stream); else launch_bwd6<M, Nt, 5, 1>(cp, wp, stream); } \

@@ -16,11 +16,14 @@
 //   conv_wgrad2_kernel            pixel tile + halo in LDS, taps owned per wave, transposing LDS reads (bf16), one fp32 atomic
 //                                 flush per workgroup into a [tap][O][I] slab (contiguous I: full-rate atomic shape,
 //                                 MI355X_MICROARCH "Global float atomics"); conv_wgrad_kernel for stride > 1
+#include <atomic>
 #include "common.h"
 #include "conv_args.h"
 #include "hdmoe.h"
 
 namespace {
+
+std::atomic<long long> g_selections[HDMOE_SEL_COUNT];     // host-side kernel-selection counters (hdmoe_kernel_selections)
 
 // ------------------------------------------------------------------ weight prep
 struct WprepArgs {
@@ -1182,7 +1185,19 @@ void launch_conv_nb(const ConvArgs& a, bool vec, hipStream_t st) {
 
 }  // namespace
 
+void hdmoe_count_selection(int which) {
+  if (which >= 0 && which < HDMOE_SEL_COUNT) g_selections[which].fetch_add(1, std::memory_order_relaxed);
+}
+
 extern "C" {
+
+int hdmoe_kernel_selections(long long* counts, int n, int reset) {
+  for (int i = 0; i < HDMOE_SEL_COUNT; ++i) {
+    const long long v = reset ? g_selections[i].exchange(0, std::memory_order_relaxed) : g_selections[i].load(std::memory_order_relaxed);
+    if (counts && i < n) counts[i] = v;
+  }
+  return HDMOE_SEL_COUNT;
+}
 
 int hdmoe_wprep_fwd(float* const* w_raw, const float* const* gain_ptr, float gain_val, const int* kh,
                     const int* kw, int ngroups, int O, int I, int Ipad, int Opad, void* wf, long wf_stride,

@@ -106,6 +106,7 @@ int conv6_try_launch(const ConvArgs& c, const ConvFuse* fuse, int dtype, hipStre
     plan.a.film_e = fuse->film_e; plan.a.film_h = fuse->film_h; plan.a.film_seed_dev = fuse->film_seed_dev;
     plan.a.film_seed_lo = (unsigned)fuse->film_seed; plan.a.film_seed_hi = (unsigned)(fuse->film_seed >> 32); plan.a.film_p = fuse->film_p;
   }
+  hdmoe_count_selection(HDMOE_SEL_CONV6);
   const C6Args& a = plan.a;
   const unsigned G = plan.G;
   const size_t lds = plan.lds;

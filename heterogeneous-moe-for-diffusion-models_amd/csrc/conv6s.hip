@@ -87,6 +87,7 @@ int conv6s_plan(const ConvArgs& c, long wplane_elems, const ConvFuse* fuse, C6SP
 int conv6_split_try_launch(const ConvArgs& c, long wplane_elems, const ConvFuse* fuse, hipStream_t stream) {
   C6SPlan plan;
   if (conv6s_plan(c, wplane_elems, fuse, plan, true)) return 1;
+  hdmoe_count_selection(HDMOE_SEL_CONV6S);
   static unsigned long long attr_set = 0;
   if (hdmoe_first_on_device(attr_set)) {
     (void)hipFuncSetAttribute((const void*)conv6_split_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

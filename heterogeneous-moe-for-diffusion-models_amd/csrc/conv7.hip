@@ -69,6 +69,7 @@ void conv7_launch(const C7Plan& p, hipStream_t stream) {
 int conv7_try_launch(const ConvArgs& c, int dtype, hipStream_t stream) {
   C7Plan plan;
   if (conv7_plan(c, dtype, plan)) return 1;
+  hdmoe_count_selection(plan.w16 ? HDMOE_SEL_CONV7_16 : HDMOE_SEL_CONV7_32);
   conv7_launch(plan, stream);
   return hdmoe_launch_status();
 }

@@ -35,6 +35,7 @@ struct ConvFuse {
 int conv6_try_launch(const ConvArgs& a, const ConvFuse* fuse, int dtype, hipStream_t stream);
 
 void* hdmoe_debug_stamp_buffer();     // development: the buffer registered with hdmoe_conv6_debug_stamps (conv6.hip), or null
+void hdmoe_count_selection(int which);   // host-side kernel-selection counter HDMOE_SEL_* += 1 (conv.hip, hdmoe_kernel_selections)
 // Whole-image streaming kernel for 32 x 32 maps (conv7.hip).  Same return convention.
 int conv7_try_launch(const ConvArgs& a, int dtype, hipStream_t stream);
 

@@ -289,6 +289,7 @@ int hdmoe_conv_wgrad6(const void* x, const void* dy, float* const* G, const int*
   const long xbytes = (long)N * H * W * Cin * esz, dybytes = (long)N * H * W * Cout * esz;
   if (xbytes >= (1l << 31) || dybytes >= (1l << 31)) return 1;
   if (N == 0) return HDMOE_OK;
+  hdmoe_count_selection(defer ? HDMOE_SEL_WGRAD6_DEFER : HDMOE_SEL_WGRAD6_DIRECT);
   const int TWS = W >= 32 ? 5 : 4, TW = 1 << TWS, TH = 256 / TW;
   const int OT = Cout % 64 == 0 ? 2 : 1;
   const int ibs = Cin / 32, obs = Cout / (32 * OT);

@@ -45,6 +45,23 @@ import collections as _collections
 STATS = _collections.Counter()
 
 
+def kernel_selections(reset: bool = False) -> dict:
+    """The library's kernel-selection counters (include/hdmoe.h HDMOE_SEL_*): {"conv7_32": n, "bwd7_32_wgrad8": n, ...}, lower-case
+    names without the prefix.  They count launches where the host code enqueues them -- under graph capture at the capture, not at
+    each replay.  ``reset``: zero them after the read."""
+    import re
+    from ._lib import HEADER_PATH
+    names = {}
+    for m in re.finditer(r"\bHDMOE_SEL_(\w+)\s*=\s*(\d+)", open(HEADER_PATH).read()):
+        if m.group(1) != "COUNT":
+            names[int(m.group(2))] = m.group(1).lower()
+    n = lib().hdmoe_kernel_selections(None, 0, 0)
+    assert sorted(names) == list(range(n)), "include/hdmoe.h HDMOE_SEL_* names and the library's counters disagree"
+    arr = (ctypes.c_longlong * n)()
+    lib().hdmoe_kernel_selections(ctypes.cast(arr, ctypes.c_void_p), n, 1 if reset else 0)
+    return {names[i]: int(arr[i]) for i in range(n)}
+
+
 def manual_seed(seed: int) -> None:
     """Seed of the device counter RNG used for dropout masks and router logit noise."""
     _seed_state["seed"] = int(seed) & 0xFFFFFFFFFFFF

@@ -114,6 +114,33 @@ int hdmoe_conv_wgrad6_reduce_batch(float* const* G, const int* const* seg, float
  * (tag << 56 | s_memtime) of every later launch; NULL switches it off (tools/conv6_check.py --stamps). */
 int hdmoe_conv6_debug_stamps(void* buf);
 
+/* Kernel-selection counters: which conv program the host code chose, counted where it enqueues the launch (plain host
+ * std::atomic<long long>, nothing is written to device memory).  Under stream / graph capture the count moves at the capture,
+ * not at each replay.  counts: HOST array of n long longs receiving the first min(n, HDMOE_SEL_COUNT) counters (NULL: none);
+ * reset != 0 zeroes all counters after the read.  Returns HDMOE_SEL_COUNT.  hdmoe_hip.ops.kernel_selections() names them. */
+enum {
+  HDMOE_SEL_CONV7_32 = 0,        /* conv7 forward / dgrad program (hdmoe_conv_fwd), 32 x 32 maps */
+  HDMOE_SEL_CONV7_16 = 1,        /* the same, 16 x 16 maps (pairs of images) */
+  HDMOE_SEL_CONV6 = 2,           /* conv6 (hdmoe_conv_fwd, hdmoe_conv_fwd_film) */
+  HDMOE_SEL_CONV6S = 3,          /* split-bf16 conv6s (hdmoe_conv_fwd with HDMOE_F32S, hdmoe_conv_fwd_split_gn) */
+  HDMOE_SEL_BWD7_32 = 4,         /* fused backward with the conv7 dgrad program, 32 x 32 maps */
+  HDMOE_SEL_BWD7_32_WGRAD8 = 5,  /*   ... with a 3x3 expert: wgrad8 (chunk layouts below) */
+  HDMOE_SEL_BWD7_32_WGRAD7 = 6,  /*   ... with a 5x5 expert: wgrad7 */
+  HDMOE_SEL_BWD7_16_OT1 = 7,     /* fused backward with the conv7 dgrad program, 16 x 16 maps, wgrad6 programs with OT = 1 */
+  HDMOE_SEL_BWD7_16_OT2 = 8,     /*   ... OT = 2 (Cout % 64 == 0) */
+  HDMOE_SEL_BWD6 = 9,            /* fused backward with the conv6 dgrad program (hdmoe_conv_bwd6 outside conv7's domain) */
+  HDMOE_SEL_BWD6S = 10,          /* fused split-bf16 backward (hdmoe_conv_bwd6s) */
+  HDMOE_SEL_WGRAD6_DIRECT = 11,  /* hdmoe_conv_wgrad6, defer = 0 (wgrad6 + its own reduction) */
+  HDMOE_SEL_WGRAD6_DEFER = 12,   /* hdmoe_conv_wgrad6, defer = 1 (partial slabs for hdmoe_conv_wgrad6_reduce_batch) */
+  HDMOE_SEL_BLK6 = 13,           /* hdmoe_unet_block_fwd */
+  HDMOE_SEL_WGRAD8_C11 = 14,     /* wgrad8 inside bwd7: icw x ocw = 1 x 1 channel chunks per workgroup */
+  HDMOE_SEL_WGRAD8_C12 = 15,     /*   1 x 2 */
+  HDMOE_SEL_WGRAD8_C21 = 16,     /*   2 x 1 */
+  HDMOE_SEL_WGRAD8_C22 = 17,     /*   2 x 2 */
+  HDMOE_SEL_COUNT = 18
+};
+int hdmoe_kernel_selections(long long* counts, int n, int reset);
+
 /* Multi-tensor weight bank: one prep launch per forward and one gradient-finish launch per backward for ALL MP_Conv weights
  * of a model.  descs: device array of descriptors (layout = hdmoe_wbank_desc_bytes() bytes each, see csrc/wbank.hip);
  * rows: device int32 pairs (descriptor index, output-channel row), one workgroup per pair. */

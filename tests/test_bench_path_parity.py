@@ -1,4 +1,9 @@
-"""The path bench.py TIMES, pinned to the reference directly.
+"""The weight-bank path bench.py runs, pinned to the reference directly -- at the fixtures' small batches (B = 2 ... 8).
+
+These batches stay below the sizes at which the streaming kernels take over (conv7 / bwd7 / wgrad7 / wgrad8 and the router trunks'
+bf16 streaming backward need >= 192 images): the kernels bench.py TIMES at B = 256 are pinned to the oracle by
+test_bench_size_oracle.py (end to end) and test_streaming_strict.py (per layer), which assert through the library's kernel-selection
+counters that they ran.
 
 From the second step on every conv weight goes through the weight bank (hdmoe_hip/bank.py): the fused dgrad + wgrad launches
 (csrc/bwd6.hip), the deferred batched weight-gradient reduction, the fused router trunk (ops._TrunkFn) and -- in bench.py -- the staged
