@@ -27,7 +27,10 @@ __global__ void zero_f32_kernel(float* p, int n) {
   if (i < n) p[i] = 0.f;
 }
 
-DEVI float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
+// torch.clamp / amax semantics: NaN propagates (fminf / fmaxf would return the other operand and turn a NaN term into its bound)
+DEVI float minf_nan(float v, float hi) { return v > hi ? hi : v; }
+DEVI float maxf_nan(float v, float lo) { return v < lo ? lo : v; }
+DEVI float clampf(float v, float lo, float hi) { return minf_nan(maxf_nan(v, lo), hi); }
 
 // single block: all (B) / (B,E) reductions.  aux[0..2E) = column means of pU | pV (kept for the backward)
 __global__ __launch_bounds__(256) void edm_loss_reduce_kernel(float* out, float* aux, const float* sse, const float* log_var,
@@ -45,11 +48,11 @@ __global__ __launch_bounds__(256) void edm_loss_reduce_kernel(float* out, float*
     for (int which = 0; which < 2; ++which) {
       const float* r = (which ? rV : rU) + (long)b * E;
       float m = -INFINITY;
-      for (int e = 0; e < E; ++e) m = fmaxf(m, clampf(r[e], -50.f, 50.f));
+      for (int e = 0; e < E; ++e) { const float c = clampf(r[e], -50.f, 50.f); m = c != c ? c : maxf_nan(m, c); }
       float s = 0.f;
       for (int e = 0; e < E; ++e) s += __expf(clampf(r[e], -50.f, 50.f) - m);
       const float lse = m + __logf(s);
-      const float z = fminf(lse * lse, 100.f);
+      const float z = minf_nan(lse * lse, 100.f);
       if (which) zv += z; else zu += z;
     }
   }
@@ -71,9 +74,9 @@ __global__ __launch_bounds__(256) void edm_loss_reduce_kernel(float* out, float*
     for (int e = 0; e < E; ++e) { bu += colU[e] * colU[e]; bv += colV[e] * colV[e]; }
     const float bal_raw = lu * E * bu + lvit * E * bv;
     const float z_raw = zb * zu + zb * zv;
-    const float pure_c = fminf(pure, 50.f), bal = fminf(bal_raw, 50.f), z = fminf(z_raw, 50.f);
+    const float pure_c = minf_nan(pure, 50.f), bal = minf_nan(bal_raw, 50.f), z = minf_nan(z_raw, 50.f);
     const float tot = pure_c + z + bal;
-    out[0] = fminf(tot, 50.f); out[1] = den; out[2] = bal; out[3] = z; out[4] = pure_c;
+    out[0] = minf_nan(tot, 50.f); out[1] = den; out[2] = bal; out[3] = z; out[4] = pure_c;
     // pass-through flags for the backward (clamp(max) has zero gradient beyond the bound; NaN compares false -> 0)
     aux[2 * E + 0] = (tot <= 50.f && pure <= 50.f) ? 1.f : 0.f;
     aux[2 * E + 1] = (tot <= 50.f && bal_raw <= 50.f) ? 1.f : 0.f;
@@ -110,7 +113,7 @@ __global__ void edm_loss_bwd_small_kernel(float* dlv, float* dpU, float* dpV, fl
       float* dp = (which ? dpV : dpU) + (long)b * E;
       const float lam = which ? lvit : lu;
       float m = -INFINITY;
-      for (int e = 0; e < E; ++e) m = fmaxf(m, clampf(r[e], -50.f, 50.f));
+      for (int e = 0; e < E; ++e) { const float c = clampf(r[e], -50.f, 50.f); m = c != c ? c : maxf_nan(m, c); }
       float s = 0.f;
       for (int e = 0; e < E; ++e) s += __expf(clampf(r[e], -50.f, 50.f) - m);
       const float lse = m + __logf(s);
