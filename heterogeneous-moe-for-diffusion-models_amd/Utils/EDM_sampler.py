@@ -11,12 +11,19 @@ evaluation alone is captured, as before.
 denoiser output standing in for the second one (N evaluations for N stages instead of 2N - 1).  Its fp32 stage is one evaluation plus the
 fused ``hdmoe_dpm2m_step`` update; with ``use_graph`` ONE captured graph is replayed once per stage.  Other latent dtypes run a host-driven loop.
 
+Stochastic sampling on the device (extensions, opt-in).  ``churn_on_device=True`` runs ``S_churn > 0`` through the fused Heun stage: the churn
+(gamma, t_hat, x_hat = x + c eps) is one kernel in front of the first evaluation, and the Euler / correction kernels read t_hat from the
+device.  ``solver="dpmpp_2m_sde"`` is DPM-Solver++(2M) SDE in its midpoint form (``eta`` scales the noise, 0 = ``dpmpp_2m``), one evaluation
+per stage.  Both draw inside the stage kernels from a counter RNG keyed by (the call's seed, the stage index), both device-resident, so the
+captured stages replay with fresh noise; ``sample(seed=...)`` fixes the draw, on the host loops too.
+
 Extensions over the reference, all opt-in (``sample()`` keywords; with their defaults every path computes what it did without them):
 image-to-image from ``init_latents`` part-way down the schedule (``strength``), inpainting (``inpaint_mask``: the known region is put back on
 its probability-flow path ``x0 + sigma * noise`` by the epilogue of the update kernels), and expert steering (``Unet_router_mask`` /
 ``Vit_router_mask``, also on ``denoise()``).
 """
 import math
+import numbers
 
 import numpy as np
 import torch
@@ -25,17 +32,26 @@ import torch.nn as nn
 from hdmoe_hip import graph as hgraph
 from hdmoe_hip import ops
 
-SOLVERS = ("heun", "dpmpp_2m")
+SOLVERS = ("heun", "dpmpp_2m", "dpmpp_2m_sde")
 
 
 class EDM_Sampler:
     def __init__(self, model: nn.Module, Guide_net: nn.Module, num_solve_steps: int = 32, sigma_min: float = 0.002,
                  sigma_max: float = 80, rho: int = 7, S_churn: float = 0.0, S_min: float = 0.0, S_max: float = float("inf"),
-                 S_noise: float = 1.0, guidance: float = 1.0, dtype=torch.float32, use_graph: bool = False, solver: str = "heun"):
+                 S_noise: float = 1.0, guidance: float = 1.0, dtype=torch.float32, use_graph: bool = False, solver: str = "heun",
+                 churn_on_device: bool = False, eta: float = 1.0):
         if not isinstance(solver, str) or solver not in SOLVERS:
             raise ValueError(f"solver must be one of {', '.join(map(repr, SOLVERS))}, got {solver!r}")
-        if solver == "dpmpp_2m" and S_churn > 0:
-            raise ValueError(f"solver='dpmpp_2m' does not take S_churn > 0 (got {S_churn}): churn is defined for solver='heun' only")
+        if solver != "heun" and S_churn > 0:
+            raise ValueError(f"solver={solver!r} does not take S_churn > 0 (got {S_churn}): churn is defined for solver='heun' only")
+        try:
+            eta_f = float(eta)
+        except (TypeError, ValueError):
+            raise ValueError(f"eta must be a finite number >= 0, got {eta!r}") from None
+        if not (math.isfinite(eta_f) and eta_f >= 0.0):
+            raise ValueError(f"eta must be a finite number >= 0, got {eta!r}")
+        if solver != "dpmpp_2m_sde" and eta_f != 1.0:
+            raise ValueError(f"eta (got {eta!r}) is the noise scale of solver='dpmpp_2m_sde' only, not of solver={solver!r}")
         self.model = model
         self.gnet = Guide_net
         self.num_steps = num_solve_steps
@@ -50,10 +66,13 @@ class EDM_Sampler:
         self.dtype = dtype
         self.use_graph = use_graph          # extension over the reference: hipGraph replay of the denoiser evaluation
         self.solver = solver                # extension over the reference: "dpmpp_2m" = DPM-Solver++(2M), one evaluation per stage
-        # no churn, fp32 latents: a solver stage = both denoiser evaluations + the fused Euler / Heun-correction kernels with sigma read from a
-        # device-side schedule; with use_graph it is ONE captured graph, replayed N - 1 times, plus one graph for the last (Euler-only) stage
+        self.churn_on_device = bool(churn_on_device)     # extension: S_churn > 0 through the fused Heun stage (noise drawn in the kernel)
+        self.eta = eta_f                    # solver="dpmpp_2m_sde": noise scale of DPM-Solver++(2M) SDE (S_noise multiplies the draw)
+        # no churn (or churn_on_device), fp32 latents: a solver stage = both denoiser evaluations + the fused (churn /) Euler / Heun-correction
+        # kernels with sigma read from a device-side schedule; with use_graph it is ONE captured graph, replayed N - 1 times, plus one graph
+        # for the last (Euler-only) stage
         self.fused_heun = False
-        # solver="dpmpp_2m", fp32 latents: a stage = one evaluation + the fused multistep update (hdmoe_dpm2m_step); with use_graph ONE
+        # solver="dpmpp_2m" / "dpmpp_2m_sde", fp32 latents: a stage = one evaluation + the fused multistep update; with use_graph ONE
         # captured graph serves every stage, the last one and the first (no history) included: the kernel picks the order on the device
         self.fused_dpm = False
         # _stage_state() of the captured evaluation ("eval") and of the fused solver stage ("heun" / "dpm"): buffers, stage functions,
@@ -108,6 +127,14 @@ class EDM_Sampler:
     def _dev_mask(m, like):
         return None if m is None else m.to(like.device).contiguous()
 
+    @staticmethod
+    def _check_seed(seed):
+        if seed is None:
+            return None
+        if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or not 0 <= int(seed) < 1 << 64:
+            raise ValueError(f"seed must be an int in [0, 2^64) or None, got {seed!r}")
+        return int(seed)
+
     def _check_conditioning(self, noise, init_latents, strength, inpaint_mask):
         try:
             strength = float(strength)
@@ -149,11 +176,13 @@ class EDM_Sampler:
         The stage kinds take sigma from the schedule t (float64, as the host computes it) at the device stage index idx, and the kernels pick
         the order on the device, so any strength shares one capture.  The SAME stage function runs eagerly and under capture: the two
         trajectories are bit-identical.  The key holds everything a capture bakes in -- shapes, which optional operands exist, and what
-        _denoise reads on the host (guide, the two modules) -- never buffer values: every input is refreshed before each run."""
+        _denoise reads on the host (guide, the two modules), the churn / SDE launch scalars -- never buffer values: every input, the seed of
+        the stochastic stages included (device word "seed"), is refreshed before each run."""
         shape = lambda a: None if a is None else tuple(a.shape)
         key = (kind, self.solver, shape(x), x.dtype, shape(text_emb), shape(uncond_text_emb), float(transition_mean), float(softness),
                self.num_steps, bool(self.use_graph), None if known is None else tuple(map(shape, known)), shape(um), shape(vm),
-               float(self.guide), id(self.model), id(self.gnet))
+               float(self.guide), id(self.model), id(self.gnet), float(self.s_churn), float(self.s_min), float(self.s_max), float(self.s_noise),
+               float(self.eta), bool(self.churn_on_device))
         slot = "_graph" if kind == "eval" else "_stage"          # one cached state for the evaluation, one for the solver stage
         st = getattr(self, slot)
         if st is not None and st["key"] == key:
@@ -172,29 +201,43 @@ class EDM_Sampler:
         def pick(j):                                          # sig = t[idx + j]
             ops.call("hdmoe_sched_pick", st["sig"], st["t"], st["idx"], j)
 
+        churn = self.s_churn > 0                              # a fused Heun stage with churn: churn_on_device (sample() decides)
+        gamma_cap = float(min(self.s_churn / self.num_steps, np.sqrt(2) - 1))
+
         def heun(last: bool):
-            pick(0)
+            if churn:                                         # x <- x_hat in place, sig = t_hat; the updates then start from t_hat
+                ops.heun_churn(st["x"], st["x"], st["sig"], st["t_hat"], st["t"], st["idx"], st["seed"], gamma_cap, self.s_min, self.s_max,
+                               self.s_noise)
+            else:
+                pick(0)
+            that = st["t_hat"] if churn else None
             d = den(st["x"])
             if last:
-                ops.heun_euler(st["x"], st["x"], d, st["t"], st["idx"], st["known"])
+                ops.heun_euler(st["x"], st["x"], d, st["t"], st["idx"], st["known"], that)
             else:
-                ops.heun_euler(st["xn"], st["x"], d, st["t"], st["idx"], st["known"])
+                ops.heun_euler(st["xn"], st["x"], d, st["t"], st["idx"], st["known"], that)
                 pick(1)
-                ops.heun_correct(st["x"], st["x"], d, st["xn"], den(st["xn"]), st["t"], st["idx"], st["known"])
+                ops.heun_correct(st["x"], st["x"], d, st["xn"], den(st["xn"]), st["t"], st["idx"], st["known"], that)
             ops.call("hdmoe_idx_advance", st["idx"])
 
         def dpm():
             pick(0)
-            ops.dpm2m_step(st["x"], st["x"], den(st["x"]), st["den_prev"], st["t"], st["idx"], st["i0"], st["known"])
+            if self.solver == "dpmpp_2m_sde":
+                ops.dpm2m_sde_step(st["x"], st["x"], den(st["x"]), st["den_prev"], st["t"], st["idx"], st["i0"], self.eta, self.s_noise,
+                                   st["seed"], st["known"])
+            else:
+                ops.dpm2m_step(st["x"], st["x"], den(st["x"]), st["den_prev"], st["t"], st["idx"], st["i0"], st["known"])
             ops.call("hdmoe_idx_advance", st["idx"])
 
         def evaluate():
             st["out"] = den(st["x"])
 
         if kind != "eval":
-            st.update(t=torch.ones(self.num_steps + 1, dtype=torch.float64, device=dev), idx=torch.zeros(1, dtype=torch.int32, device=dev))
+            st.update(t=torch.ones(self.num_steps + 1, dtype=torch.float64, device=dev), idx=torch.zeros(1, dtype=torch.int32, device=dev),
+                      seed=torch.zeros(1, dtype=torch.int64, device=dev))      # the call's 64-bit seed (two's complement of the unsigned value)
         if kind == "heun":
             st["xn"] = torch.empty_like(x)                    # the Euler predictor
+            st["t_hat"] = torch.ones(1, dtype=torch.float64, device=dev)       # the churned sigma of the current stage
         if kind == "dpm":
             st.update(den_prev=torch.zeros_like(x), i0=torch.zeros(1, dtype=torch.int32, device=dev))
         st["fns"] = {"eval": [evaluate], "heun": [lambda: heun(False), lambda: heun(True)], "dpm": [dpm]}[kind]
@@ -228,8 +271,11 @@ class EDM_Sampler:
         return graphs
 
     @staticmethod
-    def _refresh(st, x, text_emb, uncond_text_emb, known, um, vm):
-        """Every input into the static buffers: a later sample() with another prompt of the same shape must not see the captured one."""
+    def _refresh(st, x, text_emb, uncond_text_emb, known, um, vm, seed=None):
+        """Every input into the static buffers: a later sample() with another prompt of the same shape must not see the captured one.
+        seed: the 64-bit seed of this call's stochastic stages (a buffer value like the others, never part of the capture key)."""
+        if seed is not None:
+            st["seed"].fill_(seed - (1 << 64) if seed >= 1 << 63 else seed)
         st["x"].copy_(x)
         st["text"].copy_(text_emb)
         for name, src in (("unc", uncond_text_emb), ("um", um), ("vm", vm)):
@@ -238,14 +284,23 @@ class EDM_Sampler:
         for buf, src in zip(st["known"] or (), known or ()):
             buf.copy_(src)
 
-    def _dpm_host_loop(self, x, t_steps, i0, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm):
-        """solver="dpmpp_2m" for latents the fused stage does not take (non-fp32 dtype): the rule of sample() with host coefficients."""
+    @staticmethod
+    def _eps(x, seed, stage):
+        """The stage's standard normals in x's dtype: keyed by (seed, stage) like the fused stages, or from the library's stream (seed None)."""
+        eps = ops.randn_like(x, 1.0) if seed is None else ops.randn_keyed(x, seed, stage)
+        return eps.to(x.dtype)
+
+    def _dpm_host_loop(self, x, t_steps, i0, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, seed=None):
+        """solver="dpmpp_2m" / "dpmpp_2m_sde" for latents the fused stage does not take (non-fp32 dtype): the rule of sample() with host
+        coefficients."""
         N = self.num_steps
+        sde = self.solver == "dpmpp_2m_sde"
         den_prev = None
         for i in range(i0, N):
             t_cur, t_next = float(t_steps[i]), float(t_steps[i + 1])
             den = self._eval(x, t_cur, text_emb, transition_mean, softness, uncond_text_emb, um, vm)
-            a = t_next / t_cur
+            e = math.exp(-self.eta * math.log(t_cur / t_next)) if sde and t_next > 0 else 1.0
+            a = t_next / t_cur * e
             if t_next == 0:
                 x = den.clone()
             elif i == i0:
@@ -253,6 +308,8 @@ class EDM_Sampler:
             else:
                 hr = 0.5 * math.log(t_cur / t_next) / math.log(float(t_steps[i - 1]) / t_cur)      # 1 / (2 r)
                 x = ops.axpby(x, ops.axpby(den, den_prev, 1.0 + hr, -hr), a, 1.0 - a)
+            if sde and self.eta > 0 and t_next > 0:
+                x = ops.axpby(x, self._eps(x, seed, i), 1.0, t_next * math.sqrt(1.0 - e * e) * self.s_noise)
             if known is not None:
                 ops.known_blend_(x, *known, t_next)
             den_prev = den
@@ -278,7 +335,8 @@ class EDM_Sampler:
     @torch.no_grad()
     def sample(self, noise: torch.Tensor, text_emb: torch.Tensor, transition_mean: float, softness: float,
                uncond_text_emb: torch.Tensor = None, *, init_latents: torch.Tensor = None, strength: float = 1.0,
-               inpaint_mask: torch.Tensor = None, Unet_router_mask: torch.Tensor = None, Vit_router_mask: torch.Tensor = None) -> torch.Tensor:
+               inpaint_mask: torch.Tensor = None, Unet_router_mask: torch.Tensor = None, Vit_router_mask: torch.Tensor = None,
+               seed: int = None) -> torch.Tensor:
         """Solve of the probability-flow ODE over t = t_schedule() (N = num_solve_steps, t[N] = 0): Heun (solver="heun", the reference),
         or DPM-Solver++(2M) (solver="dpmpp_2m", one evaluation per stage).
 
@@ -287,6 +345,16 @@ class EDM_Sampler:
             i == i0:      x = a x + (1 - a) D_i                         (no history yet: first order)
             otherwise:    x = a x + (1 - a) ((1 + 1/(2r)) D_i - 1/(2r) D_{i-1}),   r = log(t[i-1] / t[i]) / log(t[i] / t[i+1])
         then the inpainting blend below at sigma = t[i+1], and D_{i-1} <- D_i: n_run evaluations per network.  It takes every keyword below.
+
+        solver="dpmpp_2m_sde" (DPM-Solver++(2M) SDE, midpoint form) is the same with e = exp(-eta log(t[i] / t[i+1])): a = (t[i+1] / t[i]) e
+        in place of a above, and, except on the last stage and when eta == 0, x += t[i+1] sqrt(1 - e^2) S_noise eps_i before the blend.
+        eta = 0 is solver="dpmpp_2m" bit-for-bit.
+
+        Churn (S_churn > 0, solver="heun", reference :90-97): stage i starts from t_hat = t[i] (1 + gamma), x_hat = x + sqrt(t_hat^2 - t[i]^2)
+        S_noise eps_i, gamma = min(S_churn / N, sqrt(2) - 1) where S_min <= t[i] <= S_max, else 0.  It runs on the host-driven loop unless
+        churn_on_device=True (fp32 latents on the GPU), which runs it inside the fused stage.
+
+        eps_i, one standard normal per latent element, is what hdmoe_randn draws under the key (seed, i) -- ops.randn_keyed(x, seed, i).
 
         Keywords beyond the reference (every default reproduces the plain sampler):
           strength:       in (0, 1]; the solver runs the last n_run = ceil(strength * N) stages, i0 = N - n_run ... N - 1, i.e. 2 n_run - 1
@@ -298,10 +366,15 @@ class EDM_Sampler:
                           produces latents at sigma = t[i+1] (the Euler predictor, the Heun-corrected output, the last Euler-only output, each
                           DPM-Solver++(2M) update):
                           x <- m (x0 + sigma noise) + (1 - m) x, so where m = 1 the output is x0 exactly.  Soft masks blend.
+          seed:           int in [0, 2^64) or None.  The fused stochastic stages draw from it; None takes the next value of the library's
+                          seed stream (ops.manual_seed), once per call.  The host loops draw under the same (seed, stage) key when it is
+                          given -- so they see the eps of the fused path -- and from the library's stream per stage, as before, when it is
+                          None.  A configuration that draws nothing ignores it.
           Unet_router_mask / Vit_router_mask:  (B, E) or (E,) with {0, 1} entries, passed to the model and the guide network; None = all
                           experts.  A row with no allowed expert is refused.
         Argument errors raise ValueError (naming the argument) before any device work."""
         strength = self._check_conditioning(noise, init_latents, strength, inpaint_mask)
+        seed = self._check_seed(seed)
         bs = noise.shape[0]
         um = self._router_mask(Unet_router_mask, "Unet_router_mask", bs)
         vm = self._router_mask(Vit_router_mask, "Vit_router_mask", bs)
@@ -326,15 +399,17 @@ class EDM_Sampler:
             x_next = ops.axpby(x0, lat, 1.0, float(t_steps[i0]))
             if inpaint_mask is not None:                      # expanded once per call: the kernels read a mask of the latents' size
                 known = (x0, lat, inpaint_mask.to(device).expand(noise.shape).contiguous())
-        fused = bool(self.s_churn <= 0 and self.dtype == torch.float32 and noise.is_cuda and self.num_steps >= 2)
+        fused = bool((self.s_churn <= 0 or self.churn_on_device) and self.dtype == torch.float32 and noise.is_cuda and self.num_steps >= 2)
         self.fused_heun = fused and self.solver == "heun"
-        self.fused_dpm = fused and self.solver == "dpmpp_2m"
+        self.fused_dpm = fused and self.solver != "heun"
         if fused:
-            # no churn: the whole solver runs from a device-side schedule (fused Euler / Heun-correction kernels, or the DPM-Solver++(2M) step
+            # the whole solver runs from a device-side schedule (fused churn / Euler / Heun-correction kernels, or the DPM-Solver++(2M) step
             # kernel, no host arithmetic between the evaluations); with use_graph each stage is one hipGraph replay
             kind = "heun" if self.fused_heun else "dpm"
+            if seed is None and (self.s_churn > 0 or (self.solver == "dpmpp_2m_sde" and self.eta > 0)):
+                seed = ops.next_seed()                        # a stochastic stage: one value of the library's stream per call
             st = self._stage_state(kind, x_next, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm)
-            self._refresh(st, x_next, text_emb, uncond_text_emb, known, um, vm)
+            self._refresh(st, x_next, text_emb, uncond_text_emb, known, um, vm, seed)
             st["t"].copy_(torch.from_numpy(t_steps))
             st["idx"].fill_(i0)
             if self.fused_dpm:
@@ -343,8 +418,8 @@ class EDM_Sampler:
             for i in range(i0, N):
                 runs[-1 if i == N - 1 else 0]()               # Heun: the Euler-only stage last; DPM: its one stage throughout
             return st["x"].clone()
-        if self.solver == "dpmpp_2m":
-            return self._dpm_host_loop(x_next, t_steps, i0, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm)
+        if self.solver != "heun":
+            return self._dpm_host_loop(x_next, t_steps, i0, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, seed)
         for i in range(i0, N):
             t_cur, t_next = float(t_steps[i]), float(t_steps[i + 1])
             x_cur = x_next
@@ -352,7 +427,7 @@ class EDM_Sampler:
             t_hat = t_cur + gamma * t_cur
             x_hat = x_cur
             if gamma > 0:
-                x_hat = ops.axpby(x_cur, ops.randn_like(x_cur, 1.0), 1.0, float(np.sqrt(t_hat ** 2 - t_cur ** 2) * self.s_noise))
+                x_hat = ops.axpby(x_cur, self._eps(x_cur, seed, i), 1.0, float(np.sqrt(t_hat ** 2 - t_cur ** 2) * self.s_noise))
             denoised = self._eval(x_hat, t_hat, text_emb, transition_mean, softness, uncond_text_emb, um, vm)
             # d_cur = (x_hat - denoised)/t_hat ; x_next = x_hat + (t_next - t_hat) * d_cur
             h = (t_next - t_hat)

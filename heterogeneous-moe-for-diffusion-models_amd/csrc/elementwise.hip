@@ -52,12 +52,33 @@ __global__ void sched_pick_kernel(float* sigma, const double* t, const int* idx,
 __global__ void idx_advance_kernel(int* idx) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *idx += 1;
 }
+// Four standard normals of Philox block q (Box-Muller on the u01 pairs (r0, r1), (r2, r3)): element 4 q + j of hdmoe_randn is v[j].  One
+// definition for randn_kernel and the sampler's stochastic stage kernels, so that they draw the same values by construction.
+DEVI void randn4(long q, uint32_t seed_lo, uint32_t seed_hi, float* v) {
+  uint32_t r[4];
+  philox((uint32_t)q, (uint32_t)(q >> 32), seed_lo, seed_hi, r);
+  const float a0 = sqrtf(-2.f * logf(u01(r[0]))), a1 = sqrtf(-2.f * logf(u01(r[2])));
+  const float t0 = 6.28318530717958648f * u01(r[1]), t1 = 6.28318530717958648f * u01(r[3]);
+  v[0] = a0 * cosf(t0); v[1] = a0 * sinf(t0); v[2] = a1 * cosf(t1); v[3] = a1 * sinf(t1);
+}
+// Philox key of sampler stage i: the key of hdmoe_randn(seed = *seed, *seed_dev = i).  Both words come from device memory, so a captured
+// stage replays with the noise of the current call and stage.
+DEVI void stage_key(const unsigned long long* seed, int i, uint32_t& lo, uint32_t& hi) {
+  const unsigned long long s = *seed, c = (unsigned long long)i;
+  lo = (uint32_t)s; hi = (uint32_t)(s >> 32);
+  mix_seed(lo, hi, &c);
+}
 // W fp32 elements per thread: 16-byte loads / stores when W == 4 (the launcher checks n % 4 and the alignment), scalar otherwise
 template <int W> DEVI void ldw(float* f, const float* p) {
   if constexpr (W == 4) vload<float>(f, p); else f[0] = *p;
 }
 template <int W> DEVI void stw(float* p, const float* f) {
   if constexpr (W == 4) vstore<float>(p, f); else *p = f[0];
+}
+// the draws of elements off ... off + W - 1 (off % W == 0): element j is lane j % 4 of block j / 4 whatever W is
+template <int W> DEVI void eps_w(float* e, long off, uint32_t lo, uint32_t hi) {
+  if constexpr (W == 4) randn4(off >> 2, lo, hi, e);
+  else { float v[4]; randn4(off >> 2, lo, hi, v); e[0] = v[off & 3]; }
 }
 // Known region (inpainting) on its probability-flow path at sigma = s: x <- m (x0 + s noise) + (1 - m) x.  Evaluated in exactly this form
 // (not as a lerp) so that m = 1 at s = 0 gives x0 and m = 0 gives x bit-for-bit.  Epilogue of the stage kernels, and the host-loop form.
@@ -70,13 +91,14 @@ template <int W> DEVI void known_blend_w(float* x, const float* x0, const float*
 }
 // The update arithmetic is spelled out with contraction off, in the roundings of the earlier scalar kernels (euler: two products, one sum;
 // correct: u = fma(a1, x_hat, b1 den), v = a2 x_next + b2 den2 unfused, u + v), so the result does not depend on how the compiler fuses it.
-// x_next = x_hat + (t_next - t_hat) * (x_hat - denoised) / t_hat;  with x0 / nz / m (all or none): the known-region blend at t_next
+// x_next = x_hat + (t_next - t_hat) * (x_hat - denoised) / t_hat;  with x0 / nz / m (all or none): the known-region blend at t_next.
+// t_hat = *that (the churned sigma heun_churn_kernel left on the device), or t[i] when that is NULL (no churn).
 template <int W>
-__global__ void heun_euler_kernel(float* xn, const float* xh, const float* den, const double* t, const int* idx, long nv,
+__global__ void heun_euler_kernel(float* xn, const float* xh, const float* den, const double* t, const int* idx, const double* that, long nv,
                                   const float* x0, const float* nz, const float* m) {
 #pragma clang fp contract(off)
   const int i = *idx;
-  const double th = t[i], h = t[i + 1] - th;
+  const double th = that ? *that : t[i], h = t[i + 1] - th;
   const float a = (float)(1.0 + h / th), b = (float)(-h / th), s = (float)t[i + 1];
   GRID_STRIDE(v, nv) {
     float p[W], d[W];
@@ -90,10 +112,10 @@ __global__ void heun_euler_kernel(float* xn, const float* xh, const float* den, 
 // x_out = x_hat + h * (0.5 * (x_hat - denoised) / t_hat + 0.5 * (x_next - denoised') / t_next);  x0 / nz / m: as heun_euler_kernel
 template <int W>
 __global__ void heun_correct_kernel(float* out, const float* xh, const float* den, const float* xn, const float* den2, const double* t, const int* idx,
-                                    long nv, const float* x0, const float* nz, const float* m) {
+                                    const double* that, long nv, const float* x0, const float* nz, const float* m) {
 #pragma clang fp contract(off)
   const int i = *idx;
-  const double th = t[i], tn = t[i + 1], h = tn - th;
+  const double th = that ? *that : t[i], tn = t[i + 1], h = tn - th;
   const float a1 = (float)(1.0 + 0.5 * h / th), b1 = (float)(-0.5 * h / th), a2 = (float)(0.5 * h / tn), b2 = (float)(-0.5 * h / tn);
   const float s = (float)tn;
   GRID_STRIDE(v, nv) {
@@ -109,6 +131,36 @@ __global__ void heun_correct_kernel(float* out, const float* xh, const float* de
     stw<W>(out + v * W, p);
   }
 }
+// Churn of one Heun stage (reference Utils/EDM_sampler.py:90-97) on the device: i = *idx, tc = t[i], gamma = gcap inside [smin, smax] else 0,
+// t_hat = tc + gamma tc -> *t_hat and (float) -> *sigma (what sched_pick(0) writes without churn), x_hat = x + c eps with
+// c = (float)(sqrt(t_hat^2 - tc^2) snoise) and eps the stage's draw (stage_key / eps_w).  The scalars are computed in double exactly as the
+// host loop computes them.  gamma == 0: nothing is drawn, x_hat = x bit-for-bit (no pass at all when in place).
+template <int W>
+__global__ void heun_churn_kernel(float* xh, const float* x, float* sigma, double* t_hat, const double* t, const int* idx,
+                                  const unsigned long long* seed, double gcap, double smin, double smax, double snoise, long nv) {
+#pragma clang fp contract(off)
+  const int i = *idx;
+  const double tc = t[i];
+  const double gamma = (smin <= tc && tc <= smax) ? gcap : 0.0;
+  const double th = tc + gamma * tc;
+  if (blockIdx.x == 0 && threadIdx.x == 0) { *t_hat = th; *sigma = (float)th; }
+  const bool noisy = gamma != 0.0;
+  if (!noisy && xh == x) return;
+  const float c = (float)(sqrt(th * th - tc * tc) * snoise);
+  uint32_t lo = 0u, hi = 0u;
+  if (noisy) stage_key(seed, i, lo, hi);
+  GRID_STRIDE(v, nv) {
+    float p[W];
+    ldw<W>(p, x + v * W);
+    if (noisy) {
+      float e[W];
+      eps_w<W>(e, v * W, lo, hi);
+#pragma unroll
+      for (int j = 0; j < W; ++j) p[j] = p[j] + c * e[j];
+    }
+    stw<W>(xh + v * W, p);
+  }
+}
 // One DPM-Solver++(2M) stage (multistep, data prediction) on the same device schedule, one evaluation per stage: i = *idx, a = t[i+1] / t[i];
 //   t[i+1] == 0:  x_out = den                                           (last stage)
 //   i == *i0:     x_out = a x + (1 - a) den                             (no history yet: first order)
@@ -117,15 +169,23 @@ __global__ void heun_correct_kernel(float* out, const float* xh, const float* de
 // captured graph needs no ping-pong buffers).  Roundings, contraction off: a, b = 1 - a, w1 = 1 + 1/(2r), w0 = 1/(2r) are computed in double
 // and rounded to float once; u = w1 den - w0 den_prev (two products, one difference), x_out = a x + b u (two products, one sum); first order
 // a x + b den.  den_prev is read only by the second-order branch, x not at all by the last stage.
-template <int W>
+// SDE (DPM-Solver++(2M) SDE, midpoint form): with h = log(t[i] / t[i+1]) and e = exp(-eta h), a = (t[i+1] / t[i]) e and b = 1 - a replace
+// the two above, and after the update (before the blend) x_out += c eps, c = (float)(t[i+1] sqrt(1 - e^2) snoise), eps the stage's draw
+// (stage_key / eps_w) -- only when eta > 0 and not on the last stage.  eta == 0: e = 1, the deterministic stage bit-for-bit.
+template <int W, bool SDE>
 __global__ void dpm2m_step_kernel(float* xo, const float* x, const float* den, float* dp, const double* t, const int* idx, const int* i0, long nv,
-                                  const float* x0, const float* nz, const float* m) {
+                                  const float* x0, const float* nz, const float* m, float eta, float snoise, const unsigned long long* seed) {
 #pragma clang fp contract(off)
   const int i = *idx;
   const double ti = t[i], tn = t[i + 1];
   const int order = tn == 0.0 ? 0 : (i <= *i0 ? 1 : 2);       // <=, not ==: an idx below i0 never reads t[i - 1]
-  const double ad = tn / ti, hr = order == 2 ? 0.5 * log(ti / tn) / log(t[i - 1] / ti) : 0.0;
+  const double hr = order == 2 ? 0.5 * log(ti / tn) / log(t[i - 1] / ti) : 0.0;
+  const double e = SDE && order != 0 ? exp(-(double)eta * log(ti / tn)) : 1.0, ad = tn / ti * e;
   const float a = (float)ad, b = (float)(1.0 - ad), w1 = (float)(1.0 + hr), w0 = (float)hr, s = (float)tn;
+  const bool noisy = SDE && order != 0 && eta > 0.f;
+  const float c = noisy ? (float)(tn * sqrt(1.0 - e * e) * (double)snoise) : 0.f;
+  uint32_t lo = 0u, hi = 0u;
+  if (noisy) stage_key(seed, i, lo, hi);
   GRID_STRIDE(v, nv) {
     float p[W], d[W];
     ldw<W>(d, den + v * W);
@@ -144,6 +204,12 @@ __global__ void dpm2m_step_kernel(float* xo, const float* x, const float* den, f
         const float u = w1 * d[j] - w0 * q[j];
         p[j] = a * p[j] + b * u;
       }
+    }
+    if (noisy) {
+      float z[W];
+      eps_w<W>(z, v * W, lo, hi);
+#pragma unroll
+      for (int j = 0; j < W; ++j) p[j] = p[j] + c * z[j];
     }
     if (m) known_blend_w<W>(p, x0, nz, m, s, v * W);
     stw<W>(dp + v * W, d);
@@ -1024,11 +1090,8 @@ __global__ void dropout_kernel(T* out, const T* x, uint32_t seed_lo, uint32_t se
 __global__ void randn_kernel(float* out, uint32_t seed_lo, uint32_t seed_hi, const unsigned long long* seed_dev, float scale, long n) {
   mix_seed(seed_lo, seed_hi, seed_dev);
   GRID_STRIDE(q, (n + 3) / 4) {
-    uint32_t r[4];
-    philox((uint32_t)q, (uint32_t)(q >> 32), seed_lo, seed_hi, r);
-    const float a0 = sqrtf(-2.f * logf(u01(r[0]))), a1 = sqrtf(-2.f * logf(u01(r[2])));
-    const float t0 = 6.28318530717958648f * u01(r[1]), t1 = 6.28318530717958648f * u01(r[3]);
-    const float v[4] = {a0 * cosf(t0), a0 * sinf(t0), a1 * cosf(t1), a1 * sinf(t1)};
+    float v[4];
+    randn4(q, seed_lo, seed_hi, v);
 #pragma unroll
     for (int j = 0; j < 4; ++j) if (q * 4 + j < n) out[q * 4 + j] = scale * v[j];
   }
@@ -1109,22 +1172,52 @@ int hdmoe_idx_advance(int* idx, hipStream_t stream) {
 static inline int known_block(const float* x0, const float* noise, const float* mask) {
   return (x0 == nullptr && noise == nullptr && mask == nullptr) ? 0 : (x0 && noise && mask) ? 1 : -1;
 }
-int hdmoe_heun_euler(float* xn, const float* xh, const float* den, const double* t, const int* idx, long n,
-                     const float* x0, const float* noise, const float* mask, hipStream_t stream) {
+static int heun_euler_launch(float* xn, const float* xh, const float* den, const double* t, const int* idx, const double* t_hat, long n,
+                             const float* x0, const float* noise, const float* mask, hipStream_t stream) {
   if (!xn || !xh || !den || !t || !idx || n < 0 || known_block(x0, noise, mask) < 0) return HDMOE_EINVAL;
   if (n % 4 == 0 && al16(xn) && al16(xh) && al16(den) && al16(x0) && al16(noise) && al16(mask))
-    L1D(heun_euler_kernel<4>, n / 4, xn, xh, den, t, idx, n / 4, x0, noise, mask);
+    L1D(heun_euler_kernel<4>, n / 4, xn, xh, den, t, idx, t_hat, n / 4, x0, noise, mask);
   else
-    L1D(heun_euler_kernel<1>, n, xn, xh, den, t, idx, n, x0, noise, mask);
+    L1D(heun_euler_kernel<1>, n, xn, xh, den, t, idx, t_hat, n, x0, noise, mask);
   return hdmoe_launch_status();
+}
+static int heun_correct_launch(float* out, const float* xh, const float* den, const float* xn, const float* den2, const double* t, const int* idx,
+                               const double* t_hat, long n, const float* x0, const float* noise, const float* mask, hipStream_t stream) {
+  if (!out || !xh || !den || !xn || !den2 || !t || !idx || n < 0 || known_block(x0, noise, mask) < 0) return HDMOE_EINVAL;
+  if (n % 4 == 0 && al16(out) && al16(xh) && al16(den) && al16(xn) && al16(den2) && al16(x0) && al16(noise) && al16(mask))
+    L1D(heun_correct_kernel<4>, n / 4, out, xh, den, xn, den2, t, idx, t_hat, n / 4, x0, noise, mask);
+  else
+    L1D(heun_correct_kernel<1>, n, out, xh, den, xn, den2, t, idx, t_hat, n, x0, noise, mask);
+  return hdmoe_launch_status();
+}
+int hdmoe_heun_euler(float* xn, const float* xh, const float* den, const double* t, const int* idx, long n,
+                     const float* x0, const float* noise, const float* mask, hipStream_t stream) {
+  return heun_euler_launch(xn, xh, den, t, idx, nullptr, n, x0, noise, mask, stream);
 }
 int hdmoe_heun_correct(float* out, const float* xh, const float* den, const float* xn, const float* den2, const double* t, const int* idx, long n,
                        const float* x0, const float* noise, const float* mask, hipStream_t stream) {
-  if (!out || !xh || !den || !xn || !den2 || !t || !idx || n < 0 || known_block(x0, noise, mask) < 0) return HDMOE_EINVAL;
-  if (n % 4 == 0 && al16(out) && al16(xh) && al16(den) && al16(xn) && al16(den2) && al16(x0) && al16(noise) && al16(mask))
-    L1D(heun_correct_kernel<4>, n / 4, out, xh, den, xn, den2, t, idx, n / 4, x0, noise, mask);
+  return heun_correct_launch(out, xh, den, xn, den2, t, idx, nullptr, n, x0, noise, mask, stream);
+}
+int hdmoe_heun_euler_hat(float* xn, const float* xh, const float* den, const double* t, const int* idx, const double* t_hat, long n,
+                         const float* x0, const float* noise, const float* mask, hipStream_t stream) {
+  if (!t_hat) return HDMOE_EINVAL;
+  return heun_euler_launch(xn, xh, den, t, idx, t_hat, n, x0, noise, mask, stream);
+}
+int hdmoe_heun_correct_hat(float* out, const float* xh, const float* den, const float* xn, const float* den2, const double* t, const int* idx,
+                           const double* t_hat, long n, const float* x0, const float* noise, const float* mask, hipStream_t stream) {
+  if (!t_hat) return HDMOE_EINVAL;
+  return heun_correct_launch(out, xh, den, xn, den2, t, idx, t_hat, n, x0, noise, mask, stream);
+}
+// finite and >= 0 (false for NaN)
+static inline bool nonneg_finite(double v) { return v >= 0.0 && v <= 1.79769313486231570815e308; }
+int hdmoe_heun_churn(float* x_hat, const float* x, float* sigma, double* t_hat, const double* t, const int* idx, const unsigned long long* seed,
+                     double gamma_cap, double s_min, double s_max, double s_noise, long n, hipStream_t stream) {
+  if (!x_hat || !x || !sigma || !t_hat || !t || !idx || !seed || n < 0) return HDMOE_EINVAL;
+  if (!nonneg_finite(gamma_cap) || !nonneg_finite(s_noise) || s_min != s_min || s_max != s_max) return HDMOE_EINVAL;
+  if (n % 4 == 0 && al16(x_hat) && al16(x))
+    L1D(heun_churn_kernel<4>, n / 4, x_hat, x, sigma, t_hat, t, idx, seed, gamma_cap, s_min, s_max, s_noise, n / 4);
   else
-    L1D(heun_correct_kernel<1>, n, out, xh, den, xn, den2, t, idx, n, x0, noise, mask);
+    L1D(heun_churn_kernel<1>, n, x_hat, x, sigma, t_hat, t, idx, seed, gamma_cap, s_min, s_max, s_noise, n);
   return hdmoe_launch_status();
 }
 // do the n-float ranges at p and q share an element
@@ -1132,15 +1225,29 @@ static inline bool overlap(const float* p, const float* q, long n) {
   const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q, bytes = (uintptr_t)n * sizeof(float);
   return n > 0 && a < b + bytes && b < a + bytes;
 }
-int hdmoe_dpm2m_step(float* x_out, const float* x, const float* den, float* den_prev, const double* t, const int* idx, const int* i0, long n,
-                     const float* x0, const float* noise, const float* mask, hipStream_t stream) {
+static int dpm2m_launch(bool sde, float* x_out, const float* x, const float* den, float* den_prev, const double* t, const int* idx, const int* i0, long n,
+                        const float* x0, const float* noise, const float* mask, float eta, float s_noise, const unsigned long long* seed,
+                        hipStream_t stream) {
   if (!x_out || !x || !den || !den_prev || !t || !idx || !i0 || n < 0 || known_block(x0, noise, mask) < 0) return HDMOE_EINVAL;
   if (overlap(den_prev, den, n) || overlap(den_prev, x, n) || overlap(den_prev, x_out, n)) return HDMOE_EINVAL;
-  if (n % 4 == 0 && al16(x_out) && al16(x) && al16(den) && al16(den_prev) && al16(x0) && al16(noise) && al16(mask))
-    L1D(dpm2m_step_kernel<4>, n / 4, x_out, x, den, den_prev, t, idx, i0, n / 4, x0, noise, mask);
-  else
-    L1D(dpm2m_step_kernel<1>, n, x_out, x, den, den_prev, t, idx, i0, n, x0, noise, mask);
+#define DPM2M(W, SDE, nv) L1D((dpm2m_step_kernel<W, SDE>), nv, x_out, x, den, den_prev, t, idx, i0, nv, x0, noise, mask, eta, s_noise, seed)
+  if (n % 4 == 0 && al16(x_out) && al16(x) && al16(den) && al16(den_prev) && al16(x0) && al16(noise) && al16(mask)) {
+    if (sde) DPM2M(4, true, n / 4); else DPM2M(4, false, n / 4);
+  } else {
+    if (sde) DPM2M(1, true, n); else DPM2M(1, false, n);
+  }
+#undef DPM2M
   return hdmoe_launch_status();
+}
+int hdmoe_dpm2m_step(float* x_out, const float* x, const float* den, float* den_prev, const double* t, const int* idx, const int* i0, long n,
+                     const float* x0, const float* noise, const float* mask, hipStream_t stream) {
+  return dpm2m_launch(false, x_out, x, den, den_prev, t, idx, i0, n, x0, noise, mask, 0.f, 0.f, nullptr, stream);
+}
+int hdmoe_dpm2m_sde_step(float* x_out, const float* x, const float* den, float* den_prev, const double* t, const int* idx, const int* i0, long n,
+                         const float* x0, const float* noise, const float* mask, float eta, float s_noise, const unsigned long long* seed,
+                         hipStream_t stream) {
+  if (!seed || !nonneg_finite(eta) || !nonneg_finite(s_noise)) return HDMOE_EINVAL;
+  return dpm2m_launch(true, x_out, x, den, den_prev, t, idx, i0, n, x0, noise, mask, eta, s_noise, seed, stream);
 }
 int hdmoe_known_blend(void* x, const void* x0, const void* noise, const float* mask, float s, long n, int dtype, hipStream_t stream) {
   if (!x || !x0 || !noise || !mask || n < 0) return HDMOE_EINVAL;

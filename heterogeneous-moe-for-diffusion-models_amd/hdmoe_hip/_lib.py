@@ -19,7 +19,7 @@ MAX_GROUPS = 8
 
 # one letter per argument:
 #   p device pointer (tensor / None)      P host array of device pointers (list of tensors / None entries)
-#   I host int array (list of ints)       F host float array     i int   l long   f float   u unsigned long long   s stream
+#   I host int array (list of ints)       F host float array     i int   l long   f float   d double   u unsigned long long   s stream
 # The table is derived from include/hdmoe.h itself, so the binding cannot drift from the declared C ABI.
 HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "hdmoe.h"))
 _HOST_INT_ARRAYS = {"kh", "kw", "pt", "pl", "lens", "sb", "dims"}
@@ -52,6 +52,8 @@ def _parse_header(path: str) -> dict:
                 code += "l"
             elif a.startswith("float"):
                 code += "f"
+            elif a.startswith("double"):
+                code += "d"
             elif a.startswith("int"):
                 code += "i"
             else:
@@ -63,7 +65,7 @@ def _parse_header(path: str) -> dict:
 SIGNATURES = _parse_header(HEADER_PATH)
 
 _CT = {"p": ctypes.c_void_p, "P": ctypes.c_void_p, "I": ctypes.c_void_p, "F": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_long,
-       "f": ctypes.c_float, "u": ctypes.c_ulonglong, "s": ctypes.c_void_p}
+       "f": ctypes.c_float, "d": ctypes.c_double, "u": ctypes.c_ulonglong, "s": ctypes.c_void_p}
 
 _lib = None
 
@@ -144,7 +146,7 @@ def call(name: str, *args):
             arr = _int_array(a); keep.append(arr); conv.append(ctypes.cast(arr, ctypes.c_void_p))
         elif c == "F":
             arr = (ctypes.c_float * len(a))(*[float(v) for v in a]); keep.append(arr); conv.append(ctypes.cast(arr, ctypes.c_void_p))
-        elif c == "f":
+        elif c in "fd":
             conv.append(float(a))
         else:
             conv.append(int(a))

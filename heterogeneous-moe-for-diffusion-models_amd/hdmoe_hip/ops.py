@@ -73,6 +73,12 @@ def _next_seed() -> int:
     return ((_seed_state["seed"] * 0x9E3779B97F4A7C15) ^ (_seed_state["ctr"] * 0xD1B54A32D192ED03)) & 0xFFFFFFFFFFFFFFFF
 
 
+def next_seed() -> int:
+    """The next 64-bit value of the library's seed stream (manual_seed restarts it): one per dropout / noise launch, one per stochastic
+    EDM_Sampler.sample() call on the device path."""
+    return _next_seed()
+
+
 _step_counters = {}
 
 # Independent, launch-latency-bound branches of the model (the ViT experts) run on side streams beside the main stream's
@@ -907,15 +913,38 @@ def axpby(x: Tensor, y: Optional[Tensor], a: float, b: float = 0.0) -> Tensor:
 
 # ---- EDM sampler stage (fp32 latents, schedule t and stage index idx on the device; see include/hdmoe.h).  `known` = (x0, noise, mask) of
 # the inpainting blend epilogue, or None.  Written into preallocated buffers so that the calls can be captured.
-def heun_euler(xn: Tensor, xh: Tensor, den: Tensor, t: Tensor, idx: Tensor, known: Optional[Sequence[Tensor]] = None) -> None:
+# Stochastic stages: `seed` = device int64 word holding the call's 64-bit seed, `t_hat` = device float64 word (the churned sigma); stage i
+# draws the values of randn_keyed(.., seed, i).
+def heun_euler(xn: Tensor, xh: Tensor, den: Tensor, t: Tensor, idx: Tensor, known: Optional[Sequence[Tensor]] = None,
+               t_hat: Optional[Tensor] = None) -> None:
     x0, nz, m = known if known is not None else (None, None, None)
-    call("hdmoe_heun_euler", xn, xh, den, t, idx, xn.numel(), x0, nz, m)
+    if t_hat is None:
+        call("hdmoe_heun_euler", xn, xh, den, t, idx, xn.numel(), x0, nz, m)
+    else:
+        call("hdmoe_heun_euler_hat", xn, xh, den, t, idx, t_hat, xn.numel(), x0, nz, m)
 
 
 def heun_correct(out: Tensor, xh: Tensor, den: Tensor, xn: Tensor, den2: Tensor, t: Tensor, idx: Tensor,
-                 known: Optional[Sequence[Tensor]] = None) -> None:
+                 known: Optional[Sequence[Tensor]] = None, t_hat: Optional[Tensor] = None) -> None:
     x0, nz, m = known if known is not None else (None, None, None)
-    call("hdmoe_heun_correct", out, xh, den, xn, den2, t, idx, out.numel(), x0, nz, m)
+    if t_hat is None:
+        call("hdmoe_heun_correct", out, xh, den, xn, den2, t, idx, out.numel(), x0, nz, m)
+    else:
+        call("hdmoe_heun_correct_hat", out, xh, den, xn, den2, t, idx, t_hat, out.numel(), x0, nz, m)
+
+
+def heun_churn(x_hat: Tensor, x: Tensor, sigma: Tensor, t_hat: Tensor, t: Tensor, idx: Tensor, seed: Tensor, gamma_cap: float, s_min: float,
+               s_max: float, s_noise: float) -> None:
+    """Churn of Heun stage i = idx: t_hat = t[i] (1 + gamma) into t_hat (float64) and sigma (float32), x_hat = x + sqrt(t_hat^2 - t[i]^2)
+    s_noise eps (x_hat may be x).  gamma = gamma_cap where s_min <= t[i] <= s_max, else 0 (then x_hat = x and nothing is drawn)."""
+    call("hdmoe_heun_churn", x_hat, x, sigma, t_hat, t, idx, seed, float(gamma_cap), float(s_min), float(s_max), float(s_noise), x_hat.numel())
+
+
+def dpm2m_sde_step(out: Tensor, x: Tensor, den: Tensor, den_prev: Tensor, t: Tensor, idx: Tensor, i0: Tensor, eta: float, s_noise: float,
+                   seed: Tensor, known: Optional[Sequence[Tensor]] = None) -> None:
+    """One DPM-Solver++(2M) SDE stage (midpoint form) into out: dpm2m_step with the decay exp(-eta h) on x and the stage's noise added."""
+    x0, nz, m = known if known is not None else (None, None, None)
+    call("hdmoe_dpm2m_sde_step", out, x, den, den_prev, t, idx, i0, out.numel(), x0, nz, m, float(eta), float(s_noise), seed)
 
 
 def dpm2m_step(out: Tensor, x: Tensor, den: Tensor, den_prev: Tensor, t: Tensor, idx: Tensor, i0: Tensor,
@@ -1703,6 +1732,15 @@ def dropout(x: Tensor, p: float, training: bool) -> Tensor:
 def randn_like(x: Tensor, scale: float) -> Tensor:
     out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     call("hdmoe_randn", out, _next_seed(), step_counter(x.device), float(scale), out.numel())
+    return out
+
+
+def randn_keyed(x: Tensor, seed: int, stage: int) -> Tensor:
+    """float32 standard normals of x's shape under the key (seed, stage): what hdmoe_randn writes for seed = `seed` and a device counter
+    holding `stage`, i.e. the draw of the sampler's stochastic stage kernels.  Independent of the library's seed stream."""
+    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    key = (int(seed) + int(stage) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+    call("hdmoe_randn", out, key, None, 1.0, out.numel())
     return out
 
 

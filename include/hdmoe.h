@@ -164,7 +164,20 @@ int hdmoe_mul(void* out, const void* x, const void* y, long n, int dtype, HS str
  * t[i+1] == 0: x_out = den;  i == i0: x_out = a x + (1 - a) den;  else, with r = log(t[i-1] / t[i]) / log(t[i] / t[i+1]),
  * x_out = a x + (1 - a) ((1 + 1/(2r)) den - 1/(2r) den_prev);  then the known-region epilogue as above (all NULL or all set), and
  * den_prev <- den in the same pass (den_prev is read before it is written, element by element).  x_out == x is allowed; den_prev must
- * not overlap x_out, x or den.  HDMOE_EINVAL for a NULL required pointer, n < 0, a partial known block or an overlapping den_prev. */
+ * not overlap x_out, x or den.  HDMOE_EINVAL for a NULL required pointer, n < 0, a partial known block or an overlapping den_prev.
+ * Stochastic stages.  Stage i draws one standard normal per latent element: eps[j] is the value hdmoe_randn(out, seed = *seed,
+ * *seed_dev = i, scale = 1, n) writes to out[j] (Philox block j / 4, key *seed + i * 0x9E3779B97F4A7C15), whatever the alignment, the vector
+ * width or n % 4.  seed = device word, i = *idx: nothing random is a launch scalar, so a captured stage replays with fresh noise.
+ * heun_churn (reference :90-97): tc = t[i], gamma = gamma_cap if s_min <= tc <= s_max else 0, *t_hat = tc + gamma tc (double),
+ * *sigma = (float) *t_hat (it stands in for sched_pick(.., 0)), x_hat = x + c eps with c = (float)(sqrt(t_hat^2 - tc^2) s_noise).  gamma == 0:
+ * x_hat = x bit-for-bit, nothing is drawn.  x_hat == x is allowed.  HDMOE_EINVAL for a NULL pointer, n < 0, a negative or non-finite
+ * gamma_cap or s_noise, a NaN s_min or s_max.
+ * heun_euler_hat / heun_correct_hat: heun_euler / heun_correct with t_hat = *t_hat (non-NULL) in place of t[i]; t[i+1] and the blend stay.
+ * dpm2m_sde_step: DPM-Solver++(2M) SDE, midpoint form.  dpm2m_step with h = log(t[i] / t[i+1]), e = exp(-eta h), a = (t[i+1] / t[i]) e,
+ * b = 1 - a (double, each rounded to float once): t[i+1] == 0: x_out = den;  i <= i0: x_out = a x + b den;  else
+ * x_out = a x + b ((1 + 1/(2r)) den - 1/(2r) den_prev);  then, if eta > 0 and t[i+1] != 0, x_out += c eps with
+ * c = (float)(t[i+1] sqrt(1 - e^2) s_noise);  then the known-region epilogue and den_prev <- den.  eta == 0 is dpm2m_step bit-for-bit.
+ * The rules of dpm2m_step apply; also HDMOE_EINVAL for a NULL seed and a negative or non-finite eta or s_noise. */
 int hdmoe_sched_pick(float* sigma, const double* t, const int* idx, int off, HS stream);
 int hdmoe_idx_advance(int* idx, HS stream);
 int hdmoe_heun_euler(float* xn, const float* xh, const float* den, const double* t, const int* idx, long n,
@@ -174,6 +187,15 @@ int hdmoe_heun_correct(float* out, const float* xh, const float* den, const floa
 int hdmoe_known_blend(void* x, const void* x0, const void* noise, const float* mask, float s, long n, int dtype, HS stream);
 int hdmoe_dpm2m_step(float* x_out, const float* x, const float* den, float* den_prev, const double* t, const int* idx, const int* i0, long n,
                      const float* x0, const float* noise, const float* mask, HS stream);
+int hdmoe_heun_churn(float* x_hat, const float* x, float* sigma, double* t_hat, const double* t, const int* idx, const unsigned long long* seed,
+                     double gamma_cap, double s_min, double s_max, double s_noise, long n, HS stream);
+int hdmoe_heun_euler_hat(float* xn, const float* xh, const float* den, const double* t, const int* idx, const double* t_hat, long n,
+                         const float* x0, const float* noise, const float* mask, HS stream);
+int hdmoe_heun_correct_hat(float* out, const float* xh, const float* den, const float* xn, const float* den2, const double* t, const int* idx,
+                           const double* t_hat, long n, const float* x0, const float* noise, const float* mask, HS stream);
+int hdmoe_dpm2m_sde_step(float* x_out, const float* x, const float* den, float* den_prev, const double* t, const int* idx, const int* i0, long n,
+                         const float* x0, const float* noise, const float* mask, float eta, float s_noise, const unsigned long long* seed,
+                         HS stream);
 /* Measurement aid: `blocks` x 256 threads, 8 x `iters` dependent v_exp_f32 per thread (out: blocks * 256 floats).  bench.py times it to state the
  * transcendental issue rate the attention kernels (reference models/model_internals.py:374-404: one exp per score) are bounded by. */
 int hdmoe_exp_rate(float* out, int blocks, int iters, HS stream);
