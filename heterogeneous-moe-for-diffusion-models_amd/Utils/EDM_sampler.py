@@ -21,6 +21,12 @@ Extensions over the reference, all opt-in (``sample()`` keywords; with their def
 image-to-image from ``init_latents`` part-way down the schedule (``strength``), inpainting (``inpaint_mask``: the known region is put back on
 its probability-flow path ``x0 + sigma * noise`` by the epilogue of the update kernels), and expert steering (``Unet_router_mask`` /
 ``Vit_router_mask``, also on ``denoise()``).
+
+``shared_guidance=True`` (extension, opt-in; needs ``Guide_net is model``): a guided evaluation (``guidance != 1``) is ONE pass through
+``model.forward_guided`` instead of two: everything the text does not reach -- time embedding, stem, path scaling, both routers and both
+dispatch plans -- is computed once, both text variants go through the expert banks and the fusion tail as one 2B-row batch, and the guided
+D_x is formed by the egress kernel.  Every solver, ``use_graph`` and every ``sample()`` keyword work with it; ``uncond_text_emb=None``
+then returns the plain D_x exactly (the unconditional branch IS the conditional one).
 """
 import math
 import numbers
@@ -39,7 +45,7 @@ class EDM_Sampler:
     def __init__(self, model: nn.Module, Guide_net: nn.Module, num_solve_steps: int = 32, sigma_min: float = 0.002,
                  sigma_max: float = 80, rho: int = 7, S_churn: float = 0.0, S_min: float = 0.0, S_max: float = float("inf"),
                  S_noise: float = 1.0, guidance: float = 1.0, dtype=torch.float32, use_graph: bool = False, solver: str = "heun",
-                 churn_on_device: bool = False, eta: float = 1.0):
+                 churn_on_device: bool = False, eta: float = 1.0, shared_guidance: bool = False):
         if not isinstance(solver, str) or solver not in SOLVERS:
             raise ValueError(f"solver must be one of {', '.join(map(repr, SOLVERS))}, got {solver!r}")
         if solver != "heun" and S_churn > 0:
@@ -54,6 +60,8 @@ class EDM_Sampler:
             raise ValueError(f"eta (got {eta!r}) is the noise scale of solver='dpmpp_2m_sde' only, not of solver={solver!r}")
         self.model = model
         self.gnet = Guide_net
+        self.shared_guidance = bool(shared_guidance)     # extension: a guided evaluation is ONE shared-routing pass (model.forward_guided)
+        self._check_shared()
         self.num_steps = num_solve_steps
         self.sigma_min = sigma_min
         self.sigma_max = sigma_max
@@ -82,7 +90,8 @@ class EDM_Sampler:
 
     # reference Utils/EDM_sampler.py:35-70
     def denoise(self, x, sigma, text_emb, transition_mean, softness, uncond_text_emb=None, Unet_router_mask=None, Vit_router_mask=None):
-        """One (guided) denoiser evaluation.  Router masks: (B, E) or (E,) with {0, 1} entries, None = every expert allowed (the reference)."""
+        """One (guided) denoiser evaluation.  Router masks: (B, E) or (E,) with {0, 1} entries, None = every expert allowed (the reference).
+        With shared_guidance a guided evaluation is one model.forward_guided pass (inference: call it under torch.no_grad())."""
         um = self._router_mask(Unet_router_mask, "Unet_router_mask", x.shape[0])
         vm = self._router_mask(Vit_router_mask, "Vit_router_mask", x.shape[0])
         return self._denoise(x, sigma, text_emb, transition_mean, softness, uncond_text_emb, self._dev_mask(um, x), self._dev_mask(vm, x))
@@ -95,6 +104,11 @@ class EDM_Sampler:
         vit_router_mask = torch.ones((bs, num_experts), device=x.device) if vm is None else vm
         kw = dict(x=x, sigma=sigma, Unet_router_mask=Unet_router_mask, Vit_router_mask=vit_router_mask, zeta=0,
                   transition_point=transition_mean, softness=softness)
+        if self.shared_guidance and self.guide != 1.0:
+            # one pass: routing (and so the router masks) once, both text variants through the banks and the tail, the lerp in the egress
+            self._check_shared()
+            return self.model.forward_guided(text_emb=text_emb, uncond_text_emb=uncond_text_emb, guidance=self.guide,
+                                             **kw)["denoised"].to(self.dtype)
         D_x = self.model(text_emb=text_emb, **kw)["denoised"].to(self.dtype)
         if self.guide == 1.0:
             return D_x
@@ -104,6 +118,16 @@ class EDM_Sampler:
         return ops.axpby(ref_D_x, D_x, 1.0 - self.guide, self.guide)
 
     # ---- argument checks of the extensions: ValueError naming the argument, before any device work ------------------------------------
+    def _check_shared(self):
+        """shared_guidance shares the routing of ONE network between the two text variants: the guide network must be the model itself,
+        and the model must have the shared pass."""
+        if not self.shared_guidance:
+            return
+        if self.gnet is not self.model:
+            raise ValueError("shared_guidance=True needs Guide_net to be the model itself (a different guide network takes two passes)")
+        if not callable(getattr(self.model, "forward_guided", None)):
+            raise ValueError(f"shared_guidance=True needs a model with forward_guided(); {type(self.model).__name__} has none")
+
     def _router_mask(self, m, name, bs):
         """Checked router mask as a float32 (B, E) tensor on m's device, or None.  A row without an allowed expert is refused: the gate
         would give NaN probabilities for it and silently drop the expert output."""
@@ -182,7 +206,7 @@ class EDM_Sampler:
         key = (kind, self.solver, shape(x), x.dtype, shape(text_emb), shape(uncond_text_emb), float(transition_mean), float(softness),
                self.num_steps, bool(self.use_graph), None if known is None else tuple(map(shape, known)), shape(um), shape(vm),
                float(self.guide), id(self.model), id(self.gnet), float(self.s_churn), float(self.s_min), float(self.s_max), float(self.s_noise),
-               float(self.eta), bool(self.churn_on_device))
+               float(self.eta), bool(self.churn_on_device), bool(self.shared_guidance))
         slot = "_graph" if kind == "eval" else "_stage"          # one cached state for the evaluation, one for the solver stage
         st = getattr(self, slot)
         if st is not None and st["key"] == key:

@@ -663,6 +663,25 @@ __global__ void nhwc_to_nchw_kernel(float* out, const T* F, const float* sf, con
   }
 }
 
+// Guided egress: F holds the head output of a [conditional ; unconditional] stack of 2N rows (the second half starts `half` = N*HW*C
+// elements in).  out_nchw[n] = sx[n]*x_nchw[n] + sf[n]*((1 - g)*F[N + n] + g*F[n]): the EDM egress above and the classifier-free-guidance
+// lerp of the two denoiser outputs in one read of F and one write of out.  Written so that g == 1 reduces to the kernel above operation
+// by operation (the lerp then returns F[n] exactly).
+template <typename T>
+__global__ void nhwc_to_nchw_guided_kernel(float* out, const T* F, const float* sf, const float* x, const float* sx, float g, int C, long HW,
+                                           long n) {
+  const float gu = 1.f - g;
+  GRID_STRIDE(i, n) {
+    long t = i; const long p = t % HW; t /= HW;
+    const int c = (int)(t % C); const long b = t / C;
+    const long f = (b * HW + p) * C + c;
+    float v = gu * to_f(F[n + f]) + g * to_f(F[f]);
+    if (sf) v *= sf[b];
+    if (x) v += (sx ? sx[b] : 1.f) * x[i];
+    out[i] = v;
+  }
+}
+
 // ---------------------------------------------------------------- patch <-> image relayout (Vit_expert, model_components.py:698-704)
 // tok[b][(hp,wp)][f] <-> img[b][hp*p+i][wp*p+j][c];  order 0: f = (i*p+j)*C + c ;  order 1 (PixelShuffle): f = c*p*p + i*p + j
 template <typename T, bool TO_IMG>
@@ -1478,6 +1497,12 @@ int hdmoe_nhwc_to_nchw(float* out, const void* F, const float* sf, const float* 
                        int dtype, hipStream_t stream) {
   const long n = (long)N * C * HW;
   DT_SWITCH(dtype, L1D(nhwc_to_nchw_kernel<T>, n, out, (const T*)F, sf, x, sx, C, HW, n))
+}
+int hdmoe_nhwc_to_nchw_guided(float* out, const void* F, const float* sf, const float* x, const float* sx, float g, int N, int C, long HW,
+                              int dtype, hipStream_t stream) {
+  if (!out || !F || N < 1 || C < 1 || HW < 1 || !(g == g) || g - g != 0.f) return HDMOE_EINVAL;
+  const long n = (long)N * C * HW;
+  DT_SWITCH(dtype, L1D(nhwc_to_nchw_guided_kernel<T>, n, out, (const T*)F, sf, x, sx, g, C, HW, n))
 }
 int hdmoe_patch_relayout(void* out, const void* in, int N, int H, int W, int C, int p, int hp, int wp, int order,
                          int to_img, int dtype, hipStream_t stream) {

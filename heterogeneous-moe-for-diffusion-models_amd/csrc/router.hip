@@ -141,6 +141,23 @@ __global__ void gather_rows_scalar_kernel(T* dst, const T* src, const int* perm,
     dst[i] = s >= 0 ? src[(long)s * L + c] : from_f<T>(0.f);
   }
 }
+// dst[r][:] = src[perm[r] % Bsrc][:]: the plan was built over a stack of copies of the Bsrc source rows (the guided evaluation's
+// [conditional ; unconditional] halves share the stem features and the time embedding), the source is stored once
+__global__ void gather_rows_paired_kernel(uint4* dst, const uint4* src, const int* perm, int Bsrc, long Lv, long n) {
+  GRID_STRIDE(i, n) {
+    const long r = i / Lv, c = i - r * Lv;
+    const int s = perm[r];
+    dst[i] = s >= 0 ? src[(long)(s % Bsrc) * Lv + c] : make_uint4(0, 0, 0, 0);
+  }
+}
+template <typename T>
+__global__ void gather_rows_paired_scalar_kernel(T* dst, const T* src, const int* perm, int Bsrc, long L, long n) {
+  GRID_STRIDE(i, n) {
+    const long r = i / L, c = i - r * L;
+    const int s = perm[r];
+    dst[i] = s >= 0 ? src[(long)(s % Bsrc) * L + c] : from_f<T>(0.f);
+  }
+}
 // out[b][:] = sum_j w[r_j] * ys[r_j][:], r_j = inv[b][j]  (weights optional)
 template <typename T>
 __global__ void combine_rows_fwd_kernel(T* out, const T* ys, const int* inv, const float* row_w, int kcap, long L, long n) {
@@ -238,6 +255,21 @@ int hdmoe_gather_rows(void* dst, const void* src, const int* perm, long R, long 
     hipLaunchKernelGGL(gather_rows_scalar_kernel<float>, dim3(grid_for(R * L)), dim3(TPB), 0, stream, (float*)dst, (const float*)src, perm, L, R * L);
   } else {
     hipLaunchKernelGGL(gather_rows_scalar_kernel<bf16>, dim3(grid_for(R * L)), dim3(TPB), 0, stream, (bf16*)dst, (const bf16*)src, perm, L, R * L);
+  }
+  return hdmoe_launch_status();
+}
+int hdmoe_gather_rows_paired(void* dst, const void* src, const int* perm, long R, long L, int Bsrc, int dtype, hipStream_t stream) {
+  const long esz = dtype == HDMOE_F32 ? 4 : 2;
+  if (dtype != HDMOE_F32 && dtype != HDMOE_BF16) return HDMOE_EDTYPE;
+  if (!dst || !src || !perm || R < 0 || L < 1 || Bsrc < 1) return HDMOE_EINVAL;
+  if (R == 0) return HDMOE_OK;
+  if ((L * esz) % 16 == 0 && (uintptr_t)dst % 16 == 0 && (uintptr_t)src % 16 == 0) {
+    const long Lv = L * esz / 16, n = R * Lv;
+    hipLaunchKernelGGL(gather_rows_paired_kernel, dim3(grid_for(n)), dim3(TPB), 0, stream, (uint4*)dst, (const uint4*)src, perm, Bsrc, Lv, n);
+  } else if (dtype == HDMOE_F32) {
+    hipLaunchKernelGGL(gather_rows_paired_scalar_kernel<float>, dim3(grid_for(R * L)), dim3(TPB), 0, stream, (float*)dst, (const float*)src, perm, Bsrc, L, R * L);
+  } else {
+    hipLaunchKernelGGL(gather_rows_paired_scalar_kernel<bf16>, dim3(grid_for(R * L)), dim3(TPB), 0, stream, (bf16*)dst, (const bf16*)src, perm, Bsrc, L, R * L);
   }
   return hdmoe_launch_status();
 }

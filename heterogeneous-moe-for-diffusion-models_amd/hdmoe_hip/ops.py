@@ -1822,6 +1822,19 @@ def nhwc_to_nchw_f32(F: Tensor, sf: Optional[Tensor] = None, x: Optional[Tensor]
     return _FromNHWCFn.apply(F, sf, x, sx)
 
 
+def nhwc_to_nchw_guided(F: Tensor, sf: Tensor, x: Tensor, sx: Tensor, guidance: float) -> Tensor:
+    """Guided EDM egress of the pair-stacked head output F (2N, H, W, C) = [conditional ; unconditional]:
+    out[n] = sx[n] x[n] + sf[n] ((1 - g) F[N + n] + g F[n]), float32 NCHW (N rows).  Inference only."""
+    F = _c(F.detach())
+    N2, H, W, C = F.shape
+    if N2 % 2 or x.shape != (N2 // 2, C, H, W):
+        raise ValueError(f"nhwc_to_nchw_guided: F {tuple(F.shape)} is not a pair-stacked batch of x {tuple(x.shape)}")
+    N = N2 // 2
+    out = torch.empty((N, C, H, W), dtype=torch.float32, device=F.device)
+    call("hdmoe_nhwc_to_nchw_guided", out, F, _f32(sf.detach()), _f32(x.detach()), _f32(sx.detach()), float(guidance), N, C, H * W, _dt(F))
+    return out
+
+
 class _PatchRelayoutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tok, meta):
@@ -2486,6 +2499,18 @@ class _GatherFn(torch.autograd.Function):
 def gather_rows(x: Tensor, plan: DispatchPlan) -> Tensor:
     """x[perm] : (B, ...) -> (R, ...) in expert-contiguous order (zeros in unused rows)."""
     return _GatherFn.apply(x, plan)
+
+
+def gather_rows_paired(x: Tensor, plan: DispatchPlan, B: int) -> Tensor:
+    """x[perm % B] : (B, ...) -> (R, ...) for a plan built over stacked copies of the B source rows (the guided evaluation's
+    [conditional ; unconditional] plan over the shared stem features / time embedding); zeros in unused rows.  Inference only."""
+    x = _c(x.detach())
+    if x.shape[0] != B or plan.B % B != 0:
+        raise ValueError(f"gather_rows_paired: {x.shape[0]} source rows, B = {B}, plan over {plan.B} rows")
+    L = x.numel() // B
+    out = torch.empty((plan.R, *x.shape[1:]), dtype=x.dtype, device=x.device)
+    call("hdmoe_gather_rows_paired", out, x, plan.perm, plan.R, L, B, _dt(x))
+    return out
 
 
 class _CombineFn(torch.autograd.Function):

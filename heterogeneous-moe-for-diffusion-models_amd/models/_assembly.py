@@ -77,6 +77,35 @@ def _dispatch_nhwc(x: Tensor, experts: nn.ModuleList, out_router: Tensor, time_e
     return _combine_weighted(_run_experts(x, mods, time_emb, text2d), out_router)
 
 
+def _bank_kind(mods: List[nn.Module], H: int, W: int) -> Optional[str]:
+    """Which banked path _dispatch_nhwc takes for this expert list ("unet" / "vit"), None for the per-expert fallback."""
+    if all(isinstance(e, m.Unet_expert) for e in mods) and len(mods) <= 8:
+        return "unet"
+    if VIT_BANK and m.vit_bank_compatible(mods, H, W):
+        return "vit"
+    return None
+
+
+def _dispatch_pair(x: Tensor, experts: nn.ModuleList, out_router: Tensor, time_emb: Tensor, text2d: Tensor, kcap: int) -> Tensor:
+    """_dispatch_nhwc for the guided evaluation (inference): x (B,H,W,C), time_emb (B,T) and the routing weights (B,E) are shared by the
+    two text variants, text2d (2B,text_dim) is pair-stacked.  The plan of [w ; w] is expert-contiguous and sample-stable, so each expert's
+    segment holds its conditional rows, then the same samples' unconditional rows: seg2[e] = 2 seg[e].  -> (2B,H,W,C), pair-stacked.
+    The expert-usage counters are the optimizer's and are not touched."""
+    mods = list(experts)
+    B = x.shape[0]
+    kind = _bank_kind(mods, x.shape[1], x.shape[2])
+    w2 = torch.cat([out_router, out_router])                               # (2B, E) floats; the latents are never duplicated
+    plan = ops.DispatchPlan(w2, kcap)
+    xs = ops.gather_rows_paired(x, plan, B)
+    ts = ops.gather_rows_paired(time_emb, plan, B)
+    tx = ops.gather_rows(text2d, plan)
+    if kind == "unet":
+        ys = m.unet_expert_bank_forward(mods, xs, ts, tx, plan.seg)
+    else:
+        ys = m.vit_expert_bank_forward(mods, xs, ts, tx, plan.seg)
+    return ops.combine_rows(ys, w2, plan)
+
+
 def _note_usage_sparse(experts: nn.ModuleList, out_router: Tensor) -> None:
     """Per-expert routed-row counts from the sparse gate weights (the path without a dispatch plan); see _dispatch_nhwc.note_usage."""
     if not (torch.is_grad_enabled() and isinstance(experts, nn.ModuleList)):
@@ -278,7 +307,12 @@ class _HDMOEMBase(nn.Module):
                 out_v = _combine_weighted(vit_job, w_vit)
             else:
                 out_v = _dispatch_nhwc(ops.cast(in_vit, cdt), self.VIT_experts, w_vit, te, text2d, kcap=self.top_k)
-        C = self.internal_channels
+        out, gate = self._fusion_tail(out_u, out_v, s_vit, s_unet, text_c, **kw)
+        return out, p_unet, raw_unet, p_vit, raw_vit, scaling, gate
+
+    def _fusion_tail(self, out_u: Tensor, out_v: Tensor, s_vit: Tensor, s_unet: Tensor, text_c: Optional[Tensor], **kw):
+        """Cross-attention fusion of the two bank outputs -> text cross-attention -> soft gate -> head; every operand has out_u's rows."""
+        B, H, W, C = out_u.shape
         fu = out_u.reshape(B, H * W, C)                                     # channel-last image == (B, S, C) tokens
         fv = out_v.reshape(B, H * W, C)
         q, ctx = self._fusion_inputs(fu, fv, s_vit, s_unet, **kw)
@@ -289,8 +323,51 @@ class _HDMOEMBase(nn.Module):
         g = self.gate1._fwd(ops.mp_cat(out_u, a_img, 0.5))
         g = self.gate2._fwd(ops.mp_silu(g))
         mixed, gate = ops.gate_mix(g, out_u, a_img)                         # softmax gate + mix + mp_sum(out_u, ., 0.5)
-        out = self.output_proj._fwd(mixed)
-        return out, p_unet, raw_unet, p_vit, raw_vit, scaling, gate
+        return self.output_proj._fwd(mixed), gate
+
+    def _fwd_guided(self, x: Tensor, time_vec: Tensor, text_emb: Tensor, uncond_text_emb: Tensor, Unet_router_mask: Tensor,
+                    Vit_router_mask: Tensor, zeta, **kw):
+        """One pass for both text variants of a classifier-free-guidance evaluation (inference).  The text reaches only the expert banks
+        and cross_attn_text: time embedding, stem, path scaling, both routers and their decisions are computed once on B rows; the banks
+        and the fusion tail run on the pair-stacked batch [conditional rows 0..B-1 ; unconditional rows B..2B-1].
+        Returns (out (2B,H,W,C_in) channel-last, p_unet, raw_unet, p_vit, raw_vit, scaling) -- the routing outputs per sample, B rows."""
+        B, H, W, _ = x.shape
+        cdt = hdmoe_hip.compute_dtype()
+        time_vec = ops.cast(time_vec, torch.float32)
+        te = self.Fourier_emb(time_vec)
+        te = self.out_fourier1._fwd(te)
+        te = self.out_fourier2._fwd(ops.mp_silu(te))
+        feats = self.input_proj._fwd(x)
+        s_vit, s_unet, scaling = self._scaling(time_vec, te, zeta, **kw)
+        in_unet = ops.scale_rows(feats, s_unet)
+        in_vit = ops.scale_rows(feats, s_vit)
+        text32 = ops.cast(torch.cat([text_emb, uncond_text_emb]), torch.float32)        # pair-stacked text: the one operand that differs
+        text2d = ops.seq_mean(text32) if text32.ndim == 3 else text32
+        text_c = ops.cast(text32, cdt)
+        for experts in (self.Unet_experts, self.VIT_experts):
+            if _bank_kind(list(experts), H, W) is None:
+                raise NotImplementedError("forward_guided runs the banked expert paths only (a U-Net expert bank of at most 8 experts, or a "
+                                          "ViT expert bank): this expert list takes the per-expert fallback, which has no shared-routing form")
+        w_vit, p_vit, raw_vit, _ = self.vit_router._fwd(in_vit, te, Vit_router_mask, zeta)
+        if ops.SIDE_STREAMS and x.is_cuda:
+            fork = torch.cuda.Event()
+            fork.record(torch.cuda.current_stream())                        # the ViT bank depends on nothing issued after this point
+        w_unet, p_unet, raw_unet, _ = self.Unet_router._fwd(in_unet, te, Unet_router_mask, zeta)
+        out_u = _dispatch_pair(ops.cast(in_unet, cdt), self.Unet_experts, w_unet, te, text2d, self.top_k)
+        if ops.SIDE_STREAMS and x.is_cuda:                                  # the ViT bank on its own stream, as in _fwd
+            side = ops.side_streams(x.device, 1)[0]
+            side.wait_event(fork)
+            with torch.cuda.stream(side):
+                out_v = _dispatch_pair(ops.cast(in_vit, cdt), self.VIT_experts, w_vit, te, text2d, self.top_k)
+            wbank.note_forked_streams([side])
+            torch.cuda.current_stream().wait_stream(side)
+            out_v.record_stream(torch.cuda.current_stream())
+        else:
+            out_v = _dispatch_pair(ops.cast(in_vit, cdt), self.VIT_experts, w_vit, te, text2d, self.top_k)
+        if self._has_scaling_net:                                           # only this variant's _fusion_inputs reads them: B floats, tiled
+            s_vit, s_unet = s_vit.repeat(2), s_unet.repeat(2)
+        out, _ = self._fusion_tail(out_u, out_v, s_vit, s_unet, text_c, **kw)
+        return out, p_unet, raw_unet, p_vit, raw_vit, scaling
 
     def _public(self, res):
         out, p_u, raw_u, p_v, raw_v, scaling, gate = res
@@ -319,6 +396,36 @@ class _PrecondBase(nn.Module):
             return self._forward_impl(x, sigma, text_emb, Unet_router_mask, Vit_router_mask, zeta, return_log_var, **kw)
         finally:
             wbank.deactivate()
+
+    def _forward_guided(self, x: Tensor, sigma: Tensor, text_emb: Tensor, uncond_text_emb: Optional[Tensor], guidance: float,
+                        Unet_router_mask: Tensor, Vit_router_mask: Tensor, zeta, **kw):
+        """The classifier-free-guidance evaluation (1 - g) D(x; uncond) + g D(x; text) as ONE pass with shared routing (inference only):
+        net._fwd_guided on the pair-stacked batch, the guided D_x formed by the egress kernel.  uncond_text_emb None: the unconditional
+        branch is the conditional one (the reference's ref.lerp(D, g) with ref = D), i.e. the plain evaluation."""
+        tensors = [t for t in (x, sigma, text_emb, uncond_text_emb) if isinstance(t, Tensor)]
+        if torch.is_grad_enabled() and (any(t.requires_grad for t in tensors) or any(p.requires_grad for p in self.parameters())):
+            raise RuntimeError("forward_guided is inference only: call it under torch.no_grad() (gradients take forward())")
+        if hgraph.current() is not None:
+            raise RuntimeError("forward_guided is inference only: not inside a staged training step")
+        if uncond_text_emb is None:
+            return self._forward(x, sigma, text_emb, Unet_router_mask, Vit_router_mask, zeta, False, **kw)
+        if not isinstance(uncond_text_emb, Tensor) or tuple(uncond_text_emb.shape) != tuple(text_emb.shape):
+            raise ValueError(f"uncond_text_emb must have the shape of text_emb {tuple(text_emb.shape)}, got "
+                             f"{tuple(getattr(uncond_text_emb, 'shape', ())) or type(uncond_text_emb).__name__}")
+        B = x.shape[0]
+        wbank.bank_for(self).begin_step(self.training)
+        try:
+            coef = ops.edm_coeffs(sigma, self.sigma_data, B)                # rows: c_skip, c_out, c_in, c_noise
+            c_skip, c_out, c_in, c_noise = coef[0], coef[1], coef[2], coef[3]
+            x32 = ops.cast(x, torch.float32)
+            xs = ops.to_nhwc(x32, scale=c_in, dtype=torch.float32)
+            out, p_u, raw_u, p_v, raw_v, scaling = self.net._fwd_guided(xs, c_noise, text_emb, uncond_text_emb.to(text_emb.dtype),
+                                                                         Unet_router_mask, Vit_router_mask, zeta, **kw)
+            D_x = ops.nhwc_to_nchw_guided(out, c_out, x32, ops.mul(c_skip, c_in), guidance)
+        finally:
+            wbank.deactivate()
+        return {"denoised": D_x, "Unet_router_loss": p_u, "Unet_raw": raw_u, "vit_router_loss": p_v, "vit_raw": raw_v,
+                "scaling_net_out": scaling}
 
     def _forward_impl(self, x: Tensor, sigma: Tensor, text_emb: Tensor, Unet_router_mask: Tensor, Vit_router_mask: Tensor, zeta,
                       return_log_var: bool, **kw):

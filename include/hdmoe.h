@@ -245,6 +245,10 @@ int hdmoe_softmax_rows_bwd(float* dx, const float* dy, const float* y, long rows
 int hdmoe_nchw_to_nhwc(void* out, const float* x, const float* s, int N, int C, long HW, int dtype, HS stream);  /* + per-sample scale (c_in) */
 int hdmoe_nhwc_to_nchw(float* out, const void* F, const float* sf, const float* x, const float* sx, int N, int C,
                        long HW, int dtype, HS stream);                                                           /* sf*F + sx*x : D_x, model_config2.py:449 */
+/* guided egress: F is the head output of the pair-stacked batch [conditional rows 0..N-1 ; unconditional rows N..2N-1] (NHWC);
+ * out[n] = sx[n] x[n] + sf[n] ((1 - g) F[N + n] + g F[n]) -- the EDM egress and the classifier-free-guidance lerp in one pass */
+int hdmoe_nhwc_to_nchw_guided(float* out, const void* F, const float* sf, const float* x, const float* sx, float g, int N,
+                              int C, long HW, int dtype, HS stream);
 int hdmoe_patch_relayout(void* out, const void* in, int N, int H, int W, int C, int p, int hp, int wp, int order,
                          int to_img, int dtype, HS stream);                                                      /* PixelShuffle / patchify */
 int hdmoe_fourier(float* out, const float* x, const float* freqs, const float* phases, int B, int F, HS stream); /* model_internals.py:171-174 */
@@ -375,6 +379,9 @@ int hdmoe_seg_counts(float* counts, const int* seg, int E, HS stream);
  * the whole batch (no dispatch plan); reference models/model_config1.py:26-29. */
 int hdmoe_route_counts(float* counts, const float* sparse, int B, int E, HS stream);
 int hdmoe_gather_rows(void* dst, const void* src, const int* perm, long R, long L, int dtype, HS stream);
+/* dst[r] = src[perm[r] % Bsrc] (zeros where perm[r] < 0): gather for a plan built over stacked copies of Bsrc source rows -- the
+ * guided evaluation's 2B-row plan over B-row stem features / time embeddings, which are stored once */
+int hdmoe_gather_rows_paired(void* dst, const void* src, const int* perm, long R, long L, int Bsrc, int dtype, HS stream);
 int hdmoe_combine_rows_fwd(void* out, const void* ys, const int* inv, const float* row_w, long B, int kcap, long L,
                            int dtype, HS stream);
 int hdmoe_combine_rows_bwd(void* dys, float* dsparse, const void* dout, const void* ys, const int* perm,
