@@ -38,8 +38,8 @@ def _f32(t: Tensor) -> Tensor:
 
 _seed_state = {"seed": 0x5DEECE66D, "ctr": 0}
 
-# Host-side counters of which fused paths a step took ("trunk": fused router trunk forward, "bwd6" / "bwd6s": dgrad + wgrad in one
-# launch, "w6_defer": deferred wgrad6 reduction, "blk": fused Unet_block main branch): the parity tests assert that the path they
+# Host-side counters of which fused paths a step took ("trunk": fused router trunk forward, "bwd6" / "bwd6s" / "pbwd": dgrad + wgrad in one
+# launch (k x k / split-bf16 trunk / pointwise), "w6_defer": deferred wgrad6 reduction, "blk": fused Unet_block main branch): the parity tests assert that the path they
 # pin to the reference is the one the benchmark times.
 import collections as _collections
 STATS = _collections.Counter()
@@ -411,7 +411,8 @@ def _fused_bwd(bank, ent, label, name, x, dy, wd, dx, mid, ws, tail, defer, stat
     ``name(x, dy, wd, dx, ent.G, *mid, ws, ws bytes, *tail)``.  On success ``defer`` = (seg, G, N, H, W, I, O, dtype code, khs)
     leaves the partial slabs in ``ws`` to the bank's batched reduction, the layer is noted for the bank's finish and the ``stats``
     keys are counted.  False: the layer is outside the launch's domain (nothing was launched)."""
-    if _timed("fused", label, name, x, dy, wd, dx, list(ent.G), *mid, ws, ws.numel() * 4, *tail) != 0:
+    wsargs = () if ws is None else (ws, ws.numel() * 4)       # (ws None: a launch without workspace -- hdmoe_pw_bwd)
+    if _timed("fused", label, name, x, dy, wd, dx, list(ent.G), *mid, *wsargs, *tail) != 0:
         return False
     if defer is not None:
         seg, *shape = defer
@@ -570,6 +571,15 @@ class _MPConvFn(torch.autograd.Function):
                     defer, stats = None, ()                   # (reduced inside the launch, into the bank's slabs)
                 dxo = torch.empty_like(x) if nig[0] else None
                 fused = _fused_bwd(ctx.bank, ent, label, name, x, dy, ctx.wd, dxo, mid, ws, tail, defer, stats)
+                dx = dxo if fused else None
+            elif (fast is None and nig[0] and _prof_ok() and not ones and not split and x.dtype == torch.bfloat16 and Cphys == I
+                  and Ho == H and Wo == W and all(k == 1 for k in khs) and all(k == 1 for k in kws)):
+                # pointwise layer (linear / 1x1): both gradients in one launch that reads dy once (csrc/pbwd.hip); no workspace,
+                # the weight gradient goes straight into the bank's slabs
+                label = dict(name="pw_bwd_kernel", dtype="bfloat16", seg=seg, N=N, HW=H * W, O=O, I=I, taps=[1] * G, mult=2.0)
+                dxo = torch.empty_like(x)
+                fused = _fused_bwd(ctx.bank, ent, label, "hdmoe_pw_bwd", x, dy, ctx.wd, dxo,
+                                   (seg, G, wdstride, N, H * W, I, O, alpha), None, (_dt(x),), None, ("pbwd",))
                 dx = dxo if fused else None
         if nig[0] and not fused:
             wd = ctx.wd

@@ -83,6 +83,12 @@ int hdmoe_conv_wgrad6(const void* x, const void* dy, float* const* G, const int*
 int hdmoe_conv_bwd6(const void* x, const void* dy, const void* wd, void* dx, float* const* G, const int* seg, int ngroups,
                     long wd_stride, int N, int H, int W, int Cin, int Cout, const int* kh, const int* kw, const int* pt,
                     const int* pl, float alpha, void* ws, long ws_bytes, int dtype, HS stream);
+/* Input gradient and weight gradient of one (grouped) POINTWISE bf16 layer (linear / 1x1, stride 1, no ones channel) in ONE launch
+ * (csrc/pbwd.hip): x [N * HW][Cin], dy [N * HW][Cout], dx = alpha * dy * w from the flipped image wd ([g][Cin][Cout], wd_stride
+ * elements per group), G[g] ([Cout][Cin] fp32) += dy^T x.  dy is read once.  Domain: Cin % 32 == 0, Cout % 32 == 0, both <= 128,
+ * (Cin / 32) * (Cout / 32) <= 8.  Returns 1 without launching outside it; the caller then uses hdmoe_conv_fwd + hdmoe_conv_wgrad. */
+int hdmoe_pw_bwd(const void* x, const void* dy, const void* wd, void* dx, float* const* G, const int* seg, int ngroups,
+                 long wd_stride, int N, long HW, int Cin, int Cout, float alpha, int dtype, HS stream);
 int hdmoe_conv_bwd6s(const void* x, const void* dy, const void* wd, void* dx, float* const* G, const int* seg, int ngroups,
                      long wd_stride, long wd_plane, int N, int H, int W, int Cin, int Cout, const int* kh, const int* kw,
                      const int* pt, const int* pl, float alpha, void* ws, long ws_bytes, const float* in_scale, const float* in_shift,
@@ -137,7 +143,8 @@ enum {
   HDMOE_SEL_WGRAD8_C12 = 15,     /*   1 x 2 */
   HDMOE_SEL_WGRAD8_C21 = 16,     /*   2 x 1 */
   HDMOE_SEL_WGRAD8_C22 = 17,     /*   2 x 2 */
-  HDMOE_SEL_COUNT = 18
+  HDMOE_SEL_PW_BWD = 18,         /* hdmoe_pw_bwd: pointwise layer, input + weight gradient in one launch */
+  HDMOE_SEL_COUNT = 19
 };
 int hdmoe_kernel_selections(long long* counts, int n, int reset);
 
