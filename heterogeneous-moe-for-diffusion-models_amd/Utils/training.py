@@ -46,9 +46,10 @@ def build_scheduler(optimizer: torch.optim.Optimizer, optim_config: Dict[str, An
                                                       eta_min=optim_config["eta_min"])
 
 
-def save_checkpoint(model, optimizer, step, mse_score, configs, filename) -> str:
+def save_checkpoint(model, optimizer, step, mse_score, configs, filename, ema=None) -> str:
     """Same dictionary and path rules as reference training.py:242-271 (keys step / model_state_dict /
-    optimizer_state_dict / mse / config); tensors are written from host copies so the file loads on any device."""
+    optimizer_state_dict / mse / config); tensors are written from host copies so the file loads on any device.
+    With `ema` (hdmoe_hip.ema.WeightEMA) the file additionally carries "ema_state_dict"; without it the dictionary is the reference's."""
     if "save_dir" in configs:
         save_path = configs["save_dir"]
     elif "model_configs" in configs and "save_dir" in configs["model_configs"]:
@@ -60,18 +61,22 @@ def save_checkpoint(model, optimizer, step, mse_score, configs, filename) -> str
     model_state = model.module.state_dict() if hasattr(model, "module") else model.state_dict()
     checkpoint = {"step": step, "model_state_dict": model_state, "optimizer_state_dict": optimizer.state_dict(),
                   "mse": mse_score, "config": configs}
+    if ema is not None:
+        checkpoint["ema_state_dict"] = ema.state_dict()
     torch.save(checkpoint, str(full_path))
     print(f"   [Save] Checkpoint saved: {full_path}")
     return full_path
 
 
-def load_checkpoint(path: str, model: torch.nn.Module, optimizer: Optional[torch.optim.Optimizer] = None, map_location=None) -> dict:
+def load_checkpoint(path: str, model: torch.nn.Module, optimizer: Optional[torch.optim.Optimizer] = None, map_location=None, ema=None) -> dict:
     """Inverse of `save_checkpoint` (reference training.py:303-304 loads only the model; resuming also needs the
-    optimizer moments).  Accepts files written by the reference's torch.optim.AdamW as well."""
+    optimizer moments).  Accepts files written by the reference's torch.optim.AdamW as well.  `ema` is restored when the file has one."""
     ck = torch.load(f=path, map_location=map_location, weights_only=False)
     model.load_state_dict(ck["model_state_dict"])
     if optimizer is not None and "optimizer_state_dict" in ck:
         optimizer.load_state_dict(ck["optimizer_state_dict"])
+    if ema is not None and "ema_state_dict" in ck:
+        ema.load_state_dict(ck["ema_state_dict"])
     return ck
 
 
@@ -80,7 +85,7 @@ class Trainer:
     generation, fused loss, flat-bucket gradient all-reduce, fused clip + AdamW)."""
 
     def __init__(self, model, model_config, optim_config, loss_config, mask_config, zeta_config, max_grad_norm: float = 1.0,
-                 fuse_clip_into_step: bool = True, logger=None):
+                 fuse_clip_into_step: bool = True, logger=None, ema=None):
         self.model, self.cfg, self.mask_cfg = model, model_config, mask_config
         self.optimizer = build_optimizer(model, optim_config)
         self.scheduler = build_scheduler(self.optimizer, optim_config)
@@ -98,6 +103,7 @@ class Trainer:
         self.buckets = GradBuckets(model)                    # .grad become views of flat fp32 buckets (all-reduced when world > 1)
         self.max_grad_norm, self.fuse = float(max_grad_norm), fuse_clip_into_step
         self.logger = logger                                 # graphs.logger.Logger (sync-free) or None
+        self.ema = ema                                       # hdmoe_hip.ema.WeightEMA or None: averaged right after every optimizer step
         self._clip_params = [p for p in model.parameters()]
         self.step_idx = 0
 
@@ -131,6 +137,8 @@ class Trainer:
         else:
             clip_grad_norm_(self._clip_params, self.max_grad_norm)
             self.optimizer.step()
+        if self.ema is not None:
+            self.ema.update()
         self.scheduler.step()
         self.step_idx += 1
         return {"loss": loss, "out_model": out_model, "sigma": sigma}

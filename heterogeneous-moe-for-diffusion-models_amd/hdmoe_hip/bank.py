@@ -48,10 +48,10 @@ def note_weights_changed() -> None:
 
 
 def invalidate_weights() -> None:
-    """Call after writing parameters behind autograd's back -- ``p.data.copy_()`` / ``lerp_`` / ``mul_`` (the usual EMA idiom) or a
-    loader that assigns through ``.data`` do not bump ``Tensor._version`` -- so that the next eval-mode forward re-prepares the weight
-    images.  (``load_state_dict``, in-place ops on the parameter itself, ``FusedAdamW.step`` and the train-mode forward are tracked
-    automatically; ``EDM_Sampler.sample`` additionally compares a device-side checksum of the parameters before replaying its graph.)"""
+    """Call after writing parameters behind autograd's back -- ``p.data.copy_()`` / ``lerp_`` / ``mul_`` or a loader that assigns
+    through ``.data`` do not bump ``Tensor._version`` -- so that the next eval-mode forward re-prepares the weight images.  (For an EMA
+    of the weights use ``hdmoe_hip.WeightEMA``: its ``swapped`` / ``copy_to`` call this themselves.  ``load_state_dict``, in-place ops on
+    the parameter itself, ``FusedAdamW.step`` and the train-mode forward are tracked automatically; ``EDM_Sampler.sample`` additionally compares a device-side checksum of the parameters before replaying its graph.)"""
     note_weights_changed()
 
 

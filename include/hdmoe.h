@@ -437,6 +437,21 @@ int hdmoe_mt_clip_scale(const void* descs, const int* chunks, int nchunks, const
 int hdmoe_mt_adamw(const void* descs, const int* chunks, int nchunks, int ntensors, const float* sumsq, float max_norm, const float* group_lr,
                    const float* group_wd, int ngroups, float beta1, float beta2, float eps, HS stream);
 
+/* ---- N4: exponential moving average of the weights (EDM2 power-function profiles; no counterpart in the reference) ---------------- */
+/* descs: device array of {p, e[4] addresses, numel} (hdmoe_ema_desc_bytes() bytes each), all fp32; chunks: device int32 pairs
+ * (descriptor index, 4096-element chunk index), as for N3.  hdmoe_mt_ema advances *step_counter (device int64) to t and then writes, for
+ * every element and every profile k < nprofiles (1..4), e_k += a_k * (p - e_k) with one fma.  HDMOE_EMA_POWER: gammas_or_betas = gamma_k
+ * (device doubles), a_k = 1 - (1 - 1/t)^(gamma_k + 1) evaluated in fp64 on the device, a_k = 1 at t = 1 (e_k = p bit for bit).
+ * HDMOE_EMA_CONSTANT: gammas_or_betas = beta_k, a_k = 1 - beta_k for every t.  No host value changes between steps, so one captured
+ * launch serves every step; no atomics, bit-identical from run to run.  hdmoe_mt_swap exchanges p <-> e_profile in place (twice = identity).
+ * nchunks == 0: nothing is launched, the counter stays. */
+#define HDMOE_EMA_POWER 0
+#define HDMOE_EMA_CONSTANT 1
+int hdmoe_ema_desc_bytes(void);
+int hdmoe_mt_ema(const void* descs, const int* chunks, int nchunks, int nprofiles, long long* step_counter, const double* gammas_or_betas,
+                 int mode, HS stream);
+int hdmoe_mt_swap(const void* descs, const int* chunks, int nchunks, int profile, HS stream);
+
 #undef HS
 #ifdef __cplusplus
 }
