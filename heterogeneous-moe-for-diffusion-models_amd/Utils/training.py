@@ -85,7 +85,15 @@ class Trainer:
     generation, fused loss, flat-bucket gradient all-reduce, fused clip + AdamW)."""
 
     def __init__(self, model, model_config, optim_config, loss_config, mask_config, zeta_config, max_grad_norm: float = 1.0,
-                 fuse_clip_into_step: bool = True, logger=None, ema=None):
+                 fuse_clip_into_step: bool = True, logger=None, ema=None, ema_snapshot_every: Optional[int] = None,
+                 ema_snapshot_dir: Optional[str] = None):
+        if ema_snapshot_every is not None:
+            if ema is None:
+                raise ValueError("Trainer: ema_snapshot_every needs an ema")
+            if ema_snapshot_dir is None:
+                raise ValueError("Trainer: ema_snapshot_every needs ema_snapshot_dir")
+            if int(ema_snapshot_every) < 1:
+                raise ValueError(f"Trainer: ema_snapshot_every must be >= 1, got {ema_snapshot_every}")
         self.model, self.cfg, self.mask_cfg = model, model_config, mask_config
         self.optimizer = build_optimizer(model, optim_config)
         self.scheduler = build_scheduler(self.optimizer, optim_config)
@@ -104,6 +112,9 @@ class Trainer:
         self.max_grad_norm, self.fuse = float(max_grad_norm), fuse_clip_into_step
         self.logger = logger                                 # graphs.logger.Logger (sync-free) or None
         self.ema = ema                                       # hdmoe_hip.ema.WeightEMA or None: averaged right after every optimizer step
+        # every `ema_snapshot_every` steps the averages go to <ema_snapshot_dir>/ema_<step>.pt: sources of hdmoe_hip.posthoc.reconstruct
+        self.ema_snapshot_every = None if ema_snapshot_every is None else int(ema_snapshot_every)
+        self.ema_snapshot_dir = ema_snapshot_dir
         self._clip_params = [p for p in model.parameters()]
         self.step_idx = 0
 
@@ -139,9 +150,18 @@ class Trainer:
             self.optimizer.step()
         if self.ema is not None:
             self.ema.update()
+            if self.ema_snapshot_every is not None and (step + 1) % self.ema_snapshot_every == 0:
+                self._save_ema_snapshot(step + 1)
         self.scheduler.step()
         self.step_idx += 1
         return {"loss": loss, "out_model": out_model, "sigma": sigma}
+
+    def _save_ema_snapshot(self, step: int) -> None:
+        """A host copy of every average (it syncs).  The averages are bit-identical across data-parallel ranks: rank 0 writes."""
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_rank() != 0:
+            return
+        os.makedirs(self.ema_snapshot_dir, exist_ok=True)
+        self.ema.save_snapshot(os.path.join(self.ema_snapshot_dir, f"ema_{step:08d}.pt"))
 
 
 def train_steps(trainer: Trainer, batches: Iterable, on_step: Optional[Callable[[int, dict], None]] = None) -> None:

@@ -2,6 +2,7 @@
 // exchange parameters <-> one profile.  One launch walks every tracked tensor through a (tensor, chunk) table shaped like the optimizer's
 // (optim.hip): 4096-element chunks, 256 threads.  Pure streaming: p is read once, every e_k is read and written once, (1 + 2K) * 4 bytes
 // per parameter.  Nothing is reduced and nothing is atomic, so the result is bit-identical from run to run and across data-parallel ranks.
+// Below them: the post-hoc combination of saved averages into averages of other profiles (hdmoe_mt_combine).
 #include "common.h"
 #include "hdmoe.h"
 
@@ -122,9 +123,107 @@ __global__ __launch_bounds__(256) void mt_swap_kernel(const EmaDesc* descs, cons
   }
 }
 
+// Post-hoc reconstruction: dst_t = sum_s w[s][t] src_s over nsrc saved averages, K targets per launch.  A block owns 1024 consecutive
+// elements (one float4 per lane) and walks the sources once for all K targets: (nsrc + K) * 4 bytes per element.  Every lane keeps its own
+// fp64 fma chains in source order, so the result depends neither on the launch geometry nor on K nor on the access width.  The weights and
+// the table are read-only and indexed by the loop counter alone: uniform (scalar-unit) loads, no per-lane traffic.
+constexpr int CMB_MAX_DST = 8;
+constexpr int CMB_MAX_SRC = 4096;
+constexpr int CMB_BLOCK = 1024;                    // elements per block
+constexpr int CMB_UNROLL = 4;                      // sources whose loads are issued before the first fma consumes one
+
+template <int K, int W>                            // W floats per access: 4 (float4) or 1
+DEVI void combine_span(const unsigned long long* __restrict__ src, const unsigned long long* da, int nsrc, const double* __restrict__ w,
+                       long off) {
+  typedef float vecW __attribute__((ext_vector_type(W)));
+  typedef __attribute__((address_space(1))) vecW gvecW;                        // global, not flat: the table holds plain integers
+  typedef __attribute__((address_space(1))) float gfloat;
+  double acc[K][W];
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+#pragma unroll
+    for (int c = 0; c < W; ++c) acc[k][c] = 0.0;
+  int s = 0;
+  for (; s + CMB_UNROLL <= nsrc; s += CMB_UNROLL) {
+    vecW x[CMB_UNROLL];
+#pragma unroll
+    for (int u = 0; u < CMB_UNROLL; ++u) x[u] = *(const gvecW*)((const gfloat*)src[s + u] + off);
+#pragma unroll
+    for (int u = 0; u < CMB_UNROLL; ++u)
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const double wk = w[(long)(s + u) * K + k];
+#pragma unroll
+        for (int c = 0; c < W; ++c) acc[k][c] = fma(wk, (double)x[u][c], acc[k][c]);
+      }
+  }
+  for (; s < nsrc; ++s) {
+    const vecW x = *(const gvecW*)((const gfloat*)src[s] + off);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const double wk = w[(long)s * K + k];
+#pragma unroll
+      for (int c = 0; c < W; ++c) acc[k][c] = fma(wk, (double)x[c], acc[k][c]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    vecW y;
+#pragma unroll
+    for (int c = 0; c < W; ++c) y[c] = (float)acc[k][c];
+    *(gvecW*)((gfloat*)da[k] + off) = y;
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void mt_combine_kernel(const unsigned long long* __restrict__ src, const unsigned long long* __restrict__ dst,
+                                                         int nsrc, long numel, const double* __restrict__ w) {
+  unsigned long long al = 0;                       // every block looks at the whole table: nsrc * 8 bytes from L2 next to nsrc * 4 KiB of data
+  for (int s = threadIdx.x; s < nsrc; s += 256) al |= src[s];
+  unsigned long long da[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) { da[k] = dst[k]; al |= da[k]; }
+  const bool vec = !__syncthreads_or((int)(al & 15));
+  const long i0 = (long)blockIdx.x * CMB_BLOCK;
+  const long i1 = i0 + CMB_BLOCK < numel ? i0 + CMB_BLOCK : numel;
+  long is = i0;                                    // first element left to the scalar loop
+  if (vec) {
+    const int n4 = (int)((i1 - i0) >> 2);
+    if ((int)threadIdx.x < n4) combine_span<K, 4>(src, da, nsrc, w, i0 + 4L * threadIdx.x);
+    is = i0 + 4L * n4;                             // up to 3 tail elements of the last block
+  }
+  for (long i = is + threadIdx.x; i < i1; i += 256) combine_span<K, 1>(src, da, nsrc, w, i);
+}
+
+template <int K>
+void launch_combine(const void* src, const void* dst, int nsrc, long numel, const double* w, hipStream_t stream) {
+  const long blocks = (numel + CMB_BLOCK - 1) / CMB_BLOCK;
+  hipLaunchKernelGGL(mt_combine_kernel<K>, dim3((unsigned)blocks), dim3(256), 0, stream, (const unsigned long long*)src,
+                     (const unsigned long long*)dst, nsrc, numel, w);
+}
+
 }  // namespace
 
 extern "C" {
+
+int hdmoe_mt_combine(const void* src_table, const void* dst_table, int nsrc, int ndst, long numel, const double* weights,
+                     hipStream_t stream) {
+  if (nsrc < 1 || nsrc > CMB_MAX_SRC || ndst < 1 || ndst > CMB_MAX_DST || numel < 0) return HDMOE_EINVAL;
+  if (numel > (long)CMB_BLOCK * 0x7fffffffL) return HDMOE_EINVAL;              // the grid's x dimension
+  if (numel == 0) return HDMOE_OK;
+  if (!src_table || !dst_table || !weights) return HDMOE_EINVAL;
+  switch (ndst) {
+    case 1: launch_combine<1>(src_table, dst_table, nsrc, numel, weights, stream); break;
+    case 2: launch_combine<2>(src_table, dst_table, nsrc, numel, weights, stream); break;
+    case 3: launch_combine<3>(src_table, dst_table, nsrc, numel, weights, stream); break;
+    case 4: launch_combine<4>(src_table, dst_table, nsrc, numel, weights, stream); break;
+    case 5: launch_combine<5>(src_table, dst_table, nsrc, numel, weights, stream); break;
+    case 6: launch_combine<6>(src_table, dst_table, nsrc, numel, weights, stream); break;
+    case 7: launch_combine<7>(src_table, dst_table, nsrc, numel, weights, stream); break;
+    default: launch_combine<8>(src_table, dst_table, nsrc, numel, weights, stream); break;
+  }
+  return hdmoe_launch_status();
+}
 
 int hdmoe_ema_desc_bytes(void) { return (int)sizeof(EmaDesc); }
 

@@ -13,6 +13,8 @@ from ._lib import LIB_PATH, lib                            # noqa: F401
 from .ops import manual_seed                               # noqa: F401
 from .bank import invalidate_weights                       # noqa: F401
 from .ema import WeightEMA                                 # noqa: F401
+from . import posthoc                                      # noqa: F401
+from .posthoc import ReconstructedEMA                      # noqa: F401
 
 _policy = {"compute_dtype": torch.float32}
 

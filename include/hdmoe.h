@@ -451,6 +451,14 @@ int hdmoe_ema_desc_bytes(void);
 int hdmoe_mt_ema(const void* descs, const int* chunks, int nchunks, int nprofiles, long long* step_counter, const double* gammas_or_betas,
                  int mode, HS stream);
 int hdmoe_mt_swap(const void* descs, const int* chunks, int nchunks, int profile, HS stream);
+/* Post-hoc reconstruction (EDM2 section 3.2): nsrc saved averages -> ndst new ones in one pass.  src_table / dst_table: device arrays of
+ * nsrc (1..4096) / ndst (1..8) 64-bit device addresses of flat fp32 buffers of numel elements each; weights: device doubles [nsrc][ndst],
+ * source-major.  dst_t[i] = (float) sum_s weights[s][t] * (double) src_s[i]: one fp64 fma chain per element and target in source order
+ * 0..nsrc-1, rounded to fp32 once at the store.  No atomics and no reduction across threads: bit-identical from run to run, and a target's
+ * result does not depend on which other targets share its launch.  Every source is read once for all targets and every target is
+ * written once, (nsrc + ndst) * 4 * numel bytes.  16-byte accesses when every table entry is 16-byte aligned, 4-byte ones otherwise.
+ * numel == 0: nothing is launched. */
+int hdmoe_mt_combine(const void* src_table, const void* dst_table, int nsrc, int ndst, long numel, const double* weights, HS stream);
 
 #undef HS
 #ifdef __cplusplus
