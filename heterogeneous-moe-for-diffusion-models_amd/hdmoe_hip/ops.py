@@ -780,6 +780,12 @@ def multi_linear(x: Tensor, layers, gain: float, *, seg: Optional[Tensor] = None
 
 
 
+def _call_or(fast: str, plain: str, *args) -> None:
+    """Run the entry point `fast`; where it declines the shape (return code 1: nothing launched), run `plain`, the kernel it replaces."""
+    if call(fast, *args) == 1:
+        call(plain, *args)
+
+
 class _PatchLinearFn(torch.autograd.Function):
     """Vit_expert.patch when the image divides into patches (model_components.py:670-679): a stride-p p x p conv is a linear layer on
     the patch vectors, so: one relayout pass (image -> tokens of C*p*p features in the weight's own (c, i, j) order, the parameter
@@ -795,7 +801,7 @@ class _PatchLinearFn(torch.autograd.Function):
         hp, wp, K = H // p, W // p, C * p * p
         Epad = (E + 15) // 16 * 16
         tok = torch.empty((N, hp, wp, K), dtype=x.dtype, device=x.device)
-        call("hdmoe_patch_relayout", tok, x, N, H, W, C, p, hp, wp, 1, 0, _dt(x))
+        _call_or("hdmoe_patch_relayout_tiled", "hdmoe_patch_relayout", tok, x, N, H, W, C, p, hp, wp, 1, 0, _dt(x))
         wf = torch.empty(E * K, dtype=x.dtype, device=x.device)
         wd = torch.empty(K * Epad, dtype=x.dtype, device=x.device) if ctx.needs_input_grad[0] else None
         call("hdmoe_wprep_fwd", [w], None, 1.0, [1], [1], 1, E, K, K, Epad, wf, wf.numel(), wd, 0 if wd is None else wd.numel(), 0, 0, 0, _dt(x))
@@ -819,7 +825,7 @@ class _PatchLinearFn(torch.autograd.Function):
             dtok = torch.empty((N, hp, wp, K), dtype=dy.dtype, device=dy.device)
             call("hdmoe_conv_fwd", dy, ctx.wd, dtok, None, 1.0, 0.0, None, 1, ctx.wd.numel(), N, hp, wp, hp, wp, E, E, Epad, K, K, 1, 0, [1], [1], [0], [0], dt)
             dx = torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device)
-            call("hdmoe_patch_relayout", dx, dtok, N, H, W, C, p, hp, wp, 1, 1, dt)
+            _call_or("hdmoe_patch_relayout_tiled", "hdmoe_patch_relayout", dx, dtok, N, H, W, C, p, hp, wp, 1, 1, dt)
         if ctx.needs_input_grad[1]:
             Gs = [_zeros((1, E, K), torch.float32, dy.device)]
             call("hdmoe_conv_wgrad", tok, dy, Gs, None, 1, N, hp, wp, hp, wp, K, K, E, 1, 0, [1], [1], [0], [0], dt)
@@ -1851,7 +1857,7 @@ class _PatchRelayoutFn(torch.autograd.Function):
         N, H, W, C, p, hp, wp, order = meta
         tok = _c(tok)
         out = torch.empty((N, H, W, C), dtype=tok.dtype, device=tok.device)
-        call("hdmoe_patch_relayout", out, tok, N, H, W, C, p, hp, wp, order, 1, _dt(tok))
+        _call_or("hdmoe_patch_relayout_tiled", "hdmoe_patch_relayout", out, tok, N, H, W, C, p, hp, wp, order, 1, _dt(tok))
         ctx.meta = meta
         ctx.tshape = tok.shape
         return out
@@ -1863,7 +1869,7 @@ class _PatchRelayoutFn(torch.autograd.Function):
         # tokens cover the padded hp*p x wp*p canvas; positions outside H x W receive no gradient
         dtok = torch.zeros(ctx.tshape, dtype=g.dtype, device=g.device) if (hp * p != H or wp * p != W) else \
             torch.empty(ctx.tshape, dtype=g.dtype, device=g.device)
-        call("hdmoe_patch_relayout", dtok, g, N, H, W, C, p, hp, wp, order, 0, _dt(g))
+        _call_or("hdmoe_patch_relayout_tiled", "hdmoe_patch_relayout", dtok, g, N, H, W, C, p, hp, wp, order, 0, _dt(g))
         return dtok, None
 
 
@@ -2502,7 +2508,7 @@ class _GatherFn(torch.autograd.Function):
         g = _c(g)
         L = g.numel() // plan.R
         dx = torch.empty(ctx.xshape, dtype=g.dtype, device=g.device)
-        call("hdmoe_combine_rows_fwd", dx, g, plan.inv, None, plan.B, plan.kcap, L, _dt(g))
+        _call_or("hdmoe_combine_rows_fwd_vec", "hdmoe_combine_rows_fwd", dx, g, plan.inv, None, plan.B, plan.kcap, L, _dt(g))
         return dx, None
 
 
@@ -2530,7 +2536,7 @@ class _CombineFn(torch.autograd.Function):
         ys = _c(ys)
         L = ys.numel() // plan.R
         out = torch.empty((plan.B, *ys.shape[1:]), dtype=ys.dtype, device=ys.device)
-        call("hdmoe_combine_rows_fwd", out, ys, plan.inv, plan.row_w, plan.B, plan.kcap, L, _dt(ys))
+        _call_or("hdmoe_combine_rows_fwd_vec", "hdmoe_combine_rows_fwd", out, ys, plan.inv, plan.row_w, plan.B, plan.kcap, L, _dt(ys))
         ctx.save_for_backward(ys)
         ctx.plan = plan
         return out
@@ -2543,7 +2549,8 @@ class _CombineFn(torch.autograd.Function):
         L = ys.numel() // plan.R
         dys = torch.empty_like(ys)
         dsp = _zeros((plan.B, plan.E), torch.float32, g.device, ctx.pool_ok) if ctx.needs_input_grad[1] else None
-        call("hdmoe_combine_rows_bwd", dys, dsp, g, ys, plan.perm, plan.row_expert, plan.row_w, plan.R, plan.E, L, _dt(ys))
+        _call_or("hdmoe_combine_rows_bwd_vec", "hdmoe_combine_rows_bwd", dys, dsp, g, ys, plan.perm, plan.row_expert, plan.row_w,
+                 plan.R, plan.E, L, _dt(ys))
         return dys, dsp, None
 
 

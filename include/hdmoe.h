@@ -144,7 +144,10 @@ enum {
   HDMOE_SEL_WGRAD8_C21 = 16,     /*   2 x 1 */
   HDMOE_SEL_WGRAD8_C22 = 17,     /*   2 x 2 */
   HDMOE_SEL_PW_BWD = 18,         /* hdmoe_pw_bwd: pointwise layer, input + weight gradient in one launch */
-  HDMOE_SEL_COUNT = 19
+  HDMOE_SEL_RELAYOUT_TILED = 19,   /* hdmoe_patch_relayout_tiled: order-1 patch <-> image relayout, tiled through LDS */
+  HDMOE_SEL_COMBINE_FWD_VEC = 20,  /* hdmoe_combine_rows_fwd_vec: 16-byte combine forward (also the gather's backward) */
+  HDMOE_SEL_COMBINE_BWD_VEC = 21,  /* hdmoe_combine_rows_bwd_vec: 16-byte combine backward */
+  HDMOE_SEL_COUNT = 22
 };
 int hdmoe_kernel_selections(long long* counts, int n, int reset);
 
@@ -258,6 +261,11 @@ int hdmoe_nhwc_to_nchw_guided(float* out, const void* F, const float* sf, const 
                               int C, long HW, int dtype, HS stream);
 int hdmoe_patch_relayout(void* out, const void* in, int N, int H, int W, int C, int p, int hp, int wp, int order,
                          int to_img, int dtype, HS stream);                                                      /* PixelShuffle / patchify */
+/* The same bytes for order 1 (PixelShuffle) by a tiled transpose through LDS, 16-byte accesses on both sides (csrc/relayout.hip).
+ * Returns 1 and launches nothing outside its domain -- order 0, p or C not a multiple of the 16-byte vector width (8 bf16 / 4 fp32),
+ * a token above 32 KiB, p > 64, unaligned pointers: the caller then runs hdmoe_patch_relayout. */
+int hdmoe_patch_relayout_tiled(void* out, const void* in, int N, int H, int W, int C, int p, int hp, int wp, int order,
+                               int to_img, int dtype, HS stream);
 int hdmoe_fourier(float* out, const float* x, const float* freqs, const float* phases, int B, int F, HS stream); /* model_internals.py:171-174 */
 int hdmoe_edm_coeffs(float* coef, const float* sigma, int nsig, float sigma_data, int B, HS stream);             /* model_config2.py:431-438 */
 int hdmoe_sigmoid_scaling(float* sv, float* su, float* pair, const float* c_noise, float tp, float soft, int B, HS stream); /* :244-249 */
@@ -393,6 +401,13 @@ int hdmoe_combine_rows_fwd(void* out, const void* ys, const int* inv, const floa
                            int dtype, HS stream);
 int hdmoe_combine_rows_bwd(void* dys, float* dsparse, const void* dout, const void* ys, const int* perm,
                            const int* row_expert, const float* row_w, long R, int E, long L, int dtype, HS stream);
+/* 16-byte forms (csrc/relayout.hip): one workgroup per (row, chunk), row decoded and inv / perm / row_w read once per workgroup.  out and
+ * dys are bit-identical to the scalar forms; dsparse sums its per-chunk dot product in another tree.  Return 1 and launch nothing
+ * when L is not a multiple of 8 (bf16) / 4 (fp32) or a pointer is not 16-byte aligned: the caller then runs the scalar form. */
+int hdmoe_combine_rows_fwd_vec(void* out, const void* ys, const int* inv, const float* row_w, long B, int kcap, long L,
+                               int dtype, HS stream);
+int hdmoe_combine_rows_bwd_vec(void* dys, float* dsparse, const void* dout, const void* ys, const int* perm,
+                               const int* row_expert, const float* row_w, long R, int E, long L, int dtype, HS stream);
 
 /* ---- N2 (next to the path): EDM_LOSS fused  (Utils/utils.py:127-172) ---------------------------------------------- */
 /* out[5] = loss, denoising, balance, z_loss, pure_loss; aux: 2E+3 floats kept for the backward; sse: B floats scratch */
