@@ -41,18 +41,16 @@ int blk6_plan(const void* x, const void* wa, const void* wb, void* y, const void
     if (ks[g] != 3 && ks[g] != 5 && ks[g] != 7) return 1;
     if (ks[g] > maxk) maxk = ks[g];
   }
-  if (((uintptr_t)x | (uintptr_t)wa | (uintptr_t)wb | (uintptr_t)y | (uintptr_t)res) & 15) return 1;
   const long taps = (long)maxk * maxk;
   const long xbytes = (long)N * H * W * Ca * 2;
   const long wabytes = ((long)(ngroups - 1) * wa_stride + taps * Cm * Ca) * 2, wbbytes = ((long)(ngroups - 1) * wb_stride + taps * Cb * Cm) * 2;
-  if (xbytes >= (1l << 31) || wabytes >= (1l << 31) || wbbytes >= (1l << 31) || (long)N * H * W * (Cb > Cm ? Cb : Cm) >= (1l << 31)) return 1;
+  if (!conv_align_extent_ok({x, wa, wb, y, res}, {xbytes, wabytes, wbbytes, (long)N * H * W * (Cb > Cm ? Cb : Cm)})) return 1;
   B6Args& a = plan.a;
   a.x = x; a.wa = wa; a.wb = wb; a.y = y; a.res = res; a.seg = seg; a.wa_stride = wa_stride; a.wb_stride = wb_stride;
   a.N = N; a.H = H; a.W = W; a.Ca = Ca; a.Cm = Cm; a.Cb = Cb; a.ngroups = ngroups;
   a.xbytes = (int)xbytes; a.wabytes = (int)wabytes; a.wbbytes = (int)wbbytes;
-  for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) { a.ks[g] = g < ngroups ? ks[g] : ks[0]; a.order[g] = g; }
-  for (int i = 1; i < ngroups; ++i)
-    for (int k = i; k > 0 && a.ks[a.order[k]] > a.ks[a.order[k - 1]]; --k) { const int t = a.order[k]; a.order[k] = a.order[k - 1]; a.order[k - 1] = t; }
+  for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) { a.ks[g] = g < ngroups ? ks[g] : ks[0]; }
+  conv_sort_groups_desc(a.ks, a.order, ngroups);
   const int NTM = Cm / 32, NTB = Cb % 64 == 0 ? 2 : 1;
   const int nbmax = 32 * (NTM > NTB ? NTM : NTB);
   // Geometry candidates, best first: 4-wave workgroups, two per CU (<= 80 KB of LDS each, one x buffer, conv A over <= 12 blocks), on
@@ -73,13 +71,7 @@ int blk6_plan(const void* x, const void* wa, const void* wb, void* y, const void
     const int hbp = (((th + maxk - 1) * (W + maxk - 1) * 64) + 1023) / 1024 * 1024;
     const int cap = cd.nw == 4 ? 80 * 1024 : 160 * 1024;
     const int fixed = (cd.nw == 4 ? 1 : 2) * xb + NTM * hbp + B6_EB;
-    int best = 0, best_stages = 1 << 30;
-    for (int t = 9; t >= 2; --t) {
-      if (t * (nbmax / 16) > 40 || fixed + 2 * t * nbmax * 64 > cap) continue;
-      int stages = 0;
-      for (int g = 0; g < ngroups; ++g) stages += (ks[g] * ks[g] + t - 1) / t;
-      if (stages <= best_stages) { best_stages = stages; best = t; }
-    }
+    const int best = conv_pick_stage_T(ngroups, ks, nbmax / 16, fixed, nbmax * 64, cap);
     if (!best) continue;
     a.TH = th; a.tpi = H / th; a.xb_bytes = xb; a.hb_plane = hbp; a.T = best; a.wb_bytes = best * nbmax * 64; a.nxp = xb / 1024 / cd.nw;
     plan.NW = cd.nw;
@@ -88,8 +80,7 @@ int blk6_plan(const void* x, const void* wa, const void* wb, void* y, const void
     break;
   }
   if (!found) return 1;
-  auto recip = [](int d) { return d == 1 ? 0xFFFFFFFFu : (unsigned)((1ull << 32) / (unsigned)d + 1); };
-  a.m_tpi = recip(a.tpi); a.m_T = recip(a.T);
+  a.m_tpi = conv_recip(a.tpi); a.m_T = conv_recip(a.T);
   const long units = (long)N * a.tpi;
   const long gcap = plan.NW == 4 ? 512 : 256;
   plan.G = (unsigned)(units < gcap ? units : gcap);
@@ -106,14 +97,11 @@ int blk6_launch(const B6Plan& plan, hipStream_t stream) {
     B6_ATTR(8, 1, 1, 160); B6_ATTR(8, 1, 2, 160); B6_ATTR(8, 2, 1, 160); B6_ATTR(8, 2, 2, 160);
     B6_ATTR(4, 1, 1, 80); B6_ATTR(4, 1, 2, 80); B6_ATTR(4, 2, 1, 80); B6_ATTR(4, 2, 2, 80);
   }
-#define B6_LAUNCH(W, M, B) hipLaunchKernelGGL((blk6_kernel<W, M, B>), dim3(plan.G), dim3(64 * W), plan.lds, stream, plan.a)
-#define B6_GO(W)                                                                                  \
-  do {                                                                                            \
-    if (plan.NTM == 2) { if (plan.NTB == 2) B6_LAUNCH(W, 2, 2); else B6_LAUNCH(W, 2, 1); }       \
-    else { if (plan.NTB == 2) B6_LAUNCH(W, 1, 2); else B6_LAUNCH(W, 1, 1); }                     \
-  } while (0)
   hdmoe_count_selection(HDMOE_SEL_BLK6);
-  if (plan.NW == 4) B6_GO(4); else B6_GO(8);
+  conv_pick<4, 8>(plan.NW, [&](auto Nw) { conv_pick<2, 1>(plan.NTM, [&](auto Ntm) { conv_pick<2, 1>(plan.NTB, [&](auto Ntb) {
+    constexpr int NW = decltype(Nw)::value;
+    hipLaunchKernelGGL((blk6_kernel<NW, decltype(Ntm)::value, decltype(Ntb)::value>), dim3(plan.G), dim3(64 * NW), plan.lds, stream, plan.a);
+  }); }); });
   return hdmoe_launch_status();
 }
 

@@ -58,8 +58,7 @@ DEVI void blk6_body(const B6Args& a, const int bid, const int G) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
-  const int csl = ((lane & 3) ^ ((lane >> 4) & 3)) << 4;
-  const int prow = lane >> 2;
+  const int csl = c6_dma_csl(lane), prow = c6_dma_prow(lane);
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.x), 0, a.xbytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rwa = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.wa), 0, a.wabytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rwb = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.wb), 0, a.wbbytes, 0x00020000);
@@ -76,7 +75,7 @@ DEVI void blk6_body(const B6Args& a, const int bid, const int G) {
     }
   };
   stamp(1);
-  // ---- unit list (as conv6_body.h): groups in descending kernel size; a unit = one TH x W tile of one routed row
+  // ---- unit list (as conv6_body.h, written out for the same reason); a unit = one TH x W tile of one routed row
   const int oi_l = lane & 7;
   int v_g = 0, v_ks = 0;
 #pragma unroll
@@ -95,25 +94,18 @@ DEVI void blk6_body(const B6Args& a, const int bid, const int G) {
   }
   const int total = __builtin_amdgcn_readlane(v_ustart, 7);
   v_ustart -= v_units;
-  auto udiv = [](int x, unsigned magic, int d) {
-    int q = (int)(((unsigned long long)(unsigned)x * magic) >> 32);
-    if (q * d > x) --q;
-    if ((q + 1) * d <= x) ++q;
-    return q;
-  };
   auto decode = [&](int j, B6Unit& u) {
-    const unsigned long long hit = __ballot(lane < 8 && j >= v_ustart && j < v_ustart + v_units);
-    const int slot = (int)__builtin_ctzll(hit | (1ull << 7));
+    const int slot = c6_slot_of(j, v_ustart, v_units, lane);
     const int uu = j - __builtin_amdgcn_readlane(v_ustart, slot);
     const int row0 = __builtin_amdgcn_readlane(v_row0, slot);
     u.rend = row0 + __builtin_amdgcn_readlane(v_rows, slot);
     u.g = __builtin_amdgcn_readlane(v_g, slot); u.ks = __builtin_amdgcn_readlane(v_ks, slot);
-    const int img = udiv(uu, a.m_tpi, a.tpi);
+    const int img = c6_udiv(uu, a.m_tpi, a.tpi);
     u.n = row0 + img; u.ty0 = (uu - img * a.tpi) * a.TH;
   };
   auto geo_of = [&](int ks) {
     B6Geo q;
-    q.pd = (ks - 1) >> 1; q.ntaps = ks * ks; q.ntg = udiv(q.ntaps + a.T - 1, a.m_T, a.T);
+    q.pd = (ks - 1) >> 1; q.ntaps = ks * ks; q.ntg = c6_udiv(q.ntaps + a.T - 1, a.m_T, a.T);
     q.WXp = a.W + ks - 1; q.HX = a.TH + 2 * (ks - 1); q.HM = a.TH + ks - 1;
     q.ppt = (q.WXp * q.HX + 15) >> 4;
     q.nblkA = (q.HM * a.W) >> 5;
@@ -127,10 +119,7 @@ DEVI void blk6_body(const B6Args& a, const int bid, const int G) {
     const int WXp = a.W + u.ks - 1, HX = a.TH + 2 * (u.ks - 1), ppt = (WXp * HX + 15) >> 4;
     const int pi = wave + NW * k;
     const int px = 16 * pi + prow;
-    const int magic = (1 << 20) / WXp + 1;
-    int hy = (int)(((unsigned)px * (unsigned)magic) >> 20);
-    if (hy * WXp > px) --hy;
-    const int hx = px - hy * WXp;
+    const int hy = c6_halo_row(px, c6_halo_magic(WXp), WXp), hx = px - hy * WXp;
     const int pd = (u.ks - 1) >> 1;
     const int iy = u.ty0 - 2 * pd + hy, ix = hx - pd;
     const bool ok = pi < ppt && px < WXp * HX && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
@@ -145,7 +134,7 @@ DEVI void blk6_body(const B6Args& a, const int bid, const int G) {
   const int wkA = (NW / PPTA) * a.Cm * a.Ca * 2;
   const unsigned wloB = (unsigned)((((wave / PPTB) * a.Cb + (wave % PPTB) * 16 + prow) * a.Cm) * 2 + csl);
   const int wkB = (NW / PPTB) * a.Cb * a.Cm * 2;
-  auto wpieces = [&](int ntl, int ppt) { const int per = NW / ppt; return max(0, (ntl - wave / ppt + per - 1) / per); };
+  auto wpieces = [&](int ntl, int ppt) { const int per = NW / ppt; return max(0, (ntl - wave / ppt + per - 1) / per); };   // (c6_wpieces with a run-time piece count: as the template it changes this kernel's code)
   auto baseA = [&](const B6Unit& u, int c, int t0) { return (int)(((long)u.g * a.wa_stride + (long)t0 * a.Cm * a.Ca + c * 32) * 2); };
   auto baseB = [&](const B6Unit& u, int nb, int c, int t0) {
     return (int)(((long)u.g * a.wb_stride + ((long)t0 * a.Cb + nb * NBB) * a.Cm + c * 32) * 2);
@@ -188,7 +177,7 @@ DEVI void blk6_body(const B6Args& a, const int bid, const int G) {
   const int XB0 = 0, HB0 = (XS ? 1 : 2) * a.xb_bytes, WB0 = HB0 + NTM * a.hb_plane, EB0 = WB0 + 2 * a.wb_bytes;     // EB: this unit's FiLM vector e[n][0 .. Cm)
   const int nchA = a.Ca >> 5;
   const int nblkB = a.Cb / NBB;
-  const int wl = r * 64 + ((h << 4) ^ (((r >> 2) & 3) << 4));
+  const int wl = c6_wfrag_off(r, h);
   const int tws = a.W == 32 ? 5 : 4;
   const int nblkT = (a.TH * a.W) >> 5;                          // 32-pixel blocks of the output tile (8, or 4)
 
@@ -338,7 +327,7 @@ DEVI void blk6_body(const B6Args& a, const int bid, const int G) {
         // Units are dealt round robin (j, j + G, ...): with G a multiple of the tiles per image the successor is the SAME tile of row
         // n + G / tpi -- same expert, kernel size and padding pattern unless that row belongs to the next expert: no decode, the DMA
         // source offsets just move by whole images.
-        const int dn = udiv(G, a.m_tpi, a.tpi);
+        const int dn = c6_udiv(G, a.m_tpi, a.tpi);
         if (dn * a.tpi == G && cur.n + dn < cur.rend) {
           nu = cur; nu.n = cur.n + dn;
           const unsigned step_b = (unsigned)(dn * a.H * a.W * ca2);
@@ -416,13 +405,9 @@ DEVI void blk6_body(const B6Args& a, const int bid, const int G) {
               float v[8];
 #pragma unroll
               for (int q = 0; q < 8; ++q) v[q] = a.alpha_mid * acc[m][b][8 * p + q];
-              const unsigned A0 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[0], (bf16)v[1]}), A1 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[2], (bf16)v[3]});
-              const unsigned B0 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[4], (bf16)v[5]}), B1 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[6], (bf16)v[7]});
-              const u32x2 s0 = __builtin_amdgcn_permlane32_swap(A0, B0, false, false);
-              const u32x2 s1 = __builtin_amdgcn_permlane32_swap(A1, B1, false, false);
               // this lane: channels c0 .. c0 + 7 of pixel (mr, mc), rounded to bf16 (as the unfused conv writes them)
               const int c0 = 32 * b + 16 * p + 8 * h;
-              const unsigned pk[4] = {s0[0], s1[0], s0[1], s1[1]};
+              const C6Words pk = c6_pack_bf16(v);
               unsigned ho[4] = {0u, 0u, 0u, 0u};
               if (inimg) {
                 const long eo = pix + c0;
@@ -433,10 +418,10 @@ DEVI void blk6_body(const B6Args& a, const int bid, const int G) {
                   philox((uint32_t)q0, (uint32_t)(q0 >> 32), seed_lo, seed_hi, r4);
                   philox((uint32_t)(q0 + 1), (uint32_t)((q0 + 1) >> 32), seed_lo, seed_hi, r4 + 4);
                 }
-                if (owned && U && !(a.dbg & 4)) *reinterpret_cast<uint4*>(U + eo) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
+                if (owned && U && !(a.dbg & 4)) *reinterpret_cast<uint4*>(U + eo) = make_uint4(pk.w[0], pk.w[1], pk.w[2], pk.w[3]);
 #pragma unroll
                 for (int j2 = 0; j2 < 4; ++j2) {
-                  const bf2 yv = __builtin_bit_cast(bf2, pk[j2]);
+                  const bf2 yv = __builtin_bit_cast(bf2, pk.w[j2]);
                   float f0 = mp_silu_f((float)yv[0] * ep[2 * j2]);
                   float f1 = mp_silu_f((float)yv[1] * ep[2 * j2 + 1]);
                   if (a.p > 0.f) {
@@ -536,7 +521,7 @@ DEVI void blk6_body(const B6Args& a, const int bid, const int G) {
 #pragma unroll
                   for (int q2 = 0; q2 < 4; ++q2) { v[q2] += a.beta * (float)rq[m][b][p][0][q2]; v[4 + q2] += a.beta * (float)rq[m][b][p][1][q2]; }
                 }
-                typedef __attribute__((ext_vector_type(2))) __bf16 bf2;
+                typedef __attribute__((ext_vector_type(2))) __bf16 bf2;       // (c6_pack_bf16 written out: the call changes this kernel's register allocation)
                 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
                 const unsigned A0 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[0], (bf16)v[1]}), A1 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[2], (bf16)v[3]});
                 const unsigned B0 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[4], (bf16)v[5]}), B1 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[6], (bf16)v[7]});

@@ -112,21 +112,14 @@ int hdmoe_conv_bwd6s(const void* x, const void* dy, const void* wd, void* dx, fl
   if ((in_scale == nullptr) != (in_shift == nullptr) || (in_scale && (ngroups != 1 || seg))) return HDMOE_EINVAL;
   wp.c[0].in_scale = in_scale; wp.c[0].in_shift = in_shift; wp.c[0].in_relu = in_relu;   // the weight gradient sees relu(x * scale + shift)
   wp.c[0].hi_only = hi_only ? 1 : 0;
-  ConvArgs c;
-  c.x = dy; c.w = wd; c.y = dx; c.res = nullptr; c.seg = seg; c.wstride = wd_stride;
-  c.N = N; c.H = H; c.W = W; c.Ho = H; c.Wo = W; c.Cin = Cout; c.Cphys = Cout; c.Ipad = Cout; c.Cout = Cin; c.Cstore = Cin;
-  c.stride = 1; c.ones = 0; c.ngroups = ngroups; c.n0 = 0; c.alpha = alpha; c.beta = 0.f;
-  for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) { c.kh[g] = 3; c.kw[g] = 3; c.pt[g] = 1; c.pl[g] = 1; }
+  const ConvArgs c = conv_dgrad_args(dy, wd, dx, seg, ngroups, wd_stride, N, H, W, Cin, Cout, kh, kw, pt, pl, alpha);   // (3 x 3, pad 1: wgrad6_plan_split)
   C6SPlan cp;
   if (conv6s_plan(c, wd_plane, nullptr, cp)) return 1;
   cp.sa.nprod = hi_only ? 1 : 3;
   hdmoe_count_selection(HDMOE_SEL_BWD6S);
-#define BWD6S_GO(Nt)                                                                             \
-  do {                                                                                           \
-    if (wp.TWS == 5) { if (wp.OT == 2) launch_bwd6s<Nt, 5, 2>(cp, wp, stream); else launch_bwd6s<Nt, 5, 1>(cp, wp, stream); } \
-    else { if (wp.OT == 2) launch_bwd6s<Nt, 4, 2>(cp, wp, stream); else launch_bwd6s<Nt, 4, 1>(cp, wp, stream); }            \
-  } while (0)
-  if (cp.NT == 2) BWD6S_GO(2); else BWD6S_GO(1);
+  conv_pick<2, 1>(cp.NT, [&](auto Nt) { conv_pick<5, 4>(wp.TWS, [&](auto Tws) { conv_pick<2, 1>(wp.OT, [&](auto Ot) {
+    launch_bwd6s<decltype(Nt)::value, decltype(Tws)::value, decltype(Ot)::value>(cp, wp, stream);
+  }); }); });
   return hdmoe_launch_status();
 }
 
@@ -139,22 +132,10 @@ int hdmoe_conv_bwd6(const void* x, const void* dy, const void* wd, void* dx, flo
   if (dtype != HDMOE_BF16 || !dx || !wd || ngroups < 1 || ngroups > HDMOE_MAX_GROUPS || Cout % 16) return 1;
   W6DualPlan wp;
   if (wgrad6_plan_dual(x, dy, G, seg, ngroups, N, H, W, Cin, Cout, kh, kw, pt, pl, ws, ws_bytes, dtype, wp)) return 1;
-  ConvArgs c;                                              // the dgrad as a forward conv over dy
-  c.x = dy; c.w = wd; c.y = dx; c.res = nullptr; c.seg = seg; c.wstride = wd_stride;
-  c.N = N; c.H = H; c.W = W; c.Ho = H; c.Wo = W; c.Cin = Cout; c.Cphys = Cout; c.Ipad = Cout; c.Cout = Cin; c.Cstore = Cin;
-  c.stride = 1; c.ones = 0; c.ngroups = ngroups; c.n0 = 0; c.alpha = alpha; c.beta = 0.f;
-  for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) {
-    const int s = g < ngroups ? g : 0;
-    c.kh[g] = kh[s]; c.kw[g] = kw[s]; c.pt[g] = kh[s] - 1 - pt[s]; c.pl[g] = kw[s] - 1 - pl[s];
-  }
+  const ConvArgs c = conv_dgrad_args(dy, wd, dx, seg, ngroups, wd_stride, N, H, W, Cin, Cout, kh, kw, pt, pl, alpha);
   {
     C7Plan cp7;                                            // 32 x 32 maps: the streaming kernel as the dgrad program (wgrad6 handles 3x3 / 5x5 only)
     if (!conv7_plan(c, dtype, cp7) && cp7.kmask == 3 && (cp7.w16 != 0) == (wp.TWS == 4)) {
-#define BWD7_GO(Co)                                                                              \
-  do {                                                                                           \
-    if (wp.TWS == 5) launch_bwd7<Co, 3, 5, 0>(cp7, wp, stream);                                                               \
-    else { if (wp.OT == 2) launch_bwd7<Co, 3, 4, 2>(cp7, wp, stream); else launch_bwd7<Co, 3, 4, 1>(cp7, wp, stream); }            \
-  } while (0)
       if (wp.TWS == 5) {
         hdmoe_count_selection(HDMOE_SEL_BWD7_32);
         if (wp.c[0].chunks) {
@@ -166,20 +147,19 @@ int hdmoe_conv_bwd6(const void* x, const void* dy, const void* wd, void* dx, flo
       } else {
         hdmoe_count_selection(wp.OT == 2 ? HDMOE_SEL_BWD7_16_OT2 : HDMOE_SEL_BWD7_16_OT1);
       }
-      if (cp7.CO == 2) BWD7_GO(2); else BWD7_GO(1);
+      conv_pick<2, 1>(cp7.CO, [&](auto Co) {           // 32 x 32 maps: wgrad7 / wgrad8 (OT = 0); 16 x 16: the wgrad6 programs
+        if (wp.TWS == 5) launch_bwd7<decltype(Co)::value, 3, 5, 0>(cp7, wp, stream);
+        else conv_pick<2, 1>(wp.OT, [&](auto Ot) { launch_bwd7<decltype(Co)::value, 3, 4, decltype(Ot)::value>(cp7, wp, stream); });
+      });
       return hdmoe_launch_status();
     }
   }
   C6Plan cp;
   if (conv6_plan(c, dtype, cp)) return 1;
   hdmoe_count_selection(HDMOE_SEL_BWD6);
-#define BWD6_GO(M, Nt)                                                                           \
-  do {                                                                                           \
-    if (wp.TWS == 5) { if (wp.OT == 2) launch_bwd6<M, Nt, 5, 2>(cp, wp, stream); else launch_bwd6<M, Nt, 5, 1>(cp, wp, stream); } \
-    else { if (wp.OT == 2) launch_bwd6<M, Nt, 4, 2>(cp, wp, stream); else launch_bwd6<M, Nt, 4, 1>(cp, wp, stream); }            \
-  } while (0)
-  if (cp.MT == 2) { if (cp.NT == 2) BWD6_GO(2, 2); else BWD6_GO(2, 1); }
-  else { if (cp.NT == 2) BWD6_GO(1, 2); else BWD6_GO(1, 1); }
+  conv_pick<2, 1>(cp.MT, [&](auto M) { conv_pick<2, 1>(cp.NT, [&](auto Nt) { conv_pick<5, 4>(wp.TWS, [&](auto Tws) { conv_pick<2, 1>(wp.OT, [&](auto Ot) {
+    launch_bwd6<decltype(M)::value, decltype(Nt)::value, decltype(Tws)::value, decltype(Ot)::value>(cp, wp, stream);
+  }); }); }); });
   return hdmoe_launch_status();
 }
 

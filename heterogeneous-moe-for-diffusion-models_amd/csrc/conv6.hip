@@ -43,12 +43,11 @@ int conv6_plan(const ConvArgs& c, int dtype, C6Plan& plan) {
     if (c.kh[g] > maxk) maxk = c.kh[g];
     if (c.kh[g] < mink) mink = c.kh[g];
   }
-  if (((uintptr_t)c.x | (uintptr_t)c.w | (uintptr_t)c.y | (uintptr_t)c.res) & 15) return 1;
   long maxtaps = 0;
   for (int g = 0; g < c.ngroups; ++g) if ((long)c.kh[g] * c.kw[g] > maxtaps) maxtaps = (long)c.kh[g] * c.kw[g];
   const long xbytes = (long)c.N * c.H * c.W * c.Cin * 2;
   const long wbytes = ((long)(c.ngroups - 1) * c.wstride + maxtaps * c.Cout * c.Cin) * 2;
-  if (xbytes >= (1l << 31) || wbytes >= (1l << 31) || (long)c.N * c.H * c.W * c.Cout >= (1l << 31)) return 1;
+  if (!conv_align_extent_ok({c.x, c.w, c.y, c.res}, {xbytes, wbytes, (long)c.N * c.H * c.W * c.Cout})) return 1;
   C6Args& a = plan.a;
   a.x = c.x; a.w = c.w; a.y = c.y; a.res = c.res; a.seg = c.seg; a.wstride = c.wstride;
   a.N = c.N; a.H = c.H; a.W = c.W; a.Cin = c.Cin; a.Cout = c.Cout; a.ngroups = c.ngroups; a.alpha = c.alpha; a.beta = c.beta;
@@ -56,14 +55,9 @@ int conv6_plan(const ConvArgs& c, int dtype, C6Plan& plan) {
   a.dbg = 0; a.stamps = (unsigned long long*)g_c6_stamps;
   a.w_rowpitch = c.Cin; a.w_tapstride = c.Cout * c.Cin; a.gbias = nullptr;
   a.film_e = nullptr; a.film_h = nullptr; a.film_seed_dev = nullptr; a.film_seed_lo = 0; a.film_seed_hi = 0; a.film_p = 0.f;
-  for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) { a.ks[g] = c.kh[g]; a.pt[g] = c.pt[g]; a.pl[g] = c.pl[g]; a.order[g] = g; }
-  for (int i = 1; i < c.ngroups; ++i)                       // groups by descending kernel size (longest units first)
-    for (int k = i; k > 0 && a.ks[a.order[k]] > a.ks[a.order[k - 1]]; --k) { const int t = a.order[k]; a.order[k] = a.order[k - 1]; a.order[k - 1] = t; }
-  a.TW = c.W >= 32 ? 32 : 16; a.tws = a.TW == 32 ? 5 : 4; a.TH = 256 / a.TW;
-  a.tiles_x = c.W / a.TW;
-  a.tpi = a.tiles_x * (int)cdiv(c.H, a.TH);
-  const int NT = c.Cout % 64 == 0 ? 2 : 1, NB = 32 * NT;
-  a.nblk = c.Cout / NB;
+  for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) { a.ks[g] = c.kh[g]; a.pt[g] = c.pt[g]; a.pl[g] = c.pl[g]; }
+  conv_sort_groups_desc(a.ks, a.order, c.ngroups);
+  const int NT = c6_plan_tiles(c, a), NB = 32 * NT;
   const int ppt = ((a.TH + maxk - 1) * (a.TW + maxk - 1) + 15) / 16;
   if (ppt > 34) return 1;
   const long tiles = (long)c.N * a.tpi;
@@ -72,21 +66,12 @@ int conv6_plan(const ConvArgs& c, int dtype, C6Plan& plan) {
   int T = 0;
   for (; MT >= 1; --MT) {
     a.hb_bytes = C6_NW * ((MT * ppt + C6_NW - 1) / C6_NW) * 1024;   // every wave owns the same number of 1-KB pieces
-    // largest stage (fewest barriers) that fits next to the two halo buffers; at most 40 DMA pieces per stage
-    int best = 0, best_stages = 1 << 30;
-    for (int t = 9; t >= 2; --t) {
-      if (t * (NB / 16) > 40 || 2 * a.hb_bytes + 2 * t * NB * 64 > LDS_CAP) continue;
-      int stages = 0;
-      for (int g = 0; g < c.ngroups; ++g) stages += (c.kh[g] * c.kh[g] + t - 1) / t;
-      if (stages <= best_stages) { best_stages = stages; best = t; }       // ties: the smaller stage (more even split of the taps)
-    }
-    if (best) { T = best; break; }
+    T = conv_pick_stage_T(c.ngroups, c.kh, NB / 16, 2 * a.hb_bytes, NB * 64, LDS_CAP);   // next to the two halo buffers
+    if (T) break;
   }
   if (!T) return 1;
   a.T = T; a.wb_bytes = T * NB * 64;
-  auto recip = [](int d) { return (unsigned)((1ull << 32) / (unsigned)d + 1); };
-  a.m_nblk = a.nblk == 1 ? 0xFFFFFFFFu : recip(a.nblk); a.m_T = recip(T); a.m_tpi = a.tpi == 1 ? 0xFFFFFFFFu : recip(a.tpi);
-  a.m_tx = a.tiles_x == 1 ? 0xFFFFFFFFu : recip(a.tiles_x);
+  c6_plan_magics(a);
   const size_t lds = 2 * (size_t)a.hb_bytes + 2 * (size_t)a.wb_bytes;
   if (lds > (size_t)LDS_CAP || T * (NB / 16) > 40) return 1;
   long ub = (tiles + MT - 1) / MT + c.ngroups;
@@ -108,9 +93,6 @@ int conv6_try_launch(const ConvArgs& c, const ConvFuse* fuse, int dtype, hipStre
   }
   hdmoe_count_selection(HDMOE_SEL_CONV6);
   const C6Args& a = plan.a;
-  const unsigned G = plan.G;
-  const size_t lds = plan.lds;
-  const int MT = plan.MT, NT = plan.NT;
   static unsigned long long attr_set = 0;
   if (hdmoe_first_on_device(attr_set)) {
 #define C6_ATTR(M, Nt) (void)hipFuncSetAttribute((const void*)conv6_bf16_kernel<M, Nt>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
@@ -118,14 +100,10 @@ int conv6_try_launch(const ConvArgs& c, const ConvFuse* fuse, int dtype, hipStre
 #define C6F_ATTR(M, Nt) (void)hipFuncSetAttribute((const void*)conv6_bf16_kernel<M, Nt, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
     C6F_ATTR(1, 1); C6F_ATTR(1, 2); C6F_ATTR(2, 1); C6F_ATTR(2, 2);
   }
-  if (a.film_e) {
-#define C6F_LAUNCH(M, Nt) hipLaunchKernelGGL((conv6_bf16_kernel<M, Nt, true>), dim3(G), dim3(64 * C6_NW), lds, stream, a)
-    if (MT == 2) { if (NT == 2) C6F_LAUNCH(2, 2); else C6F_LAUNCH(2, 1); }
-    else { if (NT == 2) C6F_LAUNCH(1, 2); else C6F_LAUNCH(1, 1); }
-    return hdmoe_launch_status();
-  }
-#define C6_LAUNCH(M, Nt) hipLaunchKernelGGL((conv6_bf16_kernel<M, Nt>), dim3(G), dim3(64 * C6_NW), lds, stream, a)
-  if (MT == 2) { if (NT == 2) C6_LAUNCH(2, 2); else C6_LAUNCH(2, 1); }
-  else { if (NT == 2) C6_LAUNCH(1, 2); else C6_LAUNCH(1, 1); }
+  conv_pick<2, 1>(plan.MT, [&](auto M) { conv_pick<2, 1>(plan.NT, [&](auto Nt) {
+    constexpr int MT = decltype(M)::value, NT = decltype(Nt)::value;
+    if (a.film_e) hipLaunchKernelGGL((conv6_bf16_kernel<MT, NT, true>), dim3(plan.G), dim3(64 * C6_NW), plan.lds, stream, a);
+    else hipLaunchKernelGGL((conv6_bf16_kernel<MT, NT>), dim3(plan.G), dim3(64 * C6_NW), plan.lds, stream, a);
+  }); });
   return hdmoe_launch_status();
 }

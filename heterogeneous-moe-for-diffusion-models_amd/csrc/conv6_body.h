@@ -20,8 +20,7 @@ DEVI void conv6_body(const C6Args& a, const int bid, const int G) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
-  const int csl = ((lane & 3) ^ ((lane >> 4) & 3)) << 4;     // byte offset of the (swizzled) 16-B channel slot this lane fetches
-  const int prow = lane >> 2;                                // its row inside a 16-row DMA piece
+  const int csl = c6_dma_csl(lane), prow = c6_dma_prow(lane);
   // Buffer descriptors: DMA lanes address their operand by a 32-bit byte offset; an out-of-range offset (~0: padding pixels)
   // makes the hardware write zeros, so the halo needs neither a select nor a zero page.
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.x), 0, a.xbytes, 0x00020000);
@@ -67,30 +66,23 @@ DEVI void conv6_body(const C6Args& a, const int bid, const int G) {
   }
   const int total = __builtin_amdgcn_readlane(v_ustart, 7) * a.nblk;
   v_ustart -= v_units;
-  auto udiv = [](int x, unsigned magic, int d) {            // x / d for small non-negative x: 32.32 reciprocal + fix-up
-    int q = (int)(((unsigned long long)(unsigned)x * magic) >> 32);
-    if (q * d > x) --q;
-    if ((q + 1) * d <= x) ++q;
-    return q;
-  };
   auto decode = [&](int j, C6Unit<MT>& u) {
-    const int uu0 = udiv(j, a.m_nblk, a.nblk);
+    const int uu0 = c6_udiv(j, a.m_nblk, a.nblk);
     u.nbk = j - uu0 * a.nblk;
-    const unsigned long long hit = __ballot(lane < 8 && uu0 >= v_ustart && uu0 < v_ustart + v_units);
-    const int slot = (int)__builtin_ctzll(hit | (1ull << 7));
+    const int slot = c6_slot_of(uu0, v_ustart, v_units, lane);
     const int uu = uu0 - __builtin_amdgcn_readlane(v_ustart, slot);
     const int row0 = __builtin_amdgcn_readlane(v_row0, slot), tiles = __builtin_amdgcn_readlane(v_tiles, slot);
     u.g = __builtin_amdgcn_readlane(v_g, slot); u.ks = __builtin_amdgcn_readlane(v_ks, slot);
     u.pt = __builtin_amdgcn_readlane(v_pt, slot); u.pl = __builtin_amdgcn_readlane(v_pl, slot);
-    u.ntaps = u.ks * u.ks; u.ntg = udiv(u.ntaps + a.T - 1, a.m_T, a.T);
+    u.ntaps = u.ks * u.ks; u.ntg = c6_udiv(u.ntaps + a.T - 1, a.m_T, a.T);
     u.HWp = a.TW + u.ks - 1; u.HHp = a.TH + u.ks - 1; u.ppt = (u.HWp * u.HHp + 15) >> 4;
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
       const int tt = uu * MT + m;
       u.valid[m] = tt < tiles;
       const int ttc = u.valid[m] ? tt : tiles - 1;
-      const int img = udiv(ttc, a.m_tpi, a.tpi), ti = ttc - img * a.tpi;
-      const int tyi = udiv(ti, a.m_tx, a.tiles_x);
+      const int img = c6_udiv(ttc, a.m_tpi, a.tpi), ti = ttc - img * a.tpi;
+      const int tyi = c6_udiv(ti, a.m_tx, a.tiles_x);
       u.n[m] = row0 + img; u.ty0[m] = tyi * a.TH; u.tx0[m] = (ti - tyi * a.tiles_x) * a.TW;
     }
   };
@@ -104,16 +96,14 @@ DEVI void conv6_body(const C6Args& a, const int bid, const int G) {
   auto hyx_update = [&](const C6Unit<MT>& u) {
     if (u.ks == hyx_ks) return;
     hyx_ks = u.ks;
-    const int magic = (1 << 20) / u.HWp + 1;
+    const int magic = c6_halo_magic(u.HWp);
     const int npx = u.HWp * u.HHp;
 #pragma unroll
     for (int k = 0; k < NPW; ++k) {
       const int pi = wave + NW * k;
       const int tile = (MT == 2 && pi >= u.ppt) ? 1 : 0;
       const int px = 16 * (pi - tile * u.ppt) + prow;
-      int hy = (int)(((unsigned)px * (unsigned)magic) >> 20);
-      if (hy * u.HWp > px) --hy;
-      const int hx = px - hy * u.HWp;
+      const int hy = c6_halo_row(px, magic, u.HWp), hx = px - hy * u.HWp;
       hyx[k] = (pi < MT * u.ppt && px < npx) ? (unsigned)((hy << 8) | hx) : 0xFFFFFFFFu;
     }
   };
@@ -142,7 +132,7 @@ DEVI void conv6_body(const C6Args& a, const int bid, const int G) {
   auto issue_wpiece = [&](int sb, int k, int wbo) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lptr_t)(lds + wbo + (wave + NW * k) * 1024), 16, wlo, sb + k * wkstep, 0, 0);
   };
-  auto wpieces = [&](int ntl) { return max(0, (ntl - wave / PPT + (NW / PPT) - 1) / (NW / PPT)); };   // this wave's share of a stage
+  auto wpieces = [&](int ntl) { return c6_wpieces<PPT, NW>(ntl, wave); };
   auto stage_base = [&](int wbase, int c, int t0) { return wbase + (t0 * a.w_tapstride + c * 32) * 2; };
 
   int j = bid;
@@ -161,7 +151,7 @@ DEVI void conv6_body(const C6Args& a, const int bid, const int G) {
 
   const int HB0 = 0, WB0 = 2 * a.hb_bytes;
   const int nchunks = a.Cin >> 5;
-  const int wl = r * 64 + ((h << 4) ^ (((r >> 2) & 3) << 4));       // this lane's weight-fragment byte offset inside a tap block
+  const int wl = c6_wfrag_off(r, h);
   const int mb0 = MB * wave;                                        // first 32-pixel block of this wave (of MT * 8)
   const int tile_w = (MT == 2) ? (mb0 >> 3) : 0;                    // the tile all blocks of this wave belong to
   // prologue: first weight stage, then the first unit's first chunk
@@ -336,18 +326,12 @@ DEVI void conv6_body(const C6Args& a, const int bid, const int G) {
             for (int e = 0; e < 4; ++e) { v[e] += a.beta * (float)r0[e]; v[4 + e] += a.beta * (float)r1[e]; }
           }
           typedef __attribute__((ext_vector_type(2))) __bf16 bf2;
-          typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-          const unsigned A0 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[0], (bf16)v[1]}), A1 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[2], (bf16)v[3]});
-          const unsigned B0 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[4], (bf16)v[5]}), B1 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[6], (bf16)v[7]});
-          // after the swap the lower half-wave holds channels 16p .. 16p+7 of its pixel, the upper half 16p+8 .. 16p+15
-          const u32x2 s0 = __builtin_amdgcn_permlane32_swap(A0, B0, false, false);
-          const u32x2 s1 = __builtin_amdgcn_permlane32_swap(A1, B1, false, false);
-          if (ok) *reinterpret_cast<uint4*>(Y + pix + 32 * b + 16 * p + 8 * h) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+          const C6Words pk = c6_pack_bf16(v);
+          if (ok) *reinterpret_cast<uint4*>(Y + pix + 32 * b + 16 * p + 8 * h) = make_uint4(pk.w[0], pk.w[1], pk.w[2], pk.w[3]);
           if (FILM && a.film_e && ok) {
             // FiLM + mp_silu + dropout of the 8 channels this lane just stored (from the bf16-ROUNDED values, as the separate pass reads them)
             const long eo = pix + 32 * b + 16 * p + 8 * h;                  // element index of the first of the 8 channels
             const int c0 = cur.nbk * NB + 32 * b + 16 * p + 8 * h;
-            const unsigned pk[4] = {s0[0], s1[0], s0[1], s1[1]};
             uint32_t r4[8];
             if (a.film_p > 0.f) {
               const long q0 = eo >> 2;
@@ -357,7 +341,7 @@ DEVI void conv6_body(const C6Args& a, const int bid, const int G) {
             unsigned ho[4];
 #pragma unroll
             for (int j2 = 0; j2 < 4; ++j2) {
-              const bf2 yv = __builtin_bit_cast(bf2, pk[j2]);
+              const bf2 yv = __builtin_bit_cast(bf2, pk.w[j2]);
               float f0 = mp_silu_f((float)yv[0] * a.film_e[(long)n * a.Cout + c0 + 2 * j2]);
               float f1 = mp_silu_f((float)yv[1] * a.film_e[(long)n * a.Cout + c0 + 2 * j2 + 1]);
               if (a.film_p > 0.f) {

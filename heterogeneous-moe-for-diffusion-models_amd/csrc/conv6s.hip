@@ -35,21 +35,16 @@ int conv6s_plan(const ConvArgs& c, long wplane_elems, const ConvFuse* fuse, C6SP
   if (c.stride != 1 || c.ones || c.Cphys != c.Cin || c.Ipad != c.Cin || c.Cin % 32 || c.Cout % 32 || c.Cstore != c.Cout) return 1;
   if (c.Ho != c.H || c.Wo != c.W || !(c.W == 16 || c.W % 32 == 0) || c.H < 8) return 1;
   for (int g = 0; g < c.ngroups; ++g) if (c.kh[g] != 3 || c.kw[g] != 3) return 1;
-  if (((uintptr_t)c.x | (uintptr_t)c.w | (uintptr_t)c.y | (uintptr_t)c.res) & 15) return 1;
   const long xbytes = (long)c.N * c.H * c.W * c.Cin * 4;
   const long wbytes = (wplane_elems + (long)(c.ngroups - 1) * c.wstride + 9l * c.Cout * c.Cin) * 2;
-  if (xbytes >= (1l << 31) || wbytes >= (1l << 31) || (long)c.N * c.H * c.W * c.Cout >= (1l << 31)) return 1;
+  if (!conv_align_extent_ok({c.x, c.w, c.y, c.res}, {xbytes, wbytes, (long)c.N * c.H * c.W * c.Cout})) return 1;
   C6SArgs& sa = plan.sa;
   C6Args& a = sa.c;
   a.x = c.x; a.w = c.w; a.y = c.y; a.res = c.res; a.seg = c.seg; a.wstride = c.wstride;
   a.N = c.N; a.H = c.H; a.W = c.W; a.Cin = c.Cin; a.Cout = c.Cout; a.ngroups = c.ngroups; a.alpha = c.alpha; a.beta = c.beta;
   a.xbytes = (int)xbytes; a.wbytes = (int)wbytes; a.dbg = 0; a.stamps = nullptr;
   for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) { a.ks[g] = c.kh[g]; a.pt[g] = c.pt[g]; a.pl[g] = c.pl[g]; a.order[g] = g; }
-  a.TW = c.W >= 32 ? 32 : 16; a.tws = a.TW == 32 ? 5 : 4; a.TH = 256 / a.TW;
-  a.tiles_x = c.W / a.TW;
-  a.tpi = a.tiles_x * (int)cdiv(c.H, a.TH);
-  const int NT = c.Cout % 64 == 0 ? 2 : 1, NB = 32 * NT;
-  a.nblk = c.Cout / NB;
+  const int NT = c6_plan_tiles(c, a), NB = 32 * NT;
   const int ppt = ((a.TH + 2) * (a.TW + 2) + 15) / 16;
   if (ppt > 22) return 1;
   a.hb_bytes = 2 * ppt * 1024;                           // one plane (hi or lo) of the two-tile halo image
@@ -63,9 +58,7 @@ int conv6s_plan(const ConvArgs& c, long wplane_elems, const ConvFuse* fuse, C6SP
     if (t * (NB / 16) <= 40 && 2 * a.hb_bytes + 2 * planes * t * NB * 64 + tab_bytes <= LDS_CAP && (t == 9 || t == 5 || t == 3)) { T = t; break; }
   if (!T) return 1;
   a.T = T; a.wb_bytes = planes * T * NB * 64;
-  auto recip = [](int d) { return (unsigned)((1ull << 32) / (unsigned)d + 1); };
-  a.m_nblk = a.nblk == 1 ? 0xFFFFFFFFu : recip(a.nblk); a.m_T = recip(T); a.m_tpi = a.tpi == 1 ? 0xFFFFFFFFu : recip(a.tpi);
-  a.m_tx = a.tiles_x == 1 ? 0xFFFFFFFFu : recip(a.tiles_x);
+  c6_plan_magics(a);
   sa.wplane = (int)(wplane_elems * 2);
   sa.in_scale = fuse ? fuse->in_scale : nullptr; sa.in_shift = fuse ? fuse->in_shift : nullptr; sa.in_relu = fuse ? fuse->in_relu : 0;
   sa.stats = fuse ? fuse->stats : nullptr;
@@ -93,7 +86,8 @@ int conv6_split_try_launch(const ConvArgs& c, long wplane_elems, const ConvFuse*
     (void)hipFuncSetAttribute((const void*)conv6_split_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)conv6_split_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   }
-  if (plan.NT == 2) hipLaunchKernelGGL((conv6_split_kernel<2>), dim3(plan.G), dim3(64 * C6_NW), plan.lds, stream, plan.sa);
-  else hipLaunchKernelGGL((conv6_split_kernel<1>), dim3(plan.G), dim3(64 * C6_NW), plan.lds, stream, plan.sa);
+  conv_pick<2, 1>(plan.NT, [&](auto Nt) {
+    hipLaunchKernelGGL((conv6_split_kernel<decltype(Nt)::value>), dim3(plan.G), dim3(64 * C6_NW), plan.lds, stream, plan.sa);
+  });
   return hdmoe_launch_status();
 }

@@ -33,8 +33,7 @@ DEVI void conv6s_body(const C6SArgs& sa, const int bid, const int G) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
-  const int csl = ((lane & 3) ^ ((lane >> 4) & 3)) << 4;     // weight DMA: swizzled 16-B slot of this lane
-  const int prow = lane >> 2;
+  const int csl = c6_dma_csl(lane), prow = c6_dma_prow(lane);
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.x), 0, a.xbytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.w), 0, a.wbytes, 0x00020000);
   // y through a buffer descriptor too: a store whose pixel is outside the image gets an out-of-range offset and is dropped by the
@@ -43,7 +42,7 @@ DEVI void conv6s_body(const C6SArgs& sa, const int bid, const int G) {
   const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, a.ybytes, 0x00020000);
   int pending = 0;                                                   // store instructions of the previous unit's epilogue still in flight
 
-  // ---- unit list (see conv6.hip): slot oi of the descending-kernel-size group list lives in lane oi
+  // ---- unit list (as conv6_body.h; written out in each body: as shared functions the selects and the prefix change the register allocation)
   const int oi_l = lane & 7;
   int v_g = 0, v_ks = 0, v_pt = 0, v_pl = 0;
 #pragma unroll
@@ -66,30 +65,23 @@ DEVI void conv6s_body(const C6SArgs& sa, const int bid, const int G) {
   }
   const int total = __builtin_amdgcn_readlane(v_ustart, 7) * a.nblk;
   v_ustart -= v_units;
-  auto udiv = [](int x, unsigned magic, int d) {
-    int q = (int)(((unsigned long long)(unsigned)x * magic) >> 32);
-    if (q * d > x) --q;
-    if ((q + 1) * d <= x) ++q;
-    return q;
-  };
   auto decode = [&](int j, C6Unit<MT>& u) {
-    const int uu0 = udiv(j, a.m_nblk, a.nblk);
+    const int uu0 = c6_udiv(j, a.m_nblk, a.nblk);
     u.nbk = j - uu0 * a.nblk;
-    const unsigned long long hit = __ballot(lane < 8 && uu0 >= v_ustart && uu0 < v_ustart + v_units);
-    const int slot = (int)__builtin_ctzll(hit | (1ull << 7));
+    const int slot = c6_slot_of(uu0, v_ustart, v_units, lane);
     const int uu = uu0 - __builtin_amdgcn_readlane(v_ustart, slot);
     const int row0 = __builtin_amdgcn_readlane(v_row0, slot), tiles = __builtin_amdgcn_readlane(v_tiles, slot);
     u.g = __builtin_amdgcn_readlane(v_g, slot); u.ks = __builtin_amdgcn_readlane(v_ks, slot);
     u.pt = __builtin_amdgcn_readlane(v_pt, slot); u.pl = __builtin_amdgcn_readlane(v_pl, slot);
-    u.ntaps = u.ks * u.ks; u.ntg = udiv(u.ntaps + a.T - 1, a.m_T, a.T);
+    u.ntaps = u.ks * u.ks; u.ntg = c6_udiv(u.ntaps + a.T - 1, a.m_T, a.T);
     u.HWp = a.TW + u.ks - 1; u.HHp = a.TH + u.ks - 1; u.ppt = (u.HWp * u.HHp + 15) >> 4;
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
       const int tt = uu * MT + m;
       u.valid[m] = tt < tiles;
       const int ttc = u.valid[m] ? tt : tiles - 1;
-      const int img = udiv(ttc, a.m_tpi, a.tpi), ti = ttc - img * a.tpi;
-      const int tyi = udiv(ti, a.m_tx, a.tiles_x);
+      const int img = c6_udiv(ttc, a.m_tpi, a.tpi), ti = ttc - img * a.tpi;
+      const int tyi = c6_udiv(ti, a.m_tx, a.tiles_x);
       u.n[m] = row0 + img; u.ty0[m] = tyi * a.TH; u.tx0[m] = (ti - tyi * a.tiles_x) * a.TW;
     }
   };
@@ -99,7 +91,7 @@ DEVI void conv6s_body(const C6SArgs& sa, const int bid, const int G) {
   // channels 4*(lane%8) ..+3).  ho[k]: byte offset of the lane's 16 B inside x at chunk 0 (~0 = padding / beyond the unit: reads 0).
   const int cq = lane & 7;
   auto plan = [&](const C6Unit<MT>& u, unsigned (&ho)[NHP]) {
-    const int magic = (1 << 20) / u.HWp + 1;
+    const int magic = c6_halo_magic(u.HWp);
     const int npx = u.HWp * u.HHp;
     const int cin4 = a.Cin * 4;
 #pragma unroll
@@ -108,9 +100,7 @@ DEVI void conv6s_body(const C6SArgs& sa, const int bid, const int G) {
       const int pxu = 8 * hp + (lane >> 3);                   // pixel inside the unit's two-tile halo image
       const bool t1 = pxu >= u.ppt * 16;
       const int px = pxu - (t1 ? u.ppt * 16 : 0);
-      int hy = (int)(((unsigned)px * (unsigned)magic) >> 20);
-      if (hy * u.HWp > px) --hy;
-      const int hx = px - hy * u.HWp;
+      const int hy = c6_halo_row(px, magic, u.HWp), hx = px - hy * u.HWp;
       const int n = t1 ? u.n[1] : u.n[0];
       const int iy = (t1 ? u.ty0[1] : u.ty0[0]) - u.pt + hy, ix = (t1 ? u.tx0[1] : u.tx0[0]) - u.pl + hx;
       const bool ok = pxu < 2 * u.ppt * 16 && px < npx && (t1 ? u.valid[1] : u.valid[0]) && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
@@ -173,7 +163,7 @@ DEVI void conv6s_body(const C6SArgs& sa, const int bid, const int G) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lptr_t)(lds + wbo + (wave + NW * k) * 1024), 16, wlo, sb + k * wkstep, 0, 0);
     if (P3) __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lptr_t)(lds + wbo + wb_half + (wave + NW * k) * 1024), 16, wlo, sb + sa.wplane + k * wkstep, 0, 0);
   };
-  auto wpieces = [&](int ntl) { return max(0, (ntl - wave / PPT + (NW / PPT) - 1) / (NW / PPT)); };
+  auto wpieces = [&](int ntl) { return c6_wpieces<PPT, NW>(ntl, wave); };
   auto stage_base = [&](int wbase, int plane, int c, int t0) { return wbase + plane * sa.wplane + (t0 * a.Cout * a.Cin + c * 32) * 2; };
 
   int j = bid;
@@ -188,7 +178,7 @@ DEVI void conv6s_body(const C6SArgs& sa, const int bid, const int G) {
   bool has_next = jn < total;
   const int WB0 = 2 * a.hb_bytes;
   const int nchunks = a.Cin >> 5;
-  const int wl = r * 64 + ((h << 4) ^ (((r >> 2) & 3) << 4));
+  const int wl = c6_wfrag_off(r, h);
   const int mb0 = MB * wave;
   const int tile_w = mb0 >> 3;
   // prologue: first weight stage (DMA), first halo chunk (registers -> LDS)

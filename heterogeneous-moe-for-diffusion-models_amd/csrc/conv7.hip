@@ -30,19 +30,17 @@ int conv7_plan(const ConvArgs& c, int dtype, C7Plan& plan) {
     kmask |= k == 3 ? 1 : (k == 5 ? 2 : 4);
     if ((long)k * k > maxtaps) maxtaps = (long)k * k;
   }
-  if (((uintptr_t)c.x | (uintptr_t)c.w | (uintptr_t)c.y | (uintptr_t)c.res) & 15) return 1;
   const long xbytes = (long)c.N * c.H * c.W * c.Cin * 2;
   const long wbytes = ((long)(c.ngroups - 1) * c.wstride + maxtaps * c.Cout * c.Cin) * 2;
-  if (xbytes >= (1l << 31) || wbytes >= (1l << 31) || (long)c.N * c.H * c.W * c.Cout >= (1l << 31)) return 1;
+  if (!conv_align_extent_ok({c.x, c.w, c.y, c.res}, {xbytes, wbytes, (long)c.N * c.H * c.W * c.Cout})) return 1;
   C7Args& a = plan.a;
   a.x = c.x; a.w = c.w; a.y = c.y; a.res = c.res; a.seg = c.seg; a.wstride = c.wstride;
   a.N = c.N; a.Cin = c.Cin; a.Cout = c.Cout; a.ngroups = c.ngroups; a.alpha = c.alpha; a.beta = c.beta;
   a.xbytes = (int)xbytes; a.wbytes = (int)wbytes;
   a.dbg = 0;
   a.stamps = (unsigned long long*)hdmoe_debug_stamp_buffer();
-  for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) { a.ks[g] = c.kh[g]; a.order[g] = g; }
-  for (int i = 1; i < c.ngroups; ++i)                       // groups by descending kernel size (heaviest images first)
-    for (int k = i; k > 0 && a.ks[a.order[k]] > a.ks[a.order[k - 1]]; --k) { const int t = a.order[k]; a.order[k] = a.order[k - 1]; a.order[k - 1] = t; }
+  for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) a.ks[g] = c.kh[g];
+  conv_sort_groups_desc(a.ks, a.order, c.ngroups);          // heaviest images first
   const long gcap = 256;
   const long units = w16 ? (c.N + 1) / 2 + c.ngroups : c.N;    // (16 x 16: pairs of images of one expert; an upper bound for any routing)
   plan.G = (unsigned)(units < gcap ? units : gcap);
@@ -61,9 +59,9 @@ static void conv7_launch_t(const C7Plan& p, hipStream_t stream) {
 }
 
 void conv7_launch(const C7Plan& p, hipStream_t stream) {
-#define C7_GO(Co, Km) do { if (p.w16) conv7_launch_t<Co, Km, true>(p, stream); else conv7_launch_t<Co, Km, false>(p, stream); } while (0)
-  if (p.CO == 2) { if (p.kmask == 7) C7_GO(2, 7); else C7_GO(2, 3); }
-  else { if (p.kmask == 7) C7_GO(1, 7); else C7_GO(1, 3); }
+  conv_pick<2, 1>(p.CO, [&](auto Co) { conv_pick<7, 3>(p.kmask, [&](auto Km) { conv_pick<1, 0>(p.w16 != 0, [&](auto W16) {
+    conv7_launch_t<decltype(Co)::value, decltype(Km)::value, decltype(W16)::value != 0>(p, stream);
+  }); }); });
 }
 
 int conv7_try_launch(const ConvArgs& c, int dtype, hipStream_t stream) {

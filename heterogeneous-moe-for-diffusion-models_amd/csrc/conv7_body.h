@@ -17,13 +17,11 @@
 //     and the epilogue stores in flight across the stage barriers.
 #pragma once
 #include <type_traits>
-#include <type_traits>
 #include <utility>
 #include "common.h"
+#include "conv6_common.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) void* c7_lptr_t;
 
 struct C7Args {
   const void* x; const void* w; void* y; const void* res; const int* seg;
@@ -162,11 +160,11 @@ DEVI void conv7_body(const C7Args& a, const int bid, const int G) {
         const int n = img ? u.n2 : u.n;
         const int so = (n * 16 + row) * 16 * cin2 + c * 64;
         const unsigned vo = n < 0 ? 0xFFFFFFFFu : xlane;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (c7_lptr_t)(lds + lbase + (img * 16 + row) * ROWB), 16, vo, n < 0 ? 0 : so, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lptr_t)(lds + lbase + (img * 16 + row) * ROWB), 16, vo, n < 0 ? 0 : so, 0, 0);
       } else {
         const int row = 4 * wave + (k >> 1), half = k & 1;
         const int so = ((u.n * 32 + row) * 32 + half * 16) * cin2 + c * 64;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (c7_lptr_t)(lds + lbase + row * ROWB + half * 1024), 16, xlane, so, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lptr_t)(lds + lbase + row * ROWB + half * 1024), 16, xlane, so, 0, 0);
       }
     }
   };
@@ -179,7 +177,7 @@ DEVI void conv7_body(const C7Args& a, const int bid, const int G) {
       if (ts < nt) {
         const int tap = (ky0 + ts) * ks + kx;
         const int so = (int)(((long)g * a.wstride + (long)(tap * a.Cout + blk * 32 * CO + pc * 16) * a.Cin) * 2) + c * 64;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (c7_lptr_t)(lds + sp * WBUF + pi * 1024), 16, wlane, so, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lptr_t)(lds + sp * WBUF + pi * 1024), 16, wlane, so, 0, 0);
       }
     }
   };
@@ -313,13 +311,8 @@ DEVI void conv7_body(const C7Args& a, const int bid, const int G) {
 #pragma unroll
               for (int e = 0; e < 4; ++e) { v[e] += a.beta * (float)r0[e]; v[4 + e] += a.beta * (float)r1[e]; }
             }
-            typedef __attribute__((ext_vector_type(2))) __bf16 bf2;
-            typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-            const unsigned A0 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[0], (bf16)v[1]}), A1 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[2], (bf16)v[3]});
-            const unsigned B0 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[4], (bf16)v[5]}), B1 = __builtin_bit_cast(unsigned, (bf2){(bf16)v[6], (bf16)v[7]});
-            const u32x2 s0 = __builtin_amdgcn_permlane32_swap(A0, B0, false, false);
-            const u32x2 s1 = __builtin_amdgcn_permlane32_swap(A1, B1, false, false);
-            if (live) *reinterpret_cast<uint4*>(Y + pix + cobase + 32 * b + 16 * p + 8 * h) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+            const C6Words pk = c6_pack_bf16(v);
+            if (live) *reinterpret_cast<uint4*>(Y + pix + cobase + 32 * b + 16 * p + 8 * h) = make_uint4(pk.w[0], pk.w[1], pk.w[2], pk.w[3]);
           }
       }
     } else {

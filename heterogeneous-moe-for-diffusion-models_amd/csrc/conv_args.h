@@ -1,6 +1,8 @@
 // Argument block shared by the conv forward / dgrad kernels (conv.hip: v5 and the odd-shape kernels; conv6.hip: the
 // persistent LDS-DMA pipelined kernel).
 #pragma once
+#include <initializer_list>
+#include <type_traits>
 #include "common.h"
 
 struct ConvArgs {
@@ -15,6 +17,53 @@ struct ConvArgs {
   int kh[HDMOE_MAX_GROUPS], kw[HDMOE_MAX_GROUPS], pt[HDMOE_MAX_GROUPS], pl[HDMOE_MAX_GROUPS];
   float alpha, beta;
 };
+
+// ---- plan helpers shared by conv6_plan, conv6s_plan, conv7_plan and blk6_plan
+// every pointer 16-byte aligned (null: absent) and every extent (bytes of a DMA operand, elements of an output) below 2^31
+static inline bool conv_align_extent_ok(std::initializer_list<const void*> ptrs, std::initializer_list<long> extents) {
+  for (const void* p : ptrs) if ((uintptr_t)p & 15) return false;
+  for (long e : extents) if (e >= (1l << 31)) return false;
+  return true;
+}
+// Template dispatch: f(std::integral_constant<int, A>) when v == A, else f(std::integral_constant<int, B>) -- a plan's run-time integer
+// becomes a template argument; nest one call per parameter.
+template <int A, int B, typename F> static inline void conv_pick(int v, F&& f) {
+  if (v == A) f(std::integral_constant<int, A>{}); else f(std::integral_constant<int, B>{});
+}
+// order[] = the groups by descending kernel size (longest units first; stable)
+static inline void conv_sort_groups_desc(const int* ks, int* order, int ngroups) {
+  for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) order[g] = g;
+  for (int i = 1; i < ngroups; ++i)
+    for (int k = i; k > 0 && ks[order[k]] > ks[order[k - 1]]; --k) { const int t = order[k]; order[k] = order[k - 1]; order[k - 1] = t; }
+}
+// 2^32 / d + 1: x / d = (x * magic) >> 32 with a fix-up (c6_udiv); d == 1 would need 2^32 + 1 and takes the largest magic instead
+static inline unsigned conv_recip(int d) { return d == 1 ? 0xFFFFFFFFu : (unsigned)((1ull << 32) / (unsigned)d + 1); }
+// Largest weight stage (taps per stage, 9 .. 2) that fits: at most 40 DMA pieces per stage, fixed_lds_bytes + two stage buffers within cap;
+// among those the fewest stages (barriers) over the groups, ties to the smaller stage (more even split of the taps).  0: none fits.
+static inline int conv_pick_stage_T(int ngroups, const int* ks, int pieces_per_tap, long fixed_lds_bytes, int bytes_per_tap, long cap) {
+  int best = 0, best_stages = 1 << 30;
+  for (int t = 9; t >= 2; --t) {
+    if (t * pieces_per_tap > 40 || fixed_lds_bytes + 2l * t * bytes_per_tap > cap) continue;
+    int stages = 0;
+    for (int g = 0; g < ngroups; ++g) stages += (ks[g] * ks[g] + t - 1) / t;
+    if (stages <= best_stages) { best_stages = stages; best = t; }
+  }
+  return best;
+}
+// The input gradient of a stride-1 k x k layer as a forward conv over dy with the flipped weight image wd [g][tap][Cin][Cout]: the
+// channel counts swap and the pads flip (k - 1 - p).  Cin / Cout are the layer's; groups past ngroups repeat group 0.
+static inline ConvArgs conv_dgrad_args(const void* dy, const void* wd, void* dx, const int* seg, int ngroups, long wd_stride, int N, int H, int W,
+                                       int Cin, int Cout, const int* kh, const int* kw, const int* pt, const int* pl, float alpha) {
+  ConvArgs c;
+  c.x = dy; c.w = wd; c.y = dx; c.res = nullptr; c.seg = seg; c.wstride = wd_stride;
+  c.N = N; c.H = H; c.W = W; c.Ho = H; c.Wo = W; c.Cin = Cout; c.Cphys = Cout; c.Ipad = Cout; c.Cout = Cin; c.Cstore = Cin;
+  c.stride = 1; c.ones = 0; c.ngroups = ngroups; c.n0 = 0; c.alpha = alpha; c.beta = 0.f;
+  for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) {
+    const int s = g < ngroups ? g : 0;
+    c.kh[g] = kh[s]; c.kw[g] = kw[s]; c.pt[g] = kh[s] - 1 - pt[s]; c.pl[g] = kw[s] - 1 - pl[s];
+  }
+  return c;
+}
 
 // Fused pro-/epilogue of the conv6 kernels (all optional):
 //   in_scale/in_shift [N][Cin] fp32 + in_relu: the staged input is relu(x * scale[n][c] + shift[n][c]) -- GroupNorm(1,C) + ReLU of the

@@ -108,9 +108,9 @@ int launch_conv6_pitched(const ConvArgs& c, int rowpitch, int tapstride, long wi
 #define C6O_ATTR(M, Nt) (void)hipFuncSetAttribute((const void*)conv6_ones_kernel<M, Nt>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
     C6O_ATTR(1, 1); C6O_ATTR(1, 2); C6O_ATTR(2, 1); C6O_ATTR(2, 2);
   }
-#define C6O_LAUNCH(M, Nt) hipLaunchKernelGGL((conv6_ones_kernel<M, Nt>), dim3(plan.G), dim3(64 * C6_NW), plan.lds, stream, a)
-  if (plan.MT == 2) { if (plan.NT == 2) C6O_LAUNCH(2, 2); else C6O_LAUNCH(2, 1); }
-  else { if (plan.NT == 2) C6O_LAUNCH(1, 2); else C6O_LAUNCH(1, 1); }
+  conv_pick<2, 1>(plan.MT, [&](auto M) { conv_pick<2, 1>(plan.NT, [&](auto Nt) {
+    hipLaunchKernelGGL((conv6_ones_kernel<decltype(M)::value, decltype(Nt)::value>), dim3(plan.G), dim3(64 * C6_NW), plan.lds, stream, a);
+  }); });
   return hdmoe_launch_status();
 }
 
@@ -167,12 +167,9 @@ int hdmoe_conv6_ones_bwd(const void* x, const void* dy, const void* wd, void* dx
   if (N == 0) return HDMOE_OK;
   if (dx) {
     if (!wd) return HDMOE_EINVAL;
-    ConvArgs c;                                             // dgrad as a forward conv over dy: "Cout" = C input channels, "Cin" = O
-    c.x = dy; c.w = wd; c.y = dx; c.res = nullptr; c.seg = seg; c.wstride = wdstride;
-    c.N = N; c.H = H; c.W = W; c.Ho = H; c.Wo = W; c.Cin = O; c.Cphys = O; c.Ipad = O; c.Cout = C; c.Cstore = C;
-    c.stride = 1; c.ones = 0; c.ngroups = ngroups; c.n0 = 0; c.alpha = alpha; c.beta = 0.f;
+    const ConvArgs c = conv_dgrad_args(dy, wd, dx, seg, ngroups, wdstride, N, H, W, C, O, k2, k2, pd, pd, alpha);
     int maxk = 0;
-    for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) { c.kh[g] = c.kw[g] = geo.ks[g]; c.pt[g] = c.pl[g] = pd[g]; if (g < ngroups && geo.ks[g] > maxk) maxk = geo.ks[g]; }
+    for (int g = 0; g < ngroups; ++g) if (k2[g] > maxk) maxk = k2[g];
     const int rc = launch_conv6_pitched(c, Opad, (C + 1) * Opad, (long)maxk * maxk * (C + 1) * Opad, nullptr, stream);
     if (rc) return rc;
   }
