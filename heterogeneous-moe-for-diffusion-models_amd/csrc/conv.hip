@@ -1166,24 +1166,238 @@ __global__ __launch_bounds__(256, (MAXT <= 3 ? 2 : 1)) void conv_wgrad2_kernel(W
 
 constexpr int ROWS_PER_LAUNCH = 65535;                      // gridDim.y limit of the row-per-blockIdx.y kernels
 
-template <typename T, int NB>
-void launch_conv(ConvArgs a, bool vec, hipStream_t st) {
-  for (int n0 = 0; n0 < a.N; n0 += ROWS_PER_LAUNCH) {
-    a.n0 = n0;
-    dim3 grid(cdiv((long)a.Ho * a.Wo, 128), a.N - n0 < ROWS_PER_LAUNCH ? a.N - n0 : ROWS_PER_LAUNCH, cdiv(a.Cstore, 32 * NB));
-    if (vec) hipLaunchKernelGGL((conv_fwd_kernel<T, NB, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv_fwd_kernel<T, NB, false>), grid, dim3(256), 0, st, a);
+// One launch of the planned kernel (conv_fwd5: a flat grid), or one per 65535 rows.
+void conv_fwd_launch(ConvArgs a, int dtype, const CvPlan& p, hipStream_t stream) {
+  auto rows = [&](auto launch) {
+    dim3 grid = p.grid;
+    for (int n0 = 0; n0 < a.N; n0 += ROWS_PER_LAUNCH) {
+      a.n0 = n0; grid.y = a.N - n0 < ROWS_PER_LAUNCH ? a.N - n0 : ROWS_PER_LAUNCH;
+      launch(grid);
+    }
+  };
+  conv_pick_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (p.kernel == HDMOE_ROUTE_CONV_FWD5) {
+      conv_pick<1, 2>(p.NT, [&](auto Nt) { conv_pick<1, 0>(p.lepi, [&](auto L) { conv_pick<7, 9>(p.NHR, [&](auto Hr) {
+        hipLaunchKernelGGL((conv_fwd5_kernel<T, decltype(Nt)::value, decltype(L)::value != 0, decltype(Hr)::value>), p.grid, dim3(256), p.lds,
+                           stream, a, p.TH, p.TW, p.tiles_x, p.halo_cap, p.tg, p.ntiles);
+      }); }); });
+    } else if (p.kernel == HDMOE_ROUTE_CONV_FWD3) {
+      conv_pick<1, 2>(p.NT, [&](auto Nt) { rows([&](dim3 grid) {
+        hipLaunchKernelGGL((conv_fwd3_kernel<T, decltype(Nt)::value>), grid, dim3(256), p.lds, stream, a, p.TH, p.TW, p.tiles_x, p.halo_cap, p.tg);
+      }); });
+    } else if (p.kernel == HDMOE_ROUTE_CONV_FWD2) {
+      conv_pick<1, 2>(p.NT, [&](auto Nt) { conv_pick<1, 0>(p.vec, [&](auto V) { rows([&](dim3 grid) {
+        hipLaunchKernelGGL((conv_fwd2_kernel<T, decltype(Nt)::value, decltype(V)::value != 0>), grid, dim3(256), p.lds, stream, a, p.TH, p.TW,
+                           p.tiles_x, p.halo_cap);
+      }); }); });
+    } else {
+      conv_pick<1, 2, 4>(p.NT, [&](auto Nb) { conv_pick<1, 0>(p.vec, [&](auto V) { rows([&](dim3 grid) {
+        hipLaunchKernelGGL((conv_fwd_kernel<T, decltype(Nb)::value, decltype(V)::value != 0>), grid, dim3(256), 0, stream, a);
+      }); }); });
+    }
+  });
+}
+
+// opt all 16 conv_fwd5 instantiations into up to 80 KB of dynamic LDS (two workgroups still share a CU), once per device
+void conv_fwd5_lds_attr() {
+  static unsigned long long attr_set = 0;
+  if (!hdmoe_first_on_device(attr_set)) return;
+  for (int i = 0; i < 16; ++i)
+    conv_pick_dtype(i & 1, [&](auto t) { conv_pick<1, 2>(1 + (i >> 1 & 1), [&](auto Nt) { conv_pick<1, 0>(i >> 2 & 1, [&](auto L) { conv_pick<7, 9>(i >> 3 ? 9 : 7, [&](auto Hr) {
+      (void)hipFuncSetAttribute((const void*)conv_fwd5_kernel<decltype(t), decltype(Nt)::value, decltype(L)::value != 0, decltype(Hr)::value>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+    }); }); }); });
+}
+
+WgradArgs wgrad_args(const void* x, const void* dy, float* const* G, const int* seg, int ngroups, int N, int H, int W, int Ho, int Wo, int Cin, int Cphys,
+                     int Cout, int stride, int ones, const int* kh, const int* kw, const int* pt, const int* pl) {
+  WgradArgs a;
+  a.x = x; a.dy = dy; a.seg = seg; a.N = N; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.Cin = Cin; a.Cphys = Cphys;
+  a.Cout = Cout; a.stride = stride; a.ones = ones; a.ngroups = ngroups; a.tap_lo = 0;
+  conv_fill_groups(a.G, G, ngroups);
+  conv_fill_groups(a.kh, kh, ngroups); conv_fill_groups(a.kw, kw, ngroups); conv_fill_groups(a.pt, pt, ngroups); conv_fill_groups(a.pl, pl, ngroups);
+  return a;
+}
+int wgrad_max_taps(const WgradArgs& a) {
+  int m = 0;
+  for (int g = 0; g < a.ngroups; ++g) m = a.kh[g] * a.kw[g] > m ? a.kh[g] * a.kw[g] : m;
+  return m;
+}
+
+// ---- launch plan of conv_wgrad2_kernel (stride 1): one launch per pass for each kernel-size class of the call, so the per-wave
+//      accumulator count (MAXT) matches the class
+struct Wg2ClassPlan { Wg2Geom gm; int kh, kw, passes, mt, MAXT, OT, OBP, halo, vec, ibs, obs; size_t lds; };   // (upw, chunks, groups: in gm)
+struct Wg2Plan { int nclasses; Wg2ClassPlan cls[HDMOE_MAX_GROUPS]; };
+
+// Everything of c but gm's tile geometry / groups and kh / kw.  units = (sample, pixel-tile) units of the call.  False: the class does not fit.
+bool wg2_class_plan(Wg2ClassPlan& c, long units, const WgradArgs& a, int dtype, bool aligned16) {
+  const int esz = dtype == HDMOE_BF16 ? 2 : 4, vw = 16 / esz, PTpx = esz == 4 ? Wg2PT<float>::N : Wg2PT<bf16>::N;
+  const int taps = c.kh * c.kw;
+  // a wave owns mt accumulator sets: mt = taps for taps < 4, (taps + 3) / 4 <= 7 for 4 <= taps <= 28, 7 for taps > 28, so mt <= 7 always.
+  // 13 sets per wave (7x7 in one pass) would not fit the register file: classes with more than 28 taps run as ceil(taps / 28) passes
+  // of the 7-set kernel over tap ranges (the tiles are staged once per pass)
+  c.passes = taps > 28 ? (taps + 27) / 28 : 1;
+  c.mt = c.passes > 1 ? 7 : (taps < 4 ? taps : (taps + 3) / 4);
+  c.MAXT = c.mt <= 3 ? 3 : 7;
+  c.OT = a.Cout <= 32 ? 1 : 2;
+  const int OB = 32 * c.OT;
+  c.OBP = (c.OT == 2 && esz == 2) ? OB + 32 : OB;
+  const long HHp = c.gm.TH + c.kh - 1, HWp = c.gm.TW + c.kw - 1;
+  c.halo = (int)(HHp * HWp);
+  c.lds = (size_t)esz * (PTpx * c.OBP + c.halo * WG2_IB);
+  // the kernel decodes halo pixels with (px * magic) >> 20, exact only while px * HWp < 2^20 (px < HHp * HWp)
+  if (c.lds > 64 * 1024 || HHp * HWp * HWp >= (1l << 20)) return false;
+  const int nx_cap = (esz == 2 ? 6 : 8) * 256;                    // register-prefetch capacity (16-B halo chunks)
+  c.vec = a.Cout % vw == 0 && a.Cphys % vw == 0 && aligned16 && c.halo * (WG2_IB / vw) <= nx_cap;
+  c.ibs = cdiv(a.Cin, WG2_IB); c.obs = cdiv(a.Cout, OB);
+  // Every workgroup ends with an fp32 atomic flush of its [taps][OB][32] accumulators (~1.3 TB/s chip-wide), so the
+  // flush traffic is (pixel partitions) x (weight bytes).  fp32 units are long (64-cycle MFMAs): fill the chip exactly
+  // once.  bf16 units are short and the flush dominates: fewer, longer workgroups measured best (launch_table sweeps).
+  long upw;
+  if (esz == 4) {
+    long parts = 512 / ((long)c.ibs * c.obs); if (parts < 8) parts = 8;
+    const long class_units = (units * c.gm.ngr + a.ngroups - 1) / a.ngroups;   // assume balanced routing
+    upw = (class_units + parts - 1) / parts;
+  } else {
+    // classes with more than 9 taps flush (taps x 64 x 32) floats per workgroup: fewer, longer workgroups (bench sweep:
+    // 384 -> 256 partitions = -0.7 ms/step at B = 256)
+    long parts = (taps > 9 ? 256 : 384) / ((long)c.ibs * c.obs); if (parts < 8) parts = 8;
+    upw = (units + parts - 1) / parts;
+  }
+  if (upw < 1) upw = 1;
+  c.gm.upw = (int)upw;
+  c.gm.chunks = (int)((units + upw - 1) / upw);
+  return true;
+}
+
+// LDS-staged tiles of TH rows x TW columns (TH * TW <= 128 pixels); one class per distinct kh x kw, in the order of their first group.
+// Pure.  False: some class does not fit, and the call as a whole takes conv_wgrad_kernel.
+bool wg2_plan(Wg2Plan& p, const WgradArgs& a, int dtype, bool aligned16) {
+  if (a.stride != 1 || (dtype != HDMOE_F32 && dtype != HDMOE_BF16)) return false;
+  Wg2Geom gm = {};
+  const int PTpx = dtype == HDMOE_F32 ? Wg2PT<float>::N : Wg2PT<bf16>::N;
+  // near-square tiles keep the halo small (a 2 x 64 tile of a 7x7 layer needs 8 x 70 halo pixels, a 4 x 32 tile 10 x 38);
+  // single-row tensors (flattened token rows) take the whole tile width
+  const int tw_cap = a.Ho == 1 ? PTpx : 32;
+  gm.TW = a.Wo < tw_cap ? a.Wo : tw_cap;
+  gm.TH = PTpx / gm.TW; if (gm.TH > a.Ho) gm.TH = a.Ho; if (gm.TH < 1) gm.TH = 1;
+  gm.tw_shift = -1;
+  for (int sft = 0; sft < 8; ++sft) if ((1 << sft) == gm.TW) gm.tw_shift = sft;
+  gm.tiles_y = cdiv(a.Ho, gm.TH); gm.tiles_x = cdiv(a.Wo, gm.TW);
+  const long units = (long)a.N * gm.tiles_y * gm.tiles_x;
+  if (units >= (1l << 30)) return false;
+  bool done[HDMOE_MAX_GROUPS] = {false};
+  p.nclasses = 0;
+  for (int g = 0; g < a.ngroups; ++g) {
+    if (done[g]) continue;
+    Wg2ClassPlan& c = p.cls[p.nclasses++];
+    c = Wg2ClassPlan{gm, a.kh[g], a.kw[g]};
+    for (int g2 = g; g2 < a.ngroups; ++g2)
+      if (!done[g2] && a.kh[g2] == c.kh && a.kw[g2] == c.kw) { c.gm.groups[c.gm.ngr++] = g2; done[g2] = true; }
+    if (!wg2_class_plan(c, units, a, dtype, aligned16)) return false;
+  }
+  return true;
+}
+
+void wg2_launch(WgradArgs a, const Wg2Plan& p, int dtype, hipStream_t stream) {
+  for (int k = 0; k < p.nclasses; ++k) {
+    const Wg2ClassPlan& c = p.cls[k];
+    const dim3 grid(c.ibs, c.obs, c.gm.chunks * c.gm.ngr);
+    for (int pass = 0; pass < c.passes; ++pass) {
+      a.tap_lo = 28 * pass;
+      conv_pick_dtype(dtype, [&](auto t) { conv_pick<2, 1>(c.OT, [&](auto Ot) { conv_pick<3, 7>(c.MAXT, [&](auto Mt) { conv_pick<1, 0>(c.vec, [&](auto V) {
+        hipLaunchKernelGGL((conv_wgrad2_kernel<decltype(t), decltype(Ot)::value, decltype(Mt)::value, decltype(V)::value != 0>), grid, dim3(256),
+                           c.lds, stream, a, c.gm);
+      }); }); }); });
+    }
   }
 }
 
-template <typename T>
-void launch_conv_nb(const ConvArgs& a, bool vec, hipStream_t st) {
-  if (a.Cstore <= 32) launch_conv<T, 1>(a, vec, st);
-  else if (a.Cstore <= 64) launch_conv<T, 2>(a, vec, st);
-  else launch_conv<T, 4>(a, vec, st);
+// The stem / head / pointwise kernels of lwgrad.hip, tried in this order before the kernels of this file.  Returns the HDMOE_ROUTE_WGRAD_* of
+// the one that took the layer (rc = its status), or -1.  dry_run: decide only.
+int wgrad_try_siblings(const WgradArgs& a, int dtype, hipStream_t stream, bool dry_run, int& rc) {
+  if (a.stride != 1 || a.ones || a.Ho != a.H || a.Wo != a.W) return -1;
+  const int maxtaps = wgrad_max_taps(a), k = a.kh[0];
+  const bool one_square = a.ngroups == 1 && !a.seg && k == a.kw[0];
+  if (one_square && maxtaps > 1 && maxtaps * a.Cin <= 64 && a.pt[0] == (k - 1) / 2 && a.pl[0] == (k - 1) / 2) {
+    rc = swg_try_launch(a.x, a.dy, a.G[0], a.N, a.H, a.W, a.Cin, a.Cout, k, a.pt[0], a.pl[0], dtype, stream, dry_run);
+    if (rc <= 0) return HDMOE_ROUTE_WGRAD_SWG;
+  }
+  if (one_square && a.Cout <= 4) {
+    rc = towg_try_launch(a.x, a.dy, a.G[0], a.N, a.H, a.W, a.Cin, a.Cout, k, a.pt[0], a.pl[0], dtype, stream, dry_run);
+    if (rc <= 0) return HDMOE_ROUTE_WGRAD_TOWG;
+  }
+  bool plain = maxtaps == 1;
+  for (int g = 0; g < a.ngroups; ++g) plain = plain && a.kh[g] == 1 && a.kw[g] == 1 && a.pt[g] == 0 && a.pl[g] == 0;
+  if (plain) {
+    rc = lwg_try_launch(a.x, a.dy, a.G, a.seg, a.ngroups, a.N, (long)a.H * a.W, a.Cin, a.Cout, dtype, stream, dry_run);
+    if (rc <= 0) return HDMOE_ROUTE_WGRAD_LWG;
+  }
+  return -1;
 }
 
 }  // namespace
+
+int conv_fwd_plan(const ConvArgs& a, int dtype, CvPlan& p) {
+  const int esz = dtype == HDMOE_BF16 ? 2 : 4;
+  p = CvPlan{};
+  p.vec = a.Cphys % (16 / esz) == 0 && (uintptr_t)a.x % 16 == 0;
+  if (a.stride == 1 && (long)a.Ho * a.Wo >= 64) {
+    // ---- LDS-staged 256-pixel tiles (fwd5, fwd3, fwd2)
+    const int PT = 4 * CV2_MT * 32;
+    int maxkh = 1, maxkw = 1;
+    for (int g = 0; g < a.ngroups; ++g) { if (a.kh[g] > maxkh) maxkh = a.kh[g]; if (a.kw[g] > maxkw) maxkw = a.kw[g]; }
+    const bool v5ok = !a.ones && a.Cstore % 4 == 0 && (uintptr_t)a.y % 16 == 0 && (uintptr_t)a.res % 16 == 0 && (uintptr_t)a.w % 16 == 0;
+    p.NT = a.Cstore <= 32 ? 1 : 2;
+    const int nblk = (int)cdiv(a.Cstore, 32 * p.NT);
+    const int wrows = maxkw * 32 * p.NT;                     // weight rows of one kernel row
+    const bool in_range = (long)maxkh * maxkw * a.Cout * a.Ipad < (1l << 26) && (long)a.H * a.W * a.Cphys < (1l << 30);
+    auto set_tile = [&](int TW) {
+      p.TW = TW; p.TH = PT / TW; if (p.TH > a.Ho) p.TH = a.Ho; if (p.TH < 1) p.TH = 1;
+      p.halo_cap = (p.TH + maxkh - 1) * (TW + maxkw - 1);
+    };
+    // Tile = whole image rows, or (v5 only, images wider than 32 with a real kernel window) 8 x 32 blocks: a 4 x 64 tile of a
+    // 7x7 layer needs a 10 x 70 halo, the 8 x 32 block 14 x 38.  Only when the v5 launch below is certain: the older kernels
+    // assume linear tiles.
+    bool tile2d = v5ok && p.vec && a.Ho >= 8 && a.Wo > 32 && a.Wo % 32 == 0 && maxkh * maxkw > 1 && wrows <= 576 && in_range;
+    if (tile2d) { set_tile(32); tile2d = p.halo_cap * 4 <= 9 * 256 && (size_t)80 * (p.halo_cap + wrows) <= 80 * 1024; }
+    if (!tile2d) set_tile(a.Wo < PT ? a.Wo : PT);
+    p.tiles_x = cdiv(a.Wo, p.TW);
+    p.ntiles = (int)cdiv(a.Ho, p.TH) * p.tiles_x;
+    p.grid = dim3(p.ntiles, a.N, nblk);
+    // v5 / v3 (register prefetch): rows of weights per stage <= 576 (9 chunks/thread); halo <= 448 px (7 chunks/thread), or for
+    // v5 <= 576 px (9 chunks/thread: 7x7 experts, whose halo of a 256-pixel tile is 14 x 38 or 22 x 22 pixels)
+    if (p.vec && p.halo_cap * 4 <= (v5ok ? 9 : 7) * 256 && wrows <= 576 && in_range &&
+        (long)p.halo_cap * (p.TW + maxkw - 1) < (1l << 20)) {   // the kernels' (px * magic) >> 20 halo decode is exact while px * HWp < 2^20
+      int tg = 576 / wrows;
+      if (tg > maxkh) tg = maxkh;
+      while (tg > 1 && (size_t)80 * (p.halo_cap + tg * wrows) > 64 * 1024) --tg;       // prefer <= 64 KB
+      p.tg = tg;
+      p.lds = (size_t)80 * (p.halo_cap + tg * wrows);
+      // a workgroup may use up to 80 KB of LDS under v5 (two still share a CU): needed by 7x7 experts with 64-channel tiles
+      if (v5ok && p.lds <= 80 * 1024) {
+        if (nblk > 0x3FFF) return HDMOE_EINVAL;
+        p.kernel = HDMOE_ROUTE_CONV_FWD5;
+        // LDS-transposed epilogue needs whole 16-B pieces per pixel and a slab of 4 waves x 32 px x (32 NT + pad) elements
+        p.lepi = a.Cstore % (16 / esz) == 0 && (size_t)4 * 32 * (32 * p.NT + 16 / esz) * esz <= p.lds;
+        p.NHR = p.halo_cap * 4 > 7 * 256 ? 9 : 7;
+        p.tg = tg | (tile2d ? 1 << 16 : 0) | (nblk << 17);     // bit 16: 8 x 32 block tiles; bits 17-30: channel blocks
+        p.grid = dim3((unsigned)(8 * (((long)a.N * p.ntiles + 7) / 8) * nblk));
+        return HDMOE_OK;
+      }
+      if (p.lds <= 64 * 1024 && p.halo_cap * 4 <= 7 * 256) { p.kernel = HDMOE_ROUTE_CONV_FWD3; return HDMOE_OK; }
+    }
+    p.lds = (size_t)80 * (p.halo_cap + wrows);
+    if (p.lds <= 64 * 1024 && p.grid.x <= 65535 * 32) { p.kernel = HDMOE_ROUTE_CONV_FWD2; return HDMOE_OK; }
+  }
+  // ---- one thread per output pixel and channel block (tiny images, stride > 1)
+  p.kernel = HDMOE_ROUTE_CONV_FWD;
+  p.NT = a.Cstore <= 32 ? 1 : (a.Cstore <= 64 ? 2 : 4);
+  p.lds = 0;
+  p.grid = dim3(cdiv((long)a.Ho * a.Wo, 128), a.N, cdiv(a.Cstore, 32 * p.NT));
+  return HDMOE_OK;
+}
 
 void hdmoe_count_selection(int which) {
   if (which >= 0 && which < HDMOE_SEL_COUNT) g_selections[which].fetch_add(1, std::memory_order_relaxed);
@@ -1206,11 +1420,8 @@ int hdmoe_wprep_fwd(float* const* w_raw, const float* const* gain_ptr, float gai
   if (ngroups < 1 || ngroups > HDMOE_MAX_GROUPS || O < 1 || I < 1 || Ipad < I || Ipad % 16 || !wf) return HDMOE_EINVAL;
   if (wd && (Opad < O || Opad % 16)) return HDMOE_EINVAL;
   WprepArgs a;
-  for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) {
-    const int s = g < ngroups ? g : 0;
-    a.w_raw[g] = w_raw[s]; a.gain_ptr[g] = gain_ptr ? gain_ptr[s] : nullptr;
-    a.kh[g] = kh[s]; a.kw[g] = kw[s];
-  }
+  conv_fill_groups(a.w_raw, w_raw, ngroups); conv_fill_groups(a.gain_ptr, gain_ptr, ngroups);
+  conv_fill_groups(a.kh, kh, ngroups); conv_fill_groups(a.kw, kw, ngroups);
   a.wf = wf; a.wd = wd; a.wf_stride = wf_stride; a.wd_stride = wd_stride;
   a.O = O; a.I = I; a.Ipad = Ipad; a.Opad = wd ? Opad : O; a.gain_val = gain_val;
   a.normalize = normalize; a.mutate = mutate; a.flip = flip;
@@ -1231,12 +1442,9 @@ int hdmoe_wprep_bwd(const float* const* w_raw, const float* const* gain_ptr, flo
                     int ngroups, int O, int I, int normalize, hipStream_t stream) {
   if (ngroups < 1 || ngroups > HDMOE_MAX_GROUPS || O < 1 || I < 1) return HDMOE_EINVAL;
   WprepBwdArgs a;
-  for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) {
-    const int s = g < ngroups ? g : 0;
-    a.w_raw[g] = w_raw[s]; a.gain_ptr[g] = gain_ptr ? gain_ptr[s] : nullptr;
-    a.G[g] = G[s]; a.dw[g] = dw[s]; a.dgain[g] = dgain ? dgain[s] : nullptr;
-    a.kh[g] = kh[s]; a.kw[g] = kw[s];
-  }
+  conv_fill_groups(a.w_raw, w_raw, ngroups); conv_fill_groups(a.gain_ptr, gain_ptr, ngroups);
+  conv_fill_groups(a.G, G, ngroups); conv_fill_groups(a.dw, dw, ngroups); conv_fill_groups(a.dgain, dgain, ngroups);
+  conv_fill_groups(a.kh, kh, ngroups); conv_fill_groups(a.kw, kw, ngroups);
   a.O = O; a.I = I; a.gain_val = gain_val; a.normalize = normalize;
   hipLaunchKernelGGL(wprep_bwd_kernel, dim3(O, ngroups), dim3(128), 0, stream, a);
   return hdmoe_launch_status();
@@ -1249,124 +1457,35 @@ int hdmoe_conv_fwd(const void* x, const void* w, void* y, const void* res, float
   if (!x || !w || !y || N < 0 || ngroups < 1 || ngroups > HDMOE_MAX_GROUPS) return HDMOE_EINVAL;
   if (Ipad % 16 || Ipad < Cin || Cin != Cphys + (ones ? 1 : 0) || Cstore > Cout || stride < 1) return HDMOE_EINVAL;
   if (N == 0 || Ho * Wo == 0) return HDMOE_OK;
-  ConvArgs a;
-  a.x = x; a.w = w; a.y = y; a.res = res; a.seg = seg; a.wstride = wstride;
-  a.N = N; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.Cin = Cin; a.Cphys = Cphys; a.Ipad = Ipad; a.Cout = Cout;
-  a.Cstore = Cstore; a.stride = stride; a.ones = ones; a.ngroups = ngroups; a.alpha = alpha; a.beta = beta; a.n0 = 0;
-  for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) {
-    const int s = g < ngroups ? g : 0;
-    a.kh[g] = kh[s]; a.kw[g] = kw[s]; a.pt[g] = pt[s]; a.pl[g] = pl[s];
-  }
+  const ConvArgs a = conv_fwd_args(x, w, y, res, alpha, beta, seg, ngroups, wstride, N, H, W, Ho, Wo, Cin, Cphys, Ipad, Cout, Cstore, stride, ones,
+                                   kh, kw, pt, pl);
   if (dtype == HDMOE_F32S) {                               // fp32 tensors on the bf16 pipe (conv6s.hip); callers check the domain first
     const int rc = conv6_split_try_launch(a, (long)ngroups * wstride, nullptr, stream);
     return rc == 1 ? HDMOE_EINVAL : rc;
   }
   if (dtype != HDMOE_F32 && dtype != HDMOE_BF16) return HDMOE_EDTYPE;
-  {                                                        // k x k expert layers on 32 x 32 maps: whole-image streaming kernel (conv7.hip)
-    const int rc = conv7_try_launch(a, dtype, stream);
-    if (rc <= 0) return rc;
-  }
-  {                                                        // k x k layers of the experts / trunks: persistent LDS-DMA kernel (conv6.hip)
-    const int rc = conv6_try_launch(a, nullptr, dtype, stream);
-    if (rc <= 0) return rc;
-  }
-  {                                                        // pointwise, long contraction, few outputs (kgemm.hip)
-    const int rc = kgemm_try_launch(a, dtype, stream);
-    if (rc <= 0) return rc;
-  }
-  {                                                        // grouped fp32 linear on one-position rows, long input (mlinear.hip)
-    const int rc = glin_try_launch(a, dtype, stream);
-    if (rc <= 0) return rc;
-  }
-  if (stride == 1 && (long)Ho * Wo >= 64) {
-    // ---- v2: LDS-staged 256-pixel tiles
-    const int PT = 4 * CV2_MT * 32;
-    int maxkh = 1, maxkw = 1;
-    for (int g = 0; g < ngroups; ++g) { if (kh[g] > maxkh) maxkh = kh[g]; if (kw[g] > maxkw) maxkw = kw[g]; }
-    const int esz = dtype == HDMOE_BF16 ? 2 : 4;
-    const bool v5ok = !ones && Cstore % 4 == 0 && (uintptr_t)y % 16 == 0 && (uintptr_t)res % 16 == 0 && (uintptr_t)w % 16 == 0;
-    // Tile = whole image rows, or (v5 only, images wider than 32 with a real kernel window) 8 x 32 blocks: a 4 x 64 tile of a
-    // 7x7 layer needs a 10 x 70 halo, the 8 x 32 block 14 x 38.  tile2d != 0 tells the kernel the tile is not a linear pixel run.
-    const int NTq = Cstore <= 32 ? 1 : 2;
-    const bool vecq = Cphys % (16 / esz) == 0 && (uintptr_t)x % 16 == 0;
-    // (only when the v5 launch below is certain: the older kernels assume linear tiles)
-    const bool tile2d = v5ok && vecq && Ho >= 8 && Wo > 32 && Wo % 32 == 0 && maxkh * maxkw > 1 &&
-                        (8 + maxkh - 1) * (32 + maxkw - 1) * 4 <= 9 * 256 && maxkw * 32 * NTq <= 576 &&
-                        (long)maxkh * maxkw * Cout * Ipad < (1l << 26) && (long)H * W * Cphys < (1l << 30) &&
-                        (size_t)80 * ((8 + maxkh - 1) * (32 + maxkw - 1) + maxkw * 32 * NTq) <= 80 * 1024;
-    const int TW = tile2d ? 32 : (Wo < PT ? Wo : PT);
-    int TH = PT / TW; if (TH > Ho) TH = Ho; if (TH < 1) TH = 1;
-    const int tiles_y = cdiv(Ho, TH), tiles_x = cdiv(Wo, TW);
-    const int NT = Cstore <= 32 ? 1 : 2;
-    const int halo_cap = (TH + maxkh - 1) * (TW + maxkw - 1);
-    const size_t lds = (size_t)80 * (halo_cap + maxkw * 32 * NT);
-    const bool vec = Cphys % (16 / esz) == 0 && (uintptr_t)x % 16 == 0;
-    dim3 grid(tiles_y * tiles_x, N, cdiv(Cstore, 32 * NT));
-    // v5 / v3 (register prefetch): rows of weights per stage <= 576 (9 chunks/thread); halo <= 448 px (7 chunks/thread), or for
-    // v5 <= 576 px (9 chunks/thread: 7x7 experts, whose halo of a 256-pixel tile is 14 x 38 or 22 x 22 pixels)
-    const int halo_max = v5ok ? 9 * 256 : 7 * 256;
-    if (vec && halo_cap * 4 <= halo_max && maxkw * 32 * NT <= 576 && (long)maxkh * maxkw * Cout * Ipad < (1l << 26) &&
-        (long)H * W * Cphys < (1l << 30) &&
-        (long)halo_cap * (TW + maxkw - 1) < (1l << 20)) {   // the kernels' (px * magic) >> 20 halo decode is exact while px * HWp < 2^20
-      // a workgroup may use up to 80 KB of LDS under v5 (two still share a CU): needed by 7x7 experts with 64-channel tiles
-      const size_t cap = v5ok ? 80 * 1024 : 64 * 1024;
-      int tg = 576 / (maxkw * 32 * NT);
-      if (tg > maxkh) tg = maxkh;
-      while (tg > 1 && (size_t)80 * (halo_cap + tg * maxkw * 32 * NT) > 64 * 1024) --tg;       // prefer <= 64 KB
-      const size_t lds3 = (size_t)80 * (halo_cap + tg * maxkw * 32 * NT);
-      if (lds3 <= cap && v5ok) {
-        static unsigned long long attr_set = 0;
-        if (hdmoe_first_on_device(attr_set)) {               // opt every instantiation into > 64 KB of dynamic LDS, once per device
-#define CV5_ATTR(TT, NTv, L, H) (void)hipFuncSetAttribute((const void*)conv_fwd5_kernel<TT, NTv, L, H>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024)
-#define CV5_ATTR4(TT, NTv) CV5_ATTR(TT, NTv, true, 7); CV5_ATTR(TT, NTv, false, 7); CV5_ATTR(TT, NTv, true, 9); CV5_ATTR(TT, NTv, false, 9)
-          CV5_ATTR4(float, 1); CV5_ATTR4(float, 2); CV5_ATTR4(bf16, 1); CV5_ATTR4(bf16, 2);
-        }
-        // LDS-transposed epilogue needs whole 16-B pieces per pixel and a slab of 4 waves x 32 px x (32 NT + pad) elements
-        const bool lepi = Cstore % (16 / esz) == 0 && (size_t)4 * 32 * (32 * NT + 16 / esz) * esz <= lds3;
-        const bool big_halo = halo_cap * 4 > 7 * 256;
-        const int nblk5 = (int)cdiv(Cstore, 32 * NT), ntiles5 = tiles_y * tiles_x;
-        const int tg5 = tg | (tile2d ? 1 << 16 : 0) | (nblk5 << 17);     // bit 16: 8 x 32 block tiles; bits 17-30: channel blocks
-        if (nblk5 > 0x3FFF) return HDMOE_EINVAL;
-        const long npairs = (long)N * ntiles5;
-        const dim3 grid5((unsigned)(8 * ((npairs + 7) / 8) * nblk5));
-#define CV5_LAUNCH(TT, NTv)                                                                                                                        \
-  do { if (lepi && !big_halo) hipLaunchKernelGGL((conv_fwd5_kernel<TT, NTv, true, 7>), grid5, dim3(256), lds3, stream, a, TH, TW, tiles_x, halo_cap, tg5, ntiles5);   \
-       else if (!big_halo) hipLaunchKernelGGL((conv_fwd5_kernel<TT, NTv, false, 7>), grid5, dim3(256), lds3, stream, a, TH, TW, tiles_x, halo_cap, tg5, ntiles5); \
-       else if (lepi) hipLaunchKernelGGL((conv_fwd5_kernel<TT, NTv, true, 9>), grid5, dim3(256), lds3, stream, a, TH, TW, tiles_x, halo_cap, tg5, ntiles5);       \
-       else hipLaunchKernelGGL((conv_fwd5_kernel<TT, NTv, false, 9>), grid5, dim3(256), lds3, stream, a, TH, TW, tiles_x, halo_cap, tg5, ntiles5); } while (0)
-        if (dtype == HDMOE_F32) { if (NT == 1) CV5_LAUNCH(float, 1); else CV5_LAUNCH(float, 2); }
-        else { if (NT == 1) CV5_LAUNCH(bf16, 1); else CV5_LAUNCH(bf16, 2); }
-        return hdmoe_launch_status();
-      }
-      if (lds3 <= 64 * 1024 && halo_cap * 4 <= 7 * 256) {
-        for (int n0 = 0; n0 < N; n0 += ROWS_PER_LAUNCH) {
-          a.n0 = n0; grid.y = N - n0 < ROWS_PER_LAUNCH ? N - n0 : ROWS_PER_LAUNCH;
-          if (dtype == HDMOE_F32) {
-            if (NT == 1) hipLaunchKernelGGL((conv_fwd3_kernel<float, 1>), grid, dim3(256), lds3, stream, a, TH, TW, tiles_x, halo_cap, tg);
-            else hipLaunchKernelGGL((conv_fwd3_kernel<float, 2>), grid, dim3(256), lds3, stream, a, TH, TW, tiles_x, halo_cap, tg);
-          } else {
-            if (NT == 1) hipLaunchKernelGGL((conv_fwd3_kernel<bf16, 1>), grid, dim3(256), lds3, stream, a, TH, TW, tiles_x, halo_cap, tg);
-            else hipLaunchKernelGGL((conv_fwd3_kernel<bf16, 2>), grid, dim3(256), lds3, stream, a, TH, TW, tiles_x, halo_cap, tg);
-          }
-        }
-        return hdmoe_launch_status();
-      }
-    }
-    if (lds <= 64 * 1024 && grid.x <= 65535 * 32) {
-#define CV2_LAUNCH(TT, NTv)                                                                                                   \
-  do { if (vec) hipLaunchKernelGGL((conv_fwd2_kernel<TT, NTv, true>), grid, dim3(256), lds, stream, a, TH, TW, tiles_x, halo_cap);  \
-       else hipLaunchKernelGGL((conv_fwd2_kernel<TT, NTv, false>), grid, dim3(256), lds, stream, a, TH, TW, tiles_x, halo_cap); } while (0)
-      for (int n0 = 0; n0 < N; n0 += ROWS_PER_LAUNCH) {
-        a.n0 = n0; grid.y = N - n0 < ROWS_PER_LAUNCH ? N - n0 : ROWS_PER_LAUNCH;
-        if (dtype == HDMOE_F32) { if (NT == 1) CV2_LAUNCH(float, 1); else CV2_LAUNCH(float, 2); }
-        else { if (NT == 1) CV2_LAUNCH(bf16, 1); else CV2_LAUNCH(bf16, 2); }
-      }
-      return hdmoe_launch_status();
-    }
-  }
-  if (dtype == HDMOE_F32) launch_conv_nb<float>(a, Cphys % 4 == 0 && ((uintptr_t)x % 16 == 0), stream);
-  else launch_conv_nb<bf16>(a, Cphys % 8 == 0 && ((uintptr_t)x % 16 == 0), stream);
+  int rc = conv7_try_launch(a, dtype, stream);               // k x k expert layers on 32 x 32 maps: whole-image streaming kernel (conv7.hip)
+  if (rc > 0) rc = conv6_try_launch(a, nullptr, dtype, stream);   // k x k layers of the experts / trunks: persistent LDS-DMA kernel (conv6.hip)
+  if (rc > 0) rc = kgemm_try_launch(a, dtype, stream);       // pointwise, long contraction, few outputs (kgemm.hip)
+  if (rc > 0) rc = glin_try_launch(a, dtype, stream);        // grouped fp32 linear on one-position rows, long input (mlinear.hip)
+  if (rc <= 0) return rc;
+  CvPlan p;
+  if ((rc = conv_fwd_plan(a, dtype, p))) return rc;
+  if (p.kernel == HDMOE_ROUTE_CONV_FWD5) conv_fwd5_lds_attr();
+  conv_fwd_launch(a, dtype, p, stream);
   return hdmoe_launch_status();
+}
+
+int hdmoe_conv_generic_route(int* route, int N, int H, int W, int Ho, int Wo, int Cin, int Cphys, int Ipad, int Cout, int Cstore, int stride,
+                             int ones, int ngroups, const int* kh, const int* kw, int dtype, int aligned16) {
+  if (!route || ngroups < 1 || ngroups > HDMOE_MAX_GROUPS || (dtype != HDMOE_F32 && dtype != HDMOE_BF16)) return HDMOE_EINVAL;
+  const void* ptr = (const void*)(uintptr_t)(aligned16 ? 16 : 4);   // stands for every tensor of the call; never dereferenced
+  const ConvArgs a = conv_fwd_args(ptr, ptr, (void*)ptr, ptr, 1.f, 0.f, nullptr, ngroups, 0, N, H, W, Ho, Wo, Cin, Cphys, Ipad, Cout, Cstore, stride,
+                                   ones, kh, kw, kh, kw);           // (the pads do not enter the plan)
+  CvPlan p;
+  if (const int rc = conv_fwd_plan(a, dtype, p)) return rc;
+  route[0] = p.kernel; route[1] = p.NT; route[2] = p.vec; route[3] = p.lepi; route[4] = p.NHR;
+  return HDMOE_OK;
 }
 
 int hdmoe_conv_wgrad(const void* x, const void* dy, float* const* G, const int* seg, int ngroups, int N, int H,
@@ -1374,136 +1493,49 @@ int hdmoe_conv_wgrad(const void* x, const void* dy, float* const* G, const int* 
                      const int* kw, const int* pt, const int* pl, int dtype, hipStream_t stream) {
   if (!x || !dy || !G || ngroups < 1 || ngroups > HDMOE_MAX_GROUPS || Cin != Cphys + (ones ? 1 : 0)) return HDMOE_EINVAL;
   if (N == 0 || Ho * Wo == 0) return HDMOE_OK;
-  WgradArgs a;
-  a.x = x; a.dy = dy; a.seg = seg; a.N = N; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.Cin = Cin; a.Cphys = Cphys;
-  a.Cout = Cout; a.stride = stride; a.ones = ones; a.ngroups = ngroups;
-  int maxtaps = 0;
-  for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) {
-    const int s = g < ngroups ? g : 0;
-    a.G[g] = G[s]; a.kh[g] = kh[s]; a.kw[g] = kw[s]; a.pt[g] = pt[s]; a.pl[g] = pl[s];
-    if (kh[s] * kw[s] > maxtaps) maxtaps = kh[s] * kw[s];
+  WgradArgs a = wgrad_args(x, dy, G, seg, ngroups, N, H, W, Ho, Wo, Cin, Cphys, Cout, stride, ones, kh, kw, pt, pl);
+  int rc;
+  if (wgrad_try_siblings(a, dtype, stream, false, rc) >= 0) return rc;
+  Wg2Plan p;
+  if (wg2_plan(p, a, dtype, (((uintptr_t)x | (uintptr_t)dy) & 15) == 0)) {
+    wg2_launch(a, p, dtype, stream);
+    return hdmoe_launch_status();
   }
-  a.tap_lo = 0;
-  if (stride == 1 && !ones && ngroups == 1 && !seg && Ho == H && Wo == W && kh[0] == kw[0] && maxtaps > 1 && maxtaps * Cin <= 64 &&
-      pt[0] == (kh[0] - 1) / 2 && pl[0] == (kw[0] - 1) / 2) {
-    const int rc = swg_try_launch(x, dy, G[0], N, H, W, Cin, Cout, kh[0], pt[0], pl[0], dtype, stream);
-    if (rc <= 0) return rc;
-  }
-  if (stride == 1 && !ones && ngroups == 1 && !seg && Ho == H && Wo == W && kh[0] == kw[0] && Cout <= 4) {
-    const int rc = towg_try_launch(x, dy, G[0], N, H, W, Cin, Cout, kh[0], pt[0], pl[0], dtype, stream);
-    if (rc <= 0) return rc;
-  }
-  if (stride == 1 && !ones && maxtaps == 1 && Ho == H && Wo == W) {
-    bool plain = true;
-    for (int g = 0; g < ngroups; ++g) plain = plain && kh[g] == 1 && kw[g] == 1 && pt[g] == 0 && pl[g] == 0;
-    if (plain) {
-      const int rc = lwg_try_launch(x, dy, G, seg, ngroups, N, (long)H * W, Cin, Cout, dtype, stream);
-      if (rc <= 0) return rc;
-    }
-  }
-  if (stride == 1) {
-    // ---- v2: LDS-staged tiles of TH rows x TW columns (TH * TW <= 128 pixels); one launch per kernel-size class so the
-    //      per-wave accumulator count (MAXT) matches the class (3x3 -> 3, 5x5 -> 7, 7x7 -> 13)
-    Wg2Geom gm;
-    const int PTpx = dtype == HDMOE_F32 ? Wg2PT<float>::N : Wg2PT<bf16>::N;
-    // near-square tiles keep the halo small (a 2 x 64 tile of a 7x7 layer needs 8 x 70 halo pixels, a 4 x 32 tile 10 x 38);
-    // single-row tensors (flattened token rows) take the whole tile width
-    const int tw_cap = Ho == 1 ? PTpx : 32;
-    gm.TW = Wo < tw_cap ? Wo : tw_cap;
-    gm.TH = PTpx / gm.TW; if (gm.TH > Ho) gm.TH = Ho; if (gm.TH < 1) gm.TH = 1;
-    gm.tw_shift = -1;
-    for (int sft = 0; sft < 8; ++sft) if ((1 << sft) == gm.TW) gm.tw_shift = sft;
-    gm.tiles_y = cdiv(Ho, gm.TH); gm.tiles_x = cdiv(Wo, gm.TW);
-    const long units_l = (long)N * gm.tiles_y * gm.tiles_x;
-    const int esz = dtype == HDMOE_BF16 ? 2 : 4;
-    const int vw = 16 / esz;
-    bool done[HDMOE_MAX_GROUPS] = {false};
-    bool ok = units_l < (1l << 30) && (dtype == HDMOE_F32 || dtype == HDMOE_BF16);
-    // feasibility of every class first (fall back to v1 as a whole otherwise)
-    for (int g = 0; g < ngroups && ok; ++g) {
-      const int taps = kh[g] * kw[g];
-      const int passes = taps > 28 ? (taps + 27) / 28 : 1;
-      const int mt = passes > 1 ? 7 : (taps < 4 ? taps : (taps + 3) / 4);
-      const int OT = ((passes == 1 && mt > 7) || Cout <= 32) ? 1 : 2;
-      const int OBP = (OT == 2 && esz == 2) ? 96 : 32 * OT;
-      const size_t lds = (size_t)esz * (PTpx * OBP + (gm.TH + kh[g] - 1) * (gm.TW + kw[g] - 1) * WG2_IB);
-      if (lds > 64 * 1024 || mt > 13) ok = false;
-      // the kernel decodes halo pixels with (px * magic) >> 20, exact only while px * HWp < 2^20 (px < HHp * HWp)
-      const long HWp = gm.TW + kw[g] - 1, HHp = gm.TH + kh[g] - 1;
-      if (HHp * HWp * HWp >= (1l << 20)) ok = false;
-    }
-    if (ok) {
-      for (int g = 0; g < ngroups; ++g) {
-        if (done[g]) continue;
-        gm.ngr = 0;
-        for (int g2 = g; g2 < ngroups; ++g2)
-          if (!done[g2] && kh[g2] == kh[g] && kw[g2] == kw[g]) { gm.groups[gm.ngr++] = g2; done[g2] = true; }
-        const int taps = kh[g] * kw[g];
-        // 13 accumulator sets per wave (7x7) do not fit the register file (the MAXT = 13 instantiation spills ~250 VGPRs):
-        // such classes run as ceil(taps / 28) passes of the 7-set kernel over tap ranges (the tiles are staged once per pass)
-        const int passes = taps > 28 ? (taps + 27) / 28 : 1;
-        const int mt = passes > 1 ? 7 : (taps < 4 ? taps : (taps + 3) / 4);
-        const int OT = ((passes == 1 && mt > 7) || Cout <= 32) ? 1 : 2;
-        const int OB = 32 * OT, OBP = (OT == 2 && esz == 2) ? OB + 32 : OB;
-        const int halo = (gm.TH + kh[g] - 1) * (gm.TW + kw[g] - 1);
-        const size_t lds = (size_t)esz * (PTpx * OBP + halo * WG2_IB);
-        const int nx_cap = (esz == 2 ? 6 : 8) * 256;                    // register-prefetch capacity (16-B halo chunks)
-        const bool vec = Cout % vw == 0 && Cphys % vw == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)dy % 16 == 0 &&
-                         halo * (WG2_IB / vw) <= nx_cap;
-        const int ibs = cdiv(Cin, WG2_IB), obs = cdiv(Cout, OB);
-        // every workgroup ends with an atomic flush of its [taps][OB][32] accumulators; the flush traffic is
-        // (pixel partitions) x (weight bytes) at ~1.3 TB/s, so keep the partition count near 256 / (ibs * obs) per launch
-        // Every workgroup ends with an fp32 atomic flush of its [taps][OB][32] accumulators (~1.3 TB/s chip-wide), so the
-        // flush traffic is (pixel partitions) x (weight bytes).  fp32 units are long (64-cycle MFMAs): fill the chip exactly
-        // once.  bf16 units are short and the flush dominates: fewer, longer workgroups measured best (launch_table sweeps).
-        long upw;
-        if (esz == 4) {
-            long parts = 512 / ((long)ibs * obs); if (parts < 8) parts = 8;
-            const long class_units = (units_l * gm.ngr + ngroups - 1) / ngroups;   // assume balanced routing
-            upw = (class_units + parts - 1) / parts;
-        } else {
-            // classes with more than 9 taps flush (taps x 64 x 32) floats per workgroup: fewer, longer workgroups (bench sweep:
-            // 384 -> 256 partitions = -0.7 ms/step at B = 256)
-            long parts = (taps > 9 ? 256 : 384) / ((long)ibs * obs); if (parts < 8) parts = 8;
-            upw = (units_l + parts - 1) / parts;
-        }
-        if (upw < 1) upw = 1;
-        gm.upw = (int)upw;
-        gm.chunks = (int)((units_l + upw - 1) / upw);
-        dim3 grid(ibs, obs, gm.chunks * gm.ngr);
-#define WG2_LAUNCH(TT, OTv, MT)                                                                                           \
-  do { if (vec) hipLaunchKernelGGL((conv_wgrad2_kernel<TT, OTv, MT, true>), grid, dim3(256), lds, stream, a, gm);          \
-       else hipLaunchKernelGGL((conv_wgrad2_kernel<TT, OTv, MT, false>), grid, dim3(256), lds, stream, a, gm); } while (0)
-#define WG2_BY_MT(TT, OTv)                                          \
-  if (mt <= 3) WG2_LAUNCH(TT, OTv, 3);                               \
-  else if (mt <= 7) WG2_LAUNCH(TT, OTv, 7);                          \
-  else WG2_LAUNCH(TT, OTv, 13);
-        for (int pass = 0; pass < passes; ++pass) {
-          a.tap_lo = 28 * pass;
-          if (dtype == HDMOE_F32) { if (OT == 2) { WG2_BY_MT(float, 2) } else { WG2_BY_MT(float, 1) } }
-          else { if (OT == 2) { WG2_BY_MT(bf16, 2) } else { WG2_BY_MT(bf16, 1) } }
-        }
-        a.tap_lo = 0;
-      }
-      return hdmoe_launch_status();
-    }
-  }
+  // ---- conv_wgrad_kernel: one workgroup per (tap, channel-block pair), the samples split over blockIdx.y
   const int cpl = dtype == HDMOE_BF16 ? 2 : 1;
   a.ob_count = cdiv(Cout, 32 * cpl);
   a.ib_count = cdiv(Cin, 32 * cpl);
-  const long tiles = (long)maxtaps * a.ob_count * a.ib_count;
+  const long tiles = (long)wgrad_max_taps(a) * a.ob_count * a.ib_count;
   // samples per wave: keep >= ~2048 waves in flight, but at least 1 and at most 16 samples per wave
   long spw = ((long)N * tiles) / 2048;
   if (spw < 1) spw = 1;
   if (spw > 16) spw = 16;
   a.spw = (int)spw;
   dim3 grid((unsigned)tiles, cdiv(N, 4 * spw));
-  if (dtype == HDMOE_F32) hipLaunchKernelGGL(conv_wgrad_kernel<float>, grid, dim3(256), 0, stream, a);
-  else if (dtype == HDMOE_BF16) hipLaunchKernelGGL(conv_wgrad_kernel<bf16>, grid, dim3(256), 0, stream, a);
-  else return HDMOE_EDTYPE;
+  if (dtype != HDMOE_F32 && dtype != HDMOE_BF16) return HDMOE_EDTYPE;
+  conv_pick_dtype(dtype, [&](auto t) { hipLaunchKernelGGL(conv_wgrad_kernel<decltype(t)>, grid, dim3(256), 0, stream, a); });
   return hdmoe_launch_status();
 }
 
+int hdmoe_conv_wgrad_route(int* route, int N, int H, int W, int Ho, int Wo, int Cin, int Cphys, int Cout, int stride, int ones, int ngroups,
+                           int has_seg, const int* kh, const int* kw, const int* pt, const int* pl, int dtype, int aligned16) {
+  if (!route || ngroups < 1 || ngroups > HDMOE_MAX_GROUPS || Cin != Cphys + (ones ? 1 : 0)) return HDMOE_EINVAL;
+  if (dtype != HDMOE_F32 && dtype != HDMOE_BF16) return HDMOE_EDTYPE;
+  float* const ptr = (float*)(uintptr_t)(aligned16 ? 16 : 4);       // stands for every tensor of the call; never dereferenced
+  float* const G[HDMOE_MAX_GROUPS] = {ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr};
+  const WgradArgs a = wgrad_args(ptr, ptr, G, has_seg ? (const int*)ptr : nullptr, ngroups, N, H, W, Ho, Wo, Cin, Cphys, Cout, stride, ones, kh, kw, pt, pl);
+  Wg2Plan p;
+  int rc;
+  route[1] = 0;
+  if ((route[0] = wgrad_try_siblings(a, dtype, nullptr, true, rc)) >= 0) return HDMOE_OK;
+  if (!wg2_plan(p, a, dtype, aligned16 != 0)) { route[0] = HDMOE_ROUTE_WGRAD_V1; return HDMOE_OK; }
+  route[0] = HDMOE_ROUTE_WGRAD_V2; route[1] = p.nclasses;
+  for (int k = 0; k < p.nclasses; ++k) {
+    const Wg2ClassPlan& c = p.cls[k];
+    route[2 + 4 * k] = c.passes; route[3 + 4 * k] = c.MAXT; route[4 + 4 * k] = c.OT; route[5 + 4 * k] = c.vec;
+  }
+  return HDMOE_OK;
+}
 
 /* Grouped k x k bf16 conv (the conv6 domain: stride 1, "same" padding, square k in {3,5,7}, Cin % 32 == Cout % 32 == 0) with the FiLM of
  * Unet_block fused into its epilogue (reference model_components.py:242-246): y = alpha * conv(x, w) as hdmoe_conv_fwd, and
@@ -1515,14 +1547,7 @@ int hdmoe_conv_fwd_film(const void* x, const void* w, void* y, void* h, const fl
   if (!x || !w || !y || !h || !e || N < 0 || ngroups < 1 || ngroups > HDMOE_MAX_GROUPS || p < 0.f || p >= 1.f) return HDMOE_EINVAL;
   if (dtype != HDMOE_BF16) return 1;
   if (N == 0) return HDMOE_OK;
-  ConvArgs a;
-  a.x = x; a.w = w; a.y = y; a.res = nullptr; a.seg = seg; a.wstride = wstride;
-  a.N = N; a.H = H; a.W = W; a.Ho = H; a.Wo = W; a.Cin = Cin; a.Cphys = Cin; a.Ipad = Cin; a.Cout = Cout; a.Cstore = Cout;
-  a.stride = 1; a.ones = 0; a.ngroups = ngroups; a.alpha = alpha; a.beta = 0.f; a.n0 = 0;
-  for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) {
-    const int s = g < ngroups ? g : 0;
-    a.kh[g] = kh[s]; a.kw[g] = kw[s]; a.pt[g] = pt[s]; a.pl[g] = pl[s];
-  }
+  const ConvArgs a = conv_fwd_args(x, w, y, nullptr, alpha, 0.f, seg, ngroups, wstride, N, H, W, H, W, Cin, Cin, Cin, Cout, Cout, 1, 0, kh, kw, pt, pl);
   ConvFuse f;
   f.in_scale = nullptr; f.in_shift = nullptr; f.stats = nullptr; f.in_relu = 0;
   f.film_e = e; f.film_h = h; f.film_seed_dev = seed_dev; f.film_seed = seed; f.film_p = p;
@@ -1542,11 +1567,8 @@ int hdmoe_conv_split_stats_slots(int H, int W, int Cout) {
 int hdmoe_conv_fwd_split_gn(const void* x, const void* w, void* y, const float* in_scale, const float* in_shift, int in_relu, float* stats_ws,
                             long wstride, long wplane, int N, int H, int W, int Cin, int Cout, float alpha, hipStream_t stream) {
   if (!x || !w || !y || (in_scale == nullptr) != (in_shift == nullptr)) return HDMOE_EINVAL;
-  ConvArgs a;
-  a.x = x; a.w = w; a.y = y; a.res = nullptr; a.seg = nullptr; a.wstride = wstride;
-  a.N = N; a.H = H; a.W = W; a.Ho = H; a.Wo = W; a.Cin = Cin; a.Cphys = Cin; a.Ipad = Cin; a.Cout = Cout; a.Cstore = Cout;
-  a.stride = 1; a.ones = 0; a.ngroups = 1; a.alpha = alpha; a.beta = 0.f; a.n0 = 0;
-  for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) { a.kh[g] = 3; a.kw[g] = 3; a.pt[g] = 1; a.pl[g] = 1; }
+  const int k3 = 3, p1 = 1;
+  const ConvArgs a = conv_fwd_args(x, w, y, nullptr, alpha, 0.f, nullptr, 1, wstride, N, H, W, H, W, Cin, Cin, Cin, Cout, Cout, 1, 0, &k3, &k3, &p1, &p1);
   ConvFuse f;
   f.in_scale = in_scale; f.in_shift = in_shift; f.in_relu = in_relu; f.stats = stats_ws;
   return conv6_split_try_launch(a, wplane, &f, stream);

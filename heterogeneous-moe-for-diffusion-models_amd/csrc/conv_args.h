@@ -25,10 +25,16 @@ static inline bool conv_align_extent_ok(std::initializer_list<const void*> ptrs,
   for (long e : extents) if (e >= (1l << 31)) return false;
   return true;
 }
-// Template dispatch: f(std::integral_constant<int, A>) when v == A, else f(std::integral_constant<int, B>) -- a plan's run-time integer
+// Template dispatch: f(std::integral_constant<int, A>) for the first listed A == v, else for the last one -- a plan's run-time integer
 // becomes a template argument; nest one call per parameter.
-template <int A, int B, typename F> static inline void conv_pick(int v, F&& f) {
-  if (v == A) f(std::integral_constant<int, A>{}); else f(std::integral_constant<int, B>{});
+template <int A, int... Rest, typename F> static inline void conv_pick(int v, F&& f) {
+  if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<int, A>{});
+  else if (v == A) f(std::integral_constant<int, A>{});
+  else conv_pick<Rest...>(v, f);
+}
+// The same for the element type: f(float{}) for HDMOE_F32, else f(bf16{}) (the caller has checked the dtype code)
+template <typename F> static inline void conv_pick_dtype(int dtype, F&& f) {
+  if (dtype == HDMOE_F32) f(float{}); else f(bf16{});
 }
 // order[] = the groups by descending kernel size (longest units first; stable)
 static inline void conv_sort_groups_desc(const int* ks, int* order, int ngroups) {
@@ -50,20 +56,41 @@ static inline int conv_pick_stage_T(int ngroups, const int* ks, int pieces_per_t
   }
   return best;
 }
-// The input gradient of a stride-1 k x k layer as a forward conv over dy with the flipped weight image wd [g][tap][Cin][Cout]: the
-// channel counts swap and the pads flip (k - 1 - p).  Cin / Cout are the layer's; groups past ngroups repeat group 0.
-static inline ConvArgs conv_dgrad_args(const void* dy, const void* wd, void* dx, const int* seg, int ngroups, long wd_stride, int N, int H, int W,
-                                       int Cin, int Cout, const int* kh, const int* kw, const int* pt, const int* pl, float alpha) {
+// dst[0 .. HDMOE_MAX_GROUPS) = the per-group host array src[0 .. ngroups) (null: zeros); groups past ngroups repeat group 0
+template <typename T> static inline void conv_fill_groups(T* dst, const T* src, int ngroups) {
+  for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) dst[g] = src ? src[g < ngroups ? g : 0] : T{};
+}
+// The argument block of one forward launch (n0 = 0); kh / kw / pt / pl are host arrays of ngroups entries.
+static inline ConvArgs conv_fwd_args(const void* x, const void* w, void* y, const void* res, float alpha, float beta, const int* seg, int ngroups,
+                                     long wstride, int N, int H, int W, int Ho, int Wo, int Cin, int Cphys, int Ipad, int Cout, int Cstore,
+                                     int stride, int ones, const int* kh, const int* kw, const int* pt, const int* pl) {
   ConvArgs c;
-  c.x = dy; c.w = wd; c.y = dx; c.res = nullptr; c.seg = seg; c.wstride = wd_stride;
-  c.N = N; c.H = H; c.W = W; c.Ho = H; c.Wo = W; c.Cin = Cout; c.Cphys = Cout; c.Ipad = Cout; c.Cout = Cin; c.Cstore = Cin;
-  c.stride = 1; c.ones = 0; c.ngroups = ngroups; c.n0 = 0; c.alpha = alpha; c.beta = 0.f;
-  for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) {
-    const int s = g < ngroups ? g : 0;
-    c.kh[g] = kh[s]; c.kw[g] = kw[s]; c.pt[g] = kh[s] - 1 - pt[s]; c.pl[g] = kw[s] - 1 - pl[s];
-  }
+  c.x = x; c.w = w; c.y = y; c.res = res; c.seg = seg; c.wstride = wstride;
+  c.N = N; c.H = H; c.W = W; c.Ho = Ho; c.Wo = Wo; c.Cin = Cin; c.Cphys = Cphys; c.Ipad = Ipad; c.Cout = Cout; c.Cstore = Cstore;
+  c.stride = stride; c.ones = ones; c.ngroups = ngroups; c.n0 = 0; c.alpha = alpha; c.beta = beta;
+  conv_fill_groups(c.kh, kh, ngroups); conv_fill_groups(c.kw, kw, ngroups); conv_fill_groups(c.pt, pt, ngroups); conv_fill_groups(c.pl, pl, ngroups);
   return c;
 }
+// The input gradient of a stride-1 k x k layer as a forward conv over dy with the flipped weight image wd [g][tap][Cin][Cout]: the
+// channel counts swap and the pads flip (k - 1 - p).  Cin / Cout are the layer's.
+static inline ConvArgs conv_dgrad_args(const void* dy, const void* wd, void* dx, const int* seg, int ngroups, long wd_stride, int N, int H, int W,
+                                       int Cin, int Cout, const int* kh, const int* kw, const int* pt, const int* pl, float alpha) {
+  int fpt[HDMOE_MAX_GROUPS], fpl[HDMOE_MAX_GROUPS];
+  for (int g = 0; g < ngroups; ++g) { fpt[g] = kh[g] - 1 - pt[g]; fpl[g] = kw[g] - 1 - pl[g]; }
+  return conv_fwd_args(dy, wd, dx, nullptr, alpha, 0.f, seg, ngroups, wd_stride, N, H, W, H, W, Cout, Cout, Cout, Cin, Cin, 1, 0, kh, kw, fpt, fpl);
+}
+
+// Launch plan of the generic forward kernels (conv.hip): what hdmoe_conv_fwd launches when none of the specialised kernels below takes
+// the layer.  conv_fwd_plan is pure (no HIP calls); HDMOE_EINVAL when the layer has more channel blocks than conv_fwd5 can address.
+struct CvPlan {
+  int kernel;                                  // HDMOE_ROUTE_CONV_FWD / _FWD2 / _FWD3 / _FWD5
+  int NT;                                      // 32-channel tiles per workgroup (conv_fwd_kernel: its NB = 1, 2 or 4)
+  int vec, lepi, NHR;                          // 16-byte input loads; fwd5: LDS-transposed epilogue, halo chunks per thread (7 or 9)
+  int TH, TW, tiles_x, halo_cap, tg, ntiles;   // tile geometry; tg = kernel rows per weight stage (fwd5: its tg_flags word)
+  dim3 grid;                                   // (grid.y = N: the row-per-blockIdx.y kernels run 65535 rows per launch)
+  size_t lds;
+};
+int conv_fwd_plan(const ConvArgs& a, int dtype, CvPlan& p);
 
 // Fused pro-/epilogue of the conv6 kernels (all optional):
 //   in_scale/in_shift [N][Cin] fp32 + in_relu: the staged input is relu(x * scale[n][c] + shift[n][c]) -- GroupNorm(1,C) + ReLU of the
@@ -92,19 +119,20 @@ int conv7_try_launch(const ConvArgs& a, int dtype, hipStream_t stream);
 int conv6_split_try_launch(const ConvArgs& a, long wplane_elems, const ConvFuse* fuse, hipStream_t stream);
 
 // Pointwise (linear / 1x1, stride 1) weight gradient (lwgrad.hip): G[g] [Cout][Cin] fp32 slabs (+=).  Same return convention.
+// (lwgrad.hip's three: dry_run = decide only -- same return value, nothing launched)
 int lwg_try_launch(const void* x, const void* dy, float* const* G, const int* seg, int ngroups, int N, long HW, int Cin, int Cout,
-                   int dtype, hipStream_t stream);
+                   int dtype, hipStream_t stream, bool dry_run = false);
 
 // Pointwise forward / dgrad with Cin >= 512 and Cout <= 64 (kgemm.hip).  Same return convention.
 int kgemm_try_launch(const ConvArgs& a, int dtype, hipStream_t stream);
 
 // k x k fp32 weight gradient for tiny input channel counts (taps * Cin <= 64: the stem), one expert (lwgrad.hip).  Same return convention.
 int swg_try_launch(const void* x, const void* dy, float* G, int N, int H, int W, int Cin, int Cout, int k, int pt, int pl, int dtype,
-                   hipStream_t stream);
+                   hipStream_t stream, bool dry_run = false);
 
 // k x k (k = 1 or 3) bf16 weight gradient for tiny output channel counts (Cout <= 4: output head, gate), one expert (lwgrad.hip).  Same return convention.
 int towg_try_launch(const void* x, const void* dy, float* G, int N, int H, int W, int Cin, int Cout, int k, int pt, int pl, int dtype,
-                    hipStream_t stream);
+                    hipStream_t stream, bool dry_run = false);
 
 // Grouped fp32 linear on one-position rows with a long input, 256 <= Cin <= 1024 (the experts' text projection; mlinear.hip).  Same return convention.
 int glin_try_launch(const ConvArgs& a, int dtype, hipStream_t stream);

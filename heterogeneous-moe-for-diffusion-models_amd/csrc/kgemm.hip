@@ -88,7 +88,6 @@ int kgemm_try_launch(const ConvArgs& a, int dtype, hipStream_t stream) {
   if (blocks > 0x7fffffffl) return 1;
   const int NT = a.Cout / 32;
   const size_t lds = (size_t)8 * NT * 4096;
-  if (NT == 1) hipLaunchKernelGGL(kgemm_kernel<1>, dim3((unsigned)blocks), dim3(512), lds, stream, k);
-  else hipLaunchKernelGGL(kgemm_kernel<2>, dim3((unsigned)blocks), dim3(512), lds, stream, k);
+  conv_pick<1, 2>(NT, [&](auto Nt) { hipLaunchKernelGGL(kgemm_kernel<decltype(Nt)::value>, dim3((unsigned)blocks), dim3(512), lds, stream, k); });
   return hdmoe_launch_status();
 }

@@ -378,7 +378,7 @@ __global__ __launch_bounds__(256) void towg_bf16_kernel(TowgArgs a) {
 
 // k x k bf16 weight gradient for Cout <= 4 (k = 1 or 3, one expert, stride 1, "same" geometry): G [tap][Cout][Cin] += .  Same return convention.
 int towg_try_launch(const void* x, const void* dy, float* G, int N, int H, int W, int Cin, int Cout, int k, int pt, int pl, int dtype,
-                    hipStream_t stream) {
+                    hipStream_t stream, bool dry_run) {
   if (dtype != HDMOE_BF16 || Cout < 1 || Cout > 4 || Cin % 32 || (k != 1 && k != 3) || pt != (k - 1) / 2 || pl != (k - 1) / 2) return 1;
   if (!x || !dy || !G || ((uintptr_t)x & 3)) return 1;
   TowgArgs a;
@@ -403,6 +403,7 @@ int towg_try_launch(const void* x, const void* dy, float* G, int N, int H, int W
   const size_t halo = (size_t)(a.TH + k - 1) * (W + k - 1) * 16, red = (size_t)4 * k * k * 128 * 4;
   const size_t lds = halo > red ? halo : red;
   const dim3 grid((unsigned)nb, (unsigned)cb);
+  if (dry_run) return HDMOE_OK;
   if (k == 3) hipLaunchKernelGGL(towg_bf16_kernel<3>, grid, dim3(256), lds, stream, a);
   else hipLaunchKernelGGL(towg_bf16_kernel<1>, grid, dim3(256), lds, stream, a);
   return hdmoe_launch_status();
@@ -410,8 +411,9 @@ int towg_try_launch(const void* x, const void* dy, float* G, int N, int H, int W
 
 // k x k fp32 layer with taps * Cin <= 64 (one expert, stride 1, "same" geometry): G [tap][Cout][Cin] += .  Same return convention.
 int swg_try_launch(const void* x, const void* dy, float* G, int N, int H, int W, int Cin, int Cout, int k, int pt, int pl, int dtype,
-                   hipStream_t stream) {
+                   hipStream_t stream, bool dry_run) {
   if (dtype != HDMOE_F32 || Cout % 32 || k * k * Cin > 64 || !x || !dy || !G || (long)N * H * W >= (1l << 31)) return 1;
+  if (dry_run) return HDMOE_OK;
   SwgArgs a;
   a.x = (const float*)x; a.dy = (const float*)dy; a.G = G; a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.k = k; a.pt = pt; a.pl = pl;
   const long total = (long)N * H * W;
@@ -427,7 +429,7 @@ int swg_try_launch(const void* x, const void* dy, float* G, int N, int H, int W,
 
 // Returns HDMOE_OK after launching, a negative status on a launch error, or 1 when the layer is outside this file's domain.
 int lwg_try_launch(const void* x, const void* dy, float* const* G, const int* seg, int ngroups, int N, long HW, int Cin, int Cout,
-                   int dtype, hipStream_t stream) {
+                   int dtype, hipStream_t stream, bool dry_run) {
   if (Cin % 32 || Cout % 32 || (dtype != HDMOE_BF16 && dtype != HDMOE_F32)) return 1;
   if (((uintptr_t)x | (uintptr_t)dy) & 15) return 1;
   LwgArgs a;
@@ -444,19 +446,12 @@ int lwg_try_launch(const void* x, const void* dy, float* const* G, const int* se
   if (slots > 65535 || ob > 65535) return 1;
   dim3 grid((unsigned)ib, (unsigned)ob, (unsigned)slots);
   const size_t red = (size_t)4 * OT * IT * 4096;
-#define LWG_GO(KERNEL, LDS)                                                                                   \
-  do {                                                                                                        \
-    if (OT == 2 && IT == 2) hipLaunchKernelGGL((KERNEL<2, 2>), grid, dim3(256), LDS, stream, a);               \
-    else if (OT == 2) hipLaunchKernelGGL((KERNEL<2, 1>), grid, dim3(256), LDS, stream, a);                     \
-    else if (IT == 2) hipLaunchKernelGGL((KERNEL<1, 2>), grid, dim3(256), LDS, stream, a);                     \
-    else hipLaunchKernelGGL((KERNEL<1, 1>), grid, dim3(256), LDS, stream, a);                                  \
-  } while (0)
-  if (dtype == HDMOE_BF16) {
-    const size_t stage = (size_t)4 * (OT + IT) * 4096;
-    const size_t lds = stage > red ? stage : red;
-    LWG_GO(lwg_bf16_kernel, lds);
-  } else {
-    LWG_GO(lwg_f32_kernel, red);
-  }
+  if (dry_run) return HDMOE_OK;
+  const size_t stage = (size_t)4 * (OT + IT) * 4096;                     // (bf16: the staged operands share the buffer with the reduction)
+  conv_pick<2, 1>(OT, [&](auto Ot) { conv_pick<2, 1>(IT, [&](auto It) {
+    constexpr int O = decltype(Ot)::value, I = decltype(It)::value;
+    if (dtype == HDMOE_BF16) hipLaunchKernelGGL((lwg_bf16_kernel<O, I>), grid, dim3(256), stage > red ? stage : red, stream, a);
+    else hipLaunchKernelGGL((lwg_f32_kernel<O, I>), grid, dim3(256), red, stream, a);
+  }); });
   return hdmoe_launch_status();
 }

@@ -222,11 +222,7 @@ int glin_try_launch(const ConvArgs& c, int dtype, hipStream_t stream) {
   a.x = (const float*)c.x; a.w = (const float*)c.w; a.y = (float*)c.y; a.res = (const float*)c.res; a.seg = c.seg; a.wstride = c.wstride;
   a.R = c.N; a.I = c.Cin; a.Ipad = c.Ipad; a.O = c.Cout; a.ngroups = c.ngroups; a.alpha = c.alpha; a.beta = c.beta;
   const dim3 grid((unsigned)((c.N + 3) / 4));
-  const int nj = (c.Cin + 255) / 256;
-  if (nj == 1) hipLaunchKernelGGL(glin_f32_kernel<1>, grid, dim3(256), 0, stream, a);
-  else if (nj == 2) hipLaunchKernelGGL(glin_f32_kernel<2>, grid, dim3(256), 0, stream, a);
-  else if (nj == 3) hipLaunchKernelGGL(glin_f32_kernel<3>, grid, dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL(glin_f32_kernel<4>, grid, dim3(256), 0, stream, a);
+  conv_pick<1, 2, 3, 4>((c.Cin + 255) / 256, [&](auto Nj) { hipLaunchKernelGGL(glin_f32_kernel<decltype(Nj)::value>, grid, dim3(256), 0, stream, a); });
   return hdmoe_launch_status();
 }
 

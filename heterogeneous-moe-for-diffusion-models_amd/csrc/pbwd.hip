@@ -256,11 +256,10 @@ extern "C" int hdmoe_pw_bwd(const void* x, const void* dy, const void* wd, void*
   const long slots = units / upw + ngroups + 1;
   if (slots >= (1l << 31)) return 1;
   hdmoe_count_selection(HDMOE_SEL_PW_BWD);
-#define PBW_GO(O_, I_) if (OT == O_ && IT == I_) return pbw_launch<O_, I_>(a, (unsigned)slots, lds, stream)
-  PBW_GO(1, 1); PBW_GO(1, 2); PBW_GO(1, 3); PBW_GO(1, 4);
-  PBW_GO(2, 1); PBW_GO(2, 2); PBW_GO(2, 3); PBW_GO(2, 4);
-  PBW_GO(3, 1); PBW_GO(3, 2);
-  PBW_GO(4, 1); PBW_GO(4, 2);
-#undef PBW_GO
-  return 1;
+  int rc = 1;                                                             // (OT * IT <= 8 was checked above)
+  conv_pick<1, 2, 3, 4>(OT, [&](auto Ot) { conv_pick<1, 2, 3, 4>(IT, [&](auto It) {
+    constexpr int O = decltype(Ot)::value, I = decltype(It)::value;
+    if constexpr (O * I <= 8) rc = pbw_launch<O, I>(a, (unsigned)slots, lds, stream);
+  }); });
+  return rc;
 }

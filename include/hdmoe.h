@@ -151,6 +151,29 @@ enum {
 };
 int hdmoe_kernel_selections(long long* counts, int n, int reset);
 
+/* Which generic kernel a layer gets (csrc/conv.hip), for tests and tools: the launch plan hdmoe_conv_fwd / hdmoe_conv_wgrad follow when
+ * none of the specialised forward kernels (conv6, conv6s, conv7, kgemm, glin) takes the layer -- those are not consulted here.  Nothing is
+ * launched.  aligned16 stands for the pointer tests: != 0 = every tensor of the call 16-byte aligned, 0 = 4-byte aligned only.
+ * hdmoe_conv_generic_route: route = HOST array of 5 ints {HDMOE_ROUTE_CONV_*, NT (conv_fwd_kernel: NB), VEC, LEPI, NHR}, the template
+ * arguments of the instantiation (0 where the kernel has no such parameter).
+ * hdmoe_conv_wgrad_route: route = HOST array of 34 ints {HDMOE_ROUTE_WGRAD_*, nclasses, then per kernel-size class in launch order
+ * (passes, MAXT, OT, VEC)}; nclasses = 0 unless conv_wgrad2_kernel runs.  has_seg: the call passes a seg array. */
+enum {
+  HDMOE_ROUTE_CONV_FWD = 0,   /* conv_fwd_kernel<T, NB, VEC> */
+  HDMOE_ROUTE_CONV_FWD2 = 1,  /* conv_fwd2_kernel<T, NT, VEC> */
+  HDMOE_ROUTE_CONV_FWD3 = 2,  /* conv_fwd3_kernel<T, NT> */
+  HDMOE_ROUTE_CONV_FWD5 = 3,  /* conv_fwd5_kernel<T, NT, LEPI, NHR> */
+  HDMOE_ROUTE_WGRAD_V2 = 0,   /* conv_wgrad2_kernel<T, OT, MAXT, VEC>, one launch per class and pass */
+  HDMOE_ROUTE_WGRAD_V1 = 1,   /* conv_wgrad_kernel<T> */
+  HDMOE_ROUTE_WGRAD_SWG = 2,  /* swg_f32_kernel (csrc/lwgrad.hip) */
+  HDMOE_ROUTE_WGRAD_TOWG = 3, /* towg_bf16_kernel */
+  HDMOE_ROUTE_WGRAD_LWG = 4   /* lwg_f32_kernel / lwg_bf16_kernel */
+};
+int hdmoe_conv_generic_route(int* route, int N, int H, int W, int Ho, int Wo, int Cin, int Cphys, int Ipad, int Cout, int Cstore, int stride,
+                             int ones, int ngroups, const int* kh, const int* kw, int dtype, int aligned16);
+int hdmoe_conv_wgrad_route(int* route, int N, int H, int W, int Ho, int Wo, int Cin, int Cphys, int Cout, int stride, int ones, int ngroups,
+                           int has_seg, const int* kh, const int* kw, const int* pt, const int* pl, int dtype, int aligned16);
+
 /* Multi-tensor weight bank: one prep launch per forward and one gradient-finish launch per backward for ALL MP_Conv weights
  * of a model.  descs: device array of descriptors (layout = hdmoe_wbank_desc_bytes() bytes each, see csrc/wbank.hip);
  * rows: device int32 pairs (descriptor index, output-channel row), one workgroup per pair. */
