@@ -40,10 +40,11 @@ void launch_bwd6(const C6Plan& cp, const W6DualPlan& wp, hipStream_t stream) {
 }
 
 // The same with the whole-image streaming kernel (conv7_body.h) as the dgrad program: 32 x 32 maps, enough images to fill the chip.
-template <int CO, int KMASK, int TWS, int OT>
+// EPI = 1: the dgrad program ends in the FiLM-backward epilogue (conv7_body.h) -- the layer's input is h = dropout(mp_silu(u * e)).
+template <int CO, int KMASK, int TWS, int OT, int EPI = 0>
 __global__ __launch_bounds__(512) void bwd7_kernel(C7Args c, W6Args a3, W6Args a5, int G7, int ibs, int obs) {
   const int b = blockIdx.x;
-  if (b < G7) { conv7_body<CO, KMASK, TWS == 4>(c, b, G7); return; }
+  if (b < G7) { conv7_body<CO, KMASK, TWS == 4, EPI>(c, b, G7); return; }
   int r = b - G7;
   if (TWS == 5 && OT == 0) {                                 // 32 x 32 maps: the streaming weight-gradient programs (output chunks of 32)
     const int nbx3 = a3.Cin / (32 * a3.icw), nby3 = a3.Cout / (32 * a3.ocw), n3 = nbx3 * nby3 * a3.chunks;
@@ -68,15 +69,16 @@ __global__ __launch_bounds__(512) void bwd7_kernel(C7Args c, W6Args a3, W6Args a
   }
 }
 
-template <int CO, int KMASK, int TWS, int OT>
+template <int CO, int KMASK, int TWS, int OT, int EPI = 0>
 void launch_bwd7(const C7Plan& cp, const W6DualPlan& wp, hipStream_t stream) {
   static unsigned long long attr = 0;
-  if (hdmoe_first_on_device(attr)) { (void)hipFuncSetAttribute((const void*)bwd7_kernel<CO, KMASK, TWS, OT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
-  const size_t lds = cp.lds > wp.lds ? cp.lds : wp.lds;
+  if (hdmoe_first_on_device(attr)) { (void)hipFuncSetAttribute((const void*)bwd7_kernel<CO, KMASK, TWS, OT, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
+  const size_t clds = cp.lds + (EPI ? C7Lds<TWS == 4>::film_extra(CO) : 0);
+  const size_t lds = clds > wp.lds ? clds : wp.lds;
   const int obs = OT == 0 ? wp.c[0].Cout / 32 : wp.obs;      // OT == 0: wgrad7 / wgrad8 (output chunks of 32)
   unsigned nw = (unsigned)(wp.ibs * obs * (wp.c[0].chunks + wp.c[1].chunks));
   if (OT == 0) nw = (unsigned)((wp.c[0].Cin / (32 * wp.c[0].icw)) * (wp.c[0].Cout / (32 * wp.c[0].ocw)) * wp.c[0].chunks + wp.ibs * obs * wp.c[1].chunks);
-  hipLaunchKernelGGL((bwd7_kernel<CO, KMASK, TWS, OT>), dim3(cp.G + nw), dim3(512), lds, stream, cp.a, wp.c[0], wp.c[1], (int)cp.G, wp.ibs, obs);
+  hipLaunchKernelGGL((bwd7_kernel<CO, KMASK, TWS, OT, EPI>), dim3(cp.G + nw), dim3(512), lds, stream, cp.a, wp.c[0], wp.c[1], (int)cp.G, wp.ibs, obs);
 }
 
 // The same for a router-trunk layer (fp32 tensors on the bf16 pipe: conv6_split program + wgrad6<SPLIT> program).
@@ -160,6 +162,46 @@ int hdmoe_conv_bwd6(const void* x, const void* dy, const void* wd, void* dx, flo
   conv_pick<2, 1>(cp.MT, [&](auto M) { conv_pick<2, 1>(cp.NT, [&](auto Nt) { conv_pick<5, 4>(wp.TWS, [&](auto Tws) { conv_pick<2, 1>(wp.OT, [&](auto Ot) {
     launch_bwd6<decltype(M)::value, decltype(Nt)::value, decltype(Tws)::value, decltype(Ot)::value>(cp, wp, stream);
   }); }); }); });
+  return hdmoe_launch_status();
+}
+
+/* hdmoe_conv_bwd6 for a layer whose input is h = dropout_p(mp_silu(u * e[n][c])) (conv_res2 of Unet_block) and feeds nothing else: the dgrad
+ * program applies the FiLM backward in its epilogue, so dx receives du = d(loss)/du and film_de [N][Cin] fp32 the per-sample gradient of e
+ * (written, not accumulated), as hdmoe_film_silu_drop_bwd would compute them from the dx of hdmoe_conv_bwd6 (du bit-identical).
+ * film_mask: the keep bytes of hdmoe_film_silu_drop_fwd_mask, or NULL with film_p == 0 (no dropout).  Returns 1 without launching when the
+ * layer is outside the epilogue's domain (the caller then takes hdmoe_conv_bwd6 and the standalone FiLM backward). */
+int hdmoe_conv_bwd6_film(const void* x, const void* dy, const void* wd, void* dx, float* const* G, const int* seg, int ngroups, long wd_stride,
+                         int N, int H, int W, int Cin, int Cout, const int* kh, const int* kw, const int* pt, const int* pl, float alpha,
+                         void* ws, long ws_bytes, const void* film_u, const float* film_e, const unsigned char* film_mask, float* film_de,
+                         float film_p, int dtype, hipStream_t stream) {
+  if (dtype != HDMOE_BF16 || !dx || !wd || ngroups < 1 || ngroups > HDMOE_MAX_GROUPS || Cout % 16) return 1;
+  if (!film_u || !film_e || !film_de || ((uintptr_t)film_u & 15) || ((uintptr_t)film_e & 15)) return 1;
+  if (film_p < 0.f || film_p >= 1.f || (film_p > 0.f) != (film_mask != nullptr)) return HDMOE_EINVAL;
+  W6DualPlan wp;
+  if (wgrad6_plan_dual(x, dy, G, seg, ngroups, N, H, W, Cin, Cout, kh, kw, pt, pl, ws, ws_bytes, dtype, wp)) return 1;
+  const ConvArgs c = conv_dgrad_args(dy, wd, dx, seg, ngroups, wd_stride, N, H, W, Cin, Cout, kh, kw, pt, pl, alpha);
+  C7Plan cp7;
+  if (conv7_plan(c, dtype, cp7) || cp7.kmask != 3 || (cp7.w16 != 0) != (wp.TWS == 4)) return 1;
+  // the instantiations with the epilogue: 32 x 32 maps with either output-block width, 16 x 16 maps with 64-channel blocks on both sides
+  // (the bwd7 kernels of the bench's blocks); any number of output blocks
+  const bool big = wp.TWS == 5, small = wp.TWS == 4 && cp7.CO == 2 && wp.OT == 2;
+  if (!big && !small) return 1;
+  cp7.a.film_u = film_u; cp7.a.film_e = film_e; cp7.a.film_mask = film_mask; cp7.a.film_de = film_de;
+  cp7.a.film_inv = film_p > 0.f ? 1.f / (1.f - film_p) : 1.f;
+  hdmoe_count_selection(HDMOE_SEL_FILM_DGRAD);
+  if (big) {
+    hdmoe_count_selection(HDMOE_SEL_BWD7_32);
+    if (wp.c[0].chunks) {
+      hdmoe_count_selection(HDMOE_SEL_BWD7_32_WGRAD8);
+      hdmoe_count_selection(wp.c[0].icw == 2 ? (wp.c[0].ocw == 2 ? HDMOE_SEL_WGRAD8_C22 : HDMOE_SEL_WGRAD8_C21)
+                                             : (wp.c[0].ocw == 2 ? HDMOE_SEL_WGRAD8_C12 : HDMOE_SEL_WGRAD8_C11));
+    }
+    if (wp.c[1].chunks) hdmoe_count_selection(HDMOE_SEL_BWD7_32_WGRAD7);
+    if (cp7.CO == 2) launch_bwd7<2, 3, 5, 0, 1>(cp7, wp, stream); else launch_bwd7<1, 3, 5, 0, 1>(cp7, wp, stream);
+  } else {
+    hdmoe_count_selection(HDMOE_SEL_BWD7_16_OT2);
+    launch_bwd7<2, 3, 4, 2, 1>(cp7, wp, stream);
+  }
   return hdmoe_launch_status();
 }
 

@@ -38,6 +38,7 @@ int conv7_plan(const ConvArgs& c, int dtype, C7Plan& plan) {
   a.N = c.N; a.Cin = c.Cin; a.Cout = c.Cout; a.ngroups = c.ngroups; a.alpha = c.alpha; a.beta = c.beta;
   a.xbytes = (int)xbytes; a.wbytes = (int)wbytes;
   a.dbg = 0;
+  a.film_u = nullptr; a.film_e = nullptr; a.film_mask = nullptr; a.film_de = nullptr; a.film_inv = 1.f;   // (hdmoe_conv_bwd6_film sets them)
   a.stamps = (unsigned long long*)hdmoe_debug_stamp_buffer();
   for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) a.ks[g] = c.kh[g];
   conv_sort_groups_desc(a.ks, a.order, c.ngroups);          // heaviest images first

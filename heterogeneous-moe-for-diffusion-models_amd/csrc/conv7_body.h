@@ -33,6 +33,12 @@ struct C7Args {
   int dbg;                             // always 0 (conv7_plan).  The tests on it stay: they split the MFMA loop, the interleave hints and the
                                        // epilogue into separate blocks, and without them the compiler schedules conv7 differently (more VGPRs)
   unsigned long long* stamps;          // development: s_memtime stamps of workgroup 0 ([wave][64] slots; hdmoe_conv6_debug_stamps), or null
+  // FiLM-backward epilogue (conv7_body<.., EPI = 1>, the dgrad of Unet_block's conv_res2): y = du, film_de[n][c] = sum over the image of g * u
+  const void* film_u;                  // bf16 [N][H][W][Cout]: the saved pre-activation
+  const float* film_e;                 // fp32 [N][Cout]
+  const unsigned char* film_mask;      // keep bits of the forward's dropout, one byte per 8 channels (null: all kept)
+  float* film_de;                      // fp32 [N][Cout], written (one plain store per entry), not accumulated
+  float film_inv;                      // 1 / (1 - p)
 };
 
 // Tile geometry.  32 x 32 maps: a tile is one image, [32 rows][35 pixel slots][64 B] (32 pixels + 3 pad slots shared with the next row), wave w
@@ -53,6 +59,11 @@ template <bool W16> struct C7Lds {
   static constexpr int T0 = 2 * GEO::WBUF;                     // tiles start behind the weight ring (keeps every row address >= 0)
   static constexpr int ZROW = T0 + 2 * GEO::TILE;              // zero pixel slots: what a row outside the image reads
   static constexpr int BYTES = ZROW + GEO::ZBYTES;             // 162,560 B / 156,416 B
+  // FiLM-backward epilogue: the waves' per-channel partial sums of de, [wave][image of the tile][32 CO channels] fp32 -- behind the zero rows
+  // where that fits in the 160 KiB, else (64 channels on 32 x 32 maps) in the weight-ring buffer the last stage has just consumed
+  static constexpr int film_bytes(int co) { return 8 * (W16 ? 2 : 1) * 32 * co * 4; }
+  static constexpr bool film_in_ring(int co) { return BYTES + film_bytes(co) > 160 * 1024; }
+  static constexpr int film_extra(int co) { return film_in_ring(co) ? 0 : film_bytes(co); }   // dynamic LDS on top of BYTES
 };
 
 // One stage = up to T = TCO / CO consecutive kernel rows of one kernel column (TCO: 2-KB weight blocks per ring buffer).
@@ -71,7 +82,7 @@ template <typename F, int... I> DEVI void c7_static_for_impl(F&& f, std::integer
 template <int N, typename F> DEVI void c7_static_for(F&& f) { c7_static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 template <int N> DEVI void c7_wait_barrier() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(N) : "memory"); }
 
-template <int CO, int KMASK, bool W16>
+template <int CO, int KMASK, bool W16, int EPI = 0>
 DEVI void conv7_body(const C7Args& a, const int bid, const int G) {
 #if __HIP_DEVICE_COMPILE__
   using GEO = C7Geo<W16>;
@@ -288,7 +299,81 @@ DEVI void conv7_body(const C7Args& a, const int bid, const int G) {
     const int cobase = blk * 32 * CO;
     stamp(4);
     // ---- epilogue: y = alpha * acc + beta * res, 16-byte stores (register quads paired across the half-waves)
-    if (!(a.dbg & 4)) {
+    if constexpr (EPI == 1) {
+      // ---- FiLM-backward epilogue: g = bf16(alpha * acc) is d(loss)/dh of h = dropout(mp_silu(u * e)); the store is du, the sums are de.
+      //      The arithmetic, in its order, is film_silu_bwd_vec_kernel's (elementwise.hip): du comes out bit-identical to the two launches.
+      constexpr int NIMG = W16 ? 2 : 1, NCH = 32 * CO;
+      constexpr bool RING = L::film_in_ring(CO);
+      static_assert(L::film_bytes(CO) <= WBUF, "the de partial sums do not fit a weight-ring buffer");
+      bf16* Y = (bf16*)a.y;
+      const bf16* U = (const bf16*)a.film_u;
+      // ring buffer sp holds the prefetched first stage of the next block / unit; sp ^ 1 is the one the last stage read, and nothing is
+      // issued into it before the next block's first stage barrier: free once every wave has left the MFMA loop (the barrier here)
+      float* part = reinterpret_cast<float*>(lds + (RING ? (sp ^ 1) * WBUF : L::BYTES));
+      if (RING) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      const int nimg = W16 ? ((r >> 4) ? cur.n2 : cur.n) : cur.n;
+      const bool live = !W16 || nimg >= 0;
+#pragma unroll
+      for (int b = 0; b < CO; ++b)
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          const int c0 = cobase + 32 * b + 16 * p + 8 * h;     // this lane's 8 channels
+          float ev[8], ds[8];
+          {
+            const float4 e0 = live ? *reinterpret_cast<const float4*>(a.film_e + (long)nimg * a.Cout + c0) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 e1 = live ? *reinterpret_cast<const float4*>(a.film_e + (long)nimg * a.Cout + c0 + 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+            ev[0] = e0.x; ev[1] = e0.y; ev[2] = e0.z; ev[3] = e0.w; ev[4] = e1.x; ev[5] = e1.y; ev[6] = e1.z; ev[7] = e1.w;
+          }
+#pragma unroll
+          for (int j = 0; j < 8; ++j) ds[j] = 0.f;
+#pragma unroll
+          for (int m = 0; m < MB; ++m) {                       // (rows innermost: only these 8 sums stay live across them)
+            const long o = (W16 ? (((long)nimg * 16 + 2 * wave + m) * 16 + (r & 15)) * a.Cout
+                                : (((long)nimg * 32 + 4 * wave + m) * 32 + r) * a.Cout) + c0;
+            float v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = a.alpha * acc[m][b][8 * p + e];
+            const C6Words pk = c6_pack_bf16(v);                // the rounding the stored g has in the two-launch form
+            if (live) {
+              const bf16x8 uu = *reinterpret_cast<const bf16x8*>(U + o);
+              const unsigned mb = a.film_mask ? a.film_mask[o >> 3] : 0xFFu;
+              bf16x8 out;
+#pragma unroll
+              for (int j = 0; j < 8; ++j) {
+                const unsigned wj = pk.w[j >> 1];
+                float g = __uint_as_float((j & 1) ? (wj & 0xFFFF0000u) : (wj << 16));
+                const float uv = (float)uu[j];
+                if (a.film_mask) g = (mb >> j) & 1u ? g * a.film_inv : 0.f;
+                g *= mp_silu_grad_f(uv * ev[j]);
+                ds[j] += g * uv;
+                g *= ev[j];
+                out[j] = (bf16)g;
+              }
+              *reinterpret_cast<bf16x8*>(Y + o) = out;
+            }
+          }
+          // de: over the image's pixel lanes of this half-wave (fixed butterfly), then one slot per wave, image and channel
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+#pragma unroll
+            for (int off = 1; off < (W16 ? 16 : 32); off <<= 1) ds[j] += __shfl_xor(ds[j], off);
+          }
+          if ((r & (W16 ? 15 : 31)) == 0) {
+            float* dst = part + (wave * NIMG + (W16 ? (r >> 4) : 0)) * NCH + 32 * b + 16 * p + 8 * h;
+            *reinterpret_cast<float4*>(dst) = make_float4(ds[0], ds[1], ds[2], ds[3]);
+            *reinterpret_cast<float4*>(dst + 4) = make_float4(ds[4], ds[5], ds[6], ds[7]);
+          }
+        }
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // (the slots are next written behind the next block's stage barriers)
+      if (tid < NIMG * NCH) {
+        const int img = tid / NCH, c = tid % NCH;
+        const int n = img ? cur.n2 : cur.n;
+        float sum = 0.f;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) sum += part[(w * NIMG + img) * NCH + c];
+        if (n >= 0) a.film_de[(long)n * a.Cout + cobase + c] = sum;
+      }
+    } else if (!(a.dbg & 4)) {
       bf16* Y = (bf16*)a.y;
       const bf16* R = (const bf16*)a.res;
       const int nimg = W16 ? ((r >> 4) ? cur.n2 : cur.n) : cur.n;

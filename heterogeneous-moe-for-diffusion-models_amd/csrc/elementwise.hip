@@ -838,7 +838,7 @@ __global__ void mp_silu_bwd_add_vec_kernel(T* dx, const T* dy, const T* x, const
 }
 template <typename T>
 __global__ void film_silu_fwd_vec_kernel(T* out, const T* u, const float* e, long HW, int C, long nv, uint32_t seed_lo, uint32_t seed_hi,
-                                         const unsigned long long* seed_dev, float p) {
+                                         const unsigned long long* seed_dev, float p, unsigned char* mask = nullptr) {
   constexpr int W = VT<T>::W;
   const int cv = C / W;
   if (p > 0.f) mix_seed(seed_lo, seed_hi, seed_dev);
@@ -852,6 +852,14 @@ __global__ void film_silu_fwd_vec_kernel(T* out, const T* u, const float* e, lon
     if (p > 0.f) {                                           // F.dropout fused (model_components.py:245-246): W = 4 or 8 elements
 #pragma unroll
       for (int q = 0; q < W / 4; ++q) { const long qi = (v * W) / 4 + q; philox((uint32_t)qi, (uint32_t)(qi >> 32), seed_lo, seed_hi, r4 + 4 * q); }
+      if constexpr (W == 8) {
+        if (mask) {                                          // the keep decisions for the backward: one byte per vector, bit j = element j kept
+          unsigned m = 0;
+#pragma unroll
+          for (int j = 0; j < W; ++j) m |= (u01(r4[j]) >= p ? 1u : 0u) << j;
+          mask[v] = (unsigned char)m;
+        }
+      }
     }
 #pragma unroll
     for (int j = 0; j < W; ++j) {
@@ -865,7 +873,8 @@ __global__ void film_silu_fwd_vec_kernel(T* out, const T* u, const float* e, lon
 // block = (pixel chunk, sample); a thread's vectors all carry the same channel chunk (256 % (C/W) == 0): register partials
 template <typename T>
 __global__ __launch_bounds__(256) void film_silu_bwd_vec_kernel(T* du, float* de, const T* da, const T* u, const float* e, long HW, int C, int chunk,
-                                                               uint32_t seed_lo, uint32_t seed_hi, const unsigned long long* seed_dev, float p) {
+                                                               uint32_t seed_lo, uint32_t seed_hi, const unsigned long long* seed_dev, float p,
+                                                               const unsigned char* mask = nullptr) {
   constexpr int W = VT<T>::W;
   extern __shared__ float sm[];
   if (p > 0.f) mix_seed(seed_lo, seed_hi, seed_dev);
@@ -883,7 +892,11 @@ __global__ __launch_bounds__(256) void film_silu_bwd_vec_kernel(T* du, float* de
   for (long v = p0 * cv + threadIdx.x; v < p1 * cv; v += 256) {
     float uv[W], g[W];
     vload<T>(uv, u + base + v * W); vload<T>(g, da + base + v * W);
-    if (p > 0.f) {
+    if (W == 8 && p > 0.f && mask) {                           // the forward saved its keep decisions (bit j of the vector's byte): no second draw
+      const unsigned m = mask[(base + v * W) >> 3];
+#pragma unroll
+      for (int j = 0; j < W; ++j) g[j] = (m >> j) & 1u ? g[j] * inv : 0.f;
+    } else if (p > 0.f) {
       uint32_t r4[W];
 #pragma unroll
       for (int q = 0; q < W / 4; ++q) { const long qi = (base + v * W) / 4 + q; philox((uint32_t)qi, (uint32_t)(qi >> 32), seed_lo, seed_hi, r4 + 4 * q); }
@@ -1376,6 +1389,26 @@ int hdmoe_film_silu_drop_bwd(void* du, float* de, const void* da, const void* u,
                      hipLaunchKernelGGL(film_silu_bwd_vec_kernel<T>, grid, dim3(TPB), C * sizeof(float), stream, (T*)du, de, (const T*)da, (const T*)u, e, HW, C, chunk,
                                         (uint32_t)seed, (uint32_t)(seed >> 32), seed_dev, p);
                    else return HDMOE_EINVAL)
+}
+/* hdmoe_film_silu_drop_fwd that also saves the keep decisions (bf16 only): mask [N][HW][C/8] bytes, bit j of a byte = element j of the
+ * 16-byte vector is kept.  `out` is bit-identical to hdmoe_film_silu_drop_fwd's. */
+int hdmoe_film_silu_drop_fwd_mask(void* out, unsigned char* mask, const void* u, const float* e, int N, long HW, int C, unsigned long long seed,
+                                  const unsigned long long* seed_dev, float p, int dtype, hipStream_t stream) {
+  const long n = (long)N * HW * C;
+  if (p <= 0.f || p >= 1.f || dtype != HDMOE_BF16 || !mask || C % 8 || !al16(out) || !al16(u)) return HDMOE_EINVAL;
+  L1D(film_silu_fwd_vec_kernel<bf16>, n / 8, (bf16*)out, (const bf16*)u, e, HW, C, n / 8, (uint32_t)seed, (uint32_t)(seed >> 32), seed_dev, p, mask);
+  return hdmoe_launch_status();
+}
+/* hdmoe_film_silu_drop_bwd from the saved mask instead of a second Philox draw (bf16 only; de accumulates).  du is bit-identical. */
+int hdmoe_film_silu_mask_bwd(void* du, float* de, const void* da, const void* u, const float* e, const unsigned char* mask, int N, long HW, int C,
+                             float p, int dtype, hipStream_t stream) {
+  if (N > 65535 || p <= 0.f || p >= 1.f || dtype != HDMOE_BF16 || !mask) return HDMOE_EINVAL;
+  const int chunk = 256;
+  dim3 grid(cdiv(HW, chunk), N);
+  if (!(chunk_fixed_ok<bf16>(C) && al16(du) && al16(da) && al16(u))) return HDMOE_EINVAL;
+  hipLaunchKernelGGL(film_silu_bwd_vec_kernel<bf16>, grid, dim3(TPB), C * sizeof(float), stream, (bf16*)du, de, (const bf16*)da, (const bf16*)u, e, HW, C, chunk,
+                     0u, 0u, nullptr, p, mask);
+  return hdmoe_launch_status();
 }
 int hdmoe_film_silu_bwd(void* du, float* de, const void* da, const void* u, const float* e, int N, long HW, int C,
                         int dtype, hipStream_t stream) {

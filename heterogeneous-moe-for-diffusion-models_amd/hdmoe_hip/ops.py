@@ -455,6 +455,10 @@ class _MPConvFn(torch.autograd.Function):
     def forward(ctx, x, res, seg, meta, *tensors):
         (G, gain_val, alpha, beta, ones, training, normalize, split, res_raw) = meta
         weights, gains = tensors[:G], list(tensors[G:]) or None
+        # the input is the output of a FiLM pass (ops._FilmRec): this layer's backward may run the FiLM backward in its dgrad epilogue
+        ctx.film = getattr(x, "_film_rec", None) if FILM_DGRAD and x.is_contiguous() else None
+        if ctx.film is not None:
+            ctx.film.taken += 1
         x = _c(x)
         N, H, W, Cphys = x.shape
         O, I = int(weights[0].shape[0]), int(weights[0].shape[1])
@@ -569,7 +573,22 @@ class _MPConvFn(torch.autograd.Function):
                     name, mid, tail = "hdmoe_conv6_ones_bwd", (S, g32, seg, G, wdstride, N, H, W, Cphys, O, Opad, khs, alpha), (dtc,)
                     defer, stats = None, ()                   # (reduced inside the launch, into the bank's slabs)
                 dxo = torch.empty_like(x) if nig[0] else None
-                fused = _fused_bwd(ctx.bank, ent, label, name, x, dy, ctx.wd, dxo, mid, ws, tail, defer, stats)
+                rec = ctx.film
+                if rec is not None:
+                    # (a pass that ended before the FiLM node, e.g. autograd.grad(inputs=h), leaves its hand-off behind: every pass starts clean)
+                    rec.consumed, rec.du, rec.de = False, None, None
+                if (fast == "bwd6" and rec is not None and FILM_DGRAD and nig[0] and rec.taken == 1
+                        and rec.u.shape == x.shape and rec.u.dtype == x.dtype):
+                    # dx of this launch is then du of the FiLM pass, de its embedding gradient (csrc/conv7_body.h, EPI = 1); outside the
+                    # epilogue's domain the entry returns non-zero without launching and the layer takes the plain launch below
+                    de = torch.empty(rec.e.shape, dtype=torch.float32, device=x.device)
+                    fused = _fused_bwd(ctx.bank, ent, dict(label, name="bwd7_kernel (FiLM epilogue)"), "hdmoe_conv_bwd6_film", x, dy, ctx.wd, dxo, mid, ws,
+                                       (rec.u, rec.e, rec.mask, de, rec.p, dtc), defer, stats)
+                    if fused:
+                        rec.consumed, rec.du, rec.de = True, dxo, de
+                        STATS["film_dgrad"] += 1
+                if not fused:
+                    fused = _fused_bwd(ctx.bank, ent, label, name, x, dy, ctx.wd, dxo, mid, ws, tail, defer, stats)
                 dx = dxo if fused else None
             elif (fast is None and nig[0] and _prof_ok() and not ones and not split and x.dtype == torch.bfloat16 and Cphys == I
                   and Ho == H and Wo == W and all(k == 1 for k in khs) and all(k == 1 for k in kws)):
@@ -1106,6 +1125,29 @@ def sigmoid(x: Tensor, a: float = 1.0) -> Tensor:
     return _SigmoidFn.apply(x, float(a))
 
 
+class _FilmRec:
+    """What the consumer of h = film_silu(u, e) needs to run the FiLM backward itself: the saved pre-activation, the embedding, the keep
+    bytes of the dropout (None: p == 0) -- attached to h as ``h._film_rec``.  A conv layer that reads h picks it up in its forward
+    (``taken``); in its backward the bwd7 launch writes du / de in its dgrad epilogue (``consumed``, ``du``, ``de``) and the FiLM node
+    hands them on without a launch.  h must feed that layer alone, as in Unet_block: the FiLM node checks that the gradient it receives is
+    the very tensor the conv wrote."""
+    __slots__ = ("u", "e", "mask", "p", "taken", "consumed", "du", "de")
+
+    def __init__(self, u, e, mask, p):
+        self.u, self.e, self.mask, self.p = u, e, mask, p
+        self.taken, self.consumed, self.du, self.de = 0, False, None, None
+
+
+FILM_MASK = True                                        # False: the FiLM backward draws the dropout bits again instead of reading saved keep bytes
+FILM_DGRAD = True                                       # False: the FiLM backward always runs as its own launch
+
+
+def _film_record(ctx, out, u, e, mask, p):
+    ctx.rec = None
+    if u.dtype == torch.bfloat16 and u.ndim == 4 and (p == 0.0 or mask is not None):
+        ctx.rec = out._film_rec = _FilmRec(u, e, mask, p)
+
+
 class _FilmSiluFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u, e, p, seed):
@@ -1114,24 +1156,41 @@ class _FilmSiluFn(torch.autograd.Function):
         N, C = u.shape[0], u.shape[-1]
         HW = u.numel() // (N * C)
         out = torch.empty_like(u)
-        if p > 0.0:
+        mask = None
+        if p > 0.0 and FILM_MASK and u.dtype == torch.bfloat16 and C % 8 == 0:
+            # one keep bit per element beside the output: the backward (its own launch, or the consumer's dgrad epilogue) never draws
+            mask = torch.empty(u.numel() // 8, dtype=torch.uint8, device=u.device)
+            call("hdmoe_film_silu_drop_fwd_mask", out, mask, u, e, N, HW, C, seed, step_counter(u.device), p, _dt(u))
+        elif p > 0.0:
             call("hdmoe_film_silu_drop_fwd", out, u, e, N, HW, C, seed, step_counter(u.device), p, _dt(u))
         else:
             call("hdmoe_film_silu_fwd", out, u, e, N, HW, C, _dt(u))
         ctx.save_for_backward(u, e)
         ctx.meta = (p, seed)
+        ctx.mask = mask
+        _film_record(ctx, out, u, e, mask, p)
         return out
 
     @staticmethod
     def backward(ctx, g):
         u, e = ctx.saved_tensors
         p, seed = ctx.meta
+        rec, mask = getattr(ctx, "rec", None), getattr(ctx, "mask", None)
+        if rec is not None and rec.consumed:
+            # the consumer's backward launch already applied this node's backward: g is du
+            du, de = rec.du, rec.de
+            rec.consumed, rec.du, rec.de = False, None, None
+            if du is None or g.data_ptr() != du.data_ptr() or g.shape != du.shape:
+                raise RuntimeError("film_silu: the output fed a second consumer beside the conv layer that fused its backward (set ops.FILM_DGRAD = False)")
+            return g, de, None, None
         g = _c(g)
         N, C = u.shape[0], u.shape[-1]
         HW = u.numel() // (N * C)
         du = torch.empty_like(u)
         de = _zeros(e.shape, e.dtype, e.device, ctx.pool_ok)
-        if p > 0.0:
+        if p > 0.0 and mask is not None:
+            call("hdmoe_film_silu_mask_bwd", du, de, g, u, e, mask, N, HW, C, p, _dt(u))
+        elif p > 0.0:
             call("hdmoe_film_silu_drop_bwd", du, de, g, u, e, N, HW, C, seed, step_counter(u.device), p, _dt(u))
         else:
             call("hdmoe_film_silu_bwd", du, de, g, u, e, N, HW, C, _dt(u))
@@ -1158,7 +1217,9 @@ class _FilmDoneFn(torch.autograd.Function):
         ctx.pool_ok = not e.is_leaf
         ctx.save_for_backward(u, e)
         ctx.meta = (p, seed)
-        return h.view_as(h)
+        out = h.view_as(h)
+        _film_record(ctx, out, u, e, None, p)                 # (the producing launch saved no keep bytes: a record only without dropout)
+        return out
 
     @staticmethod
     def backward(ctx, g):
@@ -1167,7 +1228,8 @@ class _FilmDoneFn(torch.autograd.Function):
 
 def mp_conv_film(x: Tensor, weights, gain, emb: Tensor, p: float, training: bool, seg: Optional[Tensor] = None) -> Tensor:
     """film_silu(mp_conv(x, weights, gain), emb, p) -- conv_res1 of Unet_block followed by FiLM, mp_silu and dropout (reference
-    model_components.py:240-246).  In the bf16 bank path the second step is an extra output of the conv kernel's epilogue."""
+    model_components.py:240-246).  In the bf16 bank path the second step is an extra output of the conv kernel's epilogue.
+    With ops.FILM_DGRAD the result may feed ONE conv layer and nothing else that needs its gradient (see ops.film_silu)."""
     global _FILM_REQ
     p = float(p) if training else 0.0
     C = int((weights[0] if isinstance(weights, (list, tuple)) else weights).shape[0])
@@ -1255,7 +1317,10 @@ def unet_block_fused(h: Tensor, res: Optional[Tensor], w1s, w2s, gain1: float, g
 
 def film_silu(u: Tensor, e: Tensor, p: float = 0.0, training: bool = False) -> Tensor:
     """dropout_p(mp_silu(u * e[n, c])) with e a float32 (N, C) embedding (model_components.py:242-246); the dropout is fused
-    into the same pass when the layout is 16-byte vectorisable, otherwise it runs as a separate kernel."""
+    into the same pass when the layout is 16-byte vectorisable, otherwise it runs as a separate kernel.
+    With ops.FILM_DGRAD (default) a bf16 result that feeds a k x k bank conv layer has its backward run in that layer's backward launch
+    (ops._FilmRec): the result must then feed that layer alone -- a second consumer that is a conv layer falls back to this node's own
+    kernel, any other second consumer raises in the backward.  Set ops.FILM_DGRAD = False for such a graph."""
     p = float(p) if training else 0.0
     C = u.shape[-1]
     vw = 16 // u.element_size()

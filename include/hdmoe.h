@@ -83,6 +83,15 @@ int hdmoe_conv_wgrad6(const void* x, const void* dy, float* const* G, const int*
 int hdmoe_conv_bwd6(const void* x, const void* dy, const void* wd, void* dx, float* const* G, const int* seg, int ngroups,
                     long wd_stride, int N, int H, int W, int Cin, int Cout, const int* kh, const int* kw, const int* pt,
                     const int* pl, float alpha, void* ws, long ws_bytes, int dtype, HS stream);
+/* The same for a layer whose input is h = dropout_p(mp_silu(u * film_e[n][c])) and feeds nothing else (conv_res2 of Unet_block): the FiLM
+ * backward runs in the dgrad program's epilogue.  dx receives du (bit-identical to hdmoe_conv_bwd6 + hdmoe_film_silu_drop_bwd), film_de
+ * [N][Cin] fp32 the gradient of film_e (written, not accumulated; summed in a fixed order).  film_mask: the keep bytes of
+ * hdmoe_film_silu_drop_fwd_mask, NULL exactly when film_p == 0.  Returns 1 without launching outside the epilogue's domain (bwd7 on
+ * 32 x 32 maps; on 16 x 16 maps Cin % 64 == 0 and Cout % 64 == 0). */
+int hdmoe_conv_bwd6_film(const void* x, const void* dy, const void* wd, void* dx, float* const* G, const int* seg, int ngroups,
+                         long wd_stride, int N, int H, int W, int Cin, int Cout, const int* kh, const int* kw, const int* pt,
+                         const int* pl, float alpha, void* ws, long ws_bytes, const void* film_u, const float* film_e,
+                         const unsigned char* film_mask, float* film_de, float film_p, int dtype, HS stream);
 /* Input gradient and weight gradient of one (grouped) POINTWISE bf16 layer (linear / 1x1, stride 1, no ones channel) in ONE launch
  * (csrc/pbwd.hip): x [N * HW][Cin], dy [N * HW][Cout], dx = alpha * dy * w from the flipped image wd ([g][Cin][Cout], wd_stride
  * elements per group), G[g] ([Cout][Cin] fp32) += dy^T x.  dy is read once.  Domain: Cin % 32 == 0, Cout % 32 == 0, both <= 128,
@@ -147,7 +156,8 @@ enum {
   HDMOE_SEL_RELAYOUT_TILED = 19,   /* hdmoe_patch_relayout_tiled: order-1 patch <-> image relayout, tiled through LDS */
   HDMOE_SEL_COMBINE_FWD_VEC = 20,  /* hdmoe_combine_rows_fwd_vec: 16-byte combine forward (also the gather's backward) */
   HDMOE_SEL_COMBINE_BWD_VEC = 21,  /* hdmoe_combine_rows_bwd_vec: 16-byte combine backward */
-  HDMOE_SEL_COUNT = 22
+  HDMOE_SEL_FILM_DGRAD = 22,       /* hdmoe_conv_bwd6_film: the bwd7 launch with the FiLM-backward epilogue in its dgrad program */
+  HDMOE_SEL_COUNT = 23
 };
 int hdmoe_kernel_selections(long long* counts, int n, int reset);
 
@@ -255,6 +265,12 @@ int hdmoe_film_silu_drop_fwd(void* out, const void* u, const float* e, int N, lo
                              const unsigned long long* seed_dev, float p, int dtype, HS stream);                  /* + F.dropout fused (:245-246) */
 int hdmoe_film_silu_drop_bwd(void* du, float* de, const void* da, const void* u, const float* e, int N, long HW, int C,
                              unsigned long long seed, const unsigned long long* seed_dev, float p, int dtype, HS stream);
+/* The same with the keep decisions saved by the forward (bf16 only): mask [N][HW][C/8] bytes, bit j = element j of the 16-byte vector kept.
+ * out / du are bit-identical to the drop_fwd / drop_bwd pair; the backward reads the byte instead of drawing the Philox words again. */
+int hdmoe_film_silu_drop_fwd_mask(void* out, unsigned char* mask, const void* u, const float* e, int N, long HW, int C,
+                                  unsigned long long seed, const unsigned long long* seed_dev, float p, int dtype, HS stream);
+int hdmoe_film_silu_mask_bwd(void* du, float* de, const void* da, const void* u, const float* e, const unsigned char* mask, int N,
+                             long HW, int C, float p, int dtype, HS stream);
 int hdmoe_scale_rows_fwd(void* out, const void* x, const float* s, long rows, long L, int dtype, HS stream);    /* out[r][:] = s[r]*x[r][:] */
 int hdmoe_scale_rows_bwd(void* dx, float* ds, const void* dy, const void* x, const float* s, long rows, long L,
                          int dtype, HS stream);                                                                  /* dx and/or ds (accumulates) */
