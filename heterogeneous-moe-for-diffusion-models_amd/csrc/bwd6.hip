@@ -41,10 +41,11 @@ void launch_bwd6(const C6Plan& cp, const W6DualPlan& wp, hipStream_t stream) {
 
 // The same with the whole-image streaming kernel (conv7_body.h) as the dgrad program: 32 x 32 maps, enough images to fill the chip.
 // EPI = 1: the dgrad program ends in the FiLM-backward epilogue (conv7_body.h) -- the layer's input is h = dropout(mp_silu(u * e)).
-template <int CO, int KMASK, int TWS, int OT, int EPI = 0>
+// DBG: the dgrad program is conv7_body's development instantiation (stamps, ablations).
+template <int CO, int KMASK, int TWS, int OT, int EPI = 0, bool DBG = false>
 __global__ __launch_bounds__(512) void bwd7_kernel(C7Args c, W6Args a3, W6Args a5, int G7, int ibs, int obs) {
   const int b = blockIdx.x;
-  if (b < G7) { conv7_body<CO, KMASK, TWS == 4, EPI>(c, b, G7); return; }
+  if (b < G7) { conv7_body<CO, KMASK, TWS == 4, EPI, DBG>(c, b, G7); return; }
   int r = b - G7;
   if (TWS == 5 && OT == 0) {                                 // 32 x 32 maps: the streaming weight-gradient programs (output chunks of 32)
     const int nbx3 = a3.Cin / (32 * a3.icw), nby3 = a3.Cout / (32 * a3.ocw), n3 = nbx3 * nby3 * a3.chunks;
@@ -69,16 +70,20 @@ __global__ __launch_bounds__(512) void bwd7_kernel(C7Args c, W6Args a3, W6Args a
   }
 }
 
-template <int CO, int KMASK, int TWS, int OT, int EPI = 0>
+template <int CO, int KMASK, int TWS, int OT, int EPI = 0, bool DBG = false>
 void launch_bwd7(const C7Plan& cp, const W6DualPlan& wp, hipStream_t stream) {
+  // a registered stamp buffer (development) takes the DBG kernel where one is instantiated: the shapes tools/conv7_check.py --stamps-bwd runs
+  if constexpr (!DBG && EPI == 0 && (TWS == 5 || OT == 2)) {
+    if (cp.a.stamps || cp.a.dbg) { launch_bwd7<CO, KMASK, TWS, OT, 0, true>(cp, wp, stream); return; }
+  }
   static unsigned long long attr = 0;
-  if (hdmoe_first_on_device(attr)) { (void)hipFuncSetAttribute((const void*)bwd7_kernel<CO, KMASK, TWS, OT, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
+  if (hdmoe_first_on_device(attr)) { (void)hipFuncSetAttribute((const void*)bwd7_kernel<CO, KMASK, TWS, OT, EPI, DBG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
   const size_t clds = cp.lds + (EPI ? C7Lds<TWS == 4>::film_extra(CO) : 0);
   const size_t lds = clds > wp.lds ? clds : wp.lds;
   const int obs = OT == 0 ? wp.c[0].Cout / 32 : wp.obs;      // OT == 0: wgrad7 / wgrad8 (output chunks of 32)
   unsigned nw = (unsigned)(wp.ibs * obs * (wp.c[0].chunks + wp.c[1].chunks));
   if (OT == 0) nw = (unsigned)((wp.c[0].Cin / (32 * wp.c[0].icw)) * (wp.c[0].Cout / (32 * wp.c[0].ocw)) * wp.c[0].chunks + wp.ibs * obs * wp.c[1].chunks);
-  hipLaunchKernelGGL((bwd7_kernel<CO, KMASK, TWS, OT, EPI>), dim3(cp.G + nw), dim3(512), lds, stream, cp.a, wp.c[0], wp.c[1], (int)cp.G, wp.ibs, obs);
+  hipLaunchKernelGGL((bwd7_kernel<CO, KMASK, TWS, OT, EPI, DBG>), dim3(cp.G + nw), dim3(512), lds, stream, cp.a, wp.c[0], wp.c[1], (int)cp.G, wp.ibs, obs);
 }
 
 // The same for a router-trunk layer (fp32 tensors on the bf16 pipe: conv6_split program + wgrad6<SPLIT> program).

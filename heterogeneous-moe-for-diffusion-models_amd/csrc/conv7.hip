@@ -9,8 +9,8 @@
 
 namespace {
 
-template <int CO, int KMASK, bool W16>
-__global__ __launch_bounds__(512) void conv7_kernel(C7Args a) { conv7_body<CO, KMASK, W16>(a, blockIdx.x, gridDim.x); }
+template <int CO, int KMASK, bool W16, bool DBG>
+__global__ __launch_bounds__(512) void conv7_kernel(C7Args a) { conv7_body<CO, KMASK, W16, 0, DBG>(a, blockIdx.x, gridDim.x); }
 
 }  // namespace
 
@@ -33,35 +33,45 @@ int conv7_plan(const ConvArgs& c, int dtype, C7Plan& plan) {
   const long xbytes = (long)c.N * c.H * c.W * c.Cin * 2;
   const long wbytes = ((long)(c.ngroups - 1) * c.wstride + maxtaps * c.Cout * c.Cin) * 2;
   if (!conv_align_extent_ok({c.x, c.w, c.y, c.res}, {xbytes, wbytes, (long)c.N * c.H * c.W * c.Cout})) return 1;
+  // the kernel builds its DMA offsets from these byte strides in 32-bit registers: the largest offset of either operand stays below 2^31,
+  // and a group's base is a multiple of 8 (its low bits carry the kernel size)
+  const long gstride = c.wstride * 2, tapstride = (long)c.Cout * c.Cin * 2, imgstride = (long)c.H * c.W * c.Cin * 2;
+  if ((gstride & 7) || (c.ngroups - 1) * gstride + maxtaps * tapstride >= (1l << 31) || c.N * imgstride >= (1l << 31)) return 1;
   C7Args& a = plan.a;
-  a.x = c.x; a.w = c.w; a.y = c.y; a.res = c.res; a.seg = c.seg; a.wstride = c.wstride;
+  a.x = c.x; a.w = c.w; a.y = c.y; a.res = c.res; a.seg = c.seg;
   a.N = c.N; a.Cin = c.Cin; a.Cout = c.Cout; a.ngroups = c.ngroups; a.alpha = c.alpha; a.beta = c.beta;
   a.xbytes = (int)xbytes; a.wbytes = (int)wbytes;
   a.dbg = 0;
   a.film_u = nullptr; a.film_e = nullptr; a.film_mask = nullptr; a.film_de = nullptr; a.film_inv = 1.f;   // (hdmoe_conv_bwd6_film sets them)
   a.stamps = (unsigned long long*)hdmoe_debug_stamp_buffer();
-  for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) a.ks[g] = c.kh[g];
-  conv_sort_groups_desc(a.ks, a.order, c.ngroups);          // heaviest images first
+  conv_sort_groups_desc(c.kh, a.order, c.ngroups);          // heaviest images first
+  for (int i = 0; i < HDMOE_MAX_GROUPS; ++i) a.gk[i] = (int)(a.order[i] * gstride) | c.kh[a.order[i]];
   const long gcap = 256;
   const long units = w16 ? (c.N + 1) / 2 + c.ngroups : c.N;    // (16 x 16: pairs of images of one expert; an upper bound for any routing)
   plan.G = (unsigned)(units < gcap ? units : gcap);
   plan.CO = c.Cout % 64 == 0 ? 2 : 1;
+  a.tapstride = (int)tapstride; a.blkstride = 32 * plan.CO * c.Cin * 2;
+  a.imgstride = (int)imgstride; a.rowstride = c.W * c.Cin * 2;
   plan.w16 = w16 ? 1 : 0;
   plan.lds = w16 ? C7Lds<true>::BYTES : C7Lds<false>::BYTES;
   plan.kmask = (kmask & 4) ? 7 : 3;                          // instantiated kernel-size sets: {3, 5} and {3, 5, 7}
   return 0;
 }
 
-template <int CO, int KMASK, bool W16>
+template <int CO, int KMASK, bool W16, bool DBG>
 static void conv7_launch_t(const C7Plan& p, hipStream_t stream) {
   static unsigned long long attr = 0;
-  if (hdmoe_first_on_device(attr)) { (void)hipFuncSetAttribute((const void*)conv7_kernel<CO, KMASK, W16>, hipFuncAttributeMaxDynamicSharedMemorySize, C7Lds<W16>::BYTES); }
-  hipLaunchKernelGGL((conv7_kernel<CO, KMASK, W16>), dim3(p.G), dim3(512), C7Lds<W16>::BYTES, stream, p.a);
+  if (hdmoe_first_on_device(attr)) { (void)hipFuncSetAttribute((const void*)conv7_kernel<CO, KMASK, W16, DBG>, hipFuncAttributeMaxDynamicSharedMemorySize, C7Lds<W16>::BYTES); }
+  hipLaunchKernelGGL((conv7_kernel<CO, KMASK, W16, DBG>), dim3(p.G), dim3(512), C7Lds<W16>::BYTES, stream, p.a);
 }
 
 void conv7_launch(const C7Plan& p, hipStream_t stream) {
   conv_pick<2, 1>(p.CO, [&](auto Co) { conv_pick<7, 3>(p.kmask, [&](auto Km) { conv_pick<1, 0>(p.w16 != 0, [&](auto W16) {
-    conv7_launch_t<decltype(Co)::value, decltype(Km)::value, decltype(W16)::value != 0>(p, stream);
+    // the development kernel (stamps, ablations) only while a stamp buffer is registered or an ablation is set; {3, 5} layers only
+    if constexpr (decltype(Km)::value == 3) {
+      if (p.a.stamps || p.a.dbg) { conv7_launch_t<decltype(Co)::value, 3, decltype(W16)::value != 0, true>(p, stream); return; }
+    }
+    conv7_launch_t<decltype(Co)::value, decltype(Km)::value, decltype(W16)::value != 0, false>(p, stream);
   }); }); });
 }
 

@@ -25,14 +25,17 @@ namespace {
 
 struct C7Args {
   const void* x; const void* w; void* y; const void* res; const int* seg;
-  long wstride;                        // elements per group in the weight image [g][tap][Cout][Cin]
   int N, Cin, Cout, ngroups;           // H = W = 32 (or 16: conv7_body<.., .., true>)
-  int ks[HDMOE_MAX_GROUPS], order[HDMOE_MAX_GROUPS];   // kernel size per group; groups in descending kernel size
+  int order[HDMOE_MAX_GROUPS];         // groups in descending kernel size
+  int gk[HDMOE_MAX_GROUPS];            // per slot of order[]: byte offset of the group in the weight image [g][tap][Cout][Cin] | kernel size (low 3 bits)
+  // byte strides of the DMA offsets, all from conv7_plan (every offset they build fits in 31 bits)
+  int tapstride, blkstride;            // w: one tap (Cout * Cin * 2), one output block of 32 CO rows (32 * CO * Cin * 2)
+  int imgstride, rowstride;            // x: one image, one image row
   float alpha, beta;
   int xbytes, wbytes;
-  int dbg;                             // always 0 (conv7_plan).  The tests on it stay: they split the MFMA loop, the interleave hints and the
-                                       // epilogue into separate blocks, and without them the compiler schedules conv7 differently (more VGPRs)
-  unsigned long long* stamps;          // development: s_memtime stamps of workgroup 0 ([wave][64] slots; hdmoe_conv6_debug_stamps), or null
+  int dbg;                             // development ablations, read by the DBG instantiations only (conv7_plan: 0)
+  unsigned long long* stamps;          // development: s_memtime stamps of workgroup 0 ([wave][64] slots; hdmoe_conv6_debug_stamps), or null.
+                                       // Non-null selects the DBG instantiation (conv7_launch, launch_bwd7); the production kernels hold neither
   // FiLM-backward epilogue (conv7_body<.., EPI = 1>, the dgrad of Unet_block's conv_res2): y = du, film_de[n][c] = sum over the image of g * u
   const void* film_u;                  // bf16 [N][H][W][Cout]: the saved pre-activation
   const float* film_e;                 // fp32 [N][Cout]
@@ -58,7 +61,8 @@ template <bool W16> struct C7Lds {
   using GEO = C7Geo<W16>;
   static constexpr int T0 = 2 * GEO::WBUF;                     // tiles start behind the weight ring (keeps every row address >= 0)
   static constexpr int ZROW = T0 + 2 * GEO::TILE;              // zero pixel slots: what a row outside the image reads
-  static constexpr int BYTES = ZROW + GEO::ZBYTES;             // 162,560 B / 156,416 B
+  static constexpr int TAB = ZROW + GEO::ZBYTES;               // unit table: one {first unit, first row, end row, gk} per slot of order[]
+  static constexpr int BYTES = TAB + HDMOE_MAX_GROUPS * 16;    // 162,688 B / 156,544 B
   // FiLM-backward epilogue: the waves' per-channel partial sums of de, [wave][image of the tile][32 CO channels] fp32 -- behind the zero rows
   // where that fits in the 160 KiB, else (64 channels on 32 x 32 maps) in the weight-ring buffer the last stage has just consumed
   static constexpr int film_bytes(int co) { return 8 * (W16 ? 2 : 1) * 32 * co * 4; }
@@ -76,19 +80,21 @@ template <int KS, int CO, int TCO> struct C7Sched {
   static constexpr int nt(int i) { return (KS * (i + 1)) / SPC - (KS * i) / SPC; }
 };
 
-struct C7Unit { int g, n, n2, ks; };
+struct C7Unit { int n, n2, gk, xb, wrow; };   // image(s), group base | kernel size, byte offset of image n in x, bytes per kernel row of the group's weights
 
 template <typename F, int... I> DEVI void c7_static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
 template <int N, typename F> DEVI void c7_static_for(F&& f) { c7_static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 template <int N> DEVI void c7_wait_barrier() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(N) : "memory"); }
 
-template <int CO, int KMASK, bool W16, int EPI = 0>
+// DBG: the development instantiation (in-kernel stamps, a.dbg ablations); the production kernels contain neither.
+template <int CO, int KMASK, bool W16, int EPI = 0, bool DBG = false>
 DEVI void conv7_body(const C7Args& a, const int bid, const int G) {
 #if __HIP_DEVICE_COMPILE__
   using GEO = C7Geo<W16>;
   using L = C7Lds<W16>;
   constexpr int MB = GEO::MB, IMG = GEO::IMG, ROWB = GEO::ROWB, TILE = GEO::TILE, WBUF = GEO::WBUF, TCO = GEO::TCO, PPW = GEO::PPW;
-  constexpr int T0 = L::T0, ZROW = L::ZROW;
+  constexpr int T0 = L::T0, ZROW = L::ZROW, TAB = L::TAB;
+  constexpr int NWJ = (2 * TCO + 7) / 8;                        // weight DMA pieces per wave and stage
   constexpr int NSTORE = MB * CO * 2;                           // epilogue stores per wave
   extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -98,41 +104,47 @@ DEVI void conv7_body(const C7Args& a, const int bid, const int G) {
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.w), 0, a.wbytes, 0x00020000);
   const int CI = a.Cin >> 5;
   const int cin2 = a.Cin * 2;
+  const int dbg = DBG ? a.dbg : 0;
   int nstamp = 0;
-  auto stamp = [&](int tag) {
-    if (a.stamps && bid == 0 && lane == 0 && nstamp < 63) {
-      a.stamps[wave * 64 + nstamp] = ((unsigned long long)tag << 56) | (__builtin_amdgcn_s_memtime() & 0x00FFFFFFFFFFFFFFull);
-      ++nstamp;
+  unsigned t_iss = 0;                                           // DBG: ticks spent in the DMA issue blocks since the last stamp 10
+  auto ticks = [&]() -> unsigned { if constexpr (DBG) return (unsigned)__builtin_amdgcn_s_memtime(); else return 0u; };
+  auto stampv = [&](int tag, unsigned long long v) {
+    if constexpr (DBG) {
+      if (a.stamps && bid == 0 && lane == 0 && nstamp < 63) { a.stamps[wave * 64 + nstamp] = ((unsigned long long)tag << 56) | v; ++nstamp; }
     }
   };
+  auto stamp = [&](int tag) { if constexpr (DBG) stampv(tag, __builtin_amdgcn_s_memtime() & 0x00FFFFFFFFFFFFFFull); };
   stamp(1);
 
-  // ---- unit list: images (pairs of images on 16 x 16 maps) of the groups in descending kernel size, dealt in a snake over the workgroups
-  int cum[HDMOE_MAX_GROUPS + 1];
-  cum[0] = 0;
+  // ---- unit list: images (pairs of images on 16 x 16 maps) of the groups in descending kernel size, dealt in a snake over the workgroups.
+  //      seg[] is read once: lane i of every wave builds slot i's table entry and the wave stores it (all waves store the same values, and
+  //      a wave reads the table behind its own stores: no barrier); a unit decode is one 16-byte read, a ballot and four v_readlane
+  int total = 0;
+  {
+    int e0 = 0x7FFFFFFF, e1 = 0, e2 = 0, e3 = 0;
 #pragma unroll
-  for (int i = 0; i < HDMOE_MAX_GROUPS; ++i) {
-    int cnt = 0;
-    if (i < a.ngroups) { const int g = a.order[i]; cnt = a.seg ? a.seg[g + 1] - a.seg[g] : a.N; }
-    cum[i + 1] = cum[i] + (W16 ? (cnt + 1) >> 1 : cnt);
+    for (int i = 0; i < HDMOE_MAX_GROUPS; ++i) {
+      if (i < a.ngroups) {
+        const int g = a.order[i];
+        const int s0 = a.seg ? a.seg[g] : 0, s1 = a.seg ? a.seg[g + 1] : a.N;
+        if (lane == i) { e0 = total; e1 = s0; e2 = s1; e3 = a.gk[i]; }
+        total += W16 ? (s1 - s0 + 1) >> 1 : s1 - s0;
+      }
+    }
+    if (lane < HDMOE_MAX_GROUPS) *reinterpret_cast<int4*>(lds + TAB + lane * 16) = make_int4(e0, e1, e2, e3);
   }
-  const int total = cum[HDMOE_MAX_GROUPS];
   auto unit_at = [&](int q, C7Unit& u) -> bool {
     const int pos = q * G + ((q & 1) ? G - 1 - bid : bid);
     if (pos >= total) return false;
-    int slot = 0;
-#pragma unroll
-    for (int i = 1; i < HDMOE_MAX_GROUPS; ++i) slot += (i < a.ngroups && pos >= cum[i]) ? 1 : 0;
-    int base = 0, g = 0;
-#pragma unroll
-    for (int i = 0; i < HDMOE_MAX_GROUPS; ++i) if (i == slot) { base = cum[i]; g = a.order[i]; }
-    int ks = 3;
-#pragma unroll
-    for (int i = 0; i < HDMOE_MAX_GROUPS; ++i) if (i == g) ks = a.ks[i];
-    const int s0 = a.seg ? a.seg[g] : 0, s1 = a.seg ? a.seg[g + 1] : a.N;
-    u.g = g; u.ks = ks;
+    const int4 e = *reinterpret_cast<const int4*>(lds + TAB + (lane & (HDMOE_MAX_GROUPS - 1)) * 16);
+    // the last slot that starts at or before pos (first units ascend; absent slots start at INT_MAX)
+    const int slot = __builtin_popcountll(__ballot(e.x <= pos) & ((1ull << HDMOE_MAX_GROUPS) - 1)) - 1;
+    const int base = __builtin_amdgcn_readlane(e.x, slot), s0 = __builtin_amdgcn_readlane(e.y, slot), s1 = __builtin_amdgcn_readlane(e.z, slot);
+    u.gk = __builtin_amdgcn_readlane(e.w, slot);
     if (W16) { u.n = s0 + 2 * (pos - base); u.n2 = u.n + 1 < s1 ? u.n + 1 : -1; }
     else { u.n = s0 + pos - base; u.n2 = -1; }
+    u.xb = u.n * a.imgstride;
+    u.wrow = (u.gk & 7) * a.tapstride;
     return true;
   };
 
@@ -148,9 +160,16 @@ DEVI void conv7_body(const C7Args& a, const int bid, const int G) {
   // tile DMA: lane i of a piece holds pixel i >> 2 (of 16) at row slot 3 + pixel (+ 16 in the right half of a 32-pixel row: same key),
   // LDS chunk i & 3; it fetches the source chunk (i & 3) ^ key(slot)
   const int dpx = lane >> 2;
-  const unsigned xlane = (unsigned)(dpx * cin2 + (((lane & 3) ^ (((3 + dpx) >> 2) & 3)) << 4));
+  // (+ the first image row of this wave: the scalar offset of a piece is then the same for all waves)
+  const unsigned xlane = (unsigned)((tid >> 6) * MB * a.rowstride + dpx * cin2 + (((lane & 3) ^ (((3 + dpx) >> 2) & 3)) << 4));
   // weight DMA: lane i holds output row i >> 2 (of 16), chunk i & 3
   const unsigned wlane = (unsigned)(dpx * cin2 + (((lane & 3) ^ ((dpx >> 2) & 3)) << 4));
+  // piece wave + 8 j of a stage: tap slot ts = piece / (2 CO) (kernel row ky0 + ts), 16-row piece pc = piece % (2 CO) inside the tap.  Its
+  // wave-dependent offset ts * wrow + pc * 16 * Cin * 2 rides in the lane offset (wrow: bytes per kernel row, ks * tapstride)
+  auto wvoff = [&](int j, int wrow) -> unsigned {
+    const int pi = (tid >> 6) + 8 * j;
+    return wlane + (unsigned)((pi / (2 * CO)) * wrow + (pi % (2 * CO)) * (16 * cin2));
+  };
   // fragment reads: row slot (lane's pixel column) + cc (cc = kernel column + 3 - pad, 0 .. 6), 16-channel k-step 0; k-step 1 = ^ 32
   int acol[7];
 #pragma unroll
@@ -160,47 +179,50 @@ DEVI void conv7_body(const C7Args& a, const int bid, const int G) {
   }
   const int wl = (r << 6) + ((h ^ ((r >> 2) & 3)) << 4);        // weight fragment of output row r, k-step 0
 
-  // issue this wave's pieces of chunk c of a unit's image(s) into tile buffer tb: 32 x 32: rows 4 wave .. + 3, two 16-pixel halves each;
-  // 16 x 16: rows 2 wave, 2 wave + 1 of both images (an absent second image reads as zeros: out-of-range offset)
-  auto issue_tile = [&](const C7Unit& u, int c, int tb) {
-    const int lbase = T0 + tb * TILE + 3 * 64;
+  // issue this wave's pieces of a chunk (byte offset coff = 64 * chunk) of a unit's image(s) into tile buffer tb: 32 x 32: rows 4 wave .. + 3,
+  // two 16-pixel halves each (eight pieces, half a row apart); 16 x 16: rows 2 wave, 2 wave + 1 of both images (an absent second image reads
+  // as zeros: out-of-range offset)
+  auto issue_tile = [&](const C7Unit& u, int coff, int tb) {
+    const int lw = T0 + 3 * 64 + (tb ? TILE : 0) + wave * (MB * ROWB);
+    int so = u.xb + coff;
 #pragma unroll
     for (int k = 0; k < PPW; ++k) {
       if (W16) {
-        const int img = k >> 1, row = 2 * wave + (k & 1);
-        const int n = img ? u.n2 : u.n;
-        const int so = (n * 16 + row) * 16 * cin2 + c * 64;
-        const unsigned vo = n < 0 ? 0xFFFFFFFFu : xlane;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lptr_t)(lds + lbase + (img * 16 + row) * ROWB), 16, vo, n < 0 ? 0 : so, 0, 0);
+        const int img = k >> 1;
+        const bool absent = img && u.n2 < 0;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lptr_t)(lds + lw + (img * 16 + (k & 1)) * ROWB), 16, absent ? 0xFFFFFFFFu : xlane, absent ? 0 : so, 0, 0);
+        so += (k & 1) ? a.imgstride - a.rowstride : a.rowstride;
       } else {
-        const int row = 4 * wave + (k >> 1), half = k & 1;
-        const int so = ((u.n * 32 + row) * 32 + half * 16) * cin2 + c * 64;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lptr_t)(lds + lbase + row * ROWB + half * 1024), 16, xlane, so, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lptr_t)(lds + lw + (k >> 1) * ROWB + (k & 1) * 1024), 16, xlane, so, 0, 0);
+        so += a.rowstride >> 1;
       }
     }
   };
-  // this wave's pieces of the weight stage (kernel column kx, rows ky0 .. ky0 + nt) of chunk c, group g, kernel size ks -> ring buffer sp
-  auto issue_wstage = [&](int g, int ks, int c, int blk, int kx, int ky0, int nt, int sp) {
+  // this wave's pieces of a weight stage of nt kernel rows -> ring buffer sp; so: byte offset of the stage's first tap in the chunk (the
+  // same for all waves), wv[j]: lane offset of piece wave + 8 j (wvoff)
+  auto issue_wstage = [&](int so, const unsigned (&wv)[NWJ], int nt, int sp) {
 #pragma unroll
-    for (int j = 0; j < (2 * TCO + 7) / 8; ++j) {
+    for (int j = 0; j < NWJ; ++j) {
       const int pi = wave + 8 * j;
-      const int ts = pi / (2 * CO), pc = pi % (2 * CO);         // tap slot, 16-row piece inside the tap
-      if (ts < nt) {
-        const int tap = (ky0 + ts) * ks + kx;
-        const int so = (int)(((long)g * a.wstride + (long)(tap * a.Cout + blk * 32 * CO + pc * 16) * a.Cin) * 2) + c * 64;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lptr_t)(lds + sp * WBUF + pi * 1024), 16, wlane, so, 0, 0);
-      }
+      if (pi < nt * 2 * CO) __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lptr_t)(lds + (sp ? WBUF : 0) + pi * 1024), 16, wv[j], so, 0, 0);
     }
   };
 
   C7Unit cur, nxt;
   int q = 0;
   if (!unit_at(q, cur)) return;
+  unsigned td0 = ticks();
   bool has_next = unit_at(q + 1, nxt);
+  stampv(11, ticks() - td0);
   int tp = 0, sp = 0;                                           // tile / weight ring parity
   auto nt0_of = [](int ks) { return ks == 3 ? C7Sched<3, CO, GEO::TCO>::nt(0) : (ks == 5 ? C7Sched<5, CO, GEO::TCO>::nt(0) : C7Sched<7, CO, GEO::TCO>::nt(0)); };
   const int nblk = a.Cout / (32 * CO);                          // output-channel blocks of 32 CO: walked one after the other over the same image
-  issue_wstage(cur.g, cur.ks, 0, 0, 0, 0, nt0_of(cur.ks), 0);    // first stage of the unit's schedule: column 0, rows 0 .. nt0
+  {
+    unsigned wv[NWJ];
+#pragma unroll
+    for (int j = 0; j < NWJ; ++j) wv[j] = wvoff(j, cur.wrow);
+    issue_wstage(cur.gk & ~7, wv, nt0_of(cur.gk & 7), 0);      // first stage of the unit's schedule: column 0, rows 0 .. nt0
+  }
   issue_tile(cur, 0, 0);
   bool first = true;
 
@@ -209,6 +231,10 @@ DEVI void conv7_body(const C7Args& a, const int bid, const int G) {
     constexpr int KS = decltype(ks_tag)::value;
     using S = C7Sched<KS, CO, TCO>;
     constexpr int P = (KS - 1) / 2, Q = 3 - P;
+    unsigned wv[NWJ];
+#pragma unroll
+    for (int j = 0; j < NWJ; ++j) wv[j] = wvoff(j, cur.wrow);
+    int wblk = cur.gk & ~7;                                     // byte offset of the output block's weights: advances by blkstride
     for (int blk = 0; blk < nblk; ++blk) {
     const bool last_blk = blk == nblk - 1;
     f32x16 acc[MB][CO];
@@ -222,8 +248,10 @@ DEVI void conv7_body(const C7Args& a, const int bid, const int G) {
       // the tile fetched beside this chunk's first stage: the unit's next chunk; behind the last chunk the first chunk again for the next
       // output block (a one-chunk image simply stays where it is), or the next unit's first chunk
       const bool same_tile = last_chunk && !last_blk && CI == 1;
-      const bool tile_next = (!last_chunk || (!last_blk && CI > 1) || (last_blk && has_next)) && !((a.dbg & 2) && last_chunk);
-      const int tbase = T0 + tp * TILE;
+      const bool tile_next = (!last_chunk || (!last_blk && CI > 1) || (last_blk && has_next)) && !((dbg & 2) && last_chunk);
+      const int tbase = T0 + (tp ? TILE : 0);
+      const int wchunk = wblk + c * 64;
+      int wcol = wchunk;                                        // kernel column of the stage being issued: advances by tapstride
       c7_static_for<S::NS>([&](auto s_c) {
         constexpr int s = decltype(s_c)::value;
         constexpr int kx = s / S::SPC, si = s % S::SPC;
@@ -241,22 +269,31 @@ DEVI void conv7_body(const C7Args& a, const int bid, const int G) {
           c7_wait_barrier<0>();
         }
         // ---- next stage's weights, next tile
+        const unsigned ti0 = ticks();
         if (s + 1 < S::NS) {
-          const int s1 = s + 1;
-          issue_wstage(cur.g, KS, c, blk, s1 / S::SPC, S::ky0(s1 % S::SPC), S::nt(s1 % S::SPC), sp ^ 1);
+          constexpr int s1 = s + 1, k1 = S::ky0(s1 % S::SPC);
+          if (s1 % S::SPC == 0) { wcol += a.tapstride; asm volatile("" : "+s"(wcol)); }   // (opaque: the column offsets stay a chain of s_add)
+          issue_wstage(wcol + k1 * cur.wrow, wv, S::nt(s1 % S::SPC), sp ^ 1);
         } else if (!last_chunk) {
-          issue_wstage(cur.g, KS, c + 1, blk, 0, S::ky0(0), S::nt(0), sp ^ 1);
+          issue_wstage(wchunk + 64, wv, S::nt(0), sp ^ 1);
         } else if (!last_blk) {
-          issue_wstage(cur.g, KS, 0, blk + 1, 0, S::ky0(0), S::nt(0), sp ^ 1);
+          issue_wstage(wblk + a.blkstride, wv, S::nt(0), sp ^ 1);
         } else if (has_next) {
-          issue_wstage(nxt.g, nxt.ks, 0, 0, 0, 0, nt0_of(nxt.ks), sp ^ 1);
+          unsigned wn[NWJ];
+#pragma unroll
+          for (int j = 0; j < NWJ; ++j) wn[j] = wvoff(j, nxt.wrow);
+          issue_wstage(nxt.gk & ~7, wn, nt0_of(nxt.gk & 7), sp ^ 1);
         }
         if (s == 0 && tile_next) {
-          if (!last_chunk) issue_tile(cur, c + 1, tp ^ 1); else if (!last_blk) issue_tile(cur, 0, tp ^ 1); else issue_tile(nxt, 0, tp ^ 1);
+          if (!last_chunk) issue_tile(cur, (c + 1) * 64, tp ^ 1); else if (!last_blk) issue_tile(cur, 0, tp ^ 1); else issue_tile(nxt, 0, tp ^ 1);
         }
+        if constexpr (DBG) t_iss += ticks() - ti0;
+        // (the two scheduling barriers keep the issue block, the MFMA block and its interleave hints separate regions, as the run-time
+        // ablation tests of the development kernel do: merged, the scheduler takes 8 - 29 more VGPRs)
+        __builtin_amdgcn_sched_barrier(0);
         // ---- MFMAs of the stage: per 16-channel k-step, the nt + MB - 1 input rows it touches, then per kernel row its weight fragment(s)
-        if (!(a.dbg & 1)) {
-          const int wb = sp * WBUF;
+        if (!(dbg & 1)) {
+          const int wb = sp ? WBUF : 0;
           const int row0 = MB * (tid >> 6) - P + ky0;           // image row of fragment j = 0 (per-lane arithmetic on purpose: the row bases then live in VGPRs, not in spilled SGPRs)
 #pragma unroll
           for (int k2 = 0; k2 < 2; ++k2) {
@@ -281,9 +318,10 @@ DEVI void conv7_body(const C7Args& a, const int bid, const int G) {
             }
           }
         }
+        __builtin_amdgcn_sched_barrier(0);
         // schedule of the stage's block: a few fragment reads ahead, then one read per MFMA until the reads run out (left alone the compiler
         // puts every ds_read right in front of its first MFMA and a wave sits out the LDS latency once per tap)
-        if ((CO == 1 || W16) && !(a.dbg & 16)) {                // (two output blocks on 32 x 32 maps: 128 accumulator registers, the interleave spills)
+        if ((CO == 1 || W16) && !(dbg & 16)) {                // (two output blocks on 32 x 32 maps: 128 accumulator registers, the interleave spills)
           constexpr int NRD = 2 * ((nt + MB - 1) + nt * CO), NMF = 2 * nt * MB * CO, LEAD = 4, R = NMF / NRD > 0 ? NMF / NRD : 1;
           __builtin_amdgcn_sched_group_barrier(0x100, LEAD < NRD ? LEAD : NRD, 0);
 #pragma unroll
@@ -297,7 +335,9 @@ DEVI void conv7_body(const C7Args& a, const int bid, const int G) {
       if (!same_tile) tp ^= 1;
     }
     const int cobase = blk * 32 * CO;
+    wblk += a.blkstride;
     stamp(4);
+    stampv(10, t_iss); t_iss = 0;
     // ---- epilogue: y = alpha * acc + beta * res, 16-byte stores (register quads paired across the half-waves)
     if constexpr (EPI == 1) {
       // ---- FiLM-backward epilogue: g = bf16(alpha * acc) is d(loss)/dh of h = dropout(mp_silu(u * e)); the store is du, the sums are de.
@@ -373,7 +413,7 @@ DEVI void conv7_body(const C7Args& a, const int bid, const int G) {
         for (int w = 0; w < 8; ++w) sum += part[(w * NIMG + img) * NCH + c];
         if (n >= 0) a.film_de[(long)n * a.Cout + cobase + c] = sum;
       }
-    } else if (!(a.dbg & 4)) {
+    } else if (!(dbg & 4)) {
       bf16* Y = (bf16*)a.y;
       const bf16* R = (const bf16*)a.res;
       const int nimg = W16 ? ((r >> 4) ? cur.n2 : cur.n) : cur.n;
@@ -412,14 +452,16 @@ DEVI void conv7_body(const C7Args& a, const int bid, const int G) {
   };
 
   while (true) {
-    if ((KMASK & 4) && cur.ks == 7) run_unit(std::integral_constant<int, 7>{});
-    else if ((KMASK & 2) && cur.ks == 5) run_unit(std::integral_constant<int, 5>{});
+    if ((KMASK & 4) && (cur.gk & 7) == 7) run_unit(std::integral_constant<int, 7>{});
+    else if ((KMASK & 2) && (cur.gk & 7) == 5) run_unit(std::integral_constant<int, 5>{});
     else run_unit(std::integral_constant<int, 3>{});
     first = false;
     if (!has_next) break;
     cur = nxt;
     ++q;
+    td0 = ticks();
     has_next = unit_at(q + 1, nxt);
+    stampv(11, ticks() - td0);
   }
 #endif
 }

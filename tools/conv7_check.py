@@ -144,9 +144,13 @@ if "--time-bwd" in sys.argv:
         time_bwd(256, 32, Cin, Cout, (3,))
 
 
+VALUE_TAGS = {10: "issue", 11: "decode"}
+
+
 def stamps7(N, R, Cin, Cout, ks):
     """One conv7 launch with in-kernel stamps of workgroup 0: per wave (tag: cycles since the previous stamp).  tags: 1 start, 2 at a chunk's first
-    stage barrier, 3 past it (tile + weights landed), 4 MFMA stages done, 5 epilogue issued."""
+    stage barrier, 3 past it (tile + weights landed), 4 MFMA stages done, 5 epilogue issued.  Value tags (ticks, not a time): 10 = spent in the DMA
+    issue blocks of the stages since the last "mfma'd" (part of the <bar .. mfma'd span), 11 = one unit decode."""
     import ctypes, torch
     from hdmoe_hip._lib import call, lib
     dev = "cuda"
@@ -179,6 +183,9 @@ def stamps7(N, R, Cin, Cout, ks):
             if v == 0:
                 break
             tag, t = (v >> 56) & 0xFF, v & ((1 << 56) - 1)
+            if tag in VALUE_TAGS:
+                out.append(f"{VALUE_TAGS[tag]}={t}")
+                continue
             out.append(f"{names.get(tag, tag)}:{t - prev}")
             prev = t
         print(f" wave {w}: " + " ".join(out), flush=True)
@@ -217,6 +224,9 @@ def stamps_bwd(N, R, Cin, Cout, ks):
                 if v == 0:
                     break
                 tag, t = (v >> 56) & 0xFF, v & ((1 << 56) - 1)
+                if sect == 0 and tag in VALUE_TAGS:
+                    out.append(f"{VALUE_TAGS[tag]}={t}")
+                    continue
                 out.append(f"{tag}:{t - prev}")
                 prev = t
             print(f" {nm} wave {w}: " + " ".join(out), flush=True)
@@ -225,3 +235,4 @@ def stamps_bwd(N, R, Cin, Cout, ks):
 if "--stamps-bwd" in sys.argv:
     stamps_bwd(512, 32, 32, 32, (3, 3, 5, 5))
     stamps_bwd(512, 32, 64, 64, (3, 3, 5, 5))
+    stamps_bwd(512, 16, 64, 64, (3, 3, 5, 5))
