@@ -20,7 +20,7 @@ import torch
 
 from hdmoe_hip.dp import GradBuckets
 from hdmoe_hip.optim import FusedAdamW
-from .utils import EDM_LOSS, MaskGenerator, ZetaScheduler, sample_sigma_hybrid
+from .utils import EDM_LOSS, DeviceInputs, MaskGenerator, ZetaScheduler, sample_sigma_hybrid
 
 
 def build_optimizer(model: torch.nn.Module, optim_config: Dict[str, Any]) -> FusedAdamW:
@@ -82,11 +82,24 @@ def load_checkpoint(path: str, model: torch.nn.Module, optimizer: Optional[torch
 
 class Trainer:
     """One training iteration of reference training.py:110-197 as a reusable object (device-side sigma / mask / noise
-    generation, fused loss, flat-bucket gradient all-reduce, fused clip + AdamW)."""
+    generation, fused loss, flat-bucket gradient all-reduce, fused clip + AdamW).
+
+    ``device_inputs=True``: sigma, the noised latents, both router masks and zeta of a step come from one fused HIP call
+    (`Utils.utils.DeviceInputs`), keyed by ``(seed, rank, step_idx)`` instead of torch's generator; zeta reaches the model as a device
+    scalar.  ``seed=None`` takes ``hdmoe_hip.ops.next_seed()`` once, here.  ``step_idx`` is assignable: a run resumed at step k
+    regenerates step k's inputs.
+
+    ``graphed=True`` (implies ``device_inputs``): forward + loss + backward run as the replay of `hdmoe_hip.graph.StagedStep` -- what
+    bench.py times -- over static buffers.  The first ``train_step`` fixes the latent and text shapes and captures; a capture failure
+    raises (no eager fallback), and a later batch of another shape raises ValueError before any device work.  The tensors in the
+    returned dictionary are then the static buffers of the captured step: valid until the next ``train_step`` overwrites them, so
+    copy what has to live longer.
+
+    With both keywords at their defaults nothing changes: the inputs come from torch's generator and the step is launched eagerly."""
 
     def __init__(self, model, model_config, optim_config, loss_config, mask_config, zeta_config, max_grad_norm: float = 1.0,
                  fuse_clip_into_step: bool = True, logger=None, ema=None, ema_snapshot_every: Optional[int] = None,
-                 ema_snapshot_dir: Optional[str] = None):
+                 ema_snapshot_dir: Optional[str] = None, device_inputs: bool = False, graphed: bool = False, seed: Optional[int] = None):
         if ema_snapshot_every is not None:
             if ema is None:
                 raise ValueError("Trainer: ema_snapshot_every needs an ema")
@@ -117,17 +130,111 @@ class Trainer:
         self.ema_snapshot_dir = ema_snapshot_dir
         self._clip_params = [p for p in model.parameters()]
         self.step_idx = 0
+        self.graphed = bool(graphed)
+        self.device_inputs = bool(device_inputs) or self.graphed
+        self.inputs = None
+        if self.device_inputs:
+            if seed is None:
+                from hdmoe_hip import ops
+                seed = ops.next_seed()
+            rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
+            self.seed = int(seed)
+            self.inputs = DeviceInputs(model_config, mask_config, zeta_config, self.unet_mask_gen, self.vit_mask_gen, self.zeta_sched,
+                                       seed=self.seed, rank=rank)
+        # model_config2 takes the soft-gate transition from the mask config; model_config1 learns its scaling and has no such arguments
+        import inspect
+        names = inspect.signature(model.forward).parameters
+        self._model_extra = {"transition_point": mask_config["p_mean"], "softness": mask_config["p_std"]} if "transition_point" in names else {}
+        self._staged = None                                  # hdmoe_hip.graph.StagedStep, built by the first graphed train_step
+        self._lat = self._text = None                        # its static latent / text buffers
+
+    def _fwd_loss(self, x, x0, sigma, text, unet_mask, vit_mask, zeta):
+        out_model = self.model(x=x, sigma=sigma, text_emb=text, Unet_router_mask=unet_mask, Vit_router_mask=vit_mask, zeta=zeta,
+                               return_log_var=True, **self._model_extra)
+        return out_model, self.criterion(sigma_vec=sigma, x=x0, sigma=sigma, out_model=out_model)
+
+    def _build_staged(self, latent_images: torch.Tensor, text_emb: torch.Tensor) -> None:
+        """Fix the shapes, fill the static buffers for `step_idx` and capture the staged step (bench.py's replay path)."""
+        from hdmoe_hip import graph as hgraph
+        if not latent_images.is_cuda:
+            raise RuntimeError("hdmoe_hip: tensors must live on the GPU (no CPU fallback in the product path)")
+        dev = latent_images.device
+        self._lat = latent_images.detach().to(torch.float32).contiguous().clone()
+        self._text = text_emb.detach().contiguous().clone()
+        self._shapes = (tuple(latent_images.shape), tuple(text_emb.shape))
+        b = self.inputs.generate(self._lat, self.step_idx)
+
+        def fwd_bwd():
+            self.buckets.zero_grad()
+            out_model, loss = self._fwd_loss(b["x"], self._lat, b["sigma"], self._text, b["unet_mask"], b["vit_mask"], b["zeta"])
+            hgraph.backward(loss["loss"])
+            return {"loss": loss, "out_model": out_model}
+
+        self.buckets.enabled = False                         # no collectives from autograd hooks while capturing
+        try:
+            self._staged = hgraph.StagedStep(fwd_bwd, dev)
+        finally:
+            self.buckets.enabled = True
+        if self.buckets.world > 1 or self.buckets.force:     # a branch's bucket goes out as soon as its backward section is launched
+            self._staged.after = self.buckets.staged_hooks(self._staged)
+        # the warm-up forwards accumulated into the routed-row counters: the first optimizer step must see only its own routing
+        seen = set()
+        for lst, _ in self.optimizer._usage.values():
+            u = getattr(lst, "_hdmoe_usage", None)
+            if u is not None and id(lst) not in seen:
+                seen.add(id(lst))
+                u.zero_()
+
+    def _graphed_fwd_bwd(self, latent_images: torch.Tensor, text_emb: torch.Tensor):
+        if self._staged is None:
+            self._build_staged(latent_images, text_emb)
+        elif (tuple(latent_images.shape), tuple(text_emb.shape)) != self._shapes:
+            raise ValueError(f"Trainer(graphed=True): batch shapes {tuple(latent_images.shape)}, {tuple(text_emb.shape)} differ from the "
+                             f"captured step's {self._shapes[0]}, {self._shapes[1]}")
+        self._lat.copy_(latent_images)
+        self._text.copy_(text_emb)
+        b = self.inputs.generate(self._lat, self.step_idx)
+        res = self._staged()
+        self.buckets.finish()
+        return res["out_model"], res["loss"], b["sigma"]
 
     def train_step(self, latent_images: torch.Tensor, text_emb: torch.Tensor) -> dict:
+        """One iteration on (latents (B,C,H,W), text embeddings).  Returns {"loss", "out_model", "sigma"}; with ``graphed=True`` their
+        tensors are the captured step's static buffers, valid until the next call."""
+        if self.device_inputs:
+            return self._train_step_device(latent_images, text_emb)
         cfg, mc, step = self.cfg, self.mask_cfg, self.step_idx
         dev = latent_images.device
         sigma = sample_sigma_hybrid(batch_size=latent_images.shape[0], sigma_max=cfg["sigma_max"], sigma_min=cfg["sigma_min"],
                                     p_mean=mc["p_mean"], p_std=mc["p_std"], extreme_prob=0.5, device=dev)
         images_noised = latent_images + torch.randn_like(latent_images) * sigma
-        out_model = self.model(x=images_noised, sigma=sigma, text_emb=text_emb, Unet_router_mask=self.unet_mask_gen(sigma=sigma, step=step),
-                               Vit_router_mask=self.vit_mask_gen(sigma=sigma, step=step), zeta=self.zeta_sched.get_zeta(step=step),
-                               transition_point=mc["p_mean"], softness=mc["p_std"], return_log_var=True)
-        loss = self.criterion(sigma_vec=sigma, x=latent_images, sigma=sigma, out_model=out_model)
+        out_model, loss = self._fwd_loss(images_noised, latent_images, sigma, text_emb, self.unet_mask_gen(sigma=sigma, step=step),
+                                         self.vit_mask_gen(sigma=sigma, step=step), self.zeta_sched.get_zeta(step=step))
+        self._log_forward(step, loss, out_model, sigma)
+        self.buckets.zero_grad()
+        loss["loss"].backward()
+        self.buckets.finish()
+        return self._update(step, loss, out_model, sigma)
+
+    def _train_step_device(self, latent_images: torch.Tensor, text_emb: torch.Tensor) -> dict:
+        step = self.step_idx
+        if self.graphed:
+            out_model, loss, sigma = self._graphed_fwd_bwd(latent_images, text_emb)
+            self._log_forward(step, loss, out_model, sigma)
+        else:
+            if latent_images.dtype != torch.float32 or not latent_images.is_contiguous():
+                latent_images = latent_images.to(torch.float32).contiguous()
+            b = self.inputs.generate(latent_images, step)
+            sigma = b["sigma"]
+            out_model, loss = self._fwd_loss(b["x"], latent_images, sigma, text_emb, b["unet_mask"], b["vit_mask"], b["zeta"])
+            self._log_forward(step, loss, out_model, sigma)
+            self.buckets.zero_grad()
+            loss["loss"].backward()
+            self.buckets.finish()
+        return self._update(step, loss, out_model, sigma)
+
+    def _log_forward(self, step: int, loss: dict, out_model: dict, sigma: torch.Tensor) -> None:
+        mc = self.mask_cfg
         lg = self.logger
         if lg is not None:                                   # same calls, same order as reference training.py:160-188
             lg.log_training_step(step=step, loss_dict=loss, zeta=self.zeta_sched.get_zeta(step=step),
@@ -136,9 +243,10 @@ class Trainer:
             lg.log_router_statistics(step=step, unet_probs=out_model["Unet_router_loss"], vit_probs=out_model["vit_router_loss"],
                                      sigma=sigma, p_mean=mc["p_mean"], p_std=mc["p_std"])
             lg.log_scaling_gating(scaling_factors=out_model["scaling_net_out"], gate_weights=out_model["out_gate"], sigma=sigma)
-        self.buckets.zero_grad()
-        loss["loss"].backward()
-        self.buckets.finish()
+
+    def _update(self, step: int, loss: dict, out_model: dict, sigma: torch.Tensor) -> dict:
+        """Everything behind the backward, in the reference's order: gradient logs, clip + AdamW, EMA, scheduler."""
+        lg = self.logger
         if lg is not None:
             lg.log_gradients(step=step, model=self.model.net)
             lg.log_weight_statistics(step=step, model=self.model.net)

@@ -3,7 +3,8 @@
 
 ``EDM_LOSS`` runs as one fused HIP forward + one fused backward with no ``.item()`` host syncs.  The input generators
 produce a few (B,)/(B,E) values per step from torch's RNG before the timed path starts; they are kept as plain
-torch device ops (data generation, not the denoiser's arithmetic).
+torch device ops (data generation, not the denoiser's arithmetic).  ``DeviceInputs`` is their fused form: one HIP call per step
+writes sigma, the noised latents, both masks and zeta into static buffers, keyed by (seed, rank, step) instead of a generator.
 """
 from __future__ import annotations
 
@@ -105,3 +106,54 @@ class MaskGenerator(nn.Module):
             progress = min(int(step / (self.total_steps * self.step_size)) / int(1.0 / self.step_size), 1.0)
             return self.bandwidth + (self.max_bw - self.bandwidth) * progress
         raise ValueError(f"Unknown bandwidth strategy: {self.strat_band}")
+
+
+class DeviceInputs:
+    """The per-step training inputs from one fused HIP call (csrc/traingen.hip; RNG contract in include/hdmoe.h) instead of
+    ``sample_sigma_hybrid`` + ``randn_like`` + two ``MaskGenerator`` calls on torch's generator.
+
+    It owns the static output buffers: allocated by the first ``generate`` and fixed to that latent shape, so captured graphs can
+    read them.  The outputs depend on ``(seed, rank, step)`` alone -- no generator state, no host sync -- so a resumed run regenerates
+    the inputs of any step.  Bandwidths and zeta are the host schedulers' values for the step."""
+
+    GOLDEN = 0x9E3779B97F4A7C15
+
+    def __init__(self, model_config, mask_config, zeta_config, unet_mask_gen: "MaskGenerator", vit_mask_gen: "MaskGenerator",
+                 zeta_sched: "ZetaScheduler", seed: int, rank: int = 0, extreme_prob: float = 0.5):
+        self.cfg, self.mask_cfg, self.zeta_cfg = model_config, mask_config, zeta_config
+        self.unet_mask_gen, self.vit_mask_gen, self.zeta_sched = unet_mask_gen, vit_mask_gen, zeta_sched
+        if unet_mask_gen.expert_centers.numel() != vit_mask_gen.expert_centers.numel() or unet_mask_gen.min_active != vit_mask_gen.min_active:
+            raise ValueError("DeviceInputs: both mask generators need the same number of experts and the same min_active")
+        self.seed = (int(seed) + int(rank) * self.GOLDEN) & 0xFFFFFFFFFFFFFFFF
+        self.extreme_prob = float(extreme_prob)
+        self.shape = None
+        self.buf = None
+
+    def _alloc(self, latents: torch.Tensor) -> None:
+        dev, B = latents.device, latents.shape[0]
+        self._ucen = self.unet_mask_gen.expert_centers.detach().to(device=dev, dtype=torch.float32).contiguous()
+        self._vcen = self.vit_mask_gen.expert_centers.detach().to(device=dev, dtype=torch.float32).contiguous()
+        E = self._ucen.numel()
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.buf = {"sigma": torch.zeros(B, 1, 1, 1, **f32), "x": torch.zeros(latents.shape, **f32), "unet_mask": torch.zeros(B, E, **f32),
+                    "vit_mask": torch.zeros(B, E, **f32), "zeta": torch.zeros(1, **f32), "src": torch.zeros(B, dtype=torch.int32, device=dev)}
+        self.shape = tuple(latents.shape)
+
+    def generate(self, latents: torch.Tensor, step: int) -> dict:
+        """{"sigma", "x", "unet_mask", "vit_mask", "zeta", "src"}: the static buffers, holding step `step`'s inputs for `latents`
+        (B,C,H,W) float32 contiguous, until the next call."""
+        if latents.ndim != 4:
+            raise ValueError(f"DeviceInputs: latents are (B,C,H,W), got {tuple(latents.shape)}")
+        if self.shape is not None and tuple(latents.shape) != self.shape:
+            raise ValueError(f"DeviceInputs: latents {tuple(latents.shape)} differ from the static buffers' {self.shape}")
+        if self.buf is None:
+            if not latents.is_cuda:
+                raise RuntimeError("hdmoe_hip: tensors must live on the GPU (no CPU fallback in the product path)")
+            self._alloc(latents)
+        b, mc = self.buf, self.mask_cfg
+        ops.train_inputs(b["x"], b["sigma"], b["unet_mask"], b["vit_mask"], b["zeta"], b["src"], latents, self._ucen, self._vcen, self.seed,
+                         int(step), sigma_min=self.cfg["sigma_min"], sigma_max=self.cfg["sigma_max"], p_mean=mc["p_mean"], p_std=mc["p_std"],
+                         extreme_prob=self.extreme_prob, unet_bw=self.unet_mask_gen.bandwidth_scheduler(step),
+                         vit_bw=self.vit_mask_gen.bandwidth_scheduler(step), min_active=self.unet_mask_gen.min_active,
+                         zeta=self.zeta_sched.get_zeta(step=step))
+        return b

@@ -187,3 +187,26 @@ DEVI void mix_seed(uint32_t& lo, uint32_t& hi, const unsigned long long* seed_de
     lo = (uint32_t)k; hi = (uint32_t)(k >> 32);
   }
 }
+
+// Four standard normals of Philox block q (Box-Muller on the u01 pairs (r0, r1), (r2, r3)): element 4 q + j of hdmoe_randn is v[j].  One
+// definition for randn_kernel, the sampler's stochastic stage kernels and the training-input generator, so that they draw the same values
+// by construction.
+DEVI void randn4(long q, uint32_t seed_lo, uint32_t seed_hi, float* v) {
+  uint32_t r[4];
+  philox((uint32_t)q, (uint32_t)(q >> 32), seed_lo, seed_hi, r);
+  const float a0 = sqrtf(-2.f * logf(u01(r[0]))), a1 = sqrtf(-2.f * logf(u01(r[2])));
+  const float t0 = 6.28318530717958648f * u01(r[1]), t1 = 6.28318530717958648f * u01(r[3]);
+  v[0] = a0 * cosf(t0); v[1] = a0 * sinf(t0); v[2] = a1 * cosf(t1); v[3] = a1 * sinf(t1);
+}
+// W fp32 elements per thread: 16-byte loads / stores when W == 4 (the launcher checks n % 4 and the alignment), scalar otherwise
+template <int W> DEVI void ldw(float* f, const float* p) {
+  if constexpr (W == 4) vload<float>(f, p); else f[0] = *p;
+}
+template <int W> DEVI void stw(float* p, const float* f) {
+  if constexpr (W == 4) vstore<float>(p, f); else *p = f[0];
+}
+// the draws of elements off ... off + W - 1 (off % W == 0): element j is lane j % 4 of block j / 4 whatever W is
+template <int W> DEVI void eps_w(float* e, long off, uint32_t lo, uint32_t hi) {
+  if constexpr (W == 4) randn4(off >> 2, lo, hi, e);
+  else { float v[4]; randn4(off >> 2, lo, hi, v); e[0] = v[off & 3]; }
+}

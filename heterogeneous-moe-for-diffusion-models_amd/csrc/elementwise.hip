@@ -52,33 +52,13 @@ __global__ void sched_pick_kernel(float* sigma, const double* t, const int* idx,
 __global__ void idx_advance_kernel(int* idx) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *idx += 1;
 }
-// Four standard normals of Philox block q (Box-Muller on the u01 pairs (r0, r1), (r2, r3)): element 4 q + j of hdmoe_randn is v[j].  One
-// definition for randn_kernel and the sampler's stochastic stage kernels, so that they draw the same values by construction.
-DEVI void randn4(long q, uint32_t seed_lo, uint32_t seed_hi, float* v) {
-  uint32_t r[4];
-  philox((uint32_t)q, (uint32_t)(q >> 32), seed_lo, seed_hi, r);
-  const float a0 = sqrtf(-2.f * logf(u01(r[0]))), a1 = sqrtf(-2.f * logf(u01(r[2])));
-  const float t0 = 6.28318530717958648f * u01(r[1]), t1 = 6.28318530717958648f * u01(r[3]);
-  v[0] = a0 * cosf(t0); v[1] = a0 * sinf(t0); v[2] = a1 * cosf(t1); v[3] = a1 * sinf(t1);
-}
+// (randn4 / ldw / stw / eps_w live in common.h: the training-input generator, csrc/traingen.hip, draws the same values)
 // Philox key of sampler stage i: the key of hdmoe_randn(seed = *seed, *seed_dev = i).  Both words come from device memory, so a captured
 // stage replays with the noise of the current call and stage.
 DEVI void stage_key(const unsigned long long* seed, int i, uint32_t& lo, uint32_t& hi) {
   const unsigned long long s = *seed, c = (unsigned long long)i;
   lo = (uint32_t)s; hi = (uint32_t)(s >> 32);
   mix_seed(lo, hi, &c);
-}
-// W fp32 elements per thread: 16-byte loads / stores when W == 4 (the launcher checks n % 4 and the alignment), scalar otherwise
-template <int W> DEVI void ldw(float* f, const float* p) {
-  if constexpr (W == 4) vload<float>(f, p); else f[0] = *p;
-}
-template <int W> DEVI void stw(float* p, const float* f) {
-  if constexpr (W == 4) vstore<float>(p, f); else *p = f[0];
-}
-// the draws of elements off ... off + W - 1 (off % W == 0): element j is lane j % 4 of block j / 4 whatever W is
-template <int W> DEVI void eps_w(float* e, long off, uint32_t lo, uint32_t hi) {
-  if constexpr (W == 4) randn4(off >> 2, lo, hi, e);
-  else { float v[4]; randn4(off >> 2, lo, hi, v); e[0] = v[off & 3]; }
 }
 // Known region (inpainting) on its probability-flow path at sigma = s: x <- m (x0 + s noise) + (1 - m) x.  Evaluated in exactly this form
 // (not as a lerp) so that m = 1 at s = 0 gives x0 and m = 0 gives x bit-for-bit.  Epilogue of the stage kernels, and the host-loop form.
@@ -1128,6 +1108,17 @@ __global__ void randn_kernel(float* out, uint32_t seed_lo, uint32_t seed_hi, con
     for (int j = 0; j < 4; ++j) if (q * 4 + j < n) out[q * 4 + j] = scale * v[j];
   }
 }
+// the same draws with the scale read from device memory: a captured launch follows a scale that changes between replays (the trainer's zeta)
+__global__ void randn_ds_kernel(float* out, uint32_t seed_lo, uint32_t seed_hi, const unsigned long long* seed_dev, const float* scale, long n) {
+  mix_seed(seed_lo, seed_hi, seed_dev);
+  const float sc = *scale;
+  GRID_STRIDE(q, (n + 3) / 4) {
+    float v[4];
+    randn4(q, seed_lo, seed_hi, v);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) if (q * 4 + j < n) out[q * 4 + j] = sc * v[j];
+  }
+}
 
 // out = sum of up to 16 same-shaped tensors: the backward of a fan-out (a tensor consumed by n layers) in ONE pass -- autograd's own
 // accumulation is n - 1 separate add launches over the same data
@@ -1593,6 +1584,11 @@ int hdmoe_dropout(void* out, const void* x, unsigned long long seed, const unsig
 }
 int hdmoe_randn(float* out, unsigned long long seed, const unsigned long long* seed_dev, float scale, long n, hipStream_t stream) {
   L1D(randn_kernel, (n + 3) / 4, out, (uint32_t)seed, (uint32_t)(seed >> 32), seed_dev, scale, n);
+  return hdmoe_launch_status();
+}
+int hdmoe_randn_ds(float* out, unsigned long long seed, const unsigned long long* seed_dev, const float* scale, long n, hipStream_t stream) {
+  if (!out || !scale || n < 0) return HDMOE_EINVAL;
+  L1D(randn_ds_kernel, (n + 3) / 4, out, (uint32_t)seed, (uint32_t)(seed >> 32), seed_dev, scale, n);
   return hdmoe_launch_status();
 }
 int hdmoe_seed_advance(unsigned long long* seed_dev, hipStream_t stream) {

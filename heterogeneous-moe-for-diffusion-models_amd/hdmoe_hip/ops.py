@@ -1809,9 +1809,16 @@ def dropout(x: Tensor, p: float, training: bool) -> Tensor:
     return _DropoutFn.apply(x, float(p), _next_seed())
 
 
-def randn_like(x: Tensor, scale: float) -> Tensor:
+def randn_like(x: Tensor, scale) -> Tensor:
+    """float32 normals of x's shape times `scale`, one value of the seed stream per call.  `scale`: a float, or a 1-element float32 device
+    tensor that the kernel reads at run time -- the same values bit for bit, and a captured launch follows the tensor between replays."""
     out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-    call("hdmoe_randn", out, _next_seed(), step_counter(x.device), float(scale), out.numel())
+    if torch.is_tensor(scale):
+        if scale.dtype != torch.float32 or scale.numel() != 1 or scale.device != x.device:
+            raise ValueError("randn_like: a tensor scale is one float32 element on x's device")
+        call("hdmoe_randn_ds", out, _next_seed(), step_counter(x.device), scale, out.numel())
+    else:
+        call("hdmoe_randn", out, _next_seed(), step_counter(x.device), float(scale), out.numel())
     return out
 
 
@@ -1822,6 +1829,35 @@ def randn_keyed(x: Tensor, seed: int, stage: int) -> Tensor:
     key = (int(seed) + int(stage) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
     call("hdmoe_randn", out, key, None, 1.0, out.numel())
     return out
+
+
+def train_inputs(x: Tensor, sigma: Tensor, unet_mask: Tensor, vit_mask: Tensor, zeta_out: Tensor, src: Tensor, x0: Tensor,
+                 unet_centers: Tensor, vit_centers: Tensor, seed: int, step: int, *, sigma_min: float, sigma_max: float, p_mean: float,
+                 p_std: float, extreme_prob: float, unet_bw: float, vit_bw: float, min_active: int, zeta: float) -> None:
+    """The inputs of training step `step` under `seed`, written into the caller's buffers in two launches (include/hdmoe.h,
+    hdmoe_train_inputs: sigma (B,1,1,1), x = x0 + sigma eps, both router masks (B,E), zeta (1,), src (B,) int32).  Element j of eps is
+    element j of randn_keyed(x, seed, 4 * step).  Nothing is read from torch's generator or the library's seed stream and nothing
+    syncs.  ValueError -- before anything is written -- for B > 4096, E > 8, min_active > E, a non-contiguous or non-float32 tensor."""
+    B = x0.shape[0] if x0.ndim else 0
+    E = unet_centers.numel()
+    want = {"x": (x, x0.shape, torch.float32), "sigma": (sigma, None, torch.float32), "unet_mask": (unet_mask, (B, E), torch.float32),
+            "vit_mask": (vit_mask, (B, E), torch.float32), "zeta": (zeta_out, None, torch.float32), "src": (src, (B,), torch.int32),
+            "x0": (x0, None, torch.float32), "unet_centers": (unet_centers, (E,), torch.float32), "vit_centers": (vit_centers, (E,), torch.float32)}
+    for name, (t, shape, dt) in want.items():
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"train_inputs: {name} must be contiguous {dt}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"train_inputs: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    if B < 1 or sigma.numel() != B or zeta_out.numel() != 1 or int(step) < 0:
+        raise ValueError("train_inputs: sigma holds B values, zeta one, step >= 0, B >= 1")
+    try:
+        call("hdmoe_train_inputs", x, sigma, unet_mask, vit_mask, zeta_out, src, x0, unet_centers, vit_centers,
+             int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), B, x0.numel() // B, E, int(min_active), sigma_min, sigma_max, p_mean, p_std,
+             extreme_prob, unet_bw, vit_bw, zeta)
+    except RuntimeError as exc:
+        if "invalid argument" in str(exc):                     # B > 4096, E > 8, min_active > E, a bad sigma range: nothing was launched
+            raise ValueError(f"train_inputs: out of range (B={B} <= 4096, E={E} <= 8, min_active={min_active} <= E): {exc}") from None
+        raise
 
 
 # =====================================================================================================

@@ -316,7 +316,32 @@ int hdmoe_take_col_pos_bwd(float* dw, const float* g, const float* w, long B, in
 int hdmoe_dropout(void* out, const void* x, unsigned long long seed, const unsigned long long* seed_dev, float p, long n, int dtype,
                   HS stream);                                                                                    /* F.dropout, model_components.py:245-246 */
 int hdmoe_randn(float* out, unsigned long long seed, const unsigned long long* seed_dev, float scale, long n, HS stream); /* randn*zeta, :155-156 */
+/* randn_ds: hdmoe_randn with the scale read from device memory (*scale, fp32): bit for bit what hdmoe_randn writes for scale = *scale,
+ * and a captured launch follows a scale that changes between replays.  HDMOE_EINVAL for a NULL out / scale or n < 0. */
+int hdmoe_randn_ds(float* out, unsigned long long seed, const unsigned long long* seed_dev, const float* scale, long n, HS stream);
 int hdmoe_seed_advance(unsigned long long* seed_dev, HS stream);
+
+/* ---- training inputs of one step, made on the device  (csrc/traingen.hip; reference Utils/utils.py:26-61, 228-330, training.py:125-135) ----
+ * One call per step, two launches: a one-workgroup kernel (sigma, shuffle, both router masks, zeta) and a 16-byte-access noising kernel.
+ * Every output goes to a caller-owned static buffer, nothing is read back by the host, so the buffers can feed captured graphs.
+ *   sigma (B) , src (B, int32), unet_mask / vit_mask (B, E) fp32 0/1, zeta_out (1), x (B, chw) = x0 + sigma[b] eps
+ * RNG contract.  Every draw is Philox4x32-10 under the key hdmoe_randn(seed = seed, *seed_dev = 4 step + r) uses, i.e.
+ * seed + (4 step + r) * 0x9E3779B97F4A7C15 (mod 2^64); value s of a stream is lane s % 4 of Philox block s / 4:
+ *   r = 0  eps: element j of eps (flat over (B, chw)) is element j of hdmoe_randn(.., scale = 1) under that key, whatever chw % 4 is;
+ *   r = 1  z_s: element s of hdmoe_randn under that key (the log-normal draws);
+ *   r = 2  u_s = u01(word s) (the log-uniform draws);      r = 3  k_i = u01(word i) (the shuffle keys).
+ * Nothing reads torch's generator or the library's seed stream; (seed, step) alone fix the outputs.
+ * Semantics.  n_ln = (int)(B (1 - extreme_prob)) in double.  Pre-shuffle value s is exp(p_mean + p_std z_s) for s < n_ln and
+ * exp(ln sigma_min + u_s (ln sigma_max - ln sigma_min)) otherwise, clamped to [sigma_min, sigma_max].  src[i] = the rank of k_i among the B
+ * keys (ties: the lower position first), a permutation of 0 .. B-1; sigma[i] = value src[i].  Masks, per router with its centers (E) and
+ * bandwidth: pct = clamp(0.5 (1 + erf((ln sigma - p_mean) / (p_std sqrt 2))), 0, 1), dist_e = |pct - center_e|, mask = dist_e <= bw, and the
+ * min_active nearest experts (ties: the lower index) are 1 in any case.  *zeta_out = zeta.
+ * HDMOE_EINVAL: a NULL pointer, B < 1 or B > 4096, chw < 1, E < 1 or E > 8, min_active < 0 or > E, sigma_min <= 0 or sigma_max < sigma_min,
+ * extreme_prob outside [0, 1].  x / x0 16-byte aligned with chw % 4 == 0 take the 16-byte path, anything else the scalar one. */
+int hdmoe_train_inputs(float* x, float* sigma, float* unet_mask, float* vit_mask, float* zeta_out, int* src, const float* x0,
+                       const float* unet_centers, const float* vit_centers, unsigned long long seed, unsigned long long step, long B, long chw,
+                       int E, int min_active, double sigma_min, double sigma_max, double p_mean, double p_std, double extreme_prob,
+                       double unet_bw, double vit_bw, float zeta, HS stream);
 
 /* ---- K6: norms  (model_internals.py:8-30; nn.GroupNorm / nn.LayerNorm in model_components.py) ------------ */
 int hdmoe_pixelnorm_fwd(void* xn, void* h, const void* x, long rows, int C, int dtype, HS stream);               /* h = mp_silu(xn), optional */
