@@ -588,6 +588,20 @@ __global__ __launch_bounds__(256) void conv_fwd5_kernel(ConvArgs a, int TH, int 
   const int magic_hw = (1 << 20) / HWp + 1;
   const T* x = (const T*)a.x + (long)n * a.H * a.W * a.Cphys;
   const T* w = (const T*)a.w + (long)g * a.wstride;
+  // position window of a flattened pointwise layer (N = H = 1, linear tiles): the row shrinks to [win[0], win[1]) * winL, counted
+  // from the window's first position, so every tile but the last is full; tiles past the window leave
+  int W = a.W, Wo = a.Wo;
+  long ywin = 0;
+  if (a.win) {
+    const long NR = a.W / a.winL;
+    long wb = a.win[0], we = a.win[1];
+    wb = wb < 0 ? 0 : (wb > NR ? NR : wb);
+    we = we < wb ? wb : (we > NR ? NR : we);
+    W = Wo = (int)((we - wb) * a.winL);
+    if (tx0 >= Wo) return;
+    x += wb * a.winL * a.Cphys;
+    ywin = wb * a.winL * a.Cstore;
+  }
 
   int abase[CV2_MT];
 #pragma unroll
@@ -616,8 +630,8 @@ __global__ __launch_bounds__(256) void conv_fwd5_kernel(ConvArgs a, int TH, int 
     const int px = e >> 2, cc = (e & 3) * VW;
     const int hy = (int)(((unsigned)px * (unsigned)magic_hw) >> 20), hx = px - hy * HWp;
     const int iy = ty0 + hy - pt, ix = tx0 + hx - pl;
-    const bool inb = e < nhal && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-    hoff[k] = inb ? (iy * a.W + ix) * a.Cphys + cc : -1;
+    const bool inb = e < nhal && iy >= 0 && iy < a.H && ix >= 0 && ix < W;
+    hoff[k] = inb ? (iy * W + ix) * a.Cphys + cc : -1;
     hlds[k] = (e < nhal) ? px * PSE + cc : -1;
   }
   // weight pieces: row = (tid >> 2) + 64 k, piece = tid & 3  ->  co = row & (NB-1), local tap = row >> LNB
@@ -690,17 +704,17 @@ __global__ __launch_bounds__(256) void conv_fwd5_kernel(ConvArgs a, int TH, int 
     }
   }
   // ---- epilogue: lane = pixel (32m + r of the wave's 64), register quad i = channels 32b + 8i + 4h .. +3
-  const long HWo = (long)a.Ho * a.Wo;
-  const long lin0 = (long)ty0 * a.Wo + tx0;
-  T* y = (T*)a.y + (long)n * HWo * a.Cstore;
-  const T* res = a.res ? (const T*)a.res + (long)n * HWo * a.Cstore : nullptr;
-  const int qlim = (TH > 1) ? npx : min(npx, a.Wo - tx0);
+  const long HWo = (long)a.Ho * Wo;
+  const long lin0 = (long)ty0 * Wo + tx0;
+  T* y = (T*)a.y + (long)n * HWo * a.Cstore + ywin;
+  const T* res = a.res ? (const T*)a.res + (long)n * HWo * a.Cstore + ywin : nullptr;
+  const int qlim = (TH > 1) ? npx : min(npx, Wo - tx0);
   // image position of tile pixel q: a linear run (whole rows, or a slice of one row) unless the tile is an 8 x 32 block
   auto pix_lin = [&](int q, bool& ok) -> long {
     if (!tile2d) { const long lin = lin0 + q; ok = q < qlim && lin < HWo; return lin; }
     const int ty = q >> 5, tx = q & 31;
-    ok = q < npx && ty0 + ty < a.Ho && tx0 + tx < a.Wo;
-    return lin0 + (long)ty * a.Wo + tx;
+    ok = q < npx && ty0 + ty < a.Ho && tx0 + tx < Wo;
+    return lin0 + (long)ty * Wo + tx;
   };
   if constexpr (LEPI) {
     // Through LDS: a quad store straight from the accumulator layout hands the memory system 32 separate 8/16-byte
@@ -1473,6 +1487,44 @@ int hdmoe_conv_fwd(const void* x, const void* w, void* y, const void* res, float
   if ((rc = conv_fwd_plan(a, dtype, p))) return rc;
   if (p.kernel == HDMOE_ROUTE_CONV_FWD5) conv_fwd5_lds_attr();
   conv_fwd_launch(a, dtype, p, stream);
+  return hdmoe_launch_status();
+}
+
+/* Pointwise (1 x 1, stride 1) forward / dgrad of ONE group, y = alpha * x w^T, over the rows [rows[0], rows[1]) of x [N][H][W][Cin] only
+ * (rows: DEVICE pointer to two ints, read by the kernels -- the launch has the all-rows grid; rows outside the window are neither read
+ * nor written, an empty window does nothing).  w: the prepared image [Cout][Ipad] of hdmoe_wprep_fwd.  The kernels are the ones
+ * hdmoe_conv_fwd runs for the same layer, so a row inside the window gets the bits the all-rows call gives it: kgemm with the window in
+ * positions; with flat != 0 the positions as one long row (the form ops.mp_conv presents a linear layer in: every tile but the window's
+ * last is full) on conv_fwd5; otherwise the generic kernels with one tile set per row.  Returns 1 (nothing launched) for another dtype
+ * than bf16. */
+int hdmoe_pw_fwd_rows(const void* x, const void* w, void* y, float alpha, const int* rows, int N, int H, int W, int Cin, int Ipad, int Cout,
+                      int flat, int dtype, hipStream_t stream) {
+  if (!x || !w || !y || !rows || N < 0 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || Ipad % 16 || Ipad < Cin) return HDMOE_EINVAL;
+  if (dtype != HDMOE_BF16) return 1;
+  if (N == 0) return HDMOE_OK;
+  const int one = 1, zero = 0;
+  const ConvArgs a = conv_fwd_args(x, w, y, nullptr, alpha, 0.f, rows, 1, 0, N, H, W, H, W, Cin, Cin, Ipad, Cout, Cout, 1, 0, &one, &one, &zero, &zero);
+  hdmoe_count_selection(HDMOE_SEL_ROW_WINDOW);
+  {
+    ConvArgs k = a;
+    k.seg = nullptr;
+    const int rc = kgemm_try_launch(k, dtype, stream, rows, (long)H * W);
+    if (rc <= 0) return rc;
+  }
+  CvPlan p;
+  const long M = (long)N * H * W;
+  if (flat && M < (1l << 31)) {
+    ConvArgs f = conv_fwd_args(x, w, y, nullptr, alpha, 0.f, nullptr, 1, 0, 1, 1, (int)M, 1, (int)M, Cin, Cin, Ipad, Cout, Cout, 1, 0, &one, &one, &zero, &zero);
+    if (conv_fwd_plan(f, dtype, p) == HDMOE_OK && p.kernel == HDMOE_ROUTE_CONV_FWD5 && !((p.tg >> 16) & 1)) {
+      f.win = rows; f.winL = H * W;
+      conv_fwd5_lds_attr();
+      conv_fwd_launch(f, dtype, p, stream);
+      return hdmoe_launch_status();
+    }
+  }
+  if (const int rc = conv_fwd_plan(a, dtype, p)) return rc;
+  if (p.kernel == HDMOE_ROUTE_CONV_FWD5) conv_fwd5_lds_attr();
+  conv_fwd_launch(a, dtype, p, stream);                      // (rows outside the window find no group and leave)
   return hdmoe_launch_status();
 }
 

@@ -16,6 +16,8 @@ struct ConvArgs {
   int n0;             // first row of this launch (row-per-blockIdx.y kernels: 65535 rows per launch)
   int kh[HDMOE_MAX_GROUPS], kw[HDMOE_MAX_GROUPS], pt[HDMOE_MAX_GROUPS], pl[HDMOE_MAX_GROUPS];
   float alpha, beta;
+  const int* win = nullptr;   // conv_fwd5 on a flattened pointwise layer (N = H = 1): DEVICE {begin, end}, only the positions
+  int winL = 0;               //   [begin * winL, end * winL) of the one long row are computed (hdmoe_pw_fwd_rows); null: all
 };
 
 // ---- plan helpers shared by conv6_plan, conv6s_plan, conv7_plan and blk6_plan
@@ -124,7 +126,7 @@ int lwg_try_launch(const void* x, const void* dy, float* const* G, const int* se
                    int dtype, hipStream_t stream, bool dry_run = false);
 
 // Pointwise forward / dgrad with Cin >= 512 and Cout <= 64 (kgemm.hip).  Same return convention.
-int kgemm_try_launch(const ConvArgs& a, int dtype, hipStream_t stream);
+int kgemm_try_launch(const ConvArgs& a, int dtype, hipStream_t stream, const int* rows = nullptr, long HW = 0);
 
 // k x k fp32 weight gradient for tiny input channel counts (taps * Cin <= 64: the stem), one expert (lwgrad.hip).  Same return convention.
 int swg_try_launch(const void* x, const void* dy, float* G, int N, int H, int W, int Cin, int Cout, int k, int pt, int pl, int dtype,

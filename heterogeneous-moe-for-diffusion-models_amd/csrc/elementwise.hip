@@ -2,6 +2,7 @@
 // All activation tensors are NHWC / [rows][C]; "vector path" tensors ((B,F) embeddings, per-sample
 // scalars) are always fp32.  Grid-stride loops, <= 2048 workgroups of 256 threads (guide G11).
 #include "common.h"
+#include "conv_args.h"
 #include "hdmoe.h"
 
 namespace {
@@ -14,6 +15,18 @@ static inline unsigned grid_for(long n) {
   return (unsigned)b;
 }
 #define GRID_STRIDE(i, n) for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
+
+// Row window of a kernel over n = N * per work items (per items for each leading row): rows = DEVICE {begin, end} restricts the launch
+// to the items [i0, i0 + n) of rows [begin, end), clamped to [0, N]; null leaves all n items.  The grid stays the all-rows one.
+DEVI void row_window(const int* rows, long per, long& i0, long& n) {
+  i0 = 0;
+  if (!rows) return;
+  const long N = per > 0 ? n / per : 0;
+  long b = rows[0], e = rows[1];
+  b = b < 0 ? 0 : (b > N ? N : b);
+  e = e < b ? b : (e > N ? N : e);
+  i0 = b * per; n = (e - b) * per;
+}
 
 // ---------------------------------------------------------------- generic pointwise
 template <typename T>
@@ -466,15 +479,20 @@ __global__ void seq_bcast_add_kernel(T* out, const T* x, const float* t, long S,
 }
 // out[r][i] = x[r][i] + bias[i]   /   colsum: dbias[i] += sum_r dy[r][i]
 template <typename T>
-__global__ void bias_add_kernel(T* out, const T* x, const float* bias, long L, long n) {
-  GRID_STRIDE(i, n) out[i] = from_f<T>(to_f(x[i]) + bias[i % L]);
+__global__ void bias_add_kernel(T* out, const T* x, const float* bias, long L, long n, const int* rows, long per) {
+  long i0;
+  row_window(rows, per, i0, n);                              // (per % L == 0)
+  GRID_STRIDE(j, n) { const long i = i0 + j; out[i] = from_f<T>(to_f(x[i]) + bias[i % L]); }
 }
 template <typename T>
-__global__ void colsum_kernel(float* out, const T* dy, long rows, long L, int rchunk) {
+__global__ void colsum_kernel(float* out, const T* dy, long rows, long L, int rchunk, const int* win, long per) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= L) return;
-  const long r0 = (long)blockIdx.y * rchunk;
-  const long r1 = (r0 + rchunk < rows) ? r0 + rchunk : rows;
+  long rb;
+  row_window(win, per, rb, rows);                            // matrix rows [rb, rb + rows) of the window (per matrix rows each)
+  const long r0 = rb + (long)blockIdx.y * rchunk;
+  const long r1 = (r0 + rchunk < rb + rows) ? r0 + rchunk : rb + rows;
+  if (r0 >= r1) return;
   float acc = 0.f;
   for (long r = r0; r < r1; ++r) acc += to_f(dy[r * L + i]);
   atomicAdd(&out[i], acc);
@@ -665,9 +683,12 @@ __global__ void nhwc_to_nchw_guided_kernel(float* out, const T* F, const float* 
 // ---------------------------------------------------------------- patch <-> image relayout (Vit_expert, model_components.py:698-704)
 // tok[b][(hp,wp)][f] <-> img[b][hp*p+i][wp*p+j][c];  order 0: f = (i*p+j)*C + c ;  order 1 (PixelShuffle): f = c*p*p + i*p + j
 template <typename T, bool TO_IMG>
-__global__ void patch_relayout_kernel(T* out, const T* in, int H, int W, int C, int p, int hp, int wp, int order, long n) {
+__global__ void patch_relayout_kernel(T* out, const T* in, int H, int W, int C, int p, int hp, int wp, int order, long n, const int* rows) {
   // iterates over image elements of the *padded-free* image (H x W); tokens cover hp*p x wp*p
-  GRID_STRIDE(i, n) {
+  long i0;
+  row_window(rows, (long)H * W * C, i0, n);
+  GRID_STRIDE(j, n) {
+    const long i = i0 + j;
     long t = i; const int c = (int)(t % C); t /= C;
     const int x = (int)(t % W); t /= W;
     const int y = (int)(t % H); const long b = t / H;
@@ -683,10 +704,13 @@ __global__ void patch_relayout_kernel(T* out, const T* in, int H, int W, int C, 
 // arithmetic (five divisions by run-time values) is paid once per vector instead of once per element.  order 0: the token side is
 // a 16-byte vector too; order 1 (PixelShuffle): the vector's channels sit p*p elements apart in the token.
 template <typename T, bool TO_IMG>
-__global__ void patch_relayout_vec_kernel(T* out, const T* in, int H, int W, int C, int p, int hp, int wp, int order, long nv) {
+__global__ void patch_relayout_vec_kernel(T* out, const T* in, int H, int W, int C, int p, int hp, int wp, int order, long nv, const int* rows) {
   constexpr int VW = VT<T>::W;
   const int CV = C / VW;
-  GRID_STRIDE(i, nv) {
+  long i0;
+  row_window(rows, (long)H * W * CV, i0, nv);
+  GRID_STRIDE(j, nv) {
+    const long i = i0 + j;
     long t = i; const int c0 = (int)(t % CV) * VW; t /= CV;
     const int x = (int)(t % W); t /= W;
     const int y = (int)(t % H); const long b = t / H;
@@ -718,10 +742,13 @@ __global__ void patch_relayout_vec_kernel(T* out, const T* in, int H, int W, int
 // of one (token, c, i) and gathers them from VW neighbouring pixels (the image-side-vector form above scatters 2-byte stores p*p
 // elements apart: 75 us for 67 MB; this form writes whole vectors).  Needs p % VW == 0.
 template <typename T>
-__global__ void patch_to_tokens_o1_vec_kernel(T* tok, const T* img, int H, int W, int C, int p, int hp, int wp, long nv) {
+__global__ void patch_to_tokens_o1_vec_kernel(T* tok, const T* img, int H, int W, int C, int p, int hp, int wp, long nv, const int* rows) {
   constexpr int VW = VT<T>::W;
   const int jv = p / VW;                                     // vectors per (c, i) row of a token
-  GRID_STRIDE(v, nv) {
+  long v0;
+  row_window(rows, (long)hp * wp * C * p * jv, v0, nv);
+  GRID_STRIDE(j, nv) {
+    const long v = v0 + j;
     long t = v;
     const int j0 = (int)(t % jv) * VW; t /= jv;
     const int ii = (int)(t % p); t /= p;
@@ -1467,13 +1494,32 @@ int hdmoe_seq_bcast_add(void* out, const void* x, const float* t, int N, long S,
 }
 int hdmoe_bias_add(void* out, const void* x, const float* bias, long rows, long L, int dtype, hipStream_t stream) {
   const long n = rows * L;
-  DT_SWITCH(dtype, L1D(bias_add_kernel<T>, n, (T*)out, (const T*)x, bias, L, n))
+  DT_SWITCH(dtype, L1D(bias_add_kernel<T>, n, (T*)out, (const T*)x, bias, L, n, nullptr, 0))
 }
 int hdmoe_colsum(float* out, const void* dy, long rows, long L, int dtype, hipStream_t stream) {
   const int rchunk = 64;
   if (cdiv(rows, rchunk) > 65535) return HDMOE_EINVAL;
   dim3 grid(cdiv(L, TPB), cdiv(rows, rchunk));
-  DT_SWITCH(dtype, hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(TPB), 0, stream, out, (const T*)dy, rows, L, rchunk))
+  DT_SWITCH(dtype, hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(TPB), 0, stream, out, (const T*)dy, rows, L, rchunk, nullptr, 0))
+}
+/* The two above over the leading rows [rows[0], rows[1]) of an [N][S][L] tensor only (rows: DEVICE pointer to two ints, read by the
+ * kernel; the grid is the all-rows one, nothing outside the window is read or written, an empty window does nothing). */
+int hdmoe_bias_add_rows(void* out, const void* x, const float* bias, const int* rows, int N, long S, long L, int dtype, hipStream_t stream) {
+  if (!out || !x || !bias || !rows || N < 0 || S < 1 || L < 1) return HDMOE_EINVAL;
+  const long n = (long)N * S * L;
+  if (n == 0) return HDMOE_OK;
+  hdmoe_count_selection(HDMOE_SEL_ROW_WINDOW);
+  DT_SWITCH(dtype, L1D(bias_add_kernel<T>, n, (T*)out, (const T*)x, bias, L, n, rows, S * L))
+}
+int hdmoe_colsum_rows(float* out, const void* dy, const int* rows, int N, long S, long L, int dtype, hipStream_t stream) {
+  if (!out || !dy || !rows || N < 0 || S < 1 || L < 1) return HDMOE_EINVAL;
+  const int rchunk = 64;
+  const long mrows = (long)N * S;
+  if (mrows == 0) return HDMOE_OK;
+  if (cdiv(mrows, rchunk) > 65535) return HDMOE_EINVAL;
+  dim3 grid(cdiv(L, TPB), cdiv(mrows, rchunk));
+  hdmoe_count_selection(HDMOE_SEL_ROW_WINDOW);
+  DT_SWITCH(dtype, hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(TPB), 0, stream, out, (const T*)dy, mrows, L, rchunk, rows, S))
 }
 int hdmoe_lerp_param_fwd(void* out, const void* a, const void* b, const float* alpha, long n, int dtype, hipStream_t stream) {
   DT_SWITCH(dtype, L1D(lerp_param_fwd_kernel<T>, n, (T*)out, (const T*)a, (const T*)b, alpha, n))
@@ -1528,21 +1574,34 @@ int hdmoe_nhwc_to_nchw_guided(float* out, const void* F, const float* sf, const 
   const long n = (long)N * C * HW;
   DT_SWITCH(dtype, L1D(nhwc_to_nchw_guided_kernel<T>, n, out, (const T*)F, sf, x, sx, g, C, HW, n))
 }
-int hdmoe_patch_relayout(void* out, const void* in, int N, int H, int W, int C, int p, int hp, int wp, int order,
-                         int to_img, int dtype, hipStream_t stream) {
+static int relayout_entry(void* out, const void* in, const int* rows, int N, int H, int W, int C, int p, int hp, int wp, int order,
+                          int to_img, int dtype, hipStream_t stream) {
   if (hp * p < H || wp * p < W) return HDMOE_EINVAL;
   const long n = (long)N * H * W * C;
+  if (rows) hdmoe_count_selection(HDMOE_SEL_ROW_WINDOW);
   if (!to_img && order == 1 && al16(out) && (dtype == HDMOE_BF16 || dtype == HDMOE_F32) && p % (dtype == HDMOE_BF16 ? 8 : 4) == 0) {
     const long nv = (long)N * hp * wp * C * p * p / (dtype == HDMOE_BF16 ? 8 : 4);      // covers the padded tokens too (zeros)
-    DT_SWITCH(dtype, L1D(patch_to_tokens_o1_vec_kernel<T>, nv, (T*)out, (const T*)in, H, W, C, p, hp, wp, nv))
+    DT_SWITCH(dtype, L1D(patch_to_tokens_o1_vec_kernel<T>, nv, (T*)out, (const T*)in, H, W, C, p, hp, wp, nv, rows))
   }
   if (al16(out) && al16(in) && C % (dtype == HDMOE_BF16 ? 8 : 4) == 0 && (dtype == HDMOE_BF16 || dtype == HDMOE_F32)) {
     const long nv = n / (dtype == HDMOE_BF16 ? 8 : 4);
-    if (to_img) { DT_SWITCH(dtype, L1D((patch_relayout_vec_kernel<T, true>), nv, (T*)out, (const T*)in, H, W, C, p, hp, wp, order, nv)) }
-    else { DT_SWITCH(dtype, L1D((patch_relayout_vec_kernel<T, false>), nv, (T*)out, (const T*)in, H, W, C, p, hp, wp, order, nv)) }
+    if (to_img) { DT_SWITCH(dtype, L1D((patch_relayout_vec_kernel<T, true>), nv, (T*)out, (const T*)in, H, W, C, p, hp, wp, order, nv, rows)) }
+    else { DT_SWITCH(dtype, L1D((patch_relayout_vec_kernel<T, false>), nv, (T*)out, (const T*)in, H, W, C, p, hp, wp, order, nv, rows)) }
   }
-  if (to_img) { DT_SWITCH(dtype, L1D((patch_relayout_kernel<T, true>), n, (T*)out, (const T*)in, H, W, C, p, hp, wp, order, n)) }
-  else { DT_SWITCH(dtype, L1D((patch_relayout_kernel<T, false>), n, (T*)out, (const T*)in, H, W, C, p, hp, wp, order, n)) }
+  if (to_img) { DT_SWITCH(dtype, L1D((patch_relayout_kernel<T, true>), n, (T*)out, (const T*)in, H, W, C, p, hp, wp, order, n, rows)) }
+  else { DT_SWITCH(dtype, L1D((patch_relayout_kernel<T, false>), n, (T*)out, (const T*)in, H, W, C, p, hp, wp, order, n, rows)) }
+}
+int hdmoe_patch_relayout(void* out, const void* in, int N, int H, int W, int C, int p, int hp, int wp, int order,
+                         int to_img, int dtype, hipStream_t stream) {
+  return relayout_entry(out, in, nullptr, N, H, W, C, p, hp, wp, order, to_img, dtype, stream);
+}
+/* hdmoe_patch_relayout over the image rows [rows[0], rows[1]) only (rows: DEVICE pointer to two ints, read by the kernel): same kernels,
+ * same grid; rows outside the window are neither read nor written. */
+int hdmoe_patch_relayout_rows(void* out, const void* in, const int* rows, int N, int H, int W, int C, int p, int hp, int wp, int order,
+                              int to_img, int dtype, hipStream_t stream) {
+  if (!rows || !out || !in || N < 0) return HDMOE_EINVAL;
+  if (N == 0) return HDMOE_OK;
+  return relayout_entry(out, in, rows, N, H, W, C, p, hp, wp, order, to_img, dtype, stream);
 }
 int hdmoe_fourier(float* out, const float* x, const float* freqs, const float* phases, int B, int F, hipStream_t stream) {
   const long n = (long)B * F;

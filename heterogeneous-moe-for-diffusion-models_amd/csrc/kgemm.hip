@@ -12,15 +12,27 @@
 
 namespace {
 
-struct KArgs { const bf16* x; const bf16* w; bf16* y; const bf16* res; long M; int K, O; float alpha, beta; };
+struct KArgs {
+  const bf16* x; const bf16* w; bf16* y; const bf16* res; long M; int K, O; float alpha, beta;
+  const int* rows; long HW;     // rows = DEVICE {begin, end}: only the positions [begin * HW, end * HW) (null: all M)
+};
 
 template <int NT>
 __global__ __launch_bounds__(512) void kgemm_kernel(KArgs a) {
   extern __shared__ __attribute__((aligned(16))) float red[];   // [8 waves][NT][16 regs][64 lanes]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
-  const long m0 = (long)blockIdx.x * 32;
-  const long mr = m0 + r < a.M ? m0 + r : a.M - 1;             // rows past the end read the last row, are never stored
+  long mb = 0, me = a.M;
+  if (a.rows) {                                                // tiles are counted from the window's first position: all of them are full
+    const long N = a.M / a.HW;
+    long b = a.rows[0], e = a.rows[1];
+    b = b < 0 ? 0 : (b > N ? N : b);
+    e = e < b ? b : (e > N ? N : e);
+    mb = b * a.HW; me = e * a.HW;
+  }
+  const long m0 = mb + (long)blockIdx.x * 32;
+  if (m0 >= me) return;
+  const long mr = m0 + r < me ? m0 + r : me - 1;               // rows past the end read the last row, are never stored
   const bf16* xrow = a.x + mr * a.K + 32 * h;
   const bf16* wrow = a.w + (long)r * a.K + 32 * h;
   f32x16 acc[NT];
@@ -65,7 +77,7 @@ __global__ __launch_bounds__(512) void kgemm_kernel(KArgs a) {
     for (int w = 0; w < 8; ++w) v += red[((w * NT + t) * 16 + reg) * 64 + l];
     const long m = m0 + (l & 31);
     const int o = 32 * t + acc_row(reg, l);
-    if (m < a.M) {
+    if (m < me) {
       v *= a.alpha;
       if (a.res) v += a.beta * (float)a.res[m * a.O + o];
       a.y[m * a.O + o] = (bf16)v;
@@ -76,7 +88,8 @@ __global__ __launch_bounds__(512) void kgemm_kernel(KArgs a) {
 }  // namespace
 
 // Returns HDMOE_OK after launching, a negative status on a launch error, or 1 when the layer is outside this file's domain.
-int kgemm_try_launch(const ConvArgs& a, int dtype, hipStream_t stream) {
+// rows != null: the row window of hdmoe_pw_fwd_rows (HW positions per row), on the all-rows grid.
+int kgemm_try_launch(const ConvArgs& a, int dtype, hipStream_t stream, const int* rows, long HW) {
   if (dtype != HDMOE_BF16 || a.ngroups != 1 || a.seg || a.stride != 1 || a.ones || a.kh[0] != 1 || a.kw[0] != 1 || a.pt[0] || a.pl[0]) return 1;
   constexpr int mink = 512;   // (768: the text projections of the fusion cross-attention, 37 + 31 -> ~2 x 12 us on the serial stage; same-box step -0.1 ms)
   if (a.Cin != a.Cphys || a.Ipad != a.Cin || a.Cin % 64 || a.Cin < mink || a.Cout != a.Cstore || a.Cout % 32 || a.Cout > 64) return 1;
@@ -84,6 +97,8 @@ int kgemm_try_launch(const ConvArgs& a, int dtype, hipStream_t stream) {
   KArgs k;
   k.x = (const bf16*)a.x; k.w = (const bf16*)a.w; k.y = (bf16*)a.y; k.res = (const bf16*)a.res;
   k.M = (long)a.N * a.H * a.W; k.K = a.Cin; k.O = a.Cout; k.alpha = a.alpha; k.beta = a.beta;
+  k.rows = rows; k.HW = HW;
+  if (rows && (HW < 1 || k.M % HW)) return 1;
   const long blocks = (k.M + 31) / 32;
   if (blocks > 0x7fffffffl) return 1;
   const int NT = a.Cout / 32;

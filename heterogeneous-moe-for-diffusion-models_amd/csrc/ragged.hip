@@ -13,6 +13,7 @@
 // One launch per layer for ALL experts instead of one per expert: the ~1100 few-microsecond launches per step of the per-expert
 // path were the step's host-enqueue floor (hipGraph replay costs ~4.8 us of host time per kernel node on this stack).
 #include "common.h"
+#include "conv_args.h"
 #include "hdmoe.h"
 
 namespace {
@@ -49,8 +50,10 @@ __global__ void rag_pack_kernel(T* dst, Ptrs srcs, FPtrs pos, Rag rg, int R, int
     dst[i] = from_f<T>(v);
   }
 }
-// backward of pack: every expert's compact gradient (zero outside its rows), pos_emb gradients accumulated
-template <typename T>
+// backward of pack: every expert's compact gradient (zero outside its rows), pos_emb gradients accumulated.
+// OWN (here and in the two unpack kernels): an expert's compact tensor is touched in its own rows [seg[g], seg[g+1]) only -- the other
+// rows are neither written nor read (the row-windowed patch / unpatch kernels of the bank's edges never look at them).
+template <typename T, bool OWN>
 __global__ void rag_pack_bwd_kernel(MPtrs dsrcs, MFPtrs dpos, const T* ddst, Rag rg, int R, int Sp, int C) {
   const long n = (long)R * Sp * C;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -58,32 +61,46 @@ __global__ void rag_pack_bwd_kernel(MPtrs dsrcs, MFPtrs dpos, const T* ddst, Rag
     const int s = (int)(t % Sp), r = (int)(t / Sp);
     const int g = rag_group(rg, r);
     const T v = ddst[i];
-    for (int e = 0; e < rg.ng; ++e)
-      if (s < rg.len[e]) ((T*)dsrcs.p[e])[((long)r * rg.len[e] + s) * C + c] = e == g ? v : from_f<T>(0.f);
+    if (OWN) {
+      if (g >= 0 && s < rg.len[g]) ((T*)dsrcs.p[g])[((long)r * rg.len[g] + s) * C + c] = v;
+    } else {
+      for (int e = 0; e < rg.ng; ++e)
+        if (s < rg.len[e]) ((T*)dsrcs.p[e])[((long)r * rg.len[e] + s) * C + c] = e == g ? v : from_f<T>(0.f);
+    }
     if (g >= 0 && s < rg.len[g] && dpos.p[g]) atomicAdd(&dpos.p[g][(long)s * C + c], to_f(v));
   }
 }
 // unpack: padded rows -> every expert's compact tensor (all rows; rows of other experts carry other tokens -- finite, unused)
-template <typename T>
+template <typename T, bool OWN>
 __global__ void rag_unpack_kernel(MPtrs dsts, const T* src, Rag rg, int R, int Sp, int C) {
   const long n = (long)R * Sp * C;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const int c = (int)(i % C); const long t = i / C;
     const int s = (int)(t % Sp), r = (int)(t / Sp);
+    if (OWN) {
+      const int g = rag_group(rg, r);
+      if (g >= 0 && s < rg.len[g]) ((T*)dsts.p[g])[((long)r * rg.len[g] + s) * C + c] = src[i];
+      continue;
+    }
     const T v = src[i];
     for (int e = 0; e < rg.ng; ++e)
       if (s < rg.len[e]) ((T*)dsts.p[e])[((long)r * rg.len[e] + s) * C + c] = v;
   }
 }
-template <typename T>
+template <typename T, bool OWN>
 __global__ void rag_unpack_bwd_kernel(T* dsrc, Ptrs ddsts, Rag rg, int R, int Sp, int C) {
   const long n = (long)R * Sp * C;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const int c = (int)(i % C); const long t = i / C;
     const int s = (int)(t % Sp), r = (int)(t / Sp);
     float v = 0.f;
-    for (int e = 0; e < rg.ng; ++e)
-      if (s < rg.len[e]) v += to_f(((const T*)ddsts.p[e])[((long)r * rg.len[e] + s) * C + c]);
+    if (OWN) {
+      const int g = rag_group(rg, r);
+      if (g >= 0 && s < rg.len[g]) v = to_f(((const T*)ddsts.p[g])[((long)r * rg.len[g] + s) * C + c]);
+    } else {
+      for (int e = 0; e < rg.ng; ++e)
+        if (s < rg.len[e]) v += to_f(((const T*)ddsts.p[e])[((long)r * rg.len[e] + s) * C + c]);
+    }
     dsrc[i] = from_f<T>(v);
   }
 }
@@ -102,6 +119,14 @@ __global__ void rag_select_bwd_kernel(MPtrs douts, const uint4* dy, Rag rg, int 
     const uint4 v = dy[i];
     for (int e = 0; e < rg.ng; ++e) ((uint4*)douts.p[e])[i] = e == g ? v : make_uint4(0, 0, 0, 0);
   }
+}
+// rows that belong to no expert (a sample routed to fewer than k experts leaves rows past seg[ng]) := 0; owned rows are not touched --
+// the experts' row-windowed kernels write those
+// (one workgroup per row: an owned row costs its workgroup one look at seg)
+__global__ void rag_zero_unowned_kernel(uint4* y, Rag rg, long L16) {
+  if (rag_group(rg, (int)blockIdx.x) >= 0) return;
+  uint4* row = y + (long)blockIdx.x * L16;
+  for (long i = threadIdx.x; i < L16; i += blockDim.x) row[i] = make_uint4(0, 0, 0, 0);
 }
 
 // ---------------------------------------------------------------- GroupNorm over a row's REAL tokens (+ activation), one block per row
@@ -329,21 +354,56 @@ int hdmoe_rag_pack_bwd(void* const* dsrcs, float* const* dpos, const void* ddst,
                        int Sp, int C, int dtype, hipStream_t stream) {
   Rag rg; if (!mk_rag(rg, seg, lens, ngroups) || !ddst || !dsrcs) return HDMOE_EINVAL;
   MPtrs s; MFPtrs p; fill(s, dsrcs, ngroups); fill(p, dpos, ngroups);
-  RAG_DT(dtype, hipLaunchKernelGGL(rag_pack_bwd_kernel<T>, dim3(grid_for((long)R * Sp * C)), dim3(TPB), 0, stream, s, p, (const T*)ddst, rg, R, Sp, C))
+  RAG_DT(dtype, hipLaunchKernelGGL((rag_pack_bwd_kernel<T, false>), dim3(grid_for((long)R * Sp * C)), dim3(TPB), 0, stream, s, p, (const T*)ddst, rg, R, Sp, C))
   return hdmoe_launch_status();
 }
 int hdmoe_rag_unpack(void* const* dsts, const void* src, const int* seg, const int* lens, int ngroups, int R, int Sp, int C, int dtype,
                      hipStream_t stream) {
   Rag rg; if (!mk_rag(rg, seg, lens, ngroups) || !src || !dsts) return HDMOE_EINVAL;
   MPtrs d; fill(d, dsts, ngroups);
-  RAG_DT(dtype, hipLaunchKernelGGL(rag_unpack_kernel<T>, dim3(grid_for((long)R * Sp * C)), dim3(TPB), 0, stream, d, (const T*)src, rg, R, Sp, C))
+  RAG_DT(dtype, hipLaunchKernelGGL((rag_unpack_kernel<T, false>), dim3(grid_for((long)R * Sp * C)), dim3(TPB), 0, stream, d, (const T*)src, rg, R, Sp, C))
   return hdmoe_launch_status();
 }
 int hdmoe_rag_unpack_bwd(void* dsrc, const void* const* ddsts, const int* seg, const int* lens, int ngroups, int R, int Sp, int C,
                          int dtype, hipStream_t stream) {
   Rag rg; if (!mk_rag(rg, seg, lens, ngroups) || !dsrc || !ddsts) return HDMOE_EINVAL;
   Ptrs d; fill(d, ddsts, ngroups);
-  RAG_DT(dtype, hipLaunchKernelGGL(rag_unpack_bwd_kernel<T>, dim3(grid_for((long)R * Sp * C)), dim3(TPB), 0, stream, (T*)dsrc, d, rg, R, Sp, C))
+  RAG_DT(dtype, hipLaunchKernelGGL((rag_unpack_bwd_kernel<T, false>), dim3(grid_for((long)R * Sp * C)), dim3(TPB), 0, stream, (T*)dsrc, d, rg, R, Sp, C))
+  return hdmoe_launch_status();
+}
+/* Own-row forms of the three above: expert g's compact tensor is written (pack_bwd, unpack) / read (unpack_bwd) in its own rows
+ * [seg[g], seg[g+1]) only; what lies outside stays untouched (pack_bwd, unpack) or counts as zero (unpack_bwd). */
+int hdmoe_rag_pack_bwd_own(void* const* dsrcs, float* const* dpos, const void* ddst, const int* seg, const int* lens, int ngroups, int R,
+                           int Sp, int C, int dtype, hipStream_t stream) {
+  Rag rg; if (!mk_rag(rg, seg, lens, ngroups) || !ddst || !dsrcs) return HDMOE_EINVAL;
+  MPtrs s; MFPtrs p; fill(s, dsrcs, ngroups); fill(p, dpos, ngroups);
+  hdmoe_count_selection(HDMOE_SEL_ROW_WINDOW);
+  RAG_DT(dtype, hipLaunchKernelGGL((rag_pack_bwd_kernel<T, true>), dim3(grid_for((long)R * Sp * C)), dim3(TPB), 0, stream, s, p, (const T*)ddst, rg, R, Sp, C))
+  return hdmoe_launch_status();
+}
+int hdmoe_rag_unpack_own(void* const* dsts, const void* src, const int* seg, const int* lens, int ngroups, int R, int Sp, int C, int dtype,
+                         hipStream_t stream) {
+  Rag rg; if (!mk_rag(rg, seg, lens, ngroups) || !src || !dsts) return HDMOE_EINVAL;
+  MPtrs d; fill(d, dsts, ngroups);
+  hdmoe_count_selection(HDMOE_SEL_ROW_WINDOW);
+  RAG_DT(dtype, hipLaunchKernelGGL((rag_unpack_kernel<T, true>), dim3(grid_for((long)R * Sp * C)), dim3(TPB), 0, stream, d, (const T*)src, rg, R, Sp, C))
+  return hdmoe_launch_status();
+}
+int hdmoe_rag_unpack_bwd_own(void* dsrc, const void* const* ddsts, const int* seg, const int* lens, int ngroups, int R, int Sp, int C,
+                             int dtype, hipStream_t stream) {
+  Rag rg; if (!mk_rag(rg, seg, lens, ngroups) || !dsrc || !ddsts) return HDMOE_EINVAL;
+  Ptrs d; fill(d, ddsts, ngroups);
+  hdmoe_count_selection(HDMOE_SEL_ROW_WINDOW);
+  RAG_DT(dtype, hipLaunchKernelGGL((rag_unpack_bwd_kernel<T, true>), dim3(grid_for((long)R * Sp * C)), dim3(TPB), 0, stream, (T*)dsrc, d, rg, R, Sp, C))
+  return hdmoe_launch_status();
+}
+/* y[r] = 0 for the rows r of [R] that lie in no expert's window; the others stay as they are; row_bytes % 16 == 0 */
+int hdmoe_rag_zero_unowned(void* y, const int* seg, int ngroups, int R, long row_bytes, hipStream_t stream) {
+  const int zeros[HDMOE_MAX_GROUPS] = {0};
+  Rag rg; if (!mk_rag(rg, seg, zeros, ngroups) || !y || R < 0 || row_bytes < 0 || row_bytes % 16 || ((uintptr_t)y & 15)) return HDMOE_EINVAL;
+  if (R == 0 || row_bytes == 0) return HDMOE_OK;
+  hdmoe_count_selection(HDMOE_SEL_ROW_WINDOW);
+  hipLaunchKernelGGL(rag_zero_unowned_kernel, dim3(R), dim3(TPB), 0, stream, (uint4*)y, rg, row_bytes / 16);
   return hdmoe_launch_status();
 }
 /* y[r] = outs[g(r)][r]; row_bytes % 16 == 0 */

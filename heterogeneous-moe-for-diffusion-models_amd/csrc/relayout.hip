@@ -36,7 +36,20 @@ struct RlArgs {
   void* tok; void* img;
   int H, W, C, p, hp, wp, TW, tpr;                          // TW tokens per full tile, tpr tiles per token row
   long ntiles;
+  const int* rows;                                          // device {begin, end}: only the tiles of image rows [begin, end) (null: all N)
+  int N;
 };
+// first tile and tile count of the launch: all of them, or those of the row window read from device memory (clamped to [0, N])
+DEVI void rl_window(const RlArgs& a, long& t0, long& nt) {
+  t0 = 0; nt = a.ntiles;
+  if (a.rows) {
+    int b = a.rows[0], e = a.rows[1];
+    b = b < 0 ? 0 : (b > a.N ? a.N : b);
+    e = e < b ? b : (e > a.N ? a.N : e);
+    const long tpi = (long)a.hp * a.tpr;
+    t0 = b * tpi; nt = (e - b) * tpi;
+  }
+}
 
 // geometry of tile t
 struct RlTile {
@@ -104,9 +117,11 @@ __global__ __launch_bounds__(TPB) void patch_relayout_tiled_kernel(RlArgs a) {
   __shared__ uint4 lds4[RL_LDS_BYTES / 16];
   T* lds = reinterpret_cast<T*>(lds4);
   uint4 r[RL_MAXV];
+  long t0, nt;
+  rl_window(a, t0, nt);
   long t = blockIdx.x;
-  if (t >= a.ntiles) return;
-  RlTile g = rl_tile<T, P>(a, t);
+  if (t >= nt) return;
+  RlTile g = rl_tile<T, P>(a, t0 + t);
   rl_load<T, P, TO_IMG>(r, a, g);
   while (true) {
     // registers -> LDS (image order)
@@ -129,8 +144,8 @@ __global__ __launch_bounds__(TPB) void patch_relayout_tiled_kernel(RlArgs a) {
     __syncthreads();
     const long tn = t + gridDim.x;
     const RlTile gc = g;
-    if (tn < a.ntiles) {                                   // the next tile's loads fly while this one leaves LDS
-      g = rl_tile<T, P>(a, tn);
+    if (tn < nt) {                                         // the next tile's loads fly while this one leaves LDS
+      g = rl_tile<T, P>(a, t0 + tn);
       rl_load<T, P, TO_IMG>(r, a, g);
     }
     // LDS -> global
@@ -152,7 +167,7 @@ __global__ __launch_bounds__(TPB) void patch_relayout_tiled_kernel(RlArgs a) {
         }
       }
     }
-    if (tn >= a.ntiles) break;
+    if (tn >= nt) break;
     t = tn;
     __syncthreads();
   }
@@ -251,8 +266,8 @@ __global__ __launch_bounds__(TPB) void combine_rows_bwd_vec_kernel(T* dys, float
 extern "C" {
 
 // 0: launched; 1: outside the tiled kernel's domain, nothing launched (the caller runs hdmoe_patch_relayout)
-int hdmoe_patch_relayout_tiled(void* out, const void* in, int N, int H, int W, int C, int p, int hp, int wp, int order, int to_img,
-                               int dtype, hipStream_t stream) {
+static int rl_entry(void* out, const void* in, const int* rows, int N, int H, int W, int C, int p, int hp, int wp, int order, int to_img, int dtype,
+                    hipStream_t stream) {
   if (!out || !in || N < 0 || H < 1 || W < 1 || C < 1 || p < 1 || hp < 1 || wp < 1 || (long)hp * p < H || (long)wp * p < W) return HDMOE_EINVAL;
   if (order != 1 || (dtype != HDMOE_BF16 && dtype != HDMOE_F32)) return 1;
   const int VW = dtype == HDMOE_BF16 ? 8 : 4, esz = dtype == HDMOE_BF16 ? 2 : 4;
@@ -263,7 +278,7 @@ int hdmoe_patch_relayout_tiled(void* out, const void* in, int N, int H, int W, i
   RlArgs a;
   a.tok = to_img ? const_cast<void*>(in) : out;
   a.img = to_img ? out : const_cast<void*>(in);
-  a.H = H; a.W = W; a.C = C; a.p = p; a.hp = hp; a.wp = wp;
+  a.H = H; a.W = W; a.C = C; a.p = p; a.hp = hp; a.wp = wp; a.rows = rows; a.N = N;
   long TW = RL_TILE_TARGET / tokb;
   if (TW < 1) TW = 1;
   if (TW > wp) TW = wp;
@@ -272,9 +287,20 @@ int hdmoe_patch_relayout_tiled(void* out, const void* in, int N, int H, int W, i
   a.ntiles = (long)N * hp * a.tpr;
   if ((long)N * hp * wp * (tokb / esz) >= (1l << 40)) return 1;
   const unsigned grid = (unsigned)(a.ntiles < RL_GRID ? a.ntiles : RL_GRID);
-  hdmoe_count_selection(HDMOE_SEL_RELAYOUT_TILED);
+  hdmoe_count_selection(rows ? HDMOE_SEL_ROW_WINDOW : HDMOE_SEL_RELAYOUT_TILED);
   if (dtype == HDMOE_BF16) return to_img ? rl_launch<bf16, true>(a, grid, stream) : rl_launch<bf16, false>(a, grid, stream);
   return to_img ? rl_launch<float, true>(a, grid, stream) : rl_launch<float, false>(a, grid, stream);
+}
+int hdmoe_patch_relayout_tiled(void* out, const void* in, int N, int H, int W, int C, int p, int hp, int wp, int order, int to_img,
+                               int dtype, hipStream_t stream) {
+  return rl_entry(out, in, nullptr, N, H, W, C, p, hp, wp, order, to_img, dtype, stream);
+}
+// The same over the image rows [rows[0], rows[1]) only (rows: DEVICE pointer to two ints, read by the kernel): the launch has the
+// all-rows grid, rows outside the window are neither read nor written, an empty window does nothing.
+int hdmoe_patch_relayout_tiled_rows(void* out, const void* in, const int* rows, int N, int H, int W, int C, int p, int hp, int wp, int order,
+                                    int to_img, int dtype, hipStream_t stream) {
+  if (!rows) return HDMOE_EINVAL;
+  return rl_entry(out, in, rows, N, H, W, C, p, hp, wp, order, to_img, dtype, stream);
 }
 
 // 0: launched; 1: L is not a whole number of 16-byte vectors or a pointer is not 16-byte aligned, nothing launched

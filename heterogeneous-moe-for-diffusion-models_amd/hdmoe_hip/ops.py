@@ -2443,6 +2443,200 @@ def rag_select(outs: Sequence[Tensor], rag: RagLayout) -> Tensor:
     return _RagSelectFn.apply(rag, *outs)
 
 
+# ---- the bank's two edges over each expert's own rows.  Rows arrive in expert-contiguous order, so expert g needs exactly the window
+# [seg[g], seg[g+1]): every kernel below gets `seg[g:g+2]` (a view: the device pointer seg + g), reads the window itself and leaves all other
+# rows alone -- the launches have the all-rows grid, nothing reads seg on the host, a captured graph follows each replay's routing.
+# The per-expert tensors are valid inside their window only; they live inside the two nodes and never reach autograd.
+VIT_BANK_ROWS = True                                    # False: patch embed / unpatch per expert over ALL rows (the path below replaces)
+
+
+def vit_bank_rows_ok(x: Tensor, ws: Sequence[Tensor], E: int) -> bool:
+    """Domain of the row-windowed edge kernels: bf16, contiguous square patch kernels ws[g] (E, C, p, p) that divide the image, whole
+    16-byte vectors of channels (the domain of _PatchLinearFn, whose kernels the windowed entry points share)."""
+    if x.dtype != torch.bfloat16 or x.ndim != 4 or not x.is_cuda:
+        return False
+    _, H, W, C = x.shape
+    if C % 8 or E % 8:
+        return False
+    for w in ws:
+        if w.ndim != 4 or w.shape[0] != E or w.shape[1] != C or w.shape[2] != w.shape[3] or not w.is_contiguous():
+            return False
+        p = int(w.shape[2])
+        if H % p or W % p or (C * p * p) % 16:
+            return False
+    return True
+
+
+def _relayout_rows(out, inp, rows, N, H, W, C, p, to_img):
+    args = (out, inp, rows, N, H, W, C, p, H // p, W // p, 1, to_img, _dt(inp))
+    if call("hdmoe_patch_relayout_tiled_rows", *args) == 1:
+        call("hdmoe_patch_relayout_rows", *args)
+
+
+def _pw_rows(x, w, y, rows, N, H, W, Cin, Ipad, Cout, flat):
+    if call("hdmoe_pw_fwd_rows", x, w, y, 1.0, rows, N, H, W, Cin, Ipad, Cout, flat, _dt(x)) != 0:
+        raise RuntimeError("hdmoe_pw_fwd_rows declined a shape that ops.vit_bank_rows_ok admitted")
+
+
+class _VitBankEmbedFn(torch.autograd.Function):
+    """Patch embedding of every expert over its own rows + pos_emb, packed: x (R,H,W,C) -> padded tokens (R,Sp,E).  Per expert the
+    launches of _PatchLinearFn (relayout, GEMM, bias) with the row window, then one hdmoe_rag_pack (which reads own rows only)."""
+
+    @staticmethod
+    def forward(ctx, x, rag, *tensors):
+        G = rag.G
+        ws, bs, pos = tensors[:G], tensors[G:2 * G], tensors[2 * G:]
+        x = _c(x)
+        R, H, W, C = x.shape
+        E, dt, seg = int(ws[0].shape[0]), _dt(x), rag.seg
+        Epad = (E + 15) // 16 * 16
+        toks, wds, ys = [], [], []
+        for g in range(G):
+            p = int(ws[g].shape[2])
+            hp, wp, K = H // p, W // p, C * p * p
+            rows = seg[g:g + 2]
+            tk = torch.empty((R, hp, wp, K), dtype=x.dtype, device=x.device)
+            _relayout_rows(tk, x, rows, R, H, W, C, p, 0)
+            wf = torch.empty(E * K, dtype=x.dtype, device=x.device)
+            wd = torch.empty(K * Epad, dtype=x.dtype, device=x.device) if ctx.needs_input_grad[0] else None
+            call("hdmoe_wprep_fwd", [ws[g]], None, 1.0, [1], [1], 1, E, K, K, Epad, wf, wf.numel(), wd, 0 if wd is None else wd.numel(), 0, 0, 0, dt)
+            y = torch.empty((R, hp * wp, E), dtype=x.dtype, device=x.device)
+            _pw_rows(tk, wf, y, rows, R, hp, wp, K, K, E, 0)
+            call("hdmoe_bias_add_rows", y, y, bs[g], rows, R, hp * wp, E, dt)
+            toks.append(tk); wds.append(wd); ys.append(y)
+        dst = torch.empty((R, rag.Sp, E), dtype=x.dtype, device=x.device)
+        call("hdmoe_rag_pack", dst, ys, [_f32(p) for p in pos], seg, rag.lens, G, R, rag.Sp, E, dt)
+        ctx.save_for_backward(*toks, *ws, *pos)
+        ctx.rag, ctx.wds, ctx.dims = rag, wds, (R, H, W, C, E, Epad)
+        return dst
+
+    @staticmethod
+    def backward(ctx, gt):
+        rag = ctx.rag
+        G, seg = rag.G, rag.seg
+        saved = ctx.saved_tensors
+        toks, ws, pos = saved[:G], saved[G:2 * G], saved[2 * G:]
+        R, H, W, C, E, Epad = ctx.dims
+        gt = _c(gt)
+        dt, dev, nig = _dt(gt), gt.device, ctx.needs_input_grad
+        dys = [torch.empty((R, L, E), dtype=gt.dtype, device=dev) for L in rag.lens]
+        bufs, dpos = _param_grads(pos)
+        call("hdmoe_rag_pack_bwd_own", dys, bufs, gt, seg, rag.lens, G, R, rag.Sp, E, dt)
+        dx = None
+        if nig[0]:
+            dx = torch.empty((R, H, W, C), dtype=gt.dtype, device=dev)
+            call("hdmoe_rag_zero_unowned", dx, seg, G, R, H * W * C * gt.element_size())
+        dws, dbs = [None] * G, [None] * G
+        for g in range(G):
+            p = int(ws[g].shape[2])
+            hp, wp, K = H // p, W // p, C * p * p
+            rows = seg[g:g + 2]
+            if nig[0]:
+                dtok = torch.empty((R, hp, wp, K), dtype=gt.dtype, device=dev)
+                _pw_rows(dys[g], ctx.wds[g], dtok, rows, R, hp, wp, E, Epad, K, 0)
+                _relayout_rows(dx, dtok, rows, R, H, W, C, p, 1)
+            if nig[2 + g]:
+                # an expert without rows: nothing is added to the zero-initialised slab, its gradient is an exact zero
+                Gs = [_zeros((1, E, K), torch.float32, dev)]
+                call("hdmoe_conv_wgrad", toks[g], dys[g], Gs, rows, 1, R, hp, wp, hp, wp, K, K, E, 1, 0, [1], [1], [0], [0], dt)
+                dws[g] = torch.empty_like(ws[g])
+                call("hdmoe_wprep_bwd", [ws[g]], None, 1.0, Gs, [dws[g]], None, [1], [1], 1, E, K, 0)
+            if nig[2 + G + g]:
+                dbs[g] = torch.zeros(E, dtype=torch.float32, device=dev)
+                call("hdmoe_colsum_rows", dbs[g], dys[g], rows, R, hp * wp, E, dt)
+        return (dx, None, *dws, *dbs, *dpos)
+
+
+def vit_bank_embed(x: Tensor, ws: Sequence[Tensor], bs: Sequence[Tensor], pos: Sequence[Tensor], rag: RagLayout) -> Tensor:
+    """rag_pack([patch_embed(x, w_g, b_g) for g], pos, rag), each expert over its own rows only.  x (R,H,W,C) -> (R,Sp,E)."""
+    if not vit_bank_rows_ok(x, ws, int(ws[0].shape[0])):
+        raise ValueError("vit_bank_embed: outside the row-windowed kernels' domain (ops.vit_bank_rows_ok); use ops.patch_embed + ops.rag_pack")
+    return _VitBankEmbedFn.apply(x, rag, *f32_params(list(ws)), *bs, *pos)
+
+
+class _VitBankUnpatchFn(torch.autograd.Function):
+    """rag_select([pixel_shuffle_tokens(mp_conv(part_g, w_g), ...) for part_g in rag_unpack(tok)]) with every expert over its own rows:
+    the pixel shuffles write their rows of ONE image tensor (no select), the linear layers run on a window of positions."""
+
+    @staticmethod
+    def forward(ctx, tok, rag, meta, *ws):
+        H, W, C, training, ps = meta
+        G, seg = rag.G, rag.seg
+        tok = _c(tok)
+        R, Sp, E = tok.shape
+        dt, dev = _dt(tok), tok.device
+        parts = [torch.empty((R, L, E), dtype=tok.dtype, device=dev) for L in rag.lens]
+        call("hdmoe_rag_unpack_own", parts, tok, seg, rag.lens, G, R, Sp, E, dt)
+        out = torch.empty((R, H, W, C), dtype=tok.dtype, device=dev)
+        call("hdmoe_rag_zero_unowned", out, seg, G, R, H * W * C * tok.element_size())
+        Ipad = (E + 15) // 16 * 16
+        ents, wds = [], []
+        for g in range(G):
+            w, L = ws[g], rag.lens[g]
+            K, p = int(w.shape[0]), ps[g]
+            Opad = (K + 15) // 16 * 16
+            # the weight images as _MPConvFn.forward makes them for this layer (gain 1, alpha 1, normalised)
+            ent = _bank.ACTIVE.lookup([w], tok.dtype, 1.0, 1.0, True) if _bank.ACTIVE is not None else None
+            if ent is not None:
+                wf, wd = ent.wf, ent.wd
+            else:
+                wf = torch.empty(K * Ipad, dtype=tok.dtype, device=dev)
+                wd = torch.empty(E * Opad, dtype=tok.dtype, device=dev) if ctx.needs_input_grad[0] else None
+                call("hdmoe_wprep_fwd", [w], None, 1.0, [1], [1], 1, K, E, Ipad, Opad, wf, K * Ipad, wd, E * Opad, 1, 1 if training else 0, 1, dt)
+                if training:
+                    _bank.note_weights_changed()
+            u = torch.empty((R, L, K), dtype=tok.dtype, device=dev)
+            _pw_rows(parts[g], wf, u, seg[g:g + 2], R, 1, L, E, Ipad, K, 1)
+            _relayout_rows(out, u, seg[g:g + 2], R, H, W, C, p, 1)
+            ents.append(ent); wds.append(wd)
+        ctx.save_for_backward(*parts, *ws)
+        ctx.rag, ctx.ents, ctx.wds, ctx.dims = rag, ents, wds, (R, Sp, E, H, W, C, ps)
+        ctx.bank = _bank.ACTIVE
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        rag = ctx.rag
+        G, seg = rag.G, rag.seg
+        saved = ctx.saved_tensors
+        parts, ws = saved[:G], saved[G:]
+        R, Sp, E, H, W, C, ps = ctx.dims
+        go = _c(go)
+        dt, dev, nig = _dt(go), go.device, ctx.needs_input_grad
+        dparts = [torch.empty((R, L, E), dtype=go.dtype, device=dev) for L in rag.lens] if nig[0] else None
+        dws = [None] * G
+        for g in range(G):
+            w, L, ent = ws[g], rag.lens[g], ctx.ents[g]
+            K, p = int(w.shape[0]), ps[g]
+            Opad = (K + 15) // 16 * 16
+            rows = seg[g:g + 2]
+            du = torch.empty((R, L, K), dtype=go.dtype, device=dev)
+            _relayout_rows(du, go, rows, R, H, W, C, p, 0)
+            if nig[0]:
+                _pw_rows(du, ctx.wds[g], dparts[g], rows, R, 1, L, K, Opad, E, 1)
+            if nig[3 + g]:
+                if ent is not None:                            # into the weight bank's slab; the bank's finish launch makes the gradient
+                    call("hdmoe_conv_wgrad", parts[g], du, list(ent.G), rows, 1, R, 1, L, 1, L, E, E, K, 1, 0, [1], [1], [0], [0], dt)
+                    ctx.bank.note_backward(ent)
+                else:
+                    Gs = [_zeros((1, K, E), torch.float32, dev)]
+                    call("hdmoe_conv_wgrad", parts[g], du, Gs, rows, 1, R, 1, L, 1, L, E, E, K, 1, 0, [1], [1], [0], [0], dt)
+                    dws[g] = torch.empty_like(w)
+                    call("hdmoe_wprep_bwd", [w], None, 1.0, Gs, [dws[g]], None, [1], [1], 1, K, E, 1)
+        dtok = None
+        if nig[0]:
+            dtok = torch.empty((R, Sp, E), dtype=go.dtype, device=dev)
+            call("hdmoe_rag_unpack_bwd_own", dtok, dparts, seg, rag.lens, G, R, Sp, E, dt)
+        return (dtok, None, None, *dws)
+
+
+def vit_bank_unpatch(tok: Tensor, ws: Sequence[Tensor], rag: RagLayout, H: int, W: int, C: int, ps: Sequence[int],
+                     training: bool = False) -> Tensor:
+    """Padded tokens (R,Sp,E) -> image (R,H,W,C): unpatch_proj (MP_Conv linear, weights ws[g] (C*p_g^2, E)) and the pixel shuffle of each
+    row's own expert; rows of no expert are zero."""
+    return _VitBankUnpatchFn.apply(tok, rag, (int(H), int(W), int(C), bool(training), tuple(int(p) for p in ps)), *f32_params(list(ws)))
+
+
 class _GNRagFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, rag, groups, act, eps, *params):

@@ -514,15 +514,20 @@ def vit_expert_bank_forward(experts: Sequence["Vit_expert"], x: Tensor, time_emb
                             seg: Tensor) -> Tensor:
     """Vit_expert.forward (reference model_components.py:655-706) over a bank of experts that differ in patch size.
     x: (R,H,W,C) channel-last rows in expert-contiguous order (rows [seg[g], seg[g+1]) belong to expert g); time_emb (R,T) /
-    text_emb (R,text_dim) fp32.  Patch embedding and un-patching have per-expert shapes and run per expert over all rows (they
-    are <2 % of the bank's arithmetic); every layer in between is one launch for all experts."""
+    text_emb (R,text_dim) fp32.  Patch embedding and un-patching have per-expert shapes: they run per expert over that expert's own
+    row window (ops.vit_bank_embed / ops.vit_bank_unpatch; outside their domain, or with ops.VIT_BANK_ROWS off, per expert over all
+    rows); every layer in between is one launch for all experts."""
     e0 = experts[0]
     tr = e0.training
     R, H, W, C = x.shape
     ps = [e.patch.kernel_size[0] for e in experts]
     rag = ops.RagLayout(seg, [(-(-H // p)) * (-(-W // p)) for p in ps], R)
-    pes = [ops.patch_embed(xe, e.patch.weight, e.patch.bias) for xe, e in zip(ops.fanout(x, len(experts)), experts)]
-    tok = ops.rag_pack(pes, [e.pos_emb for e in experts], rag)
+    rows = ops.VIT_BANK_ROWS and ops.vit_bank_rows_ok(x, [e.patch.weight for e in experts], e0.emb_dim)
+    if rows:
+        tok = ops.vit_bank_embed(x, [e.patch.weight for e in experts], [e.patch.bias for e in experts], [e.pos_emb for e in experts], rag)
+    else:
+        pes = [ops.patch_embed(xe, e.patch.weight, e.patch.bias) for xe, e in zip(ops.fanout(x, len(experts)), experts)]
+        tok = ops.rag_pack(pes, [e.pos_emb for e in experts], rag)
     t = time_emb
     if text_emb is not None:
         tx = text_emb
@@ -542,6 +547,8 @@ def vit_expert_bank_forward(experts: Sequence["Vit_expert"], x: Tensor, time_emb
         tok = vit_block_bank_forward([e.diffit[i] for e in experts], tok, t if ts is None else ts[3 * i:3 * i + 3], rag,
                                      None if tps is None else tps[3 * i:3 * i + 3])
     tok = ops.ln_rag(tok, [e.norm.weight for e in experts], [e.norm.bias for e in experts], rag, e0.norm.eps)
+    if rows:
+        return ops.vit_bank_unpatch(tok, [e.unpatch_proj.weights for e in experts], rag, H, W, C, ps, training=tr)
     outs = []
     for e, p, part in zip(experts, ps, ops.rag_unpack(tok, rag)):
         outs.append(ops.pixel_shuffle_tokens(e.unpatch_proj._fwd(part), H, W, C, p))

@@ -157,7 +157,8 @@ enum {
   HDMOE_SEL_COMBINE_FWD_VEC = 20,  /* hdmoe_combine_rows_fwd_vec: 16-byte combine forward (also the gather's backward) */
   HDMOE_SEL_COMBINE_BWD_VEC = 21,  /* hdmoe_combine_rows_bwd_vec: 16-byte combine backward */
   HDMOE_SEL_FILM_DGRAD = 22,       /* hdmoe_conv_bwd6_film: the bwd7 launch with the FiLM-backward epilogue in its dgrad program */
-  HDMOE_SEL_COUNT = 23
+  HDMOE_SEL_ROW_WINDOW = 23,       /* a row-windowed launch (the hdmoe_*_rows / hdmoe_rag_*_own entry points of the ViT bank's edges) */
+  HDMOE_SEL_COUNT = 24
 };
 int hdmoe_kernel_selections(long long* counts, int n, int reset);
 
@@ -305,6 +306,22 @@ int hdmoe_patch_relayout(void* out, const void* in, int N, int H, int W, int C, 
  * a token above 32 KiB, p > 64, unaligned pointers: the caller then runs hdmoe_patch_relayout. */
 int hdmoe_patch_relayout_tiled(void* out, const void* in, int N, int H, int W, int C, int p, int hp, int wp, int order,
                                int to_img, int dtype, HS stream);
+/* Row-windowed forms for the edges of the ViT expert bank (patch embedding in, un-patching out), where expert g owns the contiguous
+ * rows [seg[g], seg[g+1]) of the routed batch.  rows: DEVICE pointer to two ints {begin, end} (in the bank: seg + g), read by the
+ * kernel, never by the host: the launch always has the all-rows grid, so a captured graph follows the routing of each replay.  Rows
+ * inside the window get exactly what the all-rows entry point writes for them; no other row is read or written; an empty window
+ * does nothing.  (Weight gradients over a window: hdmoe_conv_wgrad / hdmoe_pw_bwd with seg = rows and one group.) */
+int hdmoe_patch_relayout_rows(void* out, const void* in, const int* rows, int N, int H, int W, int C, int p, int hp, int wp, int order,
+                              int to_img, int dtype, HS stream);
+int hdmoe_patch_relayout_tiled_rows(void* out, const void* in, const int* rows, int N, int H, int W, int C, int p, int hp, int wp,
+                                    int order, int to_img, int dtype, HS stream);                               /* 1: declined, as the all-rows form */
+int hdmoe_bias_add_rows(void* out, const void* x, const float* bias, const int* rows, int N, long S, long L, int dtype, HS stream);   /* [N][S][L] */
+int hdmoe_colsum_rows(float* out, const void* dy, const int* rows, int N, long S, long L, int dtype, HS stream);                      /* accumulates */
+/* pointwise forward / dgrad y = alpha * x w^T of one group over the row window, w = the [Cout][Ipad] image of hdmoe_wprep_fwd; flat != 0:
+ * the positions as one long row (full tiles), as ops.mp_conv presents a linear layer.  Same kernels as hdmoe_conv_fwd runs for the layer
+ * (kgemm with the window in positions, conv_fwd5, the generic per-row kernels).  1: declined (not bf16), nothing launched. */
+int hdmoe_pw_fwd_rows(const void* x, const void* w, void* y, float alpha, const int* rows, int N, int H, int W, int Cin, int Ipad,
+                      int Cout, int flat, int dtype, HS stream);
 int hdmoe_fourier(float* out, const float* x, const float* freqs, const float* phases, int B, int F, HS stream); /* model_internals.py:171-174 */
 int hdmoe_edm_coeffs(float* coef, const float* sigma, int nsig, float sigma_data, int B, HS stream);             /* model_config2.py:431-438 */
 int hdmoe_sigmoid_scaling(float* sv, float* su, float* pair, const float* c_noise, float tp, float soft, int B, HS stream); /* :244-249 */
@@ -408,6 +425,15 @@ int hdmoe_rag_unpack(void* const* dsts, const void* src, const int* seg, const i
                      int dtype, HS stream);
 int hdmoe_rag_unpack_bwd(void* dsrc, const void* const* ddsts, const int* seg, const int* lens, int ngroups, int R, int Sp,
                          int C, int dtype, HS stream);
+/* own-row forms: expert g's compact tensor is written (pack_bwd, unpack) / read (unpack_bwd) in its rows [seg[g], seg[g+1]) only */
+int hdmoe_rag_pack_bwd_own(void* const* dsrcs, float* const* dpos, const void* ddst, const int* seg, const int* lens, int ngroups,
+                           int R, int Sp, int C, int dtype, HS stream);
+int hdmoe_rag_unpack_own(void* const* dsts, const void* src, const int* seg, const int* lens, int ngroups, int R, int Sp, int C,
+                         int dtype, HS stream);
+int hdmoe_rag_unpack_bwd_own(void* dsrc, const void* const* ddsts, const int* seg, const int* lens, int ngroups, int R, int Sp,
+                             int C, int dtype, HS stream);
+/* rows of y [R][row_bytes] that lie in no expert's window := 0, the others stay untouched (the shared output of row-windowed passes) */
+int hdmoe_rag_zero_unowned(void* y, const int* seg, int ngroups, int R, long row_bytes, HS stream);
 int hdmoe_rag_select(void* y, const void* const* outs, const int* seg, int ngroups, int R, long row_bytes, HS stream);
 int hdmoe_rag_select_bwd(void* const* douts, const void* dy, const int* seg, int ngroups, int R, long row_bytes, HS stream);
 /* nn.GroupNorm(G, C) over each row's real tokens (+ act: 0 none, 1 relu, 2 mp_silu); mean / rstd [R][G] */
