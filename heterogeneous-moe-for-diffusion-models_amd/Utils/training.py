@@ -20,7 +20,7 @@ import torch
 
 from hdmoe_hip.dp import GradBuckets
 from hdmoe_hip.optim import FusedAdamW
-from .utils import EDM_LOSS, DeviceInputs, MaskGenerator, ZetaScheduler, sample_sigma_hybrid
+from .utils import EDM_LOSS, DeviceInputs, MaskGenerator, ZetaScheduler, null_text, sample_sigma_hybrid
 
 
 def build_optimizer(model: torch.nn.Module, optim_config: Dict[str, Any]) -> FusedAdamW:
@@ -46,10 +46,11 @@ def build_scheduler(optimizer: torch.optim.Optimizer, optim_config: Dict[str, An
                                                       eta_min=optim_config["eta_min"])
 
 
-def save_checkpoint(model, optimizer, step, mse_score, configs, filename, ema=None) -> str:
+def save_checkpoint(model, optimizer, step, mse_score, configs, filename, ema=None, null_text_emb=None) -> str:
     """Same dictionary and path rules as reference training.py:242-271 (keys step / model_state_dict /
     optimizer_state_dict / mse / config); tensors are written from host copies so the file loads on any device.
-    With `ema` (hdmoe_hip.ema.WeightEMA) the file additionally carries "ema_state_dict"; without it the dictionary is the reference's."""
+    With `ema` (hdmoe_hip.ema.WeightEMA) the file additionally carries "ema_state_dict", with `null_text_emb` (the null row of
+    `Trainer(cond_dropout=...)`) "null_text_emb", which the sampler needs for guidance; without them the dictionary is the reference's."""
     if "save_dir" in configs:
         save_path = configs["save_dir"]
     elif "model_configs" in configs and "save_dir" in configs["model_configs"]:
@@ -63,6 +64,8 @@ def save_checkpoint(model, optimizer, step, mse_score, configs, filename, ema=No
                   "mse": mse_score, "config": configs}
     if ema is not None:
         checkpoint["ema_state_dict"] = ema.state_dict()
+    if null_text_emb is not None:
+        checkpoint["null_text_emb"] = null_text_emb.detach().cpu()
     torch.save(checkpoint, str(full_path))
     print(f"   [Save] Checkpoint saved: {full_path}")
     return full_path
@@ -70,7 +73,8 @@ def save_checkpoint(model, optimizer, step, mse_score, configs, filename, ema=No
 
 def load_checkpoint(path: str, model: torch.nn.Module, optimizer: Optional[torch.optim.Optimizer] = None, map_location=None, ema=None) -> dict:
     """Inverse of `save_checkpoint` (reference training.py:303-304 loads only the model; resuming also needs the
-    optimizer moments).  Accepts files written by the reference's torch.optim.AdamW as well.  `ema` is restored when the file has one."""
+    optimizer moments).  Accepts files written by the reference's torch.optim.AdamW as well.  `ema` is restored when the file has one;
+    a saved "null_text_emb" comes back in the returned dictionary like every other key."""
     ck = torch.load(f=path, map_location=map_location, weights_only=False)
     model.load_state_dict(ck["model_state_dict"])
     if optimizer is not None and "optimizer_state_dict" in ck:
@@ -95,11 +99,18 @@ class Trainer:
     returned dictionary are then the static buffers of the captured step: valid until the next ``train_step`` overwrites them, so
     copy what has to live longer.
 
-    With both keywords at their defaults nothing changes: the inputs come from torch's generator and the step is launched eagerly."""
+    With both keywords at their defaults nothing changes: the inputs come from torch's generator and the step is launched eagerly.
+
+    ``cond_dropout=p`` > 0 trains the unconditional branch that classifier-free guidance extrapolates from: each step a sample's text is
+    replaced with probability p by ``null_text_emb`` (one text row; None: zeros), and the result gains ``"text_keep"`` (B,) float32 0/1.
+    With device inputs the decision is keyed by ``(seed, rank, step_idx)`` like every other input and made inside the one pass that
+    copies the text into its static buffer (`DeviceInputs.drop_text`); otherwise it is drawn from torch's generator.  At 0 nothing is
+    launched or drawn and the result has no new key."""
 
     def __init__(self, model, model_config, optim_config, loss_config, mask_config, zeta_config, max_grad_norm: float = 1.0,
                  fuse_clip_into_step: bool = True, logger=None, ema=None, ema_snapshot_every: Optional[int] = None,
-                 ema_snapshot_dir: Optional[str] = None, device_inputs: bool = False, graphed: bool = False, seed: Optional[int] = None):
+                 ema_snapshot_dir: Optional[str] = None, device_inputs: bool = False, graphed: bool = False, seed: Optional[int] = None,
+                 cond_dropout: float = 0.0, null_text_emb: Optional[torch.Tensor] = None):
         if ema_snapshot_every is not None:
             if ema is None:
                 raise ValueError("Trainer: ema_snapshot_every needs an ema")
@@ -107,6 +118,11 @@ class Trainer:
                 raise ValueError("Trainer: ema_snapshot_every needs ema_snapshot_dir")
             if int(ema_snapshot_every) < 1:
                 raise ValueError(f"Trainer: ema_snapshot_every must be >= 1, got {ema_snapshot_every}")
+        if not 0.0 <= float(cond_dropout) <= 1.0:            # NaN fails both comparisons
+            raise ValueError(f"Trainer: cond_dropout must lie in [0, 1], got {cond_dropout}")
+        if null_text_emb is not None and not torch.is_tensor(null_text_emb):
+            raise ValueError(f"Trainer: null_text_emb is a tensor of one text row or None, got {type(null_text_emb).__name__}")
+        self.cond_dropout, self.null_text_emb = float(cond_dropout), null_text_emb
         self.model, self.cfg, self.mask_cfg = model, model_config, mask_config
         self.optimizer = build_optimizer(model, optim_config)
         self.scheduler = build_scheduler(self.optimizer, optim_config)
@@ -140,7 +156,7 @@ class Trainer:
             rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
             self.seed = int(seed)
             self.inputs = DeviceInputs(model_config, mask_config, zeta_config, self.unet_mask_gen, self.vit_mask_gen, self.zeta_sched,
-                                       seed=self.seed, rank=rank)
+                                       seed=self.seed, rank=rank, cond_dropout=self.cond_dropout, null_text_emb=null_text_emb)
         # model_config2 takes the soft-gate transition from the mask config; model_config1 learns its scaling and has no such arguments
         import inspect
         names = inspect.signature(model.forward).parameters
@@ -160,7 +176,11 @@ class Trainer:
             raise RuntimeError("hdmoe_hip: tensors must live on the GPU (no CPU fallback in the product path)")
         dev = latent_images.device
         self._lat = latent_images.detach().to(torch.float32).contiguous().clone()
-        self._text = text_emb.detach().contiguous().clone()
+        if self.cond_dropout > 0:                            # the substitution is the copy into the static buffer
+            self._text = torch.empty(text_emb.shape, dtype=text_emb.dtype, device=dev)
+            self.inputs.drop_text(text_emb, self.step_idx, out=self._text)
+        else:
+            self._text = text_emb.detach().contiguous().clone()
         self._shapes = (tuple(latent_images.shape), tuple(text_emb.shape))
         b = self.inputs.generate(self._lat, self.step_idx)
 
@@ -192,19 +212,29 @@ class Trainer:
             raise ValueError(f"Trainer(graphed=True): batch shapes {tuple(latent_images.shape)}, {tuple(text_emb.shape)} differ from the "
                              f"captured step's {self._shapes[0]}, {self._shapes[1]}")
         self._lat.copy_(latent_images)
-        self._text.copy_(text_emb)
+        keep = None
+        if self.cond_dropout > 0:
+            keep = self.inputs.drop_text(text_emb, self.step_idx, out=self._text)[1]
+        else:
+            self._text.copy_(text_emb)
         b = self.inputs.generate(self._lat, self.step_idx)
         res = self._staged()
         self.buckets.finish()
-        return res["out_model"], res["loss"], b["sigma"]
+        return res["out_model"], res["loss"], b["sigma"], keep
 
     def train_step(self, latent_images: torch.Tensor, text_emb: torch.Tensor) -> dict:
-        """One iteration on (latents (B,C,H,W), text embeddings).  Returns {"loss", "out_model", "sigma"}; with ``graphed=True`` their
-        tensors are the captured step's static buffers, valid until the next call."""
+        """One iteration on (latents (B,C,H,W), text embeddings).  Returns {"loss", "out_model", "sigma"}, and "text_keep" when
+        ``cond_dropout`` > 0; with ``graphed=True`` their tensors are the captured step's static buffers, valid until the next call."""
         if self.device_inputs:
             return self._train_step_device(latent_images, text_emb)
         cfg, mc, step = self.cfg, self.mask_cfg, self.step_idx
         dev = latent_images.device
+        keep = None
+        if self.cond_dropout > 0:                            # no key to be faithful to in this mode: torch's generator
+            null = null_text(self.null_text_emb, text_emb)
+            kept = torch.rand(text_emb.shape[0], device=text_emb.device) >= self.cond_dropout
+            text_emb = torch.where(kept.view(-1, *([1] * (text_emb.ndim - 1))), text_emb, null)
+            keep = kept.to(torch.float32)
         sigma = sample_sigma_hybrid(batch_size=latent_images.shape[0], sigma_max=cfg["sigma_max"], sigma_min=cfg["sigma_min"],
                                     p_mean=mc["p_mean"], p_std=mc["p_std"], extreme_prob=0.5, device=dev)
         images_noised = latent_images + torch.randn_like(latent_images) * sigma
@@ -214,16 +244,19 @@ class Trainer:
         self.buckets.zero_grad()
         loss["loss"].backward()
         self.buckets.finish()
-        return self._update(step, loss, out_model, sigma)
+        return self._update(step, loss, out_model, sigma, keep)
 
     def _train_step_device(self, latent_images: torch.Tensor, text_emb: torch.Tensor) -> dict:
         step = self.step_idx
+        keep = None
         if self.graphed:
-            out_model, loss, sigma = self._graphed_fwd_bwd(latent_images, text_emb)
+            out_model, loss, sigma, keep = self._graphed_fwd_bwd(latent_images, text_emb)
             self._log_forward(step, loss, out_model, sigma)
         else:
             if latent_images.dtype != torch.float32 or not latent_images.is_contiguous():
                 latent_images = latent_images.to(torch.float32).contiguous()
+            if self.cond_dropout > 0:
+                text_emb, keep = self.inputs.drop_text(text_emb, step)
             b = self.inputs.generate(latent_images, step)
             sigma = b["sigma"]
             out_model, loss = self._fwd_loss(b["x"], latent_images, sigma, text_emb, b["unet_mask"], b["vit_mask"], b["zeta"])
@@ -231,7 +264,7 @@ class Trainer:
             self.buckets.zero_grad()
             loss["loss"].backward()
             self.buckets.finish()
-        return self._update(step, loss, out_model, sigma)
+        return self._update(step, loss, out_model, sigma, keep)
 
     def _log_forward(self, step: int, loss: dict, out_model: dict, sigma: torch.Tensor) -> None:
         mc = self.mask_cfg
@@ -244,7 +277,7 @@ class Trainer:
                                      sigma=sigma, p_mean=mc["p_mean"], p_std=mc["p_std"])
             lg.log_scaling_gating(scaling_factors=out_model["scaling_net_out"], gate_weights=out_model["out_gate"], sigma=sigma)
 
-    def _update(self, step: int, loss: dict, out_model: dict, sigma: torch.Tensor) -> dict:
+    def _update(self, step: int, loss: dict, out_model: dict, sigma: torch.Tensor, keep: Optional[torch.Tensor] = None) -> dict:
         """Everything behind the backward, in the reference's order: gradient logs, clip + AdamW, EMA, scheduler."""
         lg = self.logger
         if lg is not None:
@@ -262,7 +295,10 @@ class Trainer:
                 self._save_ema_snapshot(step + 1)
         self.scheduler.step()
         self.step_idx += 1
-        return {"loss": loss, "out_model": out_model, "sigma": sigma}
+        res = {"loss": loss, "out_model": out_model, "sigma": sigma}
+        if keep is not None:
+            res["text_keep"] = keep
+        return res
 
     def _save_ema_snapshot(self, step: int) -> None:
         """A host copy of every average (it syncs).  The averages are bit-identical across data-parallel ranks: rank 0 writes."""

@@ -4,7 +4,8 @@
 ``EDM_LOSS`` runs as one fused HIP forward + one fused backward with no ``.item()`` host syncs.  The input generators
 produce a few (B,)/(B,E) values per step from torch's RNG before the timed path starts; they are kept as plain
 torch device ops (data generation, not the denoiser's arithmetic).  ``DeviceInputs`` is their fused form: one HIP call per step
-writes sigma, the noised latents, both masks and zeta into static buffers, keyed by (seed, rank, step) instead of a generator.
+writes sigma, the noised latents, both masks and zeta into static buffers, keyed by (seed, rank, step) instead of a generator; its
+``drop_text`` is the conditioning dropout that trains the unconditional branch of classifier-free guidance, under the same key.
 """
 from __future__ import annotations
 
@@ -114,20 +115,32 @@ class DeviceInputs:
 
     It owns the static output buffers: allocated by the first ``generate`` and fixed to that latent shape, so captured graphs can
     read them.  The outputs depend on ``(seed, rank, step)`` alone -- no generator state, no host sync -- so a resumed run regenerates
-    the inputs of any step.  Bandwidths and zeta are the host schedulers' values for the step."""
+    the inputs of any step.  Bandwidths and zeta are the host schedulers' values for the step.
+
+    ``cond_dropout`` > 0: ``drop_text`` replaces a sample's text by ``null_text_emb`` (one row; None: zeros) with that probability,
+    in the one pass that copies the text into a static buffer (hdmoe_text_dropout), keyed like everything else here."""
 
     GOLDEN = 0x9E3779B97F4A7C15
 
     def __init__(self, model_config, mask_config, zeta_config, unet_mask_gen: "MaskGenerator", vit_mask_gen: "MaskGenerator",
-                 zeta_sched: "ZetaScheduler", seed: int, rank: int = 0, extreme_prob: float = 0.5):
+                 zeta_sched: "ZetaScheduler", seed: int, rank: int = 0, extreme_prob: float = 0.5, cond_dropout: float = 0.0,
+                 null_text_emb: Optional[torch.Tensor] = None):
         self.cfg, self.mask_cfg, self.zeta_cfg = model_config, mask_config, zeta_config
         self.unet_mask_gen, self.vit_mask_gen, self.zeta_sched = unet_mask_gen, vit_mask_gen, zeta_sched
         if unet_mask_gen.expert_centers.numel() != vit_mask_gen.expert_centers.numel() or unet_mask_gen.min_active != vit_mask_gen.min_active:
             raise ValueError("DeviceInputs: both mask generators need the same number of experts and the same min_active")
         self.seed = (int(seed) + int(rank) * self.GOLDEN) & 0xFFFFFFFFFFFFFFFF
         self.extreme_prob = float(extreme_prob)
+        self.cond_dropout = float(cond_dropout)
+        if not 0.0 <= self.cond_dropout <= 1.0:
+            raise ValueError(f"DeviceInputs: cond_dropout must lie in [0, 1], got {cond_dropout}")
+        if null_text_emb is not None and not torch.is_tensor(null_text_emb):
+            raise ValueError(f"DeviceInputs: null_text_emb is a tensor of one text row or None, got {type(null_text_emb).__name__}")
+        self.null_text_emb = null_text_emb
         self.shape = None
         self.buf = None
+        self.keep = self.text = self._null = None             # drop_text's static buffers and the null row as the kernel reads it
+        self._text_like = None
 
     def _alloc(self, latents: torch.Tensor) -> None:
         dev, B = latents.device, latents.shape[0]
@@ -157,3 +170,45 @@ class DeviceInputs:
                          vit_bw=self.vit_mask_gen.bandwidth_scheduler(step), min_active=self.unet_mask_gen.min_active,
                          zeta=self.zeta_sched.get_zeta(step=step))
         return b
+
+    def drop_text(self, text: torch.Tensor, step: int, out: Optional[torch.Tensor] = None):
+        """(text_out, keep) of step `step`: keep (B,) float32 0/1 under the key (seed, rank, step), text_out[i] = text[i] where
+        keep[i] == 1 and the null row otherwise.  `keep` is a static buffer, and so is text_out unless the caller brings `out`
+        (a captured step's own text buffer); both hold the step's values until the next call.  The first call fixes shape and dtype."""
+        if not text.is_cuda:
+            raise RuntimeError("hdmoe_hip: tensors must live on the GPU (no CPU fallback in the product path)")
+        text = text.detach()
+        if not text.is_contiguous():
+            text = text.contiguous()
+        like = (tuple(text.shape), text.dtype)
+        if self._text_like is None:
+            self._null = _null_row(self.null_text_emb, text)
+            self.keep = torch.zeros(text.shape[0], dtype=torch.float32, device=text.device)
+            self._text_like = like
+        elif like != self._text_like:
+            raise ValueError(f"DeviceInputs: text {like} differs from the static buffers' {self._text_like}")
+        if out is None:
+            if self.text is None:
+                self.text = torch.empty_like(text)
+            out = self.text
+        ops.text_dropout(out, self.keep, text, self._null, self.seed, int(step), self.cond_dropout)
+        return out, self.keep
+
+
+def _null_row(null: Optional[torch.Tensor], like: torch.Tensor) -> Optional[torch.Tensor]:
+    """`null` as one contiguous row of `like` (its device and dtype); ValueError unless it has the shape of like[0]."""
+    if null is None:
+        return None
+    if not torch.is_tensor(null) or tuple(null.shape) != tuple(like.shape[1:]):
+        got = tuple(null.shape) if torch.is_tensor(null) else type(null).__name__
+        raise ValueError(f"null text embedding: expected one row of shape {tuple(like.shape[1:])}, got {got}")
+    return null.detach().to(device=like.device, dtype=like.dtype).contiguous()
+
+
+def null_text(null: Optional[torch.Tensor], like: torch.Tensor) -> torch.Tensor:
+    """The null row a model was trained with (`Trainer(null_text_emb=...)`; None: zeros) as a batch of `like`'s shape, dtype and device:
+    what `EDM_Sampler.sample` and `forward_guided` take as `uncond_text_emb`."""
+    row = _null_row(null, like)
+    if row is None:
+        return torch.zeros_like(like)
+    return row.unsqueeze(0).expand(like.shape).contiguous()

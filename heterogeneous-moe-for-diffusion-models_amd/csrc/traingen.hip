@@ -5,6 +5,10 @@
 // Two launches.  The per-sample part (B <= 4096 values, a B x B ranking) is one workgroup: it needs all B shuffle keys at once, and in
 // LDS the ranking is B broadcast reads per position.  The noising is a plain HBM-bound pass over B * chw elements on the whole device
 // and reads the sigma the first kernel wrote; fusing the two would make every workgroup of the large pass repeat the ranking.
+//
+// hdmoe_text_dropout is the conditioning dropout of the same step (classifier-free guidance): the copy of the text embeddings into
+// their static buffer with a per-sample substitution by the null row folded in.  Its decision is one Philox block per sample, which
+// every workgroup draws again for the row segment it moves -- unlike the ranking, that is nothing beside the segment's tens of KB.
 #include "common.h"
 #include "hdmoe.h"
 
@@ -95,6 +99,53 @@ __global__ __launch_bounds__(256) void gen_noise_kernel(float* x, const float* x
   }
 }
 
+// Rows of row_n elements of T (uint4 on the 16-byte path), cut into `segs` equal segments of seg_len <= DROP_SEG elements; one segment
+// per workgroup and trip.  The drop decision is uniform over the workgroup (draw d_i of include/hdmoe.h: word i % 4 of block (i / 4,
+// c1 = 1) under the r = 3 key), so it is scalar work in front of the segment's loads: long segments, DROP_U independent loads per
+// thread, keep that preamble small beside the traffic (measured at (256, 77 x 768) fp32: DROP_U = 4 / 8 / 16 -> 18.7 / 18.0 / 17.7 us).
+constexpr int DROP_TPB = 256;
+constexpr int DROP_U = 16;
+constexpr int DROP_SEG = DROP_TPB * DROP_U;
+
+template <typename T>
+__global__ __launch_bounds__(DROP_TPB) void text_dropout_kernel(T* out, float* keep, const T* text, const T* null_row, uint32_t klo,
+                                                                 uint32_t khi, long row_n, long seg_len, long segs, long units, float p) {
+  for (long u = blockIdx.x; u < units; u += gridDim.x) {
+    const long i = u / segs, s = u - i * segs;
+    uint32_t r[4];
+    philox((uint32_t)(i >> 2), 1u, klo, khi, r);
+    const int lane = (int)(i & 3);
+    const uint32_t w = lane == 0 ? r[0] : lane == 1 ? r[1] : lane == 2 ? r[2] : r[3];
+    const bool drop = u01(w) < p;
+    if (s == 0 && threadIdx.x == 0) keep[i] = drop ? 0.f : 1.f;
+    const T* src = drop ? null_row : text + i * row_n;       // nullptr: a dropped row without a null row is zeros
+    T* dst = out + i * row_n;
+    const long e0 = s * seg_len + threadIdx.x;
+    const long end = e0 - threadIdx.x + seg_len < row_n ? e0 - threadIdx.x + seg_len : row_n;
+    T v[DROP_U];
+#pragma unroll
+    for (int j = 0; j < DROP_U; ++j) {
+      const long e = e0 + (long)j * DROP_TPB;
+      v[j] = T{};
+      if (src && e < end) v[j] = src[e];
+    }
+#pragma unroll
+    for (int j = 0; j < DROP_U; ++j) {
+      const long e = e0 + (long)j * DROP_TPB;
+      if (e < end) dst[e] = v[j];
+    }
+  }
+}
+
+template <typename T>
+void launch_text_dropout(void* out, float* keep, const void* text, const void* null_row, uint32_t klo, uint32_t khi, long B, long row_n,
+                         float p, hipStream_t stream) {
+  const long segs = (row_n + DROP_SEG - 1) / DROP_SEG, seg_len = (row_n + segs - 1) / segs, units = B * segs;
+  const long trips = (units + 2047) / 2048, grid = (units + trips - 1) / trips;      // <= 2048 workgroups, the same trips for all but the last
+  hipLaunchKernelGGL(text_dropout_kernel<T>, dim3((unsigned)grid), dim3(DROP_TPB), 0, stream, (T*)out, keep, (const T*)text,
+                     (const T*)null_row, klo, khi, row_n, seg_len, segs, units, p);
+}
+
 inline void stream_key(unsigned long long seed, unsigned long long ctr, uint32_t& lo, uint32_t& hi) {   // mix_seed on the host
   const unsigned long long k = seed + ctr * 0x9E3779B97F4A7C15ull;
   lo = (uint32_t)k; hi = (uint32_t)(k >> 32);
@@ -135,6 +186,22 @@ int hdmoe_train_inputs(float* x, float* sigma, float* unet_mask, float* vit_mask
     const long blocks = (n + 255) / 256;
     hipLaunchKernelGGL(gen_noise_kernel<1>, dim3((unsigned)(blocks > 2048 ? 2048 : blocks)), dim3(256), 0, stream, x, x0, sigma, lo, hi, chw, n);
   }
+  return hdmoe_launch_status();
+}
+
+int hdmoe_text_dropout(void* out, float* keep, const void* text, const void* null_row, unsigned long long seed, unsigned long long step,
+                       long B, long row, int elem_bytes, double p, hipStream_t stream) {
+  if (!out || !keep || !text || out == text) return HDMOE_EINVAL;
+  if (B < 1 || row < 1 || (elem_bytes != 2 && elem_bytes != 4) || !(p >= 0.0 && p <= 1.0)) return HDMOE_EINVAL;
+  uint32_t lo, hi;
+  stream_key(seed, 4ull * step + 3ull, lo, hi);
+  const long bytes = row * elem_bytes;
+  if (bytes % 16 == 0 && al16(out) && al16(text) && al16(null_row))
+    launch_text_dropout<uint4>(out, keep, text, null_row, lo, hi, B, bytes / 16, (float)p, stream);
+  else if (elem_bytes == 4)
+    launch_text_dropout<uint32_t>(out, keep, text, null_row, lo, hi, B, row, (float)p, stream);
+  else
+    launch_text_dropout<uint16_t>(out, keep, text, null_row, lo, hi, B, row, (float)p, stream);
   return hdmoe_launch_status();
 }
 

@@ -1860,6 +1860,34 @@ def train_inputs(x: Tensor, sigma: Tensor, unet_mask: Tensor, vit_mask: Tensor, 
         raise
 
 
+def text_dropout(out: Tensor, keep: Tensor, text: Tensor, null: Optional[Tensor], seed: int, step: int, p: float) -> None:
+    """Conditioning dropout of training step `step` under `seed` in one launch (include/hdmoe.h, hdmoe_text_dropout): keep (B,) float32
+    0/1, out[i] = text[i] where keep[i] == 1 and `null` (one row, text.shape[1:]; None: zeros) otherwise.  text is (B, ...) float32,
+    bfloat16 or float16; sample i is dropped iff its keyed draw is < float32(p).  Nothing is read from torch's generator or the library's
+    seed stream and nothing syncs.  ValueError -- before anything is written -- for a non-contiguous tensor, out unlike text in dtype or
+    shape, null not one row of text's dtype, keep not (B,) float32, out sharing storage with text, p outside [0, 1], step < 0."""
+    if text.ndim < 2 or text.shape[0] < 1 or text.numel() == 0:
+        raise ValueError(f"text_dropout: text is (B, ...) with B >= 1 and a non-empty row, got {tuple(text.shape)}")
+    if text.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(f"text_dropout: text must be float32, bfloat16 or float16, got {text.dtype}")
+    B = text.shape[0]
+    want = {"out": (out, text.shape, text.dtype), "keep": (keep, (B,), torch.float32), "text": (text, None, text.dtype)}
+    if null is not None:
+        want["null"] = (null, text.shape[1:], text.dtype)
+    for name, (t, shape, dt) in want.items():
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"text_dropout: {name} must be contiguous {dt}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"text_dropout: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    if out.is_cuda and text.is_cuda and out.untyped_storage().data_ptr() == text.untyped_storage().data_ptr():
+        raise ValueError("text_dropout: out shares its storage with text")
+    p = float(p)
+    if not 0.0 <= p <= 1.0 or int(step) < 0:
+        raise ValueError(f"text_dropout: p in [0, 1] and step >= 0, got p={p}, step={step}")
+    call("hdmoe_text_dropout", out, keep, text, null, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), B, text.numel() // B,
+         text.element_size(), p)
+
+
 # =====================================================================================================
 # layout / boundary
 # =====================================================================================================

@@ -359,6 +359,19 @@ int hdmoe_train_inputs(float* x, float* sigma, float* unet_mask, float* vit_mask
                        const float* unet_centers, const float* vit_centers, unsigned long long seed, unsigned long long step, long B, long chw,
                        int E, int min_active, double sigma_min, double sigma_max, double p_mean, double p_std, double extreme_prob,
                        double unet_bw, double vit_bw, float zeta, HS stream);
+/* Text-conditioning dropout of one step, for classifier-free guidance: row i of out (B rows of `row` elements of elem_bytes = 4 or 2
+ * bytes -- the kernel moves bytes, so fp32 / bf16 / fp16; a row is everything behind the batch dimension) is row i of text when
+ * keep[i] == 1 and null_row (one row; NULL: zeros) otherwise; keep (B) fp32 holds 0 / 1.  One launch over the whole device: the copy
+ * of the text into its static buffer with the substitution folded in.
+ * RNG contract (continued).  The drop draw of sample i is d_i = u01(word i % 4 of Philox4x32-10 block (c0 = i / 4, c1 = 1)) under the
+ * key of the r = 3 stream of that step, seed + (4 step + 3) * 0x9E3779B97F4A7C15; the shuffle keys k_i are the same key's blocks with
+ * c1 = 0, so no existing draw changes and no counter 4 step + r is reused.  Sample i is dropped iff d_i < (float)p; u01 > 0, so p = 0
+ * drops nothing, and p = 1 drops everything but a sample whose 24-bit word is 2^24 - 1 (its + 0.5f rounds u01 to 1.0f in fp32: one draw
+ * in 2^24).  (seed, step) alone fix the result.
+ * row * elem_bytes % 16 == 0 with out / text / null_row 16-byte aligned takes the 16-byte path, anything else moves elements.
+ * HDMOE_EINVAL: NULL out / keep / text, B < 1, row < 1, elem_bytes not 2 or 4, p outside [0, 1] or NaN, out == text. */
+int hdmoe_text_dropout(void* out, float* keep, const void* text, const void* null_row, unsigned long long seed, unsigned long long step,
+                       long B, long row, int elem_bytes, double p, HS stream);
 
 /* ---- K6: norms  (model_internals.py:8-30; nn.GroupNorm / nn.LayerNorm in model_components.py) ------------ */
 int hdmoe_pixelnorm_fwd(void* xn, void* h, const void* x, long rows, int C, int dtype, HS stream);               /* h = mp_silu(xn), optional */
