@@ -1464,6 +1464,39 @@ int hdmoe_wprep_bwd(const float* const* w_raw, const float* const* gain_ptr, flo
   return hdmoe_launch_status();
 }
 
+// The generic kernels of this file, the tail of the walk below: plan, then launch -- or, route != null, route[0 .. 5) = the plan's kernel
+// and template arguments and nothing is launched.
+static int conv_fwd_generic(const ConvArgs& a, int dtype, hipStream_t stream, int* route) {
+  CvPlan p;
+  if (const int rc = conv_fwd_plan(a, dtype, p)) return rc;
+  if (route) { route[0] = p.kernel; route[1] = p.NT; route[2] = p.vec; route[3] = p.lepi; route[4] = p.NHR; return HDMOE_OK; }
+  if (p.kernel == HDMOE_ROUTE_CONV_FWD5) conv_fwd5_lds_attr();
+  conv_fwd_launch(a, dtype, p, stream);
+  return hdmoe_launch_status();
+}
+
+// The one walk over the forward / dgrad kernel families, in the order they are tried; hdmoe_conv_fwd launches by it and
+// hdmoe_conv_fwd_route asks it.  route == null: launch.  route != null: decide only -- nothing is launched or counted, route[0] =
+// HDMOE_ROUTE_CONV_* and route[1 ..] = that family's template arguments (include/hdmoe.h).
+static int conv_fwd_dispatch(const ConvArgs& a, int dtype, hipStream_t stream, int* route) {
+  int* const t = route ? route + 1 : nullptr;
+  int fam, rc;
+  if (dtype == HDMOE_F32S) {                               // fp32 tensors on the bf16 pipe (conv6s.hip); callers ask for the domain first
+    fam = HDMOE_ROUTE_CONV_CONV6S; rc = conv6_split_try_launch(a, (long)a.ngroups * a.wstride, nullptr, stream, t);
+    if (rc == 1) { fam = HDMOE_ROUTE_CONV_NONE; rc = route ? HDMOE_OK : HDMOE_EINVAL; }
+  } else if (dtype != HDMOE_F32 && dtype != HDMOE_BF16) {
+    return HDMOE_EDTYPE;
+  } else {
+    fam = HDMOE_ROUTE_CONV_CONV7; rc = conv7_try_launch(a, dtype, stream, t);   // k x k expert layers on 32 x 32 / 16 x 16 maps: whole-image streaming kernel (conv7.hip)
+    if (rc > 0) { fam = HDMOE_ROUTE_CONV_CONV6; rc = conv6_try_launch(a, nullptr, dtype, stream, t); }   // k x k layers of the experts / trunks: persistent LDS-DMA kernel (conv6.hip)
+    if (rc > 0) { fam = HDMOE_ROUTE_CONV_KGEMM; rc = kgemm_try_launch(a, dtype, stream, nullptr, 0, t); }   // pointwise, long contraction, few outputs (kgemm.hip)
+    if (rc > 0) { fam = HDMOE_ROUTE_CONV_GLIN; rc = glin_try_launch(a, dtype, stream, t); }   // grouped fp32 linear on one-position rows, long input (mlinear.hip)
+    if (rc > 0) return conv_fwd_generic(a, dtype, stream, route);
+  }
+  if (route && rc == HDMOE_OK) route[0] = fam;               // (a sibling took the layer, or none: their template arguments are in t[])
+  return rc;
+}
+
 int hdmoe_conv_fwd(const void* x, const void* w, void* y, const void* res, float alpha, float beta,
                    const int* seg, int ngroups, long wstride, int N, int H, int W, int Ho, int Wo, int Cin,
                    int Cphys, int Ipad, int Cout, int Cstore, int stride, int ones, const int* kh, const int* kw,
@@ -1471,23 +1504,29 @@ int hdmoe_conv_fwd(const void* x, const void* w, void* y, const void* res, float
   if (!x || !w || !y || N < 0 || ngroups < 1 || ngroups > HDMOE_MAX_GROUPS) return HDMOE_EINVAL;
   if (Ipad % 16 || Ipad < Cin || Cin != Cphys + (ones ? 1 : 0) || Cstore > Cout || stride < 1) return HDMOE_EINVAL;
   if (N == 0 || Ho * Wo == 0) return HDMOE_OK;
-  const ConvArgs a = conv_fwd_args(x, w, y, res, alpha, beta, seg, ngroups, wstride, N, H, W, Ho, Wo, Cin, Cphys, Ipad, Cout, Cstore, stride, ones,
-                                   kh, kw, pt, pl);
-  if (dtype == HDMOE_F32S) {                               // fp32 tensors on the bf16 pipe (conv6s.hip); callers check the domain first
-    const int rc = conv6_split_try_launch(a, (long)ngroups * wstride, nullptr, stream);
-    return rc == 1 ? HDMOE_EINVAL : rc;
-  }
-  if (dtype != HDMOE_F32 && dtype != HDMOE_BF16) return HDMOE_EDTYPE;
-  int rc = conv7_try_launch(a, dtype, stream);               // k x k expert layers on 32 x 32 maps: whole-image streaming kernel (conv7.hip)
-  if (rc > 0) rc = conv6_try_launch(a, nullptr, dtype, stream);   // k x k layers of the experts / trunks: persistent LDS-DMA kernel (conv6.hip)
-  if (rc > 0) rc = kgemm_try_launch(a, dtype, stream);       // pointwise, long contraction, few outputs (kgemm.hip)
-  if (rc > 0) rc = glin_try_launch(a, dtype, stream);        // grouped fp32 linear on one-position rows, long input (mlinear.hip)
-  if (rc <= 0) return rc;
-  CvPlan p;
-  if ((rc = conv_fwd_plan(a, dtype, p))) return rc;
-  if (p.kernel == HDMOE_ROUTE_CONV_FWD5) conv_fwd5_lds_attr();
-  conv_fwd_launch(a, dtype, p, stream);
-  return hdmoe_launch_status();
+  return conv_fwd_dispatch(conv_fwd_args(x, w, y, res, alpha, beta, seg, ngroups, wstride, N, H, W, Ho, Wo, Cin, Cphys, Ipad, Cout, Cstore, stride,
+                                         ones, kh, kw, pt, pl), dtype, stream, nullptr);
+}
+
+int hdmoe_conv_fwd_route(int* route, int N, int H, int W, int Ho, int Wo, int Cin, int Cphys, int Ipad, int Cout, int Cstore, int stride, int ones,
+                         int ngroups, int has_seg, int has_res, long wstride, const int* kh, const int* kw, const int* pt, const int* pl,
+                         int dtype, int aligned16) {
+  if (!route || N < 0 || ngroups < 1 || ngroups > HDMOE_MAX_GROUPS) return HDMOE_EINVAL;
+  if (Ipad % 16 || Ipad < Cin || Cin != Cphys + (ones ? 1 : 0) || Cstore > Cout || stride < 1) return HDMOE_EINVAL;
+  route[0] = HDMOE_ROUTE_CONV_NONE;
+  for (int i = 1; i < 5; ++i) route[i] = 0;
+  if (N == 0 || Ho * Wo == 0) return HDMOE_OK;
+  const void* ptr = (const void*)(uintptr_t)(aligned16 ? 16 : 4);   // stands for every tensor of the call; never dereferenced
+  return conv_fwd_dispatch(conv_fwd_args(ptr, ptr, (void*)ptr, has_res ? ptr : nullptr, 1.f, 0.f, has_seg ? (const int*)ptr : nullptr, ngroups, wstride,
+                                         N, H, W, Ho, Wo, Cin, Cphys, Ipad, Cout, Cstore, stride, ones, kh, kw, pt, pl), dtype, nullptr, route);
+}
+
+int hdmoe_conv_generic_route(int* route, int N, int H, int W, int Ho, int Wo, int Cin, int Cphys, int Ipad, int Cout, int Cstore, int stride,
+                             int ones, int ngroups, const int* kh, const int* kw, int dtype, int aligned16) {
+  if (!route || ngroups < 1 || ngroups > HDMOE_MAX_GROUPS || (dtype != HDMOE_F32 && dtype != HDMOE_BF16)) return HDMOE_EINVAL;
+  const void* ptr = (const void*)(uintptr_t)(aligned16 ? 16 : 4);
+  return conv_fwd_generic(conv_fwd_args(ptr, ptr, (void*)ptr, ptr, 1.f, 0.f, nullptr, ngroups, 0, N, H, W, Ho, Wo, Cin, Cphys, Ipad, Cout, Cstore, stride,
+                                        ones, kh, kw, kh, kw), dtype, nullptr, route);   // (the pads do not enter the plan)
 }
 
 /* Pointwise (1 x 1, stride 1) forward / dgrad of ONE group, y = alpha * x w^T, over the rows [rows[0], rows[1]) of x [N][H][W][Cin] only
@@ -1526,18 +1565,6 @@ int hdmoe_pw_fwd_rows(const void* x, const void* w, void* y, float alpha, const 
   if (p.kernel == HDMOE_ROUTE_CONV_FWD5) conv_fwd5_lds_attr();
   conv_fwd_launch(a, dtype, p, stream);                      // (rows outside the window find no group and leave)
   return hdmoe_launch_status();
-}
-
-int hdmoe_conv_generic_route(int* route, int N, int H, int W, int Ho, int Wo, int Cin, int Cphys, int Ipad, int Cout, int Cstore, int stride,
-                             int ones, int ngroups, const int* kh, const int* kw, int dtype, int aligned16) {
-  if (!route || ngroups < 1 || ngroups > HDMOE_MAX_GROUPS || (dtype != HDMOE_F32 && dtype != HDMOE_BF16)) return HDMOE_EINVAL;
-  const void* ptr = (const void*)(uintptr_t)(aligned16 ? 16 : 4);   // stands for every tensor of the call; never dereferenced
-  const ConvArgs a = conv_fwd_args(ptr, ptr, (void*)ptr, ptr, 1.f, 0.f, nullptr, ngroups, 0, N, H, W, Ho, Wo, Cin, Cphys, Ipad, Cout, Cstore, stride,
-                                   ones, kh, kw, kh, kw);           // (the pads do not enter the plan)
-  CvPlan p;
-  if (const int rc = conv_fwd_plan(a, dtype, p)) return rc;
-  route[0] = p.kernel; route[1] = p.NT; route[2] = p.vec; route[3] = p.lepi; route[4] = p.NHR;
-  return HDMOE_OK;
 }
 
 int hdmoe_conv_wgrad(const void* x, const void* dy, float* const* G, const int* seg, int ngroups, int N, int H,

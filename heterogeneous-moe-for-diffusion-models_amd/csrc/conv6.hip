@@ -82,10 +82,11 @@ int conv6_plan(const ConvArgs& c, int dtype, C6Plan& plan) {
   return 0;
 }
 
-int conv6_try_launch(const ConvArgs& c, const ConvFuse* fuse, int dtype, hipStream_t stream) {
+int conv6_try_launch(const ConvArgs& c, const ConvFuse* fuse, int dtype, hipStream_t stream, int* tmpl) {
   if (fuse && (fuse->in_scale || fuse->in_shift || fuse->stats)) return 1;
   C6Plan plan;
   if (conv6_plan(c, dtype, plan)) return 1;
+  if (tmpl) { tmpl[0] = plan.MT; tmpl[1] = plan.NT; return 0; }
   if (fuse && fuse->film_e) {                                // FiLM epilogue: second output tensor
     if (!fuse->film_h || (((uintptr_t)fuse->film_h) & 15) || c.res) return 1;
     plan.a.film_e = fuse->film_e; plan.a.film_h = fuse->film_h; plan.a.film_seed_dev = fuse->film_seed_dev;

@@ -77,9 +77,10 @@ int conv6s_plan(const ConvArgs& c, long wplane_elems, const ConvFuse* fuse, C6SP
   return 0;
 }
 
-int conv6_split_try_launch(const ConvArgs& c, long wplane_elems, const ConvFuse* fuse, hipStream_t stream) {
+int conv6_split_try_launch(const ConvArgs& c, long wplane_elems, const ConvFuse* fuse, hipStream_t stream, int* tmpl) {
   C6SPlan plan;
   if (conv6s_plan(c, wplane_elems, fuse, plan, true)) return 1;
+  if (tmpl) { tmpl[0] = plan.NT; return 0; }
   hdmoe_count_selection(HDMOE_SEL_CONV6S);
   static unsigned long long attr_set = 0;
   if (hdmoe_first_on_device(attr_set)) {

@@ -14,7 +14,8 @@ __global__ __launch_bounds__(512) void conv7_kernel(C7Args a) { conv7_body<CO, K
 
 }  // namespace
 
-constexpr int C7_MIN_IMAGES = 192;   // (ops.C7_MINN mirrors it)
+constexpr int C7_MIN_IMAGES = 192;
+extern "C" int hdmoe_conv7_min_images(void) { return C7_MIN_IMAGES; }
 
 // 0 = planned, 1 = outside the domain
 int conv7_plan(const ConvArgs& c, int dtype, C7Plan& plan) {
@@ -75,9 +76,10 @@ void conv7_launch(const C7Plan& p, hipStream_t stream) {
   }); }); });
 }
 
-int conv7_try_launch(const ConvArgs& c, int dtype, hipStream_t stream) {
+int conv7_try_launch(const ConvArgs& c, int dtype, hipStream_t stream, int* tmpl) {
   C7Plan plan;
   if (conv7_plan(c, dtype, plan)) return 1;
+  if (tmpl) { tmpl[0] = plan.CO; tmpl[1] = plan.kmask; tmpl[2] = plan.w16; return 0; }
   hdmoe_count_selection(plan.w16 ? HDMOE_SEL_CONV7_16 : HDMOE_SEL_CONV7_32);
   conv7_launch(plan, stream);
   return hdmoe_launch_status();

@@ -109,16 +109,18 @@ struct ConvFuse {
 };
 
 // Returns HDMOE_OK after launching, a negative status on a launch error, or 1 when the shape is outside conv6's domain
-// (the caller then takes the general kernels).
-int conv6_try_launch(const ConvArgs& a, const ConvFuse* fuse, int dtype, hipStream_t stream);
+// (the caller then takes the general kernels).  tmpl != null, here and in the forward *_try_launch helpers below: decide only -- same
+// return value, nothing launched or counted, tmpl[] = the template arguments of the kernel that would run (include/hdmoe.h,
+// hdmoe_conv_fwd_route).
+int conv6_try_launch(const ConvArgs& a, const ConvFuse* fuse, int dtype, hipStream_t stream, int* tmpl = nullptr);
 
 void* hdmoe_debug_stamp_buffer();     // development: the buffer registered with hdmoe_conv6_debug_stamps (conv6.hip), or null
 void hdmoe_count_selection(int which);   // host-side kernel-selection counter HDMOE_SEL_* += 1 (conv.hip, hdmoe_kernel_selections)
 // Whole-image streaming kernel for 32 x 32 maps (conv7.hip).  Same return convention.
-int conv7_try_launch(const ConvArgs& a, int dtype, hipStream_t stream);
+int conv7_try_launch(const ConvArgs& a, int dtype, hipStream_t stream, int* tmpl = nullptr);
 
 // Split-bf16 variant for fp32 tensors (conv6s.hip): w = bf16 [hi | lo][g][tap][Cout][Cin], `wplane_elems` elements per plane.
-int conv6_split_try_launch(const ConvArgs& a, long wplane_elems, const ConvFuse* fuse, hipStream_t stream);
+int conv6_split_try_launch(const ConvArgs& a, long wplane_elems, const ConvFuse* fuse, hipStream_t stream, int* tmpl = nullptr);
 
 // Pointwise (linear / 1x1, stride 1) weight gradient (lwgrad.hip): G[g] [Cout][Cin] fp32 slabs (+=).  Same return convention.
 // (lwgrad.hip's three: dry_run = decide only -- same return value, nothing launched)
@@ -126,7 +128,7 @@ int lwg_try_launch(const void* x, const void* dy, float* const* G, const int* se
                    int dtype, hipStream_t stream, bool dry_run = false);
 
 // Pointwise forward / dgrad with Cin >= 512 and Cout <= 64 (kgemm.hip).  Same return convention.
-int kgemm_try_launch(const ConvArgs& a, int dtype, hipStream_t stream, const int* rows = nullptr, long HW = 0);
+int kgemm_try_launch(const ConvArgs& a, int dtype, hipStream_t stream, const int* rows = nullptr, long HW = 0, int* tmpl = nullptr);
 
 // k x k fp32 weight gradient for tiny input channel counts (taps * Cin <= 64: the stem), one expert (lwgrad.hip).  Same return convention.
 int swg_try_launch(const void* x, const void* dy, float* G, int N, int H, int W, int Cin, int Cout, int k, int pt, int pl, int dtype,
@@ -137,4 +139,4 @@ int towg_try_launch(const void* x, const void* dy, float* G, int N, int H, int W
                     hipStream_t stream, bool dry_run = false);
 
 // Grouped fp32 linear on one-position rows with a long input, 256 <= Cin <= 1024 (the experts' text projection; mlinear.hip).  Same return convention.
-int glin_try_launch(const ConvArgs& a, int dtype, hipStream_t stream);
+int glin_try_launch(const ConvArgs& a, int dtype, hipStream_t stream, int* tmpl = nullptr);

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(512) void kgemm_kernel(KArgs a) {
 
 // Returns HDMOE_OK after launching, a negative status on a launch error, or 1 when the layer is outside this file's domain.
 // rows != null: the row window of hdmoe_pw_fwd_rows (HW positions per row), on the all-rows grid.
-int kgemm_try_launch(const ConvArgs& a, int dtype, hipStream_t stream, const int* rows, long HW) {
+int kgemm_try_launch(const ConvArgs& a, int dtype, hipStream_t stream, const int* rows, long HW, int* tmpl) {
   if (dtype != HDMOE_BF16 || a.ngroups != 1 || a.seg || a.stride != 1 || a.ones || a.kh[0] != 1 || a.kw[0] != 1 || a.pt[0] || a.pl[0]) return 1;
   constexpr int mink = 512;   // (768: the text projections of the fusion cross-attention, 37 + 31 -> ~2 x 12 us on the serial stage; same-box step -0.1 ms)
   if (a.Cin != a.Cphys || a.Ipad != a.Cin || a.Cin % 64 || a.Cin < mink || a.Cout != a.Cstore || a.Cout % 32 || a.Cout > 64) return 1;
@@ -102,6 +102,7 @@ int kgemm_try_launch(const ConvArgs& a, int dtype, hipStream_t stream, const int
   const long blocks = (k.M + 31) / 32;
   if (blocks > 0x7fffffffl) return 1;
   const int NT = a.Cout / 32;
+  if (tmpl) { tmpl[0] = NT; return 0; }
   const size_t lds = (size_t)8 * NT * 4096;
   conv_pick<1, 2>(NT, [&](auto Nt) { hipLaunchKernelGGL(kgemm_kernel<decltype(Nt)::value>, dim3((unsigned)blocks), dim3(512), lds, stream, k); });
   return hdmoe_launch_status();

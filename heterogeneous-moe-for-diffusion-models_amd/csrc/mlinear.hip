@@ -213,11 +213,12 @@ static bool ml_fill(MLArgs& a, const void* x, const int* seg, const float* const
 
 // Grouped fp32 linear with 256 <= I <= 1024 on one-position rows (H = W = 1): see glin_f32_kernel.  Same return convention as the other
 // *_try_launch helpers (1 = outside the domain).
-int glin_try_launch(const ConvArgs& c, int dtype, hipStream_t stream) {
+int glin_try_launch(const ConvArgs& c, int dtype, hipStream_t stream, int* tmpl) {
   if (dtype != HDMOE_F32 || c.stride != 1 || c.ones || c.H != 1 || c.W != 1 || c.Ho != 1 || c.Wo != 1 || c.Cin != c.Cphys) return 1;
   if (c.Cin < 256 || c.Cin > 1024 || c.Cin % 4 || c.Ipad % 4 || c.Cout != c.Cstore || c.N < 1) return 1;
   for (int g = 0; g < c.ngroups; ++g) if (c.kh[g] != 1 || c.kw[g] != 1 || c.pt[g] || c.pl[g]) return 1;
   if (((uintptr_t)c.x | (uintptr_t)c.w) & 15) return 1;
+  if (tmpl) { tmpl[0] = (c.Cin + 255) / 256; return 0; }
   GLArgs a;
   a.x = (const float*)c.x; a.w = (const float*)c.w; a.y = (float*)c.y; a.res = (const float*)c.res; a.seg = c.seg; a.wstride = c.wstride;
   a.R = c.N; a.I = c.Cin; a.Ipad = c.Ipad; a.O = c.Cout; a.ngroups = c.ngroups; a.alpha = c.alpha; a.beta = c.beta;

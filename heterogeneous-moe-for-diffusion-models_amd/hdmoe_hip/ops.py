@@ -8,6 +8,7 @@ token ``(N, S, C)`` or matrix ``(M, C)`` -- in float32 or bfloat16.  "Vector pat
 from __future__ import annotations
 
 import ctypes
+import functools
 import math
 from typing import List, Optional, Sequence
 
@@ -127,7 +128,8 @@ def _prof_ok() -> bool:
     return PROFILE is None or PROFILE_FUSED
 
 
-def _timed(kind: str, info: dict, name: str, *args):
+def _timed(kind: str, info, name: str, *args):
+    """``info``: the launch's record, or a callable that makes it -- called only when PROFILE is on and the launch was made."""
     if PROFILE is None:
         return call(name, *args)
     # An event pair also spans the time the stream sits idle waiting for the host to enqueue the kernel.  A spacer launch in
@@ -141,75 +143,56 @@ def _timed(kind: str, info: dict, name: str, *args):
     rc = call(name, *args)
     e.record()
     if rc == 0:
-        if name == "hdmoe_conv_wgrad6" and "deferred" not in info.get("wgrad_name", ""):
-            info = dict(info, wgrad_name="wgrad6_kernel<split> (+ reduce)" if info.get("dtype") == "split_bf16" else "wgrad6_kernel (+ reduce)")
-        PROFILE.append((kind, info, s, e))
+        PROFILE.append((kind, info() if callable(info) else info, s, e))
     return rc
 
 
-def _conv6_domain(x, Ho, Wo, O, I, Cstore, khs, kws, cphys, split):
-    """(kernel name, dtype label) when the launch goes to the conv6 kernels (csrc/conv6.hip / conv6s.hip), else None."""
-    if Cstore != O or cphys != I or I % 32 or O % 32 or not (Wo == 16 or Wo % 32 == 0) or Ho < 8:
-        return None
-    if split:
-        return (f"conv6_split_kernel<{2 if O % 64 == 0 else 1}>", "split_bf16") if all(k == 3 for k in khs) else None
-    if x.dtype != torch.bfloat16 or any(a != b or a not in (3, 5, 7) for a, b in zip(khs, kws)):
-        return None
-    return "conv6_bf16_kernel", "bfloat16"
+def _route(query: str, n: int, *args) -> list:
+    """The ``n`` route ints of a route query of the library (include/hdmoe.h: hdmoe_conv_fwd_route, hdmoe_conv_wgrad_route) -- the library
+    alone decides which kernel a layer gets, this asks it.  Host-only: nothing is launched.  Lists go as host int arrays."""
+    r = (ctypes.c_int * n)()
+    conv = [ctypes.cast(_int_array(a), ctypes.c_void_p) if isinstance(a, (list, tuple)) else int(a) for a in args]
+    if getattr(lib(), query)(ctypes.cast(r, ctypes.c_void_p), *conv) != 0:
+        raise RuntimeError(f"{query}: the library refuses the layer")
+    return list(r)
 
 
-def _conv_info(x, seg, N, Ho, Wo, O, I, Cstore, khs, kws, cphys, split=False):
-    """Shape record of one launch + the kernel instantiation hdmoe_conv_fwd will pick (mirrors csrc/conv.hip)."""
-    c6 = _conv6_domain(x, Ho, Wo, O, I, Cstore, khs, kws, cphys, split)
-    if c6 is not None:
-        tname = "float" if x.dtype == torch.float32 else "__bf16"
-        return dict(dtype=c6[1], seg=seg, N=N, HW=Ho * Wo, O=O, I=I, taps=[a * b for a, b in zip(khs, kws)], fwd_name=c6[0],
-                    wgrad_name=_wgrad_name(tname, O, sorted(set(a * b for a, b in zip(khs, kws))), I, cphys == I))
-    esz = x.element_size()
-    vec = cphys % (16 // esz) == 0
-    tname = "float" if x.dtype == torch.float32 else "__bf16"
-    nt = 1 if Cstore <= 32 else 2
-    v5ok = I == cphys and Cstore % 4 == 0
-    mk, mw = max(khs), max(kws)
-    tile2d = (v5ok and vec and Ho >= 8 and Wo > 32 and Wo % 32 == 0 and mk * mw > 1 and (8 + mk - 1) * (32 + mw - 1) * 4 <= 9 * 256
-              and mw * 32 * nt <= 576 and 80 * ((8 + mk - 1) * (32 + mw - 1) + mw * 32 * nt) <= 80 * 1024)
-    tw = 32 if tile2d else min(Wo, 256)
-    th = max(1, min(256 // tw, Ho))
-    lds = 80 * ((th + max(khs) - 1) * (tw + max(kws) - 1) + max(kws) * 32 * nt)
-    halo = (th + max(khs) - 1) * (tw + max(kws) - 1)
-    if Ho * Wo >= 64 and vec and halo * 4 <= (9 if v5ok else 7) * 256 and max(kws) * 32 * nt <= 576:
-        tg = min(576 // (max(kws) * 32 * nt), max(khs))
-        while tg > 1 and 80 * (halo + tg * max(kws) * 32 * nt) > 64 * 1024:
-            tg -= 1
-        lds3 = 80 * (halo + tg * max(kws) * 32 * nt)
-        if v5ok and lds3 <= 80 * 1024:
-            lepi = Cstore % (16 // esz) == 0 and 4 * 32 * (32 * nt + 16 // esz) * esz <= lds3
-            fwd_name = f"conv_fwd5_kernel<{tname}, {nt}, {'true' if lepi else 'false'}, {9 if halo * 4 > 7 * 256 else 7}>"
-        elif lds3 <= 64 * 1024 and halo * 4 <= 7 * 256:
-            fwd_name = f"conv_fwd3_kernel<{tname}, {nt}>"
-        else:
-            fwd_name = f"conv_fwd2_kernel<{tname}, {nt}, {'true' if vec else 'false'}>"
-    elif Ho * Wo >= 64 and lds <= 64 * 1024:
-        fwd_name = f"conv_fwd2_kernel<{tname}, {nt}, {'true' if vec else 'false'}>"
-    else:
-        nb = 1 if Cstore <= 32 else (2 if Cstore <= 64 else 4)
-        fwd_name = f"conv_fwd_kernel<{tname}, {nb}, {'true' if vec else 'false'}>"
-    return dict(dtype=str(x.dtype).replace("torch.", ""), seg=seg, N=N, HW=Ho * Wo, O=O, I=I, taps=[a * b for a, b in zip(khs, kws)],
-                fwd_name=fwd_name, wgrad_name=_wgrad_name(tname, O, sorted(set(a * b for a, b in zip(khs, kws))), I, cphys == I))
+@functools.lru_cache(maxsize=None)
+def _c7_min_images() -> int:
+    """conv7's least number of images (csrc/conv7.hip), asked of the library once."""
+    return lib().hdmoe_conv7_min_images()
 
 
-def _wgrad_name(tname, O, tap_classes, I=0, plain=False):
-    """Kernel instantiation(s) hdmoe_conv_wgrad picks (mirrors csrc/conv.hip: one launch per kernel-size class)."""
-    if plain and tap_classes == [1] and O % 32 == 0 and I % 32 == 0:          # pointwise layers: csrc/lwgrad.hip
-        return f"lwg_{'f32' if tname == 'float' else 'bf16'}_kernel<{2 if O % 64 == 0 else 1}, {2 if I % 64 == 0 else 1}>"
-    names = []
-    for taps in tap_classes:
-        passes = (taps + 27) // 28 if taps > 28 else 1
-        mt = 7 if passes > 1 else (taps if taps < 4 else (taps + 3) // 4)
-        names.append(f"{1 if O <= 32 else 2}, {3 if mt <= 3 else 7}" + (f" x{passes} passes" if passes > 1 else ""))   # (mt <= 7 always)
-    if len(names) == 1:
-        return f"conv_wgrad2_kernel<{tname}, {names[0]}, true>"
-    return f"conv_wgrad2_kernel<{tname}, {{{' | '.join(names)}}}, true> ({len(names)} launches per call)"
+# kernel names as csrc/ spells them, by HDMOE_ROUTE_CONV_* / HDMOE_ROUTE_WGRAD_* (include/hdmoe.h); r = the route array, b = its ints as bools
+_FWD_KERNELS = ("conv_fwd_kernel<{t}, {r[1]}, {b[2]}>", "conv_fwd2_kernel<{t}, {r[1]}, {b[2]}>", "conv_fwd3_kernel<{t}, {r[1]}>",
+                "conv_fwd5_kernel<{t}, {r[1]}, {b[3]}, {r[4]}>", "conv7_kernel<{r[1]}, {r[2]}, {b[3]}>", "conv6_bf16_kernel<{r[1]}, {r[2]}>",
+                "conv6_split_kernel<{r[1]}>", "kgemm_kernel<{r[1]}>", "glin_f32_kernel<{r[1]}>", "none")
+_WGRAD_KERNELS = (None, "conv_wgrad_kernel<{t}>", "swg_f32_kernel", "towg_bf16_kernel", "lwg_{s}_kernel")
+ROUTE_CONV6S = 6                           # HDMOE_ROUTE_CONV_CONV6S
+
+
+def _kernel_label(r, x: Tensor, wgrad: bool = False) -> str:
+    """The kernel instantiation(s) that a route array of hdmoe_conv_fwd_route / hdmoe_conv_wgrad_route names, for tensors of ``x``'s type."""
+    t, s = ("float", "f32") if x.dtype == torch.float32 else ("__bf16", "bf16")
+    b = ["true" if v else "false" for v in r]
+    if not wgrad:
+        return _FWD_KERNELS[r[0]].format(t=t, r=r, b=b)
+    if r[0]:
+        return _WGRAD_KERNELS[r[0]].format(t=t, s=s)
+    # conv_wgrad2_kernel<T, OT, MAXT, VEC>, one launch per pass of each kernel-size class: (passes, MAXT, OT, VEC) per class from r[2]
+    return " + ".join(f"conv_wgrad2_kernel<{t}, {r[4 + 4 * k]}, {r[3 + 4 * k]}, {b[5 + 4 * k]}>" + (f" x {r[2 + 4 * k]} passes" if r[2 + 4 * k] > 1 else "")
+                      for k in range(r[1]))
+
+
+def _conv_record(x, seg, N, HW, O, I, khs, kws, dtype=None, **name) -> dict:
+    return dict(dtype=dtype or str(x.dtype).replace("torch.", ""), seg=seg, N=N, HW=HW, O=O, I=I, taps=[a * b for a, b in zip(khs, kws)], **name)
+
+
+def _fwd_record(x, w, y, res, alpha, beta, seg, G, wstride, N, H, W, Ho, Wo, I, Cphys, Ipad, O, Cstore, stride, ones, khs, kws, pts, pls, dtc) -> dict:
+    """Shape record of one hdmoe_conv_fwd call, from its own arguments, with the kernel the library routes it to."""
+    r = _route("hdmoe_conv_fwd_route", 5, N, H, W, Ho, Wo, I, Cphys, Ipad, O, Cstore, stride, ones, G, seg is not None, res is not None, wstride,
+               khs, kws, pts, pls, dtc, all(t is None or t.data_ptr() % 16 == 0 for t in (x, w, y, res)))
+    return _conv_record(x, seg, N, Ho * Wo, O, I, khs, kws, "split_bf16" if r[0] == ROUTE_CONV6S else None, fwd_name=_kernel_label(r, x))
 
 
 def _kernel_hw(w: Tensor):
@@ -423,28 +406,33 @@ def _fused_bwd(bank, ent, label, name, x, dy, wd, dx, mid, ws, tail, defer, stat
     return True
 
 
-def _wgrad(info, x, dy, Gs, seg, G, N, H, W, Ho, Wo, I, Cphys, O, ones, khs, kws, pts, split=False, bank=None):
+def _wgrad(x, dy, Gs, seg, G, N, H, W, Ho, Wo, I, Cphys, O, ones, khs, kws, pts, split=False, bank=None):
     """Weight gradient of a (grouped) conv into the [tap][O][I] fp32 slabs ``Gs`` (+=).  k x k bf16 layers -- and fp32 layers in
     split-bf16 mode (the router trunks) -- take the atomic-free kernel (csrc/wgrad6.hip) with a cached workspace; everything else
     the general kernel."""
+    def rec(w6=None):                                         # the record of one attempt: made only when PROFILE is on and the attempt launched
+        if w6:
+            return lambda: _conv_record(x, seg, N, Ho * Wo, O, I, khs, kws, "split_bf16" if split else None, wgrad_name=w6)
+        return lambda: _conv_record(x, seg, N, Ho * Wo, O, I, khs, kws, wgrad_name=_kernel_label(_route(
+            "hdmoe_conv_wgrad_route", 34, N, H, W, Ho, Wo, I, Cphys, O, 1, ones, G, seg is not None, khs, kws, pts, pts, _dt(x),
+            x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0), x, wgrad=True))
+    w6 = "wgrad6_kernel<split>" if split else "wgrad6_kernel"
     if (x.dtype == torch.bfloat16 or split) and not ones and Ho == H and Wo == W and Cphys == I:
         dtc = F32S if split else _dt(x)
         kib = _w6_kib(G, N, H, W, I, O, khs, kws, dtc)
         # weight-bank layer: the partial slabs stay in the arena, the bank sums all layers' partials in one batched launch
         ws = _w6_workspace("arena", x.device, kib) if bank is not None and _prof_ok() else None
         if ws is not None:
-            if _timed("conv_wgrad", dict(info, dtype="split_bf16" if split else info.get("dtype"), wgrad_name="wgrad6_kernel<split> (deferred reduce)" if split else "wgrad6_kernel (deferred reduce)"),
-                      "hdmoe_conv_wgrad6", x, dy, Gs, seg, G, N, H, W, I, O, khs, kws, pts, pts, ws, ws.numel() * 4, dtc, 1) == 0:
+            if _timed("conv_wgrad", rec(w6 + " (deferred reduce)"), "hdmoe_conv_wgrad6", x, dy, Gs, seg, G, N, H, W, I, O, khs, kws, pts, pts, ws, ws.numel() * 4,
+                      dtc, 1) == 0:
                 bank.defer_w6(Gs, seg, ws, G, N, H, W, I, O, dtc, khs)
                 STATS["w6_defer"] += 1
                 return
         ws = _w6_workspace("stream", x.device, kib)
         if ws is not None:
-            if split:
-                info = dict(info, dtype="split_bf16")
-            if _timed("conv_wgrad", info, "hdmoe_conv_wgrad6", x, dy, Gs, seg, G, N, H, W, I, O, khs, kws, pts, pts, ws, ws.numel() * 4, dtc, 0) == 0:
+            if _timed("conv_wgrad", rec(w6 + " (+ reduce)"), "hdmoe_conv_wgrad6", x, dy, Gs, seg, G, N, H, W, I, O, khs, kws, pts, pts, ws, ws.numel() * 4, dtc, 0) == 0:
                 return
-    _timed("conv_wgrad", info, "hdmoe_conv_wgrad", x, dy, Gs, seg, G, N, H, W, Ho, Wo, I, Cphys, O, 1, 1 if ones else 0, khs, kws, pts, pts, _dt(x))
+    _timed("conv_wgrad", rec(), "hdmoe_conv_wgrad", x, dy, Gs, seg, G, N, H, W, Ho, Wo, I, Cphys, O, 1, 1 if ones else 0, khs, kws, pts, pts, _dt(x))
 
 
 class _MPConvFn(torch.autograd.Function):
@@ -520,8 +508,9 @@ class _MPConvFn(torch.autograd.Function):
                 req.h = hbuf
                 fused_film = True
         if not fused_film:
-            _timed("conv_fwd", _conv_info(x, seg, N, Ho, Wo, O, I, O, khs, kws, Cphys, split), "hdmoe_conv_fwd", x, wf, y, _c(res), alpha, beta,
-                   seg, G, wstride, N, H, W, Ho, Wo, I, Cphys, Ipad, O, O, 1, 1 if ones else 0, khs, kws, pts, pts, dtc)
+            args = (x, wf, y, _c(res), alpha, beta,
+                    seg, G, wstride, N, H, W, Ho, Wo, I, Cphys, Ipad, O, O, 1, 1 if ones else 0, khs, kws, pts, pts, dtc)
+            _timed("conv_fwd", lambda: _fwd_record(*args), "hdmoe_conv_fwd", *args)
         ctx.save_for_backward(x, seg, *tensors)
         ctx.meta = (G, gain_val, alpha, beta, ones, normalize, khs, kws, pts, Ho, Wo, res is not None, split, res_raw)
         return y
@@ -605,8 +594,9 @@ class _MPConvFn(torch.autograd.Function):
             pt_d = [kh - 1 - p for kh, p in zip(khs, pts)]
             pl_d = [kw - 1 - p for kw, p in zip(kws, pts)]
             # dgrad: conv over dy (O channels) with the flipped kernel; logical out channels I, stored Cphys
-            _timed("conv_fwd", _conv_info(dy, seg, N, H, W, I, O, Cphys, khs, kws, O, split), "hdmoe_conv_fwd", dy, wd, dx, None, alpha, 0.0,
-                   seg, G, wdstride, N, Ho, Wo, H, W, O, O, Opad, I, Cphys, 1, 0, khs, kws, pt_d, pl_d, F32S if split else _dt(x))
+            args = (dy, wd, dx, None, alpha, 0.0,
+                    seg, G, wdstride, N, Ho, Wo, H, W, O, O, Opad, I, Cphys, 1, 0, khs, kws, pt_d, pl_d, F32S if split else _dt(x))
+            _timed("conv_fwd", lambda: _fwd_record(*args), "hdmoe_conv_fwd", *args)
         if has_res and nig[1]:
             if res_raw or beta == 1.0:
                 dres = dy                                     # beta == 1, or the producer of `res` applies beta in its own backward pass
@@ -619,8 +609,7 @@ class _MPConvFn(torch.autograd.Function):
             pass
         elif need_w and ctx.ent is not None:
             # bank path: accumulate into the bank's slab; one multi-tensor launch at the end of backward finishes every gradient
-            _wgrad(_conv_info(x, seg, N, Ho, Wo, O, I, O, khs, kws, Cphys), x, dy, ctx.ent.G, seg, G, N, H, W, Ho, Wo, I, Cphys, O, ones, khs, kws, pts, split,
-                   bank=ctx.bank)
+            _wgrad(x, dy, ctx.ent.G, seg, G, N, H, W, Ho, Wo, I, Cphys, O, ones, khs, kws, pts, split, bank=ctx.bank)
             ctx.bank.note_backward(ctx.ent)
         elif need_w:
             sizes = [khs[g] * kws[g] * O * I for g in range(G)]
@@ -629,7 +618,7 @@ class _MPConvFn(torch.autograd.Function):
             for g in range(G):
                 Gs.append(Gflat[off:off + sizes[g]])
                 off += sizes[g]
-            _wgrad(_conv_info(x, seg, N, Ho, Wo, O, I, O, khs, kws, Cphys), x, dy, Gs, seg, G, N, H, W, Ho, Wo, I, Cphys, O, ones, khs, kws, pts, split)
+            _wgrad(x, dy, Gs, seg, G, N, H, W, Ho, Wo, I, Cphys, O, ones, khs, kws, pts, split)
             dws = [torch.empty_like(w) for w in weights]
             if need_gain:
                 dgs = [torch.zeros((), dtype=torch.float32, device=x.device) for _ in range(G)]
@@ -691,14 +680,15 @@ _PRECOMP = None                           # output tensor a fused launch has alr
 F32S = 2                                  # C-ABI dtype code: fp32 tensors, split-bf16 arithmetic (include/hdmoe.h HDMOE_F32S)
 
 
-def _split_ok(x4: Tensor, ws, ones: bool) -> bool:
-    """Domain of the split-bf16 conv kernels (csrc/conv6s.hip); mirrored here because the weight image format depends on it."""
-    if x4.dtype != torch.float32 or ones or x4.ndim != 4:
+def _split_ok(N: int, H: int, W: int, C: int, ws) -> bool:
+    """Does the split-bf16 conv kernel (csrc/conv6s.hip) take the layer -- fp32 (N, H, W, C) input, weights ``ws``?  The library says (the
+    route of an HDMOE_F32S call); asked ahead of the launch because the weight image format depends on the answer."""
+    if any(w.ndim != 4 for w in ws):
         return False
-    _, H, W, C = x4.shape
-    O = ws[0].shape[0]
-    return (all(w.ndim == 4 and w.shape[2] == 3 and w.shape[3] == 3 for w in ws) and C % 32 == 0 and O % 32 == 0
-            and (W == 16 or W % 32 == 0) and H >= 8)
+    O, khs, kws = int(ws[0].shape[0]), [int(w.shape[2]) for w in ws], [int(w.shape[3]) for w in ws]
+    pts = [(k - 1) // 2 for k in kws]
+    return _route("hdmoe_conv_fwd_route", 5, N, H, W, H, W, C, C, (C + 15) // 16 * 16, O, O, 1, 0, len(ws), len(ws) > 1, 0,
+                  max(a * b for a, b in zip(khs, kws)) * O * ((C + 15) // 16 * 16), khs, kws, pts, pts, F32S, 1)[0] == ROUTE_CONV6S
 
 
 def mp_conv(x: Tensor, weights, gain=1.0, *, seg: Optional[Tensor] = None, res: Optional[Tensor] = None, alpha: float = 1.0,
@@ -734,7 +724,7 @@ def mp_conv(x: Tensor, weights, gain=1.0, *, seg: Optional[Tensor] = None, res: 
         x4 = x
     if res is not None:
         res = res.reshape(x4.shape[0], x4.shape[1], x4.shape[2], -1)
-    split = bool(split) and _split_ok(x4, ws, ones)
+    split = bool(split) and not ones and x4.dtype == torch.float32 and _split_ok(*x4.shape, ws)
     # res_grad_raw: the gradient handed back for `res` is dy itself, NOT beta * dy -- only for a `res` whose producer was created with
     # gx_scale = beta (ops.silu_branch / ops.pixel_norm_silu) and has no other consumer: saves a scaling pass per residual block
     meta = (G, gain_val, float(alpha), float(beta), bool(ones), bool(training), bool(normalize), split, bool(res_grad_raw))
@@ -1259,7 +1249,6 @@ BLK6 = True
 # Round 4: on 32 x 32 maps with enough routed rows the whole-image streaming kernel (csrc/conv7.hip) runs the two convs + the FiLM pass in
 # 2 x 27 + 19 us against the fused launch's 97-108 us, so "c32" leaves those blocks to it (same box: 14.00 -> 13.72 ms / step).
 BLK6_SCOPE = "c32"
-C7_MINN = 192                                               # conv7's least number of images (C7_MIN_IMAGES in csrc/conv7.hip)
 
 
 def unet_block_fused(h: Tensor, res: Optional[Tensor], w1s, w2s, gain1: float, gain2: float, emb: Tensor, p: float, training: bool,
@@ -1284,7 +1273,7 @@ def unet_block_fused(h: Tensor, res: Optional[Tensor], w1s, w2s, gain1: float, g
     C = ent1.O
     if ent1.I != Cin or ent2.I != C or ent2.O != C or (seg is None and len(w1s) != 1):
         return None
-    if BLK6_SCOPE == "c32" and (C != 32 or (H == 32 and W == 32 and N >= C7_MINN)):
+    if BLK6_SCOPE == "c32" and (C != 32 or (H == 32 and W == 32 and N >= _c7_min_images())):
         return None
     p = float(p) if training else 0.0
     e32 = _f32(emb)
@@ -2234,7 +2223,7 @@ class _TrunkFn(torch.autograd.Function):
 
 def _trunk_use7(N: int, H: int, W: int, tensors) -> bool:
     """Does _TrunkFn's backward run as plain bf16 layers on the streaming kernels (32 x 32 maps, enough samples, widths % 32)?"""
-    return (TRUNK_BWD_BF16 and H == 32 and W == 32 and N >= C7_MINN
+    return (TRUNK_BWD_BF16 and H == 32 and W == 32 and N >= _c7_min_images()
             and all(int(tensors[3 * l].shape[0]) % 32 == 0 and int(tensors[3 * l].shape[1]) % 32 == 0 for l in range(3)))
 
 
@@ -2247,8 +2236,7 @@ def trunk_ok(x: Tensor, convs) -> bool:
         return False
     c = x.shape[-1]
     for w in convs:
-        probe = torch.empty((1, x.shape[1], x.shape[2], c), dtype=torch.float32, device="meta")
-        if not _split_ok(probe, [w], False) or int(w.shape[1]) != c:
+        if int(w.shape[1]) != c or not _split_ok(*x.shape[:3], c, [w]):
             return False
         c = int(w.shape[0])
         # every layer's GroupNorm backward runs on the 16-byte-vector kernels only (the pooled-gradient form hdmoe_groupnorm_bwd_bcast has no

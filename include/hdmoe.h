@@ -162,26 +162,41 @@ enum {
 };
 int hdmoe_kernel_selections(long long* counts, int n, int reset);
 
-/* Which generic kernel a layer gets (csrc/conv.hip), for tests and tools: the launch plan hdmoe_conv_fwd / hdmoe_conv_wgrad follow when
- * none of the specialised forward kernels (conv6, conv6s, conv7, kgemm, glin) takes the layer -- those are not consulted here.  Nothing is
- * launched.  aligned16 stands for the pointer tests: != 0 = every tensor of the call 16-byte aligned, 0 = 4-byte aligned only.
- * hdmoe_conv_generic_route: route = HOST array of 5 ints {HDMOE_ROUTE_CONV_*, NT (conv_fwd_kernel: NB), VEC, LEPI, NHR}, the template
- * arguments of the instantiation (0 where the kernel has no such parameter).
+/* Which kernel a layer gets: the library is the only place that decides, these queries ask it.  Nothing is launched or counted.
+ * aligned16 stands for the pointer tests: != 0 = every tensor of the call 16-byte aligned, 0 = 4-byte aligned only.  has_seg / has_res:
+ * the call passes a seg array / a residual.
+ * hdmoe_conv_fwd_route: the walk hdmoe_conv_fwd itself makes for the same arguments (dtype HDMOE_F32S included).  route = HOST array of
+ * 5 ints {HDMOE_ROUTE_CONV_*, then the template arguments of the instantiation, 0 in the slots the family does not use}:
+ *   CONV7: CO, KMASK, W16    CONV6: MT, NT    CONV6S: NT    KGEMM: NT    GLIN: NJ    FWD / FWD2 / FWD3 / FWD5: NT (conv_fwd_kernel: NB), VEC, LEPI, NHR
+ * HDMOE_ROUTE_CONV_NONE is an answer, not an error: nothing would run (an HDMOE_F32S layer outside conv6s's domain, which hdmoe_conv_fwd
+ * refuses with HDMOE_EINVAL; an empty batch).
+ * hdmoe_conv_generic_route: the generic tail of that walk alone (conv_fwd_plan), whether or not a specialised kernel would take the layer;
+ * the same 5 ints, always one of FWD / FWD2 / FWD3 / FWD5.
  * hdmoe_conv_wgrad_route: route = HOST array of 34 ints {HDMOE_ROUTE_WGRAD_*, nclasses, then per kernel-size class in launch order
- * (passes, MAXT, OT, VEC)}; nclasses = 0 unless conv_wgrad2_kernel runs.  has_seg: the call passes a seg array. */
+ * (passes, MAXT, OT, VEC)}; nclasses = 0 unless conv_wgrad2_kernel runs. */
 enum {
   HDMOE_ROUTE_CONV_FWD = 0,   /* conv_fwd_kernel<T, NB, VEC> */
   HDMOE_ROUTE_CONV_FWD2 = 1,  /* conv_fwd2_kernel<T, NT, VEC> */
   HDMOE_ROUTE_CONV_FWD3 = 2,  /* conv_fwd3_kernel<T, NT> */
   HDMOE_ROUTE_CONV_FWD5 = 3,  /* conv_fwd5_kernel<T, NT, LEPI, NHR> */
+  HDMOE_ROUTE_CONV_CONV7 = 4, /* conv7_kernel<CO, KMASK, W16, DBG> (csrc/conv7.hip) */
+  HDMOE_ROUTE_CONV_CONV6 = 5, /* conv6_bf16_kernel<MT, NT> (csrc/conv6.hip) */
+  HDMOE_ROUTE_CONV_CONV6S = 6,/* conv6_split_kernel<NT> (csrc/conv6s.hip) */
+  HDMOE_ROUTE_CONV_KGEMM = 7, /* kgemm_kernel<NT> (csrc/kgemm.hip) */
+  HDMOE_ROUTE_CONV_GLIN = 8,  /* glin_f32_kernel<NJ> (csrc/mlinear.hip) */
+  HDMOE_ROUTE_CONV_NONE = 9,  /* no kernel */
   HDMOE_ROUTE_WGRAD_V2 = 0,   /* conv_wgrad2_kernel<T, OT, MAXT, VEC>, one launch per class and pass */
   HDMOE_ROUTE_WGRAD_V1 = 1,   /* conv_wgrad_kernel<T> */
   HDMOE_ROUTE_WGRAD_SWG = 2,  /* swg_f32_kernel (csrc/lwgrad.hip) */
   HDMOE_ROUTE_WGRAD_TOWG = 3, /* towg_bf16_kernel */
   HDMOE_ROUTE_WGRAD_LWG = 4   /* lwg_f32_kernel / lwg_bf16_kernel */
 };
+int hdmoe_conv_fwd_route(int* route, int N, int H, int W, int Ho, int Wo, int Cin, int Cphys, int Ipad, int Cout, int Cstore, int stride, int ones,
+                         int ngroups, int has_seg, int has_res, long wstride, const int* kh, const int* kw, const int* pt, const int* pl,
+                         int dtype, int aligned16);
 int hdmoe_conv_generic_route(int* route, int N, int H, int W, int Ho, int Wo, int Cin, int Cphys, int Ipad, int Cout, int Cstore, int stride,
                              int ones, int ngroups, const int* kh, const int* kw, int dtype, int aligned16);
+int hdmoe_conv7_min_images(void);   /* least number of images of a layer that conv7 (and the fused backward on it) takes */
 int hdmoe_conv_wgrad_route(int* route, int N, int H, int W, int Ho, int Wo, int Cin, int Cphys, int Cout, int stride, int ones, int ngroups,
                            int has_seg, const int* kh, const int* kw, const int* pt, const int* pl, int dtype, int aligned16);
 

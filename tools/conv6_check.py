@@ -164,9 +164,8 @@ def time_wgrad(N, R, Cin, Cout, ks, iters=10):
     seg = torch.tensor([N * i // E for i in range(E + 1)], dtype=torch.int32, device=dev)
     Gs = [torch.zeros(k * k, Cout, Cin, device=dev) for k in ks]
     pts = [(k - 1) // 2 for k in ks]
-    info = dict()
     def run():
-        ops._wgrad(info, x, dy, Gs, seg, E, N, R, R, R, R, Cin, Cin, Cout, False, list(ks), list(ks), pts)
+        ops._wgrad(x, dy, Gs, seg, E, N, R, R, R, R, Cin, Cin, Cout, False, list(ks), list(ks), pts)
     for _ in range(3):
         run()
     torch.cuda.synchronize()

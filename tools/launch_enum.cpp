@@ -6,7 +6,7 @@
 // output line per launch with the call number, the kernel's demangled name, grid, block, dynamic LDS and a hash of the kernarg bytes
 // (padding and fields the host code leaves unset are masked).  Pointers are made-up addresses; nothing is dereferenced.  Two builds of
 // the library dispatch alike exactly when their outputs are equal (diff).  Where the library exports the route queries
-// (hdmoe_conv_generic_route, hdmoe_conv_wgrad_route) every generic launch is checked against them; the summary goes to stderr.
+// (hdmoe_conv_fwd_route, hdmoe_conv_wgrad_route) every forward and weight-gradient launch is checked against them; the summary goes to stderr.
 #include <cxxabi.h>
 #include <dlfcn.h>
 #include <hip/hip_runtime_api.h>
@@ -119,7 +119,8 @@ using FwdFn = int (*)(const void*, const void*, void*, const void*, float, float
 using WgradFn = int (*)(const void*, const void*, float* const*, const int*, int, int, int, int, int, int, int, int, int, int, int, const int*,
                         const int*, const int*, const int*, int, hipStream_t);
 using PwFn = int (*)(const void*, const void*, const void*, void*, float* const*, const int*, int, long, int, long, int, int, float, int, hipStream_t);
-using FwdRouteFn = int (*)(int*, int, int, int, int, int, int, int, int, int, int, int, int, int, const int*, const int*, int, int);
+using FwdRouteFn = int (*)(int*, int, int, int, int, int, int, int, int, int, int, int, int, int, int, int, long, const int*, const int*, const int*, const int*,
+                           int, int);
 using WgRouteFn = int (*)(int*, int, int, int, int, int, int, int, int, int, int, int, int, const int*, const int*, const int*, const int*, int, int);
 
 FwdFn conv_fwd; WgradFn conv_wgrad; PwFn pw_bwd; FwdRouteFn fwd_route; WgRouteFn wg_route;
@@ -157,15 +158,29 @@ void run_fwd(int dtype, int stride, int ones, const Groups& g, int N, int H, int
   const int rc = conv_fwd(x, w, y, res, 0.5f, res ? 0.25f : 0.f, seg, g.n, wstride, N, H, W, Ho, Wo, Cin, Cphys, Ipad, Cout, Cstore, stride, ones, g.kh,
                           g.kw, pt, pl, dtype, nullptr);
   printf("%ld fwd rc %d\n", g_call_no, rc);
-  if (!fwd_route || g_call.empty() || g_call[0].rfind("conv_fwd", 0) != 0 || (align != 0 && align != 4)) return;
+  if (!fwd_route || (align != 0 && align != 4)) return;
   int r[5];
-  if (fwd_route(r, N, H, W, Ho, Wo, Cin, Cphys, Ipad, Cout, Cstore, stride, ones, g.n, g.kh, g.kw, dtype, 1) != 0) { ++g_route_bad; return; }
-  char buf[128];
-  if (r[0] == 0) snprintf(buf, sizeof buf, "conv_fwd_kernel<%s, %d, %s>", tname(dtype), r[1], bname(r[2]));
-  else if (r[0] == 1) snprintf(buf, sizeof buf, "conv_fwd2_kernel<%s, %d, %s>", tname(dtype), r[1], bname(r[2]));
-  else if (r[0] == 2) snprintf(buf, sizeof buf, "conv_fwd3_kernel<%s, %d>", tname(dtype), r[1]);
-  else snprintf(buf, sizeof buf, "conv_fwd5_kernel<%s, %d, %s, %d>", tname(dtype), r[1], bname(r[3]), r[4]);
-  check(buf);
+  const int rq = fwd_route(r, N, H, W, Ho, Wo, Cin, Cphys, Ipad, Cout, Cstore, stride, ones, g.n, seg != nullptr, res != nullptr, wstride, g.kh, g.kw, pt,
+                           pl, dtype, 1);
+  if (rc < 0 || rq != 0) {                                  // a refused call: the query refuses it too, or answers "none" (route 9)
+    ++g_route_checked;
+    if (rc >= 0 || (rq == 0 && r[0] != 9)) { ++g_route_bad; fprintf(stderr, "call %ld: rc %d, route query %d\n", g_call_no, rc, rq); }
+    return;
+  }
+  char buf[128] = "";
+  switch (r[0]) {                                           // HDMOE_ROUTE_CONV_*
+    case 0: snprintf(buf, sizeof buf, "conv_fwd_kernel<%s, %d, %s>", tname(dtype), r[1], bname(r[2])); break;
+    case 1: snprintf(buf, sizeof buf, "conv_fwd2_kernel<%s, %d, %s>", tname(dtype), r[1], bname(r[2])); break;
+    case 2: snprintf(buf, sizeof buf, "conv_fwd3_kernel<%s, %d>", tname(dtype), r[1]); break;
+    case 3: snprintf(buf, sizeof buf, "conv_fwd5_kernel<%s, %d, %s, %d>", tname(dtype), r[1], bname(r[3]), r[4]); break;
+    case 4: snprintf(buf, sizeof buf, "conv7_kernel<%d, %d, %s, false>", r[1], r[2], bname(r[3])); break;
+    case 5: snprintf(buf, sizeof buf, "conv6_bf16_kernel<%d, %d, false>", r[1], r[2]); break;
+    case 6: snprintf(buf, sizeof buf, "conv6_split_kernel<%d>", r[1]); break;
+    case 7: snprintf(buf, sizeof buf, "kgemm_kernel<%d>", r[1]); break;
+    case 8: snprintf(buf, sizeof buf, "glin_f32_kernel<%d>", r[1]); break;
+  }
+  if ((r[0] == 9) != g_call.empty()) { ++g_route_checked; ++g_route_bad; fprintf(stderr, "call %ld: route %d, %zu launches\n", g_call_no, r[0], g_call.size()); return; }
+  check(buf);                                               // (route 9 = none: nothing launched, nothing to compare)
 }
 
 void run_wgrad(int dtype, int stride, int ones, const Groups& g, int N, int H, int W, int Cphys, int Cout, int align) {
@@ -208,7 +223,7 @@ int main(int argc, char** argv) {
   void* lib = dlopen(argv[1], RTLD_NOW | RTLD_GLOBAL);
   if (!lib) { fprintf(stderr, "%s\n", dlerror()); return 2; }
   conv_fwd = (FwdFn)dlsym(lib, "hdmoe_conv_fwd"); conv_wgrad = (WgradFn)dlsym(lib, "hdmoe_conv_wgrad"); pw_bwd = (PwFn)dlsym(lib, "hdmoe_pw_bwd");
-  fwd_route = (FwdRouteFn)dlsym(lib, "hdmoe_conv_generic_route"); wg_route = (WgRouteFn)dlsym(lib, "hdmoe_conv_wgrad_route");
+  fwd_route = (FwdRouteFn)dlsym(lib, "hdmoe_conv_fwd_route"); wg_route = (WgRouteFn)dlsym(lib, "hdmoe_conv_wgrad_route");
   if (!conv_fwd || !conv_wgrad || !pw_bwd) { fprintf(stderr, "entry points missing\n"); return 2; }
   const int cins[] = {3, 6, 8, 32, 48, 64, 96}, couts[] = {1, 4, 6, 8, 32, 48, 64, 72, 128};
   for (int dtype = 0; dtype < 2; ++dtype)
@@ -240,6 +255,8 @@ int main(int argc, char** argv) {
           }
   run_fwd(1, 1, 0, kGroups[5], 2, 8, 64, 8, 36, 36, 0);          // conv_fwd5<bf16, 2, false, 9>: 7x7 block tiles, Cstore % 8 != 0
   for (int cin : {32, 64}) for (int cout : {32, 64}) run_fwd(2, 1, 0, kGroups[2], 2, 32, 32, cin, cout, cout, 0);
+  for (int n : {191, 192}) for (int hw : {16, 32}) for (int cout : {32, 64}) for (const Groups& g : {kGroups[8], kGroups[12]})   // conv7 and just below it
+    run_fwd(1, 1, 0, g, n, hw, hw, 32, cout, cout, 0);
   run_fwd(7, 1, 0, kGroups[2], 2, 8, 8, 8, 8, 8, 0);
   run_fwd(0, 1, 0, kGroups[2], 2, 8, 8, 8, 8, 16, 0);            // Cstore > Cout
   run_fwd(0, 0, 0, kGroups[2], 2, 8, 8, 8, 8, 8, 0);             // stride 0
