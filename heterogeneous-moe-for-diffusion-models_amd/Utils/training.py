@@ -3,7 +3,8 @@
 Mirrors reference ``Utils/training.py``: optimizer groups (:55-60), cosine schedule (:62-65), the per-iteration order
 forward -> loss -> zero_grad -> backward -> clip_grad_norm_(1.0) -> step -> scheduler.step (:125-197) and the checkpoint
 dictionary (:242-271, read back at :303-304).  What the reference takes from the network (Flowers102, the SD VAE, CLIP;
-``Utils/VAE_CLIP.py``) is outside this path: `train_steps` is fed latents and text embeddings by the caller.
+``Utils/VAE_CLIP.py``) is outside this path: `train_steps` is fed latents and text embeddings by the caller, or the trainer draws them
+itself from a device-resident `Utils.utils.LatentDataset` of pre-encoded latents and text rows.
 
 Differences that are deliberate and visible:
   * gradient clipping + AdamW run as two multi-tensor HIP launches with no host sync (hdmoe_hip/optim.py);
@@ -14,13 +15,13 @@ Differences that are deliberate and visible:
 from __future__ import annotations
 
 import os
-from typing import Any, Callable, Dict, Iterable, Optional
+from typing import Any, Callable, Dict, Iterable, Optional, Union
 
 import torch
 
 from hdmoe_hip.dp import GradBuckets
 from hdmoe_hip.optim import FusedAdamW
-from .utils import EDM_LOSS, DeviceInputs, MaskGenerator, ZetaScheduler, null_text, sample_sigma_hybrid
+from .utils import EDM_LOSS, DeviceInputs, LatentDataset, MaskGenerator, ZetaScheduler, null_text, sample_sigma_hybrid
 
 
 def build_optimizer(model: torch.nn.Module, optim_config: Dict[str, Any]) -> FusedAdamW:
@@ -105,12 +106,36 @@ class Trainer:
     replaced with probability p by ``null_text_emb`` (one text row; None: zeros), and the result gains ``"text_keep"`` (B,) float32 0/1.
     With device inputs the decision is keyed by ``(seed, rank, step_idx)`` like every other input and made inside the one pass that
     copies the text into its static buffer (`DeviceInputs.drop_text`); otherwise it is drawn from torch's generator.  At 0 nothing is
-    launched or drawn and the result has no new key."""
+    launched or drawn and the result has no new key.
+
+    ``dataset=LatentDataset(...), batch_size=B`` (implies ``device_inputs``): the trainer draws its own batches.  ``train_step()`` then
+    takes no arguments; the items of step k (a keyed epoch permutation, ``drop_last``, disjoint across the ranks of
+    ``torch.distributed``), their VAE-posterior draw, horizontal flip and text rows are a function of ``(seed, world, rank, step_idx)``
+    made inside the same fused input calls, and the result gains ``"item"`` (B,) int32 and ``"flip"`` (B,) float32 0/1.  Under
+    ``graphed=True`` the captured step reads the generator's own buffers: no batch is copied.  Resuming at step k sees step k's data
+    again.  With ``dataset=None`` every path is what it was."""
 
     def __init__(self, model, model_config, optim_config, loss_config, mask_config, zeta_config, max_grad_norm: float = 1.0,
                  fuse_clip_into_step: bool = True, logger=None, ema=None, ema_snapshot_every: Optional[int] = None,
                  ema_snapshot_dir: Optional[str] = None, device_inputs: bool = False, graphed: bool = False, seed: Optional[int] = None,
-                 cond_dropout: float = 0.0, null_text_emb: Optional[torch.Tensor] = None):
+                 cond_dropout: float = 0.0, null_text_emb: Optional[torch.Tensor] = None, dataset: Optional[LatentDataset] = None,
+                 batch_size: Optional[int] = None):
+        dist = torch.distributed.is_available() and torch.distributed.is_initialized()
+        self.world, self.rank = (torch.distributed.get_world_size(), torch.distributed.get_rank()) if dist else (1, 0)
+        if dataset is None:
+            if batch_size is not None:
+                raise ValueError("Trainer: batch_size is the dataset's batch size; without a dataset the caller's batches fix it")
+        else:
+            if not isinstance(dataset, LatentDataset):
+                raise ValueError(f"Trainer: dataset is a Utils.utils.LatentDataset, got {type(dataset).__name__}")
+            if dataset.text is None:
+                raise ValueError("Trainer: the dataset needs text rows (LatentDataset(text=...)): the model is text-conditioned")
+            if batch_size is None or int(batch_size) < 1:
+                raise ValueError(f"Trainer: a dataset needs batch_size >= 1, got {batch_size}")
+            if dataset.N < int(batch_size) * self.world:
+                raise ValueError(f"Trainer: the dataset's N={dataset.N} items do not fill one step of batch_size * world = "
+                                 f"{int(batch_size)} * {self.world}")
+        self.dataset, self.batch_size = dataset, None if batch_size is None else int(batch_size)
         if ema_snapshot_every is not None:
             if ema is None:
                 raise ValueError("Trainer: ema_snapshot_every needs an ema")
@@ -147,16 +172,15 @@ class Trainer:
         self._clip_params = [p for p in model.parameters()]
         self.step_idx = 0
         self.graphed = bool(graphed)
-        self.device_inputs = bool(device_inputs) or self.graphed
+        self.device_inputs = bool(device_inputs) or self.graphed or dataset is not None
         self.inputs = None
         if self.device_inputs:
             if seed is None:
                 from hdmoe_hip import ops
                 seed = ops.next_seed()
-            rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
             self.seed = int(seed)
             self.inputs = DeviceInputs(model_config, mask_config, zeta_config, self.unet_mask_gen, self.vit_mask_gen, self.zeta_sched,
-                                       seed=self.seed, rank=rank, cond_dropout=self.cond_dropout, null_text_emb=null_text_emb)
+                                       seed=self.seed, rank=self.rank, cond_dropout=self.cond_dropout, null_text_emb=null_text_emb)
         # model_config2 takes the soft-gate transition from the mask config; model_config1 learns its scaling and has no such arguments
         import inspect
         names = inspect.signature(model.forward).parameters
@@ -171,7 +195,6 @@ class Trainer:
 
     def _build_staged(self, latent_images: torch.Tensor, text_emb: torch.Tensor) -> None:
         """Fix the shapes, fill the static buffers for `step_idx` and capture the staged step (bench.py's replay path)."""
-        from hdmoe_hip import graph as hgraph
         if not latent_images.is_cuda:
             raise RuntimeError("hdmoe_hip: tensors must live on the GPU (no CPU fallback in the product path)")
         dev = latent_images.device
@@ -182,11 +205,29 @@ class Trainer:
         else:
             self._text = text_emb.detach().contiguous().clone()
         self._shapes = (tuple(latent_images.shape), tuple(text_emb.shape))
-        b = self.inputs.generate(self._lat, self.step_idx)
+        self._capture(self.inputs.generate(self._lat, self.step_idx), self._lat, dev)
+
+    def _data(self, text_out: Optional[torch.Tensor] = None):
+        """The dataset's batch of `step_idx` in the generator's static buffers: (buffers, text, keep)."""
+        b = self.inputs.generate_from(self.dataset, self.step_idx, self.batch_size, world=self.world, rank=self.rank)
+        text, keep = self.inputs.text_from(self.dataset, self.step_idx, out=text_out)
+        return b, text, keep if self.cond_dropout > 0 else None
+
+    def _build_staged_dataset(self) -> None:
+        """`_build_staged` over the generator's own buffers: x0 and x are written where the captured step reads them, the text rows are
+        gathered into the static text buffer, nothing is copied."""
+        row = tuple(self.dataset.text.shape[1:])
+        self._text = torch.empty((self.batch_size,) + row, dtype=self.dataset.text.dtype, device=self.dataset.device)
+        b, _, _ = self._data(self._text)
+        self._lat = b["x0"]
+        self._capture(b, b["x0"], self.dataset.device)
+
+    def _capture(self, b: dict, x0: torch.Tensor, dev) -> None:
+        from hdmoe_hip import graph as hgraph
 
         def fwd_bwd():
             self.buckets.zero_grad()
-            out_model, loss = self._fwd_loss(b["x"], self._lat, b["sigma"], self._text, b["unet_mask"], b["vit_mask"], b["zeta"])
+            out_model, loss = self._fwd_loss(b["x"], x0, b["sigma"], self._text, b["unet_mask"], b["vit_mask"], b["zeta"])
             hgraph.backward(loss["loss"])
             return {"loss": loss, "out_model": out_model}
 
@@ -205,7 +246,14 @@ class Trainer:
                 seen.add(id(lst))
                 u.zero_()
 
-    def _graphed_fwd_bwd(self, latent_images: torch.Tensor, text_emb: torch.Tensor):
+    def _graphed_fwd_bwd(self, latent_images: Optional[torch.Tensor], text_emb: Optional[torch.Tensor]):
+        if self.dataset is not None:
+            if self._staged is None:
+                self._build_staged_dataset()
+            b, _, keep = self._data(self._text)
+            res = self._staged()
+            self.buckets.finish()
+            return res["out_model"], res["loss"], b["sigma"], keep
         if self._staged is None:
             self._build_staged(latent_images, text_emb)
         elif (tuple(latent_images.shape), tuple(text_emb.shape)) != self._shapes:
@@ -222,9 +270,14 @@ class Trainer:
         self.buckets.finish()
         return res["out_model"], res["loss"], b["sigma"], keep
 
-    def train_step(self, latent_images: torch.Tensor, text_emb: torch.Tensor) -> dict:
-        """One iteration on (latents (B,C,H,W), text embeddings).  Returns {"loss", "out_model", "sigma"}, and "text_keep" when
-        ``cond_dropout`` > 0; with ``graphed=True`` their tensors are the captured step's static buffers, valid until the next call."""
+    def train_step(self, latent_images: Optional[torch.Tensor] = None, text_emb: Optional[torch.Tensor] = None) -> dict:
+        """One iteration on (latents (B,C,H,W), text embeddings), or with a dataset on the batch the trainer draws for `step_idx` (no
+        arguments).  Returns {"loss", "out_model", "sigma"}, "text_keep" when ``cond_dropout`` > 0 and "item" / "flip" with a dataset;
+        with ``graphed=True`` their tensors are the captured step's static buffers, valid until the next call."""
+        if self.dataset is not None and (latent_images is not None or text_emb is not None):
+            raise ValueError("Trainer: with a dataset train_step() takes no batch; the trainer draws it")
+        if self.dataset is None and (latent_images is None or text_emb is None):
+            raise ValueError("Trainer: train_step(latents, text_emb) needs a batch (or build the Trainer with dataset=...)")
         if self.device_inputs:
             return self._train_step_device(latent_images, text_emb)
         cfg, mc, step = self.cfg, self.mask_cfg, self.step_idx
@@ -246,18 +299,22 @@ class Trainer:
         self.buckets.finish()
         return self._update(step, loss, out_model, sigma, keep)
 
-    def _train_step_device(self, latent_images: torch.Tensor, text_emb: torch.Tensor) -> dict:
+    def _train_step_device(self, latent_images: Optional[torch.Tensor], text_emb: Optional[torch.Tensor]) -> dict:
         step = self.step_idx
         keep = None
         if self.graphed:
             out_model, loss, sigma, keep = self._graphed_fwd_bwd(latent_images, text_emb)
             self._log_forward(step, loss, out_model, sigma)
         else:
-            if latent_images.dtype != torch.float32 or not latent_images.is_contiguous():
-                latent_images = latent_images.to(torch.float32).contiguous()
-            if self.cond_dropout > 0:
-                text_emb, keep = self.inputs.drop_text(text_emb, step)
-            b = self.inputs.generate(latent_images, step)
+            if self.dataset is not None:
+                b, text_emb, keep = self._data()
+                latent_images = b["x0"]
+            else:
+                if latent_images.dtype != torch.float32 or not latent_images.is_contiguous():
+                    latent_images = latent_images.to(torch.float32).contiguous()
+                if self.cond_dropout > 0:
+                    text_emb, keep = self.inputs.drop_text(text_emb, step)
+                b = self.inputs.generate(latent_images, step)
             sigma = b["sigma"]
             out_model, loss = self._fwd_loss(b["x"], latent_images, sigma, text_emb, b["unet_mask"], b["vit_mask"], b["zeta"])
             self._log_forward(step, loss, out_model, sigma)
@@ -298,6 +355,8 @@ class Trainer:
         res = {"loss": loss, "out_model": out_model, "sigma": sigma}
         if keep is not None:
             res["text_keep"] = keep
+        if self.dataset is not None:
+            res["item"], res["flip"] = self.inputs.data_buf["item"], self.inputs.data_buf["flip"]
         return res
 
     def _save_ema_snapshot(self, step: int) -> None:
@@ -308,9 +367,14 @@ class Trainer:
         self.ema.save_snapshot(os.path.join(self.ema_snapshot_dir, f"ema_{step:08d}.pt"))
 
 
-def train_steps(trainer: Trainer, batches: Iterable, on_step: Optional[Callable[[int, dict], None]] = None) -> None:
-    """Drive `trainer` over (latents, text_emb) batches; `on_step(step, result)` is where logging / checkpoints hook in."""
+def train_steps(trainer: Trainer, batches: Union[Iterable, int], on_step: Optional[Callable[[int, dict], None]] = None) -> None:
+    """Drive `trainer` over (latents, text_emb) batches, or -- a trainer with a dataset -- over `batches` steps of its own data;
+    `on_step(step, result)` is where logging / checkpoints hook in."""
     trainer.model.train()
+    if isinstance(batches, int):
+        if trainer.dataset is None:
+            raise ValueError("train_steps: a number of steps needs a Trainer with a dataset")
+        batches = ((None, None) for _ in range(batches))
     for latents, text in batches:
         res = trainer.train_step(latents, text)
         if on_step is not None:

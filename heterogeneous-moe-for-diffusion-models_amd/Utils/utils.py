@@ -6,6 +6,9 @@ produce a few (B,)/(B,E) values per step from torch's RNG before the timed path 
 torch device ops (data generation, not the denoiser's arithmetic).  ``DeviceInputs`` is their fused form: one HIP call per step
 writes sigma, the noised latents, both masks and zeta into static buffers, keyed by (seed, rank, step) instead of a generator; its
 ``drop_text`` is the conditioning dropout that trains the unconditional branch of classifier-free guidance, under the same key.
+``LatentDataset`` keeps the pre-encoded latents (and text rows) on the device; ``DeviceInputs.generate_from`` / ``text_from`` then make
+the data of a step in the same fused calls -- epoch order, VAE-posterior draw, horizontal flip, text gather -- keyed by
+(seed, world, rank, step), with no host loader.
 """
 from __future__ import annotations
 
@@ -109,6 +112,65 @@ class MaskGenerator(nn.Module):
         raise ValueError(f"Unknown bandwidth strategy: {self.strat_band}")
 
 
+class LatentDataset:
+    """Pre-encoded latents, resident on the GPU, that `DeviceInputs.generate_from` / `Trainer(dataset=...)` draw their batches from
+    (the reference's Flowers102 -> VAE -> DataLoader(shuffle=True, drop_last=True) chain, Utils/training.py:226-239, VAE_CLIP.py:58-66).
+
+    ``mean`` (N,C,H,W) float32 or bfloat16 and optionally ``std`` of the same shape and dtype: a step's latent is
+    ``scale * (mean + std * eps)`` with a fresh keyed draw per step (``std=None``: ``scale * mean``), mirrored along W with probability
+    ``flip``.  ``text`` (K, ...) holds the text rows: K == 1 one prompt for every item, K == N one row per item, any K with
+    ``text_index`` (N,) int32 naming each item's row.  ``text_index`` is range-checked here, once (one host sync): the kernels follow
+    it unchecked.  Tensors are moved to ``device`` (default: the current GPU) unless they already live on a GPU; ValueError names the
+    argument of every violated condition before any device work."""
+
+    def __init__(self, mean: torch.Tensor, std: Optional[torch.Tensor] = None, *, scale: float = 1.0, flip: float = 0.0,
+                 text: Optional[torch.Tensor] = None, text_index: Optional[torch.Tensor] = None, device=None):
+        if not torch.is_tensor(mean) or mean.ndim != 4 or mean.shape[0] < 1 or mean.numel() == 0:
+            raise ValueError(f"LatentDataset: mean is a (N, C, H, W) tensor with N >= 1, got {tuple(mean.shape) if torch.is_tensor(mean) else type(mean).__name__}")
+        if mean.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"LatentDataset: mean must be float32 or bfloat16, got {mean.dtype}")
+        N = mean.shape[0]
+        if N >= 1 << 31:
+            raise ValueError(f"LatentDataset: mean holds N={N} items, the keyed order needs N < 2^31")
+        if std is not None and (not torch.is_tensor(std) or tuple(std.shape) != tuple(mean.shape) or std.dtype != mean.dtype):
+            got = (tuple(std.shape), std.dtype) if torch.is_tensor(std) else type(std).__name__
+            raise ValueError(f"LatentDataset: std must have mean's shape {tuple(mean.shape)} and dtype {mean.dtype}, got {got}")
+        scale, flip = float(scale), float(flip)
+        if not math.isfinite(scale):
+            raise ValueError(f"LatentDataset: scale must be finite, got {scale}")
+        if not 0.0 <= flip <= 1.0:
+            raise ValueError(f"LatentDataset: flip is a probability in [0, 1], got {flip}")
+        if text is None and text_index is not None:
+            raise ValueError("LatentDataset: text_index without text")
+        if text is not None:
+            if not torch.is_tensor(text) or text.ndim < 2 or text.shape[0] < 1 or text.numel() == 0:
+                raise ValueError("LatentDataset: text is a (K, ...) tensor with K >= 1 and a non-empty row")
+            if text.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+                raise ValueError(f"LatentDataset: text must be float32, bfloat16 or float16, got {text.dtype}")
+            if text_index is None and text.shape[0] not in (1, N):
+                raise ValueError(f"LatentDataset: text has K={text.shape[0]} rows for N={N} items: K must be 1 or N, or give a text_index")
+        if text_index is not None:
+            if not torch.is_tensor(text_index) or tuple(text_index.shape) != (N,) or text_index.dtype != torch.int32:
+                raise ValueError(f"LatentDataset: text_index is a (N,) = ({N},) int32 tensor")
+        tensors = [t for t in (mean, std, text, text_index) if t is not None]
+        if device is None:
+            on = [t.device for t in tensors if t.is_cuda]
+            device = on[0] if on else torch.device("cuda", torch.cuda.current_device())
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("hdmoe_hip: tensors must live on the GPU (no CPU fallback in the product path)")
+        put = lambda t: None if t is None else t.detach().to(device).contiguous()
+        self.mean, self.std, self.text, self.text_index = put(mean), put(std), put(text), put(text_index)
+        self.scale, self.flip, self.N, self.device = scale, flip, N, device
+        if self.text_index is not None:                        # the one sync: the only thing between a bad index and a device fault
+            lo, hi = int(self.text_index.min()), int(self.text_index.max())
+            if lo < 0 or hi >= self.text.shape[0]:
+                raise ValueError(f"LatentDataset: text_index holds values in [{lo}, {hi}], text has rows 0 .. {self.text.shape[0] - 1}")
+
+    def __len__(self) -> int:
+        return self.N
+
+
 class DeviceInputs:
     """The per-step training inputs from one fused HIP call (csrc/traingen.hip; RNG contract in include/hdmoe.h) instead of
     ``sample_sigma_hybrid`` + ``randn_like`` + two ``MaskGenerator`` calls on torch's generator.
@@ -129,6 +191,7 @@ class DeviceInputs:
         self.unet_mask_gen, self.vit_mask_gen, self.zeta_sched = unet_mask_gen, vit_mask_gen, zeta_sched
         if unet_mask_gen.expert_centers.numel() != vit_mask_gen.expert_centers.numel() or unet_mask_gen.min_active != vit_mask_gen.min_active:
             raise ValueError("DeviceInputs: both mask generators need the same number of experts and the same min_active")
+        self.data_seed = int(seed) & 0xFFFFFFFFFFFFFFFF        # rank-free: every rank walks the same epoch permutation (generate_from)
         self.seed = (int(seed) + int(rank) * self.GOLDEN) & 0xFFFFFFFFFFFFFFFF
         self.extreme_prob = float(extreme_prob)
         self.cond_dropout = float(cond_dropout)
@@ -141,16 +204,17 @@ class DeviceInputs:
         self.buf = None
         self.keep = self.text = self._null = None             # drop_text's static buffers and the null row as the kernel reads it
         self._text_like = None
+        self.data_buf = None                                  # generate_from's dictionary: buf plus "x0", "item", "flip"
 
-    def _alloc(self, latents: torch.Tensor) -> None:
-        dev, B = latents.device, latents.shape[0]
+    def _alloc(self, shape, dev) -> None:
+        B = shape[0]
         self._ucen = self.unet_mask_gen.expert_centers.detach().to(device=dev, dtype=torch.float32).contiguous()
         self._vcen = self.vit_mask_gen.expert_centers.detach().to(device=dev, dtype=torch.float32).contiguous()
         E = self._ucen.numel()
         f32 = dict(dtype=torch.float32, device=dev)
-        self.buf = {"sigma": torch.zeros(B, 1, 1, 1, **f32), "x": torch.zeros(latents.shape, **f32), "unet_mask": torch.zeros(B, E, **f32),
+        self.buf = {"sigma": torch.zeros(B, 1, 1, 1, **f32), "x": torch.zeros(shape, **f32), "unet_mask": torch.zeros(B, E, **f32),
                     "vit_mask": torch.zeros(B, E, **f32), "zeta": torch.zeros(1, **f32), "src": torch.zeros(B, dtype=torch.int32, device=dev)}
-        self.shape = tuple(latents.shape)
+        self.shape = tuple(shape)
 
     def generate(self, latents: torch.Tensor, step: int) -> dict:
         """{"sigma", "x", "unet_mask", "vit_mask", "zeta", "src"}: the static buffers, holding step `step`'s inputs for `latents`
@@ -162,7 +226,7 @@ class DeviceInputs:
         if self.buf is None:
             if not latents.is_cuda:
                 raise RuntimeError("hdmoe_hip: tensors must live on the GPU (no CPU fallback in the product path)")
-            self._alloc(latents)
+            self._alloc(tuple(latents.shape), latents.device)
         b, mc = self.buf, self.mask_cfg
         ops.train_inputs(b["x"], b["sigma"], b["unet_mask"], b["vit_mask"], b["zeta"], b["src"], latents, self._ucen, self._vcen, self.seed,
                          int(step), sigma_min=self.cfg["sigma_min"], sigma_max=self.cfg["sigma_max"], p_mean=mc["p_mean"], p_std=mc["p_std"],
@@ -170,6 +234,59 @@ class DeviceInputs:
                          vit_bw=self.vit_mask_gen.bandwidth_scheduler(step), min_active=self.unet_mask_gen.min_active,
                          zeta=self.zeta_sched.get_zeta(step=step))
         return b
+
+    def generate_from(self, dataset: "LatentDataset", step: int, batch_size: int, world: int = 1, rank: int = 0) -> dict:
+        """`generate`'s dictionary plus {"x0", "item", "flip"}, all static buffers: step `step`'s batch of `batch_size` items drawn from
+        `dataset` for `rank` of `world` (item (B,) int32 dataset rows, flip (B,) float32 0/1, x0 the clean latents, x the noised ones),
+        in the same two launches, until the next call.  The items follow the rank-free seed, everything else (seed, rank, step)."""
+        if not isinstance(dataset, LatentDataset):
+            raise ValueError(f"DeviceInputs: dataset is a LatentDataset, got {type(dataset).__name__}")
+        B, world, rank = int(batch_size), int(world), int(rank)
+        if B < 1 or world < 1 or not 0 <= rank < world:
+            raise ValueError(f"DeviceInputs: batch_size >= 1, world >= 1 and rank in [0, world), got {batch_size}, {world}, {rank}")
+        if dataset.N < B * world:
+            raise ValueError(f"DeviceInputs: the dataset's N={dataset.N} items do not fill one step of batch_size * world = {B} * {world}")
+        shape = (B,) + tuple(dataset.mean.shape[1:])
+        if self.shape is not None and shape != self.shape:
+            raise ValueError(f"DeviceInputs: batch {shape} differs from the static buffers' {self.shape}")
+        if self.buf is None:
+            self._alloc(shape, dataset.device)
+        if self.data_buf is None:
+            dev = dataset.device
+            self.data_buf = dict(self.buf, x0=torch.zeros(shape, dtype=torch.float32, device=dev),
+                                 item=torch.zeros(B, dtype=torch.int32, device=dev), flip=torch.zeros(B, dtype=torch.float32, device=dev))
+        b, mc = self.data_buf, self.mask_cfg
+        ops.dataset_inputs(b["x"], b["x0"], b["sigma"], b["unet_mask"], b["vit_mask"], b["zeta"], b["src"], b["item"], b["flip"], dataset.mean,
+                           dataset.std, self._ucen, self._vcen, self.seed, self.data_seed, int(step), world=world, rank=rank, scale=dataset.scale,
+                           p_flip=dataset.flip, sigma_min=self.cfg["sigma_min"], sigma_max=self.cfg["sigma_max"], p_mean=mc["p_mean"],
+                           p_std=mc["p_std"], extreme_prob=self.extreme_prob, unet_bw=self.unet_mask_gen.bandwidth_scheduler(step),
+                           vit_bw=self.vit_mask_gen.bandwidth_scheduler(step), min_active=self.unet_mask_gen.min_active,
+                           zeta=self.zeta_sched.get_zeta(step=step))
+        return b
+
+    def text_from(self, dataset: "LatentDataset", step: int, out: Optional[torch.Tensor] = None):
+        """(text_out, keep) of step `step`: the text rows of the items the last `generate_from` wrote (call it first, for the same step),
+        with `drop_text`'s substitution under the same key folded into the gather; ``cond_dropout`` 0 is a pure gather and keep all ones.
+        Static buffers like `drop_text`'s, `out` likewise."""
+        if not isinstance(dataset, LatentDataset) or dataset.text is None:
+            raise ValueError("DeviceInputs: text_from needs a LatentDataset with text")
+        if self.data_buf is None:
+            raise ValueError("DeviceInputs: text_from reads the items of generate_from: call that first")
+        item = self.data_buf["item"]
+        like = ((item.shape[0],) + tuple(dataset.text.shape[1:]), dataset.text.dtype)
+        if self._text_like is None:
+            self._null = _null_row(self.null_text_emb, dataset.text)
+            self.keep = torch.zeros(item.shape[0], dtype=torch.float32, device=item.device)
+            self._text_like = like
+        elif like != self._text_like:
+            raise ValueError(f"DeviceInputs: text {like} differs from the static buffers' {self._text_like}")
+        if out is None:
+            if self.text is None:
+                self.text = torch.empty(like[0], dtype=like[1], device=item.device)
+            out = self.text
+        ops.text_gather_dropout(out, self.keep, dataset.text, dataset.text_index, item, self._null, self.seed, int(step), self.cond_dropout,
+                                dataset.N)
+        return out, self.keep
 
     def drop_text(self, text: torch.Tensor, step: int, out: Optional[torch.Tensor] = None):
         """(text_out, keep) of step `step`: keep (B,) float32 0/1 under the key (seed, rank, step), text_out[i] = text[i] where

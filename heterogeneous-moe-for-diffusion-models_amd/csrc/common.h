@@ -25,6 +25,7 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 #define DEVI __device__ __forceinline__
+#define HDI __host__ __device__ __forceinline__      /* the few helpers a host entry point shares with the kernels (philox, keyed_perm.h) */
 
 // ---- transposing LDS reads through inline asm
 // The compiler puts "s_waitcnt vmcnt(0)" in front of every ds_read_b64_tr_b16 it emits itself while an LDS-DMA (buffer_load ... lds) is in
@@ -165,7 +166,7 @@ static inline bool hdmoe_first_on_device(unsigned long long& mask) {
 static inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
 
 // ---------------------------------------------------------------- counter RNG (Philox4x32-10)
-DEVI void philox(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1, uint32_t* o) {
+HDI void philox(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1, uint32_t* o) {
   uint32_t c[4] = {c0, c1, 0u, 0u};
 #pragma unroll
   for (int r = 0; r < 10; ++r) {

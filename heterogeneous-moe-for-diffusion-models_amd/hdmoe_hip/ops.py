@@ -1877,6 +1877,94 @@ def text_dropout(out: Tensor, keep: Tensor, text: Tensor, null: Optional[Tensor]
          text.element_size(), p)
 
 
+def dataset_inputs(x: Tensor, x0: Tensor, sigma: Tensor, unet_mask: Tensor, vit_mask: Tensor, zeta_out: Tensor, src: Tensor, item: Tensor,
+                   flip: Tensor, mean: Tensor, std: Optional[Tensor], unet_centers: Tensor, vit_centers: Tensor, seed: int, data_seed: int,
+                   step: int, *, world: int = 1, rank: int = 0, scale: float = 1.0, p_flip: float = 0.0, sigma_min: float, sigma_max: float,
+                   p_mean: float, p_std: float, extreme_prob: float, unet_bw: float, vit_bw: float, min_active: int, zeta: float) -> None:
+    """`train_inputs` with the latents made in the same call from a device-resident dataset (include/hdmoe.h, hdmoe_dataset_inputs):
+    item (B,) int32 = the rows of `mean` / `std` (N,C,H,W), float32 or bfloat16, that step `step` holds for `rank` of `world` under
+    `data_seed` (the seed before the rank is mixed in); flip (B,) float32 0/1; x0 (B,C,H,W) = scale * (mean + std * eps_p), mirrored
+    along W where flip is 1 (`std` None: scale * mean); x = x0 + sigma eps.  Element j of eps_p is element j of
+    randn_keyed(x, seed ^ 0xE7037ED1A0B428DB, 4 * step); sigma, eps, masks, zeta, src are train_inputs' for (seed, step).  Two launches, no
+    sync.  ValueError -- before anything is written -- for what train_inputs rejects, a tensor of the wrong shape / dtype / layout,
+    N < B * world, rank outside [0, world), p_flip outside [0, 1]."""
+    if mean.ndim != 4 or mean.shape[0] < 1 or mean.numel() == 0:
+        raise ValueError(f"dataset_inputs: mean is (N, C, H, W) with N >= 1, got {tuple(mean.shape)}")
+    if mean.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"dataset_inputs: mean must be float32 or bfloat16, got {mean.dtype}")
+    if x0.ndim != 4 or tuple(x0.shape[1:]) != tuple(mean.shape[1:]) or x0.shape[0] < 1:
+        raise ValueError(f"dataset_inputs: x0 has shape {tuple(x0.shape)}, expected (B,) + {tuple(mean.shape[1:])} with B >= 1")
+    N, B, E = mean.shape[0], x0.shape[0], unet_centers.numel()
+    want = {"x": (x, x0.shape, torch.float32), "x0": (x0, None, torch.float32), "sigma": (sigma, None, torch.float32),
+            "unet_mask": (unet_mask, (B, E), torch.float32), "vit_mask": (vit_mask, (B, E), torch.float32), "zeta": (zeta_out, None, torch.float32),
+            "src": (src, (B,), torch.int32), "item": (item, (B,), torch.int32), "flip": (flip, (B,), torch.float32),
+            "mean": (mean, None, mean.dtype), "unet_centers": (unet_centers, (E,), torch.float32), "vit_centers": (vit_centers, (E,), torch.float32)}
+    if std is not None:
+        want["std"] = (std, mean.shape, mean.dtype)
+    for name, (t, shape, dt) in want.items():
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"dataset_inputs: {name} must be contiguous {dt}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"dataset_inputs: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    if sigma.numel() != B or zeta_out.numel() != 1 or int(step) < 0:
+        raise ValueError("dataset_inputs: sigma holds B values, zeta one, step >= 0")
+    if x.untyped_storage().data_ptr() == x0.untyped_storage().data_ptr():
+        raise ValueError("dataset_inputs: x shares its storage with x0")
+    world, rank, p_flip, scale = int(world), int(rank), float(p_flip), float(scale)
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError(f"dataset_inputs: rank in [0, world) and world >= 1, got rank={rank}, world={world}")
+    if N >= 1 << 31 or N < B * world:
+        raise ValueError(f"dataset_inputs: N={N} items do not fill one step of B * world = {B} * {world} (and N < 2^31)")
+    if not 0.0 <= p_flip <= 1.0 or scale != scale:
+        raise ValueError(f"dataset_inputs: p_flip in [0, 1] and a scale that is a number, got p_flip={p_flip}, scale={scale}")
+    M = 0xFFFFFFFFFFFFFFFF
+    try:
+        call("hdmoe_dataset_inputs", x, x0, sigma, unet_mask, vit_mask, zeta_out, src, item, flip, mean, std, _dt(mean), unet_centers,
+             vit_centers, int(seed) & M, int(data_seed) & M, int(step), B, x0.numel() // B, N, mean.shape[2], mean.shape[3], world, rank,
+             scale, p_flip, E, int(min_active), sigma_min, sigma_max, p_mean, p_std, extreme_prob, unet_bw, vit_bw, zeta)
+    except RuntimeError as exc:
+        if "invalid argument" in str(exc):                     # B > 4096, E > 8, min_active > E, a bad sigma range: nothing was launched
+            raise ValueError(f"dataset_inputs: out of range (B={B} <= 4096, E={E} <= 8, min_active={min_active} <= E): {exc}") from None
+        raise
+
+
+def text_gather_dropout(out: Tensor, keep: Tensor, table: Tensor, text_index: Optional[Tensor], item: Tensor, null: Optional[Tensor],
+                        seed: int, step: int, p: float, n_items: int) -> None:
+    """`text_dropout` with row i of `out` (B, ...) taken from row t of `table` (K, ...): t = text_index[item[i]] with `text_index`
+    (n_items,) int32, else 0 when K == 1 and item[i] when K == n_items (include/hdmoe.h, hdmoe_text_gather_dropout).  item (B,) int32
+    holds dataset rows in [0, n_items) -- `dataset_inputs` writes it -- and `text_index` values in [0, K): neither is read back here, the
+    caller has range-checked `text_index`.  keep and the drop decision are text_dropout's for (seed, step); p = 0 is a pure gather.
+    ValueError -- before anything is written -- for a non-contiguous tensor, a wrong dtype or shape, K not in {1, n_items} without a
+    text_index, out sharing storage with table, p outside [0, 1], step < 0."""
+    if table.ndim < 2 or table.shape[0] < 1 or table.numel() == 0:
+        raise ValueError(f"text_gather_dropout: table is (K, ...) with K >= 1 and a non-empty row, got {tuple(table.shape)}")
+    if table.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(f"text_gather_dropout: table must be float32, bfloat16 or float16, got {table.dtype}")
+    if item.ndim != 1 or item.shape[0] < 1:
+        raise ValueError(f"text_gather_dropout: item is (B,) with B >= 1, got {tuple(item.shape)}")
+    K, B, n_items = table.shape[0], item.shape[0], int(n_items)
+    want = {"out": (out, (B,) + tuple(table.shape[1:]), table.dtype), "keep": (keep, (B,), torch.float32), "table": (table, None, table.dtype),
+            "item": (item, None, torch.int32)}
+    if null is not None:
+        want["null"] = (null, table.shape[1:], table.dtype)
+    if text_index is not None:
+        want["text_index"] = (text_index, (n_items,), torch.int32)
+    for name, (t, shape, dt) in want.items():
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"text_gather_dropout: {name} must be contiguous {dt}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"text_gather_dropout: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    if n_items < 1 or (text_index is None and K not in (1, n_items)):
+        raise ValueError(f"text_gather_dropout: a table of K={K} rows for n_items={n_items} needs a text_index (K is neither 1 nor n_items)")
+    if out.is_cuda and table.is_cuda and out.untyped_storage().data_ptr() == table.untyped_storage().data_ptr():
+        raise ValueError("text_gather_dropout: out shares its storage with table")
+    p = float(p)
+    if not 0.0 <= p <= 1.0 or int(step) < 0:
+        raise ValueError(f"text_gather_dropout: p in [0, 1] and step >= 0, got p={p}, step={step}")
+    call("hdmoe_text_gather_dropout", out, keep, table, text_index, item, null, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), B, K, n_items,
+         table.numel() // K, table.element_size(), p)
+
+
 # =====================================================================================================
 # layout / boundary
 # =====================================================================================================

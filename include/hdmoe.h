@@ -388,6 +388,49 @@ int hdmoe_train_inputs(float* x, float* sigma, float* unet_mask, float* vit_mask
 int hdmoe_text_dropout(void* out, float* keep, const void* text, const void* null_row, unsigned long long seed, unsigned long long step,
                        long B, long row, int elem_bytes, double p, HS stream);
 
+/* ---- the device-resident latent dataset  (csrc/traingen.hip, csrc/keyed_perm.h; reference Utils/training.py:226-239 the shuffled
+ * drop_last loader, Utils/VAE_CLIP.py:58-66 the posterior draw) ----
+ * The batch of step k is a pure function of (seed, world, rank, k): which items, their posterior draw, their horizontal flip, their text.
+ * Keyed permutation.  perm(seed, epoch, N, x) for 0 <= x < N, 1 <= N < 2^31: k = max(2, bit_length(N - 1)) rounded up to even, h = k / 2,
+ * m = 2^h - 1, K = ((seed ^ 0xA0761D6478BD642F) + epoch * 0x9E3779B97F4A7C15) mod 2^64.  Eight Feistel rounds on (L, R) = (x >> h, x & m):
+ * for r = 0..7, (L, R) <- (R, L ^ (F_r(R) & m)) with F_r(R) = word 0 of the Philox4x32-10 block (c0 = R, c1 = r) under K; y = (L << h) | R;
+ * while y >= N the eight rounds are applied to y again (cycle walking: the rounds are a bijection of [0, 2^k) and the walk started inside
+ * [0, N), so it comes back).  Host and device run the same function (csrc/keyed_perm.h).
+ * hdmoe_dataset_perm is the host side, no device needed: out[i] = perm(seed, epoch, N, first + i) for 0 <= i < count.
+ * HDMOE_EINVAL: NULL out, N < 1, N >= 2^31, first < 0, count < 0, first + count > N. */
+int hdmoe_dataset_perm(int* out, unsigned long long seed, unsigned long long epoch, long N, long first, long count);
+/* The step's batch.  spe = N / (B world) steps per epoch (>= 1: an incomplete last batch is dropped), epoch = step / spe, pos = step % spe,
+ *   item[i] = perm(data_seed, epoch, N, pos B world + rank B + i)
+ * data_seed is the run's seed before the rank is mixed in, so the ranks of a step hold disjoint slices of one epoch permutation; `seed` is
+ * the rank's own (what hdmoe_train_inputs takes).  RNG contract (continued): the data streams are Philox4x32-10 under
+ * (seed ^ 0xE7037ED1A0B428DB) + (4 step + r) * 0x9E3779B97F4A7C15, so no draw of hdmoe_train_inputs / hdmoe_text_dropout changes or is reused:
+ *   r = 0  eps_p: element j, flat over the OUTPUT (B, chw), is element j of hdmoe_randn under that key (the posterior noise);
+ *   r = 1  flip[i] = u01(word i % 4 of block (i / 4, 0)) < (float)p_flip, stored as fp32 0 / 1.
+ * Outputs, with w' = flip[i] ? W - 1 - w : w, rows of mean / std_dev (N, chw) in data_dtype (HDMOE_F32 or HDMOE_BF16, converted on load):
+ *   x0[i,c,h,w] = scale (mean[item[i],c,h,w'] + std_dev[item[i],c,h,w'] eps_p[i,c,h,w])      (std_dev NULL: scale mean[..], nothing drawn)
+ *   x[i,..] = x0[i,..] + sigma[i] eps[i,..]
+ * and sigma, eps, both masks, zeta_out, src exactly as hdmoe_train_inputs defines them for (seed, step): bit for bit.
+ * Two launches: the one-workgroup per-sample kernel, which also writes item and flip, and one pass that gathers, draws, mirrors, noises and
+ * writes x0 and x together.  It moves 4 elements per thread (16-byte stores, a mirrored vector read at W - 4 - w with its lanes reversed)
+ * when W % 4 == 0, x / x0 are 16-byte aligned and mean / std_dev aligned to 4 of their elements; chw % 4 == 0 is not enough -- at
+ * (4, 8, 6) a vector would straddle image rows -- and anything else moves single elements.  Row offsets item * chw are 64-bit.
+ * HDMOE_EINVAL: what hdmoe_train_inputs rejects, a NULL x0 / item / flip / mean, x == x0, N < 1 or >= 2^31, H or W < 1, chw no multiple
+ * of H W, world < 1, rank outside [0, world), B world > N, p_flip outside [0, 1] or NaN, scale NaN.  HDMOE_EDTYPE: another data_dtype. */
+int hdmoe_dataset_inputs(float* x, float* x0, float* sigma, float* unet_mask, float* vit_mask, float* zeta_out, int* src, int* item, float* flip,
+                         const void* mean, const void* std_dev, int data_dtype, const float* unet_centers, const float* vit_centers,
+                         unsigned long long seed, unsigned long long data_seed, unsigned long long step, long B, long chw, long N, int H, int W,
+                         int world, int rank, double scale, double p_flip, int E, int min_active, double sigma_min, double sigma_max,
+                         double p_mean, double p_std, double extreme_prob, double unet_bw, double vit_bw, float zeta, HS stream);
+/* The batch's text: hdmoe_text_dropout with row i of out taken from row t of `table` (K rows), t = text_index[item[i]] when text_index
+ * (N, int32) is given, else 0 when K == 1 (one fixed prompt) and item[i] when K == N.  The drop decision and keep are hdmoe_text_dropout's
+ * (same draw, same key, the same kernel with a row indirection); p = 0 is a pure gather.  item holds values in [0, N) and text_index values
+ * in [0, K): the kernel follows them unchecked, the caller range-checks text_index once.
+ * HDMOE_EINVAL: NULL out / keep / table / item, out == table, B, K, N or row < 1, elem_bytes not 2 or 4, p outside [0, 1] or NaN, and K
+ * neither 1 nor N without a text_index. */
+int hdmoe_text_gather_dropout(void* out, float* keep, const void* table, const int* text_index, const int* item, const void* null_row,
+                              unsigned long long seed, unsigned long long step, long B, long K, long N, long row, int elem_bytes, double p,
+                              HS stream);
+
 /* ---- K6: norms  (model_internals.py:8-30; nn.GroupNorm / nn.LayerNorm in model_components.py) ------------ */
 int hdmoe_pixelnorm_fwd(void* xn, void* h, const void* x, long rows, int C, int dtype, HS stream);               /* h = mp_silu(xn), optional */
 int hdmoe_pixelnorm_bwd(void* dx, const void* dxn, const void* dh, const void* x, long rows, int C, float sx, int dtype, HS stream);   /* sx scales dxn */
