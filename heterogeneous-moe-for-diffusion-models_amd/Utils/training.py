@@ -113,13 +113,18 @@ class Trainer:
     ``torch.distributed``), their VAE-posterior draw, horizontal flip and text rows are a function of ``(seed, world, rank, step_idx)``
     made inside the same fused input calls, and the result gains ``"item"`` (B,) int32 and ``"flip"`` (B,) float32 0/1.  Under
     ``graphed=True`` the captured step reads the generator's own buffers: no batch is copied.  Resuming at step k sees step k's data
-    again.  With ``dataset=None`` every path is what it was."""
+    again.  With ``dataset=None`` every path is what it was.
+
+    ``evaluator=Utils.evaluation.Evaluator(...), eval_every=n``: behind the update of every n-th step the trainer runs the held-out
+    evaluation -- on the raw weights and, when the evaluator was built with this trainer's ``ema``, on each EMA profile -- keeps the
+    numbers in ``last_eval`` and hands them to the logger's ``log_evaluation``.  The evaluation leaves the training state untouched.
+    With both at their defaults nothing changes."""
 
     def __init__(self, model, model_config, optim_config, loss_config, mask_config, zeta_config, max_grad_norm: float = 1.0,
                  fuse_clip_into_step: bool = True, logger=None, ema=None, ema_snapshot_every: Optional[int] = None,
                  ema_snapshot_dir: Optional[str] = None, device_inputs: bool = False, graphed: bool = False, seed: Optional[int] = None,
                  cond_dropout: float = 0.0, null_text_emb: Optional[torch.Tensor] = None, dataset: Optional[LatentDataset] = None,
-                 batch_size: Optional[int] = None):
+                 batch_size: Optional[int] = None, evaluator=None, eval_every: Optional[int] = None):
         dist = torch.distributed.is_available() and torch.distributed.is_initialized()
         self.world, self.rank = (torch.distributed.get_world_size(), torch.distributed.get_rank()) if dist else (1, 0)
         if dataset is None:
@@ -143,6 +148,18 @@ class Trainer:
                 raise ValueError("Trainer: ema_snapshot_every needs ema_snapshot_dir")
             if int(ema_snapshot_every) < 1:
                 raise ValueError(f"Trainer: ema_snapshot_every must be >= 1, got {ema_snapshot_every}")
+        if eval_every is not None:
+            if evaluator is None:
+                raise ValueError("Trainer: eval_every needs an evaluator")
+            if isinstance(eval_every, bool) or not isinstance(eval_every, int) or eval_every < 1:
+                raise ValueError(f"Trainer: eval_every must be an int >= 1, got {eval_every}")
+        elif evaluator is not None:
+            raise ValueError("Trainer: an evaluator needs eval_every")
+        if evaluator is not None and not callable(getattr(evaluator, "evaluate", None)):
+            raise ValueError(f"Trainer: evaluator is a Utils.evaluation.Evaluator, got {type(evaluator).__name__}")
+        # every `eval_every` steps, behind the update: evaluator.evaluate() on the raw weights and, when the evaluator holds this
+        # trainer's ema, on each of its profiles -> last_eval, and the logger's <run>_validation.jsonl
+        self.evaluator, self.eval_every, self.last_eval = evaluator, eval_every, None
         if not 0.0 <= float(cond_dropout) <= 1.0:            # NaN fails both comparisons
             raise ValueError(f"Trainer: cond_dropout must lie in [0, 1], got {cond_dropout}")
         if null_text_emb is not None and not torch.is_tensor(null_text_emb):
@@ -352,12 +369,27 @@ class Trainer:
                 self._save_ema_snapshot(step + 1)
         self.scheduler.step()
         self.step_idx += 1
+        if self.eval_every is not None and (step + 1) % self.eval_every == 0:
+            self._evaluate(step + 1)
         res = {"loss": loss, "out_model": out_model, "sigma": sigma}
         if keep is not None:
             res["text_keep"] = keep
         if self.dataset is not None:
             res["item"], res["flip"] = self.inputs.data_buf["item"], self.inputs.data_buf["flip"]
         return res
+
+    def _evaluate(self, step: int) -> None:
+        """The held-out numbers after `step` updates (it syncs: one host copy per evaluation): last_eval = {"step", "results": {tag:
+        Evaluator.evaluate's dictionary}} with tag "raw" and, for the evaluator's ema when it is this trainer's, "ema<k>" per profile."""
+        ev = self.evaluator
+        results = {"raw": ev.evaluate()}
+        if self.ema is not None and getattr(ev, "ema", None) is self.ema:
+            for k in range(self.ema.nprofiles):
+                results[f"ema{k}"] = ev.evaluate(profile=k)
+        self.last_eval = {"step": step, "results": results}
+        if self.logger is not None:
+            for tag, r in results.items():
+                self.logger.log_evaluation(step, r, tag=tag)
 
     def _save_ema_snapshot(self, step: int) -> None:
         """A host copy of every average (it syncs).  The averages are bit-identical across data-parallel ranks: rank 0 writes."""

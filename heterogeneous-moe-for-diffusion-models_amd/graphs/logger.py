@@ -164,6 +164,27 @@ class Logger:
                 record[f"{name}_weight_min"] = round(float(host[:, 2].min()), 6)
         self._write_jsonl(self.weight_log_file, record)
 
+    # ------------------------------------------------------------------ no counterpart in the reference
+    EVAL_SCALARS = ("mse_mean", "n")
+    EVAL_LEVELS = ("sigma", "count", "mse", "mse_stderr", "edm_weighted", "nll", "log_var", "unet_usage", "vit_usage", "unet_selected",
+                   "vit_selected")
+
+    def log_evaluation(self, step: int, result: Dict[str, Any], tag: str = "raw"):
+        """One record of `Utils.evaluation.Evaluator.evaluate` into <run>_validation.jsonl: step, tag ("raw", or the EMA profile the
+        weights came from), the scalars and the per-level lists (the usage maps as K lists of E).  `result` holds host arrays: no
+        device work.  NaN (a level without samples) is written as null."""
+        def clean(v):
+            if isinstance(v, list):
+                return [clean(u) for u in v]
+            return None if isinstance(v, float) and not math.isfinite(v) else v
+
+        record = {"step": int(step), "tag": str(tag)}
+        for key in self.EVAL_SCALARS:
+            record[key] = clean(float(result[key]))
+        for key in self.EVAL_LEVELS:
+            record[key] = clean(np.asarray(result[key], dtype=np.float64).tolist())
+        self._write_jsonl(self.log_dir / f"{self.run_name}_validation.jsonl", record)
+
     # ------------------------------------------------------------------ reference logger.py:328-345
     def _flush_training_log(self):
         if len(self.accumulators["step"]) == 0:

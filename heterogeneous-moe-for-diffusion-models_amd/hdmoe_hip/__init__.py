@@ -11,6 +11,7 @@ import torch
 from . import _lib, ops                                    # noqa: F401
 from ._lib import LIB_PATH, lib                            # noqa: F401
 from .ops import manual_seed, next_seed, train_inputs, text_dropout, dataset_inputs, text_gather_dropout   # noqa: F401
+from .ops import eval_inputs, eval_accumulate, randn_keyed   # noqa: F401
 from .bank import invalidate_weights                       # noqa: F401
 from .ema import WeightEMA                                 # noqa: F401
 from . import posthoc                                      # noqa: F401

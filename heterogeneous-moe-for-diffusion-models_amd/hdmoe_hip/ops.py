@@ -1965,6 +1965,94 @@ def text_gather_dropout(out: Tensor, keep: Tensor, table: Tensor, text_index: Op
          table.numel() // K, table.element_size(), p)
 
 
+EVAL_SALT = 0x8EBC6AF09C88C6E3                                # the evaluation noise of include/hdmoe.h: randn_keyed(., seed ^ EVAL_SALT, item K + level)
+EVAL_MAX_LEVELS, EVAL_MAX_BATCH, EVAL_MAX_EXPERTS = 64, 4096, 8
+
+
+def eval_chunk() -> int:
+    """Elements per fp32 partial sum of `eval_accumulate`'s first launch (hdmoe_eval_chunk)."""
+    return int(lib().hdmoe_eval_chunk())
+
+
+def eval_ws_floats(B: int, L: int) -> int:
+    """float32 elements of the workspace `eval_accumulate` needs for a (B, L) batch."""
+    c = eval_chunk()
+    return int(B) * ((int(L) + c - 1) // c)
+
+
+def eval_inputs(x: Tensor, x0: Tensor, sigma: Tensor, level: Tensor, item: Tensor, mean: Tensor, levels: Tensor, seed: int, round: int,
+                first: int, count: int, *, scale: float = 1.0) -> None:
+    """One held-out evaluation batch in one launch (include/hdmoe.h, hdmoe_eval_inputs): item[i] = (first + i) % N over the rows of
+    `mean` (N, ...) float32 or bfloat16, level[i] = (item[i] + round) % K for i < count and -1 for the padding rows behind, sigma[i] =
+    levels[(item[i] + round) % K] with `levels` (K,) float32, x0[i] = scale * mean[item[i]], x[i] = x0[i] + sigma[i] * eps where eps is
+    randn_keyed(x[i], seed ^ EVAL_SALT, item[i] * K + level).  Nothing syncs.  ValueError -- before anything is written -- for a tensor of
+    the wrong shape / dtype / layout, x sharing storage with x0, B > 4096, K > 64, count outside [0, B], a negative first or round."""
+    if mean.ndim < 2 or mean.shape[0] < 1 or mean.numel() == 0:
+        raise ValueError(f"eval_inputs: mean is (N, ...) with N >= 1 and a non-empty row, got {tuple(mean.shape)}")
+    if mean.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"eval_inputs: mean must be float32 or bfloat16, got {mean.dtype}")
+    if x0.ndim != mean.ndim or tuple(x0.shape[1:]) != tuple(mean.shape[1:]) or x0.shape[0] < 1:
+        raise ValueError(f"eval_inputs: x0 has shape {tuple(x0.shape)}, expected (B,) + {tuple(mean.shape[1:])} with B >= 1")
+    if levels.ndim != 1 or levels.numel() < 1:
+        raise ValueError(f"eval_inputs: levels is (K,) with K >= 1, got {tuple(levels.shape)}")
+    N, B, K = mean.shape[0], x0.shape[0], levels.numel()
+    want = {"x": (x, x0.shape, torch.float32), "x0": (x0, None, torch.float32), "sigma": (sigma, None, torch.float32),
+            "level": (level, (B,), torch.int32), "item": (item, (B,), torch.int32), "mean": (mean, None, mean.dtype),
+            "levels": (levels, None, torch.float32)}
+    for name, (t, shape, dt) in want.items():
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"eval_inputs: {name} must be contiguous {dt}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"eval_inputs: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    if sigma.numel() != B:
+        raise ValueError("eval_inputs: sigma holds B values")
+    if x.is_cuda and x0.is_cuda and x.untyped_storage().data_ptr() == x0.untyped_storage().data_ptr():
+        raise ValueError("eval_inputs: x shares its storage with x0")
+    round, first, count, scale = int(round), int(first), int(count), float(scale)
+    if B > EVAL_MAX_BATCH or K > EVAL_MAX_LEVELS or N >= 1 << 31:
+        raise ValueError(f"eval_inputs: out of range (B={B} <= {EVAL_MAX_BATCH}, K={K} <= {EVAL_MAX_LEVELS}, N={N} < 2^31)")
+    if not 0 <= count <= B or first < 0 or round < 0 or scale != scale:
+        raise ValueError(f"eval_inputs: count in [0, B], first >= 0, round >= 0 and a scale that is a number, got count={count}, "
+                         f"first={first}, round={round}, scale={scale}")
+    call("hdmoe_eval_inputs", x, x0, sigma, level, item, mean, _dt(mean), levels, int(seed) & 0xFFFFFFFFFFFFFFFF, round, first, count, B,
+         x0.numel() // B, N, K, scale)
+
+
+def eval_accumulate(acc: Tensor, ws: Tensor, denoised: Tensor, x0: Tensor, sigma: Tensor, level: Tensor, log_var: Optional[Tensor],
+                    pU: Tensor, pV: Tensor, sigma_data: float) -> None:
+    """acc (K, 6 + 4E) float64 += the per-level statistics of one batch, in two launches without atomics (include/hdmoe.h,
+    hdmoe_eval_accumulate): row k = [n, sum mse, sum mse^2, sum w mse, sum (mse exp(-lv) + lv), sum lv, sum pU, #(pU > 0), sum pV,
+    #(pV > 0)] over the samples with level == k.  denoised / x0 (B, ...) float32, sigma and log_var (None: lv = 0) B float32 values,
+    level (B,) int32, pU / pV (B, E) float32, ws >= eval_ws_floats(B, L) float32.  The caller zeroes acc.  ValueError -- before
+    anything is written -- for a tensor of the wrong shape / dtype / layout, B > 4096, E > 8, K > 64, a workspace that is too small."""
+    if denoised.ndim < 2 or denoised.shape[0] < 1 or denoised.numel() == 0:
+        raise ValueError(f"eval_accumulate: denoised is (B, ...) with B >= 1 and a non-empty row, got {tuple(denoised.shape)}")
+    if pU.ndim != 2 or pU.shape[0] != denoised.shape[0] or pU.shape[1] < 1:
+        raise ValueError(f"eval_accumulate: pU is (B, E) with E >= 1, got {tuple(pU.shape)}")
+    B, E = pU.shape
+    L = denoised.numel() // B
+    if acc.ndim != 2 or acc.shape[0] < 1 or acc.shape[1] != 6 + 4 * E:
+        raise ValueError(f"eval_accumulate: acc is (K, 6 + 4E) = (K, {6 + 4 * E}), got {tuple(acc.shape)}")
+    K = acc.shape[0]
+    want = {"acc": (acc, None, torch.float64), "ws": (ws, None, torch.float32), "denoised": (denoised, None, torch.float32),
+            "x0": (x0, denoised.shape, torch.float32), "sigma": (sigma, None, torch.float32), "level": (level, (B,), torch.int32),
+            "pU": (pU, None, torch.float32), "pV": (pV, (B, E), torch.float32)}
+    if log_var is not None:
+        want["log_var"] = (log_var, None, torch.float32)
+    for name, (t, shape, dt) in want.items():
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"eval_accumulate: {name} must be contiguous {dt}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"eval_accumulate: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    if sigma.numel() != B or (log_var is not None and log_var.numel() != B):
+        raise ValueError("eval_accumulate: sigma and log_var hold B values")
+    if B > EVAL_MAX_BATCH or E > EVAL_MAX_EXPERTS or K > EVAL_MAX_LEVELS:
+        raise ValueError(f"eval_accumulate: out of range (B={B} <= {EVAL_MAX_BATCH}, E={E} <= {EVAL_MAX_EXPERTS}, K={K} <= {EVAL_MAX_LEVELS})")
+    if ws.numel() < eval_ws_floats(B, L):
+        raise ValueError(f"eval_accumulate: ws holds {ws.numel()} floats, a (B, L) = ({B}, {L}) batch needs {eval_ws_floats(B, L)}")
+    call("hdmoe_eval_accumulate", acc, ws, denoised, x0, sigma, level, log_var, pU, pV, B, L, E, K, float(sigma_data))
+
+
 # =====================================================================================================
 # layout / boundary
 # =====================================================================================================

@@ -431,6 +431,38 @@ int hdmoe_text_gather_dropout(void* out, float* keep, const void* table, const i
                               unsigned long long seed, unsigned long long step, long B, long K, long N, long row, int elem_bytes, double p,
                               HS stream);
 
+/* ---- held-out evaluation on the device  (csrc/evalstats.hip; no counterpart in the reference, which measures nothing but the training
+ * loss of the current batch) ----
+ * hdmoe_eval_inputs: one evaluation batch from the dataset's `mean` table ((N, chw) in data_dtype, HDMOE_F32 or HDMOE_BF16), one launch.
+ * `levels` = K sigma values (device fp32).  For 0 <= i < B:
+ *   item[i] = (first + i) % N,   k_i = (item[i] + round) % K,   sigma[i] = levels[k_i],   level[i] = k_i for i < count and -1 for the rows
+ *   count <= i < B that pad the last batch (they carry a finite sigma and ordinary latents: the model sees nothing unusual);
+ *   x0[i] = scale mean[item[i]] (the posterior mean: no draw, no flip -- the target is a function of the item alone);
+ *   x[i] = x0[i] + sigma[i] eps_i, one fma per element as in hdmoe_train_inputs.
+ * RNG contract (continued).  Element j of eps_i is element j of hdmoe_randn(seed = seed ^ 0x8EBC6AF09C88C6E3, *seed_dev = item[i] K + k_i,
+ * scale = 1, n = chw), i.e. Philox4x32-10 under (seed ^ 0x8EBC6AF09C88C6E3) + (item[i] K + k_i) * 0x9E3779B97F4A7C15, lane j % 4 of block
+ * j / 4 whatever chw % 4 is.  The key holds the item and the level and nothing else: the noise of an (item, level) pair does not depend on
+ * B, the position in the batch, round, rank or step, and no draw of the training streams above changes or is reused.
+ * It moves 4 elements per thread when chw % 4 == 0, x / x0 are 16-byte aligned and mean is aligned to 4 of its elements (there is no flip,
+ * so a vector may straddle image rows); anything else moves single elements.  Row offsets item * chw are 64-bit.
+ * HDMOE_EINVAL: a NULL pointer, x == x0, B, chw, N or K < 1, K > 64, B > 4096, N >= 2^31, count < 0 or > B, first < 0, round < 0, scale
+ * NaN.  HDMOE_EDTYPE: another data_dtype.  Nothing is written on error. */
+int hdmoe_eval_inputs(float* x, float* x0, float* sigma, int* level, int* item, const void* mean, int data_dtype, const float* levels,
+                      unsigned long long seed, int round, long first, long count, long B, long chw, long N, int K, double scale, HS stream);
+/* hdmoe_eval_accumulate: acc (K, F) doubles, F = 6 + 4 E, += the statistics of one batch.  Row k sums over the samples with level[i] == k:
+ *   [ n, mse, mse^2, w mse, mse exp(-lv) + lv, lv, pU[0..E), (pU > 0)[0..E), pV[0..E), (pV > 0)[0..E) ]
+ * mse = sum_j (denoised - x0)^2 / L of the sample ((B, L) fp32 each), w = (sigma^2 + sigma_data^2) / (sigma sigma_data)^2 the EDM weight,
+ * lv = clamp(log_var, -10, 10) as hdmoe_edm_loss_fwd takes it (log_var (B) fp32; NULL: lv = 0), pU / pV the (B, E) fp32 gate
+ * probabilities of the two routers.  A row with level < 0 or >= K contributes nothing and indexes nothing.
+ * Two launches, no atomics, nothing zeroed: the caller zeroes acc between evaluations, outside any captured graph.  The first launch writes
+ * one fp32 partial sum of squares per (sample, chunk of hdmoe_eval_chunk() = 4096 elements) into ws -- B * ceil(L / hdmoe_eval_chunk())
+ * floats, caller-provided; the chunking does not depend on B -- the second is one workgroup that sums per level, in sample order, in
+ * double.  The same inputs give the same bits, eager or replayed; a NaN reaches the sums of its own level only.
+ * HDMOE_EINVAL: NULL acc / ws / denoised / x0 / sigma / level / pU / pV, B < 1 or > 4096, L < 1, E < 1 or > 8, K < 1 or > 64. */
+int hdmoe_eval_chunk(void);
+int hdmoe_eval_accumulate(double* acc, float* ws, const float* denoised, const float* x0, const float* sigma, const int* level,
+                          const float* log_var, const float* pU, const float* pV, int B, long L, int E, int K, double sigma_data, HS stream);
+
 /* ---- K6: norms  (model_internals.py:8-30; nn.GroupNorm / nn.LayerNorm in model_components.py) ------------ */
 int hdmoe_pixelnorm_fwd(void* xn, void* h, const void* x, long rows, int C, int dtype, HS stream);               /* h = mp_silu(xn), optional */
 int hdmoe_pixelnorm_bwd(void* dx, const void* dxn, const void* dh, const void* x, long rows, int C, float sx, int dtype, HS stream);   /* sx scales dxn */
