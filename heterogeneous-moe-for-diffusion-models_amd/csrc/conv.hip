@@ -1491,6 +1491,7 @@ static int conv_fwd_dispatch(const ConvArgs& a, int dtype, hipStream_t stream, i
     if (rc > 0) { fam = HDMOE_ROUTE_CONV_CONV6; rc = conv6_try_launch(a, nullptr, dtype, stream, t); }   // k x k layers of the experts / trunks: persistent LDS-DMA kernel (conv6.hip)
     if (rc > 0) { fam = HDMOE_ROUTE_CONV_KGEMM; rc = kgemm_try_launch(a, dtype, stream, nullptr, 0, t); }   // pointwise, long contraction, few outputs (kgemm.hip)
     if (rc > 0) { fam = HDMOE_ROUTE_CONV_GLIN; rc = glin_try_launch(a, dtype, stream, t); }   // grouped fp32 linear on one-position rows, long input (mlinear.hip)
+    if (rc > 0) { fam = HDMOE_ROUTE_CONV_ROWLIN; rc = rowlin_try_launch(a, dtype, stream, t); }   // fp32 pointwise on at most 2048 positions (rowlin.hip)
     if (rc > 0) return conv_fwd_generic(a, dtype, stream, route);
   }
   if (route && rc == HDMOE_OK) route[0] = fam;               // (a sibling took the layer, or none: their template arguments are in t[])

@@ -140,3 +140,6 @@ int towg_try_launch(const void* x, const void* dy, float* G, int N, int H, int W
 
 // Grouped fp32 linear on one-position rows with a long input, 256 <= Cin <= 1024 (the experts' text projection; mlinear.hip).  Same return convention.
 int glin_try_launch(const ConvArgs& a, int dtype, hipStream_t stream, int* tmpl = nullptr);
+
+// fp32 pointwise forward / dgrad on at most 2048 positions, Cin >= 32 (the conditioning layers and the router heads; rowlin.hip).  Same return convention.
+int rowlin_try_launch(const ConvArgs& a, int dtype, hipStream_t stream, int* tmpl = nullptr);

@@ -208,11 +208,16 @@ __global__ __launch_bounds__(256) void lwg_f32_kernel(LwgArgs a) {
 // taps * Cin <= 64 columns.  The tiled kernel pads Cin to 32 per tap (8x the work, 300 us); here the contraction over pixels runs on
 // v_mfma_f32_32x32x2_f32 with A = dy[pixel][o] (a coalesced row load) and B = the im2col row of x built on the fly
 // (column n = tap * Cin + i -> x[pixel + tap offset][i], zero outside the image): 2 MFMAs per 2 pixels per wave, HBM-bound on dy.
+// A wave's trip is one memory latency (24 loads, then 16 MFMAs) and nothing in it overlaps the next trip's loads.  With four waves on a
+// CU -- one workgroup per CU, so that the atomic flush of the 1152 words stays at 256 workgroups -- each SIMD holds ONE wave.  NW = 16
+// waves per workgroup put four waves on every SIMD with the same number of workgroups and atomics; they meet in LDS ([NW][NBLK]
+// accumulator tiles, 128 KB for the stem) before the one flush.  Stem launch in the replayed step: 68.8 -> 53 us (DESIGN Round 14);
+// what holds the rest is not found yet (the MFMAs are 7 us, the 38 MB of HBM 8 us).
 struct SwgArgs { const float* x; const float* dy; float* G; int N, H, W, Cin, Cout, k, pt, pl; long ppb; };
 
-template <int NBLK>
-__global__ __launch_bounds__(256) void swg_f32_kernel(SwgArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float red[];   // [4 waves][NBLK][16][64]
+template <int NBLK, int NW>
+__global__ __launch_bounds__(64 * NW) void swg_f32_kernel(SwgArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float red[];   // [NW waves][NBLK][16][64]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
   const int o0 = blockIdx.y * 32;
@@ -233,12 +238,12 @@ __global__ __launch_bounds__(256) void swg_f32_kernel(SwgArgs a) {
   for (int b = 0; b < NBLK; ++b) acc[b] = (f32x16)(0.f);
   // 8 k-steps (16 pixels of this wave) per trip: all their loads are issued before the first MFMA (one step at a time the loop ran at
   // one memory latency per step)
-  for (long base = p0; base < p1; base += 64) {
+  for (long base = p0; base < p1; base += 16 * NW) {
     float dv[8], xv[8][NBLK];
     bool okm[8], inm[8][NBLK];
 #pragma unroll
     for (int st = 0; st < 8; ++st) {
-      const long p = base + 8 * st + 2 * wave + h;
+      const long p = base + 2 * NW * st + 2 * wave + h;
       const bool ok = p < p1;
       const unsigned pc = (unsigned)(ok ? p : p0);               // 32-bit index arithmetic (64-bit div / mod cost ~500 instructions per step)
       const unsigned t = pc / (unsigned)a.W;
@@ -274,12 +279,12 @@ __global__ __launch_bounds__(256) void swg_f32_kernel(SwgArgs a) {
     for (int reg = 0; reg < 16; ++reg) red[((wave * NBLK + b) * 16 + reg) * 64 + lane] = acc[b][reg];
   __syncthreads();
   const int rot = (int)((blockIdx.x * 37u) % (unsigned)(NBLK * 4)) * 256;      // stagger the workgroups' atomic flushes (see lwg_flush)
-  for (int e0 = tid; e0 < NBLK * 1024; e0 += 256) {
+  for (int e0 = tid; e0 < NBLK * 1024; e0 += 64 * NW) {
     const int e = (e0 + rot) % (NBLK * 1024);
     const int l = e & 63, reg = (e >> 6) & 15, b = e >> 10;
     float v = 0.f;
 #pragma unroll
-    for (int w = 0; w < 4; ++w) v += red[((w * NBLK + b) * 16 + reg) * 64 + l];
+    for (int w = 0; w < NW; ++w) v += red[((w * NBLK + b) * 16 + reg) * 64 + l];
     const int o = o0 + acc_row(reg, l), n = 32 * b + (l & 31);
     if (n < ncols) {
       const int tap = n / a.Cin, i = n - tap * a.Cin;
@@ -418,12 +423,24 @@ int swg_try_launch(const void* x, const void* dy, float* G, int N, int H, int W,
   a.x = (const float*)x; a.dy = (const float*)dy; a.G = G; a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.k = k; a.pt = pt; a.pl = pl;
   const long total = (long)N * H * W;
   long blocks = 256 / (Cout / 32); if (blocks < 1) blocks = 1;       // one workgroup per CU: more only adds atomic flushes of the same 1152 words
-  long ppb = (total + blocks - 1) / blocks; ppb = (ppb + 63) / 64 * 64;
+  // 16 waves per workgroup when every workgroup has at least one trip for each of them; four waves below that (small maps)
+  const int NW = (total + blocks - 1) / blocks >= 16 * 16 ? 16 : 4;
+  long ppb = (total + blocks - 1) / blocks; ppb = (ppb + 16 * NW - 1) / (16 * NW) * (16 * NW);
   a.ppb = ppb;
   const dim3 grid((unsigned)((total + ppb - 1) / ppb), Cout / 32);
   const int NBLK = (k * k * Cin + 31) / 32;
-  if (NBLK == 1) hipLaunchKernelGGL(swg_f32_kernel<1>, grid, dim3(256), 4 * 1 * 4096, stream, a);
-  else hipLaunchKernelGGL(swg_f32_kernel<2>, grid, dim3(256), 4 * 2 * 4096, stream, a);
+  if (NW == 16) {
+    static unsigned long long attr_set = 0;
+    if (hdmoe_first_on_device(attr_set)) {
+      (void)hipFuncSetAttribute((const void*)swg_f32_kernel<1, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 1 * 4096);
+      (void)hipFuncSetAttribute((const void*)swg_f32_kernel<2, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 2 * 4096);
+    }
+    if (NBLK == 1) hipLaunchKernelGGL((swg_f32_kernel<1, 16>), grid, dim3(1024), 16 * 1 * 4096, stream, a);
+    else hipLaunchKernelGGL((swg_f32_kernel<2, 16>), grid, dim3(1024), 16 * 2 * 4096, stream, a);
+  } else {
+    if (NBLK == 1) hipLaunchKernelGGL((swg_f32_kernel<1, 4>), grid, dim3(256), 4 * 1 * 4096, stream, a);
+    else hipLaunchKernelGGL((swg_f32_kernel<2, 4>), grid, dim3(256), 4 * 2 * 4096, stream, a);
+  }
   return hdmoe_launch_status();
 }
 

@@ -660,6 +660,73 @@ static inline unsigned rows_grid(long rows, int lpr) {
   if (b < 1) b = 1;
   return (unsigned)b;
 }
+// ---- GroupNorm(1, C) backward on SINGLE-POSITION rows (S == 1: the norms of the conditioning MLPs, (N, 512 or 1024) fp32).  The image
+// kernels above run it as a statistics launch with one 512-thread workgroup per row -- two block reductions and 2 C global atomics per
+// row, 39 us for 1 MB -- and an apply launch.  Here a wave owns a row: it holds the row in registers (NJ = ceil(C / 256) float4 pieces
+// per lane), the two sums meet by cross-lane adds and dx is written at once, so a row's result depends on that row alone.  A workgroup
+// takes GNR_ROWS rows; its per-channel dgamma / dbeta partials are added over the rows in registers, over the four waves in LDS in a
+// fixed order, and leave as one atomic per channel and workgroup (N / 8 per address instead of N).
+// The backward only: everything it writes ends in fp32 parameter gradients.  The forward of these rows stays on the two image kernels
+// (5 us each): its output feeds the bf16 experts, and another summation order there moves the step's results (DESIGN Round 14).
+constexpr int GNR_ROWS = 8;
+template <int NJ>
+__global__ __launch_bounds__(256) void groupnorm_rows_bwd_kernel(float* dx, float* dgamma, float* dbeta, const float* dy, const float* x,
+                                                                const float* gamma, const float* beta, const float* mean,
+                                                                const float* rstd, int N, int C, int act) {
+  __shared__ __attribute__((aligned(16))) float sm[2][4][NJ * 256];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float invm = 1.f / (float)C;
+  f32x4 gm[NJ], bt[NJ], dg[NJ], db[NJ];
+  bool ok[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int c = 4 * (lane + 64 * j);
+    ok[j] = c < C;
+    gm[j] = ok[j] ? *reinterpret_cast<const f32x4*>(gamma + c) : (f32x4)(0.f);
+    bt[j] = ok[j] ? *reinterpret_cast<const f32x4*>(beta + c) : (f32x4)(0.f);
+    dg[j] = (f32x4)(0.f); db[j] = (f32x4)(0.f);
+  }
+  for (int k = wave; k < GNR_ROWS; k += 4) {
+    const int n = blockIdx.x * GNR_ROWS + k;
+    if (n >= N) break;
+    const float m = mean[n], rs = rstd[n];
+    f32x4 xh[NJ], dz[NJ];
+    float a1 = 0.f, a2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const long at = (long)n * C + 4 * (lane + 64 * j);
+      const f32x4 f = ok[j] ? *reinterpret_cast<const f32x4*>(x + at) : (f32x4)(0.f);
+      const f32x4 d = ok[j] ? *reinterpret_cast<const f32x4*>(dy + at) : (f32x4)(0.f);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        xh[j][e] = (f[e] - m) * rs;
+        dz[j][e] = ok[j] ? d[e] * act_grad_f(xh[j][e] * gm[j][e] + bt[j][e], act) : 0.f;
+        a1 += dz[j][e] * gm[j][e]; a2 += dz[j][e] * gm[j][e] * xh[j][e];
+        dg[j][e] += dz[j][e] * xh[j][e]; db[j][e] += dz[j][e];
+      }
+    }
+    a1 = wave_sum(a1); a2 = wave_sum(a2);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      if (!ok[j]) continue;
+      f32x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = rs * (dz[j][e] * gm[j][e] - invm * (a1 + xh[j][e] * a2));
+      *reinterpret_cast<f32x4*>(dx + (long)n * C + 4 * (lane + 64 * j)) = o;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    *reinterpret_cast<f32x4*>(&sm[0][wave][4 * (lane + 64 * j)]) = dg[j];
+    *reinterpret_cast<f32x4*>(&sm[1][wave][4 * (lane + 64 * j)]) = db[j];
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += 256) {
+    atomicAdd(&dgamma[c], ((sm[0][0][c] + sm[0][1][c]) + sm[0][2][c]) + sm[0][3][c]);
+    atomicAdd(&dbeta[c], ((sm[1][0][c] + sm[1][1][c]) + sm[1][2][c]) + sm[1][3][c]);
+  }
+}
+
 template <typename T> static inline bool gn_vec_ok(int C, int G, const void* a, const void* b, const void* c) {
   const int W = VT<T>::W;
   auto al = [](const void* p) { return p == nullptr || (uintptr_t)p % 16 == 0; };
@@ -1091,6 +1158,14 @@ static int groupnorm_bwd_impl(void* dx, float* dgamma, float* dbeta, float* ws, 
   if (dyb && dy == nullptr) dy = x;                           // (only for the vector-path alignment check; never read)
   const long n = (long)N * S * C;
   float* s1 = ws; float* s2 = ws + (long)N * G;
+  if (dtype == HDMOE_F32 && S == 1 && G == 1 && parts == 1 && !dyb && C % 4 == 0 && C <= 1024 && al16(dx) && al16(dy) && al16(x) &&
+      al16(gamma) && al16(beta)) {                            // single-position rows: statistics and apply in one launch, a wave per row
+#define GNR_LAUNCH(NJ) hipLaunchKernelGGL(groupnorm_rows_bwd_kernel<NJ>, dim3(cdiv(N, GNR_ROWS)), dim3(256), 0, stream, (float*)dx, dgamma, dbeta, \
+                                          (const float*)dy, (const float*)x, gamma, beta, mean, rstd, N, C, act)
+    switch ((C + 255) / 256) { case 1: GNR_LAUNCH(1); break; case 2: GNR_LAUNCH(2); break; case 3: GNR_LAUNCH(3); break; default: GNR_LAUNCH(4); break; }
+#undef GNR_LAUNCH
+    return hdmoe_launch_status();
+  }
   DT_SWITCH(dtype, if (gn_vec_ok<T>(C, G, dx, dy, x)) {
     const long nvec = n / VT<T>::W;
     hipLaunchKernelGGL(groupnorm_bwd_stats_vec_kernel<T>, dim3(N, parts), dim3(512), 0, stream, s1, s2, dgamma, dbeta, (const T*)dy, (const T*)x,

@@ -166,7 +166,7 @@ def _c7_min_images() -> int:
 # kernel names as csrc/ spells them, by HDMOE_ROUTE_CONV_* / HDMOE_ROUTE_WGRAD_* (include/hdmoe.h); r = the route array, b = its ints as bools
 _FWD_KERNELS = ("conv_fwd_kernel<{t}, {r[1]}, {b[2]}>", "conv_fwd2_kernel<{t}, {r[1]}, {b[2]}>", "conv_fwd3_kernel<{t}, {r[1]}>",
                 "conv_fwd5_kernel<{t}, {r[1]}, {b[3]}, {r[4]}>", "conv7_kernel<{r[1]}, {r[2]}, {b[3]}>", "conv6_bf16_kernel<{r[1]}, {r[2]}>",
-                "conv6_split_kernel<{r[1]}>", "kgemm_kernel<{r[1]}>", "glin_f32_kernel<{r[1]}>", "none")
+                "conv6_split_kernel<{r[1]}>", "kgemm_kernel<{r[1]}>", "glin_f32_kernel<{r[1]}>", "none", "rowlin_f32_kernel")
 _WGRAD_KERNELS = (None, "conv_wgrad_kernel<{t}>", "swg_f32_kernel", "towg_bf16_kernel", "lwg_{s}_kernel")
 ROUTE_CONV6S = 6                           # HDMOE_ROUTE_CONV_CONV6S
 

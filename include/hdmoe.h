@@ -167,7 +167,7 @@ int hdmoe_kernel_selections(long long* counts, int n, int reset);
  * the call passes a seg array / a residual.
  * hdmoe_conv_fwd_route: the walk hdmoe_conv_fwd itself makes for the same arguments (dtype HDMOE_F32S included).  route = HOST array of
  * 5 ints {HDMOE_ROUTE_CONV_*, then the template arguments of the instantiation, 0 in the slots the family does not use}:
- *   CONV7: CO, KMASK, W16    CONV6: MT, NT    CONV6S: NT    KGEMM: NT    GLIN: NJ    FWD / FWD2 / FWD3 / FWD5: NT (conv_fwd_kernel: NB), VEC, LEPI, NHR
+ *   CONV7: CO, KMASK, W16    CONV6: MT, NT    CONV6S: NT    KGEMM: NT    GLIN: NJ    ROWLIN: outputs per tile    FWD / FWD2 / FWD3 / FWD5: NT (conv_fwd_kernel: NB), VEC, LEPI, NHR
  * HDMOE_ROUTE_CONV_NONE is an answer, not an error: nothing would run (an HDMOE_F32S layer outside conv6s's domain, which hdmoe_conv_fwd
  * refuses with HDMOE_EINVAL; an empty batch).
  * hdmoe_conv_generic_route: the generic tail of that walk alone (conv_fwd_plan), whether or not a specialised kernel would take the layer;
@@ -185,6 +185,7 @@ enum {
   HDMOE_ROUTE_CONV_KGEMM = 7, /* kgemm_kernel<NT> (csrc/kgemm.hip) */
   HDMOE_ROUTE_CONV_GLIN = 8,  /* glin_f32_kernel<NJ> (csrc/mlinear.hip) */
   HDMOE_ROUTE_CONV_NONE = 9,  /* no kernel */
+  HDMOE_ROUTE_CONV_ROWLIN = 10, /* rowlin_f32_kernel, route[1] = outputs per tile (csrc/rowlin.hip) */
   HDMOE_ROUTE_WGRAD_V2 = 0,   /* conv_wgrad2_kernel<T, OT, MAXT, VEC>, one launch per class and pass */
   HDMOE_ROUTE_WGRAD_V1 = 1,   /* conv_wgrad_kernel<T> */
   HDMOE_ROUTE_WGRAD_SWG = 2,  /* swg_f32_kernel (csrc/lwgrad.hip) */

@@ -41,6 +41,7 @@ const ArgSpec kSpecs[] = {
     {"pw_bwd_kernel", {148}, {{124, 128}}},
     {"kgemm_kernel", {56}, {}},
     {"glin_f32_kernel", {76}, {}},
+    {"rowlin_f32_kernel", {88}, {}},
 };
 
 std::string short_name(const void* f) {
@@ -178,6 +179,7 @@ void run_fwd(int dtype, int stride, int ones, const Groups& g, int N, int H, int
     case 6: snprintf(buf, sizeof buf, "conv6_split_kernel<%d>", r[1]); break;
     case 7: snprintf(buf, sizeof buf, "kgemm_kernel<%d>", r[1]); break;
     case 8: snprintf(buf, sizeof buf, "glin_f32_kernel<%d>", r[1]); break;
+    case 10: snprintf(buf, sizeof buf, "rowlin_f32_kernel"); break;
   }
   if ((r[0] == 9) != g_call.empty()) { ++g_route_checked; ++g_route_bad; fprintf(stderr, "call %ld: route %d, %zu launches\n", g_call_no, r[0], g_call.size()); return; }
   check(buf);                                               // (route 9 = none: nothing launched, nothing to compare)
