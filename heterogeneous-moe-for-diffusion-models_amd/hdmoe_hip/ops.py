@@ -10,15 +10,19 @@ from __future__ import annotations
 import ctypes
 import functools
 import math
-from typing import List, Optional, Sequence
+from typing import Optional, Sequence
 
 import torch
 
 from . import bank as _bank
 from ._lib import dtype_code_cast  # noqa: F401
-from ._lib import _int_array, call, dtype_code, lib
+from ._lib import BF16, _int_array, call, dtype_code, lib
 
 Tensor = torch.Tensor
+
+# C-ABI constants (include/hdmoe.h)
+F32S = 2                                  # HDMOE_F32S, dtype code: fp32 tensors, split-bf16 arithmetic
+ROUTE_CONV6S = 6                          # HDMOE_ROUTE_CONV_CONV6S
 
 
 def _c(t: Optional[Tensor]) -> Optional[Tensor]:
@@ -168,7 +172,6 @@ _FWD_KERNELS = ("conv_fwd_kernel<{t}, {r[1]}, {b[2]}>", "conv_fwd2_kernel<{t}, {
                 "conv_fwd5_kernel<{t}, {r[1]}, {b[3]}, {r[4]}>", "conv7_kernel<{r[1]}, {r[2]}, {b[3]}>", "conv6_bf16_kernel<{r[1]}, {r[2]}>",
                 "conv6_split_kernel<{r[1]}>", "kgemm_kernel<{r[1]}>", "glin_f32_kernel<{r[1]}>", "none", "rowlin_f32_kernel")
 _WGRAD_KERNELS = (None, "conv_wgrad_kernel<{t}>", "swg_f32_kernel", "towg_bf16_kernel", "lwg_{s}_kernel")
-ROUTE_CONV6S = 6                           # HDMOE_ROUTE_CONV_CONV6S
 
 
 def _kernel_label(r, x: Tensor, wgrad: bool = False) -> str:
@@ -388,6 +391,69 @@ def _w6_workspace(policy, device, kib):
     return ws
 
 
+class _ConvLayer(_collections.namedtuple("_ConvLayer", "G N H W Ho Wo Cphys I O Ipad Opad khs kws pts wstride wdstride dtc gain_val alpha beta "
+                                                       "ones normalize split res_raw has_res")):
+    """One stride-1 (grouped) conv layer as its launches see it: made once in _MPConvFn.forward (or from a weight-bank entry), read by the
+    backward.  Cphys: stored input channels (I - 1 with the ones channel); pts: the padding of both axes; wstride / wdstride: elements per
+    group of the forward / the flipped dgrad weight image; dtc: the launches' C-ABI dtype code (F32S for a split layer)."""
+    __slots__ = ()
+
+    @classmethod
+    def of_entry(cls, ent, N: int, H: int, W: int, dtc: int) -> "_ConvLayer":     # a same-size bank layer over N H x W maps, no residual
+        return cls(len(ent.params), N, H, W, H, W, ent.I, ent.I, ent.O, ent.Ipad, ent.Opad, ent.khs, ent.kws, [(k - 1) // 2 for k in ent.kws],
+                   ent.wstride, ent.wdstride, dtc, ent.gain, ent.alpha, 0.0, False, ent.normalize, ent.dtype == "split", False, False)
+
+    def record(self, seg, mult: float, **name) -> dict:                           # the PROFILE record of a fused launch
+        return dict(**name, seg=seg, N=self.N, HW=self.H * self.W, O=self.O, I=self.Cphys, taps=[a * b for a, b in zip(self.khs, self.kws)], mult=mult)
+
+
+class _BwdPlan(_collections.namedtuple("_BwdPlan", "name dtc policy mid tail defer stats label film", defaults=(False,))):
+    """One fused backward launch (input + weight gradient of a weight-bank layer) as data -- _fused_bwd's arguments: entry point, dtype code,
+    workspace policy (of _w6_workspace; None: no workspace), ``mid`` (or a callable that allocates the launch's own scratch, called once the
+    workspace is there), ``tail``, ``defer``, ``stats``, the maker of the PROFILE record; film: hdmoe_conv_bwd6_film takes the same ``mid``."""
+    __slots__ = ()
+
+    def workspace(self, L: _ConvLayer, device) -> Optional[Tensor]:
+        return _w6_workspace(self.policy, device, _w6_kib(L.G, L.N, L.H, L.W, L.Cphys, L.O, L.khs, L.kws, self.dtc))
+
+    def launch(self, bank, ent, x, dy, dx, ws) -> bool:
+        return _fused_bwd(bank, ent, self.label, self.name, x, dy, ent.wd, dx, self.mid, ws, self.tail, self.defer, self.stats)
+
+
+def _kxk_bwd_plan(L: _ConvLayer, seg, policy: str, stats: tuple, kernel: str, film: bool = False, gn_in=(None, None, 0)) -> _BwdPlan:
+    """hdmoe_conv_bwd6 (k x k bf16 layer: csrc/bwd6.hip, conv7_body.h) or, for L.dtc == F32S, hdmoe_conv_bwd6s (3x3 router-trunk layer: fp32
+    tensors, split-bf16 arithmetic; ``gn_in`` = (scale, shift, 1): its input is relu(x * scale + shift)), both with deferred weight gradient."""
+    geom, defer = (L.N, L.H, L.W, L.I, L.O, L.khs, L.kws, L.pts, L.pts, L.alpha), (seg, L.G, L.N, L.H, L.W, L.I, L.O, L.dtc, L.khs)
+    if L.dtc != F32S:
+        return _BwdPlan("hdmoe_conv_bwd6", L.dtc, policy, (seg, L.G, L.wdstride, *geom), (L.dtc,), defer, stats,
+                        lambda: L.record(seg, 2.0, name=kernel, dtype="bfloat16"), film)
+    return _BwdPlan("hdmoe_conv_bwd6s", F32S, policy, (seg, L.G, L.wdstride, L.G * L.wdstride, *geom), (*gn_in, 1 if TRUNK_BWD_BF16 else 0), defer, stats,
+                    lambda: L.record(seg, 2.0, name=kernel, dtype="bfloat16" if TRUNK_BWD_BF16 else "split_bf16"))
+
+
+def _conv_bwd_plan(L: _ConvLayer, seg, need_dx: bool, ones6: bool, device) -> Optional[_BwdPlan]:
+    """Which fused backward launch a weight-bank layer takes, if any.  (A launch outside its own domain returns non-zero: the layer then
+    takes the general path.)"""
+    same = not L.ones and L.Ho == L.H and L.Wo == L.W and L.Cphys == L.I
+    conv6 = need_dx and _prof_ok() and same and L.khs == L.kws
+    if conv6 and L.dtc == BF16 and set(L.khs) == {3, 5}:        # 3x3 / 5x5 expert layer
+        return _kxk_bwd_plan(L, seg, "arena", ("bwd6",), "bwd6_kernel", film=True)
+    if conv6 and L.split and set(L.khs) == {3}:                 # a router-trunk layer run on its own
+        return _kxk_bwd_plan(L, seg, "arena", ("bwd6s",), "bwd6s_kernel")
+    if ones6:   # the ones-channel layer: dgrad on conv6, weight gradient on wgrad6 + pixel sums of dy (csrc/ones6.hip), reduced inside the launch
+        def scratch():
+            S = torch.empty((L.G, L.H, L.W, L.O), dtype=torch.float32, device=device)
+            g32 = [_zeros((kh * kw, L.O, L.Cphys), torch.float32, device) for kh, kw in zip(L.khs, L.kws)]
+            return (S, g32, seg, L.G, L.wdstride, L.N, L.H, L.W, L.Cphys, L.O, L.Opad, L.khs, L.alpha)
+        return _BwdPlan("hdmoe_conv6_ones_bwd", L.dtc, "stream", scratch, (L.dtc,), None, (),
+                        lambda: L.record(seg, 2.0 if need_dx else 1.0, name="conv6 dgrad + wgrad6 (ones-channel layer)", dtype="bfloat16"))
+    if need_dx and _prof_ok() and same and L.dtc == BF16 and all(k == 1 for k in L.khs + L.kws):
+        # pointwise layer (linear / 1x1): one launch that reads dy once (csrc/pbwd.hip); no workspace, the weight gradient goes straight into the bank's slabs
+        return _BwdPlan("hdmoe_pw_bwd", L.dtc, None, (seg, L.G, L.wdstride, L.N, L.H * L.W, L.I, L.O, L.alpha), (L.dtc,), None, ("pbwd",),
+                        lambda: L.record(seg, 2.0, name="pw_bwd_kernel", dtype="bfloat16"))
+    return None
+
+
 def _fused_bwd(bank, ent, label, name, x, dy, wd, dx, mid, ws, tail, defer, stats) -> bool:
     """One launch for the input gradient (into ``dx``) and the weight gradient of weight-bank layer ``ent``:
     ``name(x, dy, wd, dx, ent.G, *mid, ws, ws bytes, *tail)``.  On success ``defer`` = (seg, G, N, H, W, I, O, dtype code, khs)
@@ -435,18 +501,23 @@ def _wgrad(x, dy, Gs, seg, G, N, H, W, Ho, Wo, I, Cphys, O, ones, khs, kws, pts,
     _timed("conv_wgrad", rec(), "hdmoe_conv_wgrad", x, dy, Gs, seg, G, N, H, W, Ho, Wo, I, Cphys, O, 1, 1 if ones else 0, khs, kws, pts, pts, _dt(x))
 
 
+# The non-tensor argument of _MPConvFn.apply, what ops._mp_conv was asked for.  out: the output, already written by a fused launch (the
+# forward then launches nothing for the conv); film: a _FilmReq -- film_silu of the output is wanted as a second output of the conv launch.
+_ConvCall = _collections.namedtuple("_ConvCall", "G gain_val alpha beta ones training normalize split res_raw out film")
+
+
 class _MPConvFn(torch.autograd.Function):
     """y = alpha * conv(x, prep(w)) + beta * res.   x: (N, H, W, Cphys).
     ``tensors`` = G weights followed by 0 or G learnable gain scalars (one per group)."""
 
     @staticmethod
-    def forward(ctx, x, res, seg, meta, *tensors):
-        (G, gain_val, alpha, beta, ones, training, normalize, split, res_raw) = meta
+    def forward(ctx, x, res, seg, c: _ConvCall, *tensors):
+        G, gain_val, alpha, beta, ones, training, normalize, split = c.G, c.gain_val, c.alpha, c.beta, c.ones, c.training, c.normalize, c.split
         weights, gains = tensors[:G], list(tensors[G:]) or None
         # the input is the output of a FiLM pass (ops._FilmRec): this layer's backward may run the FiLM backward in its dgrad epilogue
         ctx.film = getattr(x, "_film_rec", None) if FILM_DGRAD and x.is_contiguous() else None
         if ctx.film is not None:
-            ctx.film.taken += 1
+            ctx.film.register()
         x = _c(x)
         N, H, W, Cphys = x.shape
         O, I = int(weights[0].shape[0]), int(weights[0].shape[1])
@@ -468,6 +539,8 @@ class _MPConvFn(torch.autograd.Function):
         wstride, wdstride = taps * O * Ipad, taps * I * Opad
         # split: fp32 tensors, split-bf16 arithmetic (csrc/conv6s.hip) -- weight images are bf16 [hi | lo] planes, dtype code 2
         wdt, planes, dtc = (torch.bfloat16, 2, F32S) if split else (x.dtype, 1, _dt(x))
+        L = ctx.layer = _ConvLayer(G, N, H, W, Ho, Wo, Cphys, I, O, Ipad, Opad, khs, kws, pts, wstride, wdstride, dtc, gain_val, alpha, beta, ones,
+                               normalize, split, c.res_raw, res is not None)
         ent = None
         if _bank.ACTIVE is not None and gains is None:
             ent = _bank.ACTIVE.lookup(weights, "split" if split else x.dtype, gain_val, alpha, normalize)
@@ -481,153 +554,115 @@ class _MPConvFn(torch.autograd.Function):
                  1 if normalize else 0, 1 if training else 0, 1, dtc)
             if training and normalize:                         # the train-mode forward re-normalises the stored weights in place (raw pointers:
                 _bank.note_weights_changed()                   #  Tensor._version stays) -- eval-mode images prepared earlier are stale
-        ctx.wd = wd
-        ctx.ent = ent
-        ctx.bank = _bank.ACTIVE if ent is not None else None
-        global _PRECOMP
-        pre, _PRECOMP = _PRECOMP, None
-        y = pre if pre is not None else torch.empty((N, Ho, Wo, O), dtype=x.dtype, device=x.device)
-        req = _FILM_REQ
-        fused_film = pre is not None                          # (output already computed by the fused block kernel, ops.unet_block_fused)
+        ctx.wd, ctx.ent, ctx.bank = wd, ent, (_bank.ACTIVE if ent is not None else None)
+        # the bf16 same-size bank layers without residual: the domain the two special forward launches share
+        bank16 = c.out is None and ent is not None and not split and res is None and x.dtype == torch.bfloat16 and Ho == H and Wo == W
+        ones_dom = bank16 and ones and ONES6 and _prof_ok() and khs == kws
+        film_dom = bank16 and c.film is not None and not ones and PROFILE is None and Cphys == I
+        y = c.out if c.out is not None else torch.empty((N, Ho, Wo, O), dtype=x.dtype, device=x.device)
+        gb = torch.empty((G, H, W, O), dtype=torch.float32, device=x.device) if ones_dom else None
+        hbuf = torch.empty_like(y) if film_dom else None
         ctx.ones6 = False
-        if (ones and ONES6 and pre is None and ent is not None and not split and res is None and x.dtype == torch.bfloat16 and _prof_ok()
-                and Ho == H and Wo == W and khs == kws):
+        if c.out is not None:
+            pass                                              # handed in by the fused block launch (ops.unet_block_fused): nothing to launch
+        elif ones_dom and _timed("fused", lambda: L.record(seg, 1.0, name="conv6_bf16_kernel (ones-channel layer)", dtype="bfloat16"),
+                                 "hdmoe_conv6_ones_fwd", x, wf, y, gb, alpha, seg, G, wstride, N, H, W, Cphys, O, Ipad, khs, dtc) == 0:
             # torch.cat([x, ones]) (reference model_components.py:416): the 32 real channels on conv6, the ones channel as a bias map (csrc/ones6.hip)
-            gb = torch.empty((G, H, W, O), dtype=torch.float32, device=x.device)
-            if _timed("fused", dict(name="conv6_bf16_kernel (ones-channel layer)", dtype="bfloat16", seg=seg, N=N, HW=H * W, O=O, I=Cphys, taps=[a * b for a, b in zip(khs, kws)], mult=1.0),
-                      "hdmoe_conv6_ones_fwd", x, wf, y, gb, alpha, seg, G, wstride, N, H, W, Cphys, O, Ipad, khs, dtc) == 0:
-                fused_film = True
-                ctx.ones6 = True
-                STATS["ones6"] += 1
-        if (pre is None and req is not None and ent is not None and not split and res is None and not ones and x.dtype == torch.bfloat16 and PROFILE is None
-                and Ho == H and Wo == W and Cphys == I):
+            ctx.ones6 = True
+            STATS["ones6"] += 1
+        elif film_dom and call("hdmoe_conv_fwd_film", x, wf, y, hbuf, c.film.emb, c.film.seed, step_counter(x.device), c.film.p, alpha, seg, G, wstride,
+                               N, H, W, I, O, khs, kws, pts, pts, dtc) == 0:
             # FiLM + mp_silu + dropout as a second output of this conv's epilogue (ops.mp_conv_film): one launch less on the branch's chain
-            hbuf = torch.empty_like(y)
-            if call("hdmoe_conv_fwd_film", x, wf, y, hbuf, req.emb, req.seed, step_counter(x.device), req.p, alpha, seg, G, wstride, N, H, W, I, O,
-                    khs, kws, pts, pts, dtc) == 0:
-                req.h = hbuf
-                fused_film = True
-        if not fused_film:
+            c.film.h = hbuf
+        else:                                                 # (also a layer that one of the two launches above declined: nothing was launched)
             args = (x, wf, y, _c(res), alpha, beta,
                     seg, G, wstride, N, H, W, Ho, Wo, I, Cphys, Ipad, O, O, 1, 1 if ones else 0, khs, kws, pts, pts, dtc)
             _timed("conv_fwd", lambda: _fwd_record(*args), "hdmoe_conv_fwd", *args)
         ctx.save_for_backward(x, seg, *tensors)
-        ctx.meta = (G, gain_val, alpha, beta, ones, normalize, khs, kws, pts, Ho, Wo, res is not None, split, res_raw)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, seg, *tensors = ctx.saved_tensors
-        G, gain_val, alpha, beta, ones, normalize, khs, kws, pts, Ho, Wo, has_res, split, res_raw = ctx.meta
-        weights, gains = tensors[:G], list(tensors[G:]) or None
+        L, nig = ctx.layer, ctx.needs_input_grad
+        weights, gains = tensors[:L.G], list(tensors[L.G:]) or None
         dy = _c(dy)
-        N, H, W, Cphys = x.shape
-        O, I = int(weights[0].shape[0]), int(weights[0].shape[1])
-        dt = x.dtype
-        dx = dres = None
-        nig = ctx.needs_input_grad
-        need_gain = gains is not None and any(nig[4 + G + g] for g in range(G))
-        need_w = any(nig[4 + g] for g in range(G)) or need_gain
-        Opad = (O + 15) // 16 * 16
-        wdstride = max(a * b for a, b in zip(khs, kws)) * I * Opad
-        ent, fused = ctx.ent, False
-        if need_w and ent is not None:
-            # the input gradient and the weight gradient of a weight-bank layer in one launch (a launch outside its domain returns non-zero:
-            # the layer then takes the general path below)
-            conv6 = nig[0] and _prof_ok() and not ones and Ho == H and Wo == W and Cphys == I and khs == kws
-            if conv6 and not split and x.dtype == torch.bfloat16 and set(khs) == {3, 5}:
-                fast, dtc, policy = "bwd6", _dt(x), "arena"           # 3x3 / 5x5 expert layer, deferred weight gradient (csrc/bwd6.hip)
-            elif conv6 and split and set(khs) == {3}:
-                fast, dtc, policy = "bwd6s", F32S, "arena"            # the same for a router-trunk layer (fp32 tensors, split-bf16 arithmetic)
-            elif ctx.ones6:
-                # the ones-channel layer: dgrad on conv6, weight gradient on wgrad6 + pixel sums of dy (csrc/ones6.hip)
-                fast, dtc, policy = "ones6", _dt(x), "stream"
-            else:
-                fast = None
-            ws = _w6_workspace(policy, x.device, _w6_kib(G, N, H, W, Cphys, O, khs, kws, dtc)) if fast else None
-            if ws is not None:
-                info = dict(seg=seg, N=N, HW=H * W, O=O, I=Cphys, taps=[a * b for a, b in zip(khs, kws)], mult=2.0 if nig[0] else 1.0)
-                defer, stats = (seg, G, N, H, W, I, O, dtc, khs), (fast,)
-                if fast == "bwd6":
-                    label = dict(name="bwd6_kernel", dtype="bfloat16", **info)
-                    name, mid, tail = "hdmoe_conv_bwd6", (seg, G, wdstride, N, H, W, I, O, khs, kws, pts, pts, alpha), (dtc,)
-                elif fast == "bwd6s":
-                    label = dict(name="bwd6s_kernel", dtype="bfloat16" if TRUNK_BWD_BF16 else "split_bf16", **info)
-                    name, mid = "hdmoe_conv_bwd6s", (seg, G, wdstride, G * wdstride, N, H, W, I, O, khs, kws, pts, pts, alpha)
-                    tail = (None, None, 0, 1 if TRUNK_BWD_BF16 else 0)
-                else:
-                    label = dict(name="conv6 dgrad + wgrad6 (ones-channel layer)", dtype="bfloat16", **info)
-                    S = torch.empty((G, H, W, O), dtype=torch.float32, device=x.device)
-                    g32 = [_zeros((kh * kw, O, Cphys), torch.float32, x.device) for kh, kw in zip(khs, kws)]
-                    name, mid, tail = "hdmoe_conv6_ones_bwd", (S, g32, seg, G, wdstride, N, H, W, Cphys, O, Opad, khs, alpha), (dtc,)
-                    defer, stats = None, ()                   # (reduced inside the launch, into the bank's slabs)
-                dxo = torch.empty_like(x) if nig[0] else None
-                rec = ctx.film
-                if rec is not None:
-                    # (a pass that ended before the FiLM node, e.g. autograd.grad(inputs=h), leaves its hand-off behind: every pass starts clean)
-                    rec.consumed, rec.du, rec.de = False, None, None
-                if (fast == "bwd6" and rec is not None and FILM_DGRAD and nig[0] and rec.taken == 1
-                        and rec.u.shape == x.shape and rec.u.dtype == x.dtype):
-                    # dx of this launch is then du of the FiLM pass, de its embedding gradient (csrc/conv7_body.h, EPI = 1); outside the
-                    # epilogue's domain the entry returns non-zero without launching and the layer takes the plain launch below
-                    de = torch.empty(rec.e.shape, dtype=torch.float32, device=x.device)
-                    fused = _fused_bwd(ctx.bank, ent, dict(label, name="bwd7_kernel (FiLM epilogue)"), "hdmoe_conv_bwd6_film", x, dy, ctx.wd, dxo, mid, ws,
-                                       (rec.u, rec.e, rec.mask, de, rec.p, dtc), defer, stats)
-                    if fused:
-                        rec.consumed, rec.du, rec.de = True, dxo, de
-                        STATS["film_dgrad"] += 1
-                if not fused:
-                    fused = _fused_bwd(ctx.bank, ent, label, name, x, dy, ctx.wd, dxo, mid, ws, tail, defer, stats)
-                dx = dxo if fused else None
-            elif (fast is None and nig[0] and _prof_ok() and not ones and not split and x.dtype == torch.bfloat16 and Cphys == I
-                  and Ho == H and Wo == W and all(k == 1 for k in khs) and all(k == 1 for k in kws)):
-                # pointwise layer (linear / 1x1): both gradients in one launch that reads dy once (csrc/pbwd.hip); no workspace,
-                # the weight gradient goes straight into the bank's slabs
-                label = dict(name="pw_bwd_kernel", dtype="bfloat16", seg=seg, N=N, HW=H * W, O=O, I=I, taps=[1] * G, mult=2.0)
-                dxo = torch.empty_like(x)
-                fused = _fused_bwd(ctx.bank, ent, label, "hdmoe_pw_bwd", x, dy, ctx.wd, dxo,
-                                   (seg, G, wdstride, N, H * W, I, O, alpha), None, (_dt(x),), None, ("pbwd",))
-                dx = dxo if fused else None
+        need_gain = gains is not None and any(nig[4 + L.G:])
+        need_w = any(nig[4:4 + L.G]) or need_gain
+        fused, dx = _conv_fused_bwd(ctx, L, x, dy, seg, nig[0]) if need_w and ctx.ent is not None else (False, None)
         if nig[0] and not fused:
-            wd = ctx.wd
-            dx = torch.empty_like(x)
-            pt_d = [kh - 1 - p for kh, p in zip(khs, pts)]
-            pl_d = [kw - 1 - p for kw, p in zip(kws, pts)]
-            # dgrad: conv over dy (O channels) with the flipped kernel; logical out channels I, stored Cphys
-            args = (dy, wd, dx, None, alpha, 0.0,
-                    seg, G, wdstride, N, Ho, Wo, H, W, O, O, Opad, I, Cphys, 1, 0, khs, kws, pt_d, pl_d, F32S if split else _dt(x))
-            _timed("conv_fwd", lambda: _fwd_record(*args), "hdmoe_conv_fwd", *args)
-        if has_res and nig[1]:
-            if res_raw or beta == 1.0:
+            dx = _conv_dgrad(L, x, dy, ctx.wd, seg)
+        dres = None
+        if L.has_res and nig[1]:
+            if L.res_raw or L.beta == 1.0:
                 dres = dy                                     # beta == 1, or the producer of `res` applies beta in its own backward pass
             else:
                 dres = torch.empty_like(dy)
-                call("hdmoe_axpby", dres, dy, None, beta, 0.0, dy.numel(), _dt(dy))
-        dws: List[Optional[Tensor]] = [None] * G
-        dgs: List[Optional[Tensor]] = [None] * (len(tensors) - G)
-        if fused:
-            pass
-        elif need_w and ctx.ent is not None:
-            # bank path: accumulate into the bank's slab; one multi-tensor launch at the end of backward finishes every gradient
-            _wgrad(x, dy, ctx.ent.G, seg, G, N, H, W, Ho, Wo, I, Cphys, O, ones, khs, kws, pts, split, bank=ctx.bank)
-            ctx.bank.note_backward(ctx.ent)
-        elif need_w:
-            sizes = [khs[g] * kws[g] * O * I for g in range(G)]
-            Gflat = torch.zeros(sum(sizes), dtype=torch.float32, device=x.device)           # one memset for all groups
-            Gs, off = [], 0
-            for g in range(G):
-                Gs.append(Gflat[off:off + sizes[g]])
-                off += sizes[g]
-            _wgrad(x, dy, Gs, seg, G, N, H, W, Ho, Wo, I, Cphys, O, ones, khs, kws, pts, split)
-            dws = [torch.empty_like(w) for w in weights]
-            if need_gain:
-                dgs = [torch.zeros((), dtype=torch.float32, device=x.device) for _ in range(G)]
-            call("hdmoe_wprep_bwd", list(weights), gains, gain_val, Gs, dws, dgs if need_gain else None, khs, kws, G, O, I,
-                 1 if normalize else 0)
-            if alpha != 1.0:
-                for d in list(dws) + [d for d in dgs if d is not None]:
-                    call("hdmoe_axpby", d, d, None, alpha, 0.0, d.numel(), 0)
+                call("hdmoe_axpby", dres, dy, None, L.beta, 0.0, dy.numel(), _dt(dy))
+        dws, dgs = _conv_wgrad(ctx, L, x, dy, seg, weights, gains, need_gain) if need_w and not fused else ([None] * L.G, [None] * len(gains or ()))
         return (dx, dres, None, None, *dws, *dgs)
+
+
+def _conv_fused_bwd(ctx, L: _ConvLayer, x, dy, seg, need_dx: bool):
+    """The fused step of a weight-bank layer's backward -> (launched?, dx): input and weight gradient in one launch (ops._conv_bwd_plan); behind
+    a FiLM pass (ctx.film) first the launch that also runs the FiLM backward, in its dgrad epilogue."""
+    rec = ctx.film
+    if rec is not None:
+        rec.clear()
+    plan = _conv_bwd_plan(L, seg, need_dx, ctx.ones6, x.device)
+    ws = plan.workspace(L, x.device) if plan is not None and plan.policy is not None else None
+    if plan is None or (ws is None and plan.policy is not None):
+        return False, None
+    if callable(plan.mid):
+        plan = plan._replace(mid=plan.mid())
+    dx = torch.empty_like(x) if need_dx else None
+    fused = False
+    if plan.film and rec is not None and FILM_DGRAD and need_dx and rec.sole_consumer(x):
+        # dx of this launch is then du of the FiLM pass, de its embedding gradient (csrc/conv7_body.h, EPI = 1); outside the
+        # epilogue's domain the entry returns non-zero without launching and the layer takes the plain launch below
+        de = torch.empty(rec.e.shape, dtype=torch.float32, device=x.device)
+        fused = plan._replace(name="hdmoe_conv_bwd6_film", tail=(rec.u, rec.e, rec.mask, de, rec.p, plan.dtc),
+                              label=lambda: dict(plan.label(), name="bwd7_kernel (FiLM epilogue)")).launch(ctx.bank, ctx.ent, x, dy, dx, ws)
+        if fused:
+            rec.offer(dx, de)
+            STATS["film_dgrad"] += 1
+    fused = fused or plan.launch(ctx.bank, ctx.ent, x, dy, dx, ws)
+    return fused, dx if fused else None
+
+
+def _conv_dgrad(L: _ConvLayer, x, dy, wd, seg) -> Tensor:
+    """The input gradient on its own: conv over dy (O channels) with the flipped kernel; logical out channels I, stored Cphys."""
+    dx = torch.empty_like(x)
+    pt_d = [kh - 1 - p for kh, p in zip(L.khs, L.pts)]
+    pl_d = [kw - 1 - p for kw, p in zip(L.kws, L.pts)]
+    args = (dy, wd, dx, None, L.alpha, 0.0,
+            seg, L.G, L.wdstride, L.N, L.Ho, L.Wo, L.H, L.W, L.O, L.O, L.Opad, L.I, L.Cphys, 1, 0, L.khs, L.kws, pt_d, pl_d, L.dtc)
+    _timed("conv_fwd", lambda: _fwd_record(*args), "hdmoe_conv_fwd", *args)
+    return dx
+
+
+def _conv_wgrad(ctx, L: _ConvLayer, x, dy, seg, weights, gains, need_gain: bool):
+    """The weight gradient on its own -> (dws, dgs) for autograd.  A weight-bank layer accumulates into the bank's slabs (one multi-tensor
+    launch at the end of backward finishes every gradient) and hands autograd None."""
+    G, O, I = L.G, L.O, L.I
+    geom = (seg, G, L.N, L.H, L.W, L.Ho, L.Wo, I, L.Cphys, O, L.ones, L.khs, L.kws, L.pts, L.split)
+    dgs = [None] * len(gains or ())
+    if ctx.ent is not None:
+        _wgrad(x, dy, ctx.ent.G, *geom, bank=ctx.bank)
+        ctx.bank.note_backward(ctx.ent)
+        return [None] * G, dgs
+    sizes = [kh * kw * O * I for kh, kw in zip(L.khs, L.kws)]
+    Gs = list(torch.zeros(sum(sizes), dtype=torch.float32, device=x.device).split(sizes))       # one memset for all groups
+    _wgrad(x, dy, Gs, *geom)
+    dws = [torch.empty_like(w) for w in weights]
+    if need_gain:
+        dgs = [torch.zeros((), dtype=torch.float32, device=x.device) for _ in range(G)]
+    call("hdmoe_wprep_bwd", list(weights), gains, L.gain_val, Gs, dws, dgs if need_gain else None, L.khs, L.kws, G, O, I, 1 if L.normalize else 0)
+    if L.alpha != 1.0:
+        for d in dws + [d for d in dgs if d is not None]:
+            call("hdmoe_axpby", d, d, None, L.alpha, 0.0, d.numel(), 0)
+    return dws, dgs
+
 
 
 class _StridedConvFn(torch.autograd.Function):
@@ -676,10 +711,6 @@ def mp_conv_strided(x: Tensor, w: Tensor, gain: float, stride: int, training: bo
     return _StridedConvFn.apply(x, w, float(gain), int(stride), bool(training))
 
 
-_PRECOMP = None                           # output tensor a fused launch has already produced for the NEXT _MPConvFn.forward (ops.unet_block_fused)
-F32S = 2                                  # C-ABI dtype code: fp32 tensors, split-bf16 arithmetic (include/hdmoe.h HDMOE_F32S)
-
-
 def _split_ok(N: int, H: int, W: int, C: int, ws) -> bool:
     """Does the split-bf16 conv kernel (csrc/conv6s.hip) take the layer -- fp32 (N, H, W, C) input, weights ``ws``?  The library says (the
     route of an HDMOE_F32S call); asked ahead of the launch because the weight image format depends on the answer."""
@@ -699,6 +730,15 @@ def mp_conv(x: Tensor, weights, gain=1.0, *, seg: Optional[Tensor] = None, res: 
     ``x``: (N,H,W,C) -> (N,Ho,Wo,O);  (N,S,C) -> (N,S,O);  (M,C) -> (M,O).  ``weights``: a tensor, or a list of
     per-expert tensors together with ``seg`` (device int32 row offsets) for a grouped launch.
     ``gain``: python float, a 0-dim float32 tensor (learnable out_gain), or a list of such tensors (one per group)."""
+    return _mp_conv(x, weights, gain, seg=seg, res=res, alpha=alpha, beta=beta, ones=ones, training=training, normalize=normalize, split=split,
+                    res_grad_raw=res_grad_raw)
+
+
+def _mp_conv(x, weights, gain=1.0, *, seg=None, res=None, alpha=1.0, beta=0.0, ones=False, training=False, normalize=True, split=False,
+             res_grad_raw=False, out: Optional[Tensor] = None, film: Optional["_FilmReq"] = None) -> Tensor:
+    """ops.mp_conv, and how a fused launch hands its outputs to the unfused autograd graph: ``out`` is the (N, Ho, Wo, O) output a fused
+    launch has already written -- the forward launches nothing for the conv, the graph node and the saved tensors are as usual
+    (ops.unet_block_fused); ``film`` asks for film_silu of the output as a second output of the conv launch and receives it (ops.mp_conv_film)."""
     ws = f32_params(list(weights) if isinstance(weights, (list, tuple)) else [weights])
     G = len(ws)
     if isinstance(gain, (list, tuple)):
@@ -727,8 +767,8 @@ def mp_conv(x: Tensor, weights, gain=1.0, *, seg: Optional[Tensor] = None, res: 
     split = bool(split) and not ones and x4.dtype == torch.float32 and _split_ok(*x4.shape, ws)
     # res_grad_raw: the gradient handed back for `res` is dy itself, NOT beta * dy -- only for a `res` whose producer was created with
     # gx_scale = beta (ops.silu_branch / ops.pixel_norm_silu) and has no other consumer: saves a scaling pass per residual block
-    meta = (G, gain_val, float(alpha), float(beta), bool(ones), bool(training), bool(normalize), split, bool(res_grad_raw))
-    y = _MPConvFn.apply(x4, res, seg, meta, *ws, *gts)
+    c = _ConvCall(G, gain_val, float(alpha), float(beta), bool(ones), bool(training), bool(normalize), split, bool(res_grad_raw), out, film)
+    y = _MPConvFn.apply(x4, res, seg, c, *ws, *gts)
     return y.reshape(*shape[:-1], y.shape[-1])
 
 
@@ -1117,15 +1157,34 @@ def sigmoid(x: Tensor, a: float = 1.0) -> Tensor:
 
 class _FilmRec:
     """What the consumer of h = film_silu(u, e) needs to run the FiLM backward itself: the saved pre-activation, the embedding, the keep
-    bytes of the dropout (None: p == 0) -- attached to h as ``h._film_rec``.  A conv layer that reads h picks it up in its forward
-    (``taken``); in its backward the bwd7 launch writes du / de in its dgrad epilogue (``consumed``, ``du``, ``de``) and the FiLM node
-    hands them on without a launch.  h must feed that layer alone, as in Unet_block: the FiLM node checks that the gradient it receives is
-    the very tensor the conv wrote."""
-    __slots__ = ("u", "e", "mask", "p", "taken", "consumed", "du", "de")
+    bytes of the dropout (None: p == 0) -- attached to h as ``h._film_rec``.  A conv layer that reads h registers in its forward; in its
+    backward the bwd7 launch writes du / de in its dgrad epilogue and offers them, and the FiLM node claims them and hands them on without a
+    launch.  h must feed that layer alone, as in Unet_block: the FiLM node checks that the gradient it receives is the very tensor the
+    conv wrote."""
+    __slots__ = ("u", "e", "mask", "p", "taken", "_offer")
 
     def __init__(self, u, e, mask, p):
         self.u, self.e, self.mask, self.p = u, e, mask, p
-        self.taken, self.consumed, self.du, self.de = 0, False, None, None
+        self.taken, self._offer = 0, None
+
+    def register(self) -> None:                              # a conv layer's forward reads h
+        self.taken += 1
+
+    def sole_consumer(self, x: Tensor) -> bool:              # may the one registered layer, whose input is x, run the FiLM backward?
+        return self.taken == 1 and self.u.shape == x.shape and self.u.dtype == x.dtype
+
+    def clear(self) -> None:    # every backward pass starts clean: one that ended before the FiLM node (autograd.grad(inputs=h)) leaves its offer behind
+        self._offer = None
+
+    def offer(self, du: Tensor, de: Tensor) -> None:         # the conv layer's backward launch wrote them
+        self._offer = (du, de)
+
+    def claim(self, g: Tensor):
+        """The FiLM node's backward, handed ``g``: (du, de) of the consumer's launch -- g is then du -- or None: the node runs its own kernel."""
+        offer, self._offer = self._offer, None
+        if offer is not None and (g.data_ptr() != offer[0].data_ptr() or g.shape != offer[0].shape):
+            raise RuntimeError("film_silu: the output fed a second consumer beside the conv layer that fused its backward (set ops.FILM_DGRAD = False)")
+        return offer
 
 
 FILM_MASK = True                                        # False: the FiLM backward draws the dropout bits again instead of reading saved keep bytes
@@ -1166,13 +1225,9 @@ class _FilmSiluFn(torch.autograd.Function):
         u, e = ctx.saved_tensors
         p, seed = ctx.meta
         rec, mask = getattr(ctx, "rec", None), getattr(ctx, "mask", None)
-        if rec is not None and rec.consumed:
-            # the consumer's backward launch already applied this node's backward: g is du
-            du, de = rec.du, rec.de
-            rec.consumed, rec.du, rec.de = False, None, None
-            if du is None or g.data_ptr() != du.data_ptr() or g.shape != du.shape:
-                raise RuntimeError("film_silu: the output fed a second consumer beside the conv layer that fused its backward (set ops.FILM_DGRAD = False)")
-            return g, de, None, None
+        done = rec.claim(g) if rec is not None else None
+        if done is not None:                                  # the consumer's backward launch already applied this node's backward: g is du
+            return g, done[1], None, None
         g = _c(g)
         N, C = u.shape[0], u.shape[-1]
         HW = u.numel() // (N * C)
@@ -1188,14 +1243,14 @@ class _FilmSiluFn(torch.autograd.Function):
 
 
 class _FilmReq:
+    """ops.mp_conv_film's request to the conv (ops._mp_conv(film=...)): the FiLM operands in, ``h`` out when the conv launch took the epilogue."""
     __slots__ = ("emb", "p", "seed", "h")
 
     def __init__(self, emb, p, seed):
         self.emb, self.p, self.seed, self.h = emb, p, seed, None
 
 
-_FILM_REQ = None                                        # set around the mp_conv call of ops.mp_conv_film
-CONV_FILM = True                                        # False: always the separate FiLM pass
+CONV_FILM = True                                       # False: always the separate FiLM pass
 CONV_FILM_TRAIN = False                                 # True: the fused FiLM epilogue with dropout too
 
 
@@ -1220,7 +1275,6 @@ def mp_conv_film(x: Tensor, weights, gain, emb: Tensor, p: float, training: bool
     """film_silu(mp_conv(x, weights, gain), emb, p) -- conv_res1 of Unet_block followed by FiLM, mp_silu and dropout (reference
     model_components.py:240-246).  In the bf16 bank path the second step is an extra output of the conv kernel's epilogue.
     With ops.FILM_DGRAD the result may feed ONE conv layer and nothing else that needs its gradient (see ops.film_silu)."""
-    global _FILM_REQ
     p = float(p) if training else 0.0
     C = int((weights[0] if isinstance(weights, (list, tuple)) else weights).shape[0])
     # Only without dropout (eval / sampling), unless forced (CONV_FILM_TRAIN): drawing the Philox bits in the conv epilogue -- 8 waves per CU,
@@ -1230,11 +1284,7 @@ def mp_conv_film(x: Tensor, weights, gain, emb: Tensor, p: float, training: bool
     if not ok:
         return film_silu(mp_conv(x, weights, gain, seg=seg, training=training), emb, p, training)
     req = _FilmReq(_f32(emb), p, _next_seed() if p > 0.0 else 0)
-    _FILM_REQ = req
-    try:
-        y = mp_conv(x, weights, gain, seg=seg, training=training)
-    finally:
-        _FILM_REQ = None
+    y = _mp_conv(x, weights, gain, seg=seg, training=training, film=req)
     if req.h is not None:
         return _FilmDoneFn.apply(y, req.emb, p, req.seed, req.h)
     return _FilmSiluFn.apply(y, req.emb, p, req.seed)
@@ -1258,7 +1308,6 @@ def unet_block_fused(h: Tensor, res: Optional[Tensor], w1s, w2s, gain1: float, g
     Returns None when the fused kernel does not apply (no ready weight-bank entries, fp32 mode, shapes outside its domain): the caller
     then runs the layers one by one.  The autograd graph is the unfused one (conv -> FiLM -> conv nodes over the tensors the fused
     launch wrote), so the backward is unchanged."""
-    global _PRECOMP
     w1s, w2s = list(w1s), list(w2s)
     if not (BLK6 and _bank.ACTIVE is not None and _prof_ok() and h.dtype == torch.bfloat16 and h.ndim == 4 and h.is_cuda):
         return None
@@ -1294,14 +1343,9 @@ def unet_block_fused(h: Tensor, res: Optional[Tensor], w1s, w2s, gain1: float, g
         return y
     ws1 = w1s if seg is not None else w1s[0]
     ws2 = w2s if seg is not None else w2s[0]
-    try:
-        _PRECOMP = u
-        uu = mp_conv(h, ws1, gain1, seg=seg, training=training)
-        hh = _FilmDoneFn.apply(uu, e32, p, seed, hb)
-        _PRECOMP = y
-        return mp_conv(hh, ws2, gain2, seg=seg, res=res, alpha=alpha, beta=beta, training=training, res_grad_raw=res_grad_raw)
-    finally:
-        _PRECOMP = None
+    uu = _mp_conv(h, ws1, gain1, seg=seg, training=training, out=u)
+    hh = _FilmDoneFn.apply(uu, e32, p, seed, hb)
+    return _mp_conv(hh, ws2, gain2, seg=seg, res=res, alpha=alpha, beta=beta, training=training, res_grad_raw=res_grad_raw, out=y)
 
 
 def film_silu(u: Tensor, e: Tensor, p: float = 0.0, training: bool = False) -> Tensor:
@@ -2354,7 +2398,6 @@ class _TrunkFn(torch.autograd.Function):
             ent = ents[l]
             xin = x if l == 0 else saved[5 * (l - 1)]
             isc, ish = (None, None) if l == 0 else (saved[5 * (l - 1) + 1], saved[5 * (l - 1) + 2])
-            wdstride = 9 * I * ((O + 15) // 16 * 16)
             if use7:
                 # GroupNorm + ReLU backward -> dy_l and relu(gn(y_{l-1})) -> the conv input, both bf16, in one launch (csrc/norm.hip
                 # gn1t_apply_kernel); its sums come from a statistics launch over (y_l, da), or for the pooled last layer from the forward's
@@ -2368,11 +2411,11 @@ class _TrunkFn(torch.autograd.Function):
                 call("hdmoe_gn1t_apply", dyb, a_in, bufs[2 * l], bufs[2 * l + 1], stw, None if l == 2 else da, _f32(g) if l == 2 else None,
                      1.0 / S if l == 2 else 1.0, pcnt if l == 2 else None, qsum if l == 2 else None, y, gamma, beta, mean, rstd,
                      xin, isc, ish, N, S, O, I)
-                arena = _w6_workspace("own", x.device, _w6_kib(1, N, H, W, I, O, [3], [3], 1))
+                L = _ConvLayer.of_entry(ent, N, H, W, BF16)
+                plan = _kxk_bwd_plan(L, None, "own", ("trunk_bwd", "trunk_bwd7"), "bwd7_trunk_kernel")
+                arena = plan.workspace(L, x.device)
                 da = torch.empty(xin.shape, dtype=torch.bfloat16, device=x.device)
-                if not _fused_bwd(bank, ent, dict(name="bwd7_trunk_kernel", dtype="bfloat16", seg=None, N=N, HW=S, O=O, I=I, taps=[9], mult=2.0),
-                                  "hdmoe_conv_bwd6", a_in, dyb, ent.wd, da, (None, 1, wdstride, N, H, W, I, O, [3], [3], [1], [1], 1.0), arena, (1,),
-                                  (None, 1, N, H, W, I, O, 1, [3]), ("trunk_bwd", "trunk_bwd7")):
+                if not plan.launch(bank, ent, a_in, dyb, da, arena):
                     raise RuntimeError("router trunk backward: layer outside the streaming backward kernels' domain")
                 if l == 0:                                     # the stem features are fp32: so is their gradient
                     da32 = torch.empty(xin.shape, dtype=torch.float32, device=x.device)
@@ -2385,11 +2428,11 @@ class _TrunkFn(torch.autograd.Function):
                 call("hdmoe_groupnorm_bwd_bcast", dy, bufs[2 * l], bufs[2 * l + 1], ws, _f32(g), 1.0 / S, y, gamma, beta, mean, rstd, N, S, O, 1, ACT_RELU, 0)
             else:
                 call("hdmoe_groupnorm_bwd", dy, bufs[2 * l], bufs[2 * l + 1], ws, da, y, gamma, beta, mean, rstd, N, S, O, 1, ACT_RELU, 0)
-            arena = _w6_workspace("own", x.device, _w6_kib(1, N, H, W, I, O, [3], [3], F32S))
+            L = _ConvLayer.of_entry(ent, N, H, W, F32S)
+            plan = _kxk_bwd_plan(L, None, "own", ("trunk_bwd",), "bwd6s_kernel", gn_in=(isc, ish, 1))
+            arena = plan.workspace(L, x.device)
             da = torch.empty_like(xin)
-            if not _fused_bwd(bank, ent, dict(name="bwd6s_kernel", dtype="bfloat16" if TRUNK_BWD_BF16 else "split_bf16", seg=None, N=N, HW=S, O=O, I=I, taps=[9], mult=2.0),
-                              "hdmoe_conv_bwd6s", xin, dy, ent.wd, da, (None, 1, wdstride, wdstride, N, H, W, I, O, [3], [3], [1], [1], 1.0), arena,
-                              (isc, ish, 1, 1 if TRUNK_BWD_BF16 else 0), (None, 1, N, H, W, I, O, F32S, [3]), ("trunk_bwd",)):
+            if not plan.launch(bank, ent, xin, dy, da, arena):
                 raise RuntimeError("router trunk backward: layer outside the fused backward kernel's domain")
         out = [da, None, None, None, None]
         for l in range(3):
