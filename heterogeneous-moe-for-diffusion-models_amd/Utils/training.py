@@ -118,13 +118,31 @@ class Trainer:
     ``evaluator=Utils.evaluation.Evaluator(...), eval_every=n``: behind the update of every n-th step the trainer runs the held-out
     evaluation -- on the raw weights and, when the evaluator was built with this trainer's ``ema``, on each EMA profile -- keeps the
     numbers in ``last_eval`` and hands them to the logger's ``log_evaluation``.  The evaluation leaves the training state untouched.
-    With both at their defaults nothing changes."""
+    With both at their defaults nothing changes.
+
+    ``skip_nonfinite=True`` (needs ``fuse_clip_into_step``): the guard every mixed-precision trainer has, without a host sync.  Behind
+    the gradient all-reduce one statistics pass (`hdmoe_hip.optim.GradHealth`, in place of the clip's norm pass: the same number of
+    launches) measures the gradients; clip + AdamW and the EMA then run behind its device verdict.  A step whose gradients hold a NaN or
+    an Inf, or whose squared norm overflows, is skipped: parameters, both moments, the per-tensor step counts, every EMA profile and the
+    EMA step stay bit for bit what they were.  ``step_idx``, the LR scheduler and the zeta and mask schedules still advance -- they follow
+    the data, and a rejected batch must not be drawn again -- and an EMA snapshot or an evaluation due on that step still runs.  A step
+    with a good verdict is the unguarded step bit for bit.  The result gains ``"step_ok"`` (device int32, 1 = applied) and
+    ``"grad_norm"`` (device float32, over the finite elements); nobody reads them here, so nothing syncs.  Under data parallelism the
+    gradients are all-reduced before they are measured, so every rank reaches the same verdict.
+
+    ``health_every=n``: behind the update of every n-th step the parameters are measured as well and everything is read with one
+    device-to-host copy into ``last_health`` (per-group norm / absmax / non-finite counts of gradients and weights, groups as in
+    `hdmoe_hip.optim.health_groups`, and the skip counters) and handed to the logger's ``log_health``.  A non-finite parameter raises
+    RuntimeError, and so does ``max_skips_in_a_row=m`` (needs both other keywords; the counters are only seen when they are read) once m
+    steps in a row were skipped.  Without ``skip_nonfinite`` the gradients are measured on those steps only and the update is the plain
+    one: this mode only observes.  ``health()`` does the same read on demand.  With all three at their defaults nothing changes."""
 
     def __init__(self, model, model_config, optim_config, loss_config, mask_config, zeta_config, max_grad_norm: float = 1.0,
                  fuse_clip_into_step: bool = True, logger=None, ema=None, ema_snapshot_every: Optional[int] = None,
                  ema_snapshot_dir: Optional[str] = None, device_inputs: bool = False, graphed: bool = False, seed: Optional[int] = None,
                  cond_dropout: float = 0.0, null_text_emb: Optional[torch.Tensor] = None, dataset: Optional[LatentDataset] = None,
-                 batch_size: Optional[int] = None, evaluator=None, eval_every: Optional[int] = None):
+                 batch_size: Optional[int] = None, evaluator=None, eval_every: Optional[int] = None, skip_nonfinite: bool = False,
+                 health_every: Optional[int] = None, max_skips_in_a_row: Optional[int] = None):
         dist = torch.distributed.is_available() and torch.distributed.is_initialized()
         self.world, self.rank = (torch.distributed.get_world_size(), torch.distributed.get_rank()) if dist else (1, 0)
         if dataset is None:
@@ -160,6 +178,19 @@ class Trainer:
         # every `eval_every` steps, behind the update: evaluator.evaluate() on the raw weights and, when the evaluator holds this
         # trainer's ema, on each of its profiles -> last_eval, and the logger's <run>_validation.jsonl
         self.evaluator, self.eval_every, self.last_eval = evaluator, eval_every, None
+        if not isinstance(skip_nonfinite, bool):
+            raise ValueError(f"Trainer: skip_nonfinite is a bool, got {skip_nonfinite!r}")
+        if skip_nonfinite and not fuse_clip_into_step:
+            raise ValueError("Trainer: skip_nonfinite needs fuse_clip_into_step (the verdict guards the fused clip + AdamW launch)")
+        for key, val in (("health_every", health_every), ("max_skips_in_a_row", max_skips_in_a_row)):
+            if val is not None and (isinstance(val, bool) or not isinstance(val, int) or val < 1):
+                raise ValueError(f"Trainer: {key} must be an int >= 1, got {val!r}")
+        if max_skips_in_a_row is not None and (not skip_nonfinite or health_every is None):
+            raise ValueError("Trainer: max_skips_in_a_row needs skip_nonfinite and a health_every (the counters are only seen when read)")
+        # skip_nonfinite: every step's update runs behind the device verdict of one statistics pass over the gradients; health_every: that
+        # pass's rows (and the parameters') are read every n-th step -> last_health, the logger's <run>_health.jsonl
+        self.skip_nonfinite, self.health_every, self.max_skips_in_a_row = skip_nonfinite, health_every, max_skips_in_a_row
+        self.last_health, self._health = None, None
         if not 0.0 <= float(cond_dropout) <= 1.0:            # NaN fails both comparisons
             raise ValueError(f"Trainer: cond_dropout must lie in [0, 1], got {cond_dropout}")
         if null_text_emb is not None and not torch.is_tensor(null_text_emb):
@@ -354,29 +385,76 @@ class Trainer:
     def _update(self, step: int, loss: dict, out_model: dict, sigma: torch.Tensor, keep: Optional[torch.Tensor] = None) -> dict:
         """Everything behind the backward, in the reference's order: gradient logs, clip + AdamW, EMA, scheduler."""
         lg = self.logger
+        health_due = self.health_every is not None and (step + 1) % self.health_every == 0
+        health = self._grad_health() if self.skip_nonfinite or health_due else None
+        if health is not None:                               # in place of the clip's norm pass when the update is guarded
+            health.measure(step, which="grad", verdict=self.skip_nonfinite)
         if lg is not None:
             lg.log_gradients(step=step, model=self.model.net)
             lg.log_weight_statistics(step=step, model=self.model.net)
         from hdmoe_hip.optim import clip_grad_norm_
-        if self.fuse:
+        if self.skip_nonfinite:
+            self.optimizer.step(clip=(self._clip_params, self.max_grad_norm), health=health)
+        elif self.fuse:
             self.optimizer.step(clip=(self._clip_params, self.max_grad_norm))
         else:
             clip_grad_norm_(self._clip_params, self.max_grad_norm)
             self.optimizer.step()
         if self.ema is not None:
-            self.ema.update()
+            if self.skip_nonfinite:
+                self.ema.update(ok=health.ok)
+            else:
+                self.ema.update()
             if self.ema_snapshot_every is not None and (step + 1) % self.ema_snapshot_every == 0:
                 self._save_ema_snapshot(step + 1)
         self.scheduler.step()
         self.step_idx += 1
+        if health_due:
+            self._check_health(step, self._read_health())
         if self.eval_every is not None and (step + 1) % self.eval_every == 0:
             self._evaluate(step + 1)
         res = {"loss": loss, "out_model": out_model, "sigma": sigma}
+        if self.skip_nonfinite:                              # device values, read by nobody here: no sync
+            res["step_ok"], res["grad_norm"] = health.ok[0], torch.sqrt(health.total_sumsq)[0]
         if keep is not None:
             res["text_keep"] = keep
         if self.dataset is not None:
             res["item"], res["flip"] = self.inputs.data_buf["item"], self.inputs.data_buf["flip"]
         return res
+
+    def _grad_health(self):
+        """The statistics object over the clip's parameter list, built at the first use (the gradients exist by then)."""
+        if self._health is None:
+            from hdmoe_hip.optim import GradHealth, health_groups
+            names, group_of = health_groups(self.model)
+            self._health = GradHealth(self._clip_params, group_of, names)
+        return self._health
+
+    def _read_health(self) -> dict:
+        """Measure the parameters (no verdict) and fetch every row and counter with one copy (it syncs) -> last_health."""
+        h = self._grad_health()
+        h.measure(self.step_idx, which="param", verdict=False)
+        self.last_health = h.read()
+        return self.last_health
+
+    def health(self) -> dict:
+        """`GradHealth.read()`'s dictionary on demand (it syncs): the gradient rows of the last measured step -- without
+        ``skip_nonfinite`` they are measured now, from the gradients the last step left --, the parameter rows as of now, the last
+        verdict and the skip counters.  Also kept in ``last_health``."""
+        if not self.skip_nonfinite:
+            self._grad_health().measure(max(self.step_idx - 1, 0), which="grad", verdict=False)
+        return self._read_health()
+
+    def _check_health(self, step: int, h: dict) -> None:
+        if self.logger is not None and callable(getattr(self.logger, "log_health", None)):
+            self.logger.log_health(step, h, h["groups"])
+        if h["param"]["total"]["nonfinite"] > 0:
+            bad = [n for n, c in zip(h["groups"], h["param"]["nonfinite"]) if c > 0]
+            raise RuntimeError(f"Trainer: non-finite parameters behind step {step} in {bad} "
+                               f"({h['param']['total']['nonfinite']} elements); the last good state is the last checkpoint")
+        if self.max_skips_in_a_row is not None and h["skipped_in_a_row"] >= self.max_skips_in_a_row:
+            raise RuntimeError(f"Trainer: {h['skipped_in_a_row']} steps in a row had non-finite gradients and were skipped "
+                               f"(max_skips_in_a_row={self.max_skips_in_a_row}); the last one was step {h['last_skipped_step']}")
 
     def _evaluate(self, step: int) -> None:
         """The held-out numbers after `step` updates (it syncs: one host copy per evaluation): last_eval = {"step", "results": {tag:

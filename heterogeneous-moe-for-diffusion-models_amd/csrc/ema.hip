@@ -19,7 +19,11 @@ constexpr int EMA_VEC_PER_THREAD = EMA_CHUNK / 4 / 256;    // float4 per thread 
 
 // The step count lives in device memory (int64: exact for ever, unlike a float counter) and is advanced in front of the update, so a
 // captured graph replays with the right decay for every step.
-__global__ void mt_ema_step_kernel(long long* step) { *step += 1; }
+// `ok` (hdmoe_mt_ema_ok; NULL = unguarded): a device verdict of hdmoe_mt_stats.  0 leaves the counter and every profile as they are.
+__global__ void mt_ema_step_kernel(long long* step, const int* ok) {
+  if (ok && !*ok) return;
+  *step += 1;
+}
 
 // a = 1 - beta(t).  Power profile: beta(t) = (1 - 1/t)^(gamma + 1); 1 - beta through expm1 / log1p keeps full precision when beta -> 1.
 DEVI float ema_weight(double coef, long long t, int mode) {
@@ -32,7 +36,8 @@ DEVI float ema_lerp(float p, float e, float a) { return a == 1.f ? p : fmaf(a, p
 
 template <int K>
 __global__ __launch_bounds__(256) void mt_ema_kernel(const EmaDesc* descs, const int2* chunks, const long long* step, const double* coefs,
-                                                     int mode) {
+                                                     int mode, const int* ok) {
+  if (ok && !*ok) return;                          // (block-uniform: in front of the barrier below)
   __shared__ float sa[EMA_MAX_PROFILES];
   if (threadIdx.x < K) sa[threadIdx.x] = ema_weight(coefs[threadIdx.x], *step, mode);       // fp64, once per block
   __syncthreads();
@@ -227,22 +232,27 @@ int hdmoe_mt_combine(const void* src_table, const void* dst_table, int nsrc, int
 
 int hdmoe_ema_desc_bytes(void) { return (int)sizeof(EmaDesc); }
 
-int hdmoe_mt_ema(const void* descs, const int* chunks, int nchunks, int nprofiles, long long* step_counter, const double* gammas_or_betas,
-                 int mode, hipStream_t stream) {
+int hdmoe_mt_ema_ok(const void* descs, const int* chunks, int nchunks, int nprofiles, long long* step_counter, const double* gammas_or_betas,
+                    int mode, const int* ok, hipStream_t stream) {
   if (nprofiles < 1 || nprofiles > EMA_MAX_PROFILES || nchunks < 0) return HDMOE_EINVAL;
   if (mode != HDMOE_EMA_POWER && mode != HDMOE_EMA_CONSTANT) return HDMOE_EINVAL;
   if (nchunks == 0) return HDMOE_OK;
   if (!descs || !chunks || !step_counter || !gammas_or_betas) return HDMOE_EINVAL;
   const EmaDesc* d = (const EmaDesc*)descs;
   const int2* c = (const int2*)chunks;
-  hipLaunchKernelGGL(mt_ema_step_kernel, dim3(1), dim3(1), 0, stream, step_counter);
+  hipLaunchKernelGGL(mt_ema_step_kernel, dim3(1), dim3(1), 0, stream, step_counter, ok);
   switch (nprofiles) {
-    case 1: hipLaunchKernelGGL(mt_ema_kernel<1>, dim3(nchunks), dim3(256), 0, stream, d, c, step_counter, gammas_or_betas, mode); break;
-    case 2: hipLaunchKernelGGL(mt_ema_kernel<2>, dim3(nchunks), dim3(256), 0, stream, d, c, step_counter, gammas_or_betas, mode); break;
-    case 3: hipLaunchKernelGGL(mt_ema_kernel<3>, dim3(nchunks), dim3(256), 0, stream, d, c, step_counter, gammas_or_betas, mode); break;
-    default: hipLaunchKernelGGL(mt_ema_kernel<4>, dim3(nchunks), dim3(256), 0, stream, d, c, step_counter, gammas_or_betas, mode); break;
+    case 1: hipLaunchKernelGGL(mt_ema_kernel<1>, dim3(nchunks), dim3(256), 0, stream, d, c, step_counter, gammas_or_betas, mode, ok); break;
+    case 2: hipLaunchKernelGGL(mt_ema_kernel<2>, dim3(nchunks), dim3(256), 0, stream, d, c, step_counter, gammas_or_betas, mode, ok); break;
+    case 3: hipLaunchKernelGGL(mt_ema_kernel<3>, dim3(nchunks), dim3(256), 0, stream, d, c, step_counter, gammas_or_betas, mode, ok); break;
+    default: hipLaunchKernelGGL(mt_ema_kernel<4>, dim3(nchunks), dim3(256), 0, stream, d, c, step_counter, gammas_or_betas, mode, ok); break;
   }
   return hdmoe_launch_status();
+}
+
+int hdmoe_mt_ema(const void* descs, const int* chunks, int nchunks, int nprofiles, long long* step_counter, const double* gammas_or_betas,
+                 int mode, hipStream_t stream) {
+  return hdmoe_mt_ema_ok(descs, chunks, nchunks, nprofiles, step_counter, gammas_or_betas, mode, nullptr, stream);
 }
 
 int hdmoe_mt_swap(const void* descs, const int* chunks, int nchunks, int profile, hipStream_t stream) {

@@ -185,6 +185,33 @@ class Logger:
             record[key] = clean(np.asarray(result[key], dtype=np.float64).tolist())
         self._write_jsonl(self.log_dir / f"{self.run_name}_validation.jsonl", record)
 
+    HEALTH_COUNTERS = ("measured", "skipped", "skipped_in_a_row", "last_skipped_step")
+
+    def log_health(self, step: int, health: Dict[str, Any], names: List[str]):
+        """One record of `hdmoe_hip.optim.GradHealth.read` into <run>_health.jsonl: step, the verdict ``ok``, the four skip counters,
+        the total ``grad_norm``, ``groups`` (the names) and under ``per_group``, one list entry per group, grad_norm / grad_absmax /
+        grad_nonfinite and weight_rms / weight_absmax / weight_nonfinite.  `health` holds host values: no device work.  Non-finite floats (the rms of an
+        empty group) are written as null."""
+        def clean(v):
+            if isinstance(v, list):
+                return [clean(u) for u in v]
+            return None if isinstance(v, float) and not math.isfinite(v) else v
+
+        record = {"step": int(step), "ok": int(health["ok"])}
+        for key in self.HEALTH_COUNTERS:
+            record[key] = int(health[key])
+        record["grad_norm"] = clean(float(health["grad_norm"]))
+        record["groups"] = [str(n) for n in names]
+        grad, param = health["grad"], health["param"]
+        per = {}                                             # (its own level: "grad_norm" is also the total above)
+        for key, src in (("grad_norm", grad["norm"]), ("grad_absmax", grad["absmax"]), ("weight_rms", param["rms"]),
+                         ("weight_absmax", param["absmax"])):
+            per[key] = clean([float(v) for v in src])
+        per["grad_nonfinite"] = [int(v) for v in grad["nonfinite"]]
+        per["weight_nonfinite"] = [int(v) for v in param["nonfinite"]]
+        record["per_group"] = per
+        self._write_jsonl(self.log_dir / f"{self.run_name}_health.jsonl", record)
+
     # ------------------------------------------------------------------ reference logger.py:328-345
     def _flush_training_log(self):
         if len(self.accumulators["step"]) == 0:

@@ -209,13 +209,22 @@ class WeightEMA(_Profiles):
 
     # ---------------------------------------------------------------------------------------------------------------- update
     @torch.no_grad()
-    def update(self) -> None:
+    def update(self, ok: Optional[torch.Tensor] = None) -> None:
         """Advance the device step count and fold the current parameters into every profile: one launch on the current stream, no sync,
-        no allocation (capturable).  Every tracked tensor is updated, also those the optimizer skipped this step (see the class docstring)."""
+        no allocation (capturable).  Every tracked tensor is updated, also those the optimizer skipped this step (see the class docstring).
+
+        ``ok``: a device int32 verdict (`hdmoe_hip.optim.GradHealth.ok`).  Where it reads 0 the call writes nothing -- the step count
+        and every profile stay as they are, like the optimizer step that the same verdict rejected; where it reads non-zero the call is
+        the unguarded one bit for bit."""
         if self._swapped is not None:
             raise RuntimeError("WeightEMA.update() inside swapped(): the parameters currently hold an EMA profile")
+        if ok is not None and (not torch.is_tensor(ok) or ok.dtype != torch.int32 or ok.numel() < 1 or ok.device != self.device):
+            raise ValueError("WeightEMA.update: ok is an int32 tensor on the parameters' device")
         descs, chunks, n = self._table()
-        call("hdmoe_mt_ema", descs, chunks, n, self.nprofiles, self._step, self._coefs, self.mode)
+        if ok is None:
+            call("hdmoe_mt_ema", descs, chunks, n, self.nprofiles, self._step, self._coefs, self.mode)
+        else:
+            call("hdmoe_mt_ema_ok", descs, chunks, n, self.nprofiles, self._step, self._coefs, self.mode, ok)
 
     @property
     def step(self) -> int:

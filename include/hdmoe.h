@@ -645,6 +645,30 @@ int hdmoe_mt_sumsq(float* sumsq, const void* descs, const int* chunks, int nchun
 int hdmoe_mt_clip_scale(const void* descs, const int* chunks, int nchunks, const float* sumsq, float max_norm, HS stream);
 int hdmoe_mt_adamw(const void* descs, const int* chunks, int nchunks, int ntensors, const float* sumsq, float max_norm, const float* group_lr,
                    const float* group_wd, int ngroups, float beta1, float beta2, float eps, HS stream);
+/* hdmoe_mt_adamw behind a device verdict: *ok != 0 is hdmoe_mt_adamw bit for bit, *ok == 0 writes nothing (no weight decay, no moment
+ * decay, no per-tensor step increment).  ok == NULL is hdmoe_mt_adamw. */
+int hdmoe_mt_adamw_ok(const void* descs, const int* chunks, int nchunks, int ntensors, const float* sumsq, float max_norm, const float* group_lr,
+                      const float* group_wd, int ngroups, float beta1, float beta2, float eps, const int* ok, HS stream);
+/* One statistics pass over the same table: the descriptor's `group` is a statistics group 0..ngroups-1 (1 <= ngroups <= 64; a chunk whose
+ * group lies outside counts towards the total only), `which` picks the array (d.g or d.p).
+ *   stats  (ngroups + 1, 4) fp32: {sum, sum of squares, min, max} over the FINITE elements of the group; a non-finite element adds 0
+ *   counts (ngroups + 1, 2) int64: {non-finite elements, elements}
+ * The last row of both is the total over every chunk.  A group without elements: {0, 0, +inf, -inf}, {0, 0}.
+ *   ok       (int32, may be NULL): 1 when the total non-finite count is 0 and the total sum of squares is finite (finite elements can
+ *            still overflow the sum), else 0
+ *   counters (int64 [4], may be NULL): {passes measured, passes with ok == 0, such passes in a row, step of the last such pass (-1 until
+ *            there is one; the launch scalar `step`)}; an ok pass sets the in-a-row count to 0.  The caller initialises them once.
+ *   ws       HDMOE_STATS_WS_PER_CHUNK * nchunks floats of scratch
+ * Two launches, no atomics, fixed summation order: a chunk's partial takes thread t's elements t, t + 256, ... in order and then the block
+ * tree of hdmoe_mt_sumsq; a row sums thread t's chunk partials t, t + 1024, ... in order and then the same block tree (1024 threads).  The
+ * total sum of squares of a table without a non-finite element is therefore bit-identical to hdmoe_mt_sumsq's, and stats + 4 * ngroups + 1
+ * can stand in for it as hdmoe_mt_adamw's `sumsq`.  HDMOE_EINVAL before anything is written: stats or counts NULL, ngroups outside 1..64,
+ * which outside {0, 1}, nchunks < 0, or nchunks > 0 with descs, chunks or ws NULL.  nchunks == 0 writes the empty-group rows and ok = 1. */
+#define HDMOE_STATS_GRAD 0
+#define HDMOE_STATS_PARAM 1
+#define HDMOE_STATS_WS_PER_CHUNK 6
+int hdmoe_mt_stats(float* stats, long long* counts, int* ok, long long* counters, const void* descs, const int* chunks, int nchunks,
+                   int ngroups, int which, long long step, float* ws, HS stream);
 
 /* ---- N4: exponential moving average of the weights (EDM2 power-function profiles; no counterpart in the reference) ---------------- */
 /* descs: device array of {p, e[4] addresses, numel} (hdmoe_ema_desc_bytes() bytes each), all fp32; chunks: device int32 pairs
@@ -659,6 +683,10 @@ int hdmoe_mt_adamw(const void* descs, const int* chunks, int nchunks, int ntenso
 int hdmoe_ema_desc_bytes(void);
 int hdmoe_mt_ema(const void* descs, const int* chunks, int nchunks, int nprofiles, long long* step_counter, const double* gammas_or_betas,
                  int mode, HS stream);
+/* hdmoe_mt_ema behind a device verdict (hdmoe_mt_stats' ok): *ok != 0 is hdmoe_mt_ema bit for bit, *ok == 0 writes nothing (no step
+ * increment, no profile write).  ok == NULL is hdmoe_mt_ema. */
+int hdmoe_mt_ema_ok(const void* descs, const int* chunks, int nchunks, int nprofiles, long long* step_counter, const double* gammas_or_betas,
+                    int mode, const int* ok, HS stream);
 int hdmoe_mt_swap(const void* descs, const int* chunks, int nchunks, int profile, HS stream);
 /* Post-hoc reconstruction (EDM2 section 3.2): nsrc saved averages -> ndst new ones in one pass.  src_table / dst_table: device arrays of
  * nsrc (1..4096) / ndst (1..8) 64-bit device addresses of flat fp32 buffers of numel elements each; weights: device doubles [nsrc][ndst],
