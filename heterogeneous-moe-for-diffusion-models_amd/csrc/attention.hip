@@ -1187,13 +1187,21 @@ static inline bool mk_raga(RagA& rg, const int* seg, const int* lens, const int*
   }
   return true;
 }
+// LDS of one (row, head) workgroup whose longest row holds ml tokens: K, V (forward); Q, K, V, dO, lse, delta (backward).  The launchers
+// size their launch with it and hdmoe_attn_rag_max_len answers from it, so the domain a caller is told is the domain that is launched.
+constexpr size_t RAG_LDS_LIMIT = 60 * 1024;
+constexpr size_t rag_lds_bytes(int ml, int D, bool bwd) {
+  return (bwd ? (size_t)4 * ml * D + (size_t)2 * ml : (size_t)2 * ml * D) * sizeof(float);
+}
+constexpr int rag_max_len(int D, bool bwd) { return (int)(RAG_LDS_LIMIT / rag_lds_bytes(1, D, bwd)); }   // rag_lds_bytes is linear in ml
+
 template <typename T, int D>
 int attn_rag_fwd_launch(void* out, float* lse, const void* q, const void* k, const void* v, const RagA& rg, int R, int Sp, int H,
                         hipStream_t st) {
   int ml = 0;
   for (int g = 0; g < rg.ng; ++g) ml = max(ml, rg.len[g]);
-  const size_t lds = (size_t)2 * ml * D * sizeof(float);
-  if (lds > 60 * 1024) return HDMOE_EINVAL;
+  if (ml > rag_max_len(D, false)) return HDMOE_EINVAL;
+  const size_t lds = rag_lds_bytes(ml, D, false);
   hipLaunchKernelGGL((attn_rag_fwd_kernel<T, D>), dim3(R, H), dim3(64), lds, st, (T*)out, lse, (const T*)q, (const T*)k, (const T*)v, rg, Sp, H,
                      1.f / sqrtf((float)D));
   return hdmoe_launch_status();
@@ -1203,8 +1211,8 @@ int attn_rag_bwd_launch(void* dq, void* dk, void* dv, float* delta, const void* 
                         const void* v, const float* lse, const RagA& rg, bool want_dbias, int R, int Sp, int H, hipStream_t st) {
   int ml = 0;
   for (int g = 0; g < rg.ng; ++g) ml = max(ml, rg.len[g]);
-  const size_t lds = (size_t)(4 * ml * D + 2 * ml) * sizeof(float);
-  if (lds > 60 * 1024) return HDMOE_EINVAL;
+  if (ml > rag_max_len(D, true)) return HDMOE_EINVAL;
+  const size_t lds = rag_lds_bytes(ml, D, true);
   const float scale = 1.f / sqrtf((float)D);
   hipLaunchKernelGGL((attn_rag_bwd_kernel<T, D>), dim3(R, H), dim3(64), lds, st, (T*)dq, (T*)dk, (T*)dv, delta, (const T*)dout, (const T*)out,
                      (const T*)q, (const T*)k, (const T*)v, lse, rg, Sp, H, scale);
@@ -1245,6 +1253,14 @@ int hdmoe_attn_bwd(void* dq, void* dk, void* dv, float* dbias, float* delta, con
   if (dtype == HDMOE_F32) { D_SWITCH(D, return (attn_bwd_launch<float, DD>(dq, dk, dv, dbias, delta, dout, out, q, k, v, lse, bias, B, Sq, Skv, H, Sb, stream))) }
   if (dtype == HDMOE_BF16) { D_SWITCH(D, return (attn_bwd_launch<bf16, DD>(dq, dk, dv, dbias, delta, dout, out, q, k, v, lse, bias, B, Sq, Skv, H, Sb, stream))) }
   return HDMOE_EDTYPE;
+}
+
+/* Longest row (largest lens[g]) hdmoe_attn_rag_fwd (backward == 0) / hdmoe_attn_rag_bwd (backward != 0) accept at head dim D;
+ * 0 when the kernels have no such head dim.  The launchers refuse by the same expression. */
+static int rag_max_len_of(int D, bool bwd) { D_SWITCH(D, return rag_max_len(DD, bwd)) }   // D_SWITCH: the launchers' own list of head dims
+int hdmoe_attn_rag_max_len(int D, int backward) {
+  const int n = rag_max_len_of(D, backward != 0);
+  return n > 0 ? n : 0;
 }
 
 /* Ragged self-attention of the ViT expert bank: q/k/v/out [R][Sp][H*D]; rows [seg[g], seg[g+1]) belong to expert g with lens[g]

@@ -2968,6 +2968,12 @@ def attention_rag(q: Tensor, k: Tensor, v: Tensor, biases: Sequence[Tensor], rag
     return _AttnRagFn.apply(q, k, v, rag, int(num_heads), *biases)
 
 
+def attention_rag_max_len(head_dim: int, backward: bool) -> int:
+    """The longest row (tokens) attention_rag's forward / backward kernels accept at this head dim, asked of the library
+    (hdmoe_attn_rag_max_len: the launchers refuse by the same expression); 0: no kernel for this head dim."""
+    return int(lib().hdmoe_attn_rag_max_len(int(head_dim), 1 if backward else 0))
+
+
 # =====================================================================================================
 # router head + dispatch
 # =====================================================================================================

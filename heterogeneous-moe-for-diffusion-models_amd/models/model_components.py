@@ -452,9 +452,12 @@ def vit_bank_compatible(experts: Sequence[nn.Module], H: int, W: int) -> bool:
         return False
     # domains of the ragged kernels (csrc/ragged.hip, attn_rag_* in csrc/attention.hip): outside them the per-expert path runs instead
     heads = b0.TMSA.num_heads
-    if e0.emb_dim > 256 or b0.GN.num_groups > 32 or e0.emb_dim % heads or (e0.emb_dim // heads) not in (1, 2, 4, 8, 16, 32):
+    if e0.emb_dim > 256 or b0.GN.num_groups > 32 or e0.emb_dim % heads:
         return False
-    if 2 * max(e.seq_ln for e in experts) * (e0.emb_dim // heads) * 4 > 60 * 1024:      # K / V of one (row, head) in LDS
+    # the library says how long a row its ragged attention takes (0: no kernel for this head dim).  The backward keeps more of a head
+    # in LDS than the forward, so with grad enabled it is the backward's limit that decides: a bank must never pass here, run its
+    # forward and then be refused in the backward.
+    if max(e.seq_ln for e in experts) > ops.attention_rag_max_len(e0.emb_dim // heads, torch.is_grad_enabled()):
         return False
     for e in experts:
         p = e.patch.kernel_size[0]

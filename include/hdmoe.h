@@ -561,6 +561,9 @@ int hdmoe_attn_rag_fwd(void* out, float* lse, const void* q, const void* k, cons
 int hdmoe_attn_rag_bwd(void* dq, void* dk, void* dv, float* const* dbias, float* delta, const void* dout, const void* out,
                        const void* q, const void* k, const void* v, const float* lse, const float* const* bias, const int* seg,
                        const int* lens, const int* sb, int ngroups, int R, int Sp, int H, int D, int dtype, HS stream);
+/* longest row (largest lens[g]) the two above accept at head dim D: backward == 0 hdmoe_attn_rag_fwd, else hdmoe_attn_rag_bwd, which
+ * keeps more of a head in LDS and so takes shorter rows; 0: no kernel for this D.  Launches nothing. */
+int hdmoe_attn_rag_max_len(int D, int backward);
 
 /* ---- many small linear layers over ONE input in one launch (csrc/mlinear.hip): Unet_block.emb_layer of every block
  * (model_components.py:232-236) and MP_Attention.q_time / k_time / v_time of every ViT block (model_internals.py:360-372).
