@@ -9,7 +9,7 @@ When do the collectives go out?  Almost every gradient of this path is written s
 weight bank's finish launch, the norm / bias / table backward kernels) and never passes through an AccumulateGrad node, so
 autograd hooks cannot tell when a bucket is complete.  Completion is known structurally instead:
   * default (multi-stream step): the parameters are bucketed by the SECTION of the staged step (hdmoe_hip/graph.py) whose backward
-    finishes them, in the order the sections complete: the U-Net bank's backward runs as four sections (graph.Stager, SPLIT_UNET_BWD) --
+    finishes them, in the order the sections complete: the U-Net bank's backward runs as four sections (graph.STEP, SPLIT_UNET_BWD) --
     "unet_s3" (full-resolution decoder entries + output conv), "unet_s2" (decoder below), "unet_s1" (encoder below), then "vit" (ViT
     router + experts), "unet_s0" (full-resolution encoder entries, the embedding layers of every block, the U-Net router) and "rest" (stem,
     fusion, head, preconditioning).  ``staged_hooks(staged)`` gives StagedStep one hook per section; each runs right after that section's
@@ -30,7 +30,9 @@ import torch.distributed as dist
 
 
 class GradBuckets:
-    TAGS = ("unet_s3", "unet_s2", "unet_s1", "vit", "unet_s0", "rest")     # completion order of the staged backward
+    # backward section of the staged step (hdmoe_hip/graph.py) -> tag of the bucket it completes, in the order the replay fires the hooks
+    SECTION_TAG = (("unet_bwd", "unet_s3"), ("unet_bwd2", "unet_s2"), ("unet_bwd1", "unet_s1"), ("vit_bwd", "vit"), ("unet_bwd0", "unet_s0"))
+    TAGS = tuple(t for _, t in SECTION_TAG) + ("rest",)                    # completion order of the staged backward
 
     @staticmethod
     def tag_of(name: str, top: str = "") -> str:
@@ -170,11 +172,13 @@ class GradBuckets:
         """{backward section of ``staged`` (hdmoe_hip.graph.StagedStep): hook}: each hook runs behind the launch of its section, on the
         section's stream, and hands that section's gradient bucket to the process group."""
         L = self.launch_tag
-        if len(getattr(staged, "unet_sub", [])) == 3:
-            return {"unet_bwd": lambda: L("unet_s3"), "unet_bwd2": lambda: L("unet_s2"), "unet_bwd1": lambda: L("unet_s1"),
-                    "vit_bwd": lambda: L("vit"), "unet_bwd0": lambda: L("unet_s0")}
+        sub = getattr(staged, "unet_sub", [])
+        if len(sub) == 3:
+            return {sec: (lambda tag=tag: L(tag)) for sec, tag in GradBuckets.SECTION_TAG}
+        if sub:                                                    # a bucket would go out while a later section still writes it
+            raise RuntimeError(f"staged step with a partial U-Net backward split {list(sub)}")
         # the U-Net bank's backward as ONE section: all of its buckets behind it
-        return {"vit_bwd": lambda: L("vit"), "unet_bwd": lambda: [L(t) for t in ("unet_s3", "unet_s2", "unet_s1", "unet_s0")]}
+        return {"vit_bwd": lambda: L("vit"), "unet_bwd": lambda: [L(tag) for sec, tag in GradBuckets.SECTION_TAG if sec != "vit_bwd"]}
 
     def finish(self):
         """Call after backward: reduce every bucket that has not gone out yet, wait for all."""

@@ -7,6 +7,8 @@ path is sync-free and allocation goes through torch's caching allocator, so the 
 """
 from __future__ import annotations
 
+import collections
+import contextlib
 import os
 import time
 
@@ -21,9 +23,6 @@ def _capture_mode() -> str:
     The step allocates nothing new after its warm-up runs, so the laxer mode hides nothing."""
     import torch.distributed as dist
     return "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
-
-
-import contextlib
 
 
 @contextlib.contextmanager
@@ -88,26 +87,90 @@ class GraphedStep:
 # after the other -- the tracer adds ~17-20 us of host time per dispatch, the replay becomes host-bound and the queues drain in
 # issue order.  Branch overlap has to be read from events (stage_ms), not from the trace.
 # =====================================================================================================================================
-class Stager:
-    """Stage bookkeeping shared by the eager warm-up runs and the capture run of a StagedStep.  Model code talks to it through
-    ``graph.current()``: ``cut(stage, **tensors_by_producer_stage)`` at a boundary, ``backward(loss)`` instead of loss.backward()."""
-
+# The step, one row per graph launch ("run") or hook point ("done": StagedStep.after[name] runs there, on that section's stream -- e.g.
+# dp.GradBuckets.launch_tag hands the section's gradient bucket to RCCL), in the order the host issues them in a replay.  Everything else
+# is derived from this table: the stream of each stage (KIND), the legal stage sequences of a capture (order), the backward sections
+# and the order they are captured in (sections) and the replay itself (schedule).
+#   shapes    which forms of the step contain the row.  A: SPLIT_ROUTER with the U-Net bank's backward in four sections (15 graphs; the
+#             trainer and bench.py); B: SPLIT_ROUTER with a one-level U-Net (12 graphs); C: the seven-graph form (tests set
+#             Stager.SPLIT_ROUTER = False).  `unet` and the hook of `unet_bwd` are issued at a different point in A / B / C: two rows.
+#   waits     (a, b[, shapes]): stream a waits for everything issued to stream b so far, right before the row; "cur" is the caller's
+#             stream.  A replay ends with cur waiting for main.
+#   producer  backward sections: the key of the cuts (Stager.cut / cut_local) whose leaves the section differentiates.
+#   cap       position in the capture: the order the stages are captured in (which decides the allocation inside the per-stream graph
+#             pools) differs from the replay's issue order.
+Row = collections.namedtuple("Row", "op name stream shapes waits producer cap", defaults=((), None, None))
+STEP = (
+    Row("run", "pre", "main", "ABC", (("main", "cur"),), cap=0),
+    Row("run", "unet", "u", "C", (("u", "main"),), cap=2),
     # The router FORWARD of the U-Net branch is on the critical path (the bank cannot start before the routing weights exist): it runs
     # on the bank's own stream; only its backward, which has slack, uses the third stream.
-    KIND = {"pre": "main", "ur": "u", "unet": "u", "vit": "v", "post": "main", "ucomb_bwd": "u", "ur_bwd": "r", "unet_bwd": "u", "vit_bwd": "v",
-            "pre_bwd": "main", "unet_bwd2": "u", "unet_bwd1": "u", "unet_bwd0": "u", "vcomb_bwd": "v", "vr_bwd": "main"}
+    Row("run", "ur", "u", "AB", (("u", "main"),), cap=1),
+    Row("run", "vit", "v", "ABC", (("v", "main"),), cap=3),
+    Row("run", "unet", "u", "AB", (), cap=2),                      # (behind `ur` on its stream)
+    Row("run", "post", "main", "ABC", (("main", "u"), ("main", "v")), cap=4),
+    Row("run", "ucomb_bwd", "u", "AB", (("u", "main"),), "ucomb", 5),
+    Row("run", "vcomb_bwd", "v", "AB", (("v", "main"),), "vcomb", 11),
+    # (the router's backward waits for the combine backward only: its wait is issued BEFORE the bank's backward goes to stream u)
+    Row("run", "unet_bwd", "u", "ABC", (("u", "main", "C"), ("r", "u", "AB")), "unet", 6),
+    Row("run", "ur_bwd", "r", "AB", (), "ur", 10),
     # SPLIT_VROUTER, the ViT router's backward as its own section (round 4, always on): with the U-Net bank's backward down to ~6 ms the ViT section became the LAST one to finish (stage_ms: vit_bwd
     # 6.2 -> 12.8 ms, unet_bwd0 ends at 12.4): its stream runs the ViT bank's backward (~170 small launches) and then the ViT router's trunk
     # backward (the heavy part) one after the other.  The router's backward needs only the gradient of the routing weights, which the
     # combine backward -- the section's first kernel -- produces: same cut as for the U-Net router (`vcomb_bwd` on the ViT stream, then
     # `vr_bwd` beside `vit_bwd`).  The forward stays one graph.  The stream of `vr_bwd`, same box, ms/step, with the stream
     # priorities of the time: no split 13.39; "r" (behind the U-Net router's backward) 13.13; "main" (idle between `post` and `pre_bwd`) 13.32;
-    # "r2" (a fifth stream of our own) 17.9 -- see the note on hardware queues below.  Without priorities (the default now, see StagedStep):
+    # "r2" (a fifth stream of our own) 17.9 -- see the note on hardware queues in StagedStep.  Without priorities (the default now, see StagedStep):
     # "main" 13.02, "r" 13.62.
+    Row("run", "vr_bwd", "main", "AB", (("main", "v"),), "vr", 13),   # (behind the combine backward)
+    Row("run", "vit_bwd", "v", "ABC", (("v", "main", "C"),), "vit", 12),
     # SPLIT_UNET_BWD (round 4, always on): the U-Net bank's backward as up to FOUR sections on its stream -- decoder at full resolution (+ output conv),
     # decoder below, encoder below, encoder at full resolution (+ embeddings) -- cut with detached leaves inside the forward graph
     # (models/model_components.py unet_expert_bank_forward).  Each section finishes its own weight gradients (bank.finish_stage), so its
     # gradient bucket can go to RCCL while the later sections still run (hdmoe_hip/dp.py); single-process jobs just replay four graphs.
+    # The bank's sections one after the other on its stream; behind each the hook that hands its gradient bucket on
+    # (buckets are ordered by completion: decoder sections first, then the ViT branch, then what ends with the backward).
+    Row("done", "unet_bwd", "u", "A"),
+    Row("run", "unet_bwd2", "u", "A", (), "unet_c2", 7),
+    Row("done", "unet_bwd2", "u", "A"),
+    Row("run", "unet_bwd1", "u", "A", (), "unet_c1", 8),
+    Row("done", "unet_bwd1", "u", "A"),
+    Row("run", "unet_bwd0", "u", "A", (), "unet_c0", 9),
+    Row("done", "vit_bwd", "v", "ABC", (("v", "main", "AB"),)),    # the "vit" gradient bucket holds the ViT router's parameters too: behind `vr_bwd`
+    Row("done", "unet_bwd0", "u", "A", (("u", "r"),)),             # the last U-Net bucket holds the router's parameters too: behind `ur_bwd`
+    Row("done", "unet_bwd", "u", "BC", (("u", "r", "B"),)),        # the "unet" gradient bucket holds the router's parameters too
+    Row("run", "pre_bwd", "main", "ABC", (("main", "u"), ("main", "v")), "pre", 14),
+)
+KIND = {r.name: r.stream for r in STEP if r.op == "run"}
+
+
+def order(shape: str) -> list:
+    """The stage sequence a capture of ``shape`` must produce."""
+    return [r.name for r in sorted((r for r in STEP if r.op == "run" and shape in r.shapes), key=lambda r: r.cap)]
+
+
+def sections(ran, cuts_present) -> list:
+    """[(backward section, producer key)] behind `post`, in capture order, for a forward that ran the stages ``ran`` and made the local
+    cuts ``cuts_present``: a section exists when its producer does."""
+    rows = sorted((r for r in STEP if r.producer is not None), key=lambda r: r.cap)
+    return [(r.name, r.producer) for r in rows if r.producer in ran or r.producer in cuts_present]
+
+
+def schedule(shape: str) -> list:
+    """The replay of ``shape`` as a flat list of ("wait", a, b) -- stream a waits for stream b -- / ("run", stage, stream) /
+    ("done", stage, stream); streams by name."""
+    ops = []
+    for r in STEP:
+        if shape in r.shapes:
+            ops += [("wait", a, b) for a, b, *only in r.waits if not only or shape in only[0]]
+            ops.append((r.op, r.name, r.stream))
+    return ops + [("wait", "cur", "main")]
+
+
+class Stager:
+    """Stage bookkeeping shared by the eager warm-up runs and the capture run of a StagedStep.  Model code talks to it through
+    ``graph.current()``: ``cut(stage, **tensors_by_producer_stage)`` at a boundary, ``backward(loss)`` instead of loss.backward()."""
+
     # SPLIT_ROUTER: the U-Net branch is the longer one, and its router's backward (2.2 ms of kernels) needs nothing from the bank's
     # backward but the gradient of the routing weights, which the bank's FIRST backward kernel (the combine) produces.  The router
     # therefore gets its own stream and graphs (`ur`, `ur_bwd`), and the combine backward its own small graph (`ucomb_bwd`) so that
@@ -120,18 +183,17 @@ class Stager:
         self.graphs = {}
         self.stage = None
         self._ctx = None
-        import collections
         self.cuts = collections.defaultdict(list)                # producer segment -> [(tensor, detached leaf)]
         self.order = []
 
     # -- stage switching ------------------------------------------------------------------------------------------------------
     def begin(self, name: str):
         assert self.stage is None
-        st = self.streams[self.KIND[name]]
+        st = self.streams[KIND[name]]
         if self.capture:
             g = torch.cuda.CUDAGraph()
             self.graphs[name] = g
-            self._ctx = torch.cuda.graph(g, pool=self.pools[self.KIND[name]], stream=st, capture_error_mode=_capture_mode())
+            self._ctx = torch.cuda.graph(g, pool=self.pools[KIND[name]], stream=st, capture_error_mode=_capture_mode())
         else:
             for other in self.streams.values():                  # warm-up: plain streams, fully ordered
                 st.wait_stream(other)
@@ -183,25 +245,8 @@ class Stager:
         try:
             bank.STAGE = "post"
             loss.backward()                                       # fusion + head + loss section; stops at the detached leaves
-            if "ur" in self.order:
-                self._section("ucomb_bwd", "ucomb")               # combine backward: gradients of the bank output rows and of the routing weights
-                self._section("unet_bwd", "unet")
-                for k in (2, 1, 0):                               # the bank's own sections, in backward order (SPLIT_UNET_BWD)
-                    if self.cuts.get(f"unet_c{k}"):
-                        self._section(f"unet_bwd{k}", f"unet_c{k}")
-                self._section("ur_bwd", "ur")
-            else:
-                self._section("unet_bwd", "unet")
-                for k in (2, 1, 0):
-                    if self.cuts.get(f"unet_c{k}"):
-                        self._section(f"unet_bwd{k}", f"unet_c{k}")
-            if self.cuts.get("vcomb"):                            # SPLIT_VROUTER: combine backward, then the bank and the router side by side
-                self._section("vcomb_bwd", "vcomb")
-                self._section("vit_bwd", "vit")
-                self._section("vr_bwd", "vr")
-            else:
-                self._section("vit_bwd", "vit")
-            self._section("pre_bwd", "pre")
+            for stage, producer in sections(self.order, {k for k, v in self.cuts.items() if v}):
+                self._section(stage, producer)
         finally:
             bank.DEFER_FINISH = False
             bank.STAGE = None
@@ -231,8 +276,8 @@ class StagedStep:
     streams the higher priority (see the note in __init__), ``skip`` names sections that every replay drops -- the step's results are
     then WRONG."""
 
-    ORDER = ["pre", "unet", "vit", "post", "unet_bwd", "vit_bwd", "pre_bwd"]
-    ORDER_R = ["pre", "ur", "unet", "vit", "post", "ucomb_bwd", "unet_bwd", "ur_bwd", "vit_bwd", "pre_bwd"]
+    ORDER = order("C")                                                         # the seven-graph form
+    ORDER_R = [n for n in order("B") if n not in ("vcomb_bwd", "vr_bwd")]      # SPLIT_ROUTER, without the sections of SPLIT_VROUTER / SPLIT_UNET_BWD
 
     def __init__(self, step_fn, device, warmup: int = 3, *, priorities: bool = False, skip=()):
         self.device = torch.device(device)
@@ -267,15 +312,15 @@ class StagedStep:
         torch.cuda.synchronize(self.device)
         with no_gc():
             st = self._run(step_fn, capture=True)
-        core = [n for n in st.order if n not in ("unet_bwd2", "unet_bwd1", "unet_bwd0", "vcomb_bwd", "vr_bwd")]
-        self.split_vr = "vr_bwd" in st.order                      # the ViT router's backward as its own section (SPLIT_VROUTER above)
-        if core not in (self.ORDER, self.ORDER_R):
+        shape = next((k for k in "ABC" if st.order == order(k)), None)
+        if shape is None:
             raise RuntimeError(f"staged step: unexpected stage sequence {st.order}")
-        self.split_router = core == self.ORDER_R
-        self.unet_sub = [n for n in ("unet_bwd2", "unet_bwd1", "unet_bwd0") if n in st.order]    # further sections of the U-Net bank's backward
+        self.split_router = shape != "C"
+        self.unet_sub = ["unet_bwd2", "unet_bwd1", "unet_bwd0"] if shape == "A" else []   # further sections of the U-Net bank's backward
+        self._ops = schedule(shape)
         self.graphs = st.graphs
         self._keep = st                                           # boundary tensors live in the graphs' pools
-        self.after = {}                                           # {"unet_bwd" | "vit_bwd": callable}: run on that section's stream right after its launch
+        self.after = {}                                           # {section with a "done" row in STEP: callable}: run on that section's stream behind its launch
         self.host_us = {} if os.environ.get("HDMOE_HOST_TIMES") == "1" else None
 
     def _run(self, step_fn, capture: bool):
@@ -295,9 +340,7 @@ class StagedStep:
         return st
 
     def __call__(self):
-        S, g = self.streams, self.graphs
-        main, u, v = S["main"], S["u"], S["v"]
-        cur = torch.cuda.current_stream(self.device)
+        g = self.graphs
         ev = self._events = {} if self.timing else None
 
         skip = self.skip
@@ -328,75 +371,14 @@ class StagedStep:
                 with torch.cuda.stream(stream):
                     fn()
 
-        if self.split_router:
-            r = S["r"]
-            main.wait_stream(cur)
-            run("pre", main)
-            ur_s = S[self._keep.KIND["ur"]]
-            ur_s.wait_stream(main); v.wait_stream(main)
-            run("ur", ur_s)
-            run("vit", v)
-            u.wait_stream(main); u.wait_stream(ur_s)
-            run("unet", u)
-            main.wait_stream(u); main.wait_stream(v)
-            run("post", main)
-            u.wait_stream(main); v.wait_stream(main)
-            run("ucomb_bwd", u)
-            vr_s = S[self._keep.KIND["vr_bwd"]] if self.split_vr else None
-            if self.split_vr:
-                run("vcomb_bwd", v)
-            r.wait_stream(u)
-            run("unet_bwd", u)
-            run("ur_bwd", r)
-            if self.split_vr:
-                vr_s.wait_stream(v)                               # (behind the combine backward; on "r" also behind ur_bwd: stream order)
-                run("vr_bwd", vr_s)
-            run("vit_bwd", v)
-            if self.split_vr:
-                v.wait_stream(vr_s)                               # the "vit" gradient bucket holds the ViT router's parameters too
-            if self.unet_sub:
-                # the bank's sections one after the other on its stream; behind each the hook that hands its gradient bucket on
-                # (buckets are ordered by completion: decoder sections first, then the ViT branch, then what ends with the backward)
-                done("unet_bwd", u)
-                for name in self.unet_sub[:-1]:
-                    run(name, u)
-                    done(name, u)
-                run(self.unet_sub[-1], u)
-                done("vit_bwd", v)
-                u.wait_stream(r)                                  # the last U-Net bucket holds the router's parameters too
-                done(self.unet_sub[-1], u)
+        S = dict(self.streams, cur=torch.cuda.current_stream(self.device))
+        for op, name, stream in self._ops:
+            if op == "wait":
+                S[name].wait_stream(S[stream])
+            elif op == "run":
+                run(name, S[stream])
             else:
-                done("vit_bwd", v)
-                u.wait_stream(r)                                  # the "unet" gradient bucket holds the router's parameters too
-                done("unet_bwd", u)
-            main.wait_stream(u); main.wait_stream(v)
-            run("pre_bwd", main)
-            cur.wait_stream(main)
-            return self.out
-        main.wait_stream(cur)
-        run("pre", main)
-        u.wait_stream(main); v.wait_stream(main)
-        run("unet", u)
-        run("vit", v)
-        main.wait_stream(u); main.wait_stream(v)
-        run("post", main)
-        u.wait_stream(main); v.wait_stream(main)
-        run("unet_bwd", u)
-        run("vit_bwd", v)
-        if self.unet_sub:
-            done("unet_bwd", u)
-            for name in self.unet_sub[:-1]:
-                run(name, u)
-                done(name, u)
-            run(self.unet_sub[-1], u)
-            done("vit_bwd", v)
-            done(self.unet_sub[-1], u)
-        else:
-            done("vit_bwd", v)
-            done("unet_bwd", u)
-        main.wait_stream(u); main.wait_stream(v)
-        run("pre_bwd", main)
-        cur.wait_stream(main)
+                done(name, S[stream])
         return self.out
 
     timing = False

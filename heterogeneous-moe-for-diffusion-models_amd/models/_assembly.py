@@ -263,25 +263,19 @@ class _HDMOEMBase(nn.Module):
                 (te_r, te_b), (in_r, in_b) = ops.fanout(te_u, 2), ops.fanout(in_u, 2)
                 w_unet, p_unet, raw_unet, _ = self.Unet_router._fwd(in_r, te_r, Unet_router_mask, zeta)
                 out_u = _dispatch_nhwc(ops.cast(in_b, cdt), self.Unet_experts, w_unet, te_b, text2d, kcap=self.top_k)
-            split_vr = st.SPLIT_ROUTER
             te_v, in_v = st.cut("vit", pre=(te, in_vit))
-            if split_vr:
+            if st.SPLIT_ROUTER:
                 # one forward graph, three backward sections (hdmoe_hip/graph.py SPLIT_VROUTER): the router sees its own leaves of the stem
                 # tensors, the bank a detached copy of the routing weights; the combine is the boundary between them
                 w_vit, p_vit, raw_vit, _ = self.vit_router._fwd(in_v, te_v, Vit_router_mask, zeta)
                 te_b, in_b, w_b = st.cut_local(pre=(te, in_vit), vr=(w_vit,))
                 out_v = _dispatch_nhwc(ops.cast(in_b, cdt), self.VIT_experts, w_b, te_b, text2d, kcap=self.top_k, stager=st, cut_name="vit")
+                out_u, p_unet, raw_unet, out_v, p_vit, raw_vit, s_vit, s_unet, scaling = st.cut(
+                    "post", ucomb=(out_u,), ur=(p_unet, raw_unet), vcomb=(out_v,), vr=(p_vit, raw_vit), pre=(s_vit, s_unet, scaling))
             else:
                 (te_r, te_b), (in_r, in_b) = ops.fanout(te_v, 2), ops.fanout(in_v, 2)
                 w_vit, p_vit, raw_vit, _ = self.vit_router._fwd(in_r, te_r, Vit_router_mask, zeta)
                 out_v = _dispatch_nhwc(ops.cast(in_b, cdt), self.VIT_experts, w_vit, te_b, text2d, kcap=self.top_k)
-            if split_vr:
-                out_u, p_unet, raw_unet, out_v, p_vit, raw_vit, s_vit, s_unet, scaling = st.cut(
-                    "post", ucomb=(out_u,), ur=(p_unet, raw_unet), vcomb=(out_v,), vr=(p_vit, raw_vit), pre=(s_vit, s_unet, scaling))
-            elif st.SPLIT_ROUTER:
-                out_u, p_unet, raw_unet, out_v, p_vit, raw_vit, s_vit, s_unet, scaling = st.cut(
-                    "post", ucomb=(out_u,), ur=(p_unet, raw_unet), vit=(out_v, p_vit, raw_vit), pre=(s_vit, s_unet, scaling))
-            else:
                 out_u, p_unet, raw_unet, out_v, p_vit, raw_vit, s_vit, s_unet, scaling = st.cut(
                     "post", unet=(out_u, p_unet, raw_unet), vit=(out_v, p_vit, raw_vit), pre=(s_vit, s_unet, scaling))
         elif banked and ops.SIDE_STREAMS and x.is_cuda:

@@ -1663,10 +1663,13 @@ def test_staged_step_matches_plain_backward(dtype, tol):
             staged = hgraph.StagedStep(fwd_bwd, DEV, warmup=2)
         finally:
             hgraph.Stager.SPLIT_ROUTER = split_saved
-        # (config1 / ten graphs: the U-Net bank's backward additionally runs as four sections -- Stager.SPLIT_UNET_BWD)
-        # (... and the ViT router's backward is its own section behind the combine backward -- Stager.SPLIT_VROUTER)
+        # (config1 / ten graphs: the U-Net bank's backward additionally runs as four sections -- graph.STEP, SPLIT_UNET_BWD)
+        # (... and the ViT router's backward is its own section behind the combine backward -- graph.STEP, SPLIT_VROUTER)
         want = hgraph.StagedStep.ORDER_R + ["unet_bwd2", "unet_bwd1", "unet_bwd0", "vcomb_bwd", "vr_bwd"] if mod is model_config1 else hgraph.StagedStep.ORDER
         assert sorted(staged.graphs) == sorted(want) and hgraph.current() is None
+        assert list(staged.graphs) == (["pre", "ur", "unet", "vit", "post", "ucomb_bwd", "unet_bwd", "unet_bwd2", "unet_bwd1", "unet_bwd0", "ur_bwd",
+                                        "vcomb_bwd", "vit_bwd", "vr_bwd", "pre_bwd"] if mod is model_config1 else
+                                       ["pre", "unet", "vit", "post", "unet_bwd", "vit_bwd", "pre_bwd"])    # (filled in the order of the capture)
         for _ in range(3):
             l_g = staged()
         torch.cuda.synchronize()
