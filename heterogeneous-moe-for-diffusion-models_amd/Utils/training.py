@@ -14,6 +14,7 @@ Differences that are deliberate and visible:
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Any, Callable, Dict, Iterable, Optional, Union
 
@@ -47,11 +48,13 @@ def build_scheduler(optimizer: torch.optim.Optimizer, optim_config: Dict[str, An
                                                       eta_min=optim_config["eta_min"])
 
 
-def save_checkpoint(model, optimizer, step, mse_score, configs, filename, ema=None, null_text_emb=None) -> str:
+def save_checkpoint(model, optimizer, step, mse_score, configs, filename, ema=None, null_text_emb=None, balance=None) -> str:
     """Same dictionary and path rules as reference training.py:242-271 (keys step / model_state_dict /
     optimizer_state_dict / mse / config); tensors are written from host copies so the file loads on any device.
     With `ema` (hdmoe_hip.ema.WeightEMA) the file additionally carries "ema_state_dict", with `null_text_emb` (the null row of
-    `Trainer(cond_dropout=...)`) "null_text_emb", which the sampler needs for guidance; without them the dictionary is the reference's."""
+    `Trainer(cond_dropout=...)`) "null_text_emb", which the sampler needs for guidance, with `balance` (hdmoe_hip.balance.RouterBalance,
+    `Trainer(balance_rate=...).balance`) "router_balance", the routers' selection biases, which the model's state_dict does not hold;
+    without them the dictionary is the reference's."""
     if "save_dir" in configs:
         save_path = configs["save_dir"]
     elif "model_configs" in configs and "save_dir" in configs["model_configs"]:
@@ -67,21 +70,26 @@ def save_checkpoint(model, optimizer, step, mse_score, configs, filename, ema=No
         checkpoint["ema_state_dict"] = ema.state_dict()
     if null_text_emb is not None:
         checkpoint["null_text_emb"] = null_text_emb.detach().cpu()
+    if balance is not None:
+        checkpoint["router_balance"] = balance.state_dict()
     torch.save(checkpoint, str(full_path))
     print(f"   [Save] Checkpoint saved: {full_path}")
     return full_path
 
 
-def load_checkpoint(path: str, model: torch.nn.Module, optimizer: Optional[torch.optim.Optimizer] = None, map_location=None, ema=None) -> dict:
+def load_checkpoint(path: str, model: torch.nn.Module, optimizer: Optional[torch.optim.Optimizer] = None, map_location=None, ema=None,
+                    balance=None) -> dict:
     """Inverse of `save_checkpoint` (reference training.py:303-304 loads only the model; resuming also needs the
-    optimizer moments).  Accepts files written by the reference's torch.optim.AdamW as well.  `ema` is restored when the file has one;
-    a saved "null_text_emb" comes back in the returned dictionary like every other key."""
+    optimizer moments).  Accepts files written by the reference's torch.optim.AdamW as well.  `ema` and `balance` (the routers' selection
+    biases) are restored when the file has them; a saved "null_text_emb" comes back in the returned dictionary like every other key."""
     ck = torch.load(f=path, map_location=map_location, weights_only=False)
     model.load_state_dict(ck["model_state_dict"])
     if optimizer is not None and "optimizer_state_dict" in ck:
         optimizer.load_state_dict(ck["optimizer_state_dict"])
     if ema is not None and "ema_state_dict" in ck:
         ema.load_state_dict(ck["ema_state_dict"])
+    if balance is not None and "router_balance" in ck:
+        balance.load_state_dict(ck["router_balance"])
     return ck
 
 
@@ -135,14 +143,26 @@ class Trainer:
     `hdmoe_hip.optim.health_groups`, and the skip counters) and handed to the logger's ``log_health``.  A non-finite parameter raises
     RuntimeError, and so does ``max_skips_in_a_row=m`` (needs both other keywords; the counters are only seen when they are read) once m
     steps in a row were skipped.  Without ``skip_nonfinite`` the gradients are measured on those steps only and the update is the plain
-    one: this mode only observes.  ``health()`` does the same read on demand.  With all three at their defaults nothing changes."""
+    one: this mode only observes.  ``health()`` does the same read on demand.  With all three at their defaults nothing changes.
+
+    ``balance_rate=r`` (``balance_bias_max=m``): auxiliary-loss-free load balancing (`hdmoe_hip.balance.RouterBalance`, kept in
+    ``balance``).  Both routers pick their top-k over logits + a per-expert bias that no gate weight and no loss term sees; every training
+    forward counts its routing on the device, and behind the optimizer step one launch per router moves the bias by r towards the
+    under-loaded experts, re-centres it and clamps it to +-m.  With ``skip_nonfinite`` the move runs behind the same verdict: a skipped
+    step keeps the bias bit for bit (its counts are dropped).  Under ``graphed=True`` the captured heads read the bias by pointer, so the
+    in-place update needs no recapture; under data parallelism the counts are summed over the ranks and every rank takes the same
+    decision.  The result gains ``"router_balance"``: per router the device tensors "bias", "load" and "target" of the step (nobody reads
+    them here, so nothing syncs); on steps where a health read or an evaluation syncs anyway they also go to the logger's
+    ``log_balance``.  The loss's balance weights are the caller's: turn them down or off in ``loss_config``.  At None nothing changes:
+    no buffer is registered and every path launches what it launched."""
 
     def __init__(self, model, model_config, optim_config, loss_config, mask_config, zeta_config, max_grad_norm: float = 1.0,
                  fuse_clip_into_step: bool = True, logger=None, ema=None, ema_snapshot_every: Optional[int] = None,
                  ema_snapshot_dir: Optional[str] = None, device_inputs: bool = False, graphed: bool = False, seed: Optional[int] = None,
                  cond_dropout: float = 0.0, null_text_emb: Optional[torch.Tensor] = None, dataset: Optional[LatentDataset] = None,
                  batch_size: Optional[int] = None, evaluator=None, eval_every: Optional[int] = None, skip_nonfinite: bool = False,
-                 health_every: Optional[int] = None, max_skips_in_a_row: Optional[int] = None):
+                 health_every: Optional[int] = None, max_skips_in_a_row: Optional[int] = None, balance_rate: Optional[float] = None,
+                 balance_bias_max: float = 8.0):
         dist = torch.distributed.is_available() and torch.distributed.is_initialized()
         self.world, self.rank = (torch.distributed.get_world_size(), torch.distributed.get_rank()) if dist else (1, 0)
         if dataset is None:
@@ -191,6 +211,11 @@ class Trainer:
         # pass's rows (and the parameters') are read every n-th step -> last_health, the logger's <run>_health.jsonl
         self.skip_nonfinite, self.health_every, self.max_skips_in_a_row = skip_nonfinite, health_every, max_skips_in_a_row
         self.last_health, self._health = None, None
+        for key, val in (("balance_rate", balance_rate), ("balance_bias_max", balance_bias_max)):
+            if val is None and key == "balance_rate":
+                continue
+            if isinstance(val, bool) or not isinstance(val, (int, float)) or not math.isfinite(val) or val <= 0:
+                raise ValueError(f"Trainer: {key} must be a finite number > 0, got {val!r}")
         if not 0.0 <= float(cond_dropout) <= 1.0:            # NaN fails both comparisons
             raise ValueError(f"Trainer: cond_dropout must lie in [0, 1], got {cond_dropout}")
         if null_text_emb is not None and not torch.is_tensor(null_text_emb):
@@ -210,6 +235,12 @@ class Trainer:
         self.criterion = EDM_LOSS(num_experts=model_config["num_experts"], sigma_data=model_config["sigma_data"],
                                   Unet_bal=loss_config["unet_bal"], vit_bal=loss_config["vit_bal"], z_bal=loss_config["z_bal"],
                                   prior_bal=loss_config["prior_bal"])
+        # balance_rate: the routers select over logits + a bias that one launch per router moves behind every optimizer step (built in front
+        # of the buckets, which then all-reduce the routing counts next to the usage counters)
+        self.balance = None
+        if balance_rate is not None:
+            from hdmoe_hip.balance import RouterBalance
+            self.balance = RouterBalance(model, float(balance_rate), float(balance_bias_max))
         self.buckets = GradBuckets(model)                    # .grad become views of flat fp32 buckets (all-reduced when world > 1)
         self.max_grad_norm, self.fuse = float(max_grad_norm), fuse_clip_into_step
         self.logger = logger                                 # graphs.logger.Logger (sync-free) or None
@@ -293,6 +324,8 @@ class Trainer:
             if u is not None and id(lst) not in seen:
                 seen.add(id(lst))
                 u.zero_()
+        if self.balance is not None:                         # ... and so must the first move of the selection bias
+            self.balance.clear()
 
     def _graphed_fwd_bwd(self, latent_images: Optional[torch.Tensor], text_emb: Optional[torch.Tensor]):
         if self.dataset is not None:
@@ -407,15 +440,22 @@ class Trainer:
                 self.ema.update()
             if self.ema_snapshot_every is not None and (step + 1) % self.ema_snapshot_every == 0:
                 self._save_ema_snapshot(step + 1)
+        if self.balance is not None:                         # one launch per router; behind a bad verdict only the counts are cleared
+            self.balance.step(ok=health.ok if self.skip_nonfinite else None)
         self.scheduler.step()
         self.step_idx += 1
         if health_due:
             self._check_health(step, self._read_health())
-        if self.eval_every is not None and (step + 1) % self.eval_every == 0:
+        eval_due = self.eval_every is not None and (step + 1) % self.eval_every == 0
+        if eval_due:
             self._evaluate(step + 1)
+        if self.balance is not None and (health_due or eval_due) and lg is not None and callable(getattr(lg, "log_balance", None)):
+            lg.log_balance(step, self.balance.read())        # (these steps sync anyway)
         res = {"loss": loss, "out_model": out_model, "sigma": sigma}
         if self.skip_nonfinite:                              # device values, read by nobody here: no sync
             res["step_ok"], res["grad_norm"] = health.ok[0], torch.sqrt(health.total_sumsq)[0]
+        if self.balance is not None:
+            res["router_balance"] = self.balance.last()
         if keep is not None:
             res["text_keep"] = keep
         if self.dataset is not None:

@@ -74,6 +74,121 @@ __global__ void router_head_bwd_kernel(float* dlogits, const float* dsparse, con
   }
 }
 
+// ---------------------------------------------------------------- router head with a selection bias (loss-free load balancing)
+// The head above with one change: the top-k runs over xout[e] + sel_bias[e].  probs, xout and the k gate weights -- the softmax of the RAW
+// xout over the selected experts -- never see the bias, so it has no gradient and router_head_bwd_kernel serves both heads.  The first pick
+// is no longer the largest raw value: the softmax is stabilised by the maximum of xout over the selected set.
+// load / target (both or neither): integer accumulators of the step.  load[e] counts the rows that selected e among the experts their mask
+// allows (a row with fewer allowed experts than k fills its top-k with masked ones at weight 0: the dispatch routes nothing there, and
+// nothing is counted); target[e] gains every allowing row's fair share round(2^20 min(k, a_b) / a_b), a_b = the row's allowed experts.
+// Integer sums do not depend on the order of the atomics.  Each wavefront reduces its 64 rows per expert in registers (a ballot for the
+// load, a 32-bit butterfly for the shares: 64 * 2^20 fits), one lane adds the result to the workgroup's LDS copy, and the workgroup ends
+// with E global atomics -- 256 lanes adding to the same few LDS words one by one cost more than the head itself.
+constexpr int BAL_SHIFT = 20;
+__global__ __launch_bounds__(TPB) void router_head_bias_fwd_kernel(float* sparse, float* probs, float* xout, int* idx, const float* logits,
+                                                                   const float* noise, const float* mask, const float* sel_bias,
+                                                                   unsigned long long* load, unsigned long long* target, int E, int k,
+                                                                   long B) {
+  __shared__ unsigned long long s_load[64], s_tgt[64];
+  const bool acc = load != nullptr;                             // kernel-uniform: the barriers below are reached by all threads or by none
+  if (acc) {
+    if ((int)threadIdx.x < 64) { s_load[threadIdx.x] = 0ull; s_tgt[threadIdx.x] = 0ull; }
+    __syncthreads();
+  }
+  // workgroup-uniform trip count: the wavefront reductions below need every lane, also those past the last row
+  for (long base = (long)blockIdx.x * blockDim.x; base < B; base += (long)gridDim.x * blockDim.x) {
+    const long b = base + threadIdx.x;
+    unsigned long long taken = 0ull, allow = 0ull;              // bit e: picked / allowed by the row's mask
+    unsigned share = 0u;
+    if (b < B) {
+      const float* lg = logits + b * E;
+      float* xo = xout + b * E;
+      float mx = -INFINITY;
+      int allowed = 0;
+      for (int e = 0; e < E; ++e) {
+        float v = lg[e];
+        if (noise) v += noise[b * E + e];
+        if (mask && mask[b * E + e] == 0.f) v = -INFINITY; else { ++allowed; allow |= 1ull << e; }
+        xo[e] = v;
+        mx = fmaxf(mx, v);
+      }
+      float sum = 0.f;
+      for (int e = 0; e < E; ++e) sum += expf(xo[e] - mx);
+      for (int e = 0; e < E; ++e) { probs[b * E + e] = expf(xo[e] - mx) / sum; sparse[b * E + e] = 0.f; }
+      // top-k of the biased scores by repeated argmax; ties -> lowest index.  -inf + bias stays -inf: a masked entry is picked last.
+      float top = -INFINITY;
+      for (int j = 0; j < k; ++j) {
+        int bi = -1; float bv = 0.f;
+        for (int e = 0; e < E; ++e) {
+          if ((taken >> e) & 1ull) continue;
+          const float s = xo[e] + sel_bias[e];
+          if (bi < 0 || s > bv) { bi = e; bv = s; }
+        }
+        taken |= 1ull << bi;
+        idx[b * k + j] = bi;
+        top = fmaxf(top, xo[bi]);
+      }
+      float ws = 0.f;
+      for (int j = 0; j < k; ++j) ws += expf(xo[idx[b * k + j]] - top);
+      for (int j = 0; j < k; ++j) sparse[b * E + idx[b * k + j]] = expf(xo[idx[b * k + j]] - top) / ws;
+      if (allowed > 0) {
+        const unsigned q = (unsigned)(k < allowed ? k : allowed);
+        share = ((q << BAL_SHIFT) + (unsigned)(allowed >> 1)) / (unsigned)allowed;       // <= 2^20
+      }
+    }
+    if (acc) {
+      const unsigned long long routed = taken & allow;
+      for (int e = 0; e < E; ++e) {
+        const unsigned long long picked = __ballot((routed >> e) & 1ull);
+        unsigned t = ((allow >> e) & 1ull) ? share : 0u;
+        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+        if ((threadIdx.x & 63) == 0) {
+          if (picked) atomicAdd(&s_load[e], (unsigned long long)__popcll(picked));
+          if (t) atomicAdd(&s_tgt[e], (unsigned long long)t);
+        }
+      }
+    }
+  }
+  if (acc) {
+    __syncthreads();
+    if ((int)threadIdx.x < E) {
+      if (s_load[threadIdx.x]) atomicAdd(&load[threadIdx.x], s_load[threadIdx.x]);
+      if (s_tgt[threadIdx.x]) atomicAdd(&target[threadIdx.x], s_tgt[threadIdx.x]);
+    }
+  }
+}
+
+// One wavefront, behind the optimizer.  `ok` (NULL = unguarded): the device verdict of hdmoe_mt_stats; 0 leaves the bias as it is.
+//   bias[e] += rate * sign(target[e] - 2^20 load[e])   (integers; a tie gives 0), then minus the mean, then clamped to +-bias_max;
+//   last_* = the accumulators; the accumulators = 0 -- both always: a skipped step's counts must not reach the next step's decision.
+// Every lane sums the E values in index order, so the mean does not depend on a reduction tree.
+__global__ __launch_bounds__(64) void balance_bias_update_kernel(float* bias, long long* load, long long* target, long long* last_load,
+                                                                 long long* last_target, const int* ok, float rate, float bias_max, int E) {
+  __shared__ float sb[64];
+  const int e = threadIdx.x;
+  const bool apply = !ok || *ok != 0;                          // workgroup-uniform
+  const long long l = e < E ? load[e] : 0ll, t = e < E ? target[e] : 0ll;
+  if (apply) {
+    float v = 0.f;
+    if (e < E) {
+      const long long d = t - l * (1ll << BAL_SHIFT);
+      v = bias[e] + rate * (d > 0 ? 1.f : (d < 0 ? -1.f : 0.f));
+      sb[e] = v;
+    }
+    __syncthreads();
+    if (e < E) {
+      float s = 0.f;
+      for (int i = 0; i < E; ++i) s += sb[i];
+      v -= s / (float)E;
+      bias[e] = fminf(fmaxf(v, -bias_max), bias_max);
+    }
+  }
+  if (e < E) {
+    last_load[e] = l; last_target[e] = t;
+    load[e] = 0ll; target[e] = 0ll;
+  }
+}
+
 // ---------------------------------------------------------------- dispatch plan (single workgroup)
 // routed pair (b, e) <=> sparse[b][e] > 0 (NaN > 0 is false: an all-masked sample is routed nowhere, as in the reference).
 // Output order: expert-major, sample-minor (stable) == the order x[mask] produces per expert.
@@ -227,6 +342,23 @@ int hdmoe_router_head_bwd(float* dlogits, const float* dsparse, const float* dpr
   hipLaunchKernelGGL(router_head_bwd_kernel, dim3(grid_for(B)), dim3(TPB), 0, stream, dlogits, dsparse, dprobs, dxout, sparse, probs, idx, mask, E, k, B);
   return hdmoe_launch_status();
 }
+int hdmoe_router_head_bias_fwd(float* sparse, float* probs, float* xout, int* idx, const float* logits, const float* noise,
+                               const float* mask, const float* sel_bias, long long* load, long long* target, long B, int E, int k,
+                               hipStream_t stream) {
+  if (E < 1 || E > 64 || k < 1 || k > E || B < 0 || !sel_bias || (load == nullptr) != (target == nullptr)) return HDMOE_EINVAL;
+  if (!sparse || !probs || !xout || !idx || !logits) return HDMOE_EINVAL;
+  if (B == 0) return HDMOE_OK;
+  hipLaunchKernelGGL(router_head_bias_fwd_kernel, dim3(grid_for(B)), dim3(TPB), 0, stream, sparse, probs, xout, idx, logits, noise, mask,
+                     sel_bias, (unsigned long long*)load, (unsigned long long*)target, E, k, B);
+  return hdmoe_launch_status();
+}
+int hdmoe_balance_bias_update(float* bias, long long* load, long long* target, long long* last_load, long long* last_target, const int* ok,
+                              float rate, float bias_max, int E, hipStream_t stream) {
+  if (!bias || !load || !target || !last_load || !last_target || E < 1 || E > 64) return HDMOE_EINVAL;
+  if (!(rate >= 0.f) || !(bias_max >= 0.f)) return HDMOE_EINVAL;          // (NaN fails both)
+  hipLaunchKernelGGL(balance_bias_update_kernel, dim3(1), dim3(64), 0, stream, bias, load, target, last_load, last_target, ok, rate, bias_max, E);
+  return hdmoe_launch_status();
+}
 int hdmoe_dispatch_plan(int* perm, int* row_expert, float* row_w, int* inv, int* seg, const float* sparse, int B, int E, int kcap,
                         hipStream_t stream) {
   if (B < 1 || E < 1 || E > 64 || kcap < 1 || kcap > E) return HDMOE_EINVAL;
@@ -292,6 +424,6 @@ int hdmoe_combine_rows_bwd(void* dys, float* dsparse, const void* dout, const vo
   else return HDMOE_EDTYPE;
   return hdmoe_launch_status();
 }
-int hdmoe_version(void) { return 300; }
+int hdmoe_version(void) { return 301; }
 
 }  // extern "C"

@@ -212,6 +212,19 @@ class Logger:
         record["per_group"] = per
         self._write_jsonl(self.log_dir / f"{self.run_name}_health.jsonl", record)
 
+    def log_balance(self, step: int, balance: Dict[str, Any]):
+        """One record of `hdmoe_hip.balance.RouterBalance.read` into <run>_balance.jsonl: step and, per router name, ``bias`` (the
+        selection bias behind the step's update), ``load`` (rows routed to each expert in the step) and ``load_over_target`` (1 = the
+        expert got its fair share of the rows that allow it; null where no row allowed it).  `balance` holds host values: no device work."""
+        record = {"step": int(step), "routers": {}}
+        for name, r in balance.items():
+            load = [int(v) for v in r["load"]]
+            target = [int(v) for v in r["target"]]
+            record["routers"][str(name)] = {
+                "bias": [float(v) for v in r["bias"]], "load": load,
+                "load_over_target": [round(l * float(1 << 20) / t, 6) if t > 0 else None for l, t in zip(load, target)]}
+        self._write_jsonl(self.log_dir / f"{self.run_name}_balance.jsonl", record)
+
     # ------------------------------------------------------------------ reference logger.py:328-345
     def _flush_training_log(self):
         if len(self.accumulators["step"]) == 0:

@@ -16,6 +16,8 @@ from .bank import invalidate_weights                       # noqa: F401
 from .ema import WeightEMA                                 # noqa: F401
 from . import posthoc                                      # noqa: F401
 from .posthoc import ReconstructedEMA                      # noqa: F401
+from . import balance                                      # noqa: F401
+from .balance import RouterBalance                         # noqa: F401
 
 _policy = {"compute_dtype": torch.float32}
 

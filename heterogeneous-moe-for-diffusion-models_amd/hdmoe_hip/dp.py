@@ -108,6 +108,9 @@ class GradBuckets:
             for l in lists:
                 object.__setattr__(l, "_hdmoe_usage", self.usage[off:off + len(l)])
                 off += len(l)
+        # Routers with a selection bias (hdmoe_hip/balance.py) count their routing in int64 accumulators: summed over the ranks next to the
+        # usage counters, as one tensor, so that every rank moves its bias by the same sign.
+        self._balanced = [mod for mod in module.modules() if "balance_load" in getattr(mod, "_buffers", {})]
         self._usage_work = None
         self._pending = [0] * len(self.buckets)
         self._works = [None] * len(self.buckets)
@@ -187,6 +190,12 @@ class GradBuckets:
         self._next = 0
         if self.usage is not None and (self.world > 1 or self.force):
             dist.all_reduce(self.usage, op=dist.ReduceOp.SUM, group=self.group, async_op=True).wait()
+        if self._balanced and (self.world > 1 or self.force):
+            accs = [mod._buffers[k] for mod in self._balanced for k in ("balance_load", "balance_target")]
+            flat = torch.cat(accs)
+            dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self.group, async_op=True).wait()
+            for acc, part in zip(accs, flat.split([a.numel() for a in accs])):
+                acc.copy_(part)
         for bi, w in enumerate(self._works):
             if w is not None:
                 w.wait()

@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes
 import functools
 import math
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -3003,10 +3003,68 @@ class _RouterHeadFn(torch.autograd.Function):
         return dl, None, None, None
 
 
-def router_head(logits: Tensor, noise: Optional[Tensor], mask: Optional[Tensor], k: int):
+class _RouterHeadBiasFn(torch.autograd.Function):
+    """The head with a selection bias (hdmoe_router_head_bias_fwd): the bias decides which experts are picked and nothing else, so it has
+    no gradient and the backward is the plain head's, from the saved idx and sparse."""
+
+    @staticmethod
+    def forward(ctx, logits, noise, mask, k, sel_bias, load, target):
+        logits = _f32(logits)
+        B, E = logits.shape
+        noise = None if noise is None else _f32(noise)
+        mask = None if mask is None else _c(mask.to(torch.float32))
+        sparse = torch.empty_like(logits)
+        probs = torch.empty_like(logits)
+        xout = torch.empty_like(logits)
+        idx = torch.empty((B, k), dtype=torch.int32, device=logits.device)
+        call("hdmoe_router_head_bias_fwd", sparse, probs, xout, idx, logits, noise, mask, sel_bias, load, target, B, E, k)
+        ctx.save_for_backward(sparse, probs, idx, mask)
+        ctx.k = k
+        ctx.mark_non_differentiable(idx)
+        return sparse, probs, xout, idx
+
+    @staticmethod
+    def backward(ctx, dsparse, dprobs, dxout, _didx):
+        return _RouterHeadFn.backward(ctx, dsparse, dprobs, dxout, _didx) + (None, None, None)
+
+
+def router_head(logits: Tensor, noise: Optional[Tensor], mask: Optional[Tensor], k: int, sel_bias: Optional[Tensor] = None,
+                accum: Optional[Tuple[Tensor, Tensor]] = None):
     """masked_fill -> softmax -> top-k -> softmax(top-k) -> sparse scatter (model_components.py:158-168).
-    Returns (sparse_weights, gate_probs, masked_logits, topk_idx int32)."""
-    return _RouterHeadFn.apply(logits, noise, mask, int(k))
+    Returns (sparse_weights, gate_probs, masked_logits, topk_idx int32).
+    ``sel_bias`` (E,) fp32: the top-k runs over masked_logits + sel_bias, while the gate probabilities, the returned logits and the k gate
+    weights (the softmax of the raw logits over the picked experts) stay free of it.  ``accum`` = (load, target), int64 (E,) each: the
+    call adds the rows routed to every expert and 2^20 times every expert's fair share of the rows that allow it (include/hdmoe.h).
+    Without a bias the call is the plain head's, whatever else is passed."""
+    if sel_bias is None:
+        if accum is not None:
+            raise ValueError("router_head: accum needs sel_bias (the plain head does not count)")
+        return _RouterHeadFn.apply(logits, noise, mask, int(k))
+    E = logits.shape[-1]
+    if sel_bias.dtype != torch.float32 or sel_bias.numel() != E or not sel_bias.is_contiguous() or sel_bias.device != logits.device:
+        raise ValueError(f"router_head: sel_bias is a contiguous float32 tensor of {E} entries on the logits' device")
+    load = target = None
+    if accum is not None:
+        load, target = accum
+        for t in (load, target):
+            if t.dtype != torch.int64 or t.numel() != E or not t.is_contiguous() or t.device != logits.device:
+                raise ValueError(f"router_head: accum is a pair of contiguous int64 tensors of {E} entries on the logits' device")
+    return _RouterHeadBiasFn.apply(logits, noise, mask, int(k), sel_bias, load, target)
+
+
+def balance_bias_update(bias: Tensor, load: Tensor, target: Tensor, last_load: Tensor, last_target: Tensor, ok: Optional[Tensor],
+                        rate: float, bias_max: float) -> None:
+    """One launch (hdmoe_balance_bias_update): where ``ok`` (device int32 or None) does not read 0, bias += rate * sign(target - 2^20 load),
+    re-centred and clamped to +-bias_max; always last_* = the accumulators and the accumulators = 0."""
+    E = bias.numel()
+    if bias.dtype != torch.float32 or not bias.is_contiguous():
+        raise ValueError("balance_bias_update: bias is a contiguous float32 tensor")
+    for t in (load, target, last_load, last_target):
+        if t.dtype != torch.int64 or t.numel() != E or not t.is_contiguous() or t.device != bias.device:
+            raise ValueError(f"balance_bias_update: the accumulators and their copies are contiguous int64 tensors of {E} entries")
+    if ok is not None and (ok.dtype != torch.int32 or ok.numel() < 1 or ok.device != bias.device):
+        raise ValueError("balance_bias_update: ok is an int32 tensor on the bias's device")
+    call("hdmoe_balance_bias_update", bias, load, target, last_load, last_target, ok, float(rate), float(bias_max), E)
 
 
 class DispatchPlan:

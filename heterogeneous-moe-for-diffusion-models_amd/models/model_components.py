@@ -73,6 +73,19 @@ class Router(nn.Module):
         self.linear = m.MP_Conv(in_channels=in_channels * 4, out_channels=num_experts, kernel=())
         self.k = top_k
 
+    def enable_balance(self) -> None:
+        """Auxiliary-loss-free load balancing (hdmoe_hip.balance.RouterBalance): from now on the top-k runs over logits + ``balance_bias``
+        (num_experts, fp32, zeros), in every mode; gate probabilities, logits and gate weights never see the bias.  A training forward
+        with grad enabled also adds its routing into ``balance_load`` / ``balance_target`` (int64; include/hdmoe.h,
+        hdmoe_router_head_bias_fwd), which `RouterBalance.step` turns into the next bias and clears.  The three buffers are
+        non-persistent: state_dict() keeps the reference's layout, and the bias travels in the checkpoint's "router_balance"."""
+        if "balance_bias" in self._buffers:
+            return
+        E, dev = self.linear.weights.shape[0], self.linear.weights.device
+        self.register_buffer("balance_bias", torch.zeros(E, dtype=torch.float32, device=dev), persistent=False)
+        self.register_buffer("balance_load", torch.zeros(E, dtype=torch.int64, device=dev), persistent=False)
+        self.register_buffer("balance_target", torch.zeros(E, dtype=torch.int64, device=dev), persistent=False)
+
     def _fwd(self, x: Tensor, time_emb: Tensor, mask: Optional[Tensor], zeta):
         """x channel-last (B,H,W,C); returns (sparse, probs, logits, topk_idx)."""
         hr = self.hard_route
@@ -99,7 +112,13 @@ class Router(nn.Module):
         x = ops.adaln(x, cond)
         logits = self.linear._fwd(x)
         noise = ops.randn_like(logits, zeta) if self.training else None
-        return ops.router_head(logits, noise, mask, self.k)
+        bias = self._buffers.get("balance_bias")
+        if bias is None:
+            return ops.router_head(logits, noise, mask, self.k)
+        # the sampler, the guided evaluation and the Evaluator route as training did; only a step that trains counts its routing
+        count = self.training and torch.is_grad_enabled()
+        return ops.router_head(logits, noise, mask, self.k, sel_bias=bias,
+                               accum=(self._buffers["balance_load"], self._buffers["balance_target"]) if count else None)
 
     def forward(self, x: Tensor, time_emb: Tensor, mask: Optional[Tensor] = None, zeta: Optional[float] = 1e-2):
         sparse, probs, logits, _ = self._fwd(ops.to_nhwc(x), time_emb, mask, zeta)

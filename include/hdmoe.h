@@ -584,6 +584,21 @@ int hdmoe_router_head_bwd(float* dlogits, const float* dsparse, const float* dpr
                           HS stream);
 int hdmoe_dispatch_plan(int* perm, int* row_expert, float* row_w, int* inv, int* seg, const float* sparse, int B, int E,
                         int kcap, HS stream);
+/* The head with a per-expert selection bias (auxiliary-loss-free load balancing): the top-k runs over xout[e] + sel_bias[e] (ties to the
+ * lowest index, masked entries stay -inf); probs, xout and the k gate weights -- the softmax of the raw xout over the selected experts,
+ * stabilised by their maximum -- do not see the bias, and the backward is hdmoe_router_head_bwd from the saved idx and sparse.  With a
+ * zero bias every output is bit-identical to hdmoe_router_head_fwd.  load / target (E each; both or neither) are ACCUMULATED: load[e] += 1
+ * per row that selected e among the experts its mask allows (a row with fewer allowed experts than k fills up with masked ones at weight 0:
+ * not counted), target[e] += round(2^20 min(k, a_b) / a_b) per row b whose mask allows e, a_b = that row's allowed experts (E without a
+ * mask; rows with a_b = 0 add nothing).  Integers: the sums do not depend on the order of the atomics. */
+int hdmoe_router_head_bias_fwd(float* sparse, float* probs, float* xout, int* idx, const float* logits, const float* noise,
+                               const float* mask, const float* sel_bias, long long* load, long long* target, long B, int E, int k,
+                               HS stream);
+/* One launch behind the optimizer step.  ok NULL or *ok != 0: bias[e] += rate * sign(target[e] - 2^20 load[e]) (compared in integers, a tie
+ * gives 0), then the mean over e is subtracted, then the result is clamped to [-bias_max, bias_max]; *ok == 0 leaves bias bit for bit.
+ * Always: last_load / last_target = the accumulators, then the accumulators are cleared. */
+int hdmoe_balance_bias_update(float* bias, long long* load, long long* target, long long* last_load, long long* last_target,
+                              const int* ok, float rate, float bias_max, int E, HS stream);
 /* counts[e] += seg[e+1] - seg[e] as float: rows routed to expert e since the last optimizer step (read by hdmoe_mt_adamw's `use` flags;
  * cleared by the caller behind the update) */
 int hdmoe_seg_counts(float* counts, const int* seg, int E, HS stream);

@@ -64,6 +64,8 @@ def trainer_leg(mode, args):
         kw = dict(kw, cond_dropout=args.cond_dropout, null_text_emb=torch.randn(77, mcfg["text_emb_dim"], generator=torch.Generator().manual_seed(7)))
     if args.skip_nonfinite:                                     # the device-side non-finite guard (tools/health_bench.py)
         kw = dict(kw, skip_nonfinite=True)
+    if args.balance_rate > 0:                                   # the routers' selection bias (tools/balance_bench.py)
+        kw = dict(kw, balance_rate=args.balance_rate)
     tr = training.Trainer(model, mcfg, configs.optim_configs, configs.loss_configs, configs.mask_configs, configs.zeta_configs, **kw)
     B = args.batch or bc["batch"]
     g = torch.Generator(device=dev).manual_seed(1234)
@@ -122,6 +124,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r10_trainer_graphed.json"))
     ap.add_argument("--cond-dropout", type=float, default=0.0, help="Trainer(cond_dropout=...) in every trainer leg")
     ap.add_argument("--skip-nonfinite", action="store_true", help="Trainer(skip_nonfinite=True) in every trainer leg")
+    ap.add_argument("--balance-rate", type=float, default=0.0, help="Trainer(balance_rate=...) in every trainer leg")
     ap.add_argument("--leg", default="", help=argparse.SUPPRESS)       # one trainer leg in this (child) process
     args = ap.parse_args()
     if args.steps < 50:
@@ -136,7 +139,7 @@ def main():
         res["bench_py"]["parent"] = bench_leg(os.path.abspath(args.parent_tree), args.bench_steps, args.warmup, args.bench_repeats)
     for mode in ("eager", "eager_device_inputs", "graphed"):
         out = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", mode, "--steps", str(args.steps), "--blocks", str(args.blocks),
-                              "--warmup", str(args.warmup), "--batch", str(args.batch), "--cond-dropout", str(args.cond_dropout)] + (["--skip-nonfinite"] if args.skip_nonfinite else []), check=True, capture_output=True, text=True, timeout=420).stdout
+                              "--warmup", str(args.warmup), "--batch", str(args.batch), "--cond-dropout", str(args.cond_dropout), "--balance-rate", str(args.balance_rate)] + (["--skip-nonfinite"] if args.skip_nonfinite else []), check=True, capture_output=True, text=True, timeout=420).stdout
         res[mode] = json.loads([l for l in out.splitlines() if l.startswith("LEG ")][-1][4:])
         print(f"[trainer_loop_bench] {mode}: {res[mode]['ms_per_step']} ms/step, host {res[mode]['host_enqueue_ms_per_step']} ms/step", file=sys.stderr, flush=True)
     res["graphed_over_eager"] = round(res["graphed"]["ms_per_step"] / res["eager"]["ms_per_step"], 4)
