@@ -21,7 +21,7 @@ from typing import Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from .utils import LatentDataset, _null_row, null_text
+from .utils import LatentDataset, _null_row, model_extras, null_text
 
 MAX_LEVELS, MAX_BATCH = 64, 4096
 
@@ -109,10 +109,8 @@ class Evaluator:
         self.first, self.n_rank = rank_slice(dataset.N, world, rank)
         self.E = int(model_config["num_experts"])
         self.sigma_data = float(model_config["sigma_data"])
-        names = inspect.signature(model.forward).parameters
-        # as Trainer._model_extra: model_config2 takes the soft-gate transition from the mask config
-        self._model_extra = {"transition_point": mask_config["p_mean"], "softness": mask_config["p_std"]} if "transition_point" in names else {}
-        if "return_log_var" in names:
+        self._model_extra = model_extras(model, mask_config)
+        if "return_log_var" in inspect.signature(model.forward).parameters:
             self._model_extra["return_log_var"] = True
         self.buf = None                                      # static buffers, allocated by the first evaluate()
         self._step = None                                    # hdmoe_hip.graph.GraphedStep of the batch
@@ -134,7 +132,7 @@ class Evaluator:
         self._null = _null_row(self.null_text_emb, ds.text)
 
     def _inputs(self, rnd: int, first: int, count: int) -> None:
-        """The batch's inputs into the static buffers.  round, first and count are launch scalars, so -- like `Trainer._data` in front
+        """The batch's inputs into the static buffers.  round, first and count are launch scalars, so -- like `Trainer._batch` in front
         of its captured step -- these launches are enqueued eagerly in front of every replay; nothing syncs."""
         from hdmoe_hip import ops
         b, ds = self.buf, self.dataset

@@ -14,6 +14,7 @@ Differences that are deliberate and visible:
 """
 from __future__ import annotations
 
+import collections
 import math
 import os
 from typing import Any, Callable, Dict, Iterable, Optional, Union
@@ -22,7 +23,7 @@ import torch
 
 from hdmoe_hip.dp import GradBuckets
 from hdmoe_hip.optim import FusedAdamW
-from .utils import EDM_LOSS, DeviceInputs, LatentDataset, MaskGenerator, ZetaScheduler, null_text, sample_sigma_hybrid
+from .utils import EDM_LOSS, DeviceInputs, LatentDataset, MaskGenerator, ZetaScheduler, model_extras, null_text, sample_sigma_hybrid
 
 
 def build_optimizer(model: torch.nn.Module, optim_config: Dict[str, Any]) -> FusedAdamW:
@@ -91,6 +92,72 @@ def load_checkpoint(path: str, model: torch.nn.Module, optimizer: Optional[torch
     if balance is not None and "router_balance" in ck:
         balance.load_state_dict(ck["router_balance"])
     return ck
+
+
+# The inputs of one step, whichever arm of `Trainer._batch` made them: x the noised latents, x0 the clean ones, keep the text-dropout
+# decision (B,) float32 0/1 or None.
+Batch = collections.namedtuple("Batch", "x x0 sigma text unet_mask vit_mask zeta keep")
+
+
+def _is_count(val) -> bool:
+    return not isinstance(val, bool) and isinstance(val, int) and val >= 1
+
+
+def _due(every: Optional[int], step: int) -> bool:
+    """Whether what runs behind every `every`-th update (None: never) runs behind the update of step `step`."""
+    return every is not None and (step + 1) % every == 0
+
+
+def _check_arguments(world, fuse_clip_into_step, ema, ema_snapshot_every, ema_snapshot_dir, cond_dropout, null_text_emb, dataset, batch_size,
+                     evaluator, eval_every, skip_nonfinite, health_every, max_skips_in_a_row, balance_rate, balance_bias_max) -> None:
+    """ValueError for every violated condition on `Trainer`'s keywords, in front of any use of the model."""
+    if dataset is None:
+        if batch_size is not None:
+            raise ValueError("Trainer: batch_size is the dataset's batch size; without a dataset the caller's batches fix it")
+    else:
+        if not isinstance(dataset, LatentDataset):
+            raise ValueError(f"Trainer: dataset is a Utils.utils.LatentDataset, got {type(dataset).__name__}")
+        if dataset.text is None:
+            raise ValueError("Trainer: the dataset needs text rows (LatentDataset(text=...)): the model is text-conditioned")
+        if batch_size is None or int(batch_size) < 1:
+            raise ValueError(f"Trainer: a dataset needs batch_size >= 1, got {batch_size}")
+        if dataset.N < int(batch_size) * world:
+            raise ValueError(f"Trainer: the dataset's N={dataset.N} items do not fill one step of batch_size * world = "
+                             f"{int(batch_size)} * {world}")
+    if ema_snapshot_every is not None:
+        if ema is None:
+            raise ValueError("Trainer: ema_snapshot_every needs an ema")
+        if ema_snapshot_dir is None:
+            raise ValueError("Trainer: ema_snapshot_every needs ema_snapshot_dir")
+        if int(ema_snapshot_every) < 1:
+            raise ValueError(f"Trainer: ema_snapshot_every must be >= 1, got {ema_snapshot_every}")
+    if eval_every is not None:
+        if evaluator is None:
+            raise ValueError("Trainer: eval_every needs an evaluator")
+        if not _is_count(eval_every):
+            raise ValueError(f"Trainer: eval_every must be an int >= 1, got {eval_every}")
+    elif evaluator is not None:
+        raise ValueError("Trainer: an evaluator needs eval_every")
+    if evaluator is not None and not callable(getattr(evaluator, "evaluate", None)):
+        raise ValueError(f"Trainer: evaluator is a Utils.evaluation.Evaluator, got {type(evaluator).__name__}")
+    if not isinstance(skip_nonfinite, bool):
+        raise ValueError(f"Trainer: skip_nonfinite is a bool, got {skip_nonfinite!r}")
+    if skip_nonfinite and not fuse_clip_into_step:
+        raise ValueError("Trainer: skip_nonfinite needs fuse_clip_into_step (the verdict guards the fused clip + AdamW launch)")
+    for key, val in (("health_every", health_every), ("max_skips_in_a_row", max_skips_in_a_row)):
+        if val is not None and not _is_count(val):
+            raise ValueError(f"Trainer: {key} must be an int >= 1, got {val!r}")
+    if max_skips_in_a_row is not None and (not skip_nonfinite or health_every is None):
+        raise ValueError("Trainer: max_skips_in_a_row needs skip_nonfinite and a health_every (the counters are only seen when read)")
+    for key, val in (("balance_rate", balance_rate), ("balance_bias_max", balance_bias_max)):
+        if val is None and key == "balance_rate":
+            continue
+        if isinstance(val, bool) or not isinstance(val, (int, float)) or not math.isfinite(val) or val <= 0:
+            raise ValueError(f"Trainer: {key} must be a finite number > 0, got {val!r}")
+    if not 0.0 <= float(cond_dropout) <= 1.0:                # NaN fails both comparisons
+        raise ValueError(f"Trainer: cond_dropout must lie in [0, 1], got {cond_dropout}")
+    if null_text_emb is not None and not torch.is_tensor(null_text_emb):
+        raise ValueError(f"Trainer: null_text_emb is a tensor of one text row or None, got {type(null_text_emb).__name__}")
 
 
 class Trainer:
@@ -165,61 +232,16 @@ class Trainer:
                  balance_bias_max: float = 8.0):
         dist = torch.distributed.is_available() and torch.distributed.is_initialized()
         self.world, self.rank = (torch.distributed.get_world_size(), torch.distributed.get_rank()) if dist else (1, 0)
-        if dataset is None:
-            if batch_size is not None:
-                raise ValueError("Trainer: batch_size is the dataset's batch size; without a dataset the caller's batches fix it")
-        else:
-            if not isinstance(dataset, LatentDataset):
-                raise ValueError(f"Trainer: dataset is a Utils.utils.LatentDataset, got {type(dataset).__name__}")
-            if dataset.text is None:
-                raise ValueError("Trainer: the dataset needs text rows (LatentDataset(text=...)): the model is text-conditioned")
-            if batch_size is None or int(batch_size) < 1:
-                raise ValueError(f"Trainer: a dataset needs batch_size >= 1, got {batch_size}")
-            if dataset.N < int(batch_size) * self.world:
-                raise ValueError(f"Trainer: the dataset's N={dataset.N} items do not fill one step of batch_size * world = "
-                                 f"{int(batch_size)} * {self.world}")
+        _check_arguments(self.world, fuse_clip_into_step, ema, ema_snapshot_every, ema_snapshot_dir, cond_dropout, null_text_emb, dataset,
+                         batch_size, evaluator, eval_every, skip_nonfinite, health_every, max_skips_in_a_row, balance_rate, balance_bias_max)
         self.dataset, self.batch_size = dataset, None if batch_size is None else int(batch_size)
-        if ema_snapshot_every is not None:
-            if ema is None:
-                raise ValueError("Trainer: ema_snapshot_every needs an ema")
-            if ema_snapshot_dir is None:
-                raise ValueError("Trainer: ema_snapshot_every needs ema_snapshot_dir")
-            if int(ema_snapshot_every) < 1:
-                raise ValueError(f"Trainer: ema_snapshot_every must be >= 1, got {ema_snapshot_every}")
-        if eval_every is not None:
-            if evaluator is None:
-                raise ValueError("Trainer: eval_every needs an evaluator")
-            if isinstance(eval_every, bool) or not isinstance(eval_every, int) or eval_every < 1:
-                raise ValueError(f"Trainer: eval_every must be an int >= 1, got {eval_every}")
-        elif evaluator is not None:
-            raise ValueError("Trainer: an evaluator needs eval_every")
-        if evaluator is not None and not callable(getattr(evaluator, "evaluate", None)):
-            raise ValueError(f"Trainer: evaluator is a Utils.evaluation.Evaluator, got {type(evaluator).__name__}")
         # every `eval_every` steps, behind the update: evaluator.evaluate() on the raw weights and, when the evaluator holds this
         # trainer's ema, on each of its profiles -> last_eval, and the logger's <run>_validation.jsonl
         self.evaluator, self.eval_every, self.last_eval = evaluator, eval_every, None
-        if not isinstance(skip_nonfinite, bool):
-            raise ValueError(f"Trainer: skip_nonfinite is a bool, got {skip_nonfinite!r}")
-        if skip_nonfinite and not fuse_clip_into_step:
-            raise ValueError("Trainer: skip_nonfinite needs fuse_clip_into_step (the verdict guards the fused clip + AdamW launch)")
-        for key, val in (("health_every", health_every), ("max_skips_in_a_row", max_skips_in_a_row)):
-            if val is not None and (isinstance(val, bool) or not isinstance(val, int) or val < 1):
-                raise ValueError(f"Trainer: {key} must be an int >= 1, got {val!r}")
-        if max_skips_in_a_row is not None and (not skip_nonfinite or health_every is None):
-            raise ValueError("Trainer: max_skips_in_a_row needs skip_nonfinite and a health_every (the counters are only seen when read)")
         # skip_nonfinite: every step's update runs behind the device verdict of one statistics pass over the gradients; health_every: that
         # pass's rows (and the parameters') are read every n-th step -> last_health, the logger's <run>_health.jsonl
         self.skip_nonfinite, self.health_every, self.max_skips_in_a_row = skip_nonfinite, health_every, max_skips_in_a_row
         self.last_health, self._health = None, None
-        for key, val in (("balance_rate", balance_rate), ("balance_bias_max", balance_bias_max)):
-            if val is None and key == "balance_rate":
-                continue
-            if isinstance(val, bool) or not isinstance(val, (int, float)) or not math.isfinite(val) or val <= 0:
-                raise ValueError(f"Trainer: {key} must be a finite number > 0, got {val!r}")
-        if not 0.0 <= float(cond_dropout) <= 1.0:            # NaN fails both comparisons
-            raise ValueError(f"Trainer: cond_dropout must lie in [0, 1], got {cond_dropout}")
-        if null_text_emb is not None and not torch.is_tensor(null_text_emb):
-            raise ValueError(f"Trainer: null_text_emb is a tensor of one text row or None, got {type(null_text_emb).__name__}")
         self.cond_dropout, self.null_text_emb = float(cond_dropout), null_text_emb
         self.model, self.cfg, self.mask_cfg = model, model_config, mask_config
         self.optimizer = build_optimizer(model, optim_config)
@@ -260,96 +282,82 @@ class Trainer:
             self.seed = int(seed)
             self.inputs = DeviceInputs(model_config, mask_config, zeta_config, self.unet_mask_gen, self.vit_mask_gen, self.zeta_sched,
                                        seed=self.seed, rank=self.rank, cond_dropout=self.cond_dropout, null_text_emb=null_text_emb)
-        # model_config2 takes the soft-gate transition from the mask config; model_config1 learns its scaling and has no such arguments
-        import inspect
-        names = inspect.signature(model.forward).parameters
-        self._model_extra = {"transition_point": mask_config["p_mean"], "softness": mask_config["p_std"]} if "transition_point" in names else {}
+        self._model_extra = model_extras(model, mask_config)
         self._staged = None                                  # hdmoe_hip.graph.StagedStep, built by the first graphed train_step
         self._lat = self._text = None                        # its static latent / text buffers
 
-    def _fwd_loss(self, x, x0, sigma, text, unet_mask, vit_mask, zeta):
-        out_model = self.model(x=x, sigma=sigma, text_emb=text, Unet_router_mask=unet_mask, Vit_router_mask=vit_mask, zeta=zeta,
+    def _batch(self, latents: Optional[torch.Tensor], text: Optional[torch.Tensor], step: int, text_out: Optional[torch.Tensor] = None) -> Batch:
+        """The inputs of step `step`: the one place where the input modes differ.  `text_out` is the captured step's static text buffer;
+        with it the caller's batch is copied into the static buffers (the text substitution is that copy) and the dataset's text rows
+        are gathered there -- its latents are made where the captured step reads them, nothing is copied."""
+        if not self.device_inputs:                           # torch's generator, in this order: dropout, sigma, noise
+            cfg, mc, keep = self.cfg, self.mask_cfg, None
+            if self.cond_dropout > 0:                        # no key to be faithful to in this mode
+                null = null_text(self.null_text_emb, text)
+                kept = torch.rand(text.shape[0], device=text.device) >= self.cond_dropout
+                text = torch.where(kept.view(-1, *([1] * (text.ndim - 1))), text, null)
+                keep = kept.to(torch.float32)
+            sigma = sample_sigma_hybrid(batch_size=latents.shape[0], sigma_max=cfg["sigma_max"], sigma_min=cfg["sigma_min"],
+                                        p_mean=mc["p_mean"], p_std=mc["p_std"], extreme_prob=0.5, device=latents.device)
+            return Batch(latents + torch.randn_like(latents) * sigma, latents, sigma, text, self.unet_mask_gen(sigma=sigma, step=step),
+                         self.vit_mask_gen(sigma=sigma, step=step), self.zeta_sched.get_zeta(step=step), keep)
+        if self.dataset is not None:                         # drawn by the generator into its own static buffers
+            b = self.inputs.generate_from(self.dataset, step, self.batch_size, world=self.world, rank=self.rank)
+            text, keep = self.inputs.text_from(self.dataset, step, out=text_out)
+            return Batch(b["x"], b["x0"], b["sigma"], text, b["unet_mask"], b["vit_mask"], b["zeta"], keep if self.cond_dropout > 0 else None)
+        keep = None
+        if text_out is not None:
+            latents = self._lat.copy_(latents)
+        elif latents.dtype != torch.float32 or not latents.is_contiguous():
+            latents = latents.to(torch.float32).contiguous()
+        if self.cond_dropout > 0:
+            text, keep = self.inputs.drop_text(text, step, out=text_out)
+        elif text_out is not None:
+            text = text_out.copy_(text)
+        b = self.inputs.generate(latents, step)
+        return Batch(b["x"], latents, b["sigma"], text, b["unet_mask"], b["vit_mask"], b["zeta"], keep)
+
+    def _fwd_loss(self, b: Batch):
+        out_model = self.model(x=b.x, sigma=b.sigma, text_emb=b.text, Unet_router_mask=b.unet_mask, Vit_router_mask=b.vit_mask, zeta=b.zeta,
                                return_log_var=True, **self._model_extra)
-        return out_model, self.criterion(sigma_vec=sigma, x=x0, sigma=sigma, out_model=out_model)
+        return out_model, self.criterion(sigma_vec=b.sigma, x=b.x0, sigma=b.sigma, out_model=out_model)
 
-    def _build_staged(self, latent_images: torch.Tensor, text_emb: torch.Tensor) -> None:
-        """Fix the shapes, fill the static buffers for `step_idx` and capture the staged step (bench.py's replay path)."""
-        if not latent_images.is_cuda:
-            raise RuntimeError("hdmoe_hip: tensors must live on the GPU (no CPU fallback in the product path)")
-        dev = latent_images.device
-        self._lat = latent_images.detach().to(torch.float32).contiguous().clone()
-        if self.cond_dropout > 0:                            # the substitution is the copy into the static buffer
-            self._text = torch.empty(text_emb.shape, dtype=text_emb.dtype, device=dev)
-            self.inputs.drop_text(text_emb, self.step_idx, out=self._text)
+    def _build_staged(self, latents: Optional[torch.Tensor], text: Optional[torch.Tensor]) -> None:
+        """Fix the shapes, make the static buffers, fill them for `step_idx` and capture the staged step (bench.py's replay path).  With
+        a dataset the latent buffer is the generator's own x0."""
+        if self.dataset is not None:
+            ds = self.dataset
+            self._text = torch.empty((self.batch_size,) + tuple(ds.text.shape[1:]), dtype=ds.text.dtype, device=ds.device)
         else:
-            self._text = text_emb.detach().contiguous().clone()
-        self._shapes = (tuple(latent_images.shape), tuple(text_emb.shape))
-        self._capture(self.inputs.generate(self._lat, self.step_idx), self._lat, dev)
+            if not latents.is_cuda:
+                raise RuntimeError("hdmoe_hip: tensors must live on the GPU (no CPU fallback in the product path)")
+            self._shapes = (tuple(latents.shape), tuple(text.shape))
+            self._lat = torch.empty(latents.shape, dtype=torch.float32, device=latents.device)     # `_batch` fills both: a clone each
+            self._text = torch.empty(text.shape, dtype=text.dtype, device=latents.device)
+        batch = self._batch(latents, text, self.step_idx, text_out=self._text)
+        self._lat = batch.x0
+        self._capture(batch)
 
-    def _data(self, text_out: Optional[torch.Tensor] = None):
-        """The dataset's batch of `step_idx` in the generator's static buffers: (buffers, text, keep)."""
-        b = self.inputs.generate_from(self.dataset, self.step_idx, self.batch_size, world=self.world, rank=self.rank)
-        text, keep = self.inputs.text_from(self.dataset, self.step_idx, out=text_out)
-        return b, text, keep if self.cond_dropout > 0 else None
-
-    def _build_staged_dataset(self) -> None:
-        """`_build_staged` over the generator's own buffers: x0 and x are written where the captured step reads them, the text rows are
-        gathered into the static text buffer, nothing is copied."""
-        row = tuple(self.dataset.text.shape[1:])
-        self._text = torch.empty((self.batch_size,) + row, dtype=self.dataset.text.dtype, device=self.dataset.device)
-        b, _, _ = self._data(self._text)
-        self._lat = b["x0"]
-        self._capture(b, b["x0"], self.dataset.device)
-
-    def _capture(self, b: dict, x0: torch.Tensor, dev) -> None:
+    def _capture(self, b: Batch) -> None:
         from hdmoe_hip import graph as hgraph
 
         def fwd_bwd():
             self.buckets.zero_grad()
-            out_model, loss = self._fwd_loss(b["x"], x0, b["sigma"], self._text, b["unet_mask"], b["vit_mask"], b["zeta"])
+            out_model, loss = self._fwd_loss(b)
             hgraph.backward(loss["loss"])
             return {"loss": loss, "out_model": out_model}
 
         self.buckets.enabled = False                         # no collectives from autograd hooks while capturing
         try:
-            self._staged = hgraph.StagedStep(fwd_bwd, dev)
+            self._staged = hgraph.StagedStep(fwd_bwd, b.x0.device)
         finally:
             self.buckets.enabled = True
         if self.buckets.world > 1 or self.buckets.force:     # a branch's bucket goes out as soon as its backward section is launched
             self._staged.after = self.buckets.staged_hooks(self._staged)
         # the warm-up forwards accumulated into the routed-row counters: the first optimizer step must see only its own routing
-        seen = set()
-        for lst, _ in self.optimizer._usage.values():
-            u = getattr(lst, "_hdmoe_usage", None)
-            if u is not None and id(lst) not in seen:
-                seen.add(id(lst))
-                u.zero_()
+        self.optimizer.clear_usage()
         if self.balance is not None:                         # ... and so must the first move of the selection bias
             self.balance.clear()
-
-    def _graphed_fwd_bwd(self, latent_images: Optional[torch.Tensor], text_emb: Optional[torch.Tensor]):
-        if self.dataset is not None:
-            if self._staged is None:
-                self._build_staged_dataset()
-            b, _, keep = self._data(self._text)
-            res = self._staged()
-            self.buckets.finish()
-            return res["out_model"], res["loss"], b["sigma"], keep
-        if self._staged is None:
-            self._build_staged(latent_images, text_emb)
-        elif (tuple(latent_images.shape), tuple(text_emb.shape)) != self._shapes:
-            raise ValueError(f"Trainer(graphed=True): batch shapes {tuple(latent_images.shape)}, {tuple(text_emb.shape)} differ from the "
-                             f"captured step's {self._shapes[0]}, {self._shapes[1]}")
-        self._lat.copy_(latent_images)
-        keep = None
-        if self.cond_dropout > 0:
-            keep = self.inputs.drop_text(text_emb, self.step_idx, out=self._text)[1]
-        else:
-            self._text.copy_(text_emb)
-        b = self.inputs.generate(self._lat, self.step_idx)
-        res = self._staged()
-        self.buckets.finish()
-        return res["out_model"], res["loss"], b["sigma"], keep
 
     def train_step(self, latent_images: Optional[torch.Tensor] = None, text_emb: Optional[torch.Tensor] = None) -> dict:
         """One iteration on (latents (B,C,H,W), text embeddings), or with a dataset on the batch the trainer draws for `step_idx` (no
@@ -359,50 +367,26 @@ class Trainer:
             raise ValueError("Trainer: with a dataset train_step() takes no batch; the trainer draws it")
         if self.dataset is None and (latent_images is None or text_emb is None):
             raise ValueError("Trainer: train_step(latents, text_emb) needs a batch (or build the Trainer with dataset=...)")
-        if self.device_inputs:
-            return self._train_step_device(latent_images, text_emb)
-        cfg, mc, step = self.cfg, self.mask_cfg, self.step_idx
-        dev = latent_images.device
-        keep = None
-        if self.cond_dropout > 0:                            # no key to be faithful to in this mode: torch's generator
-            null = null_text(self.null_text_emb, text_emb)
-            kept = torch.rand(text_emb.shape[0], device=text_emb.device) >= self.cond_dropout
-            text_emb = torch.where(kept.view(-1, *([1] * (text_emb.ndim - 1))), text_emb, null)
-            keep = kept.to(torch.float32)
-        sigma = sample_sigma_hybrid(batch_size=latent_images.shape[0], sigma_max=cfg["sigma_max"], sigma_min=cfg["sigma_min"],
-                                    p_mean=mc["p_mean"], p_std=mc["p_std"], extreme_prob=0.5, device=dev)
-        images_noised = latent_images + torch.randn_like(latent_images) * sigma
-        out_model, loss = self._fwd_loss(images_noised, latent_images, sigma, text_emb, self.unet_mask_gen(sigma=sigma, step=step),
-                                         self.vit_mask_gen(sigma=sigma, step=step), self.zeta_sched.get_zeta(step=step))
-        self._log_forward(step, loss, out_model, sigma)
-        self.buckets.zero_grad()
-        loss["loss"].backward()
-        self.buckets.finish()
-        return self._update(step, loss, out_model, sigma, keep)
-
-    def _train_step_device(self, latent_images: Optional[torch.Tensor], text_emb: Optional[torch.Tensor]) -> dict:
         step = self.step_idx
-        keep = None
         if self.graphed:
-            out_model, loss, sigma, keep = self._graphed_fwd_bwd(latent_images, text_emb)
-            self._log_forward(step, loss, out_model, sigma)
+            if self._staged is None:
+                self._build_staged(latent_images, text_emb)
+            elif self.dataset is None and (tuple(latent_images.shape), tuple(text_emb.shape)) != self._shapes:
+                raise ValueError(f"Trainer(graphed=True): batch shapes {tuple(latent_images.shape)}, {tuple(text_emb.shape)} differ from the "
+                                 f"captured step's {self._shapes[0]}, {self._shapes[1]}")
+        batch = self._batch(latent_images, text_emb, step, text_out=self._text)
+        if self.graphed:                                     # the replay reads the static buffers `batch` was written into
+            res = self._staged()
+            self.buckets.finish()
+            out_model, loss = res["out_model"], res["loss"]
+            self._log_forward(step, loss, out_model, batch.sigma)
         else:
-            if self.dataset is not None:
-                b, text_emb, keep = self._data()
-                latent_images = b["x0"]
-            else:
-                if latent_images.dtype != torch.float32 or not latent_images.is_contiguous():
-                    latent_images = latent_images.to(torch.float32).contiguous()
-                if self.cond_dropout > 0:
-                    text_emb, keep = self.inputs.drop_text(text_emb, step)
-                b = self.inputs.generate(latent_images, step)
-            sigma = b["sigma"]
-            out_model, loss = self._fwd_loss(b["x"], latent_images, sigma, text_emb, b["unet_mask"], b["vit_mask"], b["zeta"])
-            self._log_forward(step, loss, out_model, sigma)
+            out_model, loss = self._fwd_loss(batch)
+            self._log_forward(step, loss, out_model, batch.sigma)
             self.buckets.zero_grad()
             loss["loss"].backward()
             self.buckets.finish()
-        return self._update(step, loss, out_model, sigma, keep)
+        return self._update(step, loss, out_model, batch.sigma, batch.keep)
 
     def _log_forward(self, step: int, loss: dict, out_model: dict, sigma: torch.Tensor) -> None:
         mc = self.mask_cfg
@@ -418,42 +402,38 @@ class Trainer:
     def _update(self, step: int, loss: dict, out_model: dict, sigma: torch.Tensor, keep: Optional[torch.Tensor] = None) -> dict:
         """Everything behind the backward, in the reference's order: gradient logs, clip + AdamW, EMA, scheduler."""
         lg = self.logger
-        health_due = self.health_every is not None and (step + 1) % self.health_every == 0
-        health = self._grad_health() if self.skip_nonfinite or health_due else None
-        if health is not None:                               # in place of the clip's norm pass when the update is guarded
-            health.measure(step, which="grad", verdict=self.skip_nonfinite)
+        health_due, eval_due = _due(self.health_every, step), _due(self.eval_every, step)
+        # guard: the statistics whose device verdict the update, the EMA and the bias move run behind; None: all three are the plain calls
+        guard = self._grad_health() if self.skip_nonfinite else None
+        ok = None if guard is None else guard.ok
+        if guard is not None or health_due:                  # in place of the clip's norm pass when the update is guarded
+            self._grad_health().measure(step, which="grad", verdict=guard is not None)
         if lg is not None:
             lg.log_gradients(step=step, model=self.model.net)
             lg.log_weight_statistics(step=step, model=self.model.net)
-        from hdmoe_hip.optim import clip_grad_norm_
-        if self.skip_nonfinite:
-            self.optimizer.step(clip=(self._clip_params, self.max_grad_norm), health=health)
-        elif self.fuse:
-            self.optimizer.step(clip=(self._clip_params, self.max_grad_norm))
+        if self.fuse:
+            self.optimizer.step(clip=(self._clip_params, self.max_grad_norm), health=guard)
         else:
+            from hdmoe_hip.optim import clip_grad_norm_
             clip_grad_norm_(self._clip_params, self.max_grad_norm)
             self.optimizer.step()
         if self.ema is not None:
-            if self.skip_nonfinite:
-                self.ema.update(ok=health.ok)
-            else:
-                self.ema.update()
-            if self.ema_snapshot_every is not None and (step + 1) % self.ema_snapshot_every == 0:
+            self.ema.update(ok=ok)
+            if _due(self.ema_snapshot_every, step):
                 self._save_ema_snapshot(step + 1)
         if self.balance is not None:                         # one launch per router; behind a bad verdict only the counts are cleared
-            self.balance.step(ok=health.ok if self.skip_nonfinite else None)
+            self.balance.step(ok=ok)
         self.scheduler.step()
         self.step_idx += 1
         if health_due:
             self._check_health(step, self._read_health())
-        eval_due = self.eval_every is not None and (step + 1) % self.eval_every == 0
         if eval_due:
             self._evaluate(step + 1)
         if self.balance is not None and (health_due or eval_due) and lg is not None and callable(getattr(lg, "log_balance", None)):
             lg.log_balance(step, self.balance.read())        # (these steps sync anyway)
         res = {"loss": loss, "out_model": out_model, "sigma": sigma}
-        if self.skip_nonfinite:                              # device values, read by nobody here: no sync
-            res["step_ok"], res["grad_norm"] = health.ok[0], torch.sqrt(health.total_sumsq)[0]
+        if guard is not None:                                # device values, read by nobody here: no sync
+            res["step_ok"], res["grad_norm"] = guard.ok[0], torch.sqrt(guard.total_sumsq)[0]
         if self.balance is not None:
             res["router_balance"] = self.balance.last()
         if keep is not None:
@@ -511,7 +491,7 @@ class Trainer:
 
     def _save_ema_snapshot(self, step: int) -> None:
         """A host copy of every average (it syncs).  The averages are bit-identical across data-parallel ranks: rank 0 writes."""
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_rank() != 0:
+        if self.rank != 0:
             return
         os.makedirs(self.ema_snapshot_dir, exist_ok=True)
         self.ema.save_snapshot(os.path.join(self.ema_snapshot_dir, f"ema_{step:08d}.pt"))

@@ -12,6 +12,7 @@ the data of a step in the same fused calls -- epoch order, VAE-posterior draw, h
 """
 from __future__ import annotations
 
+import inspect
 import math
 from typing import Optional
 
@@ -216,6 +217,30 @@ class DeviceInputs:
                     "vit_mask": torch.zeros(B, E, **f32), "zeta": torch.zeros(1, **f32), "src": torch.zeros(B, dtype=torch.int32, device=dev)}
         self.shape = tuple(shape)
 
+    def _schedule(self, step: int) -> dict:
+        """The keywords `ops.train_inputs` and `ops.dataset_inputs` share: the sigma distribution and step `step`'s host schedules."""
+        mc = self.mask_cfg
+        return dict(sigma_min=self.cfg["sigma_min"], sigma_max=self.cfg["sigma_max"], p_mean=mc["p_mean"], p_std=mc["p_std"],
+                    extreme_prob=self.extreme_prob, unet_bw=self.unet_mask_gen.bandwidth_scheduler(step),
+                    vit_bw=self.vit_mask_gen.bandwidth_scheduler(step), min_active=self.unet_mask_gen.min_active,
+                    zeta=self.zeta_sched.get_zeta(step=step))
+
+    def _text_out(self, like: torch.Tensor, shape, out: Optional[torch.Tensor]) -> torch.Tensor:
+        """Where `drop_text` / `text_from` write a step's text of `shape` (dtype and device of `like`): `out`, or the lazily made static
+        ``text``.  The first call fixes shape and dtype and makes ``keep`` and the null row as the kernel reads it."""
+        sig = (tuple(shape), like.dtype)
+        if self._text_like is None:
+            self._null = _null_row(self.null_text_emb, like)
+            self.keep = torch.zeros(shape[0], dtype=torch.float32, device=like.device)
+            self._text_like = sig
+        elif sig != self._text_like:
+            raise ValueError(f"DeviceInputs: text {sig} differs from the static buffers' {self._text_like}")
+        if out is not None:
+            return out
+        if self.text is None:
+            self.text = torch.empty(sig[0], dtype=sig[1], device=like.device)
+        return self.text
+
     def generate(self, latents: torch.Tensor, step: int) -> dict:
         """{"sigma", "x", "unet_mask", "vit_mask", "zeta", "src"}: the static buffers, holding step `step`'s inputs for `latents`
         (B,C,H,W) float32 contiguous, until the next call."""
@@ -227,12 +252,9 @@ class DeviceInputs:
             if not latents.is_cuda:
                 raise RuntimeError("hdmoe_hip: tensors must live on the GPU (no CPU fallback in the product path)")
             self._alloc(tuple(latents.shape), latents.device)
-        b, mc = self.buf, self.mask_cfg
+        b = self.buf
         ops.train_inputs(b["x"], b["sigma"], b["unet_mask"], b["vit_mask"], b["zeta"], b["src"], latents, self._ucen, self._vcen, self.seed,
-                         int(step), sigma_min=self.cfg["sigma_min"], sigma_max=self.cfg["sigma_max"], p_mean=mc["p_mean"], p_std=mc["p_std"],
-                         extreme_prob=self.extreme_prob, unet_bw=self.unet_mask_gen.bandwidth_scheduler(step),
-                         vit_bw=self.vit_mask_gen.bandwidth_scheduler(step), min_active=self.unet_mask_gen.min_active,
-                         zeta=self.zeta_sched.get_zeta(step=step))
+                         int(step), **self._schedule(step))
         return b
 
     def generate_from(self, dataset: "LatentDataset", step: int, batch_size: int, world: int = 1, rank: int = 0) -> dict:
@@ -255,13 +277,10 @@ class DeviceInputs:
             dev = dataset.device
             self.data_buf = dict(self.buf, x0=torch.zeros(shape, dtype=torch.float32, device=dev),
                                  item=torch.zeros(B, dtype=torch.int32, device=dev), flip=torch.zeros(B, dtype=torch.float32, device=dev))
-        b, mc = self.data_buf, self.mask_cfg
+        b = self.data_buf
         ops.dataset_inputs(b["x"], b["x0"], b["sigma"], b["unet_mask"], b["vit_mask"], b["zeta"], b["src"], b["item"], b["flip"], dataset.mean,
                            dataset.std, self._ucen, self._vcen, self.seed, self.data_seed, int(step), world=world, rank=rank, scale=dataset.scale,
-                           p_flip=dataset.flip, sigma_min=self.cfg["sigma_min"], sigma_max=self.cfg["sigma_max"], p_mean=mc["p_mean"],
-                           p_std=mc["p_std"], extreme_prob=self.extreme_prob, unet_bw=self.unet_mask_gen.bandwidth_scheduler(step),
-                           vit_bw=self.vit_mask_gen.bandwidth_scheduler(step), min_active=self.unet_mask_gen.min_active,
-                           zeta=self.zeta_sched.get_zeta(step=step))
+                           p_flip=dataset.flip, **self._schedule(step))
         return b
 
     def text_from(self, dataset: "LatentDataset", step: int, out: Optional[torch.Tensor] = None):
@@ -273,17 +292,7 @@ class DeviceInputs:
         if self.data_buf is None:
             raise ValueError("DeviceInputs: text_from reads the items of generate_from: call that first")
         item = self.data_buf["item"]
-        like = ((item.shape[0],) + tuple(dataset.text.shape[1:]), dataset.text.dtype)
-        if self._text_like is None:
-            self._null = _null_row(self.null_text_emb, dataset.text)
-            self.keep = torch.zeros(item.shape[0], dtype=torch.float32, device=item.device)
-            self._text_like = like
-        elif like != self._text_like:
-            raise ValueError(f"DeviceInputs: text {like} differs from the static buffers' {self._text_like}")
-        if out is None:
-            if self.text is None:
-                self.text = torch.empty(like[0], dtype=like[1], device=item.device)
-            out = self.text
+        out = self._text_out(dataset.text, (item.shape[0],) + tuple(dataset.text.shape[1:]), out)
         ops.text_gather_dropout(out, self.keep, dataset.text, dataset.text_index, item, self._null, self.seed, int(step), self.cond_dropout,
                                 dataset.N)
         return out, self.keep
@@ -297,19 +306,17 @@ class DeviceInputs:
         text = text.detach()
         if not text.is_contiguous():
             text = text.contiguous()
-        like = (tuple(text.shape), text.dtype)
-        if self._text_like is None:
-            self._null = _null_row(self.null_text_emb, text)
-            self.keep = torch.zeros(text.shape[0], dtype=torch.float32, device=text.device)
-            self._text_like = like
-        elif like != self._text_like:
-            raise ValueError(f"DeviceInputs: text {like} differs from the static buffers' {self._text_like}")
-        if out is None:
-            if self.text is None:
-                self.text = torch.empty_like(text)
-            out = self.text
+        out = self._text_out(text, text.shape, out)
         ops.text_dropout(out, self.keep, text, self._null, self.seed, int(step), self.cond_dropout)
         return out, self.keep
+
+
+def model_extras(model: nn.Module, mask_config: dict) -> dict:
+    """The forward keywords only some models take: model_config2 reads the soft-gate transition from the mask config, model_config1
+    learns its scaling and has no such arguments."""
+    if "transition_point" in inspect.signature(model.forward).parameters:
+        return {"transition_point": mask_config["p_mean"], "softness": mask_config["p_std"]}
+    return {}
 
 
 def _null_row(null: Optional[torch.Tensor], like: torch.Tensor) -> Optional[torch.Tensor]:

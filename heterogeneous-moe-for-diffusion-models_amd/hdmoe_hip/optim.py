@@ -343,7 +343,12 @@ class FusedAdamW(torch.optim.Optimizer):
             call("hdmoe_mt_adamw_ok", *args, health.ok)
         else:
             call("hdmoe_mt_adamw", *args)
-        # the routed-row counters of the tracked expert lists accumulate over the forwards of a step (models/_assembly.py): start the next one at zero
+        self.clear_usage()
+        return loss
+
+    def clear_usage(self) -> None:
+        """The routed-row counters of the tracked expert lists accumulate over the forwards of a step (models/_assembly.py): start the
+        next one at zero.  `step` ends with it; whoever runs forwards that belong to no step (a capture's warm-ups) calls it too."""
         seen = set()
         for lst, _ in self._usage.values():
             if id(lst) not in seen:
@@ -351,7 +356,6 @@ class FusedAdamW(torch.optim.Optimizer):
                 u = getattr(lst, "_hdmoe_usage", None)
                 if u is not None:
                     u.zero_()
-        return loss
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)

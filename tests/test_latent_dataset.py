@@ -550,13 +550,13 @@ def test_trainer_graphed_matches_eager_and_resumes(bf16):
     for _ in range(2):
         E.train_step()
     E.step_idx = 0
-    inner = G._build_staged_dataset
+    inner = G._build_staged
 
-    def build():                                              # the capture's warm-up runs renormalise G's weights: E copies them after it
-        inner()
+    def build(*a):                                            # the capture's warm-up runs renormalise G's weights: E copies them after it
+        inner(*a)
         _follow(E, G)
 
-    G._build_staged_dataset = build
+    G._build_staged = build
     steps = []
     for step in range(3):
         _follow(E, G)
