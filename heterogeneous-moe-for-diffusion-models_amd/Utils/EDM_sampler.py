@@ -27,6 +27,11 @@ its probability-flow path ``x0 + sigma * noise`` by the epilogue of the update k
 dispatch plans -- is computed once, both text variants go through the expert banks and the fusion tail as one 2B-row batch, and the guided
 D_x is formed by the egress kernel.  Every solver, ``use_graph`` and every ``sample()`` keyword work with it; ``uncond_text_emb=None``
 then returns the plain D_x exactly (the unconditional branch IS the conditional one).
+
+Guidance interval and per-sample scales (extensions, opt-in).  ``guidance_interval=(lo, hi)`` guides only the evaluations whose sigma lies in
+[lo, hi] (limited-interval guidance); the others are the single plain conditional call, at 1x the cost.  The solver decides per evaluation
+on the host (``guidance_plan``) and, with ``use_graph``, replays the stage variant captured for that decision.  ``sample(guidance=vector)`` /
+``denoise(guidance=vector)`` take one scale per sample from a device buffer instead of the float baked into the capture.
 """
 import math
 import numbers
@@ -45,7 +50,7 @@ class EDM_Sampler:
     def __init__(self, model: nn.Module, Guide_net: nn.Module, num_solve_steps: int = 32, sigma_min: float = 0.002,
                  sigma_max: float = 80, rho: int = 7, S_churn: float = 0.0, S_min: float = 0.0, S_max: float = float("inf"),
                  S_noise: float = 1.0, guidance: float = 1.0, dtype=torch.float32, use_graph: bool = False, solver: str = "heun",
-                 churn_on_device: bool = False, eta: float = 1.0, shared_guidance: bool = False):
+                 churn_on_device: bool = False, eta: float = 1.0, shared_guidance: bool = False, guidance_interval=None):
         if not isinstance(solver, str) or solver not in SOLVERS:
             raise ValueError(f"solver must be one of {', '.join(map(repr, SOLVERS))}, got {solver!r}")
         if solver != "heun" and S_churn > 0:
@@ -71,6 +76,8 @@ class EDM_Sampler:
         self.s_max = S_max
         self.s_noise = S_noise
         self.guide = guidance
+        self.guidance_interval = guidance_interval       # extension: None, or (lo, hi): guide only the evaluations with lo <= sigma <= hi
+        self.last_evaluations = None                     # {"guided": n, "plain": m} of the last sample() call
         self.dtype = dtype
         self.use_graph = use_graph          # extension over the reference: hipGraph replay of the denoiser evaluation
         self.solver = solver                # extension over the reference: "dpmpp_2m" = DPM-Solver++(2M), one evaluation per stage
@@ -89,32 +96,42 @@ class EDM_Sampler:
         self._stage = None
 
     # reference Utils/EDM_sampler.py:35-70
-    def denoise(self, x, sigma, text_emb, transition_mean, softness, uncond_text_emb=None, Unet_router_mask=None, Vit_router_mask=None):
+    def denoise(self, x, sigma, text_emb, transition_mean, softness, uncond_text_emb=None, Unet_router_mask=None, Vit_router_mask=None,
+                guidance=None, guided=True):
         """One (guided) denoiser evaluation.  Router masks: (B, E) or (E,) with {0, 1} entries, None = every expert allowed (the reference).
-        With shared_guidance a guided evaluation is one model.forward_guided pass (inference: call it under torch.no_grad())."""
+        With shared_guidance a guided evaluation is one model.forward_guided pass (inference: call it under torch.no_grad()).
+        guidance: None = the sampler's float scale, or a (B,) tensor of finite per-sample scales (any device).  guided=False: the single
+        plain conditional evaluation, whatever the scale.  denoise() never reads sigma: whether an evaluation lies in guidance_interval is
+        the solver's decision (sample()), handed down as `guided`."""
         um = self._router_mask(Unet_router_mask, "Unet_router_mask", x.shape[0])
         vm = self._router_mask(Vit_router_mask, "Vit_router_mask", x.shape[0])
-        return self._denoise(x, sigma, text_emb, transition_mean, softness, uncond_text_emb, self._dev_mask(um, x), self._dev_mask(vm, x))
+        g = self._check_guidance(guidance, x.shape[0])
+        return self._denoise(x, sigma, text_emb, transition_mean, softness, uncond_text_emb, self._dev_mask(um, x), self._dev_mask(vm, x),
+                             bool(guided), self._dev_mask(g, x))
 
-    def _denoise(self, x, sigma, text_emb, transition_mean, softness, uncond_text_emb, um=None, vm=None):
-        """denoise() on validated device masks (or None): no host read, so it can run under stream capture."""
+    def _denoise(self, x, sigma, text_emb, transition_mean, softness, uncond_text_emb, um=None, vm=None, guided=True, g=None):
+        """denoise() on validated device masks (or None) and a validated (B,) float32 device vector of scales g (or None: self.guide): no
+        host read, so it can run under stream capture.  guided False, or a float scale of 1: one plain conditional call."""
         bs = x.shape[0]
         num_experts = self.model.num_experts
         Unet_router_mask = torch.ones((bs, num_experts), device=x.device) if um is None else um
         vit_router_mask = torch.ones((bs, num_experts), device=x.device) if vm is None else vm
         kw = dict(x=x, sigma=sigma, Unet_router_mask=Unet_router_mask, Vit_router_mask=vit_router_mask, zeta=0,
                   transition_point=transition_mean, softness=softness)
-        if self.shared_guidance and self.guide != 1.0:
+        active = guided and (g is not None or self.guide != 1.0)
+        if self.shared_guidance and active:
             # one pass: routing (and so the router masks) once, both text variants through the banks and the tail, the lerp in the egress
             self._check_shared()
-            return self.model.forward_guided(text_emb=text_emb, uncond_text_emb=uncond_text_emb, guidance=self.guide,
+            return self.model.forward_guided(text_emb=text_emb, uncond_text_emb=uncond_text_emb, guidance=self.guide if g is None else g,
                                              **kw)["denoised"].to(self.dtype)
         D_x = self.model(text_emb=text_emb, **kw)["denoised"].to(self.dtype)
-        if self.guide == 1.0:
+        if not active:
             return D_x
         emb_for_guide = uncond_text_emb if uncond_text_emb is not None else text_emb
         ref_D_x = self.gnet(text_emb=emb_for_guide, **kw)["denoised"].to(self.dtype)
         # ref.lerp(D, g) = (1-g)*ref + g*D
+        if g is not None:
+            return ops.lerp_rows(ref_D_x, D_x, g)
         return ops.axpby(ref_D_x, D_x, 1.0 - self.guide, self.guide)
 
     # ---- argument checks of the extensions: ValueError naming the argument, before any device work ------------------------------------
@@ -127,6 +144,60 @@ class EDM_Sampler:
             raise ValueError("shared_guidance=True needs Guide_net to be the model itself (a different guide network takes two passes)")
         if not callable(getattr(self.model, "forward_guided", None)):
             raise ValueError(f"shared_guidance=True needs a model with forward_guided(); {type(self.model).__name__} has none")
+
+    @property
+    def guidance_interval(self):
+        """None (guide every evaluation) or (lo, hi), 0 <= lo < hi <= inf: an evaluation at sigma s is guided iff lo <= s <= hi."""
+        return self._interval
+
+    @guidance_interval.setter
+    def guidance_interval(self, value):
+        if value is not None:
+            bad = ValueError(f"guidance_interval must be None or a pair (lo, hi) of numbers with 0 <= lo < hi, got {value!r}")
+            if isinstance(value, (str, bytes)) or isinstance(value, torch.Tensor) and value.ndim != 1:
+                raise bad
+            try:
+                lo, hi = (float(v) for v in value)
+            except (TypeError, ValueError):
+                raise bad from None
+            if not (0.0 <= lo < hi):                          # NaN fails every comparison
+                raise bad
+            value = (lo, hi)
+        self._interval = value
+
+    @staticmethod
+    def _check_guidance(g, bs):
+        """sample() / denoise() keyword `guidance`: None, or the per-sample scales as a float32 (B,) CPU tensor."""
+        if g is None:
+            return None
+        if not isinstance(g, torch.Tensor) or g.is_complex() or g.dtype == torch.bool:
+            raise ValueError(f"guidance must be None or a real tensor of shape ({bs},), got {type(g).__name__}"
+                             f"{' ' + str(g.dtype) if isinstance(g, torch.Tensor) else ''}")
+        if tuple(g.shape) != (bs,):
+            raise ValueError(f"guidance must have shape ({bs},), one scale per sample, got {tuple(g.shape)}")
+        h = g.detach().to("cpu", torch.float32)
+        if not bool(torch.isfinite(h).all()):
+            raise ValueError("guidance entries must be finite")
+        return h
+
+    def guidance_plan(self, t_steps, i0=0):
+        """Which evaluations of sample() lie in guidance_interval: one tuple of bools per stage i = i0 ... N - 1, in the order the stage
+        makes its evaluations -- Heun (first, second), its last, Euler-only stage (first,), DPM-Solver++(2M) (its one,).  Pure host
+        arithmetic on the float64 schedule: the first evaluation of stage i is made at t[i], or with churn (on the device too: gamma is a
+        function of t[i]) at t_hat = t[i] (1 + gamma); Heun's second at t[i+1].  No interval: every flag is True."""
+        N = self.num_steps
+        iv = self.guidance_interval
+        inside = (lambda s: True) if iv is None else (lambda s: bool(iv[0] <= s <= iv[1]))
+        plan = []
+        for i in range(i0, N):
+            t_cur = float(t_steps[i])
+            gamma = min(self.s_churn / N, np.sqrt(2) - 1) if (self.s_churn > 0 and self.s_min <= t_cur <= self.s_max) else 0
+            first = inside(t_cur + gamma * t_cur)
+            if self.solver == "heun" and i < N - 1:
+                plan.append((first, inside(float(t_steps[i + 1]))))
+            else:
+                plan.append((first,))
+        return plan
 
     def _router_mask(self, m, name, bs):
         """Checked router mask as a float32 (B, E) tensor on m's device, or None.  A row without an allowed expert is refused: the gate
@@ -192,7 +263,7 @@ class EDM_Sampler:
         return strength
 
     # ---- static state and hipGraph capture: fused solver stages (reference :90-107 without churn), the captured evaluation ----------------
-    def _stage_state(self, kind, x, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm):
+    def _stage_state(self, kind, x, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, gvec=None):
         """Static buffers, stage functions and (use_graph) captured graphs of one kind:
           "eval": one guided evaluation of x at sig into out (the host loops' evaluation with use_graph);
           "heun": a full Heun stage and the last, Euler-only stage; "dpm": one DPM-Solver++(2M) stage (den_prev: the previous stage's
@@ -201,12 +272,18 @@ class EDM_Sampler:
         the order on the device, so any strength shares one capture.  The SAME stage function runs eagerly and under capture: the two
         trajectories are bit-identical.  The key holds everything a capture bakes in -- shapes, which optional operands exist, and what
         _denoise reads on the host (guide, the two modules), the churn / SDE launch scalars -- never buffer values: every input, the seed of
-        the stochastic stages included (device word "seed"), is refreshed before each run."""
+        the stochastic stages included (device word "seed") and the per-sample guidance scales ("g"), is refreshed before each run.
+
+        With a guidance interval (and guidance in effect) every stage function exists once per variant -- which of its evaluations are
+        guided -- and with use_graph each variant is one graph, all in one pool over the same buffers: "sel" maps a stage's tuple of
+        guidance_plan() to its index in "fns" / "g_<kind>", so the interval's bounds are a host selection and not in the key.  Without an
+        interval the lists are the all-guided ones alone: two for "heun" (full, last), one for "dpm" and "eval"."""
         shape = lambda a: None if a is None else tuple(a.shape)
+        variants = self.guidance_interval is not None and (gvec is not None or self.guide != 1.0)
         key = (kind, self.solver, shape(x), x.dtype, shape(text_emb), shape(uncond_text_emb), float(transition_mean), float(softness),
                self.num_steps, bool(self.use_graph), None if known is None else tuple(map(shape, known)), shape(um), shape(vm),
                float(self.guide), id(self.model), id(self.gnet), float(self.s_churn), float(self.s_min), float(self.s_max), float(self.s_noise),
-               float(self.eta), bool(self.churn_on_device), bool(self.shared_guidance))
+               float(self.eta), bool(self.churn_on_device), gvec is not None, variants, bool(self.shared_guidance))
         slot = "_graph" if kind == "eval" else "_stage"          # one cached state for the evaluation, one for the solver stage
         st = getattr(self, slot)
         if st is not None and st["key"] == key:
@@ -216,11 +293,11 @@ class EDM_Sampler:
         # mods: held so that their ids, in the key, cannot be reused by other modules while this capture lives
         st = dict(key=key, x=torch.empty_like(x), sig=torch.ones((), dtype=self.dtype, device=dev), text=torch.empty_like(text_emb),
                   unc=opt(uncond_text_emb), known=None if known is None else tuple(map(torch.empty_like, known)), um=opt(um), vm=opt(vm),
-                  mods=(self.model, self.gnet))
-        self._refresh(st, x, text_emb, uncond_text_emb, known, um, vm)
+                  g=opt(gvec), variants=variants, mods=(self.model, self.gnet))
+        self._refresh(st, x, text_emb, uncond_text_emb, known, um, vm, gvec=gvec)
 
-        def den(x_):
-            return self._denoise(x_, st["sig"], st["text"], transition_mean, softness, st["unc"], st["um"], st["vm"])
+        def den(x_, guided):
+            return self._denoise(x_, st["sig"], st["text"], transition_mean, softness, st["unc"], st["um"], st["vm"], guided, st["g"])
 
         def pick(j):                                          # sig = t[idx + j]
             ops.call("hdmoe_sched_pick", st["sig"], st["t"], st["idx"], j)
@@ -228,33 +305,33 @@ class EDM_Sampler:
         churn = self.s_churn > 0                              # a fused Heun stage with churn: churn_on_device (sample() decides)
         gamma_cap = float(min(self.s_churn / self.num_steps, np.sqrt(2) - 1))
 
-        def heun(last: bool):
+        def heun(last: bool, g1: bool = True, g2: bool = True):  # g1 / g2: is the first / second evaluation guided
             if churn:                                         # x <- x_hat in place, sig = t_hat; the updates then start from t_hat
                 ops.heun_churn(st["x"], st["x"], st["sig"], st["t_hat"], st["t"], st["idx"], st["seed"], gamma_cap, self.s_min, self.s_max,
                                self.s_noise)
             else:
                 pick(0)
             that = st["t_hat"] if churn else None
-            d = den(st["x"])
+            d = den(st["x"], g1)
             if last:
                 ops.heun_euler(st["x"], st["x"], d, st["t"], st["idx"], st["known"], that)
             else:
                 ops.heun_euler(st["xn"], st["x"], d, st["t"], st["idx"], st["known"], that)
                 pick(1)
-                ops.heun_correct(st["x"], st["x"], d, st["xn"], den(st["xn"]), st["t"], st["idx"], st["known"], that)
+                ops.heun_correct(st["x"], st["x"], d, st["xn"], den(st["xn"], g2), st["t"], st["idx"], st["known"], that)
             ops.call("hdmoe_idx_advance", st["idx"])
 
-        def dpm():
+        def dpm(g1: bool = True):
             pick(0)
             if self.solver == "dpmpp_2m_sde":
-                ops.dpm2m_sde_step(st["x"], st["x"], den(st["x"]), st["den_prev"], st["t"], st["idx"], st["i0"], self.eta, self.s_noise,
+                ops.dpm2m_sde_step(st["x"], st["x"], den(st["x"], g1), st["den_prev"], st["t"], st["idx"], st["i0"], self.eta, self.s_noise,
                                    st["seed"], st["known"])
             else:
-                ops.dpm2m_step(st["x"], st["x"], den(st["x"]), st["den_prev"], st["t"], st["idx"], st["i0"], st["known"])
+                ops.dpm2m_step(st["x"], st["x"], den(st["x"], g1), st["den_prev"], st["t"], st["idx"], st["i0"], st["known"])
             ops.call("hdmoe_idx_advance", st["idx"])
 
-        def evaluate():
-            st["out"] = den(st["x"])
+        def evaluate(g1: bool = True):                        # each variant keeps its own output alive in the shared pool
+            st["out" if g1 else "out_plain"] = den(st["x"], g1)
 
         if kind != "eval":
             st.update(t=torch.ones(self.num_steps + 1, dtype=torch.float64, device=dev), idx=torch.zeros(1, dtype=torch.int32, device=dev),
@@ -264,15 +341,24 @@ class EDM_Sampler:
             st["t_hat"] = torch.ones(1, dtype=torch.float64, device=dev)       # the churned sigma of the current stage
         if kind == "dpm":
             st.update(den_prev=torch.zeros_like(x), i0=torch.zeros(1, dtype=torch.int32, device=dev))
-        st["fns"] = {"eval": [evaluate], "heun": [lambda: heun(False), lambda: heun(True)], "dpm": [dpm]}[kind]
-        st["g_" + kind] = self._capture(st, warmup=3 if kind == "eval" else 2) if self.use_graph else []
+        if not variants:
+            st["fns"] = {"eval": [evaluate], "heun": [lambda: heun(False), lambda: heun(True)], "dpm": [dpm]}[kind]
+            st["sel"] = {"heun": {(True, True): 0, (True,): 1}}.get(kind, {(True,): 0})
+        else:                                                 # the all-guided variant first: the warm-up runs size the pool with it
+            one = {"eval": evaluate, "heun": lambda a: heun(True, a), "dpm": dpm}[kind]
+            keys = [(a, b) for a in (True, False) for b in (True, False)] if kind == "heun" else []
+            keys += [(True,), (False,)]
+            st["fns"] = [(lambda k=k: heun(False, *k)) if len(k) == 2 else (lambda k=k: one(*k)) for k in keys]
+            st["sel"] = {k: n for n, k in enumerate(keys)}
+        st["g_" + kind] = self._capture(st, warmup=3 if kind == "eval" else 2, warm_all=variants) if self.use_graph else []
         setattr(self, slot, st)
         return st
 
     @staticmethod
-    def _capture(st, warmup):
+    def _capture(st, warmup, warm_all=False):
         """One graph per stage function of st, all in one memory pool, after `warmup` runs of the first on a side stream (they register the
-        weight bank and size the allocator pool).  The device stage indices restart at 0 before every run."""
+        weight bank and size the allocator pool) and, with warm_all (the guidance-interval variants), one run of each of the others: a
+        variant may be the first to make the plain model call.  The device stage indices restart at 0 before every run."""
         def restart():
             for k in ("idx", "i0"):
                 if k in st:
@@ -281,9 +367,9 @@ class EDM_Sampler:
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            for _ in range(warmup):
+            for fn in [st["fns"][0]] * warmup + (st["fns"][1:] if warm_all else []):
                 restart()
-                st["fns"][0]()
+                fn()
         torch.cuda.current_stream().wait_stream(side)
         restart()
         graphs = []
@@ -295,14 +381,14 @@ class EDM_Sampler:
         return graphs
 
     @staticmethod
-    def _refresh(st, x, text_emb, uncond_text_emb, known, um, vm, seed=None):
+    def _refresh(st, x, text_emb, uncond_text_emb, known, um, vm, seed=None, gvec=None):
         """Every input into the static buffers: a later sample() with another prompt of the same shape must not see the captured one.
         seed: the 64-bit seed of this call's stochastic stages (a buffer value like the others, never part of the capture key)."""
         if seed is not None:
             st["seed"].fill_(seed - (1 << 64) if seed >= 1 << 63 else seed)
         st["x"].copy_(x)
         st["text"].copy_(text_emb)
-        for name, src in (("unc", uncond_text_emb), ("um", um), ("vm", vm)):
+        for name, src in (("unc", uncond_text_emb), ("um", um), ("vm", vm), ("g", gvec)):
             if st[name] is not None:
                 st[name].copy_(src)
         for buf, src in zip(st["known"] or (), known or ()):
@@ -314,7 +400,8 @@ class EDM_Sampler:
         eps = ops.randn_like(x, 1.0) if seed is None else ops.randn_keyed(x, seed, stage)
         return eps.to(x.dtype)
 
-    def _dpm_host_loop(self, x, t_steps, i0, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, seed=None):
+    def _dpm_host_loop(self, x, t_steps, i0, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, seed=None, plan=None,
+                       gvec=None):
         """solver="dpmpp_2m" / "dpmpp_2m_sde" for latents the fused stage does not take (non-fp32 dtype): the rule of sample() with host
         coefficients."""
         N = self.num_steps
@@ -322,7 +409,8 @@ class EDM_Sampler:
         den_prev = None
         for i in range(i0, N):
             t_cur, t_next = float(t_steps[i]), float(t_steps[i + 1])
-            den = self._eval(x, t_cur, text_emb, transition_mean, softness, uncond_text_emb, um, vm)
+            den = self._eval(x, t_cur, text_emb, transition_mean, softness, uncond_text_emb, um, vm,
+                             True if plan is None else plan[i - i0][0], gvec)
             e = math.exp(-self.eta * math.log(t_cur / t_next)) if sde and t_next > 0 else 1.0
             a = t_next / t_cur * e
             if t_next == 0:
@@ -339,15 +427,17 @@ class EDM_Sampler:
             den_prev = den
         return x
 
-    def _eval(self, x, t, text_emb, transition_mean, softness, uncond_text_emb, um=None, vm=None):
+    def _eval(self, x, t, text_emb, transition_mean, softness, uncond_text_emb, um=None, vm=None, guided=True, gvec=None):
+        """One evaluation at sigma t of the host loops; guided: the solver's guidance-interval decision for it."""
         if not self.use_graph:
             sig = torch.tensor(t, dtype=self.dtype, device=x.device)
-            return self._denoise(x, sig, text_emb, transition_mean, softness, uncond_text_emb, um, vm)
-        st = self._stage_state("eval", x, text_emb, transition_mean, softness, uncond_text_emb, None, um, vm)
-        self._refresh(st, x, text_emb, uncond_text_emb, None, um, vm)
+            return self._denoise(x, sig, text_emb, transition_mean, softness, uncond_text_emb, um, vm, guided, gvec)
+        st = self._stage_state("eval", x, text_emb, transition_mean, softness, uncond_text_emb, None, um, vm, gvec)
+        self._refresh(st, x, text_emb, uncond_text_emb, None, um, vm, gvec=gvec)
         st["sig"].fill_(float(t))
-        st["g_eval"][0].replay()
-        return st["out"].clone()
+        guided = bool(guided) or not st["variants"]
+        st["g_eval"][st["sel"][(guided,)]].replay()
+        return st["out" if guided else "out_plain"].clone()
 
     def t_schedule(self, device):
         """Karras rho schedule with the appended 0 (reference :80-87), computed on the host in float64."""
@@ -360,7 +450,7 @@ class EDM_Sampler:
     def sample(self, noise: torch.Tensor, text_emb: torch.Tensor, transition_mean: float, softness: float,
                uncond_text_emb: torch.Tensor = None, *, init_latents: torch.Tensor = None, strength: float = 1.0,
                inpaint_mask: torch.Tensor = None, Unet_router_mask: torch.Tensor = None, Vit_router_mask: torch.Tensor = None,
-               seed: int = None) -> torch.Tensor:
+               seed: int = None, guidance: torch.Tensor = None) -> torch.Tensor:
         """Solve of the probability-flow ODE over t = t_schedule() (N = num_solve_steps, t[N] = 0): Heun (solver="heun", the reference),
         or DPM-Solver++(2M) (solver="dpmpp_2m", one evaluation per stage).
 
@@ -396,10 +486,22 @@ class EDM_Sampler:
                           None.  A configuration that draws nothing ignores it.
           Unet_router_mask / Vit_router_mask:  (B, E) or (E,) with {0, 1} entries, passed to the model and the guide network; None = all
                           experts.  A row with no allowed expert is refused.
+          guidance:       None = the sampler's float scale (baked into a capture, as before), or a (B,) tensor of finite per-sample
+                          scales on any device.  It is copied into a static device buffer like every other input and read there by the
+                          blend (ops.lerp_rows, two-pass) or the egress (shared_guidance): one batch can carry a sweep of scales, and
+                          another vector of the same shape replays the same capture.
+
+        guidance_interval = (lo, hi) (constructor argument / attribute; None = guide everywhere): an evaluation made at sigma s is guided iff
+        lo <= s <= hi, otherwise it is the ONE plain conditional call that guidance == 1 makes.  s is t[i] for a stage's first evaluation
+        (t_hat with churn), t[i+1] for Heun's second; guidance_plan() lists the decisions and last_evaluations counts them after each call.
+        With DPM-Solver++(2M) the history term D_{i-1} is whatever stage i - 1 evaluated: across an interval boundary the extrapolation
+        mixes a guided and a plain output -- that is the formula applied to the gated denoiser, not an error.  With use_graph every stage
+        variant is captured once; calls that differ in the bounds replay the same graphs.
         Argument errors raise ValueError (naming the argument) before any device work."""
         strength = self._check_conditioning(noise, init_latents, strength, inpaint_mask)
         seed = self._check_seed(seed)
         bs = noise.shape[0]
+        gvec = self._check_guidance(guidance, bs)
         um = self._router_mask(Unet_router_mask, "Unet_router_mask", bs)
         vm = self._router_mask(Vit_router_mask, "Vit_router_mask", bs)
         device = noise.device
@@ -413,7 +515,12 @@ class EDM_Sampler:
         N = self.num_steps
         i0 = N - math.ceil(strength * N)
         t_steps = self.t_schedule(device)
-        um, vm = self._dev_mask(um, noise), self._dev_mask(vm, noise)
+        um, vm, gvec = self._dev_mask(um, noise), self._dev_mask(vm, noise), self._dev_mask(gvec, noise)
+        # the guidance-interval decision of every evaluation, taken here, on the host, from the float64 sigmas: denoise() never reads sigma
+        plan = self.guidance_plan(t_steps, i0)
+        n_eval = sum(map(len, plan))
+        n_guided = sum(map(sum, plan)) if (gvec is not None or self.guide != 1.0) else 0
+        self.last_evaluations = {"guided": n_guided, "plain": n_eval - n_guided}
         known = None
         if init_latents is None:
             x_next = ops.axpby(noise.to(self.dtype), None, float(t_steps[i0]), 0.0)
@@ -432,18 +539,19 @@ class EDM_Sampler:
             kind = "heun" if self.fused_heun else "dpm"
             if seed is None and (self.s_churn > 0 or (self.solver == "dpmpp_2m_sde" and self.eta > 0)):
                 seed = ops.next_seed()                        # a stochastic stage: one value of the library's stream per call
-            st = self._stage_state(kind, x_next, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm)
-            self._refresh(st, x_next, text_emb, uncond_text_emb, known, um, vm, seed)
+            st = self._stage_state(kind, x_next, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, gvec)
+            self._refresh(st, x_next, text_emb, uncond_text_emb, known, um, vm, seed, gvec)
             st["t"].copy_(torch.from_numpy(t_steps))
             st["idx"].fill_(i0)
             if self.fused_dpm:
                 st["i0"].fill_(i0)
             runs = [g.replay for g in st["g_" + kind]] or st["fns"]
-            for i in range(i0, N):
-                runs[-1 if i == N - 1 else 0]()               # Heun: the Euler-only stage last; DPM: its one stage throughout
+            for flags in plan:                                # Heun: the Euler-only stage last; DPM: its one stage throughout
+                runs[st["sel"][flags if st["variants"] else (True,) * len(flags)]]()
             return st["x"].clone()
         if self.solver != "heun":
-            return self._dpm_host_loop(x_next, t_steps, i0, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, seed)
+            return self._dpm_host_loop(x_next, t_steps, i0, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, seed, plan,
+                                       gvec)
         for i in range(i0, N):
             t_cur, t_next = float(t_steps[i]), float(t_steps[i + 1])
             x_cur = x_next
@@ -452,14 +560,14 @@ class EDM_Sampler:
             x_hat = x_cur
             if gamma > 0:
                 x_hat = ops.axpby(x_cur, self._eps(x_cur, seed, i), 1.0, float(np.sqrt(t_hat ** 2 - t_cur ** 2) * self.s_noise))
-            denoised = self._eval(x_hat, t_hat, text_emb, transition_mean, softness, uncond_text_emb, um, vm)
+            denoised = self._eval(x_hat, t_hat, text_emb, transition_mean, softness, uncond_text_emb, um, vm, plan[i - i0][0], gvec)
             # d_cur = (x_hat - denoised)/t_hat ; x_next = x_hat + (t_next - t_hat) * d_cur
             h = (t_next - t_hat)
             x_next = ops.axpby(x_hat, denoised, 1.0 + h / t_hat, -h / t_hat)
             if known is not None:
                 ops.known_blend_(x_next, *known, t_next)
             if i < self.num_steps - 1:
-                den2 = self._eval(x_next, t_next, text_emb, transition_mean, softness, uncond_text_emb, um, vm)
+                den2 = self._eval(x_next, t_next, text_emb, transition_mean, softness, uncond_text_emb, um, vm, plan[i - i0][1], gvec)
                 # x_next = x_hat + h * (0.5*d_cur + 0.5*d_prime),  d_prime = (x_next - den2)/t_next
                 d_cur_term = ops.axpby(x_hat, denoised, 1.0 + 0.5 * h / t_hat, -0.5 * h / t_hat)     # x_hat + 0.5 h d_cur
                 d_pr = ops.axpby(x_next, den2, 0.5 * h / t_next, -0.5 * h / t_next)                  # 0.5 h d_prime

@@ -679,6 +679,66 @@ __global__ void nhwc_to_nchw_guided_kernel(float* out, const T* F, const float* 
     out[i] = v;
   }
 }
+// The guided egress with one scale per sample, g[n] read from device memory (a batch that carries a sweep of scales; a scale that changes
+// between replays of one captured graph).  The kernel above operation for operation with gu = 1 - g[b] taken per row: a constant vector
+// reproduces it bit for bit.
+template <typename T>
+__global__ void nhwc_to_nchw_guided_rows_kernel(float* out, const T* F, const float* sf, const float* x, const float* sx, const float* g, int C,
+                                                long HW, long n) {
+  GRID_STRIDE(i, n) {
+    long t = i; const long p = t % HW; t /= HW;
+    const int c = (int)(t % C); const long b = t / C;
+    const long f = (b * HW + p) * C + c;
+    const float gb = g[b], gu = 1.f - gb;
+    float v = gu * to_f(F[n + f]) + gb * to_f(F[f]);
+    if (sf) v *= sf[b];
+    if (x) v += (sx ? sx[b] : 1.f) * x[i];
+    out[i] = v;
+  }
+}
+// out[r][:] = (1 - g[r]) ref[r][:] + g[r] d[r][:]: the classifier-free-guidance blend of the two-pass path with one scale per sample.
+// A constant vector must give the bits of hdmoe_axpby(ref, d, 1 - g, g), the blend of a float scale.  a x + b y has two roundings or three
+// depending on which product the compiler folds into a multiply-add, and in the two axpby kernels it chose per kernel and per lane.  The
+// two helpers spell out what it chose there, with contraction off so that it cannot choose again here:
+//   axpby_kernel (v = a x; v += b y):   fma(b, y, round(a x))
+//   axpby_vec_kernel, W lanes:          fma(a, x, round(b y)) in lanes 0 .. W - 3, round(a x) + round(b y) in the last two
+// tests/test_sampler_guidance_interval.py compares the two entry points bit for bit on every path, so a compiler that contracts the axpby
+// kernels differently shows there.
+DEVI float axpby_as_scalar_kernel(float a, float x, float b, float y) {
+#pragma clang fp contract(off)
+  const float v = a * x;
+  return __builtin_fmaf(b, y, v);
+}
+template <int W>
+DEVI void axpby_as_vec_kernel(float* f, const float* h, float a, float b) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < W; ++j) {
+    const float p = b * h[j];
+    if (j < W - 2) f[j] = __builtin_fmaf(a, f[j], p);
+    else { const float q = a * f[j]; f[j] = q + p; }
+  }
+}
+template <typename T>
+__global__ void lerp_rows_kernel(T* out, const T* ref, const T* d, const float* g, long per, long n) {
+  GRID_STRIDE(i, n) {
+    const float b = g[i / per], a = 1.f - b;
+    out[i] = from_f<T>(axpby_as_scalar_kernel(a, to_f(ref[i]), b, to_f(d[i])));
+  }
+}
+// 16-byte path: perv = per / W vectors in a row (per % W == 0, so no vector holds elements of two rows), as axpby_vec_kernel
+template <typename T>
+__global__ void lerp_rows_vec_kernel(T* out, const T* ref, const T* d, const float* g, long perv, long nv) {
+  constexpr int W = VT<T>::W;
+  GRID_STRIDE(v, nv) {
+    const float b = g[v / perv], a = 1.f - b;
+    float f[W], h[W];
+    vload<T>(f, ref + v * W);
+    vload<T>(h, d + v * W);
+    axpby_as_vec_kernel<W>(f, h, a, b);
+    vstore<T>(out + v * W, f);
+  }
+}
 
 // ---------------------------------------------------------------- patch <-> image relayout (Vit_expert, model_components.py:698-704)
 // tok[b][(hp,wp)][f] <-> img[b][hp*p+i][wp*p+j][c];  order 0: f = (i*p+j)*C + c ;  order 1 (PixelShuffle): f = c*p*p + i*p + j
@@ -1573,6 +1633,19 @@ int hdmoe_nhwc_to_nchw_guided(float* out, const void* F, const float* sf, const 
   if (!out || !F || N < 1 || C < 1 || HW < 1 || !(g == g) || g - g != 0.f) return HDMOE_EINVAL;
   const long n = (long)N * C * HW;
   DT_SWITCH(dtype, L1D(nhwc_to_nchw_guided_kernel<T>, n, out, (const T*)F, sf, x, sx, g, C, HW, n))
+}
+int hdmoe_nhwc_to_nchw_guided_rows(float* out, const void* F, const float* sf, const float* x, const float* sx, const float* g, int N, int C,
+                                   long HW, int dtype, hipStream_t stream) {
+  if (!out || !F || !g || N < 1 || C < 1 || HW < 1) return HDMOE_EINVAL;
+  const long n = (long)N * C * HW;
+  DT_SWITCH(dtype, L1D(nhwc_to_nchw_guided_rows_kernel<T>, n, out, (const T*)F, sf, x, sx, g, C, HW, n))
+}
+int hdmoe_lerp_rows(void* out, const void* ref, const void* d, const float* g, long rows, long per, int dtype, hipStream_t stream) {
+  if (!out || !ref || !d || !g || rows < 1 || per < 1) return HDMOE_EINVAL;
+  const long n = rows * per;
+  DT_SWITCH(dtype, if (per % VT<T>::W == 0 && al16(out) && al16(ref) && al16(d))
+                     L1D(lerp_rows_vec_kernel<T>, n / VT<T>::W, (T*)out, (const T*)ref, (const T*)d, g, per / VT<T>::W, n / VT<T>::W);
+                   else L1D(lerp_rows_kernel<T>, n, (T*)out, (const T*)ref, (const T*)d, g, per, n))
 }
 static int relayout_entry(void* out, const void* in, const int* rows, int N, int H, int W, int C, int p, int hp, int wp, int order,
                           int to_img, int dtype, hipStream_t stream) {

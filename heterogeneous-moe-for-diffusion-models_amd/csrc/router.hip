@@ -424,6 +424,6 @@ int hdmoe_combine_rows_bwd(void* dys, float* dsparse, const void* dout, const vo
   else return HDMOE_EDTYPE;
   return hdmoe_launch_status();
 }
-int hdmoe_version(void) { return 301; }
+int hdmoe_version(void) { return 302; }
 
 }  // extern "C"

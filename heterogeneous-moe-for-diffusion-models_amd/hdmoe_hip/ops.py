@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes
 import functools
 import math
-from typing import Optional, Sequence, Tuple
+from typing import Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -2175,16 +2175,43 @@ def nhwc_to_nchw_f32(F: Tensor, sf: Optional[Tensor] = None, x: Optional[Tensor]
     return _FromNHWCFn.apply(F, sf, x, sx)
 
 
-def nhwc_to_nchw_guided(F: Tensor, sf: Tensor, x: Tensor, sx: Tensor, guidance: float) -> Tensor:
+def _row_scales(g: Tensor, rows: int, who: str) -> Tensor:
+    """A per-sample guidance vector as the kernels read it: (rows,) float32, contiguous, on the GPU.  Its values are the caller's to check."""
+    if g.dtype != torch.float32 or tuple(g.shape) != (rows,) or not g.is_cuda:
+        raise ValueError(f"{who}: a guidance tensor must be a ({rows},) float32 CUDA tensor, got {tuple(g.shape)} {g.dtype} on {g.device}")
+    return _c(g.detach())
+
+
+def nhwc_to_nchw_guided(F: Tensor, sf: Tensor, x: Tensor, sx: Tensor, guidance: Union[float, Tensor]) -> Tensor:
     """Guided EDM egress of the pair-stacked head output F (2N, H, W, C) = [conditional ; unconditional]:
-    out[n] = sx[n] x[n] + sf[n] ((1 - g) F[N + n] + g F[n]), float32 NCHW (N rows).  Inference only."""
+    out[n] = sx[n] x[n] + sf[n] ((1 - g) F[N + n] + g F[n]), float32 NCHW (N rows).  Inference only.
+    guidance: a float, or a (N,) float32 CUDA tensor of per-sample scales g[n] (read on the device: nothing of it is baked into a capture)."""
     F = _c(F.detach())
     N2, H, W, C = F.shape
     if N2 % 2 or x.shape != (N2 // 2, C, H, W):
         raise ValueError(f"nhwc_to_nchw_guided: F {tuple(F.shape)} is not a pair-stacked batch of x {tuple(x.shape)}")
     N = N2 // 2
+    g = _row_scales(guidance, N, "nhwc_to_nchw_guided") if isinstance(guidance, Tensor) else None
     out = torch.empty((N, C, H, W), dtype=torch.float32, device=F.device)
-    call("hdmoe_nhwc_to_nchw_guided", out, F, _f32(sf.detach()), _f32(x.detach()), _f32(sx.detach()), float(guidance), N, C, H * W, _dt(F))
+    if g is None:
+        call("hdmoe_nhwc_to_nchw_guided", out, F, _f32(sf.detach()), _f32(x.detach()), _f32(sx.detach()), float(guidance), N, C, H * W, _dt(F))
+    else:
+        call("hdmoe_nhwc_to_nchw_guided_rows", out, F, _f32(sf.detach()), _f32(x.detach()), _f32(sx.detach()), g, N, C, H * W, _dt(F))
+    return out
+
+
+def lerp_rows(ref: Tensor, d: Tensor, guidance: Union[float, Tensor]) -> Tensor:
+    """The classifier-free-guidance blend (1 - g) ref + g d of two same-shaped (B, ...) tensors.  guidance: a float -- then this is
+    axpby(ref, d, 1 - g, g) -- or a (B,) float32 CUDA tensor of per-sample scales, read on the device.  Inference only (no gradient)."""
+    if not isinstance(guidance, Tensor):
+        return axpby(ref, d, 1.0 - float(guidance), float(guidance))
+    if ref.shape != d.shape or ref.dtype != d.dtype or ref.ndim < 1:
+        raise ValueError(f"lerp_rows: ref {tuple(ref.shape)} {ref.dtype} and d {tuple(d.shape)} {d.dtype} differ")
+    g = _row_scales(guidance, ref.shape[0], "lerp_rows")
+    ref, d = _c(ref.detach()), _c(d.detach())
+    out = torch.empty_like(ref)
+    if ref.numel():
+        call("hdmoe_lerp_rows", out, ref, d, g, ref.shape[0], ref.numel() // ref.shape[0], _dt(ref))
     return out
 
 

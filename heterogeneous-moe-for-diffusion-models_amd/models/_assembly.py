@@ -8,7 +8,7 @@ the U-Net bank runs as grouped launches over those rows, and a weighted combine 
 from __future__ import annotations
 
 import math
-from typing import List, Optional, Tuple
+from typing import List, Optional, Tuple, Union
 
 import torch
 import torch.nn as nn
@@ -391,11 +391,15 @@ class _PrecondBase(nn.Module):
         finally:
             wbank.deactivate()
 
-    def _forward_guided(self, x: Tensor, sigma: Tensor, text_emb: Tensor, uncond_text_emb: Optional[Tensor], guidance: float,
+    def _forward_guided(self, x: Tensor, sigma: Tensor, text_emb: Tensor, uncond_text_emb: Optional[Tensor], guidance: Union[float, Tensor],
                         Unet_router_mask: Tensor, Vit_router_mask: Tensor, zeta, **kw):
         """The classifier-free-guidance evaluation (1 - g) D(x; uncond) + g D(x; text) as ONE pass with shared routing (inference only):
         net._fwd_guided on the pair-stacked batch, the guided D_x formed by the egress kernel.  uncond_text_emb None: the unconditional
-        branch is the conditional one (the reference's ref.lerp(D, g) with ref = D), i.e. the plain evaluation."""
+        branch is the conditional one (the reference's ref.lerp(D, g) with ref = D), i.e. the plain evaluation.
+        guidance: a float, or a (B,) tensor of per-sample scales; only the egress reads it, nothing else in the pass depends on it."""
+        if isinstance(guidance, Tensor) and (tuple(guidance.shape) != (x.shape[0],) or not guidance.is_floating_point()):
+            raise ValueError(f"guidance must be a float or a floating-point tensor of shape ({x.shape[0]},), got {tuple(guidance.shape)} "
+                             f"{guidance.dtype}")
         tensors = [t for t in (x, sigma, text_emb, uncond_text_emb) if isinstance(t, Tensor)]
         if torch.is_grad_enabled() and (any(t.requires_grad for t in tensors) or any(p.requires_grad for p in self.parameters())):
             raise RuntimeError("forward_guided is inference only: call it under torch.no_grad() (gradients take forward())")
@@ -415,6 +419,8 @@ class _PrecondBase(nn.Module):
             xs = ops.to_nhwc(x32, scale=c_in, dtype=torch.float32)
             out, p_u, raw_u, p_v, raw_v, scaling = self.net._fwd_guided(xs, c_noise, text_emb, uncond_text_emb.to(text_emb.dtype),
                                                                          Unet_router_mask, Vit_router_mask, zeta, **kw)
+            if isinstance(guidance, Tensor):
+                guidance = guidance.detach().to(device=x32.device, dtype=torch.float32)
             D_x = ops.nhwc_to_nchw_guided(out, c_out, x32, ops.mul(c_skip, c_in), guidance)
         finally:
             wbank.deactivate()

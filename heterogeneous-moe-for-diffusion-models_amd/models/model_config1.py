@@ -2,7 +2,7 @@
 ``models/model_config1.py``."""
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+from typing import List, Optional, Tuple, Union
 
 import torch
 
@@ -62,7 +62,8 @@ class preconditioned_HDMOEM(_PrecondBase):
                 return_log_var: bool = False):
         return self._forward(x, sigma, text_emb, Unet_router_mask, Vit_router_mask, zeta, return_log_var)
 
-    def forward_guided(self, x: Tensor, sigma: Tensor, text_emb: Tensor, uncond_text_emb: Optional[Tensor], guidance: float,
+    def forward_guided(self, x: Tensor, sigma: Tensor, text_emb: Tensor, uncond_text_emb: Optional[Tensor], guidance: Union[float, Tensor],
                        Unet_router_mask: Tensor, Vit_router_mask: Tensor, zeta: float):
-        """(1 - guidance) D(x; uncond_text_emb) + guidance D(x; text_emb) in one shared-routing pass (models/_assembly.py); inference only."""
+        """(1 - guidance) D(x; uncond_text_emb) + guidance D(x; text_emb) in one shared-routing pass (models/_assembly.py); inference only.
+        guidance: a float, or a (B,) tensor of per-sample scales (read on the device by the egress kernel)."""
         return self._forward_guided(x, sigma, text_emb, uncond_text_emb, guidance, Unet_router_mask, Vit_router_mask, zeta)

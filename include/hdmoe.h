@@ -315,6 +315,15 @@ int hdmoe_nhwc_to_nchw(float* out, const void* F, const float* sf, const float* 
  * out[n] = sx[n] x[n] + sf[n] ((1 - g) F[N + n] + g F[n]) -- the EDM egress and the classifier-free-guidance lerp in one pass */
 int hdmoe_nhwc_to_nchw_guided(float* out, const void* F, const float* sf, const float* x, const float* sx, float g, int N,
                               int C, long HW, int dtype, HS stream);
+/* the same with one scale per sample, g[0..N-1] in DEVICE memory: out[n] = sx[n] x[n] + sf[n] ((1 - g[n]) F[N + n] + g[n] F[n]).  A constant
+ * vector gives the bits of the scalar entry point; the values are not checked (the caller validates them on the host). */
+int hdmoe_nhwc_to_nchw_guided_rows(float* out, const void* F, const float* sf, const float* x, const float* sx, const float* g, int N,
+                                   int C, long HW, int dtype, HS stream);
+/* out[r][:] = (1 - g[r]) ref[r][:] + g[r] d[r][:], g[0..rows-1] in DEVICE memory, rows of `per` elements: the guidance blend of two
+ * denoiser outputs with one scale per sample.  16-byte accesses when per is a multiple of the vector width (8 bf16 / 4 fp32) and the
+ * pointers are aligned -- a vector never holds elements of two rows -- else element by element.  A constant vector gives the bits of
+ * hdmoe_axpby(out, ref, d, 1 - g, g) where both take the same path (always, when per is a multiple of the vector width). */
+int hdmoe_lerp_rows(void* out, const void* ref, const void* d, const float* g, long rows, long per, int dtype, HS stream);
 int hdmoe_patch_relayout(void* out, const void* in, int N, int H, int W, int C, int p, int hp, int wp, int order,
                          int to_img, int dtype, HS stream);                                                      /* PixelShuffle / patchify */
 /* The same bytes for order 1 (PixelShuffle) by a tiled transpose through LDS, 16-byte accesses on both sides (csrc/relayout.hip).

@@ -6,7 +6,11 @@ sampler (its own capture), timed runs interleaved.  Also counts, from the bindin
 evaluation goes through in both modes.  Prints one JSON line.
 --root DIR --no-shared times the floor and the two-pass mode of another checkout of the repository (one without the shared mode, built in
 place), for a same-box comparison in the manner of tools/ab_trees.sh.
-usage: sampler_guidance_bench.py [--batch 128] [--steps 40] [--reps 3] [--guidance 2.0] [--root DIR] [--no-shared] [--out FILE]"""
+--interval LO HI adds, per solver and guidance mode, a leg with guidance_interval=(LO, HI) (guided only where LO <= sigma <= HI, the plain
+evaluation elsewhere), its counts of guided and plain evaluations, and the prediction n_guided t_guided + n_plain t_floor from the same
+run's per-evaluation times of the always-guided and the floor leg.
+usage: sampler_guidance_bench.py [--batch 128] [--steps 40] [--reps 3] [--guidance 2.0] [--interval LO HI] [--root DIR] [--no-shared]
+       [--out FILE]"""
 import argparse
 import collections
 import json
@@ -31,6 +35,7 @@ ap.add_argument("--batch", type=int, default=128)
 ap.add_argument("--steps", type=int, default=40)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--guidance", type=float, default=2.0)
+ap.add_argument("--interval", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="add guidance-interval legs")
 ap.add_argument("--root", default=None, help="time the package of this checkout instead of the one the tool lives in")
 ap.add_argument("--no-shared", action="store_true", help="floor and two-pass only (a checkout without shared_guidance)")
 ap.add_argument("--out", default=None, help="also write the JSON line to this file")
@@ -54,6 +59,9 @@ solvers = {"heun": (dict(), 2 * N - 1, "fused_heun"), "dpmpp_2m": (dict(solver="
 guides = {"floor": dict(guidance=1.0), "two_pass": dict(guidance=G), "shared": dict(guidance=G, shared_guidance=True)}
 if args.no_shared:
     del guides["shared"]
+if args.interval is not None:                                       # an interval leg behind each always-guided one
+    guides.update({gm + "_interval": dict(gkw, guidance_interval=tuple(args.interval)) for gm, gkw in list(guides.items())
+                   if gm != "floor"})
 samplers = {(sv, gm): EDM_Sampler(model, Guide_net=model, num_solve_steps=N, use_graph=True, **skw, **gkw)
             for sv, (skw, _, _) in solvers.items() for gm, gkw in guides.items()}
 times = {k: [] for k in samplers}
@@ -91,6 +99,12 @@ for sv, (_, n_eval, _) in solvers.items():
         r[gm] = dict(s=round(dt, 4), imgs_per_s=round(B / dt, 1), ms_per_eval=round(1e3 * dt / n_eval, 3),
                      spread_ms_per_eval=round(1e3 * (max(ts) - min(ts)) / n_eval, 3), runs_s=[round(t, 4) for t in ts])
     r["evals"] = n_eval
+    for gm in [gm for gm in guides if gm.endswith("_interval")]:    # ms_per_eval of these legs is per evaluation of either kind
+        ev = samplers[(sv, gm)].last_evaluations
+        base = gm[:-len("_interval")]
+        pred = (ev["guided"] * r[base]["ms_per_eval"] + ev["plain"] * r["floor"]["ms_per_eval"]) / 1e3
+        r[gm].update(evaluations=ev, predicted_s=round(pred, 4), measured_vs_predicted=round(r[gm]["s"] / pred, 3),
+                     vs_always_guided_s=round(r[gm]["s"] / r[base]["s"], 3))
     r["two_pass_vs_floor_ms_per_eval"] = round(r["two_pass"]["ms_per_eval"] / r["floor"]["ms_per_eval"], 3)
     if "shared" in guides:
         r["shared_vs_two_pass_imgs_per_s"] = round(r["shared"]["imgs_per_s"] / r["two_pass"]["imgs_per_s"], 3)
@@ -98,7 +112,7 @@ for sv, (_, n_eval, _) in solvers.items():
         d = (outs[(sv, "shared")] - outs[(sv, "two_pass")]).abs().max() / outs[(sv, "two_pass")].abs().max()
         r["shared_vs_two_pass_max_rel_diff"] = float(f"{float(d):.3e}")
     res[sv] = r
-line = json.dumps(dict(metric="sampler_guidance", root=os.path.relpath(ROOT, os.getcwd()), B=B, N=N, guidance=G, reps=args.reps, launches_per_guided_eval=launches, **res))
+line = json.dumps(dict(metric="sampler_guidance", root=os.path.relpath(ROOT, os.getcwd()), B=B, N=N, guidance=G, interval=args.interval, reps=args.reps, launches_per_guided_eval=launches, **res))
 print(line)
 if args.out:
     with open(args.out, "w") as f:
