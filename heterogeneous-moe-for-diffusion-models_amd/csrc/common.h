@@ -199,12 +199,15 @@ DEVI void randn4(long q, uint32_t seed_lo, uint32_t seed_hi, float* v) {
   const float t0 = 6.28318530717958648f * u01(r[1]), t1 = 6.28318530717958648f * u01(r[3]);
   v[0] = a0 * cosf(t0); v[1] = a0 * sinf(t0); v[2] = a1 * cosf(t1); v[3] = a1 * sinf(t1);
 }
-// W fp32 elements per thread: 16-byte loads / stores when W == 4 (the launcher checks n % 4 and the alignment), scalar otherwise
-template <int W> DEVI void ldw(float* f, const float* p) {
-  if constexpr (W == 4) vload<float>(f, p); else f[0] = *p;
+// W elements of T per thread, as floats: one 16-byte load / store when W == VT<T>::W (the launcher checks the count and the alignment), one
+// element when W == 1.  A kernel body written over W lanes serves both arms of its entry point.
+template <typename T, int W> DEVI void ldw(float* f, const T* p) {
+  static_assert(W == 1 || W == VT<T>::W, "one element or one 16-byte vector");
+  if constexpr (W == 1) f[0] = to_f(*p); else vload<T>(f, p);
 }
-template <int W> DEVI void stw(float* p, const float* f) {
-  if constexpr (W == 4) vstore<float>(p, f); else *p = f[0];
+template <typename T, int W> DEVI void stw(T* p, const float* f) {
+  static_assert(W == 1 || W == VT<T>::W, "one element or one 16-byte vector");
+  if constexpr (W == 1) *p = from_f<T>(f[0]); else vstore<T>(p, f);
 }
 // the draws of elements off ... off + W - 1 (off % W == 0): element j is lane j % 4 of block j / 4 whatever W is
 template <int W> DEVI void eps_w(float* e, long off, uint32_t lo, uint32_t hi) {

@@ -27,7 +27,7 @@ struct C6Args {
   int dbg;                            // always 0.  conv6s_body.h keeps its tests on it: without them the split kernel needs one VGPR more
   unsigned long long* stamps;         // development: s_memtime stamps of workgroup 0 ([wave][64] slots), or null
   // fused FiLM epilogue (Unet_block, reference model_components.py:242-246): besides y the kernel writes
-  // film_h = dropout_p(mp_silu(y * film_e[n][c])) -- the same arithmetic and the same Philox bits as film_silu_fwd_vec_kernel
+  // film_h = dropout_p(mp_silu(y * film_e[n][c])) -- the same arithmetic and the same Philox bits as film_silu_fwd_kernel<bf16, 8>
   // (elementwise.hip) on the bf16-rounded y, so the separate pass (and its launch on the U-Net branch's serial chain) disappears.
   const float* film_e; void* film_h; const unsigned long long* film_seed_dev; unsigned film_seed_lo, film_seed_hi; float film_p;
 };

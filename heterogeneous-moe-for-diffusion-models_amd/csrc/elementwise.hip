@@ -29,12 +29,40 @@ DEVI void row_window(const int* rows, long per, long& i0, long& n) {
 }
 
 // ---------------------------------------------------------------- generic pointwise
-template <typename T>
+// Kernels written once over W lanes (ldw / stw, common.h) are instantiated at W = VT<T>::W, one 16-byte vector per thread, and at W = 1;
+// they take their counts in elements and divide by W themselves, and L1D_W below picks the arm.
+//
+// f <- a f + b h, the rounding of hdmoe_axpby.  a x + b y has two roundings or three depending on which product is folded into a
+// multiply-add; the rule, spelled out with contraction off so that no compiler chooses it, is per arm and per lane:
+//   W == 1:  fma(b, y, round(a x))
+//   W > 1:   fma(a, x, round(b y)) in lanes 0 .. W - 3, round(a x) + round(b y) in the last two
+// (every mp_sum of the model goes through hdmoe_axpby: lanes that round alike would move the bits of all of them).  hdmoe_lerp_rows blends
+// through the same function, so the two entry points agree bit for bit by construction; tests/test_sampler_guidance_interval.py compares
+// them on every arm.
+template <int W>
+DEVI void axpby_lanes(float* f, const float* h, float a, float b) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < W; ++j) {
+    const float p = b * h[j], q = a * f[j];
+    if (W == 1) f[j] = __builtin_fmaf(b, h[j], q);
+    else if (j < W - 2) f[j] = __builtin_fmaf(a, f[j], p);
+    else f[j] = q + p;
+  }
+}
+template <typename T, int W>
 __global__ void axpby_kernel(T* out, const T* x, const T* y, float a, float b, long n) {
-  GRID_STRIDE(i, n) {
-    float v = a * to_f(x[i]);
-    if (y) v += b * to_f(y[i]);
-    out[i] = from_f<T>(v);
+  GRID_STRIDE(v, n / W) {
+    float f[W], g[W];
+    ldw<T, W>(f, x + v * W);
+    if (y) {
+      ldw<T, W>(g, y + v * W);
+      axpby_lanes<W>(f, g, a, b);
+    } else {
+#pragma unroll
+      for (int j = 0; j < W; ++j) f[j] = a * f[j];
+    }
+    stw<T, W>(out + v * W, f);
   }
 }
 template <typename T>
@@ -75,10 +103,10 @@ DEVI void stage_key(const unsigned long long* seed, int i, uint32_t& lo, uint32_
 }
 // Known region (inpainting) on its probability-flow path at sigma = s: x <- m (x0 + s noise) + (1 - m) x.  Evaluated in exactly this form
 // (not as a lerp) so that m = 1 at s = 0 gives x0 and m = 0 gives x bit-for-bit.  Epilogue of the stage kernels, and the host-loop form.
-template <int W> DEVI void known_blend_w(float* x, const float* x0, const float* nz, const float* m, float s, long off) {
+template <typename T, int W> DEVI void known_blend_w(float* x, const T* x0, const T* nz, const float* m, float s, long off) {
 #pragma clang fp contract(off)
   float a[W], z[W], k[W];
-  ldw<W>(a, x0 + off); ldw<W>(z, nz + off); ldw<W>(k, m + off);
+  ldw<T, W>(a, x0 + off); ldw<T, W>(z, nz + off); ldw<float, W>(k, m + off);
 #pragma unroll
   for (int j = 0; j < W; ++j) x[j] = k[j] * (a[j] + s * z[j]) + (1.f - k[j]) * x[j];
 }
@@ -95,11 +123,11 @@ __global__ void heun_euler_kernel(float* xn, const float* xh, const float* den, 
   const float a = (float)(1.0 + h / th), b = (float)(-h / th), s = (float)t[i + 1];
   GRID_STRIDE(v, nv) {
     float p[W], d[W];
-    ldw<W>(p, xh + v * W); ldw<W>(d, den + v * W);
+    ldw<float, W>(p, xh + v * W); ldw<float, W>(d, den + v * W);
 #pragma unroll
     for (int j = 0; j < W; ++j) p[j] = a * p[j] + b * d[j];
-    if (m) known_blend_w<W>(p, x0, nz, m, s, v * W);
-    stw<W>(xn + v * W, p);
+    if (m) known_blend_w<float, W>(p, x0, nz, m, s, v * W);
+    stw<float, W>(xn + v * W, p);
   }
 }
 // x_out = x_hat + h * (0.5 * (x_hat - denoised) / t_hat + 0.5 * (x_next - denoised') / t_next);  x0 / nz / m: as heun_euler_kernel
@@ -113,15 +141,15 @@ __global__ void heun_correct_kernel(float* out, const float* xh, const float* de
   const float s = (float)tn;
   GRID_STRIDE(v, nv) {
     float p[W], d[W], q[W], d2[W];
-    ldw<W>(p, xh + v * W); ldw<W>(d, den + v * W); ldw<W>(q, xn + v * W); ldw<W>(d2, den2 + v * W);
+    ldw<float, W>(p, xh + v * W); ldw<float, W>(d, den + v * W); ldw<float, W>(q, xn + v * W); ldw<float, W>(d2, den2 + v * W);
 #pragma unroll
     for (int j = 0; j < W; ++j) {
       const float u = __builtin_fmaf(a1, p[j], b1 * d[j]);
       const float w = a2 * q[j] + b2 * d2[j];
       p[j] = u + w;
     }
-    if (m) known_blend_w<W>(p, x0, nz, m, s, v * W);
-    stw<W>(out + v * W, p);
+    if (m) known_blend_w<float, W>(p, x0, nz, m, s, v * W);
+    stw<float, W>(out + v * W, p);
   }
 }
 // Churn of one Heun stage (reference Utils/EDM_sampler.py:90-97) on the device: i = *idx, tc = t[i], gamma = gcap inside [smin, smax] else 0,
@@ -144,14 +172,14 @@ __global__ void heun_churn_kernel(float* xh, const float* x, float* sigma, doubl
   if (noisy) stage_key(seed, i, lo, hi);
   GRID_STRIDE(v, nv) {
     float p[W];
-    ldw<W>(p, x + v * W);
+    ldw<float, W>(p, x + v * W);
     if (noisy) {
       float e[W];
       eps_w<W>(e, v * W, lo, hi);
 #pragma unroll
       for (int j = 0; j < W; ++j) p[j] = p[j] + c * e[j];
     }
-    stw<W>(xh + v * W, p);
+    stw<float, W>(xh + v * W, p);
   }
 }
 // One DPM-Solver++(2M) stage (multistep, data prediction) on the same device schedule, one evaluation per stage: i = *idx, a = t[i+1] / t[i];
@@ -181,17 +209,17 @@ __global__ void dpm2m_step_kernel(float* xo, const float* x, const float* den, f
   if (noisy) stage_key(seed, i, lo, hi);
   GRID_STRIDE(v, nv) {
     float p[W], d[W];
-    ldw<W>(d, den + v * W);
+    ldw<float, W>(d, den + v * W);
     if (order == 0) {
 #pragma unroll
       for (int j = 0; j < W; ++j) p[j] = d[j];
     } else if (order == 1) {
-      ldw<W>(p, x + v * W);
+      ldw<float, W>(p, x + v * W);
 #pragma unroll
       for (int j = 0; j < W; ++j) p[j] = a * p[j] + b * d[j];
     } else {
       float q[W];
-      ldw<W>(p, x + v * W); ldw<W>(q, dp + v * W);
+      ldw<float, W>(p, x + v * W); ldw<float, W>(q, dp + v * W);
 #pragma unroll
       for (int j = 0; j < W; ++j) {
         const float u = w1 * d[j] - w0 * q[j];
@@ -204,26 +232,20 @@ __global__ void dpm2m_step_kernel(float* xo, const float* x, const float* den, f
 #pragma unroll
       for (int j = 0; j < W; ++j) p[j] = p[j] + c * z[j];
     }
-    if (m) known_blend_w<W>(p, x0, nz, m, s, v * W);
-    stw<W>(dp + v * W, d);
-    stw<W>(xo + v * W, p);
+    if (m) known_blend_w<float, W>(p, x0, nz, m, s, v * W);
+    stw<float, W>(dp + v * W, d);
+    stw<float, W>(xo + v * W, p);
   }
 }
-// host-scalar form of the blend (host-driven sampler loop: churn or non-fp32 latents); x, x0, nz in T, m fp32
-template <typename T>
+// host-scalar form of the blend (host-driven sampler loop: churn or non-fp32 latents); x, x0, nz in T, m fp32.  The mask is fp32 whatever T
+// is, so only <float, 4> has a 16-byte arm; bf16 latents take W = 1.
+template <typename T, int W>
 __global__ void known_blend_kernel(T* x, const T* x0, const T* nz, const float* m, float s, long n) {
-#pragma clang fp contract(off)
-  GRID_STRIDE(e, n) {
-    const float k = m[e];
-    x[e] = from_f<T>(k * (to_f(x0[e]) + s * to_f(nz[e])) + (1.f - k) * to_f(x[e]));
-  }
-}
-__global__ void known_blend_f4_kernel(float* x, const float* x0, const float* nz, const float* m, float s, long nv) {
-  GRID_STRIDE(v, nv) {
-    float p[4];
-    ldw<4>(p, x + v * 4);
-    known_blend_w<4>(p, x0, nz, m, s, v * 4);
-    stw<4>(x + v * 4, p);
+  GRID_STRIDE(v, n / W) {
+    float p[W];
+    ldw<T, W>(p, x + v * W);
+    known_blend_w<T, W>(p, x0, nz, m, s, v * W);
+    stw<T, W>(x + v * W, p);
   }
 }
 struct FirTaps { float k[8]; };
@@ -269,13 +291,25 @@ __global__ void fir_up_kernel(T* y, const T* x, FirTaps f, int L, int pad, float
     y[e] = from_f<T>(scale * acc);
   }
 }
-template <typename T>
+template <typename T, int W>
 __global__ void mp_silu_fwd_kernel(T* out, const T* x, long n) {
-  GRID_STRIDE(i, n) out[i] = from_f<T>(mp_silu_f(to_f(x[i])));
+  GRID_STRIDE(v, n / W) {
+    float f[W];
+    ldw<T, W>(f, x + v * W);
+#pragma unroll
+    for (int j = 0; j < W; ++j) f[j] = mp_silu_f(f[j]);
+    stw<T, W>(out + v * W, f);
+  }
 }
-template <typename T>
+template <typename T, int W>
 __global__ void mp_silu_bwd_kernel(T* dx, const T* dy, const T* x, long n) {
-  GRID_STRIDE(i, n) dx[i] = from_f<T>(to_f(dy[i]) * mp_silu_grad_f(to_f(x[i])));
+  GRID_STRIDE(v, n / W) {
+    float f[W], g[W];
+    ldw<T, W>(f, x + v * W); ldw<T, W>(g, dy + v * W);
+#pragma unroll
+    for (int j = 0; j < W; ++j) f[j] = g[j] * mp_silu_grad_f(f[j]);
+    stw<T, W>(dx + v * W, f);
+  }
 }
 template <typename T>
 __global__ void sigmoid_fwd_kernel(T* out, const T* x, float a, long n) {   // sigmoid(a*x)
@@ -289,21 +323,43 @@ __global__ void sigmoid_bwd_kernel(T* dx, const T* dy, const T* y, float a, long
 // (the counter RNG -- philox / u01 / mix_seed -- lives in common.h: the conv epilogue with fused FiLM + dropout draws the same bits)
 __global__ void seed_advance_kernel(unsigned long long* seed_dev) { *seed_dev += 1ull; }
 
-// dropout keep-mask of element i (4 elements share one Philox call): the same (seed, index) gives the same bit in fwd and bwd
-DEVI bool keep_bit(long i, uint32_t seed_lo, uint32_t seed_hi, float p) {
-  uint32_t r[4];
-  const long q = i >> 2;
-  philox((uint32_t)q, (uint32_t)(q >> 32), seed_lo, seed_hi, r);
-  return u01(r[i & 3]) >= p;
-}
-
 // ---------------------------------------------------------------- FiLM + mp_silu   (Unet_block, model_components.py:242-243)
-template <typename T>
-__global__ void film_silu_fwd_kernel(T* out, const T* u, const float* e, long HW, int C, long n) {
-  GRID_STRIDE(i, n) {
-    const long row = i / C; const int c = (int)(i - row * C);
-    const long s = row / HW;
-    out[i] = from_f<T>(mp_silu_f(to_f(u[i]) * e[s * C + c]));
+// out = mp_silu(u * e[sample]), then F.dropout(p) fused (model_components.py:245-246).  A Philox block is four elements, so only the
+// 16-byte arm draws: the W = 1 arm is reached with p == 0 only.
+template <typename T, int W>
+__global__ void film_silu_fwd_kernel(T* out, const T* u, const float* e, long HW, int C, long n, uint32_t seed_lo, uint32_t seed_hi,
+                                     const unsigned long long* seed_dev, float p, unsigned char* mask = nullptr) {
+  const int cv = C / W;
+  const bool drop = W % 4 == 0 && p > 0.f;
+  if (drop) mix_seed(seed_lo, seed_hi, seed_dev);
+  const float inv = drop ? 1.f / (1.f - p) : 1.f;
+  GRID_STRIDE(v, n / W) {
+    const long row = v / cv; const int c0 = (int)(v - row * cv) * W;
+    const float* ep = e + (row / HW) * C + c0;
+    float f[W];
+    ldw<T, W>(f, u + v * W);
+    uint32_t r4[W];
+    if constexpr (W % 4 == 0) {
+      if (drop) {
+#pragma unroll
+        for (int q = 0; q < W / 4; ++q) { const long qi = (v * W) / 4 + q; philox((uint32_t)qi, (uint32_t)(qi >> 32), seed_lo, seed_hi, r4 + 4 * q); }
+        if constexpr (W == 8) {
+          if (mask) {                                        // the keep decisions for the backward: one byte per vector, bit j = element j kept
+            unsigned m = 0;
+#pragma unroll
+            for (int j = 0; j < W; ++j) m |= (u01(r4[j]) >= p ? 1u : 0u) << j;
+            mask[v] = (unsigned char)m;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      float a = mp_silu_f(f[j] * ep[j]);
+      if (drop) a = u01(r4[j]) >= p ? a * inv : 0.f;
+      f[j] = a;
+    }
+    stw<T, W>(out + v * W, f);
   }
 }
 // one block per (pixel chunk, sample): du = da*silu'(u*e)*e ; de[n,c] += sum_pix da*silu'(u*e)*u
@@ -328,50 +384,40 @@ __global__ void film_silu_bwd_kernel(T* du, float* de, const T* da, const T* u, 
 }
 
 // ---------------------------------------------------------------- per-sample scalar scale
-template <typename T>
+template <typename T, int W>
 __global__ void scale_rows_fwd_kernel(T* out, const T* x, const float* s, long L, long n) {
-  GRID_STRIDE(i, n) out[i] = from_f<T>(to_f(x[i]) * s[i / L]);
+  const long Lv = L / W;
+  GRID_STRIDE(v, n / W) {
+    const float sv = s[v / Lv];
+    float f[W];
+    ldw<T, W>(f, x + v * W);
+#pragma unroll
+    for (int j = 0; j < W; ++j) f[j] *= sv;
+    stw<T, W>(out + v * W, f);
+  }
 }
-template <typename T>
+// block = (chunk of `chunk` W-wide items, row); the chunks of a row meet in ds through atomicAdd
+template <typename T, int W>
 __global__ void scale_rows_bwd_kernel(T* dx, float* ds, const T* dy, const T* x, const float* s, long L, int chunk) {
   __shared__ float sm[16];
   const int r = blockIdx.y;
-  const long p0 = (long)blockIdx.x * chunk;
-  const long p1 = (p0 + chunk < L) ? p0 + chunk : L;
-  const float sv = s[r];
-  float acc = 0.f;
-  for (long i = p0 + threadIdx.x; i < p1; i += blockDim.x) {
-    const float g = to_f(dy[(long)r * L + i]);
-    if (dx) dx[(long)r * L + i] = from_f<T>(g * sv);
-    if (ds) acc += g * to_f(x[(long)r * L + i]);
-  }
-  if (ds) {
-    acc = block_sum(acc, sm);
-    if (threadIdx.x == 0) atomicAdd(&ds[r], acc);
-  }
-}
-
-template <typename T>
-__global__ void scale_rows_bwd_vec_kernel(T* dx, float* ds, const T* dy, const T* x, const float* s, long Lv, int chunk) {
-  constexpr int W = VT<T>::W;
-  __shared__ float sm[16];
-  const int r = blockIdx.y;
+  const long Lv = L / W;
   const long p0 = (long)blockIdx.x * chunk;
   const long p1 = (p0 + chunk < Lv) ? p0 + chunk : Lv;
   const float sv = s[r];
   float acc = 0.f;
   for (long i = p0 + threadIdx.x; i < p1; i += blockDim.x) {
     float g[W], xv[W];
-    vload<T>(g, dy + ((long)r * Lv + i) * W);
+    ldw<T, W>(g, dy + ((long)r * Lv + i) * W);
     if (ds) {
-      vload<T>(xv, x + ((long)r * Lv + i) * W);
+      ldw<T, W>(xv, x + ((long)r * Lv + i) * W);
 #pragma unroll
       for (int j = 0; j < W; ++j) acc += g[j] * xv[j];
     }
     if (dx) {
 #pragma unroll
       for (int j = 0; j < W; ++j) g[j] *= sv;
-      vstore<T>(dx + ((long)r * Lv + i) * W, g);
+      stw<T, W>(dx + ((long)r * Lv + i) * W, g);
     }
   }
   if (ds) {
@@ -381,94 +427,71 @@ __global__ void scale_rows_bwd_vec_kernel(T* dx, float* ds, const T* dy, const T
 }
 
 // ---------------------------------------------------------------- mp_cat  (model_internals.py:69-92)
-template <typename T>
+// a thread owns W channels of one row: cva = Ca / W items of a row come from a, the other cv - cva from b
+template <typename T, int W>
 __global__ void cat2_fwd_kernel(T* out, const T* a, const T* b, float wa, float wb, int Ca, int Cb, long rows) {
-  const int C = Ca + Cb;
-  GRID_STRIDE(i, rows * C) {
-    const long r = i / C; const int c = (int)(i - r * C);
-    out[i] = from_f<T>(c < Ca ? wa * to_f(a[r * Ca + c]) : wb * to_f(b[r * Cb + c - Ca]));
+  const int cva = Ca / W, cv = (Ca + Cb) / W;
+  GRID_STRIDE(v, rows * cv) {
+    const long r = v / cv; const int c = (int)(v - r * cv);
+    float f[W];
+    const bool first = c < cva;
+    ldw<T, W>(f, first ? a + (r * cva + c) * W : b + (r * (cv - cva) + c - cva) * W);
+    const float wgt = first ? wa : wb;
+#pragma unroll
+    for (int j = 0; j < W; ++j) f[j] *= wgt;
+    stw<T, W>(out + v * W, f);
   }
 }
-template <typename T>
+template <typename T, int W>
 __global__ void cat2_bwd_kernel(T* da, T* db, const T* dout, float wa, float wb, int Ca, int Cb, long rows) {
-  const int C = Ca + Cb;
-  GRID_STRIDE(i, rows * C) {
-    const long r = i / C; const int c = (int)(i - r * C);
-    const float g = to_f(dout[i]);
-    if (c < Ca) da[r * Ca + c] = from_f<T>(wa * g);
-    else db[r * Cb + c - Ca] = from_f<T>(wb * g);
+  const int cva = Ca / W, cv = (Ca + Cb) / W;
+  GRID_STRIDE(v, rows * cv) {
+    const long r = v / cv; const int c = (int)(v - r * cv);
+    float f[W];
+    ldw<T, W>(f, dout + v * W);
+    const bool first = c < cva;
+    const float wgt = first ? wa : wb;
+#pragma unroll
+    for (int j = 0; j < W; ++j) f[j] *= wgt;
+    stw<T, W>(first ? da + (r * cva + c) * W : db + (r * (cv - cva) + c - cva) * W, f);
   }
 }
 
 // ---------------------------------------------------------------- resample (model_internals.py:95-127)
-template <typename T>   // out[n][h][w][c] = scale * sum_{2x2} x[n][2h+i][2w+j][c]
+// one thread per W output channels (cv = C / W items a pixel), 32-bit index math per row
+template <typename T, int W>   // out[n][h][w][c] = scale * sum_{2x2} x[n][2h+i][2w+j][c]
 __global__ void pool2_kernel(T* out, const T* x, int Ho, int Wo, int C, float scale, long n) {
-  GRID_STRIDE(i, n) {
-    long t = i; const int c = (int)(t % C); t /= C;
-    const int w = (int)(t % Wo); t /= Wo;
-    const int h = (int)(t % Ho); const long s = t / Ho;
-    const T* p = x + (((s * 2 * Ho + 2 * h) * 2 * Wo) + 2 * w) * C + c;
-    const long rs = (long)2 * Wo * C;
-    out[i] = from_f<T>(scale * (to_f(p[0]) + to_f(p[C]) + to_f(p[rs]) + to_f(p[rs + C])));
-  }
-}
-template <typename T>   // out[n][h][w][c] = scale * x[n][h/2][w/2][c]
-__global__ void upsample2_kernel(T* out, const T* x, int Ho, int Wo, int C, float scale, long n) {
-  GRID_STRIDE(i, n) {
-    long t = i; const int c = (int)(t % C); t /= C;
-    const int w = (int)(t % Wo); t /= Wo;
-    const int h = (int)(t % Ho); const long s = t / Ho;
-    out[i] = from_f<T>(scale * to_f(x[((s * (Ho / 2) + h / 2) * (Wo / 2) + w / 2) * C + c]));
-  }
-}
-
-// 16-byte vector forms (C a multiple of the vector width): one thread per output vector, 32-bit index math per row
-template <typename T>
-__global__ void pool2_vec_kernel(T* out, const T* x, int Ho, int Wo, int cv, float scale, long nv) {
-  constexpr int W = VT<T>::W;
-  GRID_STRIDE(i, nv) {
+  const int cv = C / W;
+  GRID_STRIDE(i, n / W) {
     const long row = i / ((long)Wo * cv);                      // (sample, output row)
     const int rem = (int)(i - row * ((long)Wo * cv));
     const int w = rem / cv, c = rem - w * cv;
     const T* p = x + ((row * 2) * (2 * Wo) + 2 * w) * (long)cv * W + (long)c * W;
     const long rs = (long)2 * Wo * cv * W;
     float a[W], b[W], d[W], e[W];
-    vload<T>(a, p); vload<T>(b, p + (long)cv * W); vload<T>(d, p + rs); vload<T>(e, p + rs + (long)cv * W);
+    ldw<T, W>(a, p); ldw<T, W>(b, p + (long)cv * W); ldw<T, W>(d, p + rs); ldw<T, W>(e, p + rs + (long)cv * W);
 #pragma unroll
     for (int j = 0; j < W; ++j) a[j] = scale * (a[j] + b[j] + d[j] + e[j]);
-    vstore<T>(out + i * W, a);
+    stw<T, W>(out + i * W, a);
   }
 }
-template <typename T>
-__global__ void upsample2_vec_kernel(T* out, const T* x, int Ho, int Wo, int cv, float scale, long nv) {
-  constexpr int W = VT<T>::W;
-  GRID_STRIDE(i, nv) {
+template <typename T, int W>   // out[n][h][w][c] = scale * x[n][h/2][w/2][c]
+__global__ void upsample2_kernel(T* out, const T* x, int Ho, int Wo, int C, float scale, long n) {
+  const int cv = C / W;
+  GRID_STRIDE(i, n / W) {
     const long row = i / ((long)Wo * cv);                      // (sample, output row): sample = row / Ho, h = row % Ho
     const int rem = (int)(i - row * ((long)Wo * cv));
     const int w = rem / cv, c = rem - w * cv;
     const long s = row / Ho; const int h = (int)(row - s * Ho);
     float a[W];
-    vload<T>(a, x + (((s * (Ho / 2) + h / 2) * (Wo / 2) + w / 2) * (long)cv + c) * W);
+    ldw<T, W>(a, x + (((s * (Ho / 2) + h / 2) * (Wo / 2) + w / 2) * (long)cv + c) * W);
 #pragma unroll
     for (int j = 0; j < W; ++j) a[j] *= scale;
-    vstore<T>(out + i * W, a);
+    stw<T, W>(out + i * W, a);
   }
 }
 
 // ---------------------------------------------------------------- sequence reduce / broadcast  ([N][S][C] <-> fp32 [N][C])
-template <typename T>
-__global__ void seq_reduce_kernel(float* out, const T* x, long S, int C, float scale, int chunk) {
-  extern __shared__ float sm[];
-  const int s = blockIdx.y;
-  for (int c = threadIdx.x; c < C; c += blockDim.x) sm[c] = 0.f;
-  __syncthreads();
-  const long p0 = (long)blockIdx.x * chunk;
-  const long p1 = (p0 + chunk < S) ? p0 + chunk : S;
-  const long base = (long)s * S * C;
-  for (long i = p0 * C + threadIdx.x; i < p1 * C; i += blockDim.x) atomicAdd(&sm[i % C], to_f(x[base + i]));
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += blockDim.x) atomicAdd(&out[(long)s * C + c], scale * sm[c]);
-}
 template <typename T>   // out = (x ? x : 0) + scale * t[n][c]
 __global__ void seq_bcast_add_kernel(T* out, const T* x, const float* t, long S, int C, float scale, long n) {
   GRID_STRIDE(i, n) {
@@ -504,33 +527,17 @@ __global__ void lerp_param_fwd_kernel(T* out, const T* a, const T* b, const floa
   const float al = *alpha;
   GRID_STRIDE(i, n) { const float av = to_f(a[i]); out[i] = from_f<T>(av + al * (to_f(b[i]) - av)); }
 }
-template <typename T>
+template <typename T, int W>
 __global__ void lerp_param_bwd_kernel(T* da, T* db, float* dalpha, const T* g, const T* a, const T* b, const float* alpha, long n) {
   __shared__ float sm[16];
   const float al = *alpha;
   float acc = 0.f;
-  GRID_STRIDE(i, n) {
-    const float gv = to_f(g[i]);
-    da[i] = from_f<T>((1.f - al) * gv);
-    db[i] = from_f<T>(al * gv);
-    acc += gv * (to_f(b[i]) - to_f(a[i]));
-  }
-  acc = block_sum(acc, sm);
-  if (threadIdx.x == 0) atomicAdd(dalpha, acc);
-}
-
-template <typename T>
-__global__ void lerp_param_bwd_vec_kernel(T* da, T* db, float* dalpha, const T* g, const T* a, const T* b, const float* alpha, long nv) {
-  constexpr int W = VT<T>::W;
-  __shared__ float sm[16];
-  const float al = *alpha;
-  float acc = 0.f;
-  GRID_STRIDE(v, nv) {
+  GRID_STRIDE(v, n / W) {
     float gv[W], av[W], bv[W], o1[W], o2[W];
-    vload<T>(gv, g + v * W); vload<T>(av, a + v * W); vload<T>(bv, b + v * W);
+    ldw<T, W>(gv, g + v * W); ldw<T, W>(av, a + v * W); ldw<T, W>(bv, b + v * W);
 #pragma unroll
     for (int j = 0; j < W; ++j) { o1[j] = (1.f - al) * gv[j]; o2[j] = al * gv[j]; acc += gv[j] * (bv[j] - av[j]); }
-    vstore<T>(da + v * W, o1); vstore<T>(db + v * W, o2);
+    stw<T, W>(da + v * W, o1); stw<T, W>(db + v * W, o2);
   }
   acc = block_sum(acc, sm);
   if (threadIdx.x == 0) atomicAdd(dalpha, acc);
@@ -697,46 +704,18 @@ __global__ void nhwc_to_nchw_guided_rows_kernel(float* out, const T* F, const fl
   }
 }
 // out[r][:] = (1 - g[r]) ref[r][:] + g[r] d[r][:]: the classifier-free-guidance blend of the two-pass path with one scale per sample.
-// A constant vector must give the bits of hdmoe_axpby(ref, d, 1 - g, g), the blend of a float scale.  a x + b y has two roundings or three
-// depending on which product the compiler folds into a multiply-add, and in the two axpby kernels it chose per kernel and per lane.  The
-// two helpers spell out what it chose there, with contraction off so that it cannot choose again here:
-//   axpby_kernel (v = a x; v += b y):   fma(b, y, round(a x))
-//   axpby_vec_kernel, W lanes:          fma(a, x, round(b y)) in lanes 0 .. W - 3, round(a x) + round(b y) in the last two
-// tests/test_sampler_guidance_interval.py compares the two entry points bit for bit on every path, so a compiler that contracts the axpby
-// kernels differently shows there.
-DEVI float axpby_as_scalar_kernel(float a, float x, float b, float y) {
-#pragma clang fp contract(off)
-  const float v = a * x;
-  return __builtin_fmaf(b, y, v);
-}
-template <int W>
-DEVI void axpby_as_vec_kernel(float* f, const float* h, float a, float b) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int j = 0; j < W; ++j) {
-    const float p = b * h[j];
-    if (j < W - 2) f[j] = __builtin_fmaf(a, f[j], p);
-    else { const float q = a * f[j]; f[j] = q + p; }
-  }
-}
-template <typename T>
+// A constant vector gives the bits of hdmoe_axpby(ref, d, 1 - g, g), the blend of a float scale, on the same arm: both kernels round
+// through axpby_lanes.  perv = per / W items in a row (per % W == 0 on the 16-byte arm, so no vector holds elements of two rows).
+template <typename T, int W>
 __global__ void lerp_rows_kernel(T* out, const T* ref, const T* d, const float* g, long per, long n) {
-  GRID_STRIDE(i, n) {
-    const float b = g[i / per], a = 1.f - b;
-    out[i] = from_f<T>(axpby_as_scalar_kernel(a, to_f(ref[i]), b, to_f(d[i])));
-  }
-}
-// 16-byte path: perv = per / W vectors in a row (per % W == 0, so no vector holds elements of two rows), as axpby_vec_kernel
-template <typename T>
-__global__ void lerp_rows_vec_kernel(T* out, const T* ref, const T* d, const float* g, long perv, long nv) {
-  constexpr int W = VT<T>::W;
-  GRID_STRIDE(v, nv) {
+  const long perv = per / W;
+  GRID_STRIDE(v, n / W) {
     const float b = g[v / perv], a = 1.f - b;
     float f[W], h[W];
-    vload<T>(f, ref + v * W);
-    vload<T>(h, d + v * W);
-    axpby_as_vec_kernel<W>(f, h, a, b);
-    vstore<T>(out + v * W, f);
+    ldw<T, W>(f, ref + v * W);
+    ldw<T, W>(h, d + v * W);
+    axpby_lanes<W>(f, h, a, b);
+    stw<T, W>(out + v * W, f);
   }
 }
 
@@ -852,45 +831,7 @@ __global__ void sigmoid_scaling_kernel(float* sv, float* su, float* pair, const 
 
 
 
-// ---------------------------------------------------------------- 16-byte vectorised variants of the hot pointwise ops
-template <typename T>
-__global__ void axpby_vec_kernel(T* out, const T* x, const T* y, float a, float b, long nv) {
-  constexpr int W = VT<T>::W;
-  GRID_STRIDE(v, nv) {
-    float f[W], g[W];
-    vload<T>(f, x + v * W);
-    if (y) { vload<T>(g, y + v * W);
-#pragma unroll
-      for (int j = 0; j < W; ++j) f[j] = a * f[j] + b * g[j];
-    } else {
-#pragma unroll
-      for (int j = 0; j < W; ++j) f[j] = a * f[j];
-    }
-    vstore<T>(out + v * W, f);
-  }
-}
-template <typename T>
-__global__ void mp_silu_fwd_vec_kernel(T* out, const T* x, long nv) {
-  constexpr int W = VT<T>::W;
-  GRID_STRIDE(v, nv) {
-    float f[W];
-    vload<T>(f, x + v * W);
-#pragma unroll
-    for (int j = 0; j < W; ++j) f[j] = mp_silu_f(f[j]);
-    vstore<T>(out + v * W, f);
-  }
-}
-template <typename T>
-__global__ void mp_silu_bwd_vec_kernel(T* dx, const T* dy, const T* x, long nv) {
-  constexpr int W = VT<T>::W;
-  GRID_STRIDE(v, nv) {
-    float f[W], g[W];
-    vload<T>(f, x + v * W); vload<T>(g, dy + v * W);
-#pragma unroll
-    for (int j = 0; j < W; ++j) f[j] = g[j] * mp_silu_grad_f(f[j]);
-    vstore<T>(dx + v * W, f);
-  }
-}
+// ---------------------------------------------------------------- kernels with a 16-byte form only, or whose 16-byte form is another algorithm
 // dx = gx + dy * silu'(x): the gradient of a tensor that feeds mp_silu AND a second consumer (residual / skip), in one pass
 template <typename T>
 __global__ void mp_silu_bwd_add_vec_kernel(T* dx, const T* dy, const T* x, const T* gx, float sx, long nv) {
@@ -903,41 +844,7 @@ __global__ void mp_silu_bwd_add_vec_kernel(T* dx, const T* dy, const T* x, const
     vstore<T>(dx + v * W, f);
   }
 }
-template <typename T>
-__global__ void film_silu_fwd_vec_kernel(T* out, const T* u, const float* e, long HW, int C, long nv, uint32_t seed_lo, uint32_t seed_hi,
-                                         const unsigned long long* seed_dev, float p, unsigned char* mask = nullptr) {
-  constexpr int W = VT<T>::W;
-  const int cv = C / W;
-  if (p > 0.f) mix_seed(seed_lo, seed_hi, seed_dev);
-  const float inv = p > 0.f ? 1.f / (1.f - p) : 1.f;
-  GRID_STRIDE(v, nv) {
-    const long row = v / cv; const int c0 = (int)(v - row * cv) * W;
-    const float* ep = e + (row / HW) * C + c0;
-    float f[W];
-    vload<T>(f, u + v * W);
-    uint32_t r4[W];
-    if (p > 0.f) {                                           // F.dropout fused (model_components.py:245-246): W = 4 or 8 elements
-#pragma unroll
-      for (int q = 0; q < W / 4; ++q) { const long qi = (v * W) / 4 + q; philox((uint32_t)qi, (uint32_t)(qi >> 32), seed_lo, seed_hi, r4 + 4 * q); }
-      if constexpr (W == 8) {
-        if (mask) {                                          // the keep decisions for the backward: one byte per vector, bit j = element j kept
-          unsigned m = 0;
-#pragma unroll
-          for (int j = 0; j < W; ++j) m |= (u01(r4[j]) >= p ? 1u : 0u) << j;
-          mask[v] = (unsigned char)m;
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < W; ++j) {
-      float a = mp_silu_f(f[j] * ep[j]);
-      if (p > 0.f) a = u01(r4[j]) >= p ? a * inv : 0.f;
-      f[j] = a;
-    }
-    vstore<T>(out + v * W, f);
-  }
-}
-// block = (pixel chunk, sample); a thread's vectors all carry the same channel chunk (256 % (C/W) == 0): register partials
+// film_silu backward, 16-byte form: block = (pixel chunk, sample); a thread's vectors all carry the same channel chunk (256 % (C/W) == 0): register partials
 template <typename T>
 __global__ __launch_bounds__(256) void film_silu_bwd_vec_kernel(T* du, float* de, const T* da, const T* u, const float* e, long HW, int C, int chunk,
                                                                uint32_t seed_lo, uint32_t seed_hi, const unsigned long long* seed_dev, float p,
@@ -983,48 +890,6 @@ __global__ __launch_bounds__(256) void film_silu_bwd_vec_kernel(T* du, float* de
   __syncthreads();
   for (int c = threadIdx.x; c < C; c += blockDim.x) atomicAdd(&de[(long)s * C + c], sm[c]);
 }
-template <typename T>
-__global__ void scale_rows_fwd_vec_kernel(T* out, const T* x, const float* s, long Lv, long nv) {
-  constexpr int W = VT<T>::W;
-  GRID_STRIDE(v, nv) {
-    const float sv = s[v / Lv];
-    float f[W];
-    vload<T>(f, x + v * W);
-#pragma unroll
-    for (int j = 0; j < W; ++j) f[j] *= sv;
-    vstore<T>(out + v * W, f);
-  }
-}
-template <typename T>
-__global__ void cat2_fwd_vec_kernel(T* out, const T* a, const T* b, float wa, float wb, int Ca, int Cb, long rows) {
-  constexpr int W = VT<T>::W;
-  const int cva = Ca / W, cv = (Ca + Cb) / W;
-  GRID_STRIDE(v, rows * cv) {
-    const long r = v / cv; const int c = (int)(v - r * cv);
-    float f[W];
-    const bool first = c < cva;
-    vload<T>(f, first ? a + (r * cva + c) * W : b + (r * (cv - cva) + c - cva) * W);
-    const float wgt = first ? wa : wb;
-#pragma unroll
-    for (int j = 0; j < W; ++j) f[j] *= wgt;
-    vstore<T>(out + v * W, f);
-  }
-}
-template <typename T>
-__global__ void cat2_bwd_vec_kernel(T* da, T* db, const T* dout, float wa, float wb, int Ca, int Cb, long rows) {
-  constexpr int W = VT<T>::W;
-  const int cva = Ca / W, cv = (Ca + Cb) / W;
-  GRID_STRIDE(v, rows * cv) {
-    const long r = v / cv; const int c = (int)(v - r * cv);
-    float f[W];
-    vload<T>(f, dout + v * W);
-    const bool first = c < cva;
-    const float wgt = first ? wa : wb;
-#pragma unroll
-    for (int j = 0; j < W; ++j) f[j] *= wgt;
-    vstore<T>(first ? da + (r * cva + c) * W : db + (r * (cv - cva) + c - cva) * W, f);
-  }
-}
 // mp_cat + mp_silu of the result in one pass (decoder blocks: the concatenation feeds mp_silu and the skip / residual path), and the
 // matching backward: d(cat) = g_cat + g_h * silu'(cat), split and weighted
 template <typename T>
@@ -1068,33 +933,7 @@ __global__ void cat2_silu_bwd_vec_kernel(T* da, T* db, const T* gcat, const T* g
     vstore<T>(first ? da + (r * cva + c) * W : db + (r * (cv - cva) + c - cva) * W, f);
   }
 }
-// seq_reduce with a fixed channel chunk per thread (256 % (C/W) == 0)
-template <typename T>
-__global__ __launch_bounds__(256) void seq_reduce_vec_kernel(float* out, const T* x, long S, int C, float scale, int chunk) {
-  constexpr int W = VT<T>::W;
-  extern __shared__ float sm[];
-  const int s = blockIdx.y, cv = C / W;
-  for (int c = threadIdx.x; c < C; c += blockDim.x) sm[c] = 0.f;
-  __syncthreads();
-  const long p0 = (long)blockIdx.x * chunk;
-  const long p1 = (p0 + chunk < S) ? p0 + chunk : S;
-  const long base = (long)s * S * C;
-  const int c0 = (threadIdx.x % cv) * W;
-  float acc[W];
-#pragma unroll
-  for (int j = 0; j < W; ++j) acc[j] = 0.f;
-  for (long v = p0 * cv + threadIdx.x; v < p1 * cv; v += 256) {
-    float f[W];
-    vload<T>(f, x + base + v * W);
-#pragma unroll
-    for (int j = 0; j < W; ++j) acc[j] += f[j];
-  }
-#pragma unroll
-  for (int j = 0; j < W; ++j) atomicAdd(&sm[c0 + j], acc[j]);
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += blockDim.x) atomicAdd(&out[(long)s * C + c], scale * sm[c]);
-}
-// Deterministic forms (no atomics: the router's average pool feeds the top-k, and run-to-run float-add order would make the
+// seq_reduce is deterministic (no atomics: the router's average pool feeds the top-k, and run-to-run float-add order would make the
 // logits -- and through bf16 rounding every downstream tensor -- differ between identical calls).
 // (a) one block per sample; thread (r, c) = (tid / cv, tid % cv) walks rows r, r + R, ... of its 16-byte channel chunk, then a
 //     fixed-order tree over the R = 256 / cv row lanes.
@@ -1244,6 +1083,10 @@ __global__ void sum_n_kernel(T* out, SumSrcs s, int n, long nv, long nelem) {
   return hdmoe_launch_status();
 
 #define L1D(kernel, n, ...) hipLaunchKernelGGL(kernel, dim3(grid_for(n)), dim3(TPB), 0, stream, __VA_ARGS__)
+// the two arms of a kernel<T, W> over n elements: 16-byte vectors when `vec_ok` (the count divides by VT<T>::W, the pointers are aligned), else W = 1
+#define L1D_W(vec_ok, kernel, n, ...)                                   \
+  if (vec_ok) L1D((kernel<T, VT<T>::W>), (n) / VT<T>::W, __VA_ARGS__);  \
+  else L1D((kernel<T, 1>), n, __VA_ARGS__)
 
 // Measurement aid (bench.py "attention", tools/exp_rate.py): issue rate of v_exp_f32, the instruction that bounds the attention kernels.
 // Every thread runs 8 independent chains a = exp2(-a) (the negation is a source modifier: one v_exp_f32 per link), `iters` links each.
@@ -1264,8 +1107,7 @@ __global__ __launch_bounds__(256) void exp_rate_kernel(float* out, int iters) {
 extern "C" {
 
 int hdmoe_axpby(void* out, const void* x, const void* y, float a, float b, long n, int dtype, hipStream_t stream) {
-  DT_SWITCH(dtype, if (n % VT<T>::W == 0 && al16(out) && al16(x) && al16(y)) L1D(axpby_vec_kernel<T>, n / VT<T>::W, (T*)out, (const T*)x, (const T*)y, a, b, n / VT<T>::W);
-                   else L1D(axpby_kernel<T>, n, (T*)out, (const T*)x, (const T*)y, a, b, n))
+  DT_SWITCH(dtype, L1D_W(n % VT<T>::W == 0 && al16(out) && al16(x) && al16(y), axpby_kernel, n, (T*)out, (const T*)x, (const T*)y, a, b, n))
 }
 /* EDM sampler stage pieces (fp32 latents; t: device float64 schedule of N + 1 values, idx: device stage index) */
 int hdmoe_sched_pick(float* sigma, const double* t, const int* idx, int off, hipStream_t stream) {
@@ -1362,10 +1204,10 @@ int hdmoe_dpm2m_sde_step(float* x_out, const float* x, const float* den, float* 
 int hdmoe_known_blend(void* x, const void* x0, const void* noise, const float* mask, float s, long n, int dtype, hipStream_t stream) {
   if (!x || !x0 || !noise || !mask || n < 0) return HDMOE_EINVAL;
   if (dtype == HDMOE_F32 && n % 4 == 0 && al16(x) && al16(x0) && al16(noise) && al16(mask)) {
-    L1D(known_blend_f4_kernel, n / 4, (float*)x, (const float*)x0, (const float*)noise, mask, s, n / 4);
+    L1D((known_blend_kernel<float, 4>), n / 4, (float*)x, (const float*)x0, (const float*)noise, mask, s, n);
     return hdmoe_launch_status();
   }
-  DT_SWITCH(dtype, L1D(known_blend_kernel<T>, n, (T*)x, (const T*)x0, (const T*)noise, mask, s, n))
+  DT_SWITCH(dtype, L1D((known_blend_kernel<T, 1>), n, (T*)x, (const T*)x0, (const T*)noise, mask, s, n))
 }
 int hdmoe_exp_rate(float* out, int blocks, int iters, hipStream_t stream) {
   if (!out || blocks < 1 || iters < 1) return HDMOE_EINVAL;
@@ -1409,12 +1251,10 @@ int hdmoe_fir_resample(void* y, const void* x, const float* taps, int L, int pad
                    else L1D(fir_down_kernel<T>, total, (T*)y, (const T*)x, f, L, pad, scale, H, W, Ho, Wo, C, total))
 }
 int hdmoe_mp_silu_fwd(void* out, const void* x, long n, int dtype, hipStream_t stream) {
-  DT_SWITCH(dtype, if (n % VT<T>::W == 0 && al16(out) && al16(x)) L1D(mp_silu_fwd_vec_kernel<T>, n / VT<T>::W, (T*)out, (const T*)x, n / VT<T>::W);
-                   else L1D(mp_silu_fwd_kernel<T>, n, (T*)out, (const T*)x, n))
+  DT_SWITCH(dtype, L1D_W(n % VT<T>::W == 0 && al16(out) && al16(x), mp_silu_fwd_kernel, n, (T*)out, (const T*)x, n))
 }
 int hdmoe_mp_silu_bwd(void* dx, const void* dy, const void* x, long n, int dtype, hipStream_t stream) {
-  DT_SWITCH(dtype, if (n % VT<T>::W == 0 && al16(dx) && al16(dy) && al16(x)) L1D(mp_silu_bwd_vec_kernel<T>, n / VT<T>::W, (T*)dx, (const T*)dy, (const T*)x, n / VT<T>::W);
-                   else L1D(mp_silu_bwd_kernel<T>, n, (T*)dx, (const T*)dy, (const T*)x, n))
+  DT_SWITCH(dtype, L1D_W(n % VT<T>::W == 0 && al16(dx) && al16(dy) && al16(x), mp_silu_bwd_kernel, n, (T*)dx, (const T*)dy, (const T*)x, n))
 }
 /* dx = sx * gx + dy * mp_silu'(x); 16-byte aligned, n % (16 / esz) == 0 */
 int hdmoe_mp_silu_bwd_add(void* dx, const void* dy, const void* x, const void* gx, float sx, long n, int dtype, hipStream_t stream) {
@@ -1446,15 +1286,14 @@ int hdmoe_sigmoid_bwd(void* dx, const void* dy, const void* y, float a, long n, 
 }
 int hdmoe_film_silu_fwd(void* out, const void* u, const float* e, int N, long HW, int C, int dtype, hipStream_t stream) {
   const long n = (long)N * HW * C;
-  DT_SWITCH(dtype, if (C % VT<T>::W == 0 && al16(out) && al16(u)) L1D(film_silu_fwd_vec_kernel<T>, n / VT<T>::W, (T*)out, (const T*)u, e, HW, C, n / VT<T>::W, 0u, 0u, nullptr, 0.f);
-                   else L1D(film_silu_fwd_kernel<T>, n, (T*)out, (const T*)u, e, HW, C, n))
+  DT_SWITCH(dtype, L1D_W(C % VT<T>::W == 0 && al16(out) && al16(u), film_silu_fwd_kernel, n, (T*)out, (const T*)u, e, HW, C, n, 0u, 0u, nullptr, 0.f))
 }
 // FiLM + mp_silu + F.dropout in one pass (vectorised layouts only: C % (16/sizeof(T)) == 0)
 int hdmoe_film_silu_drop_fwd(void* out, const void* u, const float* e, int N, long HW, int C, unsigned long long seed,
                              const unsigned long long* seed_dev, float p, int dtype, hipStream_t stream) {
   const long n = (long)N * HW * C;
   if (p < 0.f || p >= 1.f) return HDMOE_EINVAL;
-  DT_SWITCH(dtype, if (C % VT<T>::W == 0 && al16(out) && al16(u)) L1D(film_silu_fwd_vec_kernel<T>, n / VT<T>::W, (T*)out, (const T*)u, e, HW, C, n / VT<T>::W,
+  DT_SWITCH(dtype, if (C % VT<T>::W == 0 && al16(out) && al16(u)) L1D((film_silu_fwd_kernel<T, VT<T>::W>), n / VT<T>::W, (T*)out, (const T*)u, e, HW, C, n,
                                                                      (uint32_t)seed, (uint32_t)(seed >> 32), seed_dev, p);
                    else return HDMOE_EINVAL)
 }
@@ -1474,7 +1313,7 @@ int hdmoe_film_silu_drop_fwd_mask(void* out, unsigned char* mask, const void* u,
                                   const unsigned long long* seed_dev, float p, int dtype, hipStream_t stream) {
   const long n = (long)N * HW * C;
   if (p <= 0.f || p >= 1.f || dtype != HDMOE_BF16 || !mask || C % 8 || !al16(out) || !al16(u)) return HDMOE_EINVAL;
-  L1D(film_silu_fwd_vec_kernel<bf16>, n / 8, (bf16*)out, (const bf16*)u, e, HW, C, n / 8, (uint32_t)seed, (uint32_t)(seed >> 32), seed_dev, p, mask);
+  L1D((film_silu_fwd_kernel<bf16, 8>), n / 8, (bf16*)out, (const bf16*)u, e, HW, C, n, (uint32_t)seed, (uint32_t)(seed >> 32), seed_dev, p, mask);
   return hdmoe_launch_status();
 }
 /* hdmoe_film_silu_drop_bwd from the saved mask instead of a second Philox draw (bf16 only; de accumulates).  du is bit-identical. */
@@ -1500,44 +1339,36 @@ int hdmoe_film_silu_bwd(void* du, float* de, const void* da, const void* u, cons
 }
 int hdmoe_scale_rows_fwd(void* out, const void* x, const float* s, long rows, long L, int dtype, hipStream_t stream) {
   const long n = rows * L;
-  DT_SWITCH(dtype, if (L % VT<T>::W == 0 && al16(out) && al16(x)) L1D(scale_rows_fwd_vec_kernel<T>, n / VT<T>::W, (T*)out, (const T*)x, s, L / VT<T>::W, n / VT<T>::W);
-                   else L1D(scale_rows_fwd_kernel<T>, n, (T*)out, (const T*)x, s, L, n))
+  DT_SWITCH(dtype, L1D_W(L % VT<T>::W == 0 && al16(out) && al16(x), scale_rows_fwd_kernel, n, (T*)out, (const T*)x, s, L, n))
 }
 int hdmoe_scale_rows_bwd(void* dx, float* ds, const void* dy, const void* x, const float* s, long rows, long L,
                          int dtype, hipStream_t stream) {
   if (rows > 65535) return HDMOE_EINVAL;
-  const int chunk = 8192;
-  dim3 grid(cdiv(L, chunk), (unsigned)rows);
-  DT_SWITCH(dtype, if (L % VT<T>::W == 0 && al16(dx) && al16(dy) && al16(x)) {
-                     const long Lv = L / VT<T>::W;
-                     const int vchunk = 2048;                    // 16-byte vectors per workgroup: 8 per thread
-                     hipLaunchKernelGGL(scale_rows_bwd_vec_kernel<T>, dim3(cdiv(Lv, vchunk), (unsigned)rows), dim3(TPB), 0, stream, (T*)dx, ds,
-                                        (const T*)dy, (const T*)x, s, Lv, vchunk);
-                   } else hipLaunchKernelGGL(scale_rows_bwd_kernel<T>, grid, dim3(TPB), 0, stream, (T*)dx, ds, (const T*)dy,
-                                      (const T*)x, s, L, chunk))
+  // W-wide items per workgroup: 2048 16-byte vectors (8 per thread) or 8192 elements
+  DT_SWITCH(dtype, if (L % VT<T>::W == 0 && al16(dx) && al16(dy) && al16(x))
+                     hipLaunchKernelGGL((scale_rows_bwd_kernel<T, VT<T>::W>), dim3(cdiv(L / VT<T>::W, 2048), (unsigned)rows), dim3(TPB), 0, stream, (T*)dx, ds,
+                                        (const T*)dy, (const T*)x, s, L, 2048);
+                   else hipLaunchKernelGGL((scale_rows_bwd_kernel<T, 1>), dim3(cdiv(L, 8192), (unsigned)rows), dim3(TPB), 0, stream, (T*)dx, ds, (const T*)dy,
+                                      (const T*)x, s, L, 8192))
 }
 int hdmoe_cat2_fwd(void* out, const void* a, const void* b, float wa, float wb, int Ca, int Cb, long rows, int dtype,
                    hipStream_t stream) {
-  DT_SWITCH(dtype, if (Ca % VT<T>::W == 0 && Cb % VT<T>::W == 0 && al16(out) && al16(a) && al16(b))
-                     L1D(cat2_fwd_vec_kernel<T>, rows * (Ca + Cb) / VT<T>::W, (T*)out, (const T*)a, (const T*)b, wa, wb, Ca, Cb, rows);
-                   else L1D(cat2_fwd_kernel<T>, rows * (Ca + Cb), (T*)out, (const T*)a, (const T*)b, wa, wb, Ca, Cb, rows))
+  DT_SWITCH(dtype, L1D_W(Ca % VT<T>::W == 0 && Cb % VT<T>::W == 0 && al16(out) && al16(a) && al16(b), cat2_fwd_kernel, rows * (Ca + Cb),
+                         (T*)out, (const T*)a, (const T*)b, wa, wb, Ca, Cb, rows))
 }
 int hdmoe_cat2_bwd(void* da, void* db, const void* dout, float wa, float wb, int Ca, int Cb, long rows, int dtype,
                    hipStream_t stream) {
-  DT_SWITCH(dtype, if (Ca % VT<T>::W == 0 && Cb % VT<T>::W == 0 && al16(da) && al16(db) && al16(dout))
-                     L1D(cat2_bwd_vec_kernel<T>, rows * (Ca + Cb) / VT<T>::W, (T*)da, (T*)db, (const T*)dout, wa, wb, Ca, Cb, rows);
-                   else L1D(cat2_bwd_kernel<T>, rows * (Ca + Cb), (T*)da, (T*)db, (const T*)dout, wa, wb, Ca, Cb, rows))
+  DT_SWITCH(dtype, L1D_W(Ca % VT<T>::W == 0 && Cb % VT<T>::W == 0 && al16(da) && al16(db) && al16(dout), cat2_bwd_kernel, rows * (Ca + Cb),
+                         (T*)da, (T*)db, (const T*)dout, wa, wb, Ca, Cb, rows))
 }
 int hdmoe_pool2(void* out, const void* x, int N, int Ho, int Wo, int C, float scale, int dtype, hipStream_t stream) {
   const long n = (long)N * Ho * Wo * C;
-  DT_SWITCH(dtype, if (C % VT<T>::W == 0 && al16(out) && al16(x)) L1D(pool2_vec_kernel<T>, n / VT<T>::W, (T*)out, (const T*)x, Ho, Wo, C / VT<T>::W, scale, n / VT<T>::W);
-                   else L1D(pool2_kernel<T>, n, (T*)out, (const T*)x, Ho, Wo, C, scale, n))
+  DT_SWITCH(dtype, L1D_W(C % VT<T>::W == 0 && al16(out) && al16(x), pool2_kernel, n, (T*)out, (const T*)x, Ho, Wo, C, scale, n))
 }
 int hdmoe_upsample2(void* out, const void* x, int N, int Ho, int Wo, int C, float scale, int dtype, hipStream_t stream) {
   if ((Ho | Wo) & 1) return HDMOE_EINVAL;
   const long n = (long)N * Ho * Wo * C;
-  DT_SWITCH(dtype, if (C % VT<T>::W == 0 && al16(out) && al16(x)) L1D(upsample2_vec_kernel<T>, n / VT<T>::W, (T*)out, (const T*)x, Ho, Wo, C / VT<T>::W, scale, n / VT<T>::W);
-                   else L1D(upsample2_kernel<T>, n, (T*)out, (const T*)x, Ho, Wo, C, scale, n))
+  DT_SWITCH(dtype, L1D_W(C % VT<T>::W == 0 && al16(out) && al16(x), upsample2_kernel, n, (T*)out, (const T*)x, Ho, Wo, C, scale, n))
 }
 int hdmoe_seq_reduce(float* out, const void* x, int N, long S, int C, float scale, int dtype, hipStream_t stream) {
   if (N > 65535 || C > 8192) return HDMOE_EINVAL;
@@ -1588,9 +1419,9 @@ int hdmoe_lerp_param_bwd(void* da, void* db, float* dalpha, const void* g, const
                          const float* alpha, long n, int dtype, hipStream_t stream) {
   DT_SWITCH(dtype, if (n % VT<T>::W == 0 && al16(da) && al16(db) && al16(g) && al16(a) && al16(b)) {
                      long blocks = (n / VT<T>::W + TPB - 1) / TPB; if (blocks > 1024) blocks = 1024;   // (one atomic per block)
-                     hipLaunchKernelGGL(lerp_param_bwd_vec_kernel<T>, dim3((unsigned)blocks), dim3(TPB), 0, stream, (T*)da, (T*)db, dalpha, (const T*)g,
-                                        (const T*)a, (const T*)b, alpha, n / VT<T>::W);
-                   } else L1D(lerp_param_bwd_kernel<T>, n, (T*)da, (T*)db, dalpha, (const T*)g, (const T*)a, (const T*)b, alpha, n))
+                     hipLaunchKernelGGL((lerp_param_bwd_kernel<T, VT<T>::W>), dim3((unsigned)blocks), dim3(TPB), 0, stream, (T*)da, (T*)db, dalpha, (const T*)g,
+                                        (const T*)a, (const T*)b, alpha, n);
+                   } else L1D((lerp_param_bwd_kernel<T, 1>), n, (T*)da, (T*)db, dalpha, (const T*)g, (const T*)a, (const T*)b, alpha, n))
 }
 int hdmoe_gate_mix_fwd(void* out, float* gate, const void* logits, const void* U, const void* A, long rows, int C,
                        int dtype, hipStream_t stream) {
@@ -1643,9 +1474,7 @@ int hdmoe_nhwc_to_nchw_guided_rows(float* out, const void* F, const float* sf, c
 int hdmoe_lerp_rows(void* out, const void* ref, const void* d, const float* g, long rows, long per, int dtype, hipStream_t stream) {
   if (!out || !ref || !d || !g || rows < 1 || per < 1) return HDMOE_EINVAL;
   const long n = rows * per;
-  DT_SWITCH(dtype, if (per % VT<T>::W == 0 && al16(out) && al16(ref) && al16(d))
-                     L1D(lerp_rows_vec_kernel<T>, n / VT<T>::W, (T*)out, (const T*)ref, (const T*)d, g, per / VT<T>::W, n / VT<T>::W);
-                   else L1D(lerp_rows_kernel<T>, n, (T*)out, (const T*)ref, (const T*)d, g, per, n))
+  DT_SWITCH(dtype, L1D_W(per % VT<T>::W == 0 && al16(out) && al16(ref) && al16(d), lerp_rows_kernel, n, (T*)out, (const T*)ref, (const T*)d, g, per, n))
 }
 static int relayout_entry(void* out, const void* in, const int* rows, int N, int H, int W, int C, int p, int hp, int wp, int order,
                           int to_img, int dtype, hipStream_t stream) {

@@ -54,11 +54,11 @@ __global__ __launch_bounds__(256) void eval_inputs_kernel(float* x, float* x0, f
     ld_row<T, W>(m, mean + it * chw + j);
 #pragma unroll
     for (int q = 0; q < W; ++q) m[q] = scale * m[q];
-    stw<W>(x0 + off, m);
+    stw<float, W>(x0 + off, m);
     eps_w<W>(e, j, (uint32_t)key, (uint32_t)(key >> 32));
 #pragma unroll
     for (int q = 0; q < W; ++q) m[q] = fmaf(sg, e[q], m[q]);
-    stw<W>(x + off, m);
+    stw<float, W>(x + off, m);
   }
 }
 

@@ -110,12 +110,12 @@ __global__ __launch_bounds__(256) void gen_noise_kernel(float* x, const float* x
   for (long v = (long)blockIdx.x * blockDim.x + threadIdx.x; v < nv; v += (long)gridDim.x * blockDim.x) {
     const long off = v * W;
     float p[W], e[W];
-    ldw<W>(p, x0 + off);
+    ldw<float, W>(p, x0 + off);
     eps_w<W>(e, off, lo, hi);
     const float sg = sigma[off / chw];
 #pragma unroll
     for (int j = 0; j < W; ++j) p[j] = fmaf(sg, e[j], p[j]);
-    stw<W>(x + off, p);
+    stw<float, W>(x + off, p);
   }
 }
 
@@ -161,12 +161,12 @@ __global__ __launch_bounds__(256) void gen_data_kernel(float* x, float* x0, cons
     }
 #pragma unroll
     for (int j = 0; j < W; ++j) p[j] = scale * m[j];
-    stw<W>(x0 + off, p);
+    stw<float, W>(x0 + off, p);
     eps_w<W>(e, off, lo, hi);
     const float sg = sigma[b];
 #pragma unroll
     for (int j = 0; j < W; ++j) p[j] = fmaf(sg, e[j], p[j]);
-    stw<W>(x + off, p);
+    stw<float, W>(x + off, p);
   }
 }
 

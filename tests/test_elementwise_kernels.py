@@ -40,10 +40,13 @@ for fp32 outputs.  The activation figure is film_silu at u e = -88: exp(88) is f
 v_rcp_f32 returns 0, so the whole error is the `under` term; every other activation case stays below 0.5.  bf16 outputs reach
 0.996: one rounding to 8 significant bits is the 2**-8 |r| part of their bound.
 
-Which kernel each shape reaches (W = 4 fp32 / 8 bf16 elements per 16-byte vector; "vec" = the *_vec_kernel, "scalar" = the plain one;
-the vector arm needs the count or channel count to divide by W and every al16-tested pointer 16-byte aligned):
+Which kernel each shape reaches (W = 4 fp32 / 8 bf16 elements per 16-byte vector; "vec" = the 16-byte arm, "scalar" = the one-element
+arm.  axpby, mp_silu_fwd/bwd, scale_rows_fwd/bwd, cat2_fwd/bwd, pool2, upsample2, lerp_param_bwd, lerp_rows, known_blend and
+film_silu_fwd are one body each: vec = op_kernel<T, W>, scalar = op_kernel<T, 1>.  film_silu_bwd, gate_mix_*, seq_reduce and the patch
+relayouts keep a *_vec_kernel of their own beside the plain one.  The vector arm needs the count or channel count to divide by W and every
+al16-tested pointer 16-byte aligned):
 * sizes n in {1, W-1, W, W+1, 255, 257, 1024+W}: W and 1024+W -> vec, the rest scalar (axpby, mp_silu_fwd/bwd; known_blend:
-  vec = known_blend_f4_kernel, fp32 only, bf16 always known_blend_kernel; mp_silu_bwd_add has no scalar arm and takes {W, 1024+W};
+  vec = known_blend_kernel<float, 4>, fp32 only, bf16 always known_blend_kernel<bf16, 1>; mp_silu_bwd_add has no scalar arm and takes {W, 1024+W};
   affine, mul, sigmoid_*, lerp_param_fwd, seq_bcast_add, bias_add, nchw_to_nhwc and the fp32 vector-path ops have one kernel).
   A view one element into a buffer, for each pointer in turn -> the scalar arm at a vec-eligible size.
 * grid cap: n = 524,288 + 259 elements (scalar) and (524,288 + 3) W elements (vec): 2050 blocks wanted, grid_for caps at 2048, the
