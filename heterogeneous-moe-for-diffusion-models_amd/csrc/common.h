@@ -126,6 +126,18 @@ DEVI float mp_silu_grad_f(float x) {
   return s * (1.f + x * (1.f - s)) * (1.f / MP_SILU_DIV);
 }
 
+// ---- GroupNorm arithmetic: the one definition for norm.hip and the ragged GroupNorm of ragged.hip -----------------------------
+// act: 0 none, 1 ReLU, 2 mp_silu
+DEVI float act_f(float z, int act) { return act == 1 ? fmaxf(z, 0.f) : (act == 2 ? mp_silu_f(z) : z); }
+DEVI float act_grad_f(float z, int act) { return act == 1 ? (z > 0.f ? 1.f : 0.f) : (act == 2 ? mp_silu_grad_f(z) : 1.f); }
+DEVI float gn_xhat(float x, float mean, float rstd) { return (x - mean) * rstd; }
+// forward: y = act(xhat * gamma + beta)
+DEVI float gn_fwd_f(float x, float mean, float rstd, float gamma, float beta, int act) { return act_f(gn_xhat(x, mean, rstd) * gamma + beta, act); }
+// backward: dz = dy * act'(xhat * gamma + beta);  dx = rstd * (dz * gamma - invm * (s1 + xhat * s2)) with the group's sums
+// s1 = sum dz * gamma, s2 = sum dz * gamma * xhat and invm = 1 / (elements per group)
+DEVI float gn_dz(float dy, float xh, float gamma, float beta, int act) { return dy * act_grad_f(xh * gamma + beta, act); }
+DEVI float gn_dx(float dz, float xh, float rstd, float gamma, float invm, float s1, float s2) { return rstd * (dz * gamma - invm * (s1 + xh * s2)); }
+
 // ---- 16-byte vector access helpers (guide G13: bf16 as 8-wide, fp32 as 4-wide) --------------------------------------
 template <typename T> struct VT;
 template <> struct VT<bf16> { static constexpr int W = 8; };
@@ -165,6 +177,20 @@ static inline bool hdmoe_first_on_device(unsigned long long& mask) {
 }
 static inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
 
+// ---- one-dimensional launches: grid-stride loop over n items, workgroups of 256 threads, at most `cap` of them (guide G11: 2048)
+#define GRID_STRIDE(i, n) for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
+static inline unsigned grid_for(long n, long cap = 2048) {
+  long b = (n + 255) / 256;
+  if (b > cap) b = cap;
+  if (b < 1) b = 1;
+  return (unsigned)b;
+}
+// CALL with T = the element type of a C-ABI dtype code, inside an entry point that returns a status
+#define DT_SWITCH(dtype, ...)                            \
+  if ((dtype) == HDMOE_F32) { using T = float; __VA_ARGS__; }   \
+  else if ((dtype) == HDMOE_BF16) { using T = bf16; __VA_ARGS__; } \
+  else return HDMOE_EDTYPE;
+
 // ---------------------------------------------------------------- counter RNG (Philox4x32-10)
 HDI void philox(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1, uint32_t* o) {
   uint32_t c[4] = {c0, c1, 0u, 0u};
@@ -200,14 +226,28 @@ DEVI void randn4(long q, uint32_t seed_lo, uint32_t seed_hi, float* v) {
   v[0] = a0 * cosf(t0); v[1] = a0 * sinf(t0); v[2] = a1 * cosf(t1); v[3] = a1 * sinf(t1);
 }
 // W elements of T per thread, as floats: one 16-byte load / store when W == VT<T>::W (the launcher checks the count and the alignment), one
-// element when W == 1.  A kernel body written over W lanes serves both arms of its entry point.
+// element when W == 1.  A kernel body written over W lanes serves both arms of its entry point.  bf16 also at W == 4 (8 bytes), for a
+// kernel that reads bf16 next to fp32 tensors at the fp32 width.
 template <typename T, int W> DEVI void ldw(float* f, const T* p) {
-  static_assert(W == 1 || W == VT<T>::W, "one element or one 16-byte vector");
-  if constexpr (W == 1) f[0] = to_f(*p); else vload<T>(f, p);
+  static_assert(W == 1 || W == VT<T>::W || (W == 4 && sizeof(T) == 2), "one element, one 16-byte vector or four bf16");
+  if constexpr (W == 1) f[0] = to_f(*p);
+  else if constexpr (W == VT<T>::W) vload<T>(f, p);
+  else {
+    const bf16x4 v = *reinterpret_cast<const bf16x4*>(p);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) f[j] = (float)v[j];
+  }
 }
 template <typename T, int W> DEVI void stw(T* p, const float* f) {
-  static_assert(W == 1 || W == VT<T>::W, "one element or one 16-byte vector");
-  if constexpr (W == 1) *p = from_f<T>(f[0]); else vstore<T>(p, f);
+  static_assert(W == 1 || W == VT<T>::W || (W == 4 && sizeof(T) == 2), "one element, one 16-byte vector or four bf16");
+  if constexpr (W == 1) *p = from_f<T>(f[0]);
+  else if constexpr (W == VT<T>::W) vstore<T>(p, f);
+  else {
+    bf16x4 v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (bf16)f[j];
+    *reinterpret_cast<bf16x4*>(p) = v;
+  }
 }
 // the draws of elements off ... off + W - 1 (off % W == 0): element j is lane j % 4 of block j / 4 whatever W is
 template <int W> DEVI void eps_w(float* e, long off, uint32_t lo, uint32_t hi) {

@@ -8,13 +8,6 @@
 namespace {
 
 constexpr int TPB = 256;
-static inline unsigned grid_for(long n) {
-  long b = (n + TPB - 1) / TPB;
-  if (b > 2048) b = 2048;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
-#define GRID_STRIDE(i, n) for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
 
 // Row window of a kernel over n = N * per work items (per items for each leading row): rows = DEVICE {begin, end} restricts the launch
 // to the items [i0, i0 + n) of rows [begin, end), clamped to [0, N]; null leaves all n items.  The grid stays the all-rows one.
@@ -1076,11 +1069,8 @@ __global__ void sum_n_kernel(T* out, SumSrcs s, int n, long nv, long nelem) {
 
 }  // namespace
 
-#define DT_SWITCH(dtype, CALL)                    \
-  if ((dtype) == HDMOE_F32) { using T = float; CALL; }   \
-  else if ((dtype) == HDMOE_BF16) { using T = bf16; CALL; } \
-  else return HDMOE_EDTYPE;                       \
-  return hdmoe_launch_status();
+// an entry point that ends in one dtype switch: the launch, then its status
+#define DT_LAUNCH(dtype, ...) DT_SWITCH(dtype, __VA_ARGS__) return hdmoe_launch_status();
 
 #define L1D(kernel, n, ...) hipLaunchKernelGGL(kernel, dim3(grid_for(n)), dim3(TPB), 0, stream, __VA_ARGS__)
 // the two arms of a kernel<T, W> over n elements: 16-byte vectors when `vec_ok` (the count divides by VT<T>::W, the pointers are aligned), else W = 1
@@ -1107,7 +1097,7 @@ __global__ __launch_bounds__(256) void exp_rate_kernel(float* out, int iters) {
 extern "C" {
 
 int hdmoe_axpby(void* out, const void* x, const void* y, float a, float b, long n, int dtype, hipStream_t stream) {
-  DT_SWITCH(dtype, L1D_W(n % VT<T>::W == 0 && al16(out) && al16(x) && al16(y), axpby_kernel, n, (T*)out, (const T*)x, (const T*)y, a, b, n))
+  DT_LAUNCH(dtype, L1D_W(n % VT<T>::W == 0 && al16(out) && al16(x) && al16(y), axpby_kernel, n, (T*)out, (const T*)x, (const T*)y, a, b, n))
 }
 /* EDM sampler stage pieces (fp32 latents; t: device float64 schedule of N + 1 values, idx: device stage index) */
 int hdmoe_sched_pick(float* sigma, const double* t, const int* idx, int off, hipStream_t stream) {
@@ -1207,7 +1197,7 @@ int hdmoe_known_blend(void* x, const void* x0, const void* noise, const float* m
     L1D((known_blend_kernel<float, 4>), n / 4, (float*)x, (const float*)x0, (const float*)noise, mask, s, n);
     return hdmoe_launch_status();
   }
-  DT_SWITCH(dtype, L1D((known_blend_kernel<T, 1>), n, (T*)x, (const T*)x0, (const T*)noise, mask, s, n))
+  DT_LAUNCH(dtype, L1D((known_blend_kernel<T, 1>), n, (T*)x, (const T*)x0, (const T*)noise, mask, s, n))
 }
 int hdmoe_exp_rate(float* out, int blocks, int iters, hipStream_t stream) {
   if (!out || blocks < 1 || iters < 1) return HDMOE_EINVAL;
@@ -1220,13 +1210,13 @@ int hdmoe_sum_n(void* out, const void* const* srcs, const float* src_scale, int 
   bool al = al16(out);
   for (int k = 0; k < 16; ++k) { s.p[k] = srcs[k < n ? k : 0]; s.sc[k] = (src_scale && k < n) ? src_scale[k] : 1.f; al = al && al16(s.p[k]); }
   if (!al) return HDMOE_EINVAL;
-  DT_SWITCH(dtype, L1D(sum_n_kernel<T>, (nelem + VT<T>::W - 1) / VT<T>::W, (T*)out, s, n, (nelem + VT<T>::W - 1) / VT<T>::W, nelem))
+  DT_LAUNCH(dtype, L1D(sum_n_kernel<T>, (nelem + VT<T>::W - 1) / VT<T>::W, (T*)out, s, n, (nelem + VT<T>::W - 1) / VT<T>::W, nelem))
 }
 int hdmoe_affine(void* out, const void* x, float a, float c, long n, int dtype, hipStream_t stream) {
-  DT_SWITCH(dtype, L1D(affine_kernel<T>, n, (T*)out, (const T*)x, a, c, n))
+  DT_LAUNCH(dtype, L1D(affine_kernel<T>, n, (T*)out, (const T*)x, a, c, n))
 }
 int hdmoe_mul(void* out, const void* x, const void* y, long n, int dtype, hipStream_t stream) {
-  DT_SWITCH(dtype, L1D(mul_kernel<T>, n, (T*)out, (const T*)x, (const T*)y, n))
+  DT_LAUNCH(dtype, L1D(mul_kernel<T>, n, (T*)out, (const T*)x, (const T*)y, n))
 }
 int hdmoe_cast(void* out, const void* x, long n, int dt_in, int dt_out, hipStream_t stream) {
   if (dt_in == HDMOE_F32 && dt_out == HDMOE_BF16) L1D((cast_kernel<float, bf16>), n, (bf16*)out, (const float*)x, n);
@@ -1247,26 +1237,26 @@ int hdmoe_fir_resample(void* y, const void* x, const float* taps, int L, int pad
   for (int i = 0; i < 8; ++i) f.k[i] = i < L ? taps[i] : 0.f;
   const long total = (long)N * Ho * Wo * C;
   if (total == 0) return HDMOE_OK;
-  DT_SWITCH(dtype, if (up) L1D(fir_up_kernel<T>, total, (T*)y, (const T*)x, f, L, pad, scale, H, W, Ho, Wo, C, total);
+  DT_LAUNCH(dtype, if (up) L1D(fir_up_kernel<T>, total, (T*)y, (const T*)x, f, L, pad, scale, H, W, Ho, Wo, C, total);
                    else L1D(fir_down_kernel<T>, total, (T*)y, (const T*)x, f, L, pad, scale, H, W, Ho, Wo, C, total))
 }
 int hdmoe_mp_silu_fwd(void* out, const void* x, long n, int dtype, hipStream_t stream) {
-  DT_SWITCH(dtype, L1D_W(n % VT<T>::W == 0 && al16(out) && al16(x), mp_silu_fwd_kernel, n, (T*)out, (const T*)x, n))
+  DT_LAUNCH(dtype, L1D_W(n % VT<T>::W == 0 && al16(out) && al16(x), mp_silu_fwd_kernel, n, (T*)out, (const T*)x, n))
 }
 int hdmoe_mp_silu_bwd(void* dx, const void* dy, const void* x, long n, int dtype, hipStream_t stream) {
-  DT_SWITCH(dtype, L1D_W(n % VT<T>::W == 0 && al16(dx) && al16(dy) && al16(x), mp_silu_bwd_kernel, n, (T*)dx, (const T*)dy, (const T*)x, n))
+  DT_LAUNCH(dtype, L1D_W(n % VT<T>::W == 0 && al16(dx) && al16(dy) && al16(x), mp_silu_bwd_kernel, n, (T*)dx, (const T*)dy, (const T*)x, n))
 }
 /* dx = sx * gx + dy * mp_silu'(x); 16-byte aligned, n % (16 / esz) == 0 */
 int hdmoe_mp_silu_bwd_add(void* dx, const void* dy, const void* x, const void* gx, float sx, long n, int dtype, hipStream_t stream) {
   if (!dx || !dy || !x || !gx || !(al16(dx) && al16(dy) && al16(x) && al16(gx))) return HDMOE_EINVAL;
-  DT_SWITCH(dtype, if (n % VT<T>::W == 0) L1D(mp_silu_bwd_add_vec_kernel<T>, n / VT<T>::W, (T*)dx, (const T*)dy, (const T*)x, (const T*)gx, sx, n / VT<T>::W);
+  DT_LAUNCH(dtype, if (n % VT<T>::W == 0) L1D(mp_silu_bwd_add_vec_kernel<T>, n / VT<T>::W, (T*)dx, (const T*)dy, (const T*)x, (const T*)gx, sx, n / VT<T>::W);
                    else return HDMOE_EINVAL)
 }
 /* out = mp_cat(a, b) (weights wa, wb), out_h = mp_silu(out); Ca, Cb multiples of 16 / esz */
 int hdmoe_cat2_silu_fwd(void* out, void* out_h, const void* a, const void* b, float wa, float wb, int Ca, int Cb, long rows, int dtype,
                         hipStream_t stream) {
   if (!(al16(out) && al16(out_h) && al16(a) && al16(b)) || !out || !out_h) return HDMOE_EINVAL;
-  DT_SWITCH(dtype, if (Ca % VT<T>::W == 0 && Cb % VT<T>::W == 0)
+  DT_LAUNCH(dtype, if (Ca % VT<T>::W == 0 && Cb % VT<T>::W == 0)
                      L1D(cat2_silu_fwd_vec_kernel<T>, rows * (Ca + Cb) / VT<T>::W, (T*)out, (T*)out_h, (const T*)a, (const T*)b, wa, wb, Ca, Cb, rows);
                    else return HDMOE_EINVAL)
 }
@@ -1274,26 +1264,26 @@ int hdmoe_cat2_silu_fwd(void* out, void* out_h, const void* a, const void* b, fl
 int hdmoe_cat2_silu_bwd(void* da, void* db, const void* gcat, const void* gh, const void* xcat, float wa, float wb, int Ca, int Cb,
                         long rows, int dtype, hipStream_t stream) {
   if (!(al16(da) && al16(db) && al16(gcat) && al16(gh) && al16(xcat)) || !gh || !xcat) return HDMOE_EINVAL;
-  DT_SWITCH(dtype, if (Ca % VT<T>::W == 0 && Cb % VT<T>::W == 0)
+  DT_LAUNCH(dtype, if (Ca % VT<T>::W == 0 && Cb % VT<T>::W == 0)
                      L1D(cat2_silu_bwd_vec_kernel<T>, rows * (Ca + Cb) / VT<T>::W, (T*)da, (T*)db, (const T*)gcat, (const T*)gh, (const T*)xcat, wa, wb, Ca, Cb, rows);
                    else return HDMOE_EINVAL)
 }
 int hdmoe_sigmoid_fwd(void* out, const void* x, float a, long n, int dtype, hipStream_t stream) {
-  DT_SWITCH(dtype, L1D(sigmoid_fwd_kernel<T>, n, (T*)out, (const T*)x, a, n))
+  DT_LAUNCH(dtype, L1D(sigmoid_fwd_kernel<T>, n, (T*)out, (const T*)x, a, n))
 }
 int hdmoe_sigmoid_bwd(void* dx, const void* dy, const void* y, float a, long n, int dtype, hipStream_t stream) {
-  DT_SWITCH(dtype, L1D(sigmoid_bwd_kernel<T>, n, (T*)dx, (const T*)dy, (const T*)y, a, n))
+  DT_LAUNCH(dtype, L1D(sigmoid_bwd_kernel<T>, n, (T*)dx, (const T*)dy, (const T*)y, a, n))
 }
 int hdmoe_film_silu_fwd(void* out, const void* u, const float* e, int N, long HW, int C, int dtype, hipStream_t stream) {
   const long n = (long)N * HW * C;
-  DT_SWITCH(dtype, L1D_W(C % VT<T>::W == 0 && al16(out) && al16(u), film_silu_fwd_kernel, n, (T*)out, (const T*)u, e, HW, C, n, 0u, 0u, nullptr, 0.f))
+  DT_LAUNCH(dtype, L1D_W(C % VT<T>::W == 0 && al16(out) && al16(u), film_silu_fwd_kernel, n, (T*)out, (const T*)u, e, HW, C, n, 0u, 0u, nullptr, 0.f))
 }
 // FiLM + mp_silu + F.dropout in one pass (vectorised layouts only: C % (16/sizeof(T)) == 0)
 int hdmoe_film_silu_drop_fwd(void* out, const void* u, const float* e, int N, long HW, int C, unsigned long long seed,
                              const unsigned long long* seed_dev, float p, int dtype, hipStream_t stream) {
   const long n = (long)N * HW * C;
   if (p < 0.f || p >= 1.f) return HDMOE_EINVAL;
-  DT_SWITCH(dtype, if (C % VT<T>::W == 0 && al16(out) && al16(u)) L1D((film_silu_fwd_kernel<T, VT<T>::W>), n / VT<T>::W, (T*)out, (const T*)u, e, HW, C, n,
+  DT_LAUNCH(dtype, if (C % VT<T>::W == 0 && al16(out) && al16(u)) L1D((film_silu_fwd_kernel<T, VT<T>::W>), n / VT<T>::W, (T*)out, (const T*)u, e, HW, C, n,
                                                                      (uint32_t)seed, (uint32_t)(seed >> 32), seed_dev, p);
                    else return HDMOE_EINVAL)
 }
@@ -1302,7 +1292,7 @@ int hdmoe_film_silu_drop_bwd(void* du, float* de, const void* da, const void* u,
   if (N > 65535 || p < 0.f || p >= 1.f) return HDMOE_EINVAL;
   const int chunk = 256;
   dim3 grid(cdiv(HW, chunk), N);
-  DT_SWITCH(dtype, if (chunk_fixed_ok<T>(C) && al16(du) && al16(da) && al16(u))
+  DT_LAUNCH(dtype, if (chunk_fixed_ok<T>(C) && al16(du) && al16(da) && al16(u))
                      hipLaunchKernelGGL(film_silu_bwd_vec_kernel<T>, grid, dim3(TPB), C * sizeof(float), stream, (T*)du, de, (const T*)da, (const T*)u, e, HW, C, chunk,
                                         (uint32_t)seed, (uint32_t)(seed >> 32), seed_dev, p);
                    else return HDMOE_EINVAL)
@@ -1332,20 +1322,20 @@ int hdmoe_film_silu_bwd(void* du, float* de, const void* da, const void* u, cons
   if (N > 65535) return HDMOE_EINVAL;
   const int chunk = 256;
   dim3 grid(cdiv(HW, chunk), N);
-  DT_SWITCH(dtype, if (chunk_fixed_ok<T>(C) && al16(du) && al16(da) && al16(u))
+  DT_LAUNCH(dtype, if (chunk_fixed_ok<T>(C) && al16(du) && al16(da) && al16(u))
                      hipLaunchKernelGGL(film_silu_bwd_vec_kernel<T>, grid, dim3(TPB), C * sizeof(float), stream, (T*)du, de, (const T*)da, (const T*)u, e, HW, C, chunk, 0u, 0u, nullptr, 0.f);
                    else hipLaunchKernelGGL(film_silu_bwd_kernel<T>, grid, dim3(TPB), C * sizeof(float), stream, (T*)du, de,
                                       (const T*)da, (const T*)u, e, HW, C, chunk))
 }
 int hdmoe_scale_rows_fwd(void* out, const void* x, const float* s, long rows, long L, int dtype, hipStream_t stream) {
   const long n = rows * L;
-  DT_SWITCH(dtype, L1D_W(L % VT<T>::W == 0 && al16(out) && al16(x), scale_rows_fwd_kernel, n, (T*)out, (const T*)x, s, L, n))
+  DT_LAUNCH(dtype, L1D_W(L % VT<T>::W == 0 && al16(out) && al16(x), scale_rows_fwd_kernel, n, (T*)out, (const T*)x, s, L, n))
 }
 int hdmoe_scale_rows_bwd(void* dx, float* ds, const void* dy, const void* x, const float* s, long rows, long L,
                          int dtype, hipStream_t stream) {
   if (rows > 65535) return HDMOE_EINVAL;
   // W-wide items per workgroup: 2048 16-byte vectors (8 per thread) or 8192 elements
-  DT_SWITCH(dtype, if (L % VT<T>::W == 0 && al16(dx) && al16(dy) && al16(x))
+  DT_LAUNCH(dtype, if (L % VT<T>::W == 0 && al16(dx) && al16(dy) && al16(x))
                      hipLaunchKernelGGL((scale_rows_bwd_kernel<T, VT<T>::W>), dim3(cdiv(L / VT<T>::W, 2048), (unsigned)rows), dim3(TPB), 0, stream, (T*)dx, ds,
                                         (const T*)dy, (const T*)x, s, L, 2048);
                    else hipLaunchKernelGGL((scale_rows_bwd_kernel<T, 1>), dim3(cdiv(L, 8192), (unsigned)rows), dim3(TPB), 0, stream, (T*)dx, ds, (const T*)dy,
@@ -1353,27 +1343,27 @@ int hdmoe_scale_rows_bwd(void* dx, float* ds, const void* dy, const void* x, con
 }
 int hdmoe_cat2_fwd(void* out, const void* a, const void* b, float wa, float wb, int Ca, int Cb, long rows, int dtype,
                    hipStream_t stream) {
-  DT_SWITCH(dtype, L1D_W(Ca % VT<T>::W == 0 && Cb % VT<T>::W == 0 && al16(out) && al16(a) && al16(b), cat2_fwd_kernel, rows * (Ca + Cb),
+  DT_LAUNCH(dtype, L1D_W(Ca % VT<T>::W == 0 && Cb % VT<T>::W == 0 && al16(out) && al16(a) && al16(b), cat2_fwd_kernel, rows * (Ca + Cb),
                          (T*)out, (const T*)a, (const T*)b, wa, wb, Ca, Cb, rows))
 }
 int hdmoe_cat2_bwd(void* da, void* db, const void* dout, float wa, float wb, int Ca, int Cb, long rows, int dtype,
                    hipStream_t stream) {
-  DT_SWITCH(dtype, L1D_W(Ca % VT<T>::W == 0 && Cb % VT<T>::W == 0 && al16(da) && al16(db) && al16(dout), cat2_bwd_kernel, rows * (Ca + Cb),
+  DT_LAUNCH(dtype, L1D_W(Ca % VT<T>::W == 0 && Cb % VT<T>::W == 0 && al16(da) && al16(db) && al16(dout), cat2_bwd_kernel, rows * (Ca + Cb),
                          (T*)da, (T*)db, (const T*)dout, wa, wb, Ca, Cb, rows))
 }
 int hdmoe_pool2(void* out, const void* x, int N, int Ho, int Wo, int C, float scale, int dtype, hipStream_t stream) {
   const long n = (long)N * Ho * Wo * C;
-  DT_SWITCH(dtype, L1D_W(C % VT<T>::W == 0 && al16(out) && al16(x), pool2_kernel, n, (T*)out, (const T*)x, Ho, Wo, C, scale, n))
+  DT_LAUNCH(dtype, L1D_W(C % VT<T>::W == 0 && al16(out) && al16(x), pool2_kernel, n, (T*)out, (const T*)x, Ho, Wo, C, scale, n))
 }
 int hdmoe_upsample2(void* out, const void* x, int N, int Ho, int Wo, int C, float scale, int dtype, hipStream_t stream) {
   if ((Ho | Wo) & 1) return HDMOE_EINVAL;
   const long n = (long)N * Ho * Wo * C;
-  DT_SWITCH(dtype, L1D_W(C % VT<T>::W == 0 && al16(out) && al16(x), upsample2_kernel, n, (T*)out, (const T*)x, Ho, Wo, C, scale, n))
+  DT_LAUNCH(dtype, L1D_W(C % VT<T>::W == 0 && al16(out) && al16(x), upsample2_kernel, n, (T*)out, (const T*)x, Ho, Wo, C, scale, n))
 }
 int hdmoe_seq_reduce(float* out, const void* x, int N, long S, int C, float scale, int dtype, hipStream_t stream) {
   if (N > 65535 || C > 8192) return HDMOE_EINVAL;
   // accumulates into `out` (callers pass zeros or a running sum); deterministic: no atomics, fixed summation order
-  DT_SWITCH(dtype, if (chunk_fixed_ok<T>(C) && al16(x)) hipLaunchKernelGGL(seq_reduce_det_vec_kernel<T>, dim3(N), dim3(256),
+  DT_LAUNCH(dtype, if (chunk_fixed_ok<T>(C) && al16(x)) hipLaunchKernelGGL(seq_reduce_det_vec_kernel<T>, dim3(N), dim3(256),
                                                                            (size_t)(256 / (C / VT<T>::W)) * C * sizeof(float), stream,
                                                                            out, (const T*)x, S, C, scale);
                    else hipLaunchKernelGGL(seq_reduce_det_kernel<T>, dim3(cdiv(C, TPB), N), dim3(TPB), 0, stream, out, (const T*)x, S, C, scale))
@@ -1381,17 +1371,17 @@ int hdmoe_seq_reduce(float* out, const void* x, int N, long S, int C, float scal
 int hdmoe_seq_bcast_add(void* out, const void* x, const float* t, int N, long S, int C, float scale, int dtype,
                         hipStream_t stream) {
   const long n = (long)N * S * C;
-  DT_SWITCH(dtype, L1D(seq_bcast_add_kernel<T>, n, (T*)out, (const T*)x, t, S, C, scale, n))
+  DT_LAUNCH(dtype, L1D(seq_bcast_add_kernel<T>, n, (T*)out, (const T*)x, t, S, C, scale, n))
 }
 int hdmoe_bias_add(void* out, const void* x, const float* bias, long rows, long L, int dtype, hipStream_t stream) {
   const long n = rows * L;
-  DT_SWITCH(dtype, L1D(bias_add_kernel<T>, n, (T*)out, (const T*)x, bias, L, n, nullptr, 0))
+  DT_LAUNCH(dtype, L1D(bias_add_kernel<T>, n, (T*)out, (const T*)x, bias, L, n, nullptr, 0))
 }
 int hdmoe_colsum(float* out, const void* dy, long rows, long L, int dtype, hipStream_t stream) {
   const int rchunk = 64;
   if (cdiv(rows, rchunk) > 65535) return HDMOE_EINVAL;
   dim3 grid(cdiv(L, TPB), cdiv(rows, rchunk));
-  DT_SWITCH(dtype, hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(TPB), 0, stream, out, (const T*)dy, rows, L, rchunk, nullptr, 0))
+  DT_LAUNCH(dtype, hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(TPB), 0, stream, out, (const T*)dy, rows, L, rchunk, nullptr, 0))
 }
 /* The two above over the leading rows [rows[0], rows[1]) of an [N][S][L] tensor only (rows: DEVICE pointer to two ints, read by the
  * kernel; the grid is the all-rows one, nothing outside the window is read or written, an empty window does nothing). */
@@ -1400,7 +1390,7 @@ int hdmoe_bias_add_rows(void* out, const void* x, const float* bias, const int* 
   const long n = (long)N * S * L;
   if (n == 0) return HDMOE_OK;
   hdmoe_count_selection(HDMOE_SEL_ROW_WINDOW);
-  DT_SWITCH(dtype, L1D(bias_add_kernel<T>, n, (T*)out, (const T*)x, bias, L, n, rows, S * L))
+  DT_LAUNCH(dtype, L1D(bias_add_kernel<T>, n, (T*)out, (const T*)x, bias, L, n, rows, S * L))
 }
 int hdmoe_colsum_rows(float* out, const void* dy, const int* rows, int N, long S, long L, int dtype, hipStream_t stream) {
   if (!out || !dy || !rows || N < 0 || S < 1 || L < 1) return HDMOE_EINVAL;
@@ -1410,14 +1400,14 @@ int hdmoe_colsum_rows(float* out, const void* dy, const int* rows, int N, long S
   if (cdiv(mrows, rchunk) > 65535) return HDMOE_EINVAL;
   dim3 grid(cdiv(L, TPB), cdiv(mrows, rchunk));
   hdmoe_count_selection(HDMOE_SEL_ROW_WINDOW);
-  DT_SWITCH(dtype, hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(TPB), 0, stream, out, (const T*)dy, mrows, L, rchunk, rows, S))
+  DT_LAUNCH(dtype, hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(TPB), 0, stream, out, (const T*)dy, mrows, L, rchunk, rows, S))
 }
 int hdmoe_lerp_param_fwd(void* out, const void* a, const void* b, const float* alpha, long n, int dtype, hipStream_t stream) {
-  DT_SWITCH(dtype, L1D(lerp_param_fwd_kernel<T>, n, (T*)out, (const T*)a, (const T*)b, alpha, n))
+  DT_LAUNCH(dtype, L1D(lerp_param_fwd_kernel<T>, n, (T*)out, (const T*)a, (const T*)b, alpha, n))
 }
 int hdmoe_lerp_param_bwd(void* da, void* db, float* dalpha, const void* g, const void* a, const void* b,
                          const float* alpha, long n, int dtype, hipStream_t stream) {
-  DT_SWITCH(dtype, if (n % VT<T>::W == 0 && al16(da) && al16(db) && al16(g) && al16(a) && al16(b)) {
+  DT_LAUNCH(dtype, if (n % VT<T>::W == 0 && al16(da) && al16(db) && al16(g) && al16(a) && al16(b)) {
                      long blocks = (n / VT<T>::W + TPB - 1) / TPB; if (blocks > 1024) blocks = 1024;   // (one atomic per block)
                      hipLaunchKernelGGL((lerp_param_bwd_kernel<T, VT<T>::W>), dim3((unsigned)blocks), dim3(TPB), 0, stream, (T*)da, (T*)db, dalpha, (const T*)g,
                                         (const T*)a, (const T*)b, alpha, n);
@@ -1425,7 +1415,7 @@ int hdmoe_lerp_param_bwd(void* da, void* db, float* dalpha, const void* g, const
 }
 int hdmoe_gate_mix_fwd(void* out, float* gate, const void* logits, const void* U, const void* A, long rows, int C,
                        int dtype, hipStream_t stream) {
-  DT_SWITCH(dtype, {
+  DT_LAUNCH(dtype, {
     const int lpr = C / VT<T>::W;
     if (C % VT<T>::W == 0 && lpr >= 1 && lpr <= 64 && (lpr & (lpr - 1)) == 0 && al16(out) && al16(U) && al16(A))
       L1D(gate_mix_fwd_vec_kernel<T>, rows * lpr, (T*)out, gate, (const T*)logits, (const T*)U, (const T*)A, lpr, rows * lpr);
@@ -1434,7 +1424,7 @@ int hdmoe_gate_mix_fwd(void* out, float* gate, const void* logits, const void* U
 }
 int hdmoe_gate_mix_bwd(void* dU, void* dA, void* dlogits, const void* dout, const float* dgate, const float* gate,
                        const void* U, const void* A, long rows, int C, int dtype, hipStream_t stream) {
-  DT_SWITCH(dtype, {
+  DT_LAUNCH(dtype, {
     const int lpr = C / VT<T>::W;
     if (C % VT<T>::W == 0 && lpr >= 1 && lpr <= 64 && (lpr & (lpr - 1)) == 0 && al16(dU) && al16(dA) && al16(dout) && al16(U) && al16(A))
       L1D(gate_mix_bwd_vec_kernel<T>, (rows * lpr + 63) / 64 * 64, (T*)dU, (T*)dA, (T*)dlogits, (const T*)dout, dgate, gate, (const T*)U,
@@ -1452,29 +1442,29 @@ int hdmoe_softmax_rows_bwd(float* dx, const float* dy, const float* y, long rows
 }
 int hdmoe_nchw_to_nhwc(void* out, const float* x, const float* s, int N, int C, long HW, int dtype, hipStream_t stream) {
   const long n = (long)N * C * HW;
-  DT_SWITCH(dtype, L1D(nchw_to_nhwc_kernel<T>, n, (T*)out, x, s, C, HW, n))
+  DT_LAUNCH(dtype, L1D(nchw_to_nhwc_kernel<T>, n, (T*)out, x, s, C, HW, n))
 }
 int hdmoe_nhwc_to_nchw(float* out, const void* F, const float* sf, const float* x, const float* sx, int N, int C, long HW,
                        int dtype, hipStream_t stream) {
   const long n = (long)N * C * HW;
-  DT_SWITCH(dtype, L1D(nhwc_to_nchw_kernel<T>, n, out, (const T*)F, sf, x, sx, C, HW, n))
+  DT_LAUNCH(dtype, L1D(nhwc_to_nchw_kernel<T>, n, out, (const T*)F, sf, x, sx, C, HW, n))
 }
 int hdmoe_nhwc_to_nchw_guided(float* out, const void* F, const float* sf, const float* x, const float* sx, float g, int N, int C, long HW,
                               int dtype, hipStream_t stream) {
   if (!out || !F || N < 1 || C < 1 || HW < 1 || !(g == g) || g - g != 0.f) return HDMOE_EINVAL;
   const long n = (long)N * C * HW;
-  DT_SWITCH(dtype, L1D(nhwc_to_nchw_guided_kernel<T>, n, out, (const T*)F, sf, x, sx, g, C, HW, n))
+  DT_LAUNCH(dtype, L1D(nhwc_to_nchw_guided_kernel<T>, n, out, (const T*)F, sf, x, sx, g, C, HW, n))
 }
 int hdmoe_nhwc_to_nchw_guided_rows(float* out, const void* F, const float* sf, const float* x, const float* sx, const float* g, int N, int C,
                                    long HW, int dtype, hipStream_t stream) {
   if (!out || !F || !g || N < 1 || C < 1 || HW < 1) return HDMOE_EINVAL;
   const long n = (long)N * C * HW;
-  DT_SWITCH(dtype, L1D(nhwc_to_nchw_guided_rows_kernel<T>, n, out, (const T*)F, sf, x, sx, g, C, HW, n))
+  DT_LAUNCH(dtype, L1D(nhwc_to_nchw_guided_rows_kernel<T>, n, out, (const T*)F, sf, x, sx, g, C, HW, n))
 }
 int hdmoe_lerp_rows(void* out, const void* ref, const void* d, const float* g, long rows, long per, int dtype, hipStream_t stream) {
   if (!out || !ref || !d || !g || rows < 1 || per < 1) return HDMOE_EINVAL;
   const long n = rows * per;
-  DT_SWITCH(dtype, L1D_W(per % VT<T>::W == 0 && al16(out) && al16(ref) && al16(d), lerp_rows_kernel, n, (T*)out, (const T*)ref, (const T*)d, g, per, n))
+  DT_LAUNCH(dtype, L1D_W(per % VT<T>::W == 0 && al16(out) && al16(ref) && al16(d), lerp_rows_kernel, n, (T*)out, (const T*)ref, (const T*)d, g, per, n))
 }
 static int relayout_entry(void* out, const void* in, const int* rows, int N, int H, int W, int C, int p, int hp, int wp, int order,
                           int to_img, int dtype, hipStream_t stream) {
@@ -1483,15 +1473,15 @@ static int relayout_entry(void* out, const void* in, const int* rows, int N, int
   if (rows) hdmoe_count_selection(HDMOE_SEL_ROW_WINDOW);
   if (!to_img && order == 1 && al16(out) && (dtype == HDMOE_BF16 || dtype == HDMOE_F32) && p % (dtype == HDMOE_BF16 ? 8 : 4) == 0) {
     const long nv = (long)N * hp * wp * C * p * p / (dtype == HDMOE_BF16 ? 8 : 4);      // covers the padded tokens too (zeros)
-    DT_SWITCH(dtype, L1D(patch_to_tokens_o1_vec_kernel<T>, nv, (T*)out, (const T*)in, H, W, C, p, hp, wp, nv, rows))
+    DT_LAUNCH(dtype, L1D(patch_to_tokens_o1_vec_kernel<T>, nv, (T*)out, (const T*)in, H, W, C, p, hp, wp, nv, rows))
   }
   if (al16(out) && al16(in) && C % (dtype == HDMOE_BF16 ? 8 : 4) == 0 && (dtype == HDMOE_BF16 || dtype == HDMOE_F32)) {
     const long nv = n / (dtype == HDMOE_BF16 ? 8 : 4);
-    if (to_img) { DT_SWITCH(dtype, L1D((patch_relayout_vec_kernel<T, true>), nv, (T*)out, (const T*)in, H, W, C, p, hp, wp, order, nv, rows)) }
-    else { DT_SWITCH(dtype, L1D((patch_relayout_vec_kernel<T, false>), nv, (T*)out, (const T*)in, H, W, C, p, hp, wp, order, nv, rows)) }
+    if (to_img) { DT_LAUNCH(dtype, L1D((patch_relayout_vec_kernel<T, true>), nv, (T*)out, (const T*)in, H, W, C, p, hp, wp, order, nv, rows)) }
+    else { DT_LAUNCH(dtype, L1D((patch_relayout_vec_kernel<T, false>), nv, (T*)out, (const T*)in, H, W, C, p, hp, wp, order, nv, rows)) }
   }
-  if (to_img) { DT_SWITCH(dtype, L1D((patch_relayout_kernel<T, true>), n, (T*)out, (const T*)in, H, W, C, p, hp, wp, order, n, rows)) }
-  else { DT_SWITCH(dtype, L1D((patch_relayout_kernel<T, false>), n, (T*)out, (const T*)in, H, W, C, p, hp, wp, order, n, rows)) }
+  if (to_img) { DT_LAUNCH(dtype, L1D((patch_relayout_kernel<T, true>), n, (T*)out, (const T*)in, H, W, C, p, hp, wp, order, n, rows)) }
+  else { DT_LAUNCH(dtype, L1D((patch_relayout_kernel<T, false>), n, (T*)out, (const T*)in, H, W, C, p, hp, wp, order, n, rows)) }
 }
 int hdmoe_patch_relayout(void* out, const void* in, int N, int H, int W, int C, int p, int hp, int wp, int order,
                          int to_img, int dtype, hipStream_t stream) {
@@ -1541,7 +1531,7 @@ int hdmoe_take_col_pos_bwd(float* dw, const float* g, const float* w, long B, in
 int hdmoe_dropout(void* out, const void* x, unsigned long long seed, const unsigned long long* seed_dev, float p, long n, int dtype,
                   hipStream_t stream) {
   if (p < 0.f || p >= 1.f) return HDMOE_EINVAL;
-  DT_SWITCH(dtype, L1D(dropout_kernel<T>, (n + 3) / 4, (T*)out, (const T*)x, (uint32_t)seed, (uint32_t)(seed >> 32), seed_dev, p, n))
+  DT_LAUNCH(dtype, L1D(dropout_kernel<T>, (n + 3) / 4, (T*)out, (const T*)x, (uint32_t)seed, (uint32_t)(seed >> 32), seed_dev, p, n))
 }
 int hdmoe_randn(float* out, unsigned long long seed, const unsigned long long* seed_dev, float scale, long n, hipStream_t stream) {
   L1D(randn_kernel, (n + 3) / 4, out, (uint32_t)seed, (uint32_t)(seed >> 32), seed_dev, scale, n);

@@ -8,13 +8,6 @@
 namespace {
 
 constexpr int TPB = 256;
-#define GRID_STRIDE(i, n) for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
-static inline unsigned grid_for(long n) {
-  long b = (n + TPB - 1) / TPB;
-  if (b > 2048) b = 2048;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
 
 // ---------------------------------------------------------------- pixel norm (one thread per pixel row)
 template <typename T>
@@ -59,10 +52,7 @@ __global__ void pixelnorm_bwd_kernel(T* dx, const T* dxn, const T* dh, const T* 
   }
 }
 
-// ---------------------------------------------------------------- GroupNorm
-DEVI float act_f(float z, int act) { return act == 1 ? fmaxf(z, 0.f) : (act == 2 ? mp_silu_f(z) : z); }
-DEVI float act_grad_f(float z, int act) { return act == 1 ? (z > 0.f ? 1.f : 0.f) : (act == 2 ? mp_silu_grad_f(z) : 1.f); }
-
+// ---------------------------------------------------------------- GroupNorm (the arithmetic: gn_fwd_f / gn_xhat / gn_dz / gn_dx of common.h)
 // per-group block reduction: thread t owns group t % G (requires blockDim % G == 0); result for group g in red[g]
 DEVI void group_reduce(float v, int G, float* part, float* red) {
   __syncthreads();
@@ -102,15 +92,20 @@ __global__ __launch_bounds__(512) void groupnorm_stats_kernel(float* mean, float
     rstd[(long)n * G + threadIdx.x] = rsqrtf(red[threadIdx.x] / (float)(S * Cg) + eps);
   }
 }
-template <typename T>
+// y = act(GroupNorm(x)), W channels of one group per thread: W = 1, or 16-byte vectors where gn_vec_ok
+template <typename T, int W>
 __global__ void groupnorm_apply_kernel(T* y, const T* x, const float* gamma, const float* beta, const float* mean,
-                                       const float* rstd, long S, int C, int G, int act, long n) {
-  const int Cg = C / G;
-  GRID_STRIDE(i, n) {
-    const long row = i / C; const int c = (int)(i - row * C);
-    const long sg = (row / S) * G + c / Cg;
-    const float z = (to_f(x[i]) - mean[sg]) * rstd[sg] * gamma[c] + beta[c];
-    y[i] = from_f<T>(act_f(z, act));
+                                       const float* rstd, long S, int C, int G, int act, long nvec) {
+  const int Cg = C / G, cv = C / W;
+  GRID_STRIDE(v, nvec) {
+    const long row = v / cv; const int c0 = (int)(v - row * cv) * W;
+    const long sg = (row / S) * G + c0 / Cg;
+    const float m = mean[sg], rs = rstd[sg];
+    float f[W];
+    ldw<T, W>(f, x + v * W);
+#pragma unroll
+    for (int j = 0; j < W; ++j) f[j] = gn_fwd_f(f[j], m, rs, gamma[c0 + j], beta[c0 + j], act);
+    stw<T, W>(y + v * W, f);
   }
 }
 // bwd pass 1: per (sample, group) s1 = sum dz*gamma, s2 = sum dz*gamma*xhat ; per-channel dgamma/dbeta (atomics)
@@ -133,8 +128,8 @@ __global__ __launch_bounds__(512) void groupnorm_bwd_stats_kernel(float* s1, flo
     const long off = base + (it / G) * C + g * Cg;
     for (int c = 0; c < Cg; ++c) {
       const int ch = g * Cg + c;
-      const float xh = (to_f(x[off + c]) - m) * rs;
-      const float dz = to_f(dy[off + c]) * act_grad_f(xh * gamma[ch] + beta[ch], act);
+      const float xh = gn_xhat(to_f(x[off + c]), m, rs);
+      const float dz = gn_dz(to_f(dy[off + c]), xh, gamma[ch], beta[ch], act);
       a1 += dz * gamma[ch];
       a2 += dz * gamma[ch] * xh;
       atomicAdd(&sm[ch], dz * xh);
@@ -151,6 +146,9 @@ __global__ __launch_bounds__(512) void groupnorm_bwd_stats_kernel(float* s1, flo
     atomicAdd(&dbeta[c], sm[C + c]);
   }
 }
+// bwd pass 2, one element per thread.  Not the W = 1 form of groupnorm_bwd_apply_vec_kernel: as compiled, this kernel rounds dz * gamma and
+// invm * (s1 + xh * s2) each on its own (one packed multiply) and the vector kernel contracts the difference into an fma, at every width,
+// so one body cannot keep the bits of both
 template <typename T>
 __global__ void groupnorm_bwd_apply_kernel(T* dx, const T* dy, const T* x, const float* gamma, const float* beta, const float* mean,
                                            const float* rstd, const float* s1, const float* s2, long S, int C, int G, int act, long n) {
@@ -160,9 +158,38 @@ __global__ void groupnorm_bwd_apply_kernel(T* dx, const T* dy, const T* x, const
     const long row = i / C; const int c = (int)(i - row * C);
     const long sg = (row / S) * G + c / Cg;
     const float rs = rstd[sg];
-    const float xh = (to_f(x[i]) - mean[sg]) * rs;
-    const float dz = to_f(dy[i]) * act_grad_f(xh * gamma[c] + beta[c], act);
-    dx[i] = from_f<T>(rs * (dz * gamma[c] - invm * (s1[sg] + xh * s2[sg])));
+    const float xh = gn_xhat(to_f(x[i]), mean[sg], rs);
+    dx[i] = from_f<T>(gn_dx(gn_dz(to_f(dy[i]), xh, gamma[c], beta[c], act), xh, rs, gamma[c], invm, s1[sg], s2[sg]));
+  }
+}
+// bwd pass 2, W channels of one group per thread in 16-byte (or, bf16 next to fp32, 8-byte) accesses.  TD: the type of dy and dx where it
+// is not x's (router-trunk backward in bf16 mode: fp32 activations next to bf16 gradients, 4 of each per thread).
+// dyb (or null): the incoming gradient is dyb[n][c] * dybs at every position (the backward of a mean over the positions) -- read from
+// the (N, C) tensor instead of a materialised broadcast
+template <typename T, typename TD = T, int W = VT<T>::W>
+__global__ void groupnorm_bwd_apply_vec_kernel(TD* dx, const TD* dy, const T* x, const float* gamma, const float* beta, const float* mean,
+                                               const float* rstd, const float* s1, const float* s2, long S, int C, int G, int act, long nvec,
+                                               const float* dyb, float dybs) {
+  const int Cg = C / G, cv = C / W;
+  const float invm = 1.f / (float)(S * Cg);
+  GRID_STRIDE(v, nvec) {
+    const long row = v / cv; const int c0 = (int)(v - row * cv) * W;
+    const long sg = (row / S) * G + c0 / Cg;
+    const float m = mean[sg], rs = rstd[sg], u = s1[sg], w = s2[sg];
+    float f[W], d[W];
+    ldw<T, W>(f, x + v * W);
+    if (dyb) {
+#pragma unroll
+      for (int j = 0; j < W; ++j) d[j] = dyb[(row / S) * C + c0 + j] * dybs;
+    } else {
+      ldw<TD, W>(d, dy + v * W);
+    }
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      const float xh = gn_xhat(f[j], m, rs);
+      d[j] = gn_dx(gn_dz(d[j], xh, gamma[c0 + j], beta[c0 + j], act), xh, rs, gamma[c0 + j], invm, u, w);
+    }
+    stw<TD, W>(dx + v * W, d);
   }
 }
 
@@ -389,60 +416,21 @@ DEVI void vec_group_reduce(float v, int cv, int W, int Cg, int G, float* part, f
   __syncthreads();
 }
 
-// ---- GroupNorm, vectorised: one 512-thread block per sample; a thread's vectors all belong to one group and one channel
-// chunk (requires 512 % (C/W) == 0 and (C/G) % W == 0)
+// ---- GroupNorm, vectorised: 512-thread blocks; a thread's vectors all belong to one group and one channel chunk (requires
+// 512 % (C/W) == 0 and (C/G) % W == 0)
+// Two-pass moments of `rows` rows at xs, per group, with a fixed summation order: mean and M2 = sum (x - mean)^2 of the thread's group g;
+// `writer`: the thread that stores its group's result (the first channel chunk of each group)
+struct GnMoments { float mean, m2; int g; bool writer; };
 template <typename T>
-__global__ __launch_bounds__(512) void groupnorm_stats_vec_kernel(float* mean, float* rstd, const T* x, long S, int C, int G, float eps) {
+DEVI GnMoments groupnorm_moments(const T* xs, long rows, int C, int G) {
   constexpr int W = VT<T>::W;
   __shared__ float part[512];
   __shared__ float red[64];
-  const int n = blockIdx.x, Cg = C / G, cv = C / W;
-  const T* xs = x + (long)n * S * C;
-  const long nv = S * cv;
+  const int Cg = C / G, cv = C / W;
+  const long nv = rows * cv;
   const int mych = (threadIdx.x % cv) * W;
   const int g = mych / Cg;
-  // group_reduce expects thread t to own group t % G; remap through a per-thread slot instead: reduce over all threads of group g
-  float acc = 0.f;
-  for (long v = threadIdx.x; v < nv; v += blockDim.x) {
-    float f[W];
-    vload<T>(f, xs + v * W);
-#pragma unroll
-    for (int j = 0; j < W; ++j) acc += f[j];
-  }
-  vec_group_reduce(acc, cv, W, Cg, G, part, red);
-  const float m = red[g] / (float)(S * Cg);
-  acc = 0.f;
-  for (long v = threadIdx.x; v < nv; v += blockDim.x) {
-    float f[W];
-    vload<T>(f, xs + v * W);
-#pragma unroll
-    for (int j = 0; j < W; ++j) { const float d = f[j] - m; acc += d * d; }
-  }
-  const float mkeep = m;
-  vec_group_reduce(acc, cv, W, Cg, G, part, red);
-  if ((int)threadIdx.x % cv == 0 || true) {
-    if ((int)threadIdx.x < cv && (mych % Cg) == 0) {        // first channel chunk of each group writes its statistics
-      mean[(long)n * G + g] = mkeep;
-      rstd[(long)n * G + g] = rsqrtf(red[g] / (float)(S * Cg) + eps);
-    }
-  }
-}
-// Small batches: one 512-thread block per sample leaves most of the chip idle (32 samples = 32 blocks).  Split each sample's
-// rows over `parts` blocks: every block reduces its row range to per-group (mean, M2) with the same two-pass scheme, and a
-// second kernel merges the partials in a fixed order (Chan et al.), so the result stays deterministic.
-template <typename T>
-__global__ __launch_bounds__(512) void groupnorm_part_stats_vec_kernel(float* ws, const T* x, long S, int C, int G, int parts) {
-  constexpr int W = VT<T>::W;
-  __shared__ float part[512];
-  __shared__ float red[64];
-  const int n = blockIdx.x, pi = blockIdx.y, Cg = C / G, cv = C / W;
-  const long rpp = (S + parts - 1) / parts;
-  const long r0 = min((long)pi * rpp, S), r1 = min(r0 + rpp, S);
-  const T* xs = x + ((long)n * S + r0) * C;
-  const long nv = (r1 - r0) * cv;
-  const int mych = (threadIdx.x % cv) * W;
-  const int g = mych / Cg;
-  const float cnt = (float)((r1 - r0) * Cg);
+  const float cnt = (float)(rows * Cg);
   float acc = 0.f;
   for (long v = threadIdx.x; v < nv; v += blockDim.x) {
     float f[W];
@@ -459,11 +447,31 @@ __global__ __launch_bounds__(512) void groupnorm_part_stats_vec_kernel(float* ws
 #pragma unroll
     for (int j = 0; j < W; ++j) { const float d = f[j] - m; acc += d * d; }
   }
-  const float mkeep = m;
   vec_group_reduce(acc, cv, W, Cg, G, part, red);
-  if ((int)threadIdx.x < cv && (mych % Cg) == 0) {
-    float* o = ws + (((long)n * parts + pi) * G + g) * 2;
-    o[0] = mkeep; o[1] = red[g];
+  return {m, red[g], g, (int)threadIdx.x < cv && (mych % Cg) == 0};
+}
+// one block per sample
+template <typename T>
+__global__ __launch_bounds__(512) void groupnorm_stats_vec_kernel(float* mean, float* rstd, const T* x, long S, int C, int G, float eps) {
+  const int n = blockIdx.x;
+  const GnMoments r = groupnorm_moments<T>(x + (long)n * S * C, S, C, G);
+  if (r.writer) {
+    mean[(long)n * G + r.g] = r.mean;
+    rstd[(long)n * G + r.g] = rsqrtf(r.m2 / (float)(S * (C / G)) + eps);
+  }
+}
+// Small batches: one 512-thread block per sample leaves most of the chip idle (32 samples = 32 blocks).  Split each sample's
+// rows over `parts` blocks: every block reduces its row range to per-group (mean, M2) with the same two-pass scheme, and a
+// second kernel merges the partials in a fixed order (Chan et al.), so the result stays deterministic.
+template <typename T>
+__global__ __launch_bounds__(512) void groupnorm_part_stats_vec_kernel(float* ws, const T* x, long S, int C, int G, int parts) {
+  const int n = blockIdx.x, pi = blockIdx.y;
+  const long rpp = (S + parts - 1) / parts;
+  const long r0 = min((long)pi * rpp, S), r1 = min(r0 + rpp, S);
+  const GnMoments r = groupnorm_moments<T>(x + ((long)n * S + r0) * C, r1 - r0, C, G);
+  if (r.writer) {
+    float* o = ws + (((long)n * parts + pi) * G + r.g) * 2;
+    o[0] = r.mean; o[1] = r.m2;
   }
 }
 __global__ void groupnorm_merge_kernel(float* mean, float* rstd, const float* ws, long S, int C, int G, int parts, float eps, long NG) {
@@ -487,46 +495,7 @@ __global__ void groupnorm_merge_kernel(float* mean, float* rstd, const float* ws
   rstd[i] = rsqrtf(M2 / cnt + eps);
 }
 
-template <typename T>
-__global__ void groupnorm_apply_vec_kernel(T* y, const T* x, const float* gamma, const float* beta, const float* mean,
-                                           const float* rstd, long S, int C, int G, int act, long nvec) {
-  constexpr int W = VT<T>::W;
-  const int Cg = C / G, cv = C / W;
-  GRID_STRIDE(v, nvec) {
-    const long row = v / cv; const int c0 = (int)(v - row * cv) * W;
-    const long sg = (row / S) * G + c0 / Cg;
-    const float m = mean[sg], rs = rstd[sg];
-    float f[W];
-    vload<T>(f, x + v * W);
-#pragma unroll
-    for (int j = 0; j < W; ++j) f[j] = act_f((f[j] - m) * rs * gamma[c0 + j] + beta[c0 + j], act);
-    vstore<T>(y + v * W, f);
-  }
-}
-// W-element vector access for a tensor whose element type differs from the one that sets the vector width (router-trunk backward in bf16
-// mode: fp32 activations, 4 per thread, next to bf16 gradients, 4 per thread = 8 bytes)
-template <typename TD, int W> struct VecW;
-template <> struct VecW<float, 4> {
-  static DEVI void load(float* f, const float* p) { vload<float>(f, p); }
-  static DEVI void store(float* p, const float* f) { vstore<float>(p, f); }
-};
-template <> struct VecW<bf16, 8> {
-  static DEVI void load(float* f, const bf16* p) { vload<bf16>(f, p); }
-  static DEVI void store(bf16* p, const float* f) { vstore<bf16>(p, f); }
-};
-template <> struct VecW<bf16, 4> {
-  static DEVI void load(float* f, const bf16* p) {
-    const bf16x4 v = *reinterpret_cast<const bf16x4*>(p);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) f[j] = (float)v[j];
-  }
-  static DEVI void store(bf16* p, const float* f) {
-    bf16x4 v;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = (bf16)f[j];
-    *reinterpret_cast<bf16x4*>(p) = v;
-  }
-};
+// (TD, WV: as in groupnorm_bwd_apply_vec_kernel)
 template <typename T, typename TD = T, int WV = VT<T>::W>
 __global__ __launch_bounds__(512) void groupnorm_bwd_stats_vec_kernel(float* s1, float* s2, float* dgamma, float* dbeta, const TD* dy,
                                                                      const T* x, const float* gamma, const float* beta, const float* mean,
@@ -554,17 +523,17 @@ __global__ __launch_bounds__(512) void groupnorm_bwd_stats_vec_kernel(float* s1,
   for (int j = 0; j < W; ++j) gb[j] = dyb ? dyb[(long)n * C + mych + j] * dybs : 0.f;
   for (long v = threadIdx.x; v < nv; v += blockDim.x) {
     float f[W], d[W];
-    VecW<T, W>::load(f, x + base + v * W);
+    ldw<T, W>(f, x + base + v * W);
     if (dyb) {
 #pragma unroll
       for (int j = 0; j < W; ++j) d[j] = gb[j];
     } else {
-      VecW<TD, W>::load(d, dy + base + v * W);
+      ldw<TD, W>(d, dy + base + v * W);
     }
 #pragma unroll
     for (int j = 0; j < W; ++j) {
-      const float xh = (f[j] - m) * rs;
-      const float dz = d[j] * act_grad_f(xh * gm[j] + bt[j], act);
+      const float xh = gn_xhat(f[j], m, rs);
+      const float dz = gn_dz(d[j], xh, gm[j], bt[j], act);
       a1 += dz * gm[j]; a2 += dz * gm[j] * xh;
       dg[j] += dz * xh; db[j] += dz;
     }
@@ -587,35 +556,9 @@ __global__ __launch_bounds__(512) void groupnorm_bwd_stats_vec_kernel(float* s1,
     if ((int)threadIdx.x < cv) { atomicAdd(&dgamma[threadIdx.x * W + j], part[threadIdx.x]); atomicAdd(&dbeta[threadIdx.x * W + j], part2[threadIdx.x]); }
   }
 }
-template <typename T, typename TD = T, int WV = VT<T>::W>
-__global__ void groupnorm_bwd_apply_vec_kernel(TD* dx, const TD* dy, const T* x, const float* gamma, const float* beta, const float* mean,
-                                               const float* rstd, const float* s1, const float* s2, long S, int C, int G, int act, long nvec,
-                                               const float* dyb, float dybs) {
-  constexpr int W = WV;
-  const int Cg = C / G, cv = C / W;
-  const float invm = 1.f / (float)(S * Cg);
-  GRID_STRIDE(v, nvec) {
-    const long row = v / cv; const int c0 = (int)(v - row * cv) * W;
-    const long sg = (row / S) * G + c0 / Cg;
-    const float m = mean[sg], rs = rstd[sg], u = s1[sg], w = s2[sg];
-    float f[W], d[W];
-    VecW<T, W>::load(f, x + v * W);
-    if (dyb) {
-#pragma unroll
-      for (int j = 0; j < W; ++j) d[j] = dyb[(row / S) * C + c0 + j] * dybs;
-    } else {
-      VecW<TD, W>::load(d, dy + v * W);
-    }
-#pragma unroll
-    for (int j = 0; j < W; ++j) {
-      const float xh = (f[j] - m) * rs;
-      const float dz = d[j] * act_grad_f(xh * gamma[c0 + j] + beta[c0 + j], act);
-      d[j] = rs * (dz * gamma[c0 + j] - invm * (u + xh * w));
-    }
-    VecW<TD, W>::store(dx + v * W, d);
-  }
-}
 
+// eight consecutive fp32 as two 16-byte loads (the router-trunk kernels: 8 channels per thread, next to one 16-byte bf16 access)
+DEVI void ld8(float* f, const float* p) { vload<float>(f, p); vload<float>(f + 4, p + 4); }
 // a = relu(y * scale[n][c] + shift[n][c]) as bf16 (scale == null: a plain fp32 -> bf16 conversion): the input of a router-trunk conv as the
 // bf16 weight-gradient program reads it (the forward never materialises it: conv6s applies the same transform while it stages its tiles)
 __global__ void gn1t_act_kernel(bf16* out, const float* y, const float* scale, const float* shift, long S, int C, long nvec) {
@@ -623,7 +566,7 @@ __global__ void gn1t_act_kernel(bf16* out, const float* y, const float* scale, c
   GRID_STRIDE(v, nvec) {
     const long row = v / cv; const int c0 = (int)(v - row * cv) * 8;
     float f[8];
-    vload<float>(f, y + v * 8); vload<float>(f + 4, y + v * 8 + 4);
+    ld8(f, y + v * 8);
     if (scale) {
       const long sc = (row / S) * C + c0;
 #pragma unroll
@@ -651,15 +594,23 @@ template <typename T> static inline int lpr_for(int C) {
   }
 template <typename T> static inline bool row_vec_ok(int C, const void* a, const void* b, const void* c, const void* d) {
   const int W = VT<T>::W;
-  auto al = [](const void* p) { return p == nullptr || (uintptr_t)p % 16 == 0; };
-  return C % W == 0 && C / W <= 64 && al(a) && al(b) && al(c) && al(d);
+  return C % W == 0 && C / W <= 64 && al16(a) && al16(b) && al16(c) && al16(d);
 }
-static inline unsigned rows_grid(long rows, int lpr) {
+static inline unsigned rows_grid(long rows, int lpr, long cap) {
   long b = (rows * lpr + 255) / 256;
-  if (b > 4096) b = 4096;
+  if (b > cap) b = cap;
   if (b < 1) b = 1;
   return (unsigned)b;
 }
+// The arm of a row-norm entry point (dtype, C, rows, stream in scope; both kernels take the same arguments): VEC<T, LPR>, LPR lanes and
+// 16-byte accesses per row, where the row length and the pointers a..d allow it, else SCALAR<T>, a thread per row.  At most vcap / scap
+// workgroups; `lds` bytes of dynamic LDS
+#define ROW_NORM_LAUNCH(VEC, SCALAR, vcap, scap, lds, a, b, c, d, ...)                                                                   \
+  DT_SWITCH(dtype, if (row_vec_ok<T>(C, a, b, c, d)) {                                                                                   \
+    const int lpr = lpr_for<T>(C);                                                                                                       \
+    LPR_SWITCH(lpr, hipLaunchKernelGGL((VEC<T, L>), dim3(rows_grid(rows, lpr, vcap)), dim3(256), lds, stream, __VA_ARGS__))              \
+  } else hipLaunchKernelGGL(SCALAR<T>, dim3(grid_for(rows, scap)), dim3(TPB), lds, stream, __VA_ARGS__))                                 \
+  return hdmoe_launch_status();
 // ---- GroupNorm(1, C) backward on SINGLE-POSITION rows (S == 1: the norms of the conditioning MLPs, (N, 512 or 1024) fp32).  The image
 // kernels above run it as a statistics launch with one 512-thread workgroup per row -- two block reductions and 2 C global atomics per
 // row, 39 us for 1 MB -- and an apply launch.  Here a wave owns a row: it holds the row in registers (NJ = ceil(C / 256) float4 pieces
@@ -699,8 +650,8 @@ __global__ __launch_bounds__(256) void groupnorm_rows_bwd_kernel(float* dx, floa
       const f32x4 d = ok[j] ? *reinterpret_cast<const f32x4*>(dy + at) : (f32x4)(0.f);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        xh[j][e] = (f[e] - m) * rs;
-        dz[j][e] = ok[j] ? d[e] * act_grad_f(xh[j][e] * gm[j][e] + bt[j][e], act) : 0.f;
+        xh[j][e] = gn_xhat(f[e], m, rs);
+        dz[j][e] = ok[j] ? gn_dz(d[e], xh[j][e], gm[j][e], bt[j][e], act) : 0.f;
         a1 += dz[j][e] * gm[j][e]; a2 += dz[j][e] * gm[j][e] * xh[j][e];
         dg[j][e] += dz[j][e] * xh[j][e]; db[j][e] += dz[j][e];
       }
@@ -711,7 +662,7 @@ __global__ __launch_bounds__(256) void groupnorm_rows_bwd_kernel(float* dx, floa
       if (!ok[j]) continue;
       f32x4 o;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = rs * (dz[j][e] * gm[j][e] - invm * (a1 + xh[j][e] * a2));
+      for (int e = 0; e < 4; ++e) o[e] = gn_dx(dz[j][e], xh[j][e], rs, gm[j][e], invm, a1, a2);
       *reinterpret_cast<f32x4*>(dx + (long)n * C + 4 * (lane + 64 * j)) = o;
     }
   }
@@ -729,31 +680,22 @@ __global__ __launch_bounds__(256) void groupnorm_rows_bwd_kernel(float* dx, floa
 
 template <typename T> static inline bool gn_vec_ok(int C, int G, const void* a, const void* b, const void* c) {
   const int W = VT<T>::W;
-  auto al = [](const void* p) { return p == nullptr || (uintptr_t)p % 16 == 0; };
   if (C % W || (C / G) % W) return false;
   const int cv = C / W;
-  return cv <= 512 && 512 % cv == 0 && al(a) && al(b) && al(c);
+  return cv <= 512 && 512 % cv == 0 && al16(a) && al16(b) && al16(c);
 }
-
-}  // namespace
-
-#define DT_SWITCH(dtype, CALL)                    \
-  if ((dtype) == HDMOE_F32) { using T = float; CALL; }   \
-  else if ((dtype) == HDMOE_BF16) { using T = bf16; CALL; } \
-  else return HDMOE_EDTYPE;
 
 // ---------------------------------------------------------------- GroupNorm(1, C) fused into the neighbouring convs (router trunks)
 // Router.hard_route is conv -> GroupNorm(1, C) -> ReLU three times, then AdaptiveAvgPool2d(1) (reference model_components.py:100-112).
 // The split-bf16 conv kernel leaves per-sample partial (sum, sum of squares) slots of its OUTPUT (conv6s_body.h); this kernel turns
 // them into mean / rstd and the per-(sample, channel) affine  scale = gamma * rstd, shift = beta - mean * rstd * gamma  that the NEXT
 // conv (and its weight gradient) apply to the tensor while staging it: the normalised activation is never written.
-namespace {
-__global__ void gn1_finalize_kernel(float* scale, float* shift, float* mean, float* rstd, const float* ws, const float* gamma, const float* beta,
-                                    int slots, int C, float inv_count, float eps) {
-  __shared__ float sm[2];
-  const int n = blockIdx.x;
-  // wave 0: lane l takes slots l, l + 64, .. (independent loads), then a fixed-shape shuffle tree -- the order depends on `slots` only,
-  // never on the batch; fp64 for the few dozen partials (the cancellation in E[y^2] - mean^2)
+// The statistics of sample n from its slots, by every thread of the workgroup (`threads` of them): sm[0] = mean, sm[1] = rstd, also stored
+// to mean[n] / rstd[n], then scale / shift [n][C]; sm is valid for all threads on return.
+// wave 0: lane l takes slots l, l + 64, .. (independent loads), then a fixed-shape shuffle tree -- the order depends on `slots` only,
+// never on the batch; fp64 for the few dozen partials (the cancellation in E[y^2] - mean^2)
+DEVI void gn1_slot_stats(float* sm, float* scale, float* shift, float* mean, float* rstd, const float* ws, const float* gamma, const float* beta,
+                         int n, int slots, int C, float inv_count, float eps, int threads) {
   double s1 = 0.0, s2 = 0.0;
   if (threadIdx.x < 64) {
     for (int k = threadIdx.x; k < slots; k += 64) {
@@ -771,11 +713,16 @@ __global__ void gn1_finalize_kernel(float* scale, float* shift, float* mean, flo
     mean[n] = sm[0]; rstd[n] = sm[1];
   }
   __syncthreads();
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+  for (int c = threadIdx.x; c < C; c += threads) {
     const float g = gamma[c] * sm[1];
     scale[(long)n * C + c] = g;
     shift[(long)n * C + c] = beta[c] - sm[0] * g;
   }
+}
+__global__ void gn1_finalize_kernel(float* scale, float* shift, float* mean, float* rstd, const float* ws, const float* gamma, const float* beta,
+                                    int slots, int C, float inv_count, float eps) {
+  __shared__ float sm[2];
+  gn1_slot_stats(sm, scale, shift, mean, rstd, ws, gamma, beta, blockIdx.x, slots, C, inv_count, eps, blockDim.x);
 }
 // out[n][c] = mean over the S positions of relu(y[n][s][c] * scale[n][c] + shift[n][c]): the last GroupNorm + ReLU + average pool of the
 // trunk in one read of y (fixed summation order)
@@ -795,30 +742,7 @@ __global__ __launch_bounds__(GN1_POOL_THREADS) void gn1_relu_mean_kernel(float* 
   const int n = blockIdx.x, C4 = C / 4, rows = GN1_POOL_THREADS / C4;
   const int cq = threadIdx.x % C4, rw = threadIdx.x / C4;
   typedef __attribute__((ext_vector_type(4))) float f4;
-  if (ws) {                                                    // same arithmetic and order as gn1_finalize_kernel
-    double s1 = 0.0, s2 = 0.0;
-    if (threadIdx.x < 64) {
-      for (int k = threadIdx.x; k < slots; k += 64) {
-        const float2 v = *reinterpret_cast<const float2*>(ws + ((long)n * slots + k) * 2);
-        s1 += v.x; s2 += v.y;
-      }
-#pragma unroll
-      for (int d = 32; d >= 1; d >>= 1) { s1 += __shfl_down(s1, d, 64); s2 += __shfl_down(s2, d, 64); }
-    }
-    if (threadIdx.x == 0) {
-      const double m = s1 * inv_count;
-      double var = s2 * inv_count - m * m;
-      if (var < 0.0) var = 0.0;
-      smr[0] = (float)m; smr[1] = (float)(1.0 / sqrt(var + (double)eps));
-      mean[n] = smr[0]; rstd[n] = smr[1];
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += GN1_POOL_THREADS) {
-      const float g = gamma[c] * smr[1];
-      scale[(long)n * C + c] = g;
-      shift[(long)n * C + c] = beta[c] - smr[0] * g;
-    }
-  }
+  if (ws) gn1_slot_stats(smr, scale, shift, mean, rstd, ws, gamma, beta, n, slots, C, inv_count, eps, GN1_POOL_THREADS);
   f4 acc = (f4)(0.f), pc = (f4)(0.f), qc = (f4)(0.f);
   if (rw < rows) {
     f4 sc, sh, gm, bt;
@@ -838,8 +762,8 @@ __global__ __launch_bounds__(GN1_POOL_THREADS) void gn1_relu_mean_kernel(float* 
     auto pq = [&](const f4& v) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float xh = (v[e] - m) * rs;
-        const bool open = act_grad_f(xh * gm[e] + bt[e], 1) > 0.f;
+        const float xh = gn_xhat(v[e], m, rs);
+        const bool open = gn_dz(1.f, xh, gm[e], bt[e], 1) > 0.f;
         pc[e] += open ? 1.f : 0.f;
         qc[e] += open ? xh : 0.f;
       }
@@ -891,10 +815,19 @@ __global__ __launch_bounds__(GN1_POOL_THREADS) void gn1_relu_mean_kernel(float* 
 // gn1t_apply_kernel, which writes both bf16 operands of the conv's backward.  Every sum runs in an order fixed by S and C alone -- never by
 // the other samples of the batch -- and none uses a float atomic.  8 channels per thread: 16-byte accesses to every tensor.
 constexpr int GN1T_THREADS = 256;
-DEVI float wave_sum(float v) {                                 // fixed-shape shuffle tree; the total lands in lane 0
+// fixed-shape shuffle tree; the total lands in lane 0 ONLY (common.h's wave_sum leaves it in every lane)
+DEVI float wave_sum0(float v) {
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
   return v;
+}
+// One thread's rows r, r + R, r + 2 R, .. < r1: body(Rows<2>, r) takes the rows r and r + R together, so that the loads of both (up to six
+// 16-byte accesses) are in flight at once, and body(Rows<1>, r) an odd last row
+template <int K> struct Rows { static constexpr int n = K; };
+template <typename F>
+DEVI void gn1t_rows(long r, long r1, int R, F body) {
+  for (; r + R < r1; r += 2 * R) body(Rows<2>{}, r);
+  if (r < r1) body(Rows<1>{}, r);
 }
 // grid (N, parts): block (n, p) takes the rows [p * rpp, (p + 1) * rpp) of sample n; thread t the channels 8 (t % cv) .. + 7 of the rows
 // t / cv + k * R (R = 256 / cv; threads past R * cv idle).  Writes ws[n][p][2] = the (s1, s2) partials, s1 = sum dz' gamma, s2 = sum dz' gamma xh,
@@ -912,34 +845,29 @@ __global__ __launch_bounds__(GN1T_THREADS) void gn1t_stats_kernel(float* ws, flo
 #pragma unroll
   for (int j = 0; j < 8; ++j) { gm[j] = gamma[c0 + j]; bt[j] = beta[c0 + j]; dg[j] = 0.f; db[j] = 0.f; }
   float a1 = 0.f, a2 = 0.f;
-  auto acc = [&](const float* f, const float* d) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float xh = (f[j] - m) * rs;
-      const float dzz = d[j] * act_grad_f(xh * gm[j] + bt[j], 1);
-      a1 += dzz * gm[j]; a2 += dzz * gm[j] * xh;
-      dg[j] += dzz * xh; db[j] += dzz;
-    }
-  };
   if (rt < R) {
     const float* xp = x + (long)n * S * C + c0;
     const bf16* dp = dz + (long)n * S * C + c0;
-    long r = r0 + rt;
-    for (; r + R < r1; r += 2 * R) {                            // two rows' loads (six 16-byte accesses) in flight per thread
-      float f0[8], f1[8], d0[8], d1[8];
-      vload<float>(f0, xp + r * C); vload<float>(f0 + 4, xp + r * C + 4); vload<bf16>(d0, dp + r * C);
-      vload<float>(f1, xp + (r + R) * C); vload<float>(f1 + 4, xp + (r + R) * C + 4); vload<bf16>(d1, dp + (r + R) * C);
-      acc(f0, d0); acc(f1, d1);
-    }
-    if (r < r1) {
-      float f0[8], d0[8];
-      vload<float>(f0, xp + r * C); vload<float>(f0 + 4, xp + r * C + 4); vload<bf16>(d0, dp + r * C);
-      acc(f0, d0);
-    }
+    gn1t_rows(r0 + rt, r1, R, [&](auto rows, long r) {
+      constexpr int K = decltype(rows)::n;
+      float f[K][8], d[K][8];
+#pragma unroll
+      for (int k = 0; k < K; ++k) { ld8(f[k], xp + (r + k * R) * C); vload<bf16>(d[k], dp + (r + k * R) * C); }
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float xh = gn_xhat(f[k][j], m, rs);
+          const float dzz = gn_dz(d[k][j], xh, gm[j], bt[j], 1);
+          a1 += dzz * gm[j]; a2 += dzz * gm[j] * xh;
+          dg[j] += dzz * xh; db[j] += dzz;
+        }
+      }
+    });
 #pragma unroll
     for (int j = 0; j < 8; ++j) { lds[0][rt * C + c0 + j] = dg[j]; lds[1][rt * C + c0 + j] = db[j]; }
   }
-  a1 = wave_sum(a1); a2 = wave_sum(a2);
+  a1 = wave_sum0(a1); a2 = wave_sum0(a2);
   const int wv = threadIdx.x / 64;
   if (threadIdx.x % 64 == 0) { red[0][wv] = a1; red[1][wv] = a2; }
   __syncthreads();
@@ -984,7 +912,7 @@ __global__ __launch_bounds__(GN1T_THREADS) void gn1t_apply_kernel(bf16* dx, bf16
 #pragma unroll 4
       for (long i = lane; i < NP; i += 64) { sg += pg[i]; sb += pb[i]; }
     }
-    sg = wave_sum(sg); sb = wave_sum(sb);
+    sg = wave_sum0(sg); sb = wave_sum0(sb);
     if (lane == 0) { dgamma[c] += sg; dbeta[c] += sb; }
     return;
   }
@@ -997,7 +925,7 @@ __global__ __launch_bounds__(GN1T_THREADS) void gn1t_apply_kernel(bf16* dx, bf16
       const float gg = g[(long)n * C + c] * gscale * gamma[c];
       u += gg * pcnt[(long)n * C + c]; w += gg * qsum[(long)n * C + c];
     }
-    u = wave_sum(u); w = wave_sum(w);
+    u = wave_sum0(u); w = wave_sum0(w);
     if (lane == 0) { red[0][wv] = u; red[1][wv] = w; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1024,20 +952,20 @@ __global__ __launch_bounds__(GN1T_THREADS) void gn1t_apply_kernel(bf16* dx, bf16
     auto out = [&](float* f, const float* d) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const float xh = (f[j] - m) * rs;
-        const float dzz = d[j] * act_grad_f(xh * gm[j] + bt[j], 1);
-        f[j] = rs * (dzz * gm[j] - invm * (u + xh * w));
+        const float xh = gn_xhat(f[j], m, rs);
+        f[j] = gn_dx(gn_dz(d[j], xh, gm[j], bt[j], 1), xh, rs, gm[j], invm, u, w);
       }
     };
     if (rt < R) {
       const float* xp = x + (long)n * S * C + c0;
       const bf16* dp = dz ? dz + (long)n * S * C + c0 : nullptr;
       bf16* op = dx + (long)n * S * C + c0;
+      // gn1t_rows written out: this kernel sits at 96 VGPRs, the most that 5 waves per SIMD allow, and every form of this loop over the
+      // helper (the branch on dp inside a row's lambda) took 98 to 116
       long r = r0 + rt;
       for (; r + R < r1; r += 2 * R) {
         float f0[8], f1[8], d0[8], d1[8];
-        vload<float>(f0, xp + r * C); vload<float>(f0 + 4, xp + r * C + 4);
-        vload<float>(f1, xp + (r + R) * C); vload<float>(f1 + 4, xp + (r + R) * C + 4);
+        ld8(f0, xp + r * C); ld8(f1, xp + (r + R) * C);
         if (dp) { vload<bf16>(d0, dp + r * C); vload<bf16>(d1, dp + (r + R) * C); }
         else {
 #pragma unroll
@@ -1048,7 +976,7 @@ __global__ __launch_bounds__(GN1T_THREADS) void gn1t_apply_kernel(bf16* dx, bf16
       }
       if (r < r1) {
         float f0[8], d0[8];
-        vload<float>(f0, xp + r * C); vload<float>(f0 + 4, xp + r * C + 4);
+        ld8(f0, xp + r * C);
         if (dp) vload<bf16>(d0, dp + r * C);
         else {
 #pragma unroll
@@ -1067,29 +995,24 @@ __global__ __launch_bounds__(GN1T_THREADS) void gn1t_apply_kernel(bf16* dx, bf16
 #pragma unroll
       for (int j = 0; j < 8; ++j) { sc[j] = scale[(long)n * CI + c0 + j]; sh[j] = shift[(long)n * CI + c0 + j]; }
     }
-    auto act = [&](float* f) {
-      if (scale) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = fmaxf(f[j] * sc[j] + sh[j], 0.f);
-      }
-    };
     if (rt < R) {
       const float* ip = xin + (long)n * S * CI + c0;
       bf16* op = a + (long)n * S * CI + c0;
-      long r = r0 + rt;
-      for (; r + R < r1; r += 2 * R) {
-        float f0[8], f1[8];
-        vload<float>(f0, ip + r * CI); vload<float>(f0 + 4, ip + r * CI + 4);
-        vload<float>(f1, ip + (r + R) * CI); vload<float>(f1 + 4, ip + (r + R) * CI + 4);
-        act(f0); act(f1);
-        vstore<bf16>(op + r * CI, f0); vstore<bf16>(op + (r + R) * CI, f1);
-      }
-      if (r < r1) {
-        float f0[8];
-        vload<float>(f0, ip + r * CI); vload<float>(f0 + 4, ip + r * CI + 4);
-        act(f0);
-        vstore<bf16>(op + r * CI, f0);
-      }
+      gn1t_rows(r0 + rt, r1, R, [&](auto rows, long r) {
+        constexpr int K = decltype(rows)::n;
+        float f[K][8];
+#pragma unroll
+        for (int k = 0; k < K; ++k) ld8(f[k], ip + (r + k * R) * CI);
+        if (scale) {
+#pragma unroll
+          for (int k = 0; k < K; ++k) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f[k][j] = fmaxf(f[k][j] * sc[j] + sh[j], 0.f);
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) vstore<bf16>(op + (r + k * R) * CI, f[k]);
+      });
     }
   }
 }
@@ -1099,23 +1022,12 @@ static inline int gn1t_parts(long S) { const long p = S / 128; return (int)(p < 
 extern "C" {
 
 int hdmoe_pixelnorm_fwd(void* xn, void* h, const void* x, long rows, int C, int dtype, hipStream_t stream) {
-  DT_SWITCH(dtype, if (row_vec_ok<T>(C, xn, h, x, nullptr)) {
-    const int lpr = lpr_for<T>(C);
-    LPR_SWITCH(lpr, hipLaunchKernelGGL((pixelnorm_fwd_vec_kernel<T, L>), dim3(rows_grid(rows, lpr)), dim3(256), 0, stream, (T*)xn, (T*)h, (const T*)x, C, rows))
-    return hdmoe_launch_status();
-  })
-  DT_SWITCH(dtype, hipLaunchKernelGGL(pixelnorm_fwd_kernel<T>, dim3(grid_for(rows)), dim3(TPB), 0, stream, (T*)xn, (T*)h, (const T*)x, C, rows))
-  return hdmoe_launch_status();
+  ROW_NORM_LAUNCH(pixelnorm_fwd_vec_kernel, pixelnorm_fwd_kernel, 4096, 2048, 0, xn, h, x, nullptr, (T*)xn, (T*)h, (const T*)x, C, rows)
 }
 int hdmoe_pixelnorm_bwd(void* dx, const void* dxn, const void* dh, const void* x, long rows, int C, float sx, int dtype, hipStream_t stream) {
   if (!dxn && !dh) return HDMOE_EINVAL;
-  DT_SWITCH(dtype, if (row_vec_ok<T>(C, dx, dxn, dh, x)) {
-    const int lpr = lpr_for<T>(C);
-    LPR_SWITCH(lpr, hipLaunchKernelGGL((pixelnorm_bwd_vec_kernel<T, L>), dim3(rows_grid(rows, lpr)), dim3(256), 0, stream, (T*)dx, (const T*)dxn, (const T*)dh, (const T*)x, C, rows, sx))
-    return hdmoe_launch_status();
-  })
-  DT_SWITCH(dtype, hipLaunchKernelGGL(pixelnorm_bwd_kernel<T>, dim3(grid_for(rows)), dim3(TPB), 0, stream, (T*)dx, (const T*)dxn, (const T*)dh, (const T*)x, C, rows, sx))
-  return hdmoe_launch_status();
+  ROW_NORM_LAUNCH(pixelnorm_bwd_vec_kernel, pixelnorm_bwd_kernel, 4096, 2048, 0, dx, dxn, dh, x, (T*)dx, (const T*)dxn, (const T*)dh, (const T*)x, C,
+                  rows, sx)
 }
 static int gn_check(int N, int C, int G) {
   if (N < 1 || G < 1 || G > 64 || (G & (G - 1)) || C % G || C > 4096) return HDMOE_EINVAL;   // G must divide 512 (thread<->group map)
@@ -1133,12 +1045,12 @@ static int groupnorm_fwd_impl(void* y, float* mean, float* rstd, float* ws, int 
     } else {
       hipLaunchKernelGGL(groupnorm_stats_vec_kernel<T>, dim3(N), dim3(512), 0, stream, mean, rstd, (const T*)x, S, C, G, eps);
     }
-    hipLaunchKernelGGL(groupnorm_apply_vec_kernel<T>, dim3(grid_for(nvec)), dim3(TPB), 0, stream, (T*)y, (const T*)x, gamma, beta, mean, rstd, S, C, G, act, nvec);
+    hipLaunchKernelGGL((groupnorm_apply_kernel<T, VT<T>::W>), dim3(grid_for(nvec)), dim3(TPB), 0, stream, (T*)y, (const T*)x, gamma, beta, mean, rstd, S, C, G, act, nvec);
     return hdmoe_launch_status();
   })
   DT_SWITCH(dtype, {
     hipLaunchKernelGGL(groupnorm_stats_kernel<T>, dim3(N), dim3(512), 0, stream, mean, rstd, (const T*)x, S, C, G, eps);
-    hipLaunchKernelGGL(groupnorm_apply_kernel<T>, dim3(grid_for(n)), dim3(TPB), 0, stream, (T*)y, (const T*)x, gamma, beta, mean, rstd, S, C, G, act, n);
+    hipLaunchKernelGGL((groupnorm_apply_kernel<T, 1>), dim3(grid_for(n)), dim3(TPB), 0, stream, (T*)y, (const T*)x, gamma, beta, mean, rstd, S, C, G, act, n);
   })
   return hdmoe_launch_status();
 }
@@ -1173,9 +1085,8 @@ static int groupnorm_bwd_impl(void* dx, float* dgamma, float* dbeta, float* ws, 
     // 512, not 2048 blocks: this pass belongs to the router trunks' backward, which has slack, and a chip-filling grid of it holds up the
     // expert branch's kernels on the critical stream (same-box A/B 2048 -> 512: 15.52 -> 15.40 ms/step; the reverse experiment, four
     // row-range blocks per sample in the statistics pass, cost +0.4 ms)
-    unsigned gb = grid_for(nvec); if (gb > 512) gb = 512;
-    hipLaunchKernelGGL(groupnorm_bwd_apply_vec_kernel<T>, dim3(gb), dim3(TPB), 0, stream, (T*)dx, (const T*)dy, (const T*)x,
-                       gamma, beta, mean, rstd, s1, s2, S, C, G, act, nvec, dyb, dybs);
+    hipLaunchKernelGGL(groupnorm_bwd_apply_vec_kernel<T>, dim3(grid_for(nvec, 512)), dim3(TPB), 0, stream, (T*)dx, (const T*)dy,
+                       (const T*)x, gamma, beta, mean, rstd, s1, s2, S, C, G, act, nvec, dyb, dybs);
     return hdmoe_launch_status();
   })
   if (dyb) return HDMOE_EINVAL;                               // the broadcast form exists for the vector kernels only
@@ -1217,10 +1128,9 @@ int hdmoe_gn1t_bwd(void* dx, float* dgamma, float* dbeta, float* ws, const void*
   if (C % 4 || C / 4 > 512 || 512 % (C / 4) || ((uintptr_t)x & 15) || ((uintptr_t)dx & 15) || ((uintptr_t)dz & 15)) return HDMOE_EINVAL;
   const long nvec = (long)N * S * C / 4;
   float* s1 = ws; float* s2 = ws + N;
-  unsigned gb = grid_for(nvec); if (gb > 512) gb = 512;      // (as in groupnorm_bwd_impl)
   hipLaunchKernelGGL((groupnorm_bwd_stats_vec_kernel<float, bf16, 4>), dim3(N, 1), dim3(512), 0, stream, s1, s2, dgamma, dbeta, (const bf16*)dz, x, gamma, beta,
                      mean, rstd, S, C, 1, 1, 1, dz ? nullptr : g, gscale);
-  hipLaunchKernelGGL((groupnorm_bwd_apply_vec_kernel<float, bf16, 4>), dim3(gb), dim3(TPB), 0, stream, (bf16*)dx, (const bf16*)dz, x, gamma, beta, mean, rstd,
+  hipLaunchKernelGGL((groupnorm_bwd_apply_vec_kernel<float, bf16, 4>), dim3(grid_for(nvec, 512)), dim3(TPB), 0, stream, (bf16*)dx, (const bf16*)dz, x, gamma, beta, mean, rstd,
                      s1, s2, S, C, 1, 1, nvec, dz ? nullptr : g, gscale);
   return hdmoe_launch_status();
 }
@@ -1228,8 +1138,7 @@ int hdmoe_gn1t_bwd(void* dx, float* dgamma, float* dbeta, float* ws, const void*
 int hdmoe_gn1t_act(void* out, const float* y, const float* scale, const float* shift, int N, long S, int C, hipStream_t stream) {
   if (!out || !y || (scale == nullptr) != (shift == nullptr) || N < 1 || S < 1 || C % 8 || !al16(out) || !al16(y)) return HDMOE_EINVAL;
   const long nvec = (long)N * S * C / 8;
-  unsigned gb = grid_for(nvec); if (gb > 1024) gb = 1024;
-  hipLaunchKernelGGL(gn1t_act_kernel, dim3(gb), dim3(TPB), 0, stream, (bf16*)out, y, scale, shift, S, C, nvec);
+  hipLaunchKernelGGL(gn1t_act_kernel, dim3(grid_for(nvec, 1024)), dim3(TPB), 0, stream, (bf16*)out, y, scale, shift, S, C, nvec);
   return hdmoe_launch_status();
 }
 /* Floats of the statistics workspace of hdmoe_gn1t_stats: 2 N parts (s1 / s2 slots) + 2 C N parts (per-channel slots); parts a function of S. */
@@ -1271,31 +1180,15 @@ int hdmoe_gn1t_apply(void* dx, void* a, float* dgamma, float* dbeta, const float
 }
 int hdmoe_layernorm_fwd(void* y, float* mean, float* rstd, const void* x, const float* gamma, const float* beta, long rows,
                         int C, float eps, int dtype, hipStream_t stream) {
-  DT_SWITCH(dtype, if (row_vec_ok<T>(C, y, x, nullptr, nullptr)) {
-    const int lpr = lpr_for<T>(C);
-    LPR_SWITCH(lpr, hipLaunchKernelGGL((layernorm_fwd_vec_kernel<T, L>), dim3(rows_grid(rows, lpr)), dim3(256), 0, stream, (T*)y, mean, rstd, (const T*)x, gamma, beta, C, eps, rows))
-    return hdmoe_launch_status();
-  })
-  DT_SWITCH(dtype, hipLaunchKernelGGL(layernorm_fwd_kernel<T>, dim3(grid_for(rows)), dim3(TPB), 0, stream, (T*)y, mean, rstd, (const T*)x, gamma, beta, C, eps, rows))
-  return hdmoe_launch_status();
+  ROW_NORM_LAUNCH(layernorm_fwd_vec_kernel, layernorm_fwd_kernel, 4096, 2048, 0, y, x, nullptr, nullptr, (T*)y, mean, rstd, (const T*)x, gamma, beta,
+                  C, eps, rows)
 }
 int hdmoe_layernorm_bwd(void* dx, float* dgamma, float* dbeta, const void* dy, const void* x, const float* gamma,
                         const float* mean, const float* rstd, long rows, int C, int dtype, hipStream_t stream) {
   if (C > 4096) return HDMOE_EINVAL;
-  DT_SWITCH(dtype, if (row_vec_ok<T>(C, dx, dy, x, nullptr)) {
-    const int lpr = lpr_for<T>(C);
-    unsigned gv = rows_grid(rows, lpr); if (gv > 512) gv = 512;
-    LPR_SWITCH(lpr, hipLaunchKernelGGL((layernorm_bwd_vec_kernel<T, L>), dim3(gv), dim3(256), 2 * C * sizeof(float), stream, (T*)dx, dgamma, dbeta,
-                                       (const T*)dy, (const T*)x, gamma, mean, rstd, C, rows))
-    return hdmoe_launch_status();
-  })
-  unsigned g = grid_for(rows);
-  if (g > 256) g = 256;
-  DT_SWITCH(dtype, hipLaunchKernelGGL(layernorm_bwd_kernel<T>, dim3(g), dim3(TPB), 2 * C * sizeof(float), stream, (T*)dx, dgamma, dbeta,
-                                      (const T*)dy, (const T*)x, gamma, mean, rstd, C, rows))
-  return hdmoe_launch_status();
+  ROW_NORM_LAUNCH(layernorm_bwd_vec_kernel, layernorm_bwd_kernel, 512, 256, 2 * C * sizeof(float), dx, dy, x, nullptr, (T*)dx, dgamma, dbeta,
+                  (const T*)dy, (const T*)x, gamma, mean, rstd, C, rows)
 }
-
 
 /* partial slots [N][slots][2] of a conv output (hdmoe_conv_fwd_split_gn) -> mean / rstd [N] and scale / shift [N][C] of GroupNorm(1, C) */
 int hdmoe_gn1_finalize(float* scale, float* shift, float* mean, float* rstd, const float* ws, const float* gamma, const float* beta, int N,
@@ -1304,37 +1197,34 @@ int hdmoe_gn1_finalize(float* scale, float* shift, float* mean, float* rstd, con
   hipLaunchKernelGGL(gn1_finalize_kernel, dim3(N), dim3(128), 0, stream, scale, shift, mean, rstd, ws, gamma, beta, slots, C, 1.f / (float)count, eps);
   return hdmoe_launch_status();
 }
+/* The three hdmoe_gn1_*relu_mean* forms: ws == null, scale / shift are inputs; else they, mean and rstd are written from the slots; pcnt (with
+ * qsum) != null, the PQ kernel */
+static int gn1_relu_mean_impl(float* out, float* scale, float* shift, float* mean, float* rstd, float* pcnt, float* qsum, const float* y, const float* ws,
+                              const float* gamma, const float* beta, int N, int slots, long S, int C, float eps, hipStream_t stream) {
+  if (!out || !y || !scale || !shift || N < 1 || S < 1 || C < 4 || C % 4 || C > 1024) return HDMOE_EINVAL;
+  if (ws && (!mean || !rstd || !gamma || !beta || slots < 1)) return HDMOE_EINVAL;
+  const int rows = GN1_POOL_THREADS / (C / 4);
+  hipLaunchKernelGGL(pcnt ? gn1_relu_mean_kernel<true> : gn1_relu_mean_kernel<false>, dim3(N), dim3(GN1_POOL_THREADS), (size_t)rows * C * sizeof(float),
+                     stream, out, y, scale, shift, S, C, ws, gamma, beta, mean, rstd, slots, ws ? 1.f / ((float)S * (float)C) : 0.f, ws ? eps : 0.f, pcnt, qsum);
+  return hdmoe_launch_status();
+}
 /* out [N][C] = mean_s relu(y [N][S][C] * scale [N][C] + shift [N][C])   (fp32; C % 4 == 0, C <= 1024) */
 int hdmoe_gn1_relu_mean(float* out, const float* y, const float* scale, const float* shift, int N, long S, int C, hipStream_t stream) {
-  if (!out || !y || !scale || !shift || N < 1 || S < 1 || C < 4 || C % 4 || C > 1024) return HDMOE_EINVAL;
-  const int rows = GN1_POOL_THREADS / (C / 4);
-  hipLaunchKernelGGL(gn1_relu_mean_kernel<false>, dim3(N), dim3(GN1_POOL_THREADS), (size_t)rows * C * sizeof(float), stream, out, y, (float*)scale,
-                     (float*)shift, S, C, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr, 0, 0.f, 0.f,
-                     (float*)nullptr, (float*)nullptr);
-  return hdmoe_launch_status();
+  return gn1_relu_mean_impl(out, (float*)scale, (float*)shift, nullptr, nullptr, nullptr, nullptr, y, nullptr, nullptr, nullptr, N, 0, S, C, 0.f, stream);
 }
 /* hdmoe_gn1_finalize + hdmoe_gn1_relu_mean in one launch: statistics from the conv's partial slots ws [N][slots][2]; scale / shift [N][C] and
  * mean / rstd [N] are written (for the backward), out [N][C] = mean_s relu(GroupNorm(1, C)(y)). */
 int hdmoe_gn1_finalize_relu_mean(float* out, float* scale, float* shift, float* mean, float* rstd, const float* y, const float* ws,
                                  const float* gamma, const float* beta, int N, int slots, long S, int C, float eps, hipStream_t stream) {
-  if (!out || !y || !scale || !shift || !mean || !rstd || !ws || !gamma || !beta || N < 1 || slots < 1 || S < 1 || C < 4 || C % 4 || C > 1024)
-    return HDMOE_EINVAL;
-  const int rows = GN1_POOL_THREADS / (C / 4);
-  hipLaunchKernelGGL(gn1_relu_mean_kernel<false>, dim3(N), dim3(GN1_POOL_THREADS), (size_t)rows * C * sizeof(float), stream, out, y, scale, shift, S, C, ws,
-                     gamma, beta, mean, rstd, slots, 1.f / ((float)S * (float)C), eps, (float*)nullptr, (float*)nullptr);
-  return hdmoe_launch_status();
+  if (!ws) return HDMOE_EINVAL;
+  return gn1_relu_mean_impl(out, scale, shift, mean, rstd, nullptr, nullptr, y, ws, gamma, beta, N, slots, S, C, eps, stream);
 }
 /* The same, and pcnt / qsum [N][C] (fp32): per channel, the number of positions where the ReLU is open and the sum of the normalised value
  * (y - mean) * rstd over them -- the statistics hdmoe_gn1t_apply derives this layer's backward sums from when its gradient comes from the pool. */
 int hdmoe_gn1_finalize_relu_mean_pq(float* out, float* scale, float* shift, float* mean, float* rstd, float* pcnt, float* qsum, const float* y,
                                     const float* ws, const float* gamma, const float* beta, int N, int slots, long S, int C, float eps, hipStream_t stream) {
-  if (!out || !y || !scale || !shift || !mean || !rstd || !pcnt || !qsum || !ws || !gamma || !beta || N < 1 || slots < 1 || S < 1 || C < 4 || C % 4 ||
-      C > 1024)
-    return HDMOE_EINVAL;
-  const int rows = GN1_POOL_THREADS / (C / 4);
-  hipLaunchKernelGGL(gn1_relu_mean_kernel<true>, dim3(N), dim3(GN1_POOL_THREADS), (size_t)rows * C * sizeof(float), stream, out, y, scale, shift, S, C, ws,
-                     gamma, beta, mean, rstd, slots, 1.f / ((float)S * (float)C), eps, pcnt, qsum);
-  return hdmoe_launch_status();
+  if (!ws || !pcnt || !qsum) return HDMOE_EINVAL;
+  return gn1_relu_mean_impl(out, scale, shift, mean, rstd, pcnt, qsum, y, ws, gamma, beta, N, slots, S, C, eps, stream);
 }
 
 }  // extern "C"

@@ -131,14 +131,11 @@ __global__ void rag_zero_unowned_kernel(uint4* y, Rag rg, long L16) {
 
 // ---------------------------------------------------------------- GroupNorm over a row's REAL tokens (+ activation), one block per row
 // nn.GroupNorm on (B, C, S): statistics over (C / G channels) x S tokens per sample (reference Vit_block.GN, :529-531).
-DEVI float act_f(float v, int act) { return act == 1 ? fmaxf(v, 0.f) : (act == 2 ? mp_silu_f(v) : v); }
-DEVI float act_grad_f(float v, int act) { return act == 1 ? (v > 0.f ? 1.f : 0.f) : (act == 2 ? mp_silu_grad_f(v) : 1.f); }
-
-// deterministic block sum (fixed shuffle tree, then the waves' partials in wave order): every thread gets the total
-DEVI float block_sum(float v, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();                                          // `red` may still be read from the previous call
+// deterministic sum over the TPB threads (fixed shuffle tree, then the waves' partials in wave order): every thread gets the total.
+// common.h's block_sum with the wave count a constant
+DEVI float rag_block_sum(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();                                         // `red` may still be read from the previous call
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   float t = 0.f;
@@ -163,7 +160,7 @@ __global__ __launch_bounds__(TPB) void gn_rag_fwd_kernel(T* y, float* mean, floa
   for (int gr = 0; gr < G; ++gr) {
     float p = 0.f;
     for (int e = tid; e < len * Cg; e += TPB) p += to_f(xr[(e / Cg) * C + gr * Cg + e % Cg]);
-    const float tot = block_sum(p, red);
+    const float tot = rag_block_sum(p, red);
     if (tid == 0) s1[gr] = tot;
   }
   __syncthreads();
@@ -171,7 +168,7 @@ __global__ __launch_bounds__(TPB) void gn_rag_fwd_kernel(T* y, float* mean, floa
     const float mu = s1[gr] * inv_m;
     float p = 0.f;
     for (int e = tid; e < len * Cg; e += TPB) { const float d = to_f(xr[(e / Cg) * C + gr * Cg + e % Cg]) - mu; p += d * d; }
-    const float tot = block_sum(p, red);
+    const float tot = rag_block_sum(p, red);
     if (tid == 0) s2[gr] = tot;
   }
   __syncthreads();
@@ -180,8 +177,7 @@ __global__ __launch_bounds__(TPB) void gn_rag_fwd_kernel(T* y, float* mean, floa
     float o = 0.f;
     if (e < n) {
       const int c = e % C, gr = c / Cg;
-      const float xh = (to_f(xr[e]) - s1[gr] * inv_m) * rsqrtf(s2[gr] * inv_m + eps);
-      o = act_f(xh * gamma.p[g][c] + beta.p[g][c], act);
+      o = gn_fwd_f(to_f(xr[e]), s1[gr] * inv_m, rsqrtf(s2[gr] * inv_m + eps), gamma.p[g][c], beta.p[g][c], act);
     }
     yr[e] = from_f<T>(o);
   }
@@ -207,14 +203,14 @@ __global__ __launch_bounds__(TPB) void gn_rag_bwd_kernel(T* dx, MFPtrs dgamma, M
     float p1 = 0.f, p2 = 0.f;
     for (int q = tid; q < len * Cg; q += TPB) {
       const int c = gr * Cg + q % Cg, e = (q / Cg) * C + c;
-      const float xh = (to_f(xr[e]) - mu) * rs;
-      const float dz = to_f(dyr[e]) * act_grad_f(xh * gamma.p[g][c] + beta.p[g][c], act);
+      const float xh = gn_xhat(to_f(xr[e]), mu, rs);
+      const float dz = gn_dz(to_f(dyr[e]), xh, gamma.p[g][c], beta.p[g][c], act);
       p1 += dz * gamma.p[g][c];
       p2 += dz * gamma.p[g][c] * xh;
       atomicAdd(&sm[c], dz * xh);                            // per-channel parameter sums (added to global memory with atomics anyway)
       atomicAdd(&sm[C + c], dz);
     }
-    const float t1 = block_sum(p1, red), t2 = block_sum(p2, red);
+    const float t1 = rag_block_sum(p1, red), t2 = rag_block_sum(p2, red);
     if (tid == 0) { a1[gr] = t1; a2[gr] = t2; }
   }
   __syncthreads();
@@ -224,9 +220,8 @@ __global__ __launch_bounds__(TPB) void gn_rag_bwd_kernel(T* dx, MFPtrs dgamma, M
     if (e < n) {
       const int c = e % C, gr = c / Cg;
       const float rs = rstd[(long)r * G + gr];
-      const float xh = (to_f(xr[e]) - mean[(long)r * G + gr]) * rs;
-      const float dz = to_f(dyr[e]) * act_grad_f(xh * gamma.p[g][c] + beta.p[g][c], act);
-      o = rs * (dz * gamma.p[g][c] - inv_m * (a1[gr] + xh * a2[gr]));
+      const float xh = gn_xhat(to_f(xr[e]), mean[(long)r * G + gr], rs);
+      o = gn_dx(gn_dz(to_f(dyr[e]), xh, gamma.p[g][c], beta.p[g][c], act), xh, rs, gamma.p[g][c], inv_m, a1[gr], a2[gr]);
     }
     dxr[e] = from_f<T>(o);                                  // zero gradient into the padding
   }
@@ -322,7 +317,7 @@ __global__ __launch_bounds__(TPB) void ln_rag_bwd_kernel(T* dx, MFPtrs dgamma, M
     }
 }
 
-static inline unsigned grid_for(long n) { long b = (n + TPB - 1) / TPB; if (b > 4096) b = 4096; if (b < 1) b = 1; return (unsigned)b; }
+constexpr long RAG_GRID_CAP = 4096;                         // workgroups of the element-wise pack / unpack / select launches
 static inline bool mk_rag(Rag& rg, const int* seg, const int* lens, int ng) {
   if (!seg || !lens || ng < 1 || ng > HDMOE_MAX_GROUPS) return false;
   rg.seg = seg; rg.ng = ng;
@@ -335,10 +330,6 @@ template <typename P, typename Q> static inline void fill(P& dst, Q* const* src,
 
 }  // namespace
 
-#define RAG_DT(dtype, STMT)                                   \
-  if (dtype == HDMOE_F32) { typedef float T; STMT; }          \
-  else if (dtype == HDMOE_BF16) { typedef bf16 T; STMT; }     \
-  else return HDMOE_EDTYPE;
 
 extern "C" {
 
@@ -347,28 +338,28 @@ int hdmoe_rag_pack(void* dst, const void* const* srcs, const float* const* pos, 
                    int Sp, int C, int dtype, hipStream_t stream) {
   Rag rg; if (!mk_rag(rg, seg, lens, ngroups) || !dst || !srcs) return HDMOE_EINVAL;
   Ptrs s; FPtrs p; fill(s, srcs, ngroups); fill(p, pos, ngroups);
-  RAG_DT(dtype, hipLaunchKernelGGL(rag_pack_kernel<T>, dim3(grid_for((long)R * Sp * C)), dim3(TPB), 0, stream, (T*)dst, s, p, rg, R, Sp, C))
+  DT_SWITCH(dtype, hipLaunchKernelGGL(rag_pack_kernel<T>, dim3(grid_for((long)R * Sp * C, RAG_GRID_CAP)), dim3(TPB), 0, stream, (T*)dst, s, p, rg, R, Sp, C))
   return hdmoe_launch_status();
 }
 int hdmoe_rag_pack_bwd(void* const* dsrcs, float* const* dpos, const void* ddst, const int* seg, const int* lens, int ngroups, int R,
                        int Sp, int C, int dtype, hipStream_t stream) {
   Rag rg; if (!mk_rag(rg, seg, lens, ngroups) || !ddst || !dsrcs) return HDMOE_EINVAL;
   MPtrs s; MFPtrs p; fill(s, dsrcs, ngroups); fill(p, dpos, ngroups);
-  RAG_DT(dtype, hipLaunchKernelGGL((rag_pack_bwd_kernel<T, false>), dim3(grid_for((long)R * Sp * C)), dim3(TPB), 0, stream, s, p, (const T*)ddst, rg, R, Sp, C))
+  DT_SWITCH(dtype, hipLaunchKernelGGL((rag_pack_bwd_kernel<T, false>), dim3(grid_for((long)R * Sp * C, RAG_GRID_CAP)), dim3(TPB), 0, stream, s, p, (const T*)ddst, rg, R, Sp, C))
   return hdmoe_launch_status();
 }
 int hdmoe_rag_unpack(void* const* dsts, const void* src, const int* seg, const int* lens, int ngroups, int R, int Sp, int C, int dtype,
                      hipStream_t stream) {
   Rag rg; if (!mk_rag(rg, seg, lens, ngroups) || !src || !dsts) return HDMOE_EINVAL;
   MPtrs d; fill(d, dsts, ngroups);
-  RAG_DT(dtype, hipLaunchKernelGGL((rag_unpack_kernel<T, false>), dim3(grid_for((long)R * Sp * C)), dim3(TPB), 0, stream, d, (const T*)src, rg, R, Sp, C))
+  DT_SWITCH(dtype, hipLaunchKernelGGL((rag_unpack_kernel<T, false>), dim3(grid_for((long)R * Sp * C, RAG_GRID_CAP)), dim3(TPB), 0, stream, d, (const T*)src, rg, R, Sp, C))
   return hdmoe_launch_status();
 }
 int hdmoe_rag_unpack_bwd(void* dsrc, const void* const* ddsts, const int* seg, const int* lens, int ngroups, int R, int Sp, int C,
                          int dtype, hipStream_t stream) {
   Rag rg; if (!mk_rag(rg, seg, lens, ngroups) || !dsrc || !ddsts) return HDMOE_EINVAL;
   Ptrs d; fill(d, ddsts, ngroups);
-  RAG_DT(dtype, hipLaunchKernelGGL((rag_unpack_bwd_kernel<T, false>), dim3(grid_for((long)R * Sp * C)), dim3(TPB), 0, stream, (T*)dsrc, d, rg, R, Sp, C))
+  DT_SWITCH(dtype, hipLaunchKernelGGL((rag_unpack_bwd_kernel<T, false>), dim3(grid_for((long)R * Sp * C, RAG_GRID_CAP)), dim3(TPB), 0, stream, (T*)dsrc, d, rg, R, Sp, C))
   return hdmoe_launch_status();
 }
 /* Own-row forms of the three above: expert g's compact tensor is written (pack_bwd, unpack) / read (unpack_bwd) in its own rows
@@ -378,7 +369,7 @@ int hdmoe_rag_pack_bwd_own(void* const* dsrcs, float* const* dpos, const void* d
   Rag rg; if (!mk_rag(rg, seg, lens, ngroups) || !ddst || !dsrcs) return HDMOE_EINVAL;
   MPtrs s; MFPtrs p; fill(s, dsrcs, ngroups); fill(p, dpos, ngroups);
   hdmoe_count_selection(HDMOE_SEL_ROW_WINDOW);
-  RAG_DT(dtype, hipLaunchKernelGGL((rag_pack_bwd_kernel<T, true>), dim3(grid_for((long)R * Sp * C)), dim3(TPB), 0, stream, s, p, (const T*)ddst, rg, R, Sp, C))
+  DT_SWITCH(dtype, hipLaunchKernelGGL((rag_pack_bwd_kernel<T, true>), dim3(grid_for((long)R * Sp * C, RAG_GRID_CAP)), dim3(TPB), 0, stream, s, p, (const T*)ddst, rg, R, Sp, C))
   return hdmoe_launch_status();
 }
 int hdmoe_rag_unpack_own(void* const* dsts, const void* src, const int* seg, const int* lens, int ngroups, int R, int Sp, int C, int dtype,
@@ -386,7 +377,7 @@ int hdmoe_rag_unpack_own(void* const* dsts, const void* src, const int* seg, con
   Rag rg; if (!mk_rag(rg, seg, lens, ngroups) || !src || !dsts) return HDMOE_EINVAL;
   MPtrs d; fill(d, dsts, ngroups);
   hdmoe_count_selection(HDMOE_SEL_ROW_WINDOW);
-  RAG_DT(dtype, hipLaunchKernelGGL((rag_unpack_kernel<T, true>), dim3(grid_for((long)R * Sp * C)), dim3(TPB), 0, stream, d, (const T*)src, rg, R, Sp, C))
+  DT_SWITCH(dtype, hipLaunchKernelGGL((rag_unpack_kernel<T, true>), dim3(grid_for((long)R * Sp * C, RAG_GRID_CAP)), dim3(TPB), 0, stream, d, (const T*)src, rg, R, Sp, C))
   return hdmoe_launch_status();
 }
 int hdmoe_rag_unpack_bwd_own(void* dsrc, const void* const* ddsts, const int* seg, const int* lens, int ngroups, int R, int Sp, int C,
@@ -394,7 +385,7 @@ int hdmoe_rag_unpack_bwd_own(void* dsrc, const void* const* ddsts, const int* se
   Rag rg; if (!mk_rag(rg, seg, lens, ngroups) || !dsrc || !ddsts) return HDMOE_EINVAL;
   Ptrs d; fill(d, ddsts, ngroups);
   hdmoe_count_selection(HDMOE_SEL_ROW_WINDOW);
-  RAG_DT(dtype, hipLaunchKernelGGL((rag_unpack_bwd_kernel<T, true>), dim3(grid_for((long)R * Sp * C)), dim3(TPB), 0, stream, (T*)dsrc, d, rg, R, Sp, C))
+  DT_SWITCH(dtype, hipLaunchKernelGGL((rag_unpack_bwd_kernel<T, true>), dim3(grid_for((long)R * Sp * C, RAG_GRID_CAP)), dim3(TPB), 0, stream, (T*)dsrc, d, rg, R, Sp, C))
   return hdmoe_launch_status();
 }
 /* y[r] = 0 for the rows r of [R] that lie in no expert's window; the others stay as they are; row_bytes % 16 == 0 */
@@ -411,14 +402,14 @@ int hdmoe_rag_select(void* y, const void* const* outs, const int* seg, int ngrou
   const int zeros[HDMOE_MAX_GROUPS] = {0};
   Rag rg; if (!mk_rag(rg, seg, zeros, ngroups) || !y || !outs || row_bytes % 16) return HDMOE_EINVAL;
   Ptrs o; fill(o, outs, ngroups);
-  hipLaunchKernelGGL(rag_select_kernel, dim3(grid_for((long)R * (row_bytes / 16))), dim3(TPB), 0, stream, (uint4*)y, o, rg, R, row_bytes / 16);
+  hipLaunchKernelGGL(rag_select_kernel, dim3(grid_for((long)R * (row_bytes / 16), RAG_GRID_CAP)), dim3(TPB), 0, stream, (uint4*)y, o, rg, R, row_bytes / 16);
   return hdmoe_launch_status();
 }
 int hdmoe_rag_select_bwd(void* const* douts, const void* dy, const int* seg, int ngroups, int R, long row_bytes, hipStream_t stream) {
   const int zeros[HDMOE_MAX_GROUPS] = {0};
   Rag rg; if (!mk_rag(rg, seg, zeros, ngroups) || !dy || !douts || row_bytes % 16) return HDMOE_EINVAL;
   MPtrs o; fill(o, douts, ngroups);
-  hipLaunchKernelGGL(rag_select_bwd_kernel, dim3(grid_for((long)R * (row_bytes / 16))), dim3(TPB), 0, stream, o, (const uint4*)dy, rg, R, row_bytes / 16);
+  hipLaunchKernelGGL(rag_select_bwd_kernel, dim3(grid_for((long)R * (row_bytes / 16), RAG_GRID_CAP)), dim3(TPB), 0, stream, o, (const uint4*)dy, rg, R, row_bytes / 16);
   return hdmoe_launch_status();
 }
 /* GroupNorm(G, C) over each row's real tokens + activation (0 none, 1 relu, 2 mp_silu); mean / rstd [R][G]; gamma / beta per expert */
@@ -427,7 +418,7 @@ int hdmoe_gn_rag_fwd(void* y, float* mean, float* rstd, const void* x, const flo
                      hipStream_t stream) {
   Rag rg; if (!mk_rag(rg, seg, lens, ngroups) || G < 1 || G > 32 || C % G) return HDMOE_EINVAL;
   FPtrs ga, be; fill(ga, gamma, ngroups); fill(be, beta, ngroups);
-  RAG_DT(dtype, hipLaunchKernelGGL(gn_rag_fwd_kernel<T>, dim3(R), dim3(TPB), 0, stream, (T*)y, mean, rstd, (const T*)x, ga, be, rg, Sp, C, G, act, eps))
+  DT_SWITCH(dtype, hipLaunchKernelGGL(gn_rag_fwd_kernel<T>, dim3(R), dim3(TPB), 0, stream, (T*)y, mean, rstd, (const T*)x, ga, be, rg, Sp, C, G, act, eps))
   return hdmoe_launch_status();
 }
 int hdmoe_gn_rag_bwd(void* dx, float* const* dgamma, float* const* dbeta, const void* dy, const void* x, const float* const* gamma,
@@ -435,7 +426,7 @@ int hdmoe_gn_rag_bwd(void* dx, float* const* dgamma, float* const* dbeta, const 
                      int R, int Sp, int C, int G, int act, int dtype, hipStream_t stream) {
   Rag rg; if (!mk_rag(rg, seg, lens, ngroups) || G < 1 || G > 32 || C % G) return HDMOE_EINVAL;
   FPtrs ga, be; MFPtrs dg, db; fill(ga, gamma, ngroups); fill(be, beta, ngroups); fill(dg, dgamma, ngroups); fill(db, dbeta, ngroups);
-  RAG_DT(dtype, hipLaunchKernelGGL(gn_rag_bwd_kernel<T>, dim3(R), dim3(TPB), 2 * C * sizeof(float), stream, (T*)dx, dg, db, (const T*)dy, (const T*)x, ga, be,
+  DT_SWITCH(dtype, hipLaunchKernelGGL(gn_rag_bwd_kernel<T>, dim3(R), dim3(TPB), 2 * C * sizeof(float), stream, (T*)dx, dg, db, (const T*)dy, (const T*)x, ga, be,
                                    mean, rstd, rg, Sp, C, G, act))
   return hdmoe_launch_status();
 }
@@ -451,7 +442,7 @@ int hdmoe_ln_rag_fwd(void* y, float* mean, float* rstd, const void* x, const flo
   else if (C <= 128) hipLaunchKernelGGL((KERNEL<T, 4>), dim3(R), dim3(TPB), 0, stream, __VA_ARGS__); \
   else hipLaunchKernelGGL((KERNEL<T, 8>), dim3(R), dim3(TPB), 0, stream, __VA_ARGS__);
   if (C < 1 || C > 256) return HDMOE_EINVAL;
-  RAG_DT(dtype, LN_CPL(ln_rag_fwd_kernel, (T*)y, mean, rstd, (const T*)x, ga, be, rg, Sp, C, eps))
+  DT_SWITCH(dtype, LN_CPL(ln_rag_fwd_kernel, (T*)y, mean, rstd, (const T*)x, ga, be, rg, Sp, C, eps))
   return hdmoe_launch_status();
 }
 int hdmoe_ln_rag_bwd(void* dx, float* const* dgamma, float* const* dbeta, const void* dy, const void* x, const float* const* gamma,
@@ -461,7 +452,7 @@ int hdmoe_ln_rag_bwd(void* dx, float* const* dgamma, float* const* dbeta, const 
   Rag rg; if (!mk_rag(rg, seg, zeros, ngroups)) return HDMOE_EINVAL;
   FPtrs ga; MFPtrs dg, db; fill(ga, gamma, ngroups); fill(dg, dgamma, ngroups); fill(db, dbeta, ngroups);
   if (C < 1 || C > 256) return HDMOE_EINVAL;
-  RAG_DT(dtype, LN_CPL(ln_rag_bwd_kernel, (T*)dx, dg, db, (const T*)dy, (const T*)x, ga, mean, rstd, rg, Sp, C))
+  DT_SWITCH(dtype, LN_CPL(ln_rag_bwd_kernel, (T*)dx, dg, db, (const T*)dy, (const T*)x, ga, mean, rstd, rg, Sp, C))
   return hdmoe_launch_status();
 }
 

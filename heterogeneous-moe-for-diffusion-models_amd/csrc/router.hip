@@ -10,13 +10,6 @@
 namespace {
 
 constexpr int TPB = 256;
-#define GRID_STRIDE(i, n) for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
-static inline unsigned grid_for(long n) {
-  long b = (n + TPB - 1) / TPB;
-  if (b > 2048) b = 2048;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
 
 // ---------------------------------------------------------------- router head (one thread per row; E <= 64)
 __global__ void router_head_fwd_kernel(float* sparse, float* probs, float* xout, int* idx, const float* logits, const float* noise,

@@ -51,9 +51,10 @@ Which kernel each shape reaches (W = 4 fp32 / 8 bf16 channels per 16-byte vector
     (16, 40 and 72 are there for the arms the other counts leave out: fp32 LPR 32, bf16 LPR 2, 8 and 16)
     rows = 16,400 (fp32 C = 256): 4100 blocks wanted, the forward's cap is 4096; rows = 2,100: 525 > the LayerNorm backward's 512;
     rows = 524,300 (C = 3): 2049 blocks > the scalar kernels' 2048.  A view one element into a buffer -> the scalar kernels.
-* ops.group_norm -> groupnorm_{stats,apply,bwd_stats,bwd_apply}_vec_kernel when C % W == 0, (C / G) % W == 0, cv = C / W divides 512
-  and the pointers are aligned, else the scalar kernels (thread -> group = t % G); forward row ranges (groupnorm_part_stats_vec_kernel
-  + groupnorm_merge_kernel) when S >= 512, backward row ranges (atomics into s1 / s2) when N < 128 and S >= 256.  See GN_CASES.
+* ops.group_norm -> groupnorm_{stats,bwd_stats,bwd_apply}_vec_kernel and groupnorm_apply_kernel<T, W> when C % W == 0, (C / G) % W == 0,
+  cv = C / W divides 512 and the pointers are aligned, else the scalar kernels (thread -> group = t % G) and groupnorm_apply_kernel<T, 1>;
+  forward row ranges (groupnorm_part_stats_vec_kernel + groupnorm_merge_kernel; the statistics body of both vector kernels is
+  groupnorm_moments) when S >= 512, backward row ranges (atomics into s1 / s2) when N < 128 and S >= 256.  See GN_CASES.
 * router trunks: direct calls, see the case tables of section 3.
 """
 import math
