@@ -14,6 +14,26 @@ namespace {
 constexpr int TQ = 256;     // rows owned by a block (one per thread)
 constexpr int TK = 128;     // streamed rows per LDS tile
 constexpr int CH = 16;      // online-softmax chunk
+constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
+
+// The pieces the dense and the ragged one-row-per-thread kernels share.  What differs between them stays with the callers: whether a score
+// starts from the bias or gets it added after the dot product, and the chunked / per-key online maximum of the two forward kernels.
+// Three places keep their own copy because the shared one cost them occupancy (profiles/attention_resources.txt): the staging loop of
+// attn_bwd_dkv_kernel, the dot product of attn_bwd_dq_kernel, and both of the dbias kernels' bodies.
+// rows [row0, row0 + n) of head h of a / b [rows][E] -> da / db [n][D] in LDS as fp32 (a times `mul`), by the NT threads of the workgroup
+template <int NT, int D, typename T>
+DEVI void stage_heads(float* da, float* db, const T* a, const T* b, long row0, int n, int E, int h, float mul) {
+  for (int e = threadIdx.x; e < n * D; e += NT) {
+    const long src = (row0 + e / D) * E + h * D + e % D;
+    da[e] = to_f(a[src]) * mul; db[e] = to_f(b[src]);
+  }
+}
+// s += a . b, dp += c . d over one head: the score and dP = dO . V of one (query, key) pair
+template <int D>
+DEVI void dot2(float& s, float& dp, const float* a, const float* b, const float* c, const float* d) {
+#pragma unroll
+  for (int i = 0; i < D; ++i) { s += a[i] * b[i]; dp += c[i] * d[i]; }
+}
 
 template <typename T, int D, bool BIAS>
 __global__ __launch_bounds__(TQ) void attn_fwd_kernel(T* out, float* lse, const T* q, const T* k, const T* v, const float* bias,
@@ -30,10 +50,7 @@ __global__ __launch_bounds__(TQ) void attn_fwd_kernel(T* out, float* lse, const 
   for (int j0 = 0; j0 < Skv; j0 += TK) {
     const int nj = min(TK, Skv - j0);
     __syncthreads();
-    for (int e = threadIdx.x; e < nj * D; e += TQ) {
-      const long src = ((long)b * Skv + j0 + e / D) * E + h * D + e % D;
-      sk[e] = to_f(k[src]); sv[e] = to_f(v[src]);
-    }
+    stage_heads<TQ, D>(sk, sv, k, v, (long)b * Skv + j0, nj, E, h, 1.f);
     __syncthreads();
     if (!act) continue;
     for (int c0 = 0; c0 < nj; c0 += CH) {
@@ -100,16 +117,13 @@ __global__ __launch_bounds__(TQ) void attn_bwd_dq_kernel(T* dq, float* delta, fl
   for (int j0 = 0; j0 < Skv; j0 += TK) {
     const int nj = min(TK, Skv - j0);
     __syncthreads();
-    for (int e = threadIdx.x; e < nj * D; e += TQ) {
-      const long src = ((long)b * Skv + j0 + e / D) * E + h * D + e % D;
-      sk[e] = to_f(k[src]); sv[e] = to_f(v[src]);
-    }
+    stage_heads<TQ, D>(sk, sv, k, v, (long)b * Skv + j0, nj, E, h, 1.f);
     __syncthreads();
     if (!act) continue;
 #pragma unroll 8
     for (int j = 0; j < nj; ++j) {
       float s = 0.f, dp = 0.f;
-#pragma unroll
+#pragma unroll                                                // (not dot2: with it <T, 8, false> takes 73 VGPRs for 64, 6 waves for 8)
       for (int d = 0; d < D; ++d) { s += qv[d] * sk[j * D + d]; dp += dov[d] * sv[j * D + d]; }
       if (BIAS) s += bias[boff + j0 + j];
       const float ds = __expf(s - ls) * (dp - dl);
@@ -143,7 +157,7 @@ __global__ __launch_bounds__(TQ) void attn_bwd_dkv_kernel(T* dk, T* dv, const T*
   for (int i0 = 0; i0 < Sq; i0 += TK) {
     const int ni = min(TK, Sq - i0);
     __syncthreads();
-    for (int e = threadIdx.x; e < ni * D; e += TQ) {
+    for (int e = threadIdx.x; e < ni * D; e += TQ) {           // (not stage_heads: with it <T, 4, true> takes 97 VGPRs for 92, 4 waves for 5)
       const long src = ((long)b * Sq + i0 + e / D) * E + h * D + e % D;
       sq[e] = to_f(q[src]) * scale; sdo[e] = to_f(dout[src]);
     }
@@ -156,8 +170,7 @@ __global__ __launch_bounds__(TQ) void attn_bwd_dkv_kernel(T* dk, T* dv, const T*
 #pragma unroll 8
     for (int i = 0; i < ni; ++i) {
       float s = 0.f, dp = 0.f;
-#pragma unroll
-      for (int d = 0; d < D; ++d) { s += sq[i * D + d] * kv[d]; dp += sdo[i * D + d] * vv[d]; }
+      dot2<D>(s, dp, sq + i * D, kv, sdo + i * D, vv);
       if (BIAS) s += bias[((long)h * Sb + i0 + i) * Sb + j];
       const float p = __expf(s - sl[i]);
       const float ds = p * (dp - sd[i]);
@@ -234,13 +247,13 @@ __global__ void attn_dbias_kernel(float* dbias, const T* dout, const T* q, const
 // the same strided loads but 8x fewer of them, off the sweep.  What the 16-byte padded rows of the old image supplied -- the copy of
 // k for the hi / lo pair, the 1 of V's fifth column, zeros -- now comes from registers (a duplicated 8-byte read) and from a constant
 // 256-byte block the lanes of the transposing read that address columns 4..15 point to instead of the row.
-#ifndef HDMOE_ATTN_DBG
-#define HDMOE_ATTN_DBG 0
-#endif
 constexpr int ATT_HS = 1024;                                 // rows of the streamed side staged per head image
 constexpr int ATT_IMG = ATT_HS * 8;                          // bytes of one raw head image
 constexpr int ATT_CONST = 1024;                              // constant block, period 64 B: 8-byte word 0 = [1 0 0 0], word 2 = [1 1 1 0], else zeros
 constexpr int CB_ONE = 0, CB_ZERO = 8, CB_ONE3 = 16;
+constexpr int ATT_QD_IMG = 2 * ATT_IMG + ATT_HS * 16;        // Q | dO | one 16-byte row of shifts per query (the backward kernels below)
+constexpr int ATT_KV_LDS = 4 * ATT_IMG + ATT_CONST;          // forward and dq kernels: [2 buffers][K | V], the constant block
+constexpr int ATT_DKV_LDS = 2 * ATT_QD_IMG + ATT_CONST + 8 * 32 * 8 * 4;   // dk / dv kernel: two images, the constant block, 8 waves' partial sums
 DEVI f32x16 mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 DEVI bf16x8 pack8(const f32x16& v, int s) {
   bf16x8 o;
@@ -282,6 +295,23 @@ DEVI bf16x8 shift_frag(float x, int j0) {
   const bf16 b2 = (bf16)r1;
   f[j0] = a; f[j0 + 1] = b2; f[j0 + 2] = (bf16)(r1 - (float)b2);
   return f;
+}
+// The 16-byte shift row of one query in a Q | dO | shift image, [-lse hi, lo, 0, 0 | -delta hi, mid, lo, 0] (ls = lse in log2 units), and the
+// lse that stands for a query past Sq: p = exp2(S' - 1e4) = 0
+constexpr float LSE_PAST_SQ = 1.0e4f;
+DEVI bf16x8 shift_row(float ls, float dl) {
+  const bf16x8 a = shift_frag(-ls, 0);
+  bf16x8 w = shift_frag(-dl, 4);
+  w[0] = a[0]; w[1] = a[1];
+  return w;
+}
+DEVI float delta4(bf16x4 a, bf16x4 o) {                       // delta = dO . out of one query and head
+  return (float)a[0] * (float)o[0] + (float)a[1] * (float)o[1] + (float)a[2] * (float)o[2] + (float)a[3] * (float)o[3];
+}
+DEVI void qd_row_write(unsigned char* img, int rr, uint2 wq, uint2 wd, float ls, float dl) {   // row rr of a Q | dO | shift image
+  *reinterpret_cast<uint2*>(img + rr * 8) = wq;
+  *reinterpret_cast<uint2*>(img + ATT_IMG + rr * 8) = wd;
+  *reinterpret_cast<bf16x8*>(img + 2 * ATT_IMG + rr * 16) = shift_row(ls, dl);
 }
 DEVI bf16x8 ones_frag(int j0, int n) {                        // slots j0 .. j0+n-1 = 1
   bf16x8 f = (bf16x8)(0);
@@ -326,19 +356,59 @@ DEVI const unsigned char* tr_ptr(const unsigned char* img, const unsigned char* 
   const int p = lane & 3;
   return p == 0 ? img + tr_row(lane) * 8 : cb + ((p == 1 && ones) ? CB_ONE : CB_ZERO);
 }
-DEVI bf16x8 tr_frag(const unsigned char* p) {
+DEVI bf16x8 tr_pair(const unsigned char* p0, const unsigned char* p1) {   // two transposing reads = one fragment
   typedef __attribute__((ext_vector_type(4))) short s16x4;
   typedef __attribute__((ext_vector_type(8))) short s16x8;
   typedef __attribute__((address_space(3))) s16x4* lds_p;
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p + 64));
+  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p0));
+  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p1));
   return __builtin_bit_cast(bf16x8, (s16x8)__builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
 }
+DEVI bf16x8 tr_frag(const unsigned char* p) { return tr_pair(p, p + 64); }
 DEVI u32x2 row8(const unsigned char* p) { return *reinterpret_cast<const u32x2*>(p); }
 DEVI bf16x8 frag2(const unsigned char* lo, const unsigned char* hi) {   // two 8-byte reads = one fragment
   const u32x2 a = row8(lo), b = row8(hi);
   return frag_of(a.x, a.y, b.x, b.y);
 }
+DEVI void store4(bf16* dst, float a0, float a1, float a2, float a3, float s) {   // one head row of an output: s * a as bf16
+  bf16x4 o;
+  o[0] = (bf16)(a0 * s); o[1] = (bf16)(a1 * s); o[2] = (bf16)(a2 * s); o[3] = (bf16)(a3 * s);
+  *reinterpret_cast<bf16x4*>(dst) = o;
+}
+
+// The K | V side of the forward and dq kernels: stage st = head st / nch, key chunk st % nch of one sample, double-buffered at the front
+// of the LDS as [2 buffers][K | V].  While a wave sweeps stage st, stage st + 1 travels global -> registers (prefetch) and, after the sweep,
+// registers -> the other buffer (commit: last read in stage st - 1, and every wave has passed that stage's barrier).
+struct KVStages {
+  const bf16 *k, *v;
+  unsigned char* lds;
+  long row0;                                                  // first key row of the sample
+  int Skv, E, tid, nch, nst, nn;
+  HeadRegs rk, rv;
+  DEVI int head(int st) const { return st / nch; }
+  DEVI int chunk(int st) const { return st - head(st) * nch; }
+  DEVI int rows(int st) const { return min(ATT_HS, Skv - chunk(st) * ATT_HS); }
+  DEVI const unsigned char* imgK(int st) const { return lds + (st & 1) * 2 * ATT_IMG; }
+  DEVI void load(int st) {
+    nn = rows(st);
+    head_load(rk, k, row0 + chunk(st) * ATT_HS, nn, E, head(st), tid);
+    head_load(rv, v, row0 + chunk(st) * ATT_HS, nn, E, head(st), tid);
+  }
+  DEVI void write(int st) {                                   // + the barrier that publishes it
+    unsigned char* buf = lds + (st & 1) * 2 * ATT_IMG;
+    head_write(rk, buf, nn, tid);
+    head_write(rv, buf + ATT_IMG, nn, tid);
+    __syncthreads();
+  }
+  DEVI void start(const bf16* k_, const bf16* v_, unsigned char* lds_, int b, int Skv_, int E_, int H, int tid_) {
+    k = k_; v = v_; lds = lds_; row0 = (long)b * Skv_; Skv = Skv_; E = E_; tid = tid_;
+    nch = (Skv + ATT_HS - 1) / ATT_HS; nst = H * nch;
+    load(0);
+    write(0);
+  }
+  DEVI void prefetch(int st) { if (st + 1 < nst) load(st + 1); }
+  DEVI void commit(int st) { if (st + 1 < nst) write(st + 1); }
+};
 
 // One sweep of a wave's 32 queries of one head over the staged keys [0, n).  fq: lanes hh == 0 [hi(c q) | lo(c q)], lanes hh == 1 zeros.
 // FAST: fixed shift (see the header); else the online maximum.  o / m carry over between key chunks (first = chunk 0 of the head).
@@ -383,10 +453,8 @@ DEVI void attn_fwd_sweep(f32x16& o, float& m, bf16x8& fqs, const bool first, con
         if (kb + acc_row(reg, lane) >= n) s[reg] = -INFINITY;
     }
     if (FAST) {
-#if HDMOE_ATTN_DBG != 1 && HDMOE_ATTN_DBG != 3
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) s[reg] = __builtin_amdgcn_exp2f(s[reg]);
-#endif
     } else {
       float tm = s[0];
 #pragma unroll
@@ -399,12 +467,8 @@ DEVI void attn_fwd_sweep(f32x16& o, float& m, bf16x8& fqs, const bool first, con
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) s[reg] = __builtin_amdgcn_exp2f(s[reg] - mn);
     }
-#if HDMOE_ATTN_DBG == 2 || HDMOE_ATTN_DBG == 3
-    o[0] += s[0] + s[5] + s[10] + s[15]; o[1] += s[1] + s[4] + s[11] + s[14]; o[2] += s[2] + s[7] + s[8] + s[13]; o[3] += s[3] + s[6] + s[9] + s[12];
-#else
     o = mfma_bf16(fv0, pack8(s, 0), o);
     o = mfma_bf16(fv1, pack8(s, 1), o);
-#endif
   };
   int kb = 0;
   for (; kb + 128 <= n; kb += 128) {                          // four full tiles per pointer step
@@ -426,54 +490,36 @@ __global__ __launch_bounds__(512) void attn_fwd_mfma_kernel(bf16* out, float* ls
   const int b = blockIdx.y, q0 = blockIdx.x * 256 + wave * 32, E = H * 4;
   const bool qok = q0 + r < Sq;
   const long qrow = ((long)b * Sq + q0 + (qok ? r : 0)) * E;
-  const int nch = (Skv + ATT_HS - 1) / ATT_HS, nst = H * nch;
-  const bool slow = force_slow != 0 || nch > 1;               // (the repeat-on-overflow needs the head's keys in ONE image)
   const_block(cb, tid);
-  HeadRegs rk, rv;
-  head_load(rk, k, (long)b * Skv, min(ATT_HS, Skv), E, 0, tid);
-  head_load(rv, v, (long)b * Skv, min(ATT_HS, Skv), E, 0, tid);
-  head_write(rk, smem_attn, min(ATT_HS, Skv), tid);
-  head_write(rv, smem_attn + ATT_IMG, min(ATT_HS, Skv), tid);
-  __syncthreads();
+  KVStages kv;
+  kv.start(k, v, smem_attn, b, Skv, E, H, tid);
+  const int nch = kv.nch;
+  const bool slow = force_slow != 0 || nch > 1;               // (the repeat-on-overflow needs the head's keys in ONE image)
   f32x16 o;
   float m;
   bf16x8 fq, fqs;
-  for (int st = 0; st < nst; ++st) {
-    const int h = st / nch, ch = st - h * nch, n = min(ATT_HS, Skv - ch * ATT_HS);
-    const unsigned char* imgK = smem_attn + (st & 1) * 2 * ATT_IMG;
+  for (int st = 0; st < kv.nst; ++st) {
+    const int h = kv.head(st), ch = kv.chunk(st), n = kv.rows(st);
+    const unsigned char* imgK = kv.imgK(st);
     const unsigned char* imgV = imgK + ATT_IMG;
-    int nn = 0;
-    if (st + 1 < nst) {                                       // the next head / chunk: global -> registers beside this sweep
-      const int h2 = (st + 1) / nch, ch2 = st + 1 - h2 * nch;
-      nn = min(ATT_HS, Skv - ch2 * ATT_HS);
-      head_load(rk, k, (long)b * Skv + ch2 * ATT_HS, nn, E, h2, tid);
-      head_load(rv, v, (long)b * Skv + ch2 * ATT_HS, nn, E, h2, tid);
-    }
+    kv.prefetch(st);
     if (ch == 0) fq = scaled_frag(q + qrow + h * 4, hh == 0 && qok, c);
     if (slow) attn_fwd_sweep<false>(o, m, fqs, ch == 0, imgK, imgV, cb, fq, n, lane);
     else {
       attn_fwd_sweep<true>(o, m, fqs, true, imgK, imgV, cb, fq, n, lane);
       const float l0 = __shfl_xor(o[0], 32, 64);
-      const bool bad = HDMOE_ATTN_DBG == 0 && hh == 0 && !(finite_f(o[0]) && finite_f(o[1]) && finite_f(o[2]) && finite_f(o[3]) && finite_f(l0) && l0 > 0.f);
+      const bool bad = hh == 0 && !(finite_f(o[0]) && finite_f(o[1]) && finite_f(o[2]) && finite_f(o[3]) && finite_f(l0) && l0 > 0.f);
       if (__builtin_amdgcn_ballot_w64(bad) != 0)              // (never on the model's activations; tests force it)
         attn_fwd_sweep<false>(o, m, fqs, true, imgK, imgV, cb, fq, n, lane);
     }
     if (ch == nch - 1) {
       const float l = __shfl_xor(o[0], 32, 64);               // row 4 of O^T (lane + 32, register 0) = sum of the probabilities
       if (hh == 0 && qok) {
-        const float il = 1.f / l;
-        bf16x4 ov;
-        ov[0] = (bf16)(o[0] * il); ov[1] = (bf16)(o[1] * il); ov[2] = (bf16)(o[2] * il); ov[3] = (bf16)(o[3] * il);
-        *reinterpret_cast<bf16x4*>(out + qrow + h * 4) = ov;
-        lse[((long)b * H + h) * Sq + q0 + r] = (m + __builtin_amdgcn_logf(l)) * 0.6931471805599453f;
+        store4(out + qrow + h * 4, o[0], o[1], o[2], o[3], 1.f / l);
+        lse[((long)b * H + h) * Sq + q0 + r] = (m + __builtin_amdgcn_logf(l)) * LN2;
       }
     }
-    if (st + 1 < nst) {
-      unsigned char* nxt = smem_attn + ((st + 1) & 1) * 2 * ATT_IMG;   // last read in stage st - 1: every wave has passed that stage's barrier
-      head_write(rk, nxt, nn, tid);
-      head_write(rv, nxt + ATT_IMG, nn, tid);
-      __syncthreads();
-    }
+    kv.commit(st);
   }
 }
 
@@ -487,35 +533,24 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_mfma_kernel(bf16* dq, float* 
   const int b = blockIdx.y, q0 = blockIdx.x * 256 + wave * 32, E = H * 4;
   const bool qok = q0 + r < Sq;
   const long qrow = ((long)b * Sq + q0 + (qok ? r : 0)) * E;
-  const int nch = (Skv + ATT_HS - 1) / ATT_HS, nst = H * nch;
   const_block(cb, tid);
-  HeadRegs rk, rv;
-  head_load(rk, k, (long)b * Skv, min(ATT_HS, Skv), E, 0, tid);
-  head_load(rv, v, (long)b * Skv, min(ATT_HS, Skv), E, 0, tid);
-  head_write(rk, smem_attn, min(ATT_HS, Skv), tid);
-  head_write(rv, smem_attn + ATT_IMG, min(ATT_HS, Skv), tid);
-  __syncthreads();
+  KVStages kv;
+  kv.start(k, v, smem_attn, b, Skv, E, H, tid);
+  const int nch = kv.nch;
   const int kstep = (lane & 3) == 0 ? 256 : 0, rstep = hh == 0 ? 256 : 0;
   f32x16 acc;
   bf16x8 fq, fdo;
-  for (int st = 0; st < nst; ++st) {
-    const int h = st / nch, ch = st - h * nch, n = min(ATT_HS, Skv - ch * ATT_HS);
-    const unsigned char* imgK = smem_attn + (st & 1) * 2 * ATT_IMG;
+  for (int st = 0; st < kv.nst; ++st) {
+    const int h = kv.head(st), ch = kv.chunk(st), n = kv.rows(st);
+    const unsigned char* imgK = kv.imgK(st);
     const unsigned char* imgV = imgK + ATT_IMG;
-    int nn = 0;
-    if (st + 1 < nst) {
-      const int h2 = (st + 1) / nch, ch2 = st + 1 - h2 * nch;
-      nn = min(ATT_HS, Skv - ch2 * ATT_HS);
-      head_load(rk, k, (long)b * Skv + ch2 * ATT_HS, nn, E, h2, tid);
-      head_load(rv, v, (long)b * Skv + ch2 * ATT_HS, nn, E, h2, tid);
-    }
+    kv.prefetch(st);
     if (ch == 0) {
       const long qoff = qrow + h * 4;
       float dl = 0.f, ls = 0.f;
       if (qok) {
-        const bf16x4 a = *reinterpret_cast<const bf16x4*>(dout + qoff), o4 = *reinterpret_cast<const bf16x4*>(out + qoff);
-        dl = (float)a[0] * (float)o4[0] + (float)a[1] * (float)o4[1] + (float)a[2] * (float)o4[2] + (float)a[3] * (float)o4[3];
-        ls = lse[((long)b * H + h) * Sq + q0 + r] * 1.4426950408889634f;
+        dl = delta4(*reinterpret_cast<const bf16x4*>(dout + qoff), *reinterpret_cast<const bf16x4*>(out + qoff));
+        ls = lse[((long)b * H + h) * Sq + q0 + r] * LOG2E;
         if (hh == 0) delta[((long)b * H + h) * Sq + q0 + r] = dl;
       }
       // S'^T = c q.k - lse (log2 units) and dP'^T = V.dO - delta come out of the matrix pipe: slots 8-10 carry the two shifts
@@ -551,29 +586,82 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_mfma_kernel(bf16* dq, float* 
       tile(0);
       aK0 += rstep; aK1 += rstep; aV0 += rstep; aKt += kstep;
     }
-    if (ch == nch - 1 && hh == 0 && qok) {
-      bf16x4 ov;
-      ov[0] = (bf16)(acc[0] * scale); ov[1] = (bf16)(acc[1] * scale); ov[2] = (bf16)(acc[2] * scale); ov[3] = (bf16)(acc[3] * scale);
-      *reinterpret_cast<bf16x4*>(dq + qrow + h * 4) = ov;
-    }
-    if (st + 1 < nst) {
-      unsigned char* nxt = smem_attn + ((st + 1) & 1) * 2 * ATT_IMG;
-      head_write(rk, nxt, nn, tid);
-      head_write(rv, nxt + ATT_IMG, nn, tid);
-      __syncthreads();
+    if (ch == nch - 1 && hh == 0 && qok) store4(dq + qrow + h * 4, acc[0], acc[1], acc[2], acc[3], scale);
+    kv.commit(st);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The 32 x 32 backward tile with rows = queries, columns = keys (the dk / dv kernel and the merged kernel).  The queries' side is a
+// Q | dO | shift image (ATT_QD_IMG): the raw Q and dO rows plus shift_row() per query, which is the A fragment of the half-wave hh == 1
+// in BOTH first products (the K operand holds ones in slots 8-9, the V operand in slots 12-14).
+// QdTile: the six A-fragment pointers of one query tile and their per-lane strides to the next tile (lanes hh == 0: the Q / dO row, 256 B a
+// tile; lanes hh == 1: the query's shift row, 512 B a tile; the transposing reads as tr_ptr()).
+struct QdTile {
+  const unsigned char *q0, *q1, *d0, *d1, *qt, *dt;
+  int astep, d1step, tstep;
+  DEVI QdTile at(int j) const {                               // j tiles further
+    return {q0 + j * astep, q1 + j * astep, d0 + j * astep, d1 + j * d1step, qt + j * tstep, dt + j * tstep, astep, d1step, tstep};
+  }
+};
+DEVI QdTile qd_tile(const unsigned char* imgQ, const unsigned char* cb, int lane, int t) {   // tile t of the image at imgQ
+  const int r = lane & 31, hh = lane >> 5;
+  const unsigned char* imgD = imgQ + ATT_IMG;
+  const unsigned char* imgS = imgD + ATT_IMG;
+  const QdTile p = {hh == 0 ? imgQ + r * 8 : imgS + r * 16, hh == 0 ? imgQ + r * 8 : imgS + r * 16 + 8,
+                    hh == 0 ? imgD + r * 8 : imgS + r * 16, hh == 0 ? cb + CB_ZERO : imgS + r * 16 + 8,
+                    tr_ptr(imgQ, cb, lane, false),          tr_ptr(imgD, cb, lane, false),
+                    hh == 0 ? 256 : 512, hh == 0 ? 0 : 512, (lane & 3) == 0 ? 256 : 0};
+  return p.at(t);
+}
+// One tile: S' and dP' (first products), `between()` (the merged kernel puts the transposed half of its previous tile there), p = exp2(S'),
+// dS = p dP', then dV^T and dK^T of the wave's 32 keys accumulate.  Returns dS packed for the second product (the merged kernel's dQ needs it).
+struct DsFrags { bf16x8 s0, s1; };
+template <typename F>
+DEVI DsFrags bwd_tile_qk(f32x16& ak, f32x16& av, const QdTile& p, const bf16x8 fkB, const bf16x8 fvB, F&& between) {
+  const bf16x8 fqr = frag2(p.q0, p.q1);
+  const bf16x8 fdr = frag2(p.d0, p.d1);
+  const bf16x8 fd0 = tr_frag(p.dt), fd1 = tr_frag(p.dt + 128);
+  const bf16x8 fq0 = tr_frag(p.qt), fq1 = tr_frag(p.qt + 128);
+  f32x16 s = mfma_bf16(fqr, fkB, (f32x16)(0.f));              // S'[q][k] = c q.k - lse[q]: rows = queries, columns = keys
+  f32x16 dp = mfma_bf16(fdr, fvB, (f32x16)(0.f));             // dP'[q][k] = dO[q] . V[k] - delta[q]
+  between();
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg) {
+    s[reg] = __builtin_amdgcn_exp2f(s[reg]);
+    dp[reg] *= s[reg];
+  }
+  av = mfma_bf16(fd0, pack8(s, 0), av);                       // dV^T[d][k] += dO^T[d][q] P[q][k]
+  av = mfma_bf16(fd1, pack8(s, 1), av);
+  const DsFrags ds = {pack8(dp, 0), pack8(dp, 1)};
+  ak = mfma_bf16(fq0, ds.s0, ak);                             // dK^T[d][k] += Q^T[d][q] dS[q][k]
+  ak = mfma_bf16(fq1, ds.s1, ak);
+  return ds;
+}
+// The dK | dV partial sums of the waves that share a key block meet in LDS: a wave with `put` leaves rows 0-3 of its accumulators in its slot
+// `mine` ([8] floats per key); after the barrier a wave with `get` adds the n slots first, first + stride, ... in that order.
+DEVI void dkv_exchange(f32x16& ak, f32x16& av, float* mine, bool put, const float* first, int stride, int n, bool get) {
+  if (put) {
+    *reinterpret_cast<f32x4*>(mine) = (f32x4){ak[0], ak[1], ak[2], ak[3]};
+    *reinterpret_cast<f32x4*>(mine + 4) = (f32x4){av[0], av[1], av[2], av[3]};
+  }
+  __syncthreads();
+  if (get) {
+    for (int i = 0; i < n; ++i) {
+      const float* o2 = first + (long)i * stride;
+      const f32x4 pk = *reinterpret_cast<const f32x4*>(o2), pv = *reinterpret_cast<const f32x4*>(o2 + 4);
+      ak[0] += pk[0]; ak[1] += pk[1]; ak[2] += pk[2]; ak[3] += pk[3];
+      av[0] += pv[0]; av[1] += pv[1]; av[2] += pv[2]; av[3] += pv[3];
     }
   }
 }
 
-// dk, dv: wave = 32 keys, heads in turn; the head's queries and dO rows staged raw, plus a 16-byte row of shifts per query,
-// [-lse hi, lo, 0, 0 | -delta hi, mid, lo, 0]: the A fragment of the half-wave hh == 1 in BOTH first products (the K operand holds ones in
-// slots 8-9, the V operand in slots 12-14).
-constexpr int ATT_KV_BUF = 2 * ATT_IMG + ATT_HS * 16;        // Q | dO | shifts
+// dk, dv: wave = 32 keys, heads in turn; the head's Q | dO | shift image is staged double-buffered, delta read from the dq kernel's output.
 __global__ __launch_bounds__(512, 4) void attn_bwd_dkv_mfma_kernel(bf16* dk, bf16* dv, const bf16* dout, const bf16* q, const bf16* k,
                                                                const bf16* v, const float* lse, const float* delta, int Sq, int Skv,
                                                                int H, float scale, float c, int nkb) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_attn[];
-  unsigned char* cb = smem_attn + 2 * ATT_KV_BUF;
+  unsigned char* cb = smem_attn + 2 * ATT_QD_IMG;
   float* red = reinterpret_cast<float*>(cb + ATT_CONST);      // [8 waves][32 keys][8] partial dK | dV of the query splits
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
   // nkb (1, 2, 4 or 8) key blocks per workgroup; with fewer than 8 the waves of a key block split the queries 8 / nkb ways (the text
@@ -593,38 +681,27 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_dkv_mfma_kernel(bf16* dk, bf1
 #pragma unroll
     for (int i = 0; i < ATT_HS / 512; ++i) {
       const int rr = tid + i * 512;
-      rl[i] = rr < nv ? lse[((long)b * H + h2) * Sq + i0 + rr] * 1.4426950408889634f : 1.0e4f;   // queries past Sq: p = exp2(-1e4) = 0
+      rl[i] = rr < nv ? lse[((long)b * H + h2) * Sq + i0 + rr] * LOG2E : LSE_PAST_SQ;
       rdl[i] = rr < nv ? delta[((long)b * H + h2) * Sq + i0 + rr] : 0.f;
     }
     return nv;
   };
   auto stage_write = [&](int st, int nv) {
-    unsigned char* buf = smem_attn + (st & 1) * ATT_KV_BUF;
-    head_write(rq, buf, nv, tid);
-    head_write(rd, buf + ATT_IMG, nv, tid);
+    unsigned char* buf = smem_attn + (st & 1) * ATT_QD_IMG;
 #pragma unroll
     for (int i = 0; i < ATT_HS / 512; ++i) {
       const int rr = tid + i * 512;
-      if (rr < ((nv + 31) & ~31)) {
-        const bf16x8 a = shift_frag(-rl[i], 0);
-        bf16x8 w = shift_frag(-rdl[i], 4);
-        w[0] = a[0]; w[1] = a[1];
-        *reinterpret_cast<bf16x8*>(buf + 2 * ATT_IMG + rr * 16) = w;
-      }
+      if (rr < ((nv + 31) & ~31)) qd_row_write(buf, rr, rq.v[i], rd.v[i], rl[i], rdl[i]);   // (whole tiles: rows past nv are zeros)
     }
   };
   int nv0 = stage_load(0);
   stage_write(0, nv0);
   __syncthreads();
   const bf16x8 onesK = ones_frag(0, 2), onesV = ones_frag(4, 3);
-  const int tstep = (lane & 3) == 0 ? 256 : 0, astep = hh == 0 ? 256 : 512;
   f32x16 ak, av;
   bf16x8 fkB, fvB;
   for (int st = 0; st < nst; ++st) {
     const int h = st / nch, ch = st - h * nch, n = min(ATT_HS, Sq - ch * ATT_HS);
-    const unsigned char* imgQ = smem_attn + (st & 1) * ATT_KV_BUF;
-    const unsigned char* imgD = imgQ + ATT_IMG;
-    const unsigned char* imgS = imgD + ATT_IMG;
     int nn = 0;
     if (st + 1 < nst) nn = stage_load(st + 1);
     if (ch == 0) {
@@ -632,60 +709,18 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_dkv_mfma_kernel(bf16* dk, bf1
       fvB = hh == 0 ? head_frag(v + krow + h * 4, kok) : onesV;
       ak = (f32x16)(0.f); av = (f32x16)(0.f);
     }
-    // A fragments: lanes hh == 0 [q | q] and [dO | 0], lanes hh == 1 the query's shift row (both products)
-    const unsigned char* aQ0 = hh == 0 ? imgQ + r * 8 : imgS + r * 16;
-    const unsigned char* aQ1 = hh == 0 ? imgQ + r * 8 : imgS + r * 16 + 8;
-    const unsigned char* aD0 = hh == 0 ? imgD + r * 8 : imgS + r * 16;
-    const unsigned char* aD1 = hh == 0 ? cb + CB_ZERO : imgS + r * 16 + 8;
-    const unsigned char* aQt = tr_ptr(imgQ, cb, lane, false);
-    const unsigned char* aDt = tr_ptr(imgD, cb, lane, false);
-    const int d1step = hh == 0 ? 0 : 512;
-    auto tile = [&](const int off) {                          // (off counts 256-byte row tiles; the shift rows are twice as wide)
-      const int offa = hh == 0 ? off : 2 * off;
-      const bf16x8 fqr = frag2(aQ0 + offa, aQ1 + offa);
-      const bf16x8 fdr = frag2(aD0 + offa, aD1 + offa);
-      const bf16x8 fd0 = tr_frag(aDt + off), fd1 = tr_frag(aDt + off + 128);
-      const bf16x8 fq0 = tr_frag(aQt + off), fq1 = tr_frag(aQt + off + 128);
-      f32x16 s = mfma_bf16(fqr, fkB, (f32x16)(0.f));          // S'[q][k] = c q.k - lse[q]: rows = queries, columns = keys
-      f32x16 dp = mfma_bf16(fdr, fvB, (f32x16)(0.f));         // dP'[q][k] = dO[q] . V[k] - delta[q]
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        s[reg] = __builtin_amdgcn_exp2f(s[reg]);
-        dp[reg] *= s[reg];
-      }
-      av = mfma_bf16(fd0, pack8(s, 0), av);                   // dV^T[d][k] += dO^T[d][q] P[q][k]
-      av = mfma_bf16(fd1, pack8(s, 1), av);
-      ak = mfma_bf16(fq0, pack8(dp, 0), ak);                  // dK^T[d][k] += Q^T[d][q] dS[q][k]
-      ak = mfma_bf16(fq1, pack8(dp, 1), ak);
-    };
     const int ntq = (n + 31) >> 5, t0 = split * ntq / nsplit, t1 = (split + 1) * ntq / nsplit;
-    aQ0 += t0 * astep; aQ1 += t0 * astep; aD0 += t0 * astep; aD1 += t0 * d1step; aQt += t0 * tstep; aDt += t0 * tstep;
+    QdTile p = qd_tile(smem_attn + (st & 1) * ATT_QD_IMG, cb, lane, t0);
     for (int t = t0; t < t1; ++t) {
-      tile(0);
-      aQ0 += astep; aQ1 += astep; aD0 += astep; aD1 += d1step; aQt += tstep; aDt += tstep;
+      bwd_tile_qk(ak, av, p, fkB, fvB, [] {});
+      p = p.at(1);
     }
-    if (nsplit > 1 && ch == nch - 1) {                        // (uniform over the workgroup)
-      float* mine = red + ((long)wave * 32 + r) * 8;
-      if (split > 0 && hh == 0) {
-        *reinterpret_cast<f32x4*>(mine) = (f32x4){ak[0], ak[1], ak[2], ak[3]};
-        *reinterpret_cast<f32x4*>(mine + 4) = (f32x4){av[0], av[1], av[2], av[3]};
-      }
-      __syncthreads();
-      if (split == 0 && hh == 0) {
-        for (int sp = 1; sp < nsplit; ++sp) {
-          const float* o2 = red + ((long)(sp * nkb + kbw) * 32 + r) * 8;
-          const f32x4 pk = *reinterpret_cast<const f32x4*>(o2), pv = *reinterpret_cast<const f32x4*>(o2 + 4);
-          ak[0] += pk[0]; ak[1] += pk[1]; ak[2] += pk[2]; ak[3] += pk[3];
-          av[0] += pv[0]; av[1] += pv[1]; av[2] += pv[2]; av[3] += pv[3];
-        }
-      }
-    }
+    if (nsplit > 1 && ch == nch - 1)                          // (uniform over the workgroup)
+      dkv_exchange(ak, av, red + ((long)wave * 32 + r) * 8, split > 0 && hh == 0, red + ((long)(nkb + kbw) * 32 + r) * 8, nkb * 32 * 8,
+                   nsplit - 1, split == 0 && hh == 0);
     if (ch == nch - 1 && hh == 0 && kok && split == 0) {
-      bf16x4 ok4, ov4;
-      ok4[0] = (bf16)(ak[0] * scale); ok4[1] = (bf16)(ak[1] * scale); ok4[2] = (bf16)(ak[2] * scale); ok4[3] = (bf16)(ak[3] * scale);
-      ov4[0] = (bf16)av[0]; ov4[1] = (bf16)av[1]; ov4[2] = (bf16)av[2]; ov4[3] = (bf16)av[3];
-      *reinterpret_cast<bf16x4*>(dk + krow + h * 4) = ok4;
-      *reinterpret_cast<bf16x4*>(dv + krow + h * 4) = ov4;
+      store4(dk + krow + h * 4, ak[0], ak[1], ak[2], ak[3], scale);
+      store4(dv + krow + h * 4, av[0], av[1], av[2], av[3], 1.f);
     }
     if (st + 1 < nst) {
       stage_write(st + 1, nn);
@@ -708,35 +743,24 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_dkv_mfma_kernel(bf16* dk, bf1
 // (A first version gave each wave its own key block and added the dQ^T tiles into an LDS accumulator: ds_add_f32 costs ~64 cycles per
 // wave instruction, 4 per tile -- 1.66 ms instead of 0.68 without the adds.)  delta is computed while the head's dO / out rows are staged.
 constexpr int MG_WAVES = 4, MG_TPW = ATT_HS / 32 / MG_WAVES;  // query tiles per wave
-constexpr int MG_IMG = 2 * ATT_IMG + ATT_HS * 16;            // Q | dO | shifts of one head
 constexpr int MG_RED = 2 * (MG_WAVES - 1) * 32 * 8 * 4;      // dK | dV partial sums of waves 1-3, two buffers
-constexpr int MG_LDS = MG_IMG + MG_RED + MG_WAVES * 4096 + MG_WAVES * 256 + ATT_CONST;
+constexpr int MG_LDS = ATT_QD_IMG + MG_RED + MG_WAVES * 4096 + MG_WAVES * 256 + ATT_CONST;
 DEVI void wave_lds_fence() {                                 // (same wave: the LDS keeps the order; this only stops the compiler)
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-DEVI bf16x8 tr_pair(const unsigned char* p0, const unsigned char* p1) {
-  typedef __attribute__((ext_vector_type(4))) short s16x4;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  typedef __attribute__((address_space(3))) s16x4* lds_p;
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p0));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p1));
-  return __builtin_bit_cast(bf16x8, (s16x8)__builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
 __global__ __launch_bounds__(256, 2) void attn_bwd_merged_kernel(bf16* dq, bf16* dk, bf16* dv, const bf16* dout, const bf16* out,
                                                                 const bf16* q, const bf16* k, const bf16* v, const float* lse, int Sq,
                                                                 int Skv, int H, int hpw, float scale, float c) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_attn[];
-  unsigned char* imgQ = smem_attn;
-  unsigned char* imgD = imgQ + ATT_IMG;
-  unsigned char* imgS = imgD + ATT_IMG;
-  float* red = reinterpret_cast<float*>(smem_attn + MG_IMG);  // [2][3 waves][32 keys][8]
+  unsigned char* img = smem_attn;                             // the head's Q | dO | shift image
+  float* red = reinterpret_cast<float*>(smem_attn + ATT_QD_IMG);  // [2][3 waves][32 keys][8]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
-  unsigned char* dst = smem_attn + MG_IMG + MG_RED + wave * 4096;          // this wave's two dS^T tiles [32 keys][32 queries] bf16
-  unsigned char* kim = smem_attn + MG_IMG + MG_RED + MG_WAVES * 4096 + wave * 256;  // this wave's copy of the pass's K rows [32][8 B]
-  unsigned char* cb = smem_attn + MG_IMG + MG_RED + MG_WAVES * 4096 + MG_WAVES * 256;
+  unsigned char* dst = smem_attn + ATT_QD_IMG + MG_RED + wave * 4096;      // this wave's two dS^T tiles [32 keys][32 queries] bf16
+  unsigned char* kim = smem_attn + ATT_QD_IMG + MG_RED + MG_WAVES * 4096 + wave * 256;  // this wave's copy of the pass's K rows [32][8 B]
+  unsigned char* cb = smem_attn + ATT_QD_IMG + MG_RED + MG_WAVES * 4096 + MG_WAVES * 256;
   const int b = blockIdx.y, E = H * 4;
   const_block(cb, tid);
   const int Sq32 = (Sq + 31) & ~31, ntq = Sq32 >> 5;
@@ -756,14 +780,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_merged_kernel(bf16* dq, bf16*
       const int row = 16 * s2 + 8 * hh + qp + 4 * j, chunk = 4 * (g16 & 1) + p4;
       roff[s2][j] = row * 64 + ((chunk ^ (row & 7)) << 3);
     }
-  // A-fragment pointers of this wave's FIRST tile (lanes hh == 0: the Q / dO row; lanes hh == 1: the query's shift row)
-  const unsigned char* bQ0 = (hh == 0 ? imgQ + r * 8 : imgS + r * 16) + t0w * (hh == 0 ? 256 : 512);
-  const unsigned char* bQ1 = (hh == 0 ? imgQ + r * 8 : imgS + r * 16 + 8) + t0w * (hh == 0 ? 256 : 512);
-  const unsigned char* bD0 = (hh == 0 ? imgD + r * 8 : imgS + r * 16) + t0w * (hh == 0 ? 256 : 512);
-  const unsigned char* bD1 = hh == 0 ? cb + CB_ZERO : imgS + r * 16 + 8 + t0w * 512;
-  const unsigned char* bQt = tr_ptr(imgQ, cb, lane, false) + (p4 == 0 ? t0w * 256 : 0);
-  const unsigned char* bDt = tr_ptr(imgD, cb, lane, false) + (p4 == 0 ? t0w * 256 : 0);
-  const int astep = hh == 0 ? 256 : 512, d1step = hh == 0 ? 0 : 512, tstep = p4 == 0 ? 256 : 0;
+  const QdTile first = qd_tile(img, cb, lane, t0w);           // this wave's FIRST tile
   int parity = 0;
   for (int hi = 0; hi < hpw; ++hi) {
     const int h = blockIdx.x * hpw + hi;
@@ -771,21 +788,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_merged_kernel(bf16* dq, bf16*
     __syncthreads();                                          // the previous head's sweeps are done
     for (int rr = tid; rr < Sq32; rr += 256) {
       uint2 wq = make_uint2(0, 0), wd = make_uint2(0, 0);
-      float ls = 1.0e4f, dl = 0.f;                            // queries past Sq: p = exp2(-1e4) = 0
+      float ls = LSE_PAST_SQ, dl = 0.f;
       if (rr < Sq) {
         const long ro = ((long)b * Sq + rr) * E + h * 4;
         wq = *reinterpret_cast<const uint2*>(q + ro);
         wd = *reinterpret_cast<const uint2*>(dout + ro);
-        const bf16x4 a = __builtin_bit_cast(bf16x4, wd), o4 = *reinterpret_cast<const bf16x4*>(out + ro);
-        dl = (float)a[0] * (float)o4[0] + (float)a[1] * (float)o4[1] + (float)a[2] * (float)o4[2] + (float)a[3] * (float)o4[3];
-        ls = lse[((long)b * H + h) * Sq + rr] * 1.4426950408889634f;
+        dl = delta4(__builtin_bit_cast(bf16x4, wd), *reinterpret_cast<const bf16x4*>(out + ro));
+        ls = lse[((long)b * H + h) * Sq + rr] * LOG2E;
       }
-      *reinterpret_cast<uint2*>(imgQ + rr * 8) = wq;
-      *reinterpret_cast<uint2*>(imgD + rr * 8) = wd;
-      const bf16x8 sa = shift_frag(-ls, 0);
-      bf16x8 w = shift_frag(-dl, 4);
-      w[0] = sa[0]; w[1] = sa[1];
-      *reinterpret_cast<bf16x8*>(imgS + rr * 16) = w;
+      qd_row_write(img, rr, wq, wd, ls, dl);
     }
     __syncthreads();
     float dqa[MG_TPW][4];
@@ -821,24 +832,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_merged_kernel(bf16* dq, bf16*
       for (int j = 0; j < MG_TPW; ++j) {
         if (t0w + j < ntq) {                                  // (uniform over the wave)
           wave_lds_fence();                                   // iteration j - 1 wrote buffer (j - 1) & 1 and read buffer j & 1
-          const bf16x8 fqr = frag2(bQ0 + j * astep, bQ1 + j * astep);
-          const bf16x8 fdr = frag2(bD0 + j * astep, bD1 + j * d1step);
-          const bf16x8 fd0 = tr_frag(bDt + j * tstep), fd1 = tr_frag(bDt + j * tstep + 128);
-          const bf16x8 fq0 = tr_frag(bQt + j * tstep), fq1 = tr_frag(bQt + j * tstep + 128);
-          f32x16 s = mfma_bf16(fqr, fkB, (f32x16)(0.f));      // S'[q][k] = c q.k - lse[q]: rows = queries, columns = keys
-          f32x16 dp = mfma_bf16(fdr, fvB, (f32x16)(0.f));     // dP'[q][k] = dO[q] . V[k] - delta[q]
-          if (j > 0) dq_part(j - 1);
-#pragma unroll
-          for (int reg = 0; reg < 16; ++reg) {
-            s[reg] = __builtin_amdgcn_exp2f(s[reg]);
-            dp[reg] *= s[reg];
-          }
-          const bf16x8 ds0 = pack8(dp, 0), ds1 = pack8(dp, 1);
-          av = mfma_bf16(fd0, pack8(s, 0), av);               // dV^T[d][k] += dO^T[d][q] P[q][k]
-          av = mfma_bf16(fd1, pack8(s, 1), av);
-          ak = mfma_bf16(fq0, ds0, ak);                       // dK^T[d][k] += Q^T[d][q] dS[q][k]
-          ak = mfma_bf16(fq1, ds1, ak);
-          const u32x4 w0 = __builtin_bit_cast(u32x4, ds0), w1 = __builtin_bit_cast(u32x4, ds1);
+          const DsFrags ds = bwd_tile_qk(ak, av, first.at(j), fkB, fvB, [&] { if (j > 0) dq_part(j - 1); });
+          const u32x4 w0 = __builtin_bit_cast(u32x4, ds.s0), w1 = __builtin_bit_cast(u32x4, ds.s1);
           unsigned char* dw = dst + (j & 1) * 2048;           // dS -> LDS (key-major), read back transposed in the next iteration
           *reinterpret_cast<u32x2*>(dw + woff[0]) = (u32x2){w0.x, w0.y};
           *reinterpret_cast<u32x2*>(dw + woff[1]) = (u32x2){w0.z, w0.w};
@@ -853,37 +848,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_merged_kernel(bf16* dq, bf16*
         for (int j = 0; j < MG_TPW; ++j) if (j == nj - 1) dq_part(j);
       }
       // dK / dV of the pass: the four waves' partial sums meet in LDS (buffer `parity`: the previous pass's may still be read)
-      float* mine = red + ((long)(parity * (MG_WAVES - 1) + wave - 1) * 32 + r) * 8;
-      if (wave > 0 && hh == 0) {
-        *reinterpret_cast<f32x4*>(mine) = (f32x4){ak[0], ak[1], ak[2], ak[3]};
-        *reinterpret_cast<f32x4*>(mine + 4) = (f32x4){av[0], av[1], av[2], av[3]};
+      float* slot0 = red + ((long)(parity * (MG_WAVES - 1)) * 32 + r) * 8;
+      const bool sum = wave == 0 && hh == 0 && kok;
+      dkv_exchange(ak, av, slot0 + (wave - 1) * 32 * 8, wave > 0 && hh == 0, slot0, 32 * 8, MG_WAVES - 1, sum);
+      if (sum) {
+        store4(dk + krow, ak[0], ak[1], ak[2], ak[3], scale);
+        store4(dv + krow, av[0], av[1], av[2], av[3], 1.f);
       }
-      __syncthreads();
-      if (wave == 0 && hh == 0 && kok) {
-#pragma unroll
-        for (int w2 = 0; w2 < MG_WAVES - 1; ++w2) {
-          const float* o2 = red + ((long)(parity * (MG_WAVES - 1) + w2) * 32 + r) * 8;
-          const f32x4 pk = *reinterpret_cast<const f32x4*>(o2), pv = *reinterpret_cast<const f32x4*>(o2 + 4);
-          ak[0] += pk[0]; ak[1] += pk[1]; ak[2] += pk[2]; ak[3] += pk[3];
-          av[0] += pv[0]; av[1] += pv[1]; av[2] += pv[2]; av[3] += pv[3];
-        }
-        bf16x4 ok4, ov4;
-        ok4[0] = (bf16)(ak[0] * scale); ok4[1] = (bf16)(ak[1] * scale); ok4[2] = (bf16)(ak[2] * scale); ok4[3] = (bf16)(ak[3] * scale);
-        ov4[0] = (bf16)av[0]; ov4[1] = (bf16)av[1]; ov4[2] = (bf16)av[2]; ov4[3] = (bf16)av[3];
-        *reinterpret_cast<bf16x4*>(dk + krow) = ok4;
-        *reinterpret_cast<bf16x4*>(dv + krow) = ov4;
-      }
-      parity ^= 1;                                            // (one barrier per pass: the other buffer is free again two passes later)
+      parity ^= 1;                                           // (one barrier per pass: the other buffer is free again two passes later)
     }
     // dq of this wave's query tiles, straight from the registers
 #pragma unroll
     for (int j = 0; j < MG_TPW; ++j) {
       const int qq = (t0w + j) * 32 + r;
-      if (hh == 0 && qq < Sq) {
-        bf16x4 o4;
-        o4[0] = (bf16)(dqa[j][0] * scale); o4[1] = (bf16)(dqa[j][1] * scale); o4[2] = (bf16)(dqa[j][2] * scale); o4[3] = (bf16)(dqa[j][3] * scale);
-        *reinterpret_cast<bf16x4*>(dq + ((long)b * Sq + qq) * E + h * 4) = o4;
-      }
+      if (hh == 0 && qq < Sq) store4(dq + ((long)b * Sq + qq) * E + h * 4, dqa[j][0], dqa[j][1], dqa[j][2], dqa[j][3], scale);
     }
   }
 }
@@ -897,29 +875,23 @@ static int attn_force_slow() {                                // (tests: the onl
   return e && atoi(e) != 0;
 }
 
-static void attn_mfma_attrs() {                              // (the dk / dv kernel's two buffers are 64 KB + the constant block)
-  static unsigned long long done = 0;
-  if (!hdmoe_first_on_device(done)) return;
-  (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * ATT_KV_BUF + ATT_CONST + 8 * 32 * 8 * 4);
-}
+// the one place where the runtime `bias != nullptr` becomes the kernels' template argument BIAS
+#define BIAS_SWITCH(bias, ...)                                  \
+  if (bias) { constexpr bool BIAS = true; __VA_ARGS__; }       \
+  else { constexpr bool BIAS = false; __VA_ARGS__; }
 
 template <typename T, int D>
 int attn_fwd_launch(void* out, float* lse, const void* q, const void* k, const void* v, const float* bias, int B, int Sq, int Skv,
                     int H, int Sb, hipStream_t st) {
   if constexpr (sizeof(T) == 2 && D == 4) {
     if (!bias && attn_mfma_ok(H, out, q, k, v)) {
-      const size_t lds = 4 * ATT_IMG + ATT_CONST;
-      attn_mfma_attrs();
-      hipLaunchKernelGGL(attn_fwd_mfma_kernel, dim3(cdiv(Sq, 256), B), dim3(512), lds, st, (bf16*)out, lse, (const bf16*)q, (const bf16*)k,
-                         (const bf16*)v, Sq, Skv, H, 1.4426950408889634f / sqrtf((float)D), attn_force_slow());
+      hipLaunchKernelGGL(attn_fwd_mfma_kernel, dim3(cdiv(Sq, 256), B), dim3(512), ATT_KV_LDS, st, (bf16*)out, lse, (const bf16*)q,
+                         (const bf16*)k, (const bf16*)v, Sq, Skv, H, LOG2E / sqrtf((float)D), attn_force_slow());
       return hdmoe_launch_status();
     }
   }
-  dim3 grid(cdiv(Sq, TQ), H, B);
-  if (bias) hipLaunchKernelGGL((attn_fwd_kernel<T, D, true>), grid, dim3(TQ), 0, st, (T*)out, lse, (const T*)q, (const T*)k, (const T*)v, bias, Sq,
-                     Skv, H, Sb, 1.f / sqrtf((float)D));
-  else hipLaunchKernelGGL((attn_fwd_kernel<T, D, false>), grid, dim3(TQ), 0, st, (T*)out, lse, (const T*)q, (const T*)k, (const T*)v, bias, Sq,
-                     Skv, H, Sb, 1.f / sqrtf((float)D));
+  BIAS_SWITCH(bias, hipLaunchKernelGGL((attn_fwd_kernel<T, D, BIAS>), dim3(cdiv(Sq, TQ), H, B), dim3(TQ), 0, st, (T*)out, lse, (const T*)q,
+                                       (const T*)k, (const T*)v, bias, Sq, Skv, H, Sb, 1.f / sqrtf((float)D)))
   return hdmoe_launch_status();
 }
 template <typename T, int D>
@@ -929,33 +901,33 @@ int attn_bwd_launch(void* dq, void* dk, void* dv, float* dbias, float* delta, co
   const float scale = 1.f / sqrtf((float)D);
   if constexpr (sizeof(T) == 2 && D == 4) {
     if (!bias && attn_mfma_ok(H, dq, dk, dv, dout) && attn_mfma_ok(H, out, q, k, v)) {
-      const float c = scale * 1.4426950408889634f;
-      static const bool merged = !(getenv("HDMOE_ATTN_BWD_MERGED") && atoi(getenv("HDMOE_ATTN_BWD_MERGED")) == 0);
-      if (merged && Sq <= ATT_HS) {                           // one evaluation of the probabilities for dq, dk and dv
+      const float c = scale * LOG2E;
+      if (Sq <= ATT_HS) {                                     // one evaluation of the probabilities for dq, dk and dv
         static unsigned long long attr = 0;
-        if (hdmoe_first_on_device(attr)) { (void)hipFuncSetAttribute((const void*)attn_bwd_merged_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MG_LDS); }
+        if (hdmoe_first_on_device(attr))
+          (void)hipFuncSetAttribute((const void*)attn_bwd_merged_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MG_LDS);
         int hg = (int)cdiv(512, B); if (hg > H) hg = H; if (hg < 1) hg = 1;
         const int hpw = (int)cdiv(H, hg);
         hipLaunchKernelGGL(attn_bwd_merged_kernel, dim3(cdiv(H, hpw), B), dim3(64 * MG_WAVES), MG_LDS, st, (bf16*)dq, (bf16*)dk, (bf16*)dv,
                            (const bf16*)dout, (const bf16*)out, (const bf16*)q, (const bf16*)k, (const bf16*)v, lse, Sq, Skv, H, hpw, scale, c);
         return hdmoe_launch_status();
       }
-      const size_t lds_q = 4 * ATT_IMG + ATT_CONST, lds_kv = 2 * ATT_KV_BUF + ATT_CONST + 8 * 32 * 8 * 4;
       const int nb32 = (int)cdiv(Skv, 32), nkb = nb32 >= 5 ? 8 : (nb32 >= 3 ? 4 : nb32);
-      attn_mfma_attrs();
-      hipLaunchKernelGGL(attn_bwd_dq_mfma_kernel, dim3(cdiv(Sq, 256), B), dim3(512), lds_q, st, (bf16*)dq, delta, (const bf16*)dout,
+      hipLaunchKernelGGL(attn_bwd_dq_mfma_kernel, dim3(cdiv(Sq, 256), B), dim3(512), ATT_KV_LDS, st, (bf16*)dq, delta, (const bf16*)dout,
                          (const bf16*)out, (const bf16*)q, (const bf16*)k, (const bf16*)v, lse, Sq, Skv, H, scale, c);
-      hipLaunchKernelGGL(attn_bwd_dkv_mfma_kernel, dim3(cdiv(Skv, 32 * nkb), B), dim3(512), lds_kv, st, (bf16*)dk, (bf16*)dv, (const bf16*)dout,
-                         (const bf16*)q, (const bf16*)k, (const bf16*)v, lse, delta, Sq, Skv, H, scale, c, nkb);
+      static unsigned long long attr_dkv = 0;                 // (the dk / dv kernel's two images are 64 KB + the constant block)
+      if (hdmoe_first_on_device(attr_dkv))
+        (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_DKV_LDS);
+      hipLaunchKernelGGL(attn_bwd_dkv_mfma_kernel, dim3(cdiv(Skv, 32 * nkb), B), dim3(512), ATT_DKV_LDS, st, (bf16*)dk, (bf16*)dv,
+                         (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v, lse, delta, Sq, Skv, H, scale, c, nkb);
       return hdmoe_launch_status();
     }
   }
-#define ATTN_BWD(BB)                                                                                                                  \
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, D, BB>), dim3(cdiv(Sq, TQ), H, B), dim3(TQ), 0, st, (T*)dq, delta, dbias, (const T*)dout,  \
-                     (const T*)out, (const T*)q, (const T*)k, (const T*)v, lse, bias, Sq, Skv, H, Sb, scale);                          \
-  hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, D, BB>), dim3(cdiv(Skv, TQ), H, B), dim3(TQ), 0, st, (T*)dk, (T*)dv, (const T*)dout,      \
-                     (const T*)q, (const T*)k, (const T*)v, lse, delta, bias, Sq, Skv, H, Sb, scale);
-  if (bias) { ATTN_BWD(true) } else { ATTN_BWD(false) }
+  BIAS_SWITCH(bias,
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<T, D, BIAS>), dim3(cdiv(Sq, TQ), H, B), dim3(TQ), 0, st, (T*)dq, delta, dbias, (const T*)dout,
+                       (const T*)out, (const T*)q, (const T*)k, (const T*)v, lse, bias, Sq, Skv, H, Sb, scale);
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, D, BIAS>), dim3(cdiv(Skv, TQ), H, B), dim3(TQ), 0, st, (T*)dk, (T*)dv, (const T*)dout,
+                       (const T*)q, (const T*)k, (const T*)v, lse, delta, bias, Sq, Skv, H, Sb, scale))
   if (bias && dbias) {
     const long nthreads = (long)H * Sq * Skv;
     hipLaunchKernelGGL((attn_dbias_kernel<T, D>), dim3(cdiv(nthreads, 256)), dim3(256), 0, st, dbias, (const T*)dout, (const T*)q, (const T*)k,
@@ -1042,10 +1014,7 @@ __global__ __launch_bounds__(64) void attn_rag_fwd_kernel(T* out, float* lse, co
   const int len = g >= 0 ? rg.len[g] : 0;
   float* sk = sm_rag;
   float* sv = sm_rag + len * D;
-  for (int e = threadIdx.x; e < len * D; e += 64) {
-    const long src = ((long)r * Sp + e / D) * E + h * D + e % D;
-    sk[e] = to_f(k[src]); sv[e] = to_f(v[src]);
-  }
+  stage_heads<64, D>(sk, sv, k, v, (long)r * Sp, len, E, h, 1.f);
   __syncthreads();
   for (int i = threadIdx.x; i < Sp; i += 64) {
     const long row = ((long)r * Sp + i) * E + h * D;
@@ -1092,10 +1061,8 @@ __global__ __launch_bounds__(64) void attn_rag_bwd_kernel(T* dq, T* dk, T* dv, f
   float* sdo = sv + len * D;
   float* sl = sdo + len * D;                                 // lse
   float* sd = sl + len;                                      // delta
-  for (int e = threadIdx.x; e < len * D; e += 64) {
-    const long src = ((long)r * Sp + e / D) * E + h * D + e % D;
-    sq[e] = to_f(q[src]) * scale; sk[e] = to_f(k[src]); sv[e] = to_f(v[src]); sdo[e] = to_f(dout[src]);
-  }
+  stage_heads<64, D>(sq, sdo, q, dout, (long)r * Sp, len, E, h, scale);
+  stage_heads<64, D>(sk, sv, k, v, (long)r * Sp, len, E, h, 1.f);
   for (int i = threadIdx.x; i < len; i += 64) {
     const long row = ((long)r * Sp + i) * E + h * D;
     float dl = 0.f;
@@ -1114,8 +1081,7 @@ __global__ __launch_bounds__(64) void attn_rag_bwd_kernel(T* dq, T* dk, T* dv, f
       const float* brow = rg.bias[g] + ((long)h * rg.sb[g] + i) * rg.sb[g];
       for (int j = 0; j < len; ++j) {
         float s = brow[j], dp = 0.f;
-#pragma unroll
-        for (int d = 0; d < D; ++d) { s += sq[i * D + d] * sk[j * D + d]; dp += sdo[i * D + d] * sv[j * D + d]; }
+        dot2<D>(s, dp, sq + i * D, sk + j * D, sdo + i * D, sv + j * D);
         const float ds = __expf(s - sl[i]) * (dp - sd[i]);
 #pragma unroll
         for (int d = 0; d < D; ++d) acc[d] += ds * sk[j * D + d];
@@ -1133,8 +1099,7 @@ __global__ __launch_bounds__(64) void attn_rag_bwd_kernel(T* dq, T* dk, T* dv, f
       const float* bcol = rg.bias[g] + (long)h * rg.sb[g] * rg.sb[g] + j;
       for (int i = 0; i < len; ++i) {
         float s = bcol[(long)i * rg.sb[g]], dp = 0.f;
-#pragma unroll
-        for (int d = 0; d < D; ++d) { s += sq[i * D + d] * sk[j * D + d]; dp += sdo[i * D + d] * sv[j * D + d]; }
+        dot2<D>(s, dp, sq + i * D, sk + j * D, sdo + i * D, sv + j * D);
         const float p = __expf(s - sl[i]);
         const float ds = p * (dp - sd[i]);
 #pragma unroll
@@ -1194,12 +1159,16 @@ constexpr size_t rag_lds_bytes(int ml, int D, bool bwd) {
   return (bwd ? (size_t)4 * ml * D + (size_t)2 * ml : (size_t)2 * ml * D) * sizeof(float);
 }
 constexpr int rag_max_len(int D, bool bwd) { return (int)(RAG_LDS_LIMIT / rag_lds_bytes(1, D, bwd)); }   // rag_lds_bytes is linear in ml
+static inline int rag_longest(const RagA& rg) {
+  int ml = 0;
+  for (int g = 0; g < rg.ng; ++g) ml = max(ml, rg.len[g]);
+  return ml;
+}
 
 template <typename T, int D>
 int attn_rag_fwd_launch(void* out, float* lse, const void* q, const void* k, const void* v, const RagA& rg, int R, int Sp, int H,
                         hipStream_t st) {
-  int ml = 0;
-  for (int g = 0; g < rg.ng; ++g) ml = max(ml, rg.len[g]);
+  const int ml = rag_longest(rg);
   if (ml > rag_max_len(D, false)) return HDMOE_EINVAL;
   const size_t lds = rag_lds_bytes(ml, D, false);
   hipLaunchKernelGGL((attn_rag_fwd_kernel<T, D>), dim3(R, H), dim3(64), lds, st, (T*)out, lse, (const T*)q, (const T*)k, (const T*)v, rg, Sp, H,
@@ -1209,8 +1178,7 @@ int attn_rag_fwd_launch(void* out, float* lse, const void* q, const void* k, con
 template <typename T, int D>
 int attn_rag_bwd_launch(void* dq, void* dk, void* dv, float* delta, const void* dout, const void* out, const void* q, const void* k,
                         const void* v, const float* lse, const RagA& rg, bool want_dbias, int R, int Sp, int H, hipStream_t st) {
-  int ml = 0;
-  for (int g = 0; g < rg.ng; ++g) ml = max(ml, rg.len[g]);
+  const int ml = rag_longest(rg);
   if (ml > rag_max_len(D, true)) return HDMOE_EINVAL;
   const size_t lds = rag_lds_bytes(ml, D, true);
   const float scale = 1.f / sqrtf((float)D);
@@ -1240,9 +1208,7 @@ extern "C" {
 int hdmoe_attn_fwd(void* out, float* lse, const void* q, const void* k, const void* v, const float* bias, int B, int Sq, int Skv,
                    int H, int D, int Sb, int dtype, hipStream_t stream) {
   if (B < 1 || B > 65535 || H < 1 || H > 65535 || Sq < 1 || Skv < 1 || (bias && (Sb < Sq || Sb < Skv))) return HDMOE_EINVAL;
-  if (dtype == HDMOE_F32) { D_SWITCH(D, return (attn_fwd_launch<float, DD>(out, lse, q, k, v, bias, B, Sq, Skv, H, Sb, stream))) }
-  if (dtype == HDMOE_BF16) { D_SWITCH(D, return (attn_fwd_launch<bf16, DD>(out, lse, q, k, v, bias, B, Sq, Skv, H, Sb, stream))) }
-  return HDMOE_EDTYPE;
+  DT_SWITCH(dtype, D_SWITCH(D, return (attn_fwd_launch<T, DD>(out, lse, q, k, v, bias, B, Sq, Skv, H, Sb, stream))))
 }
 
 // delta: [B][H][Sq] fp32 scratch; dbias: [H][Sb][Sb] fp32 accumulator (caller zeroes) or null
@@ -1250,9 +1216,7 @@ int hdmoe_attn_bwd(void* dq, void* dk, void* dv, float* dbias, float* delta, con
                    const void* k, const void* v, const float* lse, const float* bias, int B, int Sq, int Skv, int H, int D, int Sb,
                    int dtype, hipStream_t stream) {
   if (B < 1 || B > 65535 || H < 1 || H > 65535 || Sq < 1 || Skv < 1 || (bias && (Sb < Sq || Sb < Skv)) || (dbias && !bias)) return HDMOE_EINVAL;
-  if (dtype == HDMOE_F32) { D_SWITCH(D, return (attn_bwd_launch<float, DD>(dq, dk, dv, dbias, delta, dout, out, q, k, v, lse, bias, B, Sq, Skv, H, Sb, stream))) }
-  if (dtype == HDMOE_BF16) { D_SWITCH(D, return (attn_bwd_launch<bf16, DD>(dq, dk, dv, dbias, delta, dout, out, q, k, v, lse, bias, B, Sq, Skv, H, Sb, stream))) }
-  return HDMOE_EDTYPE;
+  DT_SWITCH(dtype, D_SWITCH(D, return (attn_bwd_launch<T, DD>(dq, dk, dv, dbias, delta, dout, out, q, k, v, lse, bias, B, Sq, Skv, H, Sb, stream))))
 }
 
 /* Longest row (largest lens[g]) hdmoe_attn_rag_fwd (backward == 0) / hdmoe_attn_rag_bwd (backward != 0) accept at head dim D;
@@ -1269,9 +1233,7 @@ int hdmoe_attn_rag_fwd(void* out, float* lse, const void* q, const void* k, cons
                        const int* lens, const int* sb, int ngroups, int R, int Sp, int H, int D, int dtype, hipStream_t stream) {
   RagA rg;
   if (R < 1 || H < 1 || H > 65535 || !mk_raga(rg, seg, lens, sb, bias, nullptr, ngroups, Sp, H)) return HDMOE_EINVAL;
-  if (dtype == HDMOE_F32) { D_SWITCH(D, return (attn_rag_fwd_launch<float, DD>(out, lse, q, k, v, rg, R, Sp, H, stream))) }
-  if (dtype == HDMOE_BF16) { D_SWITCH(D, return (attn_rag_fwd_launch<bf16, DD>(out, lse, q, k, v, rg, R, Sp, H, stream))) }
-  return HDMOE_EDTYPE;
+  DT_SWITCH(dtype, D_SWITCH(D, return (attn_rag_fwd_launch<T, DD>(out, lse, q, k, v, rg, R, Sp, H, stream))))
 }
 int hdmoe_attn_rag_bwd(void* dq, void* dk, void* dv, float* const* dbias, float* delta, const void* dout, const void* out,
                        const void* q, const void* k, const void* v, const float* lse, const float* const* bias, const int* seg,
@@ -1279,9 +1241,7 @@ int hdmoe_attn_rag_bwd(void* dq, void* dk, void* dv, float* const* dbias, float*
   RagA rg;
   if (R < 1 || H < 1 || H > 65535 || !mk_raga(rg, seg, lens, sb, bias, dbias, ngroups, Sp, H)) return HDMOE_EINVAL;
   const bool wd = dbias != nullptr;
-  if (dtype == HDMOE_F32) { D_SWITCH(D, return (attn_rag_bwd_launch<float, DD>(dq, dk, dv, delta, dout, out, q, k, v, lse, rg, wd, R, Sp, H, stream))) }
-  if (dtype == HDMOE_BF16) { D_SWITCH(D, return (attn_rag_bwd_launch<bf16, DD>(dq, dk, dv, delta, dout, out, q, k, v, lse, rg, wd, R, Sp, H, stream))) }
-  return HDMOE_EDTYPE;
+  DT_SWITCH(dtype, D_SWITCH(D, return (attn_rag_bwd_launch<T, DD>(dq, dk, dv, delta, dout, out, q, k, v, lse, rg, wd, R, Sp, H, stream))))
 }
 
 // out [H][S][S] <- table [H][S0][S0] (fwd);  dtable [H][S0][S0] (caller zeroes) += resize^T(dout [H][S][S]) (bwd)

@@ -1,6 +1,6 @@
-"""dev tool: the MFMA attention kernels (csrc/attention.hip) at the model's two shapes -- max error against an fp64 softmax on the
-bf16-rounded operands (fast shift, forced online maximum, and an input that overflows the fast shift), then kernel times under
-hipGraph replay.     python tools/attn_bench.py [--time-only]"""
+"""dev tool: the MFMA attention kernels (csrc/attention.hip) -- max error against an fp64 softmax on the bf16-rounded operands (fast
+shift, forced online maximum, and an input that overflows the fast shift), then kernel times under hipGraph replay at the model's two
+shapes and at one with more than 1024 queries (the dq + dk/dv pair).     python tools/attn_bench.py [--time-only]"""
 import os, sys, math
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "heterogeneous-moe-for-diffusion-models_amd"), ROOT]
@@ -85,7 +85,7 @@ def timeit(B, Sq, Skv, H, iters=10):
         s.record(); gr.replay(); e.record(); torch.cuda.synchronize()
         res.append(1e3 * s.elapsed_time(e) / iters)
     exps = B * H * Sq * Skv
-    merged = Sq <= 1024 and os.environ.get("HDMOE_ATTN_BWD_MERGED", "1") != "0"        # one evaluation of the probabilities instead of two
+    merged = Sq <= 1024                                                               # one evaluation of the probabilities instead of two
     print(f"time B={B} Sq={Sq} Skv={Skv} H={H}: fwd {res[0]:7.1f} us ({exps / res[0] / 1e6:5.2f} Texp/s)   bwd ({'merged' if merged else 'dq + dk/dv'}) {res[1]:7.1f} us "
           f"({(1 if merged else 2) * exps / res[1] / 1e6:5.2f} Texp/s)", flush=True)
 
@@ -104,4 +104,5 @@ if __name__ == "__main__":
         print("ATTN ALL OK" if good else "ATTN FAILURES", flush=True)
     timeit(256, 1024, 1024, 8)
     timeit(256, 1024, 77, 8)
+    timeit(64, 2048, 2048, 8)                                             # more than 1024 queries: the dq + dk/dv pair
     sys.exit(0 if good else 1)
