@@ -1745,6 +1745,143 @@ def gate_mix(logits: Tensor, U: Tensor, A: Tensor):
     return _GateMixFn.apply(logits, U, A)
 
 
+# ---- fusion stage: the token-local chain in front of the first attention call, one launch per direction (csrc/fusion.hip)
+FUSION_FUSED = True                                     # False: always the unfused chain (axpby, scale_rows, three mp_conv)
+
+
+class _FusionInFn(torch.autograd.Function):
+    """(query, ctx, q, k, v) = hdmoe_fusion_in_fwd(fu, fv, sw) with the prepared images of the weight-bank entries ``ents`` (q, k, v
+    projection); without ``sw`` query and ctx are fu and fv themselves.  The backward is one hdmoe_fusion_in_bwd launch for dfu, dfv
+    and dsw -- the gradient fan-in of query and ctx included -- and one weight-only launch per projection into the bank's slabs."""
+
+    @staticmethod
+    def forward(ctx, fu, fv, sw, ents, S, *weights):
+        ctx.set_materialize_grads(False)
+        rows = fu.numel() // 32
+        query, cx = (torch.empty_like(fu), torch.empty_like(fu)) if sw is not None else (None, None)
+        q, k, v = torch.empty_like(fu), torch.empty_like(fu), torch.empty_like(fu)
+        if call("hdmoe_fusion_in_fwd", fu, fv, sw, ents[0].wf, ents[1].wf, ents[2].wf, query, cx, q, k, v, rows, S, 32,
+                ents[0].alpha, ents[1].alpha, ents[2].alpha, BF16) != 0:
+            raise RuntimeError("hdmoe_fusion_in_fwd declined a call that ops.fusion_in admitted")
+        ctx.ents, ctx.bank, ctx.S, ctx.pool_ok = ents, _bank.ACTIVE, S, sw is not None and not sw.is_leaf
+        ctx.save_for_backward(fu, fv, *(() if sw is None else (sw, query, cx)))
+        STATS["fusion_in"] += 1
+        return (fu, fv, q, k, v) if sw is None else (query, cx, q, k, v)
+
+    @staticmethod
+    def backward(ctx, gquery, gctx, gq, gk, gv):
+        fu, fv, *rest = ctx.saved_tensors
+        sw, query, cx = rest if rest else (None, fu, fv)
+        ents, rows = ctx.ents, fu.numel() // 32
+        gq, gk, gv = (torch.zeros_like(fu) if g is None else _c(g) for g in (gq, gk, gv))
+        dfu, dfv = torch.empty_like(fu), torch.empty_like(fv)
+        dsw = None if sw is None else _zeros(sw.shape, torch.float32, sw.device, ctx.pool_ok)
+        if call("hdmoe_fusion_in_bwd", gq, gk, gv, _c(gquery), _c(gctx), fu, fv, sw, ents[0].wd, ents[1].wd, ents[2].wd, dfu, dfv, dsw,
+                rows, ctx.S, 32, ents[0].alpha, ents[1].alpha, ents[2].alpha, BF16) != 0:
+            raise RuntimeError("hdmoe_fusion_in_bwd declined a call whose forward ran fused")
+        if any(ctx.needs_input_grad[5:]):
+            # weight gradients on the weight-only kernel, straight into the bank's slabs (finished with every other layer's)
+            for ent, x, dy in zip(ents, (query, cx, cx), (gq, gk, gv)):
+                _bank_wgrad(ctx.bank, ent, x, dy, rows, 32, 32)
+        return (dfu, dfv, dsw, None, None) + (None,) * len(ents)
+
+
+def fusion_in(fu: Tensor, fv: Tensor, sw: Optional[Tensor], projs, gain: float = 1.0):
+    """The head of the fusion stage in one launch: query = fu + sw (fv - fu), ctx = fv - sw (fv - fu) (``sw``: (B,) float32, or None --
+    then query, ctx = fu, fv) and q, k, v = the three pointwise projections ``projs`` (weight tensors, plain ``gain``) of query, ctx,
+    ctx.  fu, fv: (B, S, 32).  Returns (query, ctx, q, k, v), or None outside the fused kernel's domain (bf16 rows of 32 channels,
+    16-byte aligned, every projection a ready weight-bank entry): the caller then runs the unfused ops."""
+    bank = _bank.ACTIVE
+    if not (FUSION_FUSED and _prof_ok() and bank is not None and fu.is_cuda and fu.ndim == 3 and fu.shape == fv.shape and fu.shape[-1] == 32
+            and fu.dtype == fv.dtype == torch.bfloat16 and fu.is_contiguous() and fv.is_contiguous()
+            and fu.data_ptr() % 16 == 0 and fv.data_ptr() % 16 == 0 and fu.numel() > 0):
+        return None
+    if sw is not None and not (sw.dtype == torch.float32 and sw.numel() == fu.shape[0] and sw.is_contiguous()):
+        return None
+    ws = f32_params(list(projs))
+    if not all(w.shape[0] == 32 and w.shape[1] == 32 and _kernel_hw(w) == (1, 1) for w in ws):
+        return None
+    ents = [bank.lookup([w], torch.bfloat16, float(gain), 1.0, True) for w in ws]      # (the key ops.mp_conv registers the layer under)
+    if any(e is None for e in ents):
+        return None
+    return _FusionInFn.apply(fu, fv, sw, ents, int(fu.shape[1]), *ws)
+
+
+def _bank_wgrad(bank, ent, x, dy, rows: int, I: int, O: int) -> None:
+    """Weight gradient of pointwise bank layer ``ent`` on the weight-only kernel, from x (rows, I) and dy (rows, O), into the bank's slab."""
+    _timed("conv_wgrad", lambda: _conv_record(x, None, 1, rows, O, I, [1], [1], wgrad_name="towg_bf16_kernel" if O <= 4 else "lwg_bf16_kernel"),
+           "hdmoe_conv_wgrad", x, dy, list(ent.G), None, 1, 1, 1, rows, 1, rows, I, I, O, 1, 0, [1], [1], [0], [0], BF16)
+    bank.note_backward(ent)
+
+
+class _FusionOutFn(torch.autograd.Function):
+    """(mixed, gate) = hdmoe_fusion_out_fwd(o2, a, U): out_proj of the text cross-attention with its residual, lerp_param, mp_cat, gate1,
+    mp_silu, gate2 and gate_mix.  ``ents``: the bank entries of out_proj, gate1, gate2; ``k`` = (alpha_o, beta_o, wa, wb).  The backward
+    is one hdmoe_fusion_out_bwd launch (do2, da, dU, dalpha) and one weight-only launch per layer."""
+
+    @staticmethod
+    def forward(ctx, o2, a, U, alpha_txt, ents, k, *weights):
+        ctx.set_materialize_grads(False)
+        rows = o2.numel() // 32
+        mixed = torch.empty_like(U)
+        a2 = g1 = s = cat = None
+        if any(ctx.needs_input_grad):                          # (else: inference, nothing is saved)
+            a2, g1, s = (torch.empty_like(U) for _ in range(3))
+            cat = torch.empty((rows, 64), dtype=U.dtype, device=U.device)
+        gate = torch.empty((*U.shape[:-1], 2), dtype=torch.float32, device=U.device)
+        consts = (*k, ents[1].alpha, ents[2].alpha)
+        if call("hdmoe_fusion_out_fwd", o2, a, U, alpha_txt, ents[0].wf, ents[1].wf, ents[2].wf, mixed, gate, a2, g1, cat, s, rows, 32,
+                *consts, BF16) != 0:
+            raise RuntimeError("hdmoe_fusion_out_fwd declined a call that ops.fusion_out admitted")
+        ctx.ents, ctx.bank, ctx.consts = ents, _bank.ACTIVE, consts
+        if a2 is not None:
+            ctx.save_for_backward(o2, a, U, alpha_txt, a2, g1, cat, s, gate)
+        STATS["fusion_out"] += 1
+        return mixed, gate
+
+    @staticmethod
+    def backward(ctx, dmixed, dgate):
+        o2, a, U, alpha_txt, a2, g1, cat, s, gate = ctx.saved_tensors
+        ents, rows = ctx.ents, o2.numel() // 32
+        dmixed = torch.zeros_like(U) if dmixed is None else _c(dmixed)
+        dgate = None if dgate is None else _f32(dgate)
+        do2, da, dU, dat, dg1 = torch.empty_like(o2), torch.empty_like(a), torch.empty_like(U), torch.empty_like(o2), torch.empty_like(o2)
+        dl = torch.empty((rows, 2), dtype=U.dtype, device=U.device)
+        direct = _direct(alpha_txt)
+        dal = alpha_txt.grad if direct else torch.zeros_like(alpha_txt)
+        if call("hdmoe_fusion_out_bwd", dmixed, dgate, gate, U, a2, g1, o2, a, alpha_txt, ents[0].wf, ents[0].wd, ents[1].wd, ents[2].wd,
+                do2, da, dU, dat, dg1, dl, dal, rows, 32, *ctx.consts, BF16) != 0:
+            raise RuntimeError("hdmoe_fusion_out_bwd declined a call whose forward ran fused")
+        if any(ctx.needs_input_grad[6:]):
+            _bank_wgrad(ctx.bank, ents[2], s, dl, rows, 32, 2)
+            _bank_wgrad(ctx.bank, ents[1], cat, dg1, rows, 64, 32)
+            _bank_wgrad(ctx.bank, ents[0], o2, dat, rows, 32, 32)
+        return (do2, da, dU, None if direct else dal, None, None) + (None,) * len(ents)
+
+
+def fusion_out(o2: Tensor, a: Tensor, U: Tensor, alpha_txt: Tensor, w_out: Tensor, alpha: float, beta: float, w_gate1: Tensor, w_gate2: Tensor,
+               gain: float = 1.0):
+    """The tail of the fusion stage in one launch: at = out_proj(o2) mixed with the residual ``a`` (alpha, beta as MP_Attention passes them to
+    mp_conv), a2 = lerp_param(a, at, alpha_txt), g = gate2(mp_silu(gate1(mp_cat(U, a2, 0.5)))), gate_mix(g, U, a2).  o2, a: (B, S, 32);
+    U: (B, H, W, 32).  Returns (mixed, gate) shaped like U, or None outside the fused kernel's domain: the caller then runs the ops."""
+    bank = _bank.ACTIVE
+    ts = (o2, a, U)
+    if not (FUSION_FUSED and _prof_ok() and bank is not None and U.is_cuda and U.shape[-1] == 32 and U.numel() > 0
+            and all(t.dtype == torch.bfloat16 and t.is_contiguous() and t.data_ptr() % 16 == 0 and t.numel() == U.numel() for t in ts)
+            and alpha_txt.dtype == torch.float32 and alpha_txt.numel() == 1):
+        return None
+    ws = f32_params([w_out, w_gate1, w_gate2])
+    if [tuple(w.shape[:2]) for w in ws] != [(32, 32), (32, 64), (2, 32)] or any(_kernel_hw(w) != (1, 1) for w in ws):
+        return None
+    ents = [bank.lookup([ws[0]], torch.bfloat16, float(gain), float(alpha), True), bank.lookup([ws[1]], torch.bfloat16, 1.0, 1.0, True),
+            bank.lookup([ws[2]], torch.bfloat16, 1.0, 1.0, True)]
+    if any(e is None for e in ents):
+        return None
+    c = math.sqrt(64 / 0.5)                                  # mp_cat(U, a2, 0.5) of two 32-channel tensors
+    k = (float(alpha), float(beta), c * 0.5 / math.sqrt(32), c * 0.5 / math.sqrt(32))
+    return _FusionOutFn.apply(o2, a, U, alpha_txt, ents, k, *ws)
+
+
 class _SoftmaxRowsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, scale):

@@ -220,7 +220,11 @@ class _HDMOEMBase(nn.Module):
     def _scaling(self, time_vec: Tensor, time_embed: Tensor, zeta, **kw):
         raise NotImplementedError
 
-    def _fusion_inputs(self, fu: Tensor, fv: Tensor, s_vit: Tensor, s_unet: Tensor, **kw):
+    def _fusion_swap(self, s_vit: Tensor, s_unet: Tensor, **kw) -> Optional[Tensor]:
+        """The per-sample query / context swap weights (B,), or None: query, context = U-Net features, ViT features."""
+        raise NotImplementedError
+
+    def _fusion_inputs(self, fu: Tensor, fv: Tensor, sw: Optional[Tensor]):
         raise NotImplementedError
 
     def _fwd(self, x: Tensor, time_vec: Tensor, text_emb: Tensor, Unet_router_mask: Tensor, Vit_router_mask: Tensor, zeta, **kw):
@@ -309,9 +313,22 @@ class _HDMOEMBase(nn.Module):
         B, H, W, C = out_u.shape
         fu = out_u.reshape(B, H * W, C)                                     # channel-last image == (B, S, C) tokens
         fv = out_v.reshape(B, H * W, C)
-        q, ctx = self._fusion_inputs(fu, fv, s_vit, s_unet, **kw)
-        a = self.cross_attn(query=q, context=ctx, gain_s=1.0, gain_t=1.0)
-        at = self.cross_attn_text(query=a, context=text_c, gain_s=1.0, gain_t=1.0)
+        sw = self._fusion_swap(s_vit, s_unet, **kw)
+        ca = self.cross_attn
+        # fusion inputs + the q / k / v projections in one launch (csrc/fusion.hip); None outside its domain: the op chain
+        head = None if ca.time_dependent else ops.fusion_in(fu, fv, sw, (ca.q_proj.weights, ca.k_proj.weights, ca.v_proj.weights), 1.0)
+        if head is not None:
+            a = ca._attend(*head, gain_s=1.0)
+        else:
+            q, ctx = self._fusion_inputs(fu, fv, sw)
+            a = ca(query=q, context=ctx, gain_s=1.0, gain_t=1.0)
+        cat = self.cross_attn_text
+        o2 = cat(query=a, context=text_c, gain_s=1.0, gain_t=1.0, core_only=True)
+        # everything behind the text attention in one launch (csrc/fusion.hip); None outside its domain: the op chain
+        tail = ops.fusion_out(o2, a, out_u, self.alpha_txt, cat.out_proj.weights, *cat._out_mix(), self.gate1.weights, self.gate2.weights, 1.0)
+        if tail is not None:
+            return self.output_proj._fwd(tail[0]), tail[1]
+        at = cat._project_out(o2, a, 1.0)
         a = ops.lerp_param(a, at, self.alpha_txt)                           # a + alpha_txt * (at - a)
         a_img = a.reshape(B, H, W, C)
         g = self.gate1._fwd(ops.mp_cat(out_u, a_img, 0.5))

@@ -23,8 +23,10 @@ class HDMOEM(_HDMOEMBase):
         sf = self.scaling_net(x=time_embed, zeta=zeta)                       # (B, 2): [:, 0] ViT, [:, 1] U-Net
         return sf[:, 0], sf[:, 1], sf
 
-    def _fusion_inputs(self, fu, fv, s_vit, s_unet, alpha_routing=10):
-        sw = ops.sigmoid(ops.axpby(s_vit, s_unet, 1.0, -1.0), float(alpha_routing))     # (B,)
+    def _fusion_swap(self, s_vit, s_unet, alpha_routing=10):
+        return ops.sigmoid(ops.axpby(s_vit, s_unet, 1.0, -1.0), float(alpha_routing))   # (B,)
+
+    def _fusion_inputs(self, fu, fv, sw):
         d = ops.scale_rows(ops.axpby(fv, fu, 1.0, -1.0), sw)                # sw * (fv - fu)
         return ops.axpby(fu, d, 1.0, 1.0), ops.axpby(fv, d, 1.0, -1.0)     # query, context (:282-283)
 

@@ -22,7 +22,10 @@ class HDMOEM(_HDMOEMBase):
     def _scaling(self, time_vec, time_embed, zeta, transition_point, softness):
         return ops.sigmoid_scaling(time_vec, transition_point, softness)
 
-    def _fusion_inputs(self, fu, fv, s_vit, s_unet, **kw):
+    def _fusion_swap(self, s_vit, s_unet, **kw):
+        return None
+
+    def _fusion_inputs(self, fu, fv, sw):
         return fu, fv
 
     def forward(self, x: Tensor, time_vec: Tensor, text_emb: Tensor, Unet_router_mask: Tensor, Vit_router_mask: Tensor,

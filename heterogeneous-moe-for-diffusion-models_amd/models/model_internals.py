@@ -199,7 +199,7 @@ class MP_Attention(nn.Module):
         self.out_proj = MP_Conv(emb_dim, emb_dim, kernel=(1, 1))
 
     def forward(self, query: Tensor, gain_s: float, gain_t: float, context: Optional[Tensor] = None,
-                time_embedding: Optional[Tensor] = None) -> Tensor:
+                time_embedding: Optional[Tensor] = None, core_only: bool = False) -> Tensor:
         batch_size, seq_len, emb_dim = query.shape
         assert emb_dim == self.emb_dim
         dt = query.dtype
@@ -213,13 +213,27 @@ class MP_Attention(nn.Module):
             if not self.is_cross:
                 k = ops.seq_bcast_add(k, self.k_time._fwd(te, gain_t))
                 v = ops.seq_bcast_add(v, self.v_time._fwd(te, gain_t))
+        return self._attend(query, ctx, q, k, v, gain_s, core_only)
+
+    def _attend(self, query: Tensor, ctx: Tensor, q: Tensor, k: Tensor, v: Tensor, gain_s: float, core_only: bool = False) -> Tensor:
+        """Attention core + out_proj with the residual, from projections already made (forward, or the fused head of the fusion stage).
+        core_only: the attention output alone -- the caller runs `_project_out`, or a fused launch that contains it."""
+        seq_len = query.shape[1]
         bias = None
         if not self.is_cross:
             bias = self.rel_pos_bias                      # the kernel reads the [:S, :S] corner in place
             if seq_len > bias.shape[1]:                   # longer than trained: bicubic resize of the table (:388-397)
                 bias = ops.bicubic_resize(bias, seq_len)
         o = ops.attention(q, k, v, bias, self.num_heads)
+        return o if core_only else self._project_out(o, query, gain_s)
+
+    def _out_mix(self):
+        """(alpha, beta) of out_proj's epilogue: mp_sum(query, out_proj(o), attn_balance)."""
         t = self.attn_balance
         n = math.sqrt((1.0 - t) ** 2 + t ** 2)
+        return t / n, (1.0 - t) / n
+
+    def _project_out(self, o: Tensor, query: Tensor, gain_s: float) -> Tensor:
         # out_proj with the mp_sum(res, out, attn_balance) residual fused into the conv epilogue
-        return self.out_proj._fwd(o, gain_s, res=query, alpha=t / n, beta=(1.0 - t) / n)
+        alpha, beta = self._out_mix()
+        return self.out_proj._fwd(o, gain_s, res=query, alpha=alpha, beta=beta)

@@ -98,6 +98,40 @@ int hdmoe_conv_bwd6_film(const void* x, const void* dy, const void* wd, void* dx
  * (Cin / 32) * (Cout / 32) <= 8.  Returns 1 without launching outside it; the caller then uses hdmoe_conv_fwd + hdmoe_conv_wgrad. */
 int hdmoe_pw_bwd(const void* x, const void* dy, const void* wd, void* dx, float* const* G, const int* seg, int ngroups,
                  long wd_stride, int N, long HW, int Cin, int Cout, float alpha, int dtype, HS stream);
+/* Fusion stage, the token-local chain in front of the first attention call in one launch per direction (csrc/fusion.hip).  All tensors
+ * [rows][32] bf16, contiguous, 16-byte aligned; sw [rows / S] fp32 per-sample swap weights or NULL; wq / wk / wv the prepared FORWARD
+ * images ([32][32]) of the three projections, wdq / wdk / wdv their flipped images, alpha_* the layers' output scales.
+ *   fwd: query = fu + sw (fv - fu), ctx = fv - sw (fv - fu) (not written, and may be NULL, when sw is NULL: they are fu and fv),
+ *        q = alpha_q Wq query, k = alpha_k Wk ctx, v = alpha_v Wv ctx.
+ *   bwd: dfu, dfv from dq, dk, dv and the further gradients gquery / gctx of query / ctx (either may be NULL); dsw [rows / S] fp32
+ *        accumulates (float atomics, as hdmoe_scale_rows_bwd); fu, fv, dsw are read only with sw.  No weight gradients: those are
+ *        hdmoe_conv_wgrad's, from query / ctx and dq / dk / dv.
+ * bf16 rounding at every point where the unfused chain (hdmoe_axpby, hdmoe_scale_rows_*, hdmoe_conv_fwd, hdmoe_pw_bwd, the sums of
+ * two gradients) stores a tensor.  Returns 1 without launching outside the domain: dtype bf16, C == 32, aligned bases. */
+int hdmoe_fusion_in_fwd(const void* fu, const void* fv, const float* sw, const void* wq, const void* wk, const void* wv,
+                        void* query, void* ctx, void* q, void* k, void* v, long rows, long S, int C, float alpha_q,
+                        float alpha_k, float alpha_v, int dtype, HS stream);
+int hdmoe_fusion_in_bwd(const void* dq, const void* dk, const void* dv, const void* gquery, const void* gctx, const void* fu,
+                        const void* fv, const float* sw, const void* wdq, const void* wdk, const void* wdv, void* dfu, void* dfv,
+                        float* dsw, long rows, long S, int C, float alpha_q, float alpha_k, float alpha_v, int dtype, HS stream);
+/* The chain behind the text attention of the fusion stage, down to the gate, in one launch per direction (csrc/fusion.hip).  Row tensors
+ * [rows][32] bf16 unless noted; alpha_txt the device scalar of lerp_param; wo / w1 / w2 the forward images of cross_attn_text.out_proj
+ * ([32][32], output scale alpha_o, residual weight beta_o), gate1 ([32][64], alpha_1) and gate2 ([2][32], alpha_2), wdo / wd1 / wd2
+ * their flipped images ([32][32], [64][32], [32][16]); wa, wb the weights of mp_cat.
+ *   fwd: at = alpha_o Wo o2 + beta_o a; a2 = a + alpha_txt (at - a); cat = [wa U | wb a2] ([rows][64]); g1 = alpha_1 W1 cat;
+ *        s = mp_silu(g1); gate = softmax(alpha_2 W2 s) ([rows][2] fp32); mixed = hdmoe_gate_mix_fwd(logits, U, a2).
+ *        a2, g1, cat, s are what the backward and the weight gradients read; all four NULL: not written (inference).
+ *   bwd: from dmixed and dgate (or NULL): do2, da (the lerp's and the residual's share, summed), dU (gate_mix's and mp_cat's share,
+ *        summed), dalpha += (fp32, one atomic per workgroup), and dat, dg1, dl ([rows][2]): the dy of the three weight gradients
+ *        (hdmoe_conv_wgrad with x = o2, cat, s).
+ * bf16 rounding wherever the unfused ops store a tensor.  Returns 1 without launching outside the domain (bf16, C == 32, aligned). */
+int hdmoe_fusion_out_fwd(const void* o2, const void* a, const void* U, const float* alpha_txt, const void* wo, const void* w1,
+                         const void* w2, void* mixed, float* gate, void* a2, void* g1, void* cat, void* s, long rows, int C,
+                         float alpha_o, float beta_o, float wa, float wb, float alpha_1, float alpha_2, int dtype, HS stream);
+int hdmoe_fusion_out_bwd(const void* dmixed, const float* dgate, const float* gate, const void* U, const void* a2, const void* g1,
+                         const void* o2, const void* a, const float* alpha_txt, const void* wo, const void* wdo, const void* wd1,
+                         const void* wd2, void* do2, void* da, void* dU, void* dat, void* dg1, void* dl, float* dalpha, long rows,
+                         int C, float alpha_o, float beta_o, float wa, float wb, float alpha_1, float alpha_2, int dtype, HS stream);
 int hdmoe_conv_bwd6s(const void* x, const void* dy, const void* wd, void* dx, float* const* G, const int* seg, int ngroups,
                      long wd_stride, long wd_plane, int N, int H, int W, int Cin, int Cout, const int* kh, const int* kw,
                      const int* pt, const int* pl, float alpha, void* ws, long ws_bytes, const float* in_scale, const float* in_shift,
@@ -158,7 +192,11 @@ enum {
   HDMOE_SEL_COMBINE_BWD_VEC = 21,  /* hdmoe_combine_rows_bwd_vec: 16-byte combine backward */
   HDMOE_SEL_FILM_DGRAD = 22,       /* hdmoe_conv_bwd6_film: the bwd7 launch with the FiLM-backward epilogue in its dgrad program */
   HDMOE_SEL_ROW_WINDOW = 23,       /* a row-windowed launch (the hdmoe_*_rows / hdmoe_rag_*_own entry points of the ViT bank's edges) */
-  HDMOE_SEL_COUNT = 24
+  HDMOE_SEL_FUSION_IN = 24,        /* hdmoe_fusion_in_fwd: fusion inputs + q / k / v projections of cross_attn in one launch */
+  HDMOE_SEL_FUSION_IN_BWD = 25,    /* hdmoe_fusion_in_bwd: their input gradients, the gradient fan-in and dsw in one launch */
+  HDMOE_SEL_FUSION_OUT = 26,       /* hdmoe_fusion_out_fwd: text out_proj + lerp + mp_cat + gate1 + mp_silu + gate2 + gate_mix in one launch */
+  HDMOE_SEL_FUSION_OUT_BWD = 27,   /* hdmoe_fusion_out_bwd: their input gradients, the gradient fan-in and dalpha in one launch */
+  HDMOE_SEL_COUNT = 28
 };
 int hdmoe_kernel_selections(long long* counts, int n, int reset);
 
