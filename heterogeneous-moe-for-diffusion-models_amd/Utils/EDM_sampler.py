@@ -32,6 +32,14 @@ Guidance interval and per-sample scales (extensions, opt-in).  ``guidance_interv
 [lo, hi] (limited-interval guidance); the others are the single plain conditional call, at 1x the cost.  The solver decides per evaluation
 on the host (``guidance_plan``) and, with ``use_graph``, replays the stage variant captured for that decision.  ``sample(guidance=vector)`` /
 ``denoise(guidance=vector)`` take one scale per sample from a device buffer instead of the float baked into the capture.
+
+Guidance rescale and adaptive projected guidance, APG (extensions, opt-in).  ``guidance_rescale`` > 0 pulls the per-sample standard
+deviation of the guided output back to that of the conditional output (Lin et al. 2024, section 3.4); ``apg_eta`` (with
+``apg_norm_threshold`` and ``apg_momentum``) splits the guidance update into its parts parallel and orthogonal to the conditional output,
+weights the parallel part by eta, clamps the update's norm and gives it a momentum across evaluations (Sadat et al. 2024).  Either one turns
+the blend of every guided evaluation into ONE launch of the combine kernel (``ops.guide_combine`` two-pass, the egress
+``ops.nhwc_to_nchw_guide_combine`` with shared_guidance); the momentum lives in a device buffer of the stage state, so captured stages
+replay it.  With the defaults no launch changes.
 """
 import math
 import numbers
@@ -50,7 +58,9 @@ class EDM_Sampler:
     def __init__(self, model: nn.Module, Guide_net: nn.Module, num_solve_steps: int = 32, sigma_min: float = 0.002,
                  sigma_max: float = 80, rho: int = 7, S_churn: float = 0.0, S_min: float = 0.0, S_max: float = float("inf"),
                  S_noise: float = 1.0, guidance: float = 1.0, dtype=torch.float32, use_graph: bool = False, solver: str = "heun",
-                 churn_on_device: bool = False, eta: float = 1.0, shared_guidance: bool = False, guidance_interval=None):
+                 churn_on_device: bool = False, eta: float = 1.0, shared_guidance: bool = False, guidance_interval=None,
+                 guidance_rescale: float = 0.0, apg_eta: float = None, apg_norm_threshold: float = float("inf"),
+                 apg_momentum: float = 0.0):
         if not isinstance(solver, str) or solver not in SOLVERS:
             raise ValueError(f"solver must be one of {', '.join(map(repr, SOLVERS))}, got {solver!r}")
         if solver != "heun" and S_churn > 0:
@@ -63,6 +73,15 @@ class EDM_Sampler:
             raise ValueError(f"eta must be a finite number >= 0, got {eta!r}")
         if solver != "dpmpp_2m_sde" and eta_f != 1.0:
             raise ValueError(f"eta (got {eta!r}) is the noise scale of solver='dpmpp_2m_sde' only, not of solver={solver!r}")
+        # guidance rescale / APG: checked here, launch scalars of the combine kernel from then on (part of every capture key)
+        self.guidance_rescale = self._check_number(guidance_rescale, "guidance_rescale", "in [0, 1]", lambda v: 0.0 <= v <= 1.0)
+        self.apg_eta = None if apg_eta is None else self._check_number(apg_eta, "apg_eta", "None or in [0, 1]", lambda v: 0.0 <= v <= 1.0)
+        self.apg_norm_threshold = self._check_number(apg_norm_threshold, "apg_norm_threshold", "> 0 (inf: no clamp)", lambda v: v > 0.0)
+        self.apg_momentum = self._check_number(apg_momentum, "apg_momentum", "in (-1, 1)", lambda v: -1.0 < v < 1.0)
+        if self.apg_eta is None:
+            for name, val, default in (("apg_norm_threshold", self.apg_norm_threshold, float("inf")), ("apg_momentum", self.apg_momentum, 0.0)):
+                if val != default:
+                    raise ValueError(f"{name}={val} belongs to projected guidance: it needs apg_eta (got apg_eta=None)")
         self.model = model
         self.gnet = Guide_net
         self.shared_guidance = bool(shared_guidance)     # extension: a guided evaluation is ONE shared-routing pass (model.forward_guided)
@@ -97,21 +116,35 @@ class EDM_Sampler:
 
     # reference Utils/EDM_sampler.py:35-70
     def denoise(self, x, sigma, text_emb, transition_mean, softness, uncond_text_emb=None, Unet_router_mask=None, Vit_router_mask=None,
-                guidance=None, guided=True):
+                guidance=None, guided=True, momentum_state=None):
         """One (guided) denoiser evaluation.  Router masks: (B, E) or (E,) with {0, 1} entries, None = every expert allowed (the reference).
         With shared_guidance a guided evaluation is one model.forward_guided pass (inference: call it under torch.no_grad()).
         guidance: None = the sampler's float scale, or a (B,) tensor of finite per-sample scales (any device).  guided=False: the single
         plain conditional evaluation, whatever the scale.  denoise() never reads sigma: whether an evaluation lies in guidance_interval is
-        the solver's decision (sample()), handed down as `guided`."""
+        the solver's decision (sample()), handed down as `guided`.
+        momentum_state: the APG momentum buffer, a contiguous (B, C, H, W) float32 tensor on x's device, updated in place by a guided
+        evaluation (zero it before the first evaluation of a trajectory).  apg_momentum != 0 needs it; otherwise it is not used."""
         um = self._router_mask(Unet_router_mask, "Unet_router_mask", x.shape[0])
         vm = self._router_mask(Vit_router_mask, "Vit_router_mask", x.shape[0])
         g = self._check_guidance(guidance, x.shape[0])
+        if self.apg_momentum != 0.0:
+            ms = momentum_state
+            if not isinstance(ms, torch.Tensor):
+                raise ValueError(f"apg_momentum={self.apg_momentum} needs momentum_state, a float32 tensor of shape {tuple(x.shape)} on "
+                                 f"{x.device}, got {type(ms).__name__}")
+            if ms.dtype != torch.float32 or tuple(ms.shape) != tuple(x.shape) or ms.device != x.device or not ms.is_contiguous():
+                raise ValueError(f"momentum_state must be a contiguous float32 tensor of shape {tuple(x.shape)} on {x.device}, got "
+                                 f"{tuple(ms.shape)} {ms.dtype} on {ms.device}")
+        else:
+            momentum_state = None
         return self._denoise(x, sigma, text_emb, transition_mean, softness, uncond_text_emb, self._dev_mask(um, x), self._dev_mask(vm, x),
-                             bool(guided), self._dev_mask(g, x))
+                             bool(guided), self._dev_mask(g, x), momentum_state)
 
-    def _denoise(self, x, sigma, text_emb, transition_mean, softness, uncond_text_emb, um=None, vm=None, guided=True, g=None):
+    def _denoise(self, x, sigma, text_emb, transition_mean, softness, uncond_text_emb, um=None, vm=None, guided=True, g=None, mom=None):
         """denoise() on validated device masks (or None) and a validated (B,) float32 device vector of scales g (or None: self.guide): no
-        host read, so it can run under stream capture.  guided False, or a float scale of 1: one plain conditional call."""
+        host read, so it can run under stream capture.  guided False, or a float scale of 1: one plain conditional call.
+        With guidance rescale / APG (combine_params()) the blend of a guided evaluation is the combine kernel; mom: its momentum buffer
+        (apg_momentum != 0), read and written by guided evaluations only."""
         bs = x.shape[0]
         num_experts = self.model.num_experts
         Unet_router_mask = torch.ones((bs, num_experts), device=x.device) if um is None else um
@@ -119,9 +152,12 @@ class EDM_Sampler:
         kw = dict(x=x, sigma=sigma, Unet_router_mask=Unet_router_mask, Vit_router_mask=vit_router_mask, zeta=0,
                   transition_point=transition_mean, softness=softness)
         active = guided and (g is not None or self.guide != 1.0)
+        comb = self.combine_params() if active else None
         if self.shared_guidance and active:
             # one pass: routing (and so the router masks) once, both text variants through the banks and the tail, the lerp in the egress
             self._check_shared()
+            if comb is not None:                              # the egress is the combine kernel
+                kw["guide_combine"] = comb + (mom,)
             return self.model.forward_guided(text_emb=text_emb, uncond_text_emb=uncond_text_emb, guidance=self.guide if g is None else g,
                                              **kw)["denoised"].to(self.dtype)
         D_x = self.model(text_emb=text_emb, **kw)["denoised"].to(self.dtype)
@@ -129,6 +165,10 @@ class EDM_Sampler:
             return D_x
         emb_for_guide = uncond_text_emb if uncond_text_emb is not None else text_emb
         ref_D_x = self.gnet(text_emb=emb_for_guide, **kw)["denoised"].to(self.dtype)
+        if comb is not None:
+            eta, r, beta, phi = comb
+            return ops.guide_combine(ref_D_x, D_x, self.guide if g is None else g, eta=eta, norm_threshold=r, momentum=beta, rescale=phi,
+                                     state=mom)
         # ref.lerp(D, g) = (1-g)*ref + g*D
         if g is not None:
             return ops.lerp_rows(ref_D_x, D_x, g)
@@ -144,6 +184,27 @@ class EDM_Sampler:
             raise ValueError("shared_guidance=True needs Guide_net to be the model itself (a different guide network takes two passes)")
         if not callable(getattr(self.model, "forward_guided", None)):
             raise ValueError(f"shared_guidance=True needs a model with forward_guided(); {type(self.model).__name__} has none")
+
+    @staticmethod
+    def _check_number(v, name, what, ok):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a number {what}, got {v!r}") from None
+        if isinstance(v, bool) or not ok(f):                  # NaN fails every comparison
+            raise ValueError(f"{name} must be {what}, got {v!r}")
+        return f
+
+    def combine_params(self):
+        """None when neither guidance rescale nor APG is on (guided evaluations then blend as before), else the launch scalars
+        (eta, norm_threshold, momentum, rescale) of the combine kernel; apg_eta None is eta = 1, the plain update."""
+        if self.guidance_rescale <= 0.0 and self.apg_eta is None:
+            return None
+        return (1.0 if self.apg_eta is None else self.apg_eta, self.apg_norm_threshold, self.apg_momentum, self.guidance_rescale)
+
+    def _needs_momentum(self, gvec):
+        """Does a guided evaluation of this configuration carry the APG momentum buffer?"""
+        return self.combine_params() is not None and self.apg_momentum != 0.0 and (gvec is not None or self.guide != 1.0)
 
     @property
     def guidance_interval(self):
@@ -273,6 +334,8 @@ class EDM_Sampler:
         trajectories are bit-identical.  The key holds everything a capture bakes in -- shapes, which optional operands exist, and what
         _denoise reads on the host (guide, the two modules), the churn / SDE launch scalars -- never buffer values: every input, the seed of
         the stochastic stages included (device word "seed") and the per-sample guidance scales ("g"), is refreshed before each run.
+        combine_params() -- launch scalars of the combine kernel -- are in the key; the APG momentum ("mom", float32, None without
+        apg_momentum) is a buffer value: _refresh zeroes it at the start of a sample() call, every guided evaluation updates it in place.
 
         With a guidance interval (and guidance in effect) every stage function exists once per variant -- which of its evaluations are
         guided -- and with use_graph each variant is one graph, all in one pool over the same buffers: "sel" maps a stage's tuple of
@@ -283,7 +346,7 @@ class EDM_Sampler:
         key = (kind, self.solver, shape(x), x.dtype, shape(text_emb), shape(uncond_text_emb), float(transition_mean), float(softness),
                self.num_steps, bool(self.use_graph), None if known is None else tuple(map(shape, known)), shape(um), shape(vm),
                float(self.guide), id(self.model), id(self.gnet), float(self.s_churn), float(self.s_min), float(self.s_max), float(self.s_noise),
-               float(self.eta), bool(self.churn_on_device), gvec is not None, variants, bool(self.shared_guidance))
+               float(self.eta), bool(self.churn_on_device), self.combine_params(), gvec is not None, variants, bool(self.shared_guidance))
         slot = "_graph" if kind == "eval" else "_stage"          # one cached state for the evaluation, one for the solver stage
         st = getattr(self, slot)
         if st is not None and st["key"] == key:
@@ -293,11 +356,13 @@ class EDM_Sampler:
         # mods: held so that their ids, in the key, cannot be reused by other modules while this capture lives
         st = dict(key=key, x=torch.empty_like(x), sig=torch.ones((), dtype=self.dtype, device=dev), text=torch.empty_like(text_emb),
                   unc=opt(uncond_text_emb), known=None if known is None else tuple(map(torch.empty_like, known)), um=opt(um), vm=opt(vm),
-                  g=opt(gvec), variants=variants, mods=(self.model, self.gnet))
+                  g=opt(gvec), variants=variants, mods=(self.model, self.gnet),
+                  mom=torch.zeros(x.shape, dtype=torch.float32, device=dev) if self._needs_momentum(gvec) else None)
         self._refresh(st, x, text_emb, uncond_text_emb, known, um, vm, gvec=gvec)
 
         def den(x_, guided):
-            return self._denoise(x_, st["sig"], st["text"], transition_mean, softness, st["unc"], st["um"], st["vm"], guided, st["g"])
+            return self._denoise(x_, st["sig"], st["text"], transition_mean, softness, st["unc"], st["um"], st["vm"], guided, st["g"],
+                                 st["mom"])
 
         def pick(j):                                          # sig = t[idx + j]
             ops.call("hdmoe_sched_pick", st["sig"], st["t"], st["idx"], j)
@@ -381,9 +446,13 @@ class EDM_Sampler:
         return graphs
 
     @staticmethod
-    def _refresh(st, x, text_emb, uncond_text_emb, known, um, vm, seed=None, gvec=None):
+    def _refresh(st, x, text_emb, uncond_text_emb, known, um, vm, seed=None, gvec=None, reset_momentum=True):
         """Every input into the static buffers: a later sample() with another prompt of the same shape must not see the captured one.
-        seed: the 64-bit seed of this call's stochastic stages (a buffer value like the others, never part of the capture key)."""
+        seed: the 64-bit seed of this call's stochastic stages (a buffer value like the others, never part of the capture key).
+        reset_momentum: zero the APG momentum -- the start of a sample() call (the warm-up runs of a capture have written it too); the
+        captured evaluation of the host loops keeps it from one evaluation of a call to the next."""
+        if reset_momentum and st["mom"] is not None:
+            st["mom"].zero_()
         if seed is not None:
             st["seed"].fill_(seed - (1 << 64) if seed >= 1 << 63 else seed)
         st["x"].copy_(x)
@@ -401,7 +470,7 @@ class EDM_Sampler:
         return eps.to(x.dtype)
 
     def _dpm_host_loop(self, x, t_steps, i0, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, seed=None, plan=None,
-                       gvec=None):
+                       gvec=None, mom=None):
         """solver="dpmpp_2m" / "dpmpp_2m_sde" for latents the fused stage does not take (non-fp32 dtype): the rule of sample() with host
         coefficients."""
         N = self.num_steps
@@ -410,7 +479,7 @@ class EDM_Sampler:
         for i in range(i0, N):
             t_cur, t_next = float(t_steps[i]), float(t_steps[i + 1])
             den = self._eval(x, t_cur, text_emb, transition_mean, softness, uncond_text_emb, um, vm,
-                             True if plan is None else plan[i - i0][0], gvec)
+                             True if plan is None else plan[i - i0][0], gvec, mom, first=i == i0)
             e = math.exp(-self.eta * math.log(t_cur / t_next)) if sde and t_next > 0 else 1.0
             a = t_next / t_cur * e
             if t_next == 0:
@@ -427,13 +496,15 @@ class EDM_Sampler:
             den_prev = den
         return x
 
-    def _eval(self, x, t, text_emb, transition_mean, softness, uncond_text_emb, um=None, vm=None, guided=True, gvec=None):
-        """One evaluation at sigma t of the host loops; guided: the solver's guidance-interval decision for it."""
+    def _eval(self, x, t, text_emb, transition_mean, softness, uncond_text_emb, um=None, vm=None, guided=True, gvec=None, mom=None,
+              first=False):
+        """One evaluation at sigma t of the host loops; guided: the solver's guidance-interval decision for it.  mom: the call's APG
+        momentum buffer (eager); the captured evaluation carries its own, zeroed on the first evaluation of a call."""
         if not self.use_graph:
             sig = torch.tensor(t, dtype=self.dtype, device=x.device)
-            return self._denoise(x, sig, text_emb, transition_mean, softness, uncond_text_emb, um, vm, guided, gvec)
+            return self._denoise(x, sig, text_emb, transition_mean, softness, uncond_text_emb, um, vm, guided, gvec, mom)
         st = self._stage_state("eval", x, text_emb, transition_mean, softness, uncond_text_emb, None, um, vm, gvec)
-        self._refresh(st, x, text_emb, uncond_text_emb, None, um, vm, gvec=gvec)
+        self._refresh(st, x, text_emb, uncond_text_emb, None, um, vm, gvec=gvec, reset_momentum=first)
         st["sig"].fill_(float(t))
         guided = bool(guided) or not st["variants"]
         st["g_eval"][st["sel"][(guided,)]].replay()
@@ -497,6 +568,13 @@ class EDM_Sampler:
         With DPM-Solver++(2M) the history term D_{i-1} is whatever stage i - 1 evaluated: across an interval boundary the extrapolation
         mixes a guided and a plain output -- that is the formula applied to the gated denoiser, not an error.  With use_graph every stage
         variant is captured once; calls that differ in the bounds replay the same graphs.
+
+        guidance_rescale / apg_eta / apg_norm_threshold / apg_momentum (constructor arguments): with w the scale, D_c / D_u the two
+        denoiser outputs of a guided evaluation and all sums over one sample, the guided output is
+            M = (D_c - D_u) + apg_momentum M_prev;   s = min(1, apg_norm_threshold / |M|);   c = <M, D_c> / |D_c|^2
+            O = D_c + (w - 1) s (M - (1 - apg_eta) c D_c);   out = (guidance_rescale std(D_c) / std(O) + 1 - guidance_rescale) O
+        (apg_eta None: eta = 1, no clamp, no momentum, i.e. O = (1 - w) D_u + w D_c).  M_prev is zero at the start of every call and is
+        updated by the guided evaluations in the order the solver makes them; evaluations outside guidance_interval leave it alone.
         Argument errors raise ValueError (naming the argument) before any device work."""
         strength = self._check_conditioning(noise, init_latents, strength, inpaint_mask)
         seed = self._check_seed(seed)
@@ -549,9 +627,11 @@ class EDM_Sampler:
             for flags in plan:                                # Heun: the Euler-only stage last; DPM: its one stage throughout
                 runs[st["sel"][flags if st["variants"] else (True,) * len(flags)]]()
             return st["x"].clone()
+        # host loops: this call's APG momentum (the captured evaluation of use_graph holds its own and zeroes it on the first evaluation)
+        mom = torch.zeros(x_next.shape, dtype=torch.float32, device=device) if self._needs_momentum(gvec) and not self.use_graph else None
         if self.solver != "heun":
             return self._dpm_host_loop(x_next, t_steps, i0, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, seed, plan,
-                                       gvec)
+                                       gvec, mom)
         for i in range(i0, N):
             t_cur, t_next = float(t_steps[i]), float(t_steps[i + 1])
             x_cur = x_next
@@ -560,14 +640,15 @@ class EDM_Sampler:
             x_hat = x_cur
             if gamma > 0:
                 x_hat = ops.axpby(x_cur, self._eps(x_cur, seed, i), 1.0, float(np.sqrt(t_hat ** 2 - t_cur ** 2) * self.s_noise))
-            denoised = self._eval(x_hat, t_hat, text_emb, transition_mean, softness, uncond_text_emb, um, vm, plan[i - i0][0], gvec)
+            denoised = self._eval(x_hat, t_hat, text_emb, transition_mean, softness, uncond_text_emb, um, vm, plan[i - i0][0], gvec, mom,
+                                  first=i == i0)
             # d_cur = (x_hat - denoised)/t_hat ; x_next = x_hat + (t_next - t_hat) * d_cur
             h = (t_next - t_hat)
             x_next = ops.axpby(x_hat, denoised, 1.0 + h / t_hat, -h / t_hat)
             if known is not None:
                 ops.known_blend_(x_next, *known, t_next)
             if i < self.num_steps - 1:
-                den2 = self._eval(x_next, t_next, text_emb, transition_mean, softness, uncond_text_emb, um, vm, plan[i - i0][1], gvec)
+                den2 = self._eval(x_next, t_next, text_emb, transition_mean, softness, uncond_text_emb, um, vm, plan[i - i0][1], gvec, mom)
                 # x_next = x_hat + h * (0.5*d_cur + 0.5*d_prime),  d_prime = (x_next - den2)/t_next
                 d_cur_term = ops.axpby(x_hat, denoised, 1.0 + 0.5 * h / t_hat, -0.5 * h / t_hat)     # x_hat + 0.5 h d_cur
                 d_pr = ops.axpby(x_next, den2, 0.5 * h / t_next, -0.5 * h / t_next)                  # 0.5 h d_prime

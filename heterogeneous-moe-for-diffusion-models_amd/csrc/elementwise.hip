@@ -712,6 +712,155 @@ __global__ void lerp_rows_kernel(T* out, const T* ref, const T* d, const float* 
   }
 }
 
+// ---------------------------------------------------------------- guidance combine: rescale + projected guidance (APG), hdmoe.h
+// One workgroup of GC_TPB threads per sample.  Thread t owns the W-element vectors t, t + GC_TPB, ... of its sample.  Resident arm
+// (RES, per <= GC_TPB * GC_R): the GC_R / W vectors of D_c and M stay in registers across the reduction, so ref / d / F / x and the
+// momentum are read once and out and the momentum written once.  Re-read arm: the operands are read again after the reduction (from L2 for
+// any sample that fits it) and M is formed a second time by the same fp32 operations, so both passes see the same M.  The five sums are
+// fp64 per thread, then wave shuffle, then one LDS slot per wave and a second butterfly over the slots: no atomics, and every thread of the
+// workgroup computes the same scalars.
+constexpr int GC_TPB = 1024, GC_R = 16;
+static_assert(GC_TPB * GC_R == HDMOE_GUIDE_COMBINE_RESIDENT, "the resident limit of hdmoe.h");
+struct GcPar { float g; const float* g_rows; float eta, r, beta, phi; };
+// the two loaders: D_c / D_u of elements e ... e + W - 1 of sample n
+template <typename T> struct GcPair {                    // two-pass: ref = D_u, d = D_c, (B, per)
+  const T* ref; const T* d;
+  struct Cur {};
+  template <int W> DEVI Cur seek(long) const { return {}; }
+  DEVI void advance(Cur&) const {}
+  DEVI void rewind(Cur&) const {}
+  template <int W> DEVI void load(float* dc, float* du, long n, long per, long e, const Cur&) const {
+    ldw<T, W>(dc, d + n * per + e);
+    ldw<T, W>(du, ref + n * per + e);
+  }
+};
+template <typename T> struct GcEgress {                  // shared-routing egress: sx x + sf F[n] and sx x + sf F[N + n], NCHW element e = c HW + p
+  const T* F; const float* sf; const float* x; const float* sx; int C; unsigned HW; long half;       // per = C HW < 2^31: 32-bit division
+  // (c, p) of a thread's current vector, carried from vector to vector by the step's quotient and remainder: one division per pass
+  struct Cur { unsigned c, p, dq, dr; };
+  template <int W> DEVI Cur seek(long e) const {
+    const unsigned c = (unsigned)e / HW, step = GC_TPB * W;
+    return {c, (unsigned)e - c * HW, step / HW, step % HW};
+  }
+  DEVI void advance(Cur& k) const {
+    k.c += k.dq; k.p += k.dr;
+    if (k.p >= HW) { k.p -= HW; ++k.c; }
+  }
+  DEVI void rewind(Cur& k) const { k.c = 0; k.p = 0; }     // element 0
+  template <int W> DEVI void load(float* dc, float* du, long n, long per, long e, const Cur& k) const {
+#pragma clang fp contract(off)
+    const T* f = F + ((long)n * HW + k.p) * C + k.c;     // W > 1: HW % W == 0, the W elements share c
+    const float a = sf[n], s = sx[n];
+    float xs[W];
+    ldw<float, W>(xs, x + n * per + e);
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      const float t = s * xs[j];
+      dc[j] = t + a * to_f(f[(long)j * C]);
+      du[j] = t + a * to_f(f[half + (long)j * C]);
+    }
+  }
+};
+template <int W> DEVI void gc_ldf(float* f, const float* p) {      // W floats: 16-byte loads, two of them at the bf16 width
+  if constexpr (W == 8) { ldw<float, 4>(f, p); ldw<float, 4>(f + 4, p + 4); }
+  else ldw<float, W>(f, p);
+}
+template <int W> DEVI void gc_stf(float* p, const float* f) {
+  if constexpr (W == 8) { stw<float, 4>(p, f); stw<float, 4>(p + 4, f + 4); }
+  else stw<float, W>(p, f);
+}
+template <typename L, typename TO, int W, bool RES, bool MOM>
+__global__ __launch_bounds__(GC_TPB) void guide_combine_kernel(L ld, TO* out, float* mom, GcPar q, long per) {
+#pragma clang fp contract(off)
+  constexpr int K = RES ? GC_R / W : 1, NW = GC_TPB / 64;
+  __shared__ double sm[5][NW];
+  const long n = blockIdx.x, step = (long)GC_TPB * W, e0 = (long)threadIdx.x * W;
+  float dc[K][W], m[K][W];
+  double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  auto form = [&](float* dcv, float* mv, long e, const typename L::Cur& cur) {      // step 1 (fp32) of elements e ... e + W - 1
+    float du[W];
+    ld.template load<W>(dcv, du, n, per, e, cur);
+    if constexpr (MOM) {
+      float mp[W];
+      gc_ldf<W>(mp, mom + n * per + e);
+#pragma unroll
+      for (int j = 0; j < W; ++j) mv[j] = (dcv[j] - du[j]) + q.beta * mp[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < W; ++j) mv[j] = dcv[j] - du[j];
+    }
+  };
+  auto sums = [&](const float* dcv, const float* mv) {    // step 2: the products of two fp32 values are exact in fp64
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      const double a = (double)mv[j], b = (double)dcv[j];
+      s[0] = __builtin_fma(a, a, s[0]); s[1] = __builtin_fma(a, b, s[1]); s[2] = __builtin_fma(b, b, s[2]);
+      s[3] += b; s[4] += a;
+    }
+  };
+  typename L::Cur cur = ld.template seek<W>(e0);
+  if constexpr (RES) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {                         // no branch: a vector past the end reads element 0 and counts as zeros
+      const unsigned e = (unsigned)e0 + k * (unsigned)step;          // resident: offsets of 32 bits
+      const bool ok = e < (unsigned)per;
+      typename L::Cur at = cur;
+      if (!ok) ld.rewind(at);
+      form(dc[k], m[k], ok ? e : 0u, at);
+#pragma unroll
+      for (int j = 0; j < W; ++j) { dc[k][j] = ok ? dc[k][j] : 0.f; m[k][j] = ok ? m[k][j] : 0.f; }
+      sums(dc[k], m[k]);
+      ld.advance(cur);
+    }
+  } else {
+    for (long e = e0; e < per; e += step) { form(dc[0], m[0], e, cur); sums(dc[0], m[0]); ld.advance(cur); }
+  }
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s[i] += __shfl_xor(s[i], o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {                          // one branch after all five: a branch per sum lets the compiler sink the other
+#pragma unroll                                            // sums' accumulation below it, with every element held as a double meanwhile
+    for (int i = 0; i < 5; ++i) sm[i][threadIdx.x >> 6] = s[i];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {                          // a butterfly over the NW slots: a + b == b + a, so every lane holds the same bits
+    s[i] = sm[i][threadIdx.x & (NW - 1)];
+#pragma unroll
+    for (int o = NW / 2; o > 0; o >>= 1) s[i] += __shfl_xor(s[i], o, 64);
+  }
+  // steps 3 - 5 (fp64)
+  const double S1 = s[0], S2 = s[1], S3 = s[2], T1 = s[3], T2 = s[4], cnt = (double)per;
+  const double w1 = (double)(q.g_rows ? q.g_rows[n] : q.g) - 1.0, r = (double)q.r, phi = (double)q.phi;
+  const double nrm = sqrt(S1), sc = nrm > r ? r / nrm : 1.0;
+  const double c = S3 == 0.0 ? 0.0 : S2 / S3;
+  const double b = w1 * sc, a = 1.0 - b * (1.0 - (double)q.eta) * c;
+  const double so = a * T1 + b * T2, so2 = a * a * S3 + 2.0 * a * b * S2 + b * b * S1;
+  const double varc = S3 - T1 * T1 / cnt, varo = so2 - so * so / cnt;
+  const double rho = (varc <= 0.0 || varo <= 0.0) ? 1.0 : sqrt(varc / varo);
+  const double f = phi * rho + (1.0 - phi);
+  const float fa = (float)(f * a), fb = (float)(f * b);
+  auto emit = [&](const float* dcv, const float* mv, long e) {      // step 6 (fp32), out rounded once
+    float o[W];
+#pragma unroll
+    for (int j = 0; j < W; ++j) o[j] = fa * dcv[j] + fb * mv[j];
+    if constexpr (MOM) gc_stf<W>(mom + n * per + e, mv);
+    stw<TO, W>(out + n * per + e, o);
+  };
+  if constexpr (RES) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const unsigned e = (unsigned)e0 + k * (unsigned)step;
+      if (e < (unsigned)per) emit(dc[k], m[k], e);
+    }
+  } else {
+    cur = ld.template seek<W>(e0);
+    for (long e = e0; e < per; e += step) { form(dc[0], m[0], e, cur); emit(dc[0], m[0], e); ld.advance(cur); }
+  }
+}
+
 // ---------------------------------------------------------------- patch <-> image relayout (Vit_expert, model_components.py:698-704)
 // tok[b][(hp,wp)][f] <-> img[b][hp*p+i][wp*p+j][c];  order 0: f = (i*p+j)*C + c ;  order 1 (PixelShuffle): f = c*p*p + i*p + j
 template <typename T, bool TO_IMG>
@@ -1465,6 +1614,46 @@ int hdmoe_lerp_rows(void* out, const void* ref, const void* d, const float* g, l
   if (!out || !ref || !d || !g || rows < 1 || per < 1) return HDMOE_EINVAL;
   const long n = rows * per;
   DT_LAUNCH(dtype, L1D_W(per % VT<T>::W == 0 && al16(out) && al16(ref) && al16(d), lerp_rows_kernel, n, (T*)out, (const T*)ref, (const T*)d, g, per, n))
+}
+// the arms of guide_combine_kernel: W = VW when `vec_ok` else 1, resident when the sample fits GC_TPB * GC_R elements, with or without momentum
+#define GC_ARM(L, TO, W_, RES_, ld, out, mom, q, rows, per)                                                                                  \
+  if (mom) hipLaunchKernelGGL((guide_combine_kernel<L, TO, W_, RES_, true>), dim3(rows), dim3(GC_TPB), 0, stream, ld, out, mom, q, per);    \
+  else hipLaunchKernelGGL((guide_combine_kernel<L, TO, W_, RES_, false>), dim3(rows), dim3(GC_TPB), 0, stream, ld, out, mom, q, per)
+#define GC_LAUNCH(vec_ok, VW, L, TO, ld, out, mom, q, rows, per)                                       \
+  if (vec_ok) {                                                                                        \
+    if ((per) <= GC_TPB * GC_R) { GC_ARM(L, TO, VW, true, ld, out, mom, q, rows, per); }               \
+    else { GC_ARM(L, TO, VW, false, ld, out, mom, q, rows, per); }                                     \
+  } else {                                                                                             \
+    if ((per) <= GC_TPB * GC_R) { GC_ARM(L, TO, 1, true, ld, out, mom, q, rows, per); }                \
+    else { GC_ARM(L, TO, 1, false, ld, out, mom, q, rows, per); }                                      \
+  }
+// eta, r, beta, phi are the caller's to range-check; a NaN among them (or in g) is refused, r = inf is the "no clamp" value
+static bool gc_args_ok(float g, const float* g_rows, float eta, float r, float beta, float phi, const float* momentum) {
+  const bool fin = (g_rows || g - g == 0.f) && eta - eta == 0.f && beta - beta == 0.f && phi - phi == 0.f;
+  return fin && r > 0.f && (beta == 0.f || momentum);
+}
+int hdmoe_guide_combine(void* out, const void* ref, const void* d, float g, const float* g_rows, float eta, float r, float beta, float phi,
+                        float* momentum, long rows, long per, int dtype, hipStream_t stream) {
+  if (!out || !ref || !d || rows < 1 || rows > 0x7fffffffL || per < 1 || !gc_args_ok(g, g_rows, eta, r, beta, phi, momentum)) return HDMOE_EINVAL;
+  const GcPar q{g, g_rows, eta, r, beta, phi};
+  float* mom = beta != 0.f ? momentum : nullptr;
+  DT_LAUNCH(dtype, {
+    const GcPair<T> ld{(const T*)ref, (const T*)d};
+    GC_LAUNCH(per % VT<T>::W == 0 && al16(out) && al16(ref) && al16(d) && al16(mom), VT<T>::W, GcPair<T>, T, ld, (T*)out, mom, q, (unsigned)rows, per);
+  })
+}
+int hdmoe_nhwc_to_nchw_guide_combine(float* out, const void* F, const float* sf, const float* x, const float* sx, float g, const float* g_rows,
+                                     float eta, float r, float beta, float phi, float* momentum, int N, int C, long HW, int dtype,
+                                     hipStream_t stream) {
+  if (!out || !F || !sf || !x || !sx || N < 1 || C < 1 || HW < 1 || (long)C * HW > 0x7fffffffL || !gc_args_ok(g, g_rows, eta, r, beta, phi, momentum))
+    return HDMOE_EINVAL;
+  const GcPar q{g, g_rows, eta, r, beta, phi};
+  float* mom = beta != 0.f ? momentum : nullptr;
+  const long per = (long)C * HW;
+  DT_LAUNCH(dtype, {
+    const GcEgress<T> ld{(const T*)F, sf, x, sx, C, (unsigned)HW, (long)N * per};
+    GC_LAUNCH(HW % 4 == 0 && al16(out) && al16(x) && al16(mom), 4, GcEgress<T>, float, ld, out, mom, q, (unsigned)N, per);
+  })
 }
 static int relayout_entry(void* out, const void* in, const int* rows, int N, int H, int W, int C, int p, int hp, int wp, int order,
                           int to_img, int dtype, hipStream_t stream) {

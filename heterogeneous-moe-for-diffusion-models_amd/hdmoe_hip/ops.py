@@ -2352,6 +2352,70 @@ def lerp_rows(ref: Tensor, d: Tensor, guidance: Union[float, Tensor]) -> Tensor:
     return out
 
 
+# Samples of at most this many elements stay in registers across the reduction of the guidance-combine kernel (every operand read once);
+# larger ones re-read their operands after it.  HDMOE_GUIDE_COMBINE_RESIDENT of include/hdmoe.h.
+GUIDE_COMBINE_RESIDENT = 16384
+
+
+def _combine_args(who: str, guidance, rows: int, eta, norm_threshold, momentum, rescale, state, shape, device):
+    """The launch scalars of the guidance combine as floats, the (rows,) scale vector or None, and the checked momentum buffer (None
+    when momentum == 0: the kernel then neither reads nor writes one)."""
+    eta, r, beta, phi = float(eta), float(norm_threshold), float(momentum), float(rescale)
+    if not (0.0 <= eta <= 1.0 and r > 0.0 and -1.0 < beta < 1.0 and 0.0 <= phi <= 1.0):
+        raise ValueError(f"{who}: needs eta in [0, 1], norm_threshold > 0, momentum in (-1, 1) and rescale in [0, 1], got eta={eta}, "
+                         f"norm_threshold={r}, momentum={beta}, rescale={phi}")
+    g = _row_scales(guidance, rows, who) if isinstance(guidance, Tensor) else None
+    if g is None and not math.isfinite(float(guidance)):
+        raise ValueError(f"{who}: guidance must be finite, got {guidance}")
+    if beta == 0.0:
+        return eta, r, beta, phi, g, None
+    if not isinstance(state, Tensor) or state.dtype != torch.float32 or tuple(state.shape) != tuple(shape) or state.device != device \
+            or not state.is_contiguous():
+        raise ValueError(f"{who}: momentum != 0 needs state, a contiguous float32 tensor of shape {tuple(shape)} on {device} (the momentum "
+                         f"buffer, updated in place), got {type(state).__name__ if not isinstance(state, Tensor) else (tuple(state.shape), state.dtype, state.device)}")
+    return eta, r, beta, phi, g, state
+
+
+def guide_combine(ref: Tensor, d: Tensor, guidance: Union[float, Tensor], *, eta: float = 1.0, norm_threshold: float = float("inf"),
+                  momentum: float = 0.0, rescale: float = 0.0, state: Optional[Tensor] = None) -> Tensor:
+    """Guidance rescale and adaptive projected guidance (APG) of the two-pass outputs ref = D_u and d = D_c, same-shaped (B, ...), in one
+    launch; every sum runs over one sample (hdmoe_guide_combine, include/hdmoe.h, has the formulas):
+      M = (D_c - D_u) + momentum * state (state <- M, float32, in place; momentum == 0: no state is read or written),
+      out = f (a D_c + b M): b = (w - 1) min(1, norm_threshold / |M|), a = 1 - b (1 - eta) <M, D_c> / |D_c|^2,
+      f = rescale * std(D_c) / std(a D_c + b M) + 1 - rescale.
+    guidance: w, a float, or a (B,) float32 CUDA tensor read on the device.  eta = 1, norm_threshold = inf, momentum = 0, rescale = 0 is
+    (1 - w) D_u + w D_c.  Inference only (no gradient)."""
+    if ref.shape != d.shape or ref.dtype != d.dtype or ref.ndim < 1 or ref.numel() == 0:
+        raise ValueError(f"guide_combine: ref {tuple(ref.shape)} {ref.dtype} and d {tuple(d.shape)} {d.dtype} differ (or are empty)")
+    rows = ref.shape[0]
+    eta, r, beta, phi, g, state = _combine_args("guide_combine", guidance, rows, eta, norm_threshold, momentum, rescale, state, ref.shape,
+                                                ref.device)
+    ref, d = _c(ref.detach()), _c(d.detach())
+    out = torch.empty_like(ref)
+    call("hdmoe_guide_combine", out, ref, d, 0.0 if g is not None else float(guidance), g, eta, r, beta, phi, state, rows,
+         ref.numel() // rows, _dt(ref))
+    return out
+
+
+def nhwc_to_nchw_guide_combine(F: Tensor, sf: Tensor, x: Tensor, sx: Tensor, guidance: Union[float, Tensor], *, eta: float = 1.0,
+                               norm_threshold: float = float("inf"), momentum: float = 0.0, rescale: float = 0.0,
+                               state: Optional[Tensor] = None) -> Tensor:
+    """guide_combine as the egress of the pair-stacked head output F (2N, H, W, C) = [conditional ; unconditional]: D_c = sx[n] x[n] +
+    sf[n] F[n] and D_u = sx[n] x[n] + sf[n] F[N + n] are formed in registers, the result is float32 NCHW (N rows); state (momentum != 0):
+    (N, C, H, W) float32.  Inference only."""
+    F = _c(F.detach())
+    N2, H, W, C = F.shape
+    if N2 % 2 or x.shape != (N2 // 2, C, H, W):
+        raise ValueError(f"nhwc_to_nchw_guide_combine: F {tuple(F.shape)} is not a pair-stacked batch of x {tuple(x.shape)}")
+    N = N2 // 2
+    eta, r, beta, phi, g, state = _combine_args("nhwc_to_nchw_guide_combine", guidance, N, eta, norm_threshold, momentum, rescale, state,
+                                                (N, C, H, W), F.device)
+    out = torch.empty((N, C, H, W), dtype=torch.float32, device=F.device)
+    call("hdmoe_nhwc_to_nchw_guide_combine", out, F, _f32(sf.detach()), _f32(x.detach()), _f32(sx.detach()),
+         0.0 if g is not None else float(guidance), g, eta, r, beta, phi, state, N, C, H * W, _dt(F))
+    return out
+
+
 class _PatchRelayoutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tok, meta):

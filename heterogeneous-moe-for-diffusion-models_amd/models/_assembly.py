@@ -409,11 +409,14 @@ class _PrecondBase(nn.Module):
             wbank.deactivate()
 
     def _forward_guided(self, x: Tensor, sigma: Tensor, text_emb: Tensor, uncond_text_emb: Optional[Tensor], guidance: Union[float, Tensor],
-                        Unet_router_mask: Tensor, Vit_router_mask: Tensor, zeta, **kw):
+                        Unet_router_mask: Tensor, Vit_router_mask: Tensor, zeta, guide_combine=None, **kw):
         """The classifier-free-guidance evaluation (1 - g) D(x; uncond) + g D(x; text) as ONE pass with shared routing (inference only):
         net._fwd_guided on the pair-stacked batch, the guided D_x formed by the egress kernel.  uncond_text_emb None: the unconditional
         branch is the conditional one (the reference's ref.lerp(D, g) with ref = D), i.e. the plain evaluation.
-        guidance: a float, or a (B,) tensor of per-sample scales; only the egress reads it, nothing else in the pass depends on it."""
+        guidance: a float, or a (B,) tensor of per-sample scales; only the egress reads it, nothing else in the pass depends on it.
+        guide_combine: None, or the record (eta, norm_threshold, momentum, rescale, state) of ops.nhwc_to_nchw_guide_combine: the egress
+        is then that kernel (projected guidance and rescale of the two outputs, state = the (B, C, H, W) float32 momentum buffer or None).
+        With uncond_text_emb None the two outputs coincide and the record changes nothing: the plain evaluation, the buffer untouched."""
         if isinstance(guidance, Tensor) and (tuple(guidance.shape) != (x.shape[0],) or not guidance.is_floating_point()):
             raise ValueError(f"guidance must be a float or a floating-point tensor of shape ({x.shape[0]},), got {tuple(guidance.shape)} "
                              f"{guidance.dtype}")
@@ -438,7 +441,12 @@ class _PrecondBase(nn.Module):
                                                                          Unet_router_mask, Vit_router_mask, zeta, **kw)
             if isinstance(guidance, Tensor):
                 guidance = guidance.detach().to(device=x32.device, dtype=torch.float32)
-            D_x = ops.nhwc_to_nchw_guided(out, c_out, x32, ops.mul(c_skip, c_in), guidance)
+            if guide_combine is None:
+                D_x = ops.nhwc_to_nchw_guided(out, c_out, x32, ops.mul(c_skip, c_in), guidance)
+            else:
+                eta, r, beta, phi, state = guide_combine
+                D_x = ops.nhwc_to_nchw_guide_combine(out, c_out, x32, ops.mul(c_skip, c_in), guidance, eta=eta, norm_threshold=r,
+                                                     momentum=beta, rescale=phi, state=state)
         finally:
             wbank.deactivate()
         return {"denoised": D_x, "Unet_router_loss": p_u, "Unet_raw": raw_u, "vit_router_loss": p_v, "vit_raw": raw_v,

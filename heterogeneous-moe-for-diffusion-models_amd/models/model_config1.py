@@ -65,7 +65,10 @@ class preconditioned_HDMOEM(_PrecondBase):
         return self._forward(x, sigma, text_emb, Unet_router_mask, Vit_router_mask, zeta, return_log_var)
 
     def forward_guided(self, x: Tensor, sigma: Tensor, text_emb: Tensor, uncond_text_emb: Optional[Tensor], guidance: Union[float, Tensor],
-                       Unet_router_mask: Tensor, Vit_router_mask: Tensor, zeta: float):
+                       Unet_router_mask: Tensor, Vit_router_mask: Tensor, zeta: float, guide_combine=None):
         """(1 - guidance) D(x; uncond_text_emb) + guidance D(x; text_emb) in one shared-routing pass (models/_assembly.py); inference only.
-        guidance: a float, or a (B,) tensor of per-sample scales (read on the device by the egress kernel)."""
-        return self._forward_guided(x, sigma, text_emb, uncond_text_emb, guidance, Unet_router_mask, Vit_router_mask, zeta)
+        guidance: a float, or a (B,) tensor of per-sample scales (read on the device by the egress kernel).
+        guide_combine: None, or (eta, norm_threshold, momentum, rescale, state): projected guidance and rescale in the egress
+        (ops.nhwc_to_nchw_guide_combine) instead of the plain blend."""
+        return self._forward_guided(x, sigma, text_emb, uncond_text_emb, guidance, Unet_router_mask, Vit_router_mask, zeta,
+                                    guide_combine=guide_combine)

@@ -362,6 +362,24 @@ int hdmoe_nhwc_to_nchw_guided_rows(float* out, const void* F, const float* sf, c
  * pointers are aligned -- a vector never holds elements of two rows -- else element by element.  A constant vector gives the bits of
  * hdmoe_axpby(out, ref, d, 1 - g, g) where both take the same path (always, when per is a multiple of the vector width). */
 int hdmoe_lerp_rows(void* out, const void* ref, const void* d, const float* g, long rows, long per, int dtype, HS stream);
+/* Guidance combine: rescale and projected guidance (APG) in one launch, one workgroup per sample, all sums over the sample's `per` elements.
+ * With D_c = d[n], D_u = ref[n], w = g_rows ? g_rows[n] : g (g_rows: DEVICE memory or NULL):
+ *   M   = (D_c - D_u) + beta M_prev                       fp32; M_prev = momentum[n] (fp32, read and overwritten by M); beta == 0: the
+ *                                                         buffer is neither read nor written and may be NULL, beta != 0 needs it
+ *   S1 = sum M^2, S2 = sum M D_c, S3 = sum D_c^2, T1 = sum D_c, T2 = sum M          accumulated in fp64
+ *   s   = sqrt(S1) > r ? r / sqrt(S1) : 1;   c = S3 == 0 ? 0 : S2 / S3;   b = (w - 1) s;   a = 1 - b (1 - eta) c               (fp64)
+ *   rho = sqrt(var(D_c) / var(a D_c + b M)) from the five sums, 1 when a variance is <= 0;   f = phi rho + (1 - phi)            (fp64)
+ *   out = fl(f a) D_c + fl(f b) M                         fp32, rounded once to the output dtype
+ * eta = 1, r = inf, beta = 0, phi = 0 is (1 - w) D_u + w D_c.  Samples of at most HDMOE_GUIDE_COMBINE_RESIDENT elements stay in registers
+ * across the reduction (every operand read once); larger ones re-read their operands after it.  16-byte accesses when per is a multiple
+ * of the vector width and the pointers are aligned, else element by element.  dtype: of ref, d and out (fp32 / bf16). */
+#define HDMOE_GUIDE_COMBINE_RESIDENT 16384
+int hdmoe_guide_combine(void* out, const void* ref, const void* d, float g, const float* g_rows, float eta, float r, float beta, float phi,
+                        float* momentum, long rows, long per, int dtype, HS stream);
+/* The same on the pair-stacked head output F (2N, H, W, C) of the shared-routing pass: D_c = sx[n] x[n] + sf[n] F[n] and
+ * D_u = sx[n] x[n] + sf[n] F[N + n] are formed in registers and never written; out and momentum are fp32 NCHW, per = C HW.  dtype: of F. */
+int hdmoe_nhwc_to_nchw_guide_combine(float* out, const void* F, const float* sf, const float* x, const float* sx, float g, const float* g_rows,
+                                     float eta, float r, float beta, float phi, float* momentum, int N, int C, long HW, int dtype, HS stream);
 int hdmoe_patch_relayout(void* out, const void* in, int N, int H, int W, int C, int p, int hp, int wp, int order,
                          int to_img, int dtype, HS stream);                                                      /* PixelShuffle / patchify */
 /* The same bytes for order 1 (PixelShuffle) by a tiled transpose through LDS, 16-byte accesses on both sides (csrc/relayout.hip).

@@ -9,8 +9,11 @@ place), for a same-box comparison in the manner of tools/ab_trees.sh.
 --interval LO HI adds, per solver and guidance mode, a leg with guidance_interval=(LO, HI) (guided only where LO <= sigma <= HI, the plain
 evaluation elsewhere), its counts of guided and plain evaluations, and the prediction n_guided t_guided + n_plain t_floor from the same
 run's per-evaluation times of the always-guided and the floor leg.
-usage: sampler_guidance_bench.py [--batch 128] [--steps 40] [--reps 3] [--guidance 2.0] [--interval LO HI] [--root DIR] [--no-shared]
-       [--out FILE]"""
+--combine adds, per solver and guidance mode, three legs whose guided evaluations blend through the combine kernel (guidance rescale 0.7;
+APG with eta 0, norm threshold 15, momentum -0.5; both), each next to the plain-guided leg of the same run: imgs/s against it, the extra
+ms per evaluation, and the plain leg's spread over the repetitions, which is what that difference has to be read against.
+usage: sampler_guidance_bench.py [--batch 128] [--steps 40] [--reps 3] [--guidance 2.0] [--interval LO HI] [--combine] [--root DIR]
+       [--no-shared] [--out FILE]"""
 import argparse
 import collections
 import json
@@ -36,6 +39,7 @@ ap.add_argument("--steps", type=int, default=40)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--guidance", type=float, default=2.0)
 ap.add_argument("--interval", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="add guidance-interval legs")
+ap.add_argument("--combine", action="store_true", help="add guidance-rescale / APG legs (the combine kernel)")
 ap.add_argument("--root", default=None, help="time the package of this checkout instead of the one the tool lives in")
 ap.add_argument("--no-shared", action="store_true", help="floor and two-pass only (a checkout without shared_guidance)")
 ap.add_argument("--out", default=None, help="also write the JSON line to this file")
@@ -62,6 +66,12 @@ if args.no_shared:
 if args.interval is not None:                                       # an interval leg behind each always-guided one
     guides.update({gm + "_interval": dict(gkw, guidance_interval=tuple(args.interval)) for gm, gkw in list(guides.items())
                    if gm != "floor"})
+COMBINE = {"rescale": dict(guidance_rescale=0.7), "apg": dict(apg_eta=0.0, apg_norm_threshold=15.0, apg_momentum=-0.5)}
+COMBINE["both"] = dict(COMBINE["rescale"], **COMBINE["apg"])
+combine_legs = {}
+if args.combine:                                                    # three combine legs behind each always-guided one
+    combine_legs = {f"{gm}_{leg}": gm for gm in [gm for gm in ("two_pass", "shared") if gm in guides] for leg in COMBINE}
+    guides.update({name: dict(guides[gm], **COMBINE[name[len(gm) + 1:]]) for name, gm in combine_legs.items()})
 samplers = {(sv, gm): EDM_Sampler(model, Guide_net=model, num_solve_steps=N, use_graph=True, **skw, **gkw)
             for sv, (skw, _, _) in solvers.items() for gm, gkw in guides.items()}
 times = {k: [] for k in samplers}
@@ -81,15 +91,16 @@ with torch.no_grad():
     # library calls of ONE eager guided evaluation (the second one: the first may prepare weight images)
     launches = {}
     sig = torch.tensor(1.3, device="cuda")
-    for gm in [gm for gm in ("two_pass", "shared") if gm in guides]:
+    for gm in [gm for gm in ("two_pass", "shared", "two_pass_both", "shared_both") if gm in guides]:
         s = EDM_Sampler(model, Guide_net=model, num_solve_steps=N, **guides[gm])
-        s.denoise(noise, sig, text, -1.2, 1.2, unc)
+        ms = dict(momentum_state=torch.zeros_like(noise)) if gm in combine_legs else {}
+        s.denoise(noise, sig, text, -1.2, 1.2, unc, **ms)
         _lib.CALL_LOG = []
-        s.denoise(noise, sig, text, -1.2, 1.2, unc)
+        s.denoise(noise, sig, text, -1.2, 1.2, unc, **ms)
         log, _lib.CALL_LOG = collections.Counter(name for name, _ in _lib.CALL_LOG), None
         launches[gm] = dict(total=sum(log.values()), **{n: log[n] for n in (
             "hdmoe_router_head_fwd", "hdmoe_dispatch_plan", "hdmoe_gather_rows", "hdmoe_gather_rows_paired", "hdmoe_nhwc_to_nchw",
-            "hdmoe_nhwc_to_nchw_guided", "hdmoe_axpby", "hdmoe_conv_fwd")})
+            "hdmoe_nhwc_to_nchw_guided", "hdmoe_axpby", "hdmoe_conv_fwd", "hdmoe_guide_combine", "hdmoe_nhwc_to_nchw_guide_combine")})
 res = {}
 for sv, (_, n_eval, _) in solvers.items():
     r = {}
@@ -105,6 +116,12 @@ for sv, (_, n_eval, _) in solvers.items():
         pred = (ev["guided"] * r[base]["ms_per_eval"] + ev["plain"] * r["floor"]["ms_per_eval"]) / 1e3
         r[gm].update(evaluations=ev, predicted_s=round(pred, 4), measured_vs_predicted=round(r[gm]["s"] / pred, 3),
                      vs_always_guided_s=round(r[gm]["s"] / r[base]["s"], 3))
+    for gm, base in combine_legs.items():                           # next to the plain-guided leg of the same run
+        r[gm].update(vs_plain_imgs_per_s=round(r[gm]["imgs_per_s"] / r[base]["imgs_per_s"], 4),
+                     extra_ms_per_eval=round(r[gm]["ms_per_eval"] - r[base]["ms_per_eval"], 3),
+                     plain_spread_ms_per_eval=r[base]["spread_ms_per_eval"])
+        d = (outs[(sv, gm)] - outs[(sv, base)]).abs().max() / outs[(sv, base)].abs().max()
+        r[gm]["vs_plain_max_rel_diff"] = float(f"{float(d):.3e}")
     r["two_pass_vs_floor_ms_per_eval"] = round(r["two_pass"]["ms_per_eval"] / r["floor"]["ms_per_eval"], 3)
     if "shared" in guides:
         r["shared_vs_two_pass_imgs_per_s"] = round(r["shared"]["imgs_per_s"] / r["two_pass"]["imgs_per_s"], 3)
@@ -112,7 +129,7 @@ for sv, (_, n_eval, _) in solvers.items():
         d = (outs[(sv, "shared")] - outs[(sv, "two_pass")]).abs().max() / outs[(sv, "two_pass")].abs().max()
         r["shared_vs_two_pass_max_rel_diff"] = float(f"{float(d):.3e}")
     res[sv] = r
-line = json.dumps(dict(metric="sampler_guidance", root=os.path.relpath(ROOT, os.getcwd()), B=B, N=N, guidance=G, interval=args.interval, reps=args.reps, launches_per_guided_eval=launches, **res))
+line = json.dumps(dict(metric="sampler_guidance", root=os.path.relpath(ROOT, os.getcwd()), B=B, N=N, guidance=G, interval=args.interval, combine=COMBINE if args.combine else None, reps=args.reps, launches_per_guided_eval=launches, **res))
 print(line)
 if args.out:
     with open(args.out, "w") as f:
