@@ -40,6 +40,16 @@ weights the parallel part by eta, clamps the update's norm and gives it a moment
 the blend of every guided evaluation into ONE launch of the combine kernel (``ops.guide_combine`` two-pass, the egress
 ``ops.nhwc_to_nchw_guide_combine`` with shared_guidance); the momentum lives in a device buffer of the stage state, so captured stages
 replay it.  With the defaults no launch changes.
+
+Composed guidance over several prompts (extension, opt-in; ``sample()`` / ``denoise()`` keywords ``compose_text``, ``compose_weights``,
+``compose_masks``).  K conditions -- ``text_emb`` and the K - 1 of ``compose_text`` -- with per-sample weights a and optional spatial masks
+m in [0, 1] over the latent positions stand in for the one conditional output (composable diffusion, Liu et al. 2022):
+D_c = D_u + sum_k a_k m_k (D_k - D_u); prompt blending, negative prompts (a_k < 0) and regional prompts are its cases.  D_c then takes the
+place of the conditional output in everything above: the scale, per-sample scales, the interval, rescale and APG.  With
+``shared_guidance`` an evaluation is ONE ``model.forward_composed`` pass -- the routing once, the K + 1 text variants stacked through the
+banks and the tail, D_c formed in the egress kernel; otherwise K passes of the model, one of the guide network and ONE launch of
+``ops.guide_compose``.  D_c needs D_u, so an evaluation outside the guidance interval is the composed evaluation at scale 1 (out = D_c),
+not one plain call.  Without the keywords nothing changes.
 """
 import math
 import numbers
@@ -116,14 +126,17 @@ class EDM_Sampler:
 
     # reference Utils/EDM_sampler.py:35-70
     def denoise(self, x, sigma, text_emb, transition_mean, softness, uncond_text_emb=None, Unet_router_mask=None, Vit_router_mask=None,
-                guidance=None, guided=True, momentum_state=None):
+                guidance=None, guided=True, momentum_state=None, compose_text=None, compose_weights=None, compose_masks=None):
         """One (guided) denoiser evaluation.  Router masks: (B, E) or (E,) with {0, 1} entries, None = every expert allowed (the reference).
         With shared_guidance a guided evaluation is one model.forward_guided pass (inference: call it under torch.no_grad()).
         guidance: None = the sampler's float scale, or a (B,) tensor of finite per-sample scales (any device).  guided=False: the single
         plain conditional evaluation, whatever the scale.  denoise() never reads sigma: whether an evaluation lies in guidance_interval is
         the solver's decision (sample()), handed down as `guided`.
         momentum_state: the APG momentum buffer, a contiguous (B, C, H, W) float32 tensor on x's device, updated in place by a guided
-        evaluation (zero it before the first evaluation of a trajectory).  apg_momentum != 0 needs it; otherwise it is not used."""
+        evaluation (zero it before the first evaluation of a trajectory).  apg_momentum != 0 needs it; otherwise it is not used.
+        compose_text / compose_weights / compose_masks: composed guidance, see sample(); guided=False is then D_c, the composed
+        evaluation at scale 1."""
+        comp = self._check_compose(x, text_emb, uncond_text_emb, compose_text, compose_weights, compose_masks)
         um = self._router_mask(Unet_router_mask, "Unet_router_mask", x.shape[0])
         vm = self._router_mask(Vit_router_mask, "Vit_router_mask", x.shape[0])
         g = self._check_guidance(guidance, x.shape[0])
@@ -138,13 +151,16 @@ class EDM_Sampler:
         else:
             momentum_state = None
         return self._denoise(x, sigma, text_emb, transition_mean, softness, uncond_text_emb, self._dev_mask(um, x), self._dev_mask(vm, x),
-                             bool(guided), self._dev_mask(g, x), momentum_state)
+                             bool(guided), self._dev_mask(g, x), momentum_state, self._dev_compose(comp, x, text_emb))
 
-    def _denoise(self, x, sigma, text_emb, transition_mean, softness, uncond_text_emb, um=None, vm=None, guided=True, g=None, mom=None):
+    def _denoise(self, x, sigma, text_emb, transition_mean, softness, uncond_text_emb, um=None, vm=None, guided=True, g=None, mom=None,
+                 comp=None):
         """denoise() on validated device masks (or None) and a validated (B,) float32 device vector of scales g (or None: self.guide): no
         host read, so it can run under stream capture.  guided False, or a float scale of 1: one plain conditional call.
         With guidance rescale / APG (combine_params()) the blend of a guided evaluation is the combine kernel; mom: its momentum buffer
-        (apg_momentum != 0), read and written by guided evaluations only."""
+        (apg_momentum != 0), read and written by guided evaluations only.
+        comp: None, or the device operands (texts (K, B, ...), weights (B, K), masks (B, K, H, W) or None) of composed guidance; text_emb
+        is then texts[0] and is not read."""
         bs = x.shape[0]
         num_experts = self.model.num_experts
         Unet_router_mask = torch.ones((bs, num_experts), device=x.device) if um is None else um
@@ -153,6 +169,19 @@ class EDM_Sampler:
                   transition_point=transition_mean, softness=softness)
         active = guided and (g is not None or self.guide != 1.0)
         comb = self.combine_params() if active else None
+        if comp is not None:
+            # composed guidance: D_c of the K conditions takes the conditional output's place.  Not active (the interval, guided=False,
+            # a float scale of 1): the same evaluation at scale 1 with the identity scalars, out = D_c, the momentum untouched
+            texts, cw, cm = comp
+            gd = (self.guide if g is None else g) if active else 1.0
+            eta, r, beta, phi = comb if comb is not None else (1.0, float("inf"), 0.0, 0.0)
+            if self.shared_guidance:
+                self._check_shared(composed=True)
+                return self.model.forward_composed(text_embs=texts, uncond_text_emb=uncond_text_emb, weights=cw, masks=cm, guidance=gd,
+                                                   guide_combine=None if comb is None else comb + (mom,), **kw)["denoised"].to(self.dtype)
+            ds = [self.model(text_emb=texts[k], **kw)["denoised"].to(self.dtype) for k in range(texts.shape[0])]
+            ref_D_x = self.gnet(text_emb=uncond_text_emb, **kw)["denoised"].to(self.dtype)
+            return ops.guide_compose(ref_D_x, ds, cw, cm, gd, eta=eta, norm_threshold=r, momentum=beta, rescale=phi, state=mom)
         if self.shared_guidance and active:
             # one pass: routing (and so the router masks) once, both text variants through the banks and the tail, the lerp in the egress
             self._check_shared()
@@ -175,11 +204,14 @@ class EDM_Sampler:
         return ops.axpby(ref_D_x, D_x, 1.0 - self.guide, self.guide)
 
     # ---- argument checks of the extensions: ValueError naming the argument, before any device work ------------------------------------
-    def _check_shared(self):
+    def _check_shared(self, composed=False):
         """shared_guidance shares the routing of ONE network between the two text variants: the guide network must be the model itself,
-        and the model must have the shared pass."""
+        and the model must have the shared pass (composed: the pass over K + 1 variants, forward_composed)."""
         if not self.shared_guidance:
             return
+        if composed and not callable(getattr(self.model, "forward_composed", None)):
+            raise ValueError(f"shared_guidance=True with compose_text / compose_weights / compose_masks needs a model with "
+                             f"forward_composed(); {type(self.model).__name__} has none")
         if self.gnet is not self.model:
             raise ValueError("shared_guidance=True needs Guide_net to be the model itself (a different guide network takes two passes)")
         if not callable(getattr(self.model, "forward_guided", None)):
@@ -240,6 +272,64 @@ class EDM_Sampler:
         if not bool(torch.isfinite(h).all()):
             raise ValueError("guidance entries must be finite")
         return h
+
+    @staticmethod
+    def _check_compose(x, text_emb, uncond_text_emb, compose_text, compose_weights, compose_masks):
+        """The composed-guidance keywords of sample() / denoise(): None when none of the three is given, else (extra, weights, masks) --
+        the (K - 1, B, ...) further conditions, the (B, K) float32 weights (default: ones) and the (B, K, H, W) float32 masks or None.
+        The rule for K = 1: composition over text_emb alone is legal, but has to be asked for with an explicit EMPTY compose_text of shape
+        (0,) + text_emb.shape; weights or masks with compose_text=None are refused (a forgotten compose_text is the likelier cause)."""
+        if compose_text is None and compose_weights is None and compose_masks is None:
+            return None
+        if compose_text is None:
+            raise ValueError("compose_text is missing: compose_weights / compose_masks need it (for K = 1, the weights or masks on text_emb "
+                             f"alone, pass an empty compose_text of shape {(0,) + tuple(text_emb.shape)})")
+        want = tuple(text_emb.shape)
+        if not isinstance(compose_text, torch.Tensor) or not compose_text.is_floating_point() or tuple(compose_text.shape[1:]) != want \
+                or compose_text.ndim != len(want) + 1:
+            raise ValueError(f"compose_text must be a floating-point tensor of shape (K - 1,) + {want}, the further conditions stacked, got "
+                             f"{tuple(getattr(compose_text, 'shape', ())) or type(compose_text).__name__}")
+        K = compose_text.shape[0] + 1
+        if K > ops.COMPOSE_MAX:
+            raise ValueError(f"compose_text holds {K - 1} conditions: with text_emb that is K = {K}, above the limit of {ops.COMPOSE_MAX}")
+        if not isinstance(uncond_text_emb, torch.Tensor) or tuple(uncond_text_emb.shape) != want:
+            raise ValueError(f"uncond_text_emb of shape {want} is required with compose_text (D_c is built on the unconditional output), got "
+                             f"{tuple(getattr(uncond_text_emb, 'shape', ())) or type(uncond_text_emb).__name__}")
+        bs = x.shape[0]
+        if compose_weights is None:
+            w = torch.ones((bs, K), dtype=torch.float32)
+        else:
+            if not isinstance(compose_weights, torch.Tensor) or compose_weights.is_complex() or compose_weights.dtype == torch.bool \
+                    or tuple(compose_weights.shape) not in ((bs, K), (K,)):
+                raise ValueError(f"compose_weights must be a real tensor of shape ({bs}, {K}) or ({K},), one weight per condition, got "
+                                 f"{tuple(getattr(compose_weights, 'shape', ())) or type(compose_weights).__name__}")
+            w = compose_weights.detach().to("cpu", torch.float32).expand(bs, K).contiguous()
+            if not bool(torch.isfinite(w).all()):
+                raise ValueError("compose_weights entries must be finite")
+        m = None
+        if compose_masks is not None:
+            hw = tuple(x.shape[2:])
+            if not isinstance(compose_masks, torch.Tensor) or not compose_masks.is_floating_point() \
+                    or compose_masks.ndim not in (3, 4) or tuple(compose_masks.shape[:-2]) not in ((bs, K), (K,)):
+                raise ValueError(f"compose_masks must be a floating-point tensor of shape ({bs}, {K}, H, W) or ({K}, H, W), got "
+                                 f"{tuple(getattr(compose_masks, 'shape', ())) or type(compose_masks).__name__}")
+            if tuple(compose_masks.shape[-2:]) != hw:
+                raise ValueError(f"compose_masks must have the latents' H, W = {hw}, got {tuple(compose_masks.shape[-2:])}")
+            m = compose_masks.detach().to(torch.float32)
+            lo, hi = (float(v) for v in torch.aminmax(m))
+            if not (0.0 <= lo and hi <= 1.0):                 # NaN fails every comparison
+                raise ValueError(f"compose_masks values must be finite and lie in [0, 1], got [{lo}, {hi}]")
+            m = m.expand((bs, K) + hw)
+        return compose_text.detach(), w, m
+
+    @staticmethod
+    def _dev_compose(comp, x, text_emb):
+        """_check_compose's record on x's device as _denoise reads it: (texts (K, B, ...) with text_emb first, weights, masks)."""
+        if comp is None:
+            return None
+        extra, w, m = comp
+        texts = torch.cat([text_emb.detach()[None].to(x.device), extra.to(device=x.device, dtype=text_emb.dtype)])
+        return texts, w.to(x.device).contiguous(), None if m is None else m.to(x.device).contiguous()
 
     def guidance_plan(self, t_steps, i0=0):
         """Which evaluations of sample() lie in guidance_interval: one tuple of bools per stage i = i0 ... N - 1, in the order the stage
@@ -324,7 +414,7 @@ class EDM_Sampler:
         return strength
 
     # ---- static state and hipGraph capture: fused solver stages (reference :90-107 without churn), the captured evaluation ----------------
-    def _stage_state(self, kind, x, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, gvec=None):
+    def _stage_state(self, kind, x, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, gvec=None, comp=None):
         """Static buffers, stage functions and (use_graph) captured graphs of one kind:
           "eval": one guided evaluation of x at sig into out (the host loops' evaluation with use_graph);
           "heun": a full Heun stage and the last, Euler-only stage; "dpm": one DPM-Solver++(2M) stage (den_prev: the previous stage's
@@ -340,10 +430,14 @@ class EDM_Sampler:
         With a guidance interval (and guidance in effect) every stage function exists once per variant -- which of its evaluations are
         guided -- and with use_graph each variant is one graph, all in one pool over the same buffers: "sel" maps a stage's tuple of
         guidance_plan() to its index in "fns" / "g_<kind>", so the interval's bounds are a host selection and not in the key.  Without an
-        interval the lists are the all-guided ones alone: two for "heun" (full, last), one for "dpm" and "eval"."""
+        interval the lists are the all-guided ones alone: two for "heun" (full, last), one for "dpm" and "eval".
+
+        comp (composed guidance): its texts, weights and masks are static buffers ("texts", "cw", "cm") refreshed like every input; only K
+        and whether there are masks are in the key (its second entry)."""
         shape = lambda a: None if a is None else tuple(a.shape)
         variants = self.guidance_interval is not None and (gvec is not None or self.guide != 1.0)
-        key = (kind, self.solver, shape(x), x.dtype, shape(text_emb), shape(uncond_text_emb), float(transition_mean), float(softness),
+        key = (kind, None if comp is None else (int(comp[0].shape[0]), comp[2] is not None), self.solver, shape(x), x.dtype,
+               shape(text_emb), shape(uncond_text_emb), float(transition_mean), float(softness),
                self.num_steps, bool(self.use_graph), None if known is None else tuple(map(shape, known)), shape(um), shape(vm),
                float(self.guide), id(self.model), id(self.gnet), float(self.s_churn), float(self.s_min), float(self.s_max), float(self.s_noise),
                float(self.eta), bool(self.churn_on_device), self.combine_params(), gvec is not None, variants, bool(self.shared_guidance))
@@ -357,12 +451,15 @@ class EDM_Sampler:
         st = dict(key=key, x=torch.empty_like(x), sig=torch.ones((), dtype=self.dtype, device=dev), text=torch.empty_like(text_emb),
                   unc=opt(uncond_text_emb), known=None if known is None else tuple(map(torch.empty_like, known)), um=opt(um), vm=opt(vm),
                   g=opt(gvec), variants=variants, mods=(self.model, self.gnet),
-                  mom=torch.zeros(x.shape, dtype=torch.float32, device=dev) if self._needs_momentum(gvec) else None)
-        self._refresh(st, x, text_emb, uncond_text_emb, known, um, vm, gvec=gvec)
+                  mom=torch.zeros(x.shape, dtype=torch.float32, device=dev) if self._needs_momentum(gvec) else None,
+                  texts=None if comp is None else torch.empty_like(comp[0]), cw=None if comp is None else torch.empty_like(comp[1]),
+                  cm=None if comp is None else opt(comp[2]))
+        self._refresh(st, x, text_emb, uncond_text_emb, known, um, vm, gvec=gvec, comp=comp)
+        st_comp = None if comp is None else (st["texts"], st["cw"], st["cm"])
 
         def den(x_, guided):
             return self._denoise(x_, st["sig"], st["text"], transition_mean, softness, st["unc"], st["um"], st["vm"], guided, st["g"],
-                                 st["mom"])
+                                 st["mom"], st_comp)
 
         def pick(j):                                          # sig = t[idx + j]
             ops.call("hdmoe_sched_pick", st["sig"], st["t"], st["idx"], j)
@@ -446,7 +543,7 @@ class EDM_Sampler:
         return graphs
 
     @staticmethod
-    def _refresh(st, x, text_emb, uncond_text_emb, known, um, vm, seed=None, gvec=None, reset_momentum=True):
+    def _refresh(st, x, text_emb, uncond_text_emb, known, um, vm, seed=None, gvec=None, reset_momentum=True, comp=None):
         """Every input into the static buffers: a later sample() with another prompt of the same shape must not see the captured one.
         seed: the 64-bit seed of this call's stochastic stages (a buffer value like the others, never part of the capture key).
         reset_momentum: zero the APG momentum -- the start of a sample() call (the warm-up runs of a capture have written it too); the
@@ -462,6 +559,9 @@ class EDM_Sampler:
                 st[name].copy_(src)
         for buf, src in zip(st["known"] or (), known or ()):
             buf.copy_(src)
+        for name, src in zip(("texts", "cw", "cm"), comp or ()):      # composed guidance: (texts, weights, masks or None)
+            if st[name] is not None:
+                st[name].copy_(src)
 
     @staticmethod
     def _eps(x, seed, stage):
@@ -470,7 +570,7 @@ class EDM_Sampler:
         return eps.to(x.dtype)
 
     def _dpm_host_loop(self, x, t_steps, i0, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, seed=None, plan=None,
-                       gvec=None, mom=None):
+                       gvec=None, mom=None, comp=None):
         """solver="dpmpp_2m" / "dpmpp_2m_sde" for latents the fused stage does not take (non-fp32 dtype): the rule of sample() with host
         coefficients."""
         N = self.num_steps
@@ -479,7 +579,7 @@ class EDM_Sampler:
         for i in range(i0, N):
             t_cur, t_next = float(t_steps[i]), float(t_steps[i + 1])
             den = self._eval(x, t_cur, text_emb, transition_mean, softness, uncond_text_emb, um, vm,
-                             True if plan is None else plan[i - i0][0], gvec, mom, first=i == i0)
+                             True if plan is None else plan[i - i0][0], gvec, mom, first=i == i0, comp=comp)
             e = math.exp(-self.eta * math.log(t_cur / t_next)) if sde and t_next > 0 else 1.0
             a = t_next / t_cur * e
             if t_next == 0:
@@ -497,14 +597,14 @@ class EDM_Sampler:
         return x
 
     def _eval(self, x, t, text_emb, transition_mean, softness, uncond_text_emb, um=None, vm=None, guided=True, gvec=None, mom=None,
-              first=False):
+              first=False, comp=None):
         """One evaluation at sigma t of the host loops; guided: the solver's guidance-interval decision for it.  mom: the call's APG
         momentum buffer (eager); the captured evaluation carries its own, zeroed on the first evaluation of a call."""
         if not self.use_graph:
             sig = torch.tensor(t, dtype=self.dtype, device=x.device)
-            return self._denoise(x, sig, text_emb, transition_mean, softness, uncond_text_emb, um, vm, guided, gvec, mom)
-        st = self._stage_state("eval", x, text_emb, transition_mean, softness, uncond_text_emb, None, um, vm, gvec)
-        self._refresh(st, x, text_emb, uncond_text_emb, None, um, vm, gvec=gvec, reset_momentum=first)
+            return self._denoise(x, sig, text_emb, transition_mean, softness, uncond_text_emb, um, vm, guided, gvec, mom, comp)
+        st = self._stage_state("eval", x, text_emb, transition_mean, softness, uncond_text_emb, None, um, vm, gvec, comp)
+        self._refresh(st, x, text_emb, uncond_text_emb, None, um, vm, gvec=gvec, reset_momentum=first, comp=comp)
         st["sig"].fill_(float(t))
         guided = bool(guided) or not st["variants"]
         st["g_eval"][st["sel"][(guided,)]].replay()
@@ -521,7 +621,8 @@ class EDM_Sampler:
     def sample(self, noise: torch.Tensor, text_emb: torch.Tensor, transition_mean: float, softness: float,
                uncond_text_emb: torch.Tensor = None, *, init_latents: torch.Tensor = None, strength: float = 1.0,
                inpaint_mask: torch.Tensor = None, Unet_router_mask: torch.Tensor = None, Vit_router_mask: torch.Tensor = None,
-               seed: int = None, guidance: torch.Tensor = None) -> torch.Tensor:
+               seed: int = None, guidance: torch.Tensor = None, compose_text: torch.Tensor = None, compose_weights: torch.Tensor = None,
+               compose_masks: torch.Tensor = None) -> torch.Tensor:
         """Solve of the probability-flow ODE over t = t_schedule() (N = num_solve_steps, t[N] = 0): Heun (solver="heun", the reference),
         or DPM-Solver++(2M) (solver="dpmpp_2m", one evaluation per stage).
 
@@ -575,7 +676,18 @@ class EDM_Sampler:
             O = D_c + (w - 1) s (M - (1 - apg_eta) c D_c);   out = (guidance_rescale std(D_c) / std(O) + 1 - guidance_rescale) O
         (apg_eta None: eta = 1, no clamp, no momentum, i.e. O = (1 - w) D_u + w D_c).  M_prev is zero at the start of every call and is
         updated by the guided evaluations in the order the solver makes them; evaluations outside guidance_interval leave it alone.
+
+        compose_text / compose_weights / compose_masks (composed guidance; all None: off).  The K conditions are text_emb and the K - 1
+        rows of compose_text, (K - 1, B, S, D), K <= 8; uncond_text_emb is required.  compose_weights: (B, K) or (K,), finite, any sign,
+        default ones; compose_masks: (B, K, H, W) or (K, H, W) in [0, 1] at the latents' H, W, default none.  Per element, in fp32,
+            c_k = weights[n, k] masks[n, k, p];   c_0 = 1 - sum_k c_k;   D_c = c_0 D_u + sum_k c_k D_k
+        and D_c replaces the conditional output D_c in the formulas above (scale, per-sample scales, rescale, APG).  An evaluation outside
+        guidance_interval is out = D_c (the same evaluation at scale 1, momentum untouched): guidance_plan and last_evaluations keep their
+        meaning, but a "plain" evaluation costs what a guided one does.  K = 1 (weights or masks on text_emb alone) has to be asked for
+        with an empty compose_text of shape (0, B, S, D); weights or masks without compose_text are refused.  With use_graph the extra
+        text, the weights and the masks are static buffers: other values of the same K replay the same capture.
         Argument errors raise ValueError (naming the argument) before any device work."""
+        comp = self._check_compose(noise, text_emb, uncond_text_emb, compose_text, compose_weights, compose_masks)
         strength = self._check_conditioning(noise, init_latents, strength, inpaint_mask)
         seed = self._check_seed(seed)
         bs = noise.shape[0]
@@ -594,6 +706,7 @@ class EDM_Sampler:
         i0 = N - math.ceil(strength * N)
         t_steps = self.t_schedule(device)
         um, vm, gvec = self._dev_mask(um, noise), self._dev_mask(vm, noise), self._dev_mask(gvec, noise)
+        comp = self._dev_compose(comp, noise, text_emb)
         # the guidance-interval decision of every evaluation, taken here, on the host, from the float64 sigmas: denoise() never reads sigma
         plan = self.guidance_plan(t_steps, i0)
         n_eval = sum(map(len, plan))
@@ -617,8 +730,8 @@ class EDM_Sampler:
             kind = "heun" if self.fused_heun else "dpm"
             if seed is None and (self.s_churn > 0 or (self.solver == "dpmpp_2m_sde" and self.eta > 0)):
                 seed = ops.next_seed()                        # a stochastic stage: one value of the library's stream per call
-            st = self._stage_state(kind, x_next, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, gvec)
-            self._refresh(st, x_next, text_emb, uncond_text_emb, known, um, vm, seed, gvec)
+            st = self._stage_state(kind, x_next, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, gvec, comp)
+            self._refresh(st, x_next, text_emb, uncond_text_emb, known, um, vm, seed, gvec, comp=comp)
             st["t"].copy_(torch.from_numpy(t_steps))
             st["idx"].fill_(i0)
             if self.fused_dpm:
@@ -631,7 +744,7 @@ class EDM_Sampler:
         mom = torch.zeros(x_next.shape, dtype=torch.float32, device=device) if self._needs_momentum(gvec) and not self.use_graph else None
         if self.solver != "heun":
             return self._dpm_host_loop(x_next, t_steps, i0, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, seed, plan,
-                                       gvec, mom)
+                                       gvec, mom, comp)
         for i in range(i0, N):
             t_cur, t_next = float(t_steps[i]), float(t_steps[i + 1])
             x_cur = x_next
@@ -641,14 +754,14 @@ class EDM_Sampler:
             if gamma > 0:
                 x_hat = ops.axpby(x_cur, self._eps(x_cur, seed, i), 1.0, float(np.sqrt(t_hat ** 2 - t_cur ** 2) * self.s_noise))
             denoised = self._eval(x_hat, t_hat, text_emb, transition_mean, softness, uncond_text_emb, um, vm, plan[i - i0][0], gvec, mom,
-                                  first=i == i0)
+                                  first=i == i0, comp=comp)
             # d_cur = (x_hat - denoised)/t_hat ; x_next = x_hat + (t_next - t_hat) * d_cur
             h = (t_next - t_hat)
             x_next = ops.axpby(x_hat, denoised, 1.0 + h / t_hat, -h / t_hat)
             if known is not None:
                 ops.known_blend_(x_next, *known, t_next)
             if i < self.num_steps - 1:
-                den2 = self._eval(x_next, t_next, text_emb, transition_mean, softness, uncond_text_emb, um, vm, plan[i - i0][1], gvec, mom)
+                den2 = self._eval(x_next, t_next, text_emb, transition_mean, softness, uncond_text_emb, um, vm, plan[i - i0][1], gvec, mom, comp=comp)
                 # x_next = x_hat + h * (0.5*d_cur + 0.5*d_prime),  d_prime = (x_next - den2)/t_next
                 d_cur_term = ops.axpby(x_hat, denoised, 1.0 + 0.5 * h / t_hat, -0.5 * h / t_hat)     # x_hat + 0.5 h d_cur
                 d_pr = ops.axpby(x_next, den2, 0.5 * h / t_next, -0.5 * h / t_next)                  # 0.5 h d_prime

@@ -769,6 +769,98 @@ template <int W> DEVI void gc_stf(float* p, const float* f) {
   if constexpr (W == 8) { stw<float, 4>(p, f); stw<float, 4>(p + 4, f + 4); }
   else stw<float, W>(p, f);
 }
+// Composed guidance (hdmoe.h): the two loaders below put D_c = c_0 D_u + sum_k c_k D_k in front of the unchanged combine steps.  K is a
+// run-time count; the coefficients are walked twice (c_0 first, then the sum) so that no array indexed by k has to live in registers.
+// c_k of positions p ... p + W - 1: a[n][k], times the mask plane (n, k) -- mk, a uniform pointer, or null: no masks -- at p (one load:
+// on the W > 1 arm HW % W == 0)
+template <int W> DEVI void gc_coef(float* c, float ak, const float* mk, unsigned p) {
+#pragma clang fp contract(off)
+  if (mk) {
+    float mv[W];
+    gc_ldf<W>(mv, mk + p);
+#pragma unroll
+    for (int j = 0; j < W; ++j) c[j] = ak * mv[j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < W; ++j) c[j] = ak;
+  }
+}
+// c_0 = (((1 - c_1) - c_2) - ...) - c_K;  an: a[n][0 .. K-1], mn: mask plane (n, 0), planes HW apart (or null), p: the vector's position
+template <int W> DEVI void gc_coef0(float* c0, const float* an, const float* mn, int K, unsigned HW, unsigned p) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < W; ++j) c0[j] = 1.f;
+#pragma nounroll                                          // K <= 8 at run time: a rolled loop, the resident arm holds 16 / W copies of it
+  for (int k = 0; k < K; ++k) {
+    float c[W];
+    gc_coef<W>(c, an[k], mn ? mn + (long)k * HW : nullptr, p);
+#pragma unroll
+    for (int j = 0; j < W; ++j) c0[j] = c0[j] - c[j];
+  }
+}
+template <typename T> struct GcCompose {                 // two-pass: ref = D_u, d[k] = D_{k+1}, (B, per) each; a (B, K); m (B, K, HW) or null, per = C HW
+  const T* d[HDMOE_COMPOSE_MAX]; const T* ref; const float* a; const float* m; int K; unsigned HW;
+  struct Cur { unsigned p, dr; };                        // p = e % HW of a thread's current vector (masks only), carried by the step's remainder
+  template <int W> DEVI Cur seek(long e) const {
+    if (!m) return {0u, 0u};
+    return {(unsigned)(e % (long)HW), (unsigned)(((long)GC_TPB * W) % (long)HW)};
+  }
+  DEVI void advance(Cur& k) const {
+    k.p += k.dr;
+    if (k.p >= HW) k.p -= HW;
+  }
+  DEVI void rewind(Cur& k) const { k.p = 0; }
+  template <int W> DEVI void load(float* dc, float* du, long n, long per, long e, const Cur& cur) const {
+#pragma clang fp contract(off)
+    const float* an = a + n * K;
+    const float* mn = m ? m + n * K * (long)HW : nullptr;
+    float c0[W];
+    gc_coef0<W>(c0, an, mn, K, HW, cur.p);
+    ldw<T, W>(du, ref + n * per + e);
+#pragma unroll
+    for (int j = 0; j < W; ++j) dc[j] = c0[j] * du[j];
+#pragma nounroll
+    for (int k = 0; k < K; ++k) {
+      float c[W], dk[W];
+      gc_coef<W>(c, an[k], mn ? mn + (long)k * HW : nullptr, cur.p);
+      ldw<T, W>(dk, d[k] + n * per + e);
+#pragma unroll
+      for (int j = 0; j < W; ++j) dc[j] = dc[j] + c[j] * dk[j];
+    }
+    __builtin_amdgcn_sched_barrier(0);                   // the resident arm unrolls 16 / W of these k loops: keep them apart, or their loads pile up in registers
+  }
+};
+template <typename T> struct GcComposeEgress {           // shared-routing egress of the variant-stacked F ((K + 1) N rows, the last N unconditional):
+  GcEgress<T> eg; int K; const float* a; const float* m;      // D_k = sx x + sf F[k N + n], formed as GcEgress forms its pair; eg.half = N per
+  using Cur = typename GcEgress<T>::Cur;
+  template <int W> DEVI Cur seek(long e) const { return eg.template seek<W>(e); }
+  DEVI void advance(Cur& k) const { eg.advance(k); }
+  DEVI void rewind(Cur& k) const { eg.rewind(k); }
+  template <int W> DEVI void load(float* dc, float* du, long n, long per, long e, const Cur& k) const {
+#pragma clang fp contract(off)
+    const T* f = eg.F + ((long)n * eg.HW + k.p) * eg.C + k.c;
+    const float sf = eg.sf[n], s = eg.sx[n];
+    const float* an = a + n * K;
+    const float* mn = m ? m + n * K * (long)eg.HW : nullptr;
+    float c0[W], t[W];
+    gc_coef0<W>(c0, an, mn, K, eg.HW, k.p);
+    ldw<float, W>(t, eg.x + n * per + e);
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      t[j] = s * t[j];
+      du[j] = t[j] + sf * to_f(f[(long)K * eg.half + (long)j * eg.C]);
+      dc[j] = c0[j] * du[j];
+    }
+#pragma nounroll
+    for (int v = 0; v < K; ++v) {
+      float c[W];
+      gc_coef<W>(c, an[v], mn ? mn + (long)v * eg.HW : nullptr, k.p);
+#pragma unroll
+      for (int j = 0; j < W; ++j) dc[j] = dc[j] + c[j] * (t[j] + sf * to_f(f[(long)v * eg.half + (long)j * eg.C]));
+    }
+    __builtin_amdgcn_sched_barrier(0);                   // as in GcCompose
+  }
+};
 template <typename L, typename TO, int W, bool RES, bool MOM>
 __global__ __launch_bounds__(GC_TPB) void guide_combine_kernel(L ld, TO* out, float* mom, GcPar q, long per) {
 #pragma clang fp contract(off)
@@ -1653,6 +1745,51 @@ int hdmoe_nhwc_to_nchw_guide_combine(float* out, const void* F, const float* sf,
   DT_LAUNCH(dtype, {
     const GcEgress<T> ld{(const T*)F, sf, x, sx, C, (unsigned)HW, (long)N * per};
     GC_LAUNCH(HW % 4 == 0 && al16(out) && al16(x) && al16(mom), 4, GcEgress<T>, float, ld, out, mom, q, (unsigned)N, per);
+  })
+}
+// composed guidance: what both entry points refuse about K, the weights and the masks (masks: HW positions per plane, per = C HW)
+static bool gc_compose_ok(int K, const float* a, const float* m, long HW, long per) {
+  if (K < 1 || K > HDMOE_COMPOSE_MAX || !a) return false;
+  return !m || (HW >= 1 && HW <= 0x7fffffffL && per % HW == 0);
+}
+int hdmoe_guide_compose(void* out, const void* ref, const void* const* d_ptrs, int K, const float* a, const float* m, long HW, float g,
+                        const float* g_rows, float eta, float r, float beta, float phi, float* momentum, long rows, long per, int dtype,
+                        hipStream_t stream) {
+  if (!out || !ref || !d_ptrs || rows < 1 || rows > 0x7fffffffL || per < 1 || !gc_compose_ok(K, a, m, HW, per) ||
+      !gc_args_ok(g, g_rows, eta, r, beta, phi, momentum))
+    return HDMOE_EINVAL;
+  bool al = al16(out) && al16(ref);
+  for (int k = 0; k < K; ++k) {
+    if (!d_ptrs[k]) return HDMOE_EINVAL;
+    al = al && al16(d_ptrs[k]);
+  }
+  const GcPar q{g, g_rows, eta, r, beta, phi};
+  float* mom = beta != 0.f ? momentum : nullptr;
+  DT_LAUNCH(dtype, {
+    GcCompose<T> ld{{}, (const T*)ref, a, m, K, m ? (unsigned)HW : 1u};
+    for (int k = 0; k < K; ++k) ld.d[k] = (const T*)d_ptrs[k];
+    // The element arm always re-reads: its resident form (16 unrolled vectors, each with the two k loops) does not fit the 128 registers
+    // of a 1024-thread workgroup and would spill.  It is the fall-back for odd sizes and unaligned pointers, served from L2.
+    if (per % VT<T>::W == 0 && al && al16(mom) && (!m || (HW % VT<T>::W == 0 && al16(m)))) {
+      if (per <= GC_TPB * GC_R) { GC_ARM(GcCompose<T>, T, VT<T>::W, true, ld, (T*)out, mom, q, (unsigned)rows, per); }
+      else { GC_ARM(GcCompose<T>, T, VT<T>::W, false, ld, (T*)out, mom, q, (unsigned)rows, per); }
+    } else {
+      GC_ARM(GcCompose<T>, T, 1, false, ld, (T*)out, mom, q, (unsigned)rows, per);
+    }
+  })
+}
+int hdmoe_nhwc_to_nchw_compose(float* out, const void* F, const float* sf, const float* x, const float* sx, int K, const float* a, const float* m,
+                               float g, const float* g_rows, float eta, float r, float beta, float phi, float* momentum, int N, int C, long HW,
+                               int dtype, hipStream_t stream) {
+  if (!out || !F || !sf || !x || !sx || N < 1 || C < 1 || HW < 1 || (long)C * HW > 0x7fffffffL || !gc_compose_ok(K, a, m, HW, (long)C * HW) ||
+      !gc_args_ok(g, g_rows, eta, r, beta, phi, momentum))
+    return HDMOE_EINVAL;
+  const GcPar q{g, g_rows, eta, r, beta, phi};
+  float* mom = beta != 0.f ? momentum : nullptr;
+  const long per = (long)C * HW;
+  DT_LAUNCH(dtype, {
+    const GcComposeEgress<T> ld{{(const T*)F, sf, x, sx, C, (unsigned)HW, (long)N * per}, K, a, m};
+    GC_LAUNCH(HW % 4 == 0 && al16(out) && al16(x) && al16(mom) && al16(m), 4, GcComposeEgress<T>, float, ld, out, mom, q, (unsigned)N, per);
   })
 }
 static int relayout_entry(void* out, const void* in, const int* rows, int N, int H, int W, int C, int p, int hp, int wp, int order,

@@ -2416,6 +2416,77 @@ def nhwc_to_nchw_guide_combine(F: Tensor, sf: Tensor, x: Tensor, sx: Tensor, gui
     return out
 
 
+# At most this many conditions in one composed evaluation.  HDMOE_COMPOSE_MAX of include/hdmoe.h.
+COMPOSE_MAX = 8
+
+
+def _compose_args(who: str, weights, masks, rows: int, K: int, spatial, device):
+    """The weights (rows, K) and masks (rows, K, *spatial) or None of a composed evaluation as the kernels read them: float32, contiguous,
+    on `device`.  Their values are the caller's to check (nothing is read from the device here)."""
+    if not 1 <= K <= COMPOSE_MAX:
+        raise ValueError(f"{who}: needs 1 <= K <= {COMPOSE_MAX} conditions, got {K}")
+    if not isinstance(weights, Tensor) or weights.dtype != torch.float32 or tuple(weights.shape) != (rows, K) or weights.device != device:
+        raise ValueError(f"{who}: weights must be a ({rows}, {K}) float32 tensor on {device}, got "
+                         f"{(tuple(weights.shape), weights.dtype, weights.device) if isinstance(weights, Tensor) else type(weights).__name__}")
+    if masks is not None:
+        want = (rows, K) + tuple(spatial)
+        if not isinstance(masks, Tensor) or masks.dtype != torch.float32 or tuple(masks.shape) != want or masks.device != device:
+            raise ValueError(f"{who}: masks must be None or a {want} float32 tensor on {device}, got "
+                             f"{(tuple(masks.shape), masks.dtype, masks.device) if isinstance(masks, Tensor) else type(masks).__name__}")
+        masks = _c(masks.detach())
+    return _c(weights.detach()), masks
+
+
+def guide_compose(ref: Tensor, ds: Sequence[Tensor], weights: Tensor, masks: Optional[Tensor], guidance: Union[float, Tensor], *,
+                  eta: float = 1.0, norm_threshold: float = float("inf"), momentum: float = 0.0, rescale: float = 0.0,
+                  state: Optional[Tensor] = None) -> Tensor:
+    """Composed guidance of the two-pass outputs: ref = D_u and ds = [D_1, ..., D_K], all (B, C, *spatial) of one dtype, become
+    D_c = D_u + sum_k c_k (D_k - D_u), c_k = weights[n, k] * masks[n, k, p] (masks None: c_k = weights[n, k]), formed in registers in front
+    of the steps of guide_combine, in one launch (hdmoe_guide_compose, include/hdmoe.h, has the arithmetic).  weights: (B, K) float32;
+    masks: None or (B, K, *spatial) float32 in [0, 1], broadcast over channels.  K = 1, weights 1, no masks is guide_combine(ref, ds[0])
+    bit for bit; guidance 1 with the default scalars returns D_c.  Inference only (no gradient)."""
+    ds = list(ds)
+    K = len(ds)
+    if ref.ndim < 1 or ref.numel() == 0 or any(not isinstance(d, Tensor) or d.shape != ref.shape or d.dtype != ref.dtype or
+                                               d.device != ref.device for d in ds):
+        raise ValueError(f"guide_compose: every entry of ds must be a tensor like ref {tuple(ref.shape)} {ref.dtype} (and ref not empty)")
+    rows = ref.shape[0]
+    a, m = _compose_args("guide_compose", weights, masks, rows, K, ref.shape[2:], ref.device)
+    eta, r, beta, phi, g, state = _combine_args("guide_compose", guidance, rows, eta, norm_threshold, momentum, rescale, state, ref.shape,
+                                                ref.device)
+    ref, ds = _c(ref.detach()), [_c(d.detach()) for d in ds]
+    out = torch.empty_like(ref)
+    hw = 1
+    for s in ref.shape[2:]:
+        hw *= s
+    call("hdmoe_guide_compose", out, ref, ds, K, a, m, hw, 0.0 if g is not None else float(guidance), g, eta, r, beta, phi, state, rows,
+         ref.numel() // rows, _dt(ref))
+    return out
+
+
+def nhwc_to_nchw_compose(F: Tensor, sf: Tensor, x: Tensor, sx: Tensor, K: int, weights: Tensor, masks: Optional[Tensor],
+                         guidance: Union[float, Tensor], *, eta: float = 1.0, norm_threshold: float = float("inf"), momentum: float = 0.0,
+                         rescale: float = 0.0, state: Optional[Tensor] = None) -> Tensor:
+    """guide_compose as the egress of the variant-stacked head output F ((K + 1) N, H, W, C): rows k N .. k N + N - 1 belong to condition
+    k + 1, the last N rows are unconditional.  D_k = sx[n] x[n] + sf[n] F[k N + n] and D_u are formed in registers; the result is float32
+    NCHW (N rows).  weights (N, K), masks None or (N, K, H, W), state (momentum != 0): (N, C, H, W) float32.  Inference only."""
+    F = _c(F.detach())
+    NV, H, W, C = F.shape
+    K = int(K)
+    if not 1 <= K <= COMPOSE_MAX:
+        raise ValueError(f"nhwc_to_nchw_compose: needs 1 <= K <= {COMPOSE_MAX} conditions, got {K}")
+    if NV % (K + 1) or x.shape != (NV // (K + 1), C, H, W):
+        raise ValueError(f"nhwc_to_nchw_compose: F {tuple(F.shape)} is not a batch of x {tuple(x.shape)} stacked {K + 1} times")
+    N = NV // (K + 1)
+    a, m = _compose_args("nhwc_to_nchw_compose", weights, masks, N, K, (H, W), F.device)
+    eta, r, beta, phi, g, state = _combine_args("nhwc_to_nchw_compose", guidance, N, eta, norm_threshold, momentum, rescale, state,
+                                                (N, C, H, W), F.device)
+    out = torch.empty((N, C, H, W), dtype=torch.float32, device=F.device)
+    call("hdmoe_nhwc_to_nchw_compose", out, F, _f32(sf.detach()), _f32(x.detach()), _f32(sx.detach()), K, a, m,
+         0.0 if g is not None else float(guidance), g, eta, r, beta, phi, state, N, C, H * W, _dt(F))
+    return out
+
+
 class _PatchRelayoutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tok, meta):

@@ -86,15 +86,17 @@ def _bank_kind(mods: List[nn.Module], H: int, W: int) -> Optional[str]:
     return None
 
 
-def _dispatch_pair(x: Tensor, experts: nn.ModuleList, out_router: Tensor, time_emb: Tensor, text2d: Tensor, kcap: int) -> Tensor:
+def _dispatch_pair(x: Tensor, experts: nn.ModuleList, out_router: Tensor, time_emb: Tensor, text2d: Tensor, kcap: int, V: int = 2) -> Tensor:
     """_dispatch_nhwc for the guided evaluation (inference): x (B,H,W,C), time_emb (B,T) and the routing weights (B,E) are shared by the
     two text variants, text2d (2B,text_dim) is pair-stacked.  The plan of [w ; w] is expert-contiguous and sample-stable, so each expert's
     segment holds its conditional rows, then the same samples' unconditional rows: seg2[e] = 2 seg[e].  -> (2B,H,W,C), pair-stacked.
-    The expert-usage counters are the optimizer's and are not touched."""
+    The expert-usage counters are the optimizer's and are not touched.
+    V: the number of stacked text variants (composed guidance: K conditions and the unconditional row, V = K + 1); everything above
+    holds with V copies of w, text2d (V B, text_dim) and segments of V seg[e] rows."""
     mods = list(experts)
     B = x.shape[0]
     kind = _bank_kind(mods, x.shape[1], x.shape[2])
-    w2 = torch.cat([out_router, out_router])                               # (2B, E) floats; the latents are never duplicated
+    w2 = torch.cat([out_router] * V)                                       # (V B, E) floats; the latents are never duplicated
     plan = ops.DispatchPlan(w2, kcap)
     xs = ops.gather_rows_paired(x, plan, B)
     ts = ops.gather_rows_paired(time_emb, plan, B)
@@ -337,12 +339,15 @@ class _HDMOEMBase(nn.Module):
         return self.output_proj._fwd(mixed), gate
 
     def _fwd_guided(self, x: Tensor, time_vec: Tensor, text_emb: Tensor, uncond_text_emb: Tensor, Unet_router_mask: Tensor,
-                    Vit_router_mask: Tensor, zeta, **kw):
+                    Vit_router_mask: Tensor, zeta, more_text=(), **kw):
         """One pass for both text variants of a classifier-free-guidance evaluation (inference).  The text reaches only the expert banks
         and cross_attn_text: time embedding, stem, path scaling, both routers and their decisions are computed once on B rows; the banks
         and the fusion tail run on the pair-stacked batch [conditional rows 0..B-1 ; unconditional rows B..2B-1].
-        Returns (out (2B,H,W,C_in) channel-last, p_unet, raw_unet, p_vit, raw_vit, scaling) -- the routing outputs per sample, B rows."""
+        more_text: further conditions of a composed evaluation, each shaped like text_emb; the batch is then variant-stacked in the order
+        [text_emb ; more_text ... ; uncond_text_emb], V = 2 + len(more_text) copies of the B rows.
+        Returns (out (VB,H,W,C_in) channel-last, p_unet, raw_unet, p_vit, raw_vit, scaling) -- the routing outputs per sample, B rows."""
         B, H, W, _ = x.shape
+        V = 2 + len(more_text)
         cdt = hdmoe_hip.compute_dtype()
         time_vec = ops.cast(time_vec, torch.float32)
         te = self.Fourier_emb(time_vec)
@@ -352,31 +357,32 @@ class _HDMOEMBase(nn.Module):
         s_vit, s_unet, scaling = self._scaling(time_vec, te, zeta, **kw)
         in_unet = ops.scale_rows(feats, s_unet)
         in_vit = ops.scale_rows(feats, s_vit)
-        text32 = ops.cast(torch.cat([text_emb, uncond_text_emb]), torch.float32)        # pair-stacked text: the one operand that differs
+        text32 = ops.cast(torch.cat([text_emb, *more_text, uncond_text_emb]), torch.float32)      # stacked text: the one operand that differs
         text2d = ops.seq_mean(text32) if text32.ndim == 3 else text32
         text_c = ops.cast(text32, cdt)
         for experts in (self.Unet_experts, self.VIT_experts):
             if _bank_kind(list(experts), H, W) is None:
-                raise NotImplementedError("forward_guided runs the banked expert paths only (a U-Net expert bank of at most 8 experts, or a "
-                                          "ViT expert bank): this expert list takes the per-expert fallback, which has no shared-routing form")
+                raise NotImplementedError("forward_guided / forward_composed run the banked expert paths only (a U-Net expert bank of at most "
+                                          "8 experts, or a ViT expert bank): this expert list takes the per-expert fallback, which has no "
+                                          "shared-routing form")
         w_vit, p_vit, raw_vit, _ = self.vit_router._fwd(in_vit, te, Vit_router_mask, zeta)
         if ops.SIDE_STREAMS and x.is_cuda:
             fork = torch.cuda.Event()
             fork.record(torch.cuda.current_stream())                        # the ViT bank depends on nothing issued after this point
         w_unet, p_unet, raw_unet, _ = self.Unet_router._fwd(in_unet, te, Unet_router_mask, zeta)
-        out_u = _dispatch_pair(ops.cast(in_unet, cdt), self.Unet_experts, w_unet, te, text2d, self.top_k)
+        out_u = _dispatch_pair(ops.cast(in_unet, cdt), self.Unet_experts, w_unet, te, text2d, self.top_k, V)
         if ops.SIDE_STREAMS and x.is_cuda:                                  # the ViT bank on its own stream, as in _fwd
             side = ops.side_streams(x.device, 1)[0]
             side.wait_event(fork)
             with torch.cuda.stream(side):
-                out_v = _dispatch_pair(ops.cast(in_vit, cdt), self.VIT_experts, w_vit, te, text2d, self.top_k)
+                out_v = _dispatch_pair(ops.cast(in_vit, cdt), self.VIT_experts, w_vit, te, text2d, self.top_k, V)
             wbank.note_forked_streams([side])
             torch.cuda.current_stream().wait_stream(side)
             out_v.record_stream(torch.cuda.current_stream())
         else:
-            out_v = _dispatch_pair(ops.cast(in_vit, cdt), self.VIT_experts, w_vit, te, text2d, self.top_k)
+            out_v = _dispatch_pair(ops.cast(in_vit, cdt), self.VIT_experts, w_vit, te, text2d, self.top_k, V)
         if self._has_scaling_net:                                           # only this variant's _fusion_inputs reads them: B floats, tiled
-            s_vit, s_unet = s_vit.repeat(2), s_unet.repeat(2)
+            s_vit, s_unet = s_vit.repeat(V), s_unet.repeat(V)
         out, _ = self._fusion_tail(out_u, out_v, s_vit, s_unet, text_c, **kw)
         return out, p_unet, raw_unet, p_vit, raw_vit, scaling
 
@@ -447,6 +453,51 @@ class _PrecondBase(nn.Module):
                 eta, r, beta, phi, state = guide_combine
                 D_x = ops.nhwc_to_nchw_guide_combine(out, c_out, x32, ops.mul(c_skip, c_in), guidance, eta=eta, norm_threshold=r,
                                                      momentum=beta, rescale=phi, state=state)
+        finally:
+            wbank.deactivate()
+        return {"denoised": D_x, "Unet_router_loss": p_u, "Unet_raw": raw_u, "vit_router_loss": p_v, "vit_raw": raw_v,
+                "scaling_net_out": scaling}
+
+    def _forward_composed(self, x: Tensor, sigma: Tensor, text_embs: Tensor, uncond_text_emb: Tensor, weights: Tensor,
+                          masks: Optional[Tensor], guidance: Union[float, Tensor], Unet_router_mask: Tensor, Vit_router_mask: Tensor, zeta,
+                          guide_combine=None, **kw):
+        """Composed guidance over K conditions as ONE pass with shared routing (inference only): net._fwd_guided on the variant-stacked
+        batch [condition 1 ; ... ; condition K ; unconditional], then the egress ops.nhwc_to_nchw_compose, which forms
+        D_c = D_u + sum_k weights[n, k] masks[n, k, p] (D_k - D_u) in registers and applies the guidance combine to (D_c, D_u).
+        text_embs: (K, B, ...), 1 <= K <= ops.COMPOSE_MAX; uncond_text_emb: (B, ...), required; weights: (B, K) float32; masks: None or
+        (B, K, H, W) float32 in [0, 1] (values are the caller's to check: nothing is read from the device).
+        guidance / guide_combine: as in forward_guided; without a record the egress gets the identity scalars, i.e.
+        (1 - g) D_u + g D_c."""
+        B = x.shape[0]
+        if isinstance(guidance, Tensor) and (tuple(guidance.shape) != (B,) or not guidance.is_floating_point()):
+            raise ValueError(f"guidance must be a float or a floating-point tensor of shape ({B},), got {tuple(guidance.shape)} "
+                             f"{guidance.dtype}")
+        tensors = [t for t in (x, sigma, text_embs, uncond_text_emb, weights, masks) if isinstance(t, Tensor)]
+        if torch.is_grad_enabled() and (any(t.requires_grad for t in tensors) or any(p.requires_grad for p in self.parameters())):
+            raise RuntimeError("forward_composed is inference only: call it under torch.no_grad() (gradients take forward())")
+        if hgraph.current() is not None:
+            raise RuntimeError("forward_composed is inference only: not inside a staged training step")
+        if not isinstance(text_embs, Tensor) or text_embs.ndim < 3 or text_embs.shape[1] != B or not 1 <= text_embs.shape[0] <= ops.COMPOSE_MAX:
+            raise ValueError(f"text_embs must be a (K, {B}, ...) tensor with 1 <= K <= {ops.COMPOSE_MAX}, got "
+                             f"{tuple(getattr(text_embs, 'shape', ())) or type(text_embs).__name__}")
+        K = text_embs.shape[0]
+        if not isinstance(uncond_text_emb, Tensor) or tuple(uncond_text_emb.shape) != tuple(text_embs.shape[1:]):
+            raise ValueError(f"uncond_text_emb is required and must have the shape of one condition {tuple(text_embs.shape[1:])}, got "
+                             f"{tuple(getattr(uncond_text_emb, 'shape', ())) or type(uncond_text_emb).__name__}")
+        wbank.bank_for(self).begin_step(self.training)
+        try:
+            coef = ops.edm_coeffs(sigma, self.sigma_data, B)                # rows: c_skip, c_out, c_in, c_noise
+            c_skip, c_out, c_in, c_noise = coef[0], coef[1], coef[2], coef[3]
+            x32 = ops.cast(x, torch.float32)
+            xs = ops.to_nhwc(x32, scale=c_in, dtype=torch.float32)
+            out, p_u, raw_u, p_v, raw_v, scaling = self.net._fwd_guided(xs, c_noise, text_embs[0], uncond_text_emb.to(text_embs.dtype),
+                                                                         Unet_router_mask, Vit_router_mask, zeta,
+                                                                         more_text=tuple(text_embs[1:].unbind(0)), **kw)
+            if isinstance(guidance, Tensor):
+                guidance = guidance.detach().to(device=x32.device, dtype=torch.float32)
+            eta, r, beta, phi, state = (1.0, float("inf"), 0.0, 0.0, None) if guide_combine is None else guide_combine
+            D_x = ops.nhwc_to_nchw_compose(out, c_out, x32, ops.mul(c_skip, c_in), K, weights, masks, guidance, eta=eta, norm_threshold=r,
+                                           momentum=beta, rescale=phi, state=state)
         finally:
             wbank.deactivate()
         return {"denoised": D_x, "Unet_router_loss": p_u, "Unet_raw": raw_u, "vit_router_loss": p_v, "vit_raw": raw_v,

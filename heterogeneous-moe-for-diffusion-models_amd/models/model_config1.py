@@ -72,3 +72,13 @@ class preconditioned_HDMOEM(_PrecondBase):
         (ops.nhwc_to_nchw_guide_combine) instead of the plain blend."""
         return self._forward_guided(x, sigma, text_emb, uncond_text_emb, guidance, Unet_router_mask, Vit_router_mask, zeta,
                                     guide_combine=guide_combine)
+
+    def forward_composed(self, x: Tensor, sigma: Tensor, text_embs: Tensor, uncond_text_emb: Tensor, weights: Tensor,
+                         masks: Optional[Tensor], guidance: Union[float, Tensor], Unet_router_mask: Tensor, Vit_router_mask: Tensor,
+                         zeta: float, guide_combine=None):
+        """Composed guidance over the K conditions text_embs (K, B, ...) in one shared-routing pass (models/_assembly.py); inference only.
+        With D_c = D_u + sum_k weights[n, k] masks[n, k, p] (D_k - D_u): (1 - guidance) D_u + guidance D_c, or, with the record
+        guide_combine = (eta, norm_threshold, momentum, rescale, state), projected guidance and rescale of (D_c, D_u).
+        weights: (B, K) float32; masks: None or (B, K, H, W) float32 in [0, 1]; uncond_text_emb is required."""
+        return self._forward_composed(x, sigma, text_embs, uncond_text_emb, weights, masks, guidance, Unet_router_mask, Vit_router_mask, zeta,
+                                      guide_combine=guide_combine)

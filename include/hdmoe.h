@@ -380,6 +380,33 @@ int hdmoe_guide_combine(void* out, const void* ref, const void* d, float g, cons
  * D_u = sx[n] x[n] + sf[n] F[N + n] are formed in registers and never written; out and momentum are fp32 NCHW, per = C HW.  dtype: of F. */
 int hdmoe_nhwc_to_nchw_guide_combine(float* out, const void* F, const float* sf, const float* x, const float* sx, float g, const float* g_rows,
                                      float eta, float r, float beta, float phi, float* momentum, int N, int C, long HW, int dtype, HS stream);
+/* Composed guidance: K conditions D_1 .. D_K (1 <= K <= HDMOE_COMPOSE_MAX) with weights a[n][k] (fp32, DEVICE memory, (rows, K), any
+ * sign) and optional masks m[n][k][p] (fp32 in [0, 1], DEVICE memory, (rows, K, HW) over the HW latent positions, broadcast over
+ * channels: per = C HW, element e = c HW + p; NULL = no masks) become ONE conditional operand in registers, per element, in fp32, with
+ * contraction off and left to right:
+ *   c_k = a[n][k] m[n][k][p]                              (no masks: c_k = a[n][k], no multiplication)
+ *   c_0 = (((1 - c_1) - c_2) - ...) - c_K
+ *   D_c = (((c_0 D_u) + c_1 D_1) + c_2 D_2) + ... + c_K D_K          i.e. D_u + sum_k c_k (D_k - D_u)
+ * D_c and D_u then enter the steps of hdmoe_guide_combine above unchanged (same kernel body): M = (D_c - D_u) + beta M_prev, the five
+ * fp64 sums, s / c / b / a / rho / f, out = fl(f a) D_c + fl(f b) M.  K = 1, a = 1, no masks: c_0 = 0 and D_c = D_1 (finite D_u), the
+ * output has the bits of hdmoe_guide_combine / hdmoe_nhwc_to_nchw_guide_combine with the same launch scalars.  w = 1, eta = 1, r = inf,
+ * beta = 0, phi = 0: out = D_c exactly.  On the re-read arm D_c is formed a second time by the same fp32 operations, as M is.  The
+ * values of a and m are not checked (the caller validates them on the host).  16-byte accesses under the conditions of the parent entry
+ * point and, with masks, HW a multiple of the vector width and m aligned (a vector's mask values are then one load); else element by
+ * element (hdmoe_guide_compose: element by element always re-reads, whatever the sample's size).  HDMOE_EINVAL, nothing launched: K out of range, a NULL, a NULL entry of d_ptrs, masks with HW < 1 or per % HW != 0, and
+ * whatever the parent refuses.  HW is not read without masks.
+ * d_ptrs: HOST array of K DEVICE pointers to (rows, per) tensors of `dtype` (fp32 / bf16), like ref and out. */
+#define HDMOE_COMPOSE_MAX 8
+int hdmoe_guide_compose(void* out, const void* ref, const void* const* d_ptrs, int K, const float* a, const float* m, long HW, float g,
+                        const float* g_rows, float eta, float r, float beta, float phi, float* momentum, long rows, long per, int dtype,
+                        HS stream);
+/* The same as the egress of the shared-routing pass: F (NHWC, `dtype`) is the head output of the variant-stacked batch of (K + 1) N rows,
+ * rows k N .. k N + N - 1 belong to condition k + 1 and the last N rows are unconditional (K = 1: the pair stacking above).
+ * D_k = sx[n] x[n] + sf[n] F[k N + n] and D_u = sx[n] x[n] + sf[n] F[K N + n] are formed in registers as
+ * hdmoe_nhwc_to_nchw_guide_combine forms its two operands, and never written; out and momentum are fp32 NCHW, m is (N, K, HW). */
+int hdmoe_nhwc_to_nchw_compose(float* out, const void* F, const float* sf, const float* x, const float* sx, int K, const float* a, const float* m,
+                               float g, const float* g_rows, float eta, float r, float beta, float phi, float* momentum, int N, int C, long HW,
+                               int dtype, HS stream);
 int hdmoe_patch_relayout(void* out, const void* in, int N, int H, int W, int C, int p, int hp, int wp, int order,
                          int to_img, int dtype, HS stream);                                                      /* PixelShuffle / patchify */
 /* The same bytes for order 1 (PixelShuffle) by a tiled transpose through LDS, 16-byte accesses on both sides (csrc/relayout.hip).
