@@ -7,6 +7,7 @@
 // read by every lane at the same address (LDS broadcast, conflict-free).
 #include <stdlib.h>
 #include "common.h"
+#include "conv_args.h"
 #include "hdmoe.h"
 
 namespace {
@@ -188,8 +189,9 @@ __global__ __launch_bounds__(TQ) void attn_bwd_dkv_kernel(T* dk, T* dv, const T*
   }
 }
 
-// d(rel_pos_bias)[h][i][j] = sum_b ds[b][h][i][j].  One thread per (h, i, j) walks the batch (no atomics: with B samples
-// adding into the same H*S*S words the atomic version was 256-way contended and cost ~100 us per call on S = 64).
+// d(rel_pos_bias)[h][i][j] += sum_b ds[b][h][i][j].  One thread per (h, i, j) walks the batch and owns its word of dbias, so the
+// accumulation needs no atomic (with B samples adding into the same H*S*S words an atomic version was 256-way contended and cost
+// ~100 us per call on S = 64).
 template <typename T, int D>
 __global__ void attn_dbias_kernel(float* dbias, const T* dout, const T* q, const T* k, const T* v, const float* lse,
                                   const float* delta, const float* bias, int B, int Sq, int Skv, int H, int Sb, float scale) {
@@ -212,7 +214,7 @@ __global__ void attn_dbias_kernel(float* dbias, const T* dout, const T* q, const
     const long li = ((long)b * H + h) * Sq + i;
     acc += __expf(s * scale + bv - lse[li]) * (dp - delta[li]);
   }
-  dbias[((long)h * Sb + i) * Sb + j] = acc;
+  dbias[((long)h * Sb + i) * Sb + j] += acc;
 }
 
 // =====================================================================================================================
@@ -887,11 +889,13 @@ int attn_fwd_launch(void* out, float* lse, const void* q, const void* k, const v
     if (!bias && attn_mfma_ok(H, out, q, k, v)) {
       hipLaunchKernelGGL(attn_fwd_mfma_kernel, dim3(cdiv(Sq, 256), B), dim3(512), ATT_KV_LDS, st, (bf16*)out, lse, (const bf16*)q,
                          (const bf16*)k, (const bf16*)v, Sq, Skv, H, LOG2E / sqrtf((float)D), attn_force_slow());
+      hdmoe_count_selection(HDMOE_SEL_ATTN_FWD_MFMA);
       return hdmoe_launch_status();
     }
   }
   BIAS_SWITCH(bias, hipLaunchKernelGGL((attn_fwd_kernel<T, D, BIAS>), dim3(cdiv(Sq, TQ), H, B), dim3(TQ), 0, st, (T*)out, lse, (const T*)q,
                                        (const T*)k, (const T*)v, bias, Sq, Skv, H, Sb, 1.f / sqrtf((float)D)))
+  hdmoe_count_selection(HDMOE_SEL_ATTN_GENERIC);
   return hdmoe_launch_status();
 }
 template <typename T, int D>
@@ -910,6 +914,7 @@ int attn_bwd_launch(void* dq, void* dk, void* dv, float* dbias, float* delta, co
         const int hpw = (int)cdiv(H, hg);
         hipLaunchKernelGGL(attn_bwd_merged_kernel, dim3(cdiv(H, hpw), B), dim3(64 * MG_WAVES), MG_LDS, st, (bf16*)dq, (bf16*)dk, (bf16*)dv,
                            (const bf16*)dout, (const bf16*)out, (const bf16*)q, (const bf16*)k, (const bf16*)v, lse, Sq, Skv, H, hpw, scale, c);
+        hdmoe_count_selection(HDMOE_SEL_ATTN_BWD_MERGED);
         return hdmoe_launch_status();
       }
       const int nb32 = (int)cdiv(Skv, 32), nkb = nb32 >= 5 ? 8 : (nb32 >= 3 ? 4 : nb32);
@@ -920,6 +925,7 @@ int attn_bwd_launch(void* dq, void* dk, void* dv, float* dbias, float* delta, co
         (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_DKV_LDS);
       hipLaunchKernelGGL(attn_bwd_dkv_mfma_kernel, dim3(cdiv(Skv, 32 * nkb), B), dim3(512), ATT_DKV_LDS, st, (bf16*)dk, (bf16*)dv,
                          (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v, lse, delta, Sq, Skv, H, scale, c, nkb);
+      hdmoe_count_selection(HDMOE_SEL_ATTN_BWD_PAIR);
       return hdmoe_launch_status();
     }
   }
@@ -933,6 +939,7 @@ int attn_bwd_launch(void* dq, void* dk, void* dv, float* dbias, float* delta, co
     hipLaunchKernelGGL((attn_dbias_kernel<T, D>), dim3(cdiv(nthreads, 256)), dim3(256), 0, st, dbias, (const T*)dout, (const T*)q, (const T*)k,
                        (const T*)v, lse, delta, bias, B, Sq, Skv, H, Sb, scale);
   }
+  hdmoe_count_selection(HDMOE_SEL_ATTN_GENERIC);
   return hdmoe_launch_status();
 }
 
@@ -1211,7 +1218,7 @@ int hdmoe_attn_fwd(void* out, float* lse, const void* q, const void* k, const vo
   DT_SWITCH(dtype, D_SWITCH(D, return (attn_fwd_launch<T, DD>(out, lse, q, k, v, bias, B, Sq, Skv, H, Sb, stream))))
 }
 
-// delta: [B][H][Sq] fp32 scratch; dbias: [H][Sb][Sb] fp32 accumulator (caller zeroes) or null
+// delta: [B][H][Sq] fp32 scratch; dbias: [H][Sb][Sb] fp32 or null: its [:, :Sq, :Skv] corner accumulates (+=); the caller zeroes a fresh buffer
 int hdmoe_attn_bwd(void* dq, void* dk, void* dv, float* dbias, float* delta, const void* dout, const void* out, const void* q,
                    const void* k, const void* v, const float* lse, const float* bias, int B, int Sq, int Skv, int H, int D, int Sb,
                    int dtype, hipStream_t stream) {

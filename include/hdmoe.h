@@ -196,7 +196,11 @@ enum {
   HDMOE_SEL_FUSION_IN_BWD = 25,    /* hdmoe_fusion_in_bwd: their input gradients, the gradient fan-in and dsw in one launch */
   HDMOE_SEL_FUSION_OUT = 26,       /* hdmoe_fusion_out_fwd: text out_proj + lerp + mp_cat + gate1 + mp_silu + gate2 + gate_mix in one launch */
   HDMOE_SEL_FUSION_OUT_BWD = 27,   /* hdmoe_fusion_out_bwd: their input gradients, the gradient fan-in and dalpha in one launch */
-  HDMOE_SEL_COUNT = 28
+  HDMOE_SEL_ATTN_FWD_MFMA = 28,    /* hdmoe_attn_fwd: the bf16 D = 4 MFMA forward kernel */
+  HDMOE_SEL_ATTN_BWD_MERGED = 29,  /* hdmoe_attn_bwd: the merged MFMA backward (Sq <= 1024) */
+  HDMOE_SEL_ATTN_BWD_PAIR = 30,    /* hdmoe_attn_bwd: the MFMA dq + dk / dv pair (Sq > 1024) */
+  HDMOE_SEL_ATTN_GENERIC = 31,     /* hdmoe_attn_fwd / hdmoe_attn_bwd: the one-row-per-thread kernels (one count per call) */
+  HDMOE_SEL_COUNT = 32
 };
 int hdmoe_kernel_selections(long long* counts, int n, int reset);
 
@@ -596,7 +600,9 @@ int hdmoe_layernorm_fwd(void* y, float* mean, float* rstd, const void* x, const 
 int hdmoe_layernorm_bwd(void* dx, float* dgamma, float* dbeta, const void* dy, const void* x, const float* gamma,
                         const float* mean, const float* rstd, long rows, int C, int dtype, HS stream);
 
-/* ---- K5: attention core  (model_internals.py:374-404) -------------------------------------------------------- */
+/* ---- K5: attention core  (model_internals.py:374-404) --------------------------------------------------------
+ * hdmoe_attn_bwd: delta [B][H][Sq] fp32 scratch; dbias [H][Sb][Sb] fp32 or null: its [:, :Sq, :Skv] corner accumulates (+=; the caller
+ * zeroes a fresh buffer), the rest is not touched. */
 int hdmoe_attn_fwd(void* out, float* lse, const void* q, const void* k, const void* v, const float* bias, int B, int Sq,
                    int Skv, int H, int D, int Sb, int dtype, HS stream);
 int hdmoe_attn_bwd(void* dq, void* dk, void* dv, float* dbias, float* delta, const void* dout, const void* out,
