@@ -50,6 +50,12 @@ place of the conditional output in everything above: the scale, per-sample scale
 banks and the tail, D_c formed in the egress kernel; otherwise K passes of the model, one of the guide network and ONE launch of
 ``ops.guide_compose``.  D_c needs D_u, so an evaluation outside the guidance interval is the composed evaluation at scale 1 (out = D_c),
 not one plain call.  Without the keywords nothing changes.
+
+Tiled sampling (extension, opt-in; ``sample()`` keywords ``tile``, ``tile_overlap``, ``tile_window``, ``tile_batch``).  The model can only
+be evaluated at the latent size it was built for; every solver update is pointwise, so a larger (B, C, H, W) latent runs through the
+solvers unchanged and only the denoiser evaluation is tiled: ``den_big = blend(model(gather(x_big)))`` over overlapping model-sized windows
+(``ops.tile_plan`` / ``ops.tile_gather`` / ``ops.tile_blend``, MultiDiffusion, Bar-Tal et al. 2023).  One method, ``_denoise_tiled``,
+serves the fused and captured stages and the host loops; the text, the router masks and the per-sample scales are repeated per tile row.
 """
 import math
 import numbers
@@ -414,7 +420,65 @@ class EDM_Sampler:
         return strength
 
     # ---- static state and hipGraph capture: fused solver stages (reference :90-107 without churn), the captured evaluation ----------------
-    def _stage_state(self, kind, x, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, gvec=None, comp=None):
+    def _check_tile(self, noise, comp, tile, tile_overlap, tile_window, tile_batch):
+        """The tiling keywords of sample(): None without `tile`, else the record {"plan": ops.TilePlan, "tb": tile rows per model call,
+        "key": what a capture bakes in}.  Host arithmetic only."""
+        if tile is None:
+            return None
+        try:
+            h, w = (int(v) for v in tile)
+        except (TypeError, ValueError):
+            raise ValueError(f"tile must be None or a pair (h, w) of ints, the model's latent size, got {tile!r}") from None
+        if noise.ndim != 4 or h < 1 or w < 1 or noise.shape[2] < h or noise.shape[3] < w:
+            raise ValueError(f"tile=({h}, {w}) needs (B, C, H, W) latents with H >= {h} and W >= {w}, got noise of shape {tuple(noise.shape)}")
+        if comp is not None:
+            raise ValueError("tile does not combine with composed guidance (compose_text / compose_weights / compose_masks): the spatial "
+                             "masks would have to be tiled too")
+        if self.combine_params() is not None:
+            raise ValueError("tile does not combine with guidance_rescale or apg_eta / apg_norm_threshold / apg_momentum: their per-sample "
+                             "statistics and momentum would become per-tile ones")
+        B, _, H, W = (int(v) for v in noise.shape)
+        try:
+            plan = ops.tile_plan(H, W, h, w, tile_overlap, tile_window)
+        except ValueError as e:
+            raise ValueError(f"tile / tile_overlap / tile_window: {e}") from None
+        n = B * plan.T
+        tb = n if tile_batch is None else tile_batch
+        if isinstance(tb, bool) or not isinstance(tb, numbers.Integral) or tb < 1 or n % int(tb):
+            raise ValueError(f"tile_batch must be a positive int dividing B * T = {B} * {plan.T} = {n}, got {tile_batch!r}")
+        return dict(plan=plan, tb=int(tb), key=((h, w), plan.overlap, plan.window, int(tb), H, W))
+
+    def _tile_bufs(self, tile, x):
+        """The tile record with its device side: the plan's arrays on x's device, the gather target "xt" (tb, C, h, w) and, when an
+        evaluation takes more than one model call, the tile buffer "buf" (B T, C, h, w) the chunks' outputs are collected in (fp32)."""
+        plan, tb = tile["plan"], tile["tb"]
+        plan.device(x.device)
+        B, C = x.shape[:2]
+        mk = lambda rows: torch.empty((rows, C, plan.h, plan.w), dtype=torch.float32, device=x.device)
+        return dict(tile, xt=mk(tb), buf=mk(B * plan.T) if tb < B * plan.T else None)
+
+    def _denoise_tiled(self, tile, x, sigma, text_emb, transition_mean, softness, uncond_text_emb, um, vm, guided, g):
+        """_denoise() of a latent larger than the model: den_big = blend(model(gather(x_big))).  x keeps its B rows; every per-row operand
+        (text, masks, scales) has B T rows, tile-batch order.  Per chunk of tb rows: ops.tile_gather, _denoise, and (more than one chunk)
+        one copy_ into the tile buffer; then ONE ops.tile_blend.  The tile kernels are fp32: other latent dtypes are cast on the way in
+        and out, as _denoise casts the model's output.  No host read: it runs under stream capture like _denoise."""
+        plan, tb = tile["plan"], tile["tb"]
+        n = x.shape[0] * plan.T
+        xf = x.to(torch.float32).contiguous()
+        cut = (lambda a, sl: a) if tb == n else (lambda a, sl: None if a is None else a[sl])
+        for r0 in range(0, n, tb):
+            sl = slice(r0, r0 + tb)
+            xt = ops.tile_gather(xf, plan, r0, tb, out=tile["xt"])
+            d = self._denoise(xt.to(self.dtype), sigma, cut(text_emb, sl), transition_mean, softness, cut(uncond_text_emb, sl), cut(um, sl),
+                              cut(vm, sl), guided, cut(g, sl))
+            if tb == n:
+                tiles = d.to(torch.float32).contiguous()      # one chunk: blended from where the model left it
+            else:
+                tiles = tile["buf"]
+                tiles[sl].copy_(d)
+        return ops.tile_blend(tiles, plan, x.shape[0]).to(self.dtype)
+
+    def _stage_state(self, kind, x, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, gvec=None, comp=None, tile=None):
         """Static buffers, stage functions and (use_graph) captured graphs of one kind:
           "eval": one guided evaluation of x at sig into out (the host loops' evaluation with use_graph);
           "heun": a full Heun stage and the last, Euler-only stage; "dpm": one DPM-Solver++(2M) stage (den_prev: the previous stage's
@@ -433,10 +497,15 @@ class EDM_Sampler:
         interval the lists are the all-guided ones alone: two for "heun" (full, last), one for "dpm" and "eval".
 
         comp (composed guidance): its texts, weights and masks are static buffers ("texts", "cw", "cm") refreshed like every input; only K
-        and whether there are masks are in the key (its second entry)."""
+        and whether there are masks are in the key (its second entry).
+
+        tile (tiled sampling, _check_tile's record): every evaluation of the state is _denoise_tiled.  x keeps its B rows, the per-row
+        operands come with B T rows; the plan's device arrays and the tile buffers are part of the state ("tile"), and the tile spec --
+        (h, w), the overlaps, the window, tile_batch, H, W -- is one more key entry, present only with tiling."""
         shape = lambda a: None if a is None else tuple(a.shape)
         variants = self.guidance_interval is not None and (gvec is not None or self.guide != 1.0)
-        key = (kind, None if comp is None else (int(comp[0].shape[0]), comp[2] is not None), self.solver, shape(x), x.dtype,
+        key = (kind, None if comp is None else (int(comp[0].shape[0]), comp[2] is not None), self.solver, shape(x), x.dtype) \
+            + (() if tile is None else (("tile",) + tile["key"],)) + (
                shape(text_emb), shape(uncond_text_emb), float(transition_mean), float(softness),
                self.num_steps, bool(self.use_graph), None if known is None else tuple(map(shape, known)), shape(um), shape(vm),
                float(self.guide), id(self.model), id(self.gnet), float(self.s_churn), float(self.s_min), float(self.s_max), float(self.s_noise),
@@ -453,11 +522,14 @@ class EDM_Sampler:
                   g=opt(gvec), variants=variants, mods=(self.model, self.gnet),
                   mom=torch.zeros(x.shape, dtype=torch.float32, device=dev) if self._needs_momentum(gvec) else None,
                   texts=None if comp is None else torch.empty_like(comp[0]), cw=None if comp is None else torch.empty_like(comp[1]),
-                  cm=None if comp is None else opt(comp[2]))
+                  cm=None if comp is None else opt(comp[2]), tile=None if tile is None else self._tile_bufs(tile, x))
         self._refresh(st, x, text_emb, uncond_text_emb, known, um, vm, gvec=gvec, comp=comp)
         st_comp = None if comp is None else (st["texts"], st["cw"], st["cm"])
 
         def den(x_, guided):
+            if st["tile"] is not None:
+                return self._denoise_tiled(st["tile"], x_, st["sig"], st["text"], transition_mean, softness, st["unc"], st["um"], st["vm"],
+                                           guided, st["g"])
             return self._denoise(x_, st["sig"], st["text"], transition_mean, softness, st["unc"], st["um"], st["vm"], guided, st["g"],
                                  st["mom"], st_comp)
 
@@ -570,7 +642,7 @@ class EDM_Sampler:
         return eps.to(x.dtype)
 
     def _dpm_host_loop(self, x, t_steps, i0, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, seed=None, plan=None,
-                       gvec=None, mom=None, comp=None):
+                       gvec=None, mom=None, comp=None, tile=None):
         """solver="dpmpp_2m" / "dpmpp_2m_sde" for latents the fused stage does not take (non-fp32 dtype): the rule of sample() with host
         coefficients."""
         N = self.num_steps
@@ -579,7 +651,7 @@ class EDM_Sampler:
         for i in range(i0, N):
             t_cur, t_next = float(t_steps[i]), float(t_steps[i + 1])
             den = self._eval(x, t_cur, text_emb, transition_mean, softness, uncond_text_emb, um, vm,
-                             True if plan is None else plan[i - i0][0], gvec, mom, first=i == i0, comp=comp)
+                             True if plan is None else plan[i - i0][0], gvec, mom, first=i == i0, comp=comp, tile=tile)
             e = math.exp(-self.eta * math.log(t_cur / t_next)) if sde and t_next > 0 else 1.0
             a = t_next / t_cur * e
             if t_next == 0:
@@ -597,13 +669,16 @@ class EDM_Sampler:
         return x
 
     def _eval(self, x, t, text_emb, transition_mean, softness, uncond_text_emb, um=None, vm=None, guided=True, gvec=None, mom=None,
-              first=False, comp=None):
+              first=False, comp=None, tile=None):
         """One evaluation at sigma t of the host loops; guided: the solver's guidance-interval decision for it.  mom: the call's APG
-        momentum buffer (eager); the captured evaluation carries its own, zeroed on the first evaluation of a call."""
+        momentum buffer (eager); the captured evaluation carries its own, zeroed on the first evaluation of a call.  tile: the tile
+        record of a tiled call (eager: with this call's buffers, _tile_bufs); the evaluation is then _denoise_tiled."""
         if not self.use_graph:
             sig = torch.tensor(t, dtype=self.dtype, device=x.device)
+            if tile is not None:
+                return self._denoise_tiled(tile, x, sig, text_emb, transition_mean, softness, uncond_text_emb, um, vm, guided, gvec)
             return self._denoise(x, sig, text_emb, transition_mean, softness, uncond_text_emb, um, vm, guided, gvec, mom, comp)
-        st = self._stage_state("eval", x, text_emb, transition_mean, softness, uncond_text_emb, None, um, vm, gvec, comp)
+        st = self._stage_state("eval", x, text_emb, transition_mean, softness, uncond_text_emb, None, um, vm, gvec, comp, tile)
         self._refresh(st, x, text_emb, uncond_text_emb, None, um, vm, gvec=gvec, reset_momentum=first, comp=comp)
         st["sig"].fill_(float(t))
         guided = bool(guided) or not st["variants"]
@@ -622,7 +697,8 @@ class EDM_Sampler:
                uncond_text_emb: torch.Tensor = None, *, init_latents: torch.Tensor = None, strength: float = 1.0,
                inpaint_mask: torch.Tensor = None, Unet_router_mask: torch.Tensor = None, Vit_router_mask: torch.Tensor = None,
                seed: int = None, guidance: torch.Tensor = None, compose_text: torch.Tensor = None, compose_weights: torch.Tensor = None,
-               compose_masks: torch.Tensor = None) -> torch.Tensor:
+               compose_masks: torch.Tensor = None, tile=None, tile_overlap=0, tile_window: str = "feather",
+               tile_batch: int = None) -> torch.Tensor:
         """Solve of the probability-flow ODE over t = t_schedule() (N = num_solve_steps, t[N] = 0): Heun (solver="heun", the reference),
         or DPM-Solver++(2M) (solver="dpmpp_2m", one evaluation per stage).
 
@@ -686,6 +762,21 @@ class EDM_Sampler:
         meaning, but a "plain" evaluation costs what a guided one does.  K = 1 (weights or masks on text_emb alone) has to be asked for
         with an empty compose_text of shape (0, B, S, D); weights or masks without compose_text are refused.  With use_graph the extra
         text, the weights and the masks are static buffers: other values of the same K replay the same capture.
+
+        tile / tile_overlap / tile_window / tile_batch (tiled sampling of latents larger than the model's resolution, MultiDiffusion
+        style; tile=None: off, nothing changes).  tile = (h, w) is the model's own latent size; noise, init_latents, inpaint_mask and the
+        result are (B, C, H, W) with H >= h, W >= w.  The solver updates are pointwise and run on the large latent unchanged; every
+        denoiser evaluation is den_big = blend(model(gather(x_big))) over the T = Ty Tx windows of ops.tile_plan(H, W, h, w, tile_overlap,
+        tile_window): along an axis of length L with tile length n and overlap o (an int, or (oy, ox) in tile_overlap; 0 <= o < n) the
+        stride is n - o, there are 1 + ceil((L - n) / (n - o)) tiles (at most 32) and the last is clamped to the edge.  tile_window:
+        "uniform" (plain average over the covering tiles) or "feather" (1-D weight min(i + 1, n - i, r) / r, r = max(o, 1), normalised
+        over the covering tiles).  A position under one tile takes that tile's output bit for bit.  text_emb, uncond_text_emb, the router
+        masks and the per-sample guidance vector are repeated T times per sample, so guidance, the interval, per-sample scales and the
+        masks apply per tile row.  tile_batch: tile rows per model call, a divisor of B T (default B T, one call per evaluation).
+        Every solver, churn_on_device, use_graph, image-to-image, strength, inpainting, seed and non-fp32 dtype (host loops; the tile
+        kernels run in fp32) work with it; with use_graph the tile spec is part of the capture key, and a second call of the same shapes
+        replays the same graphs.  Refused (ValueError naming tile): composed guidance (its spatial masks would have to be tiled too),
+        guidance_rescale and apg_* (their per-sample statistics and momentum would become per-tile ones).
         Argument errors raise ValueError (naming the argument) before any device work."""
         comp = self._check_compose(noise, text_emb, uncond_text_emb, compose_text, compose_weights, compose_masks)
         strength = self._check_conditioning(noise, init_latents, strength, inpaint_mask)
@@ -694,6 +785,11 @@ class EDM_Sampler:
         gvec = self._check_guidance(guidance, bs)
         um = self._router_mask(Unet_router_mask, "Unet_router_mask", bs)
         vm = self._router_mask(Vit_router_mask, "Vit_router_mask", bs)
+        tile = self._check_tile(noise, comp, tile, tile_overlap, tile_window, tile_batch)
+        if tile is not None and tile["plan"].T > 1:
+            # per-row operands: from here on _stage_state, _refresh, the static buffers and _denoise see a plain batch of B T rows
+            rep = lambda a: None if a is None else a.repeat_interleave(tile["plan"].T, 0)
+            text_emb, uncond_text_emb, um, vm, gvec = rep(text_emb), rep(uncond_text_emb), rep(um), rep(vm), rep(gvec)
         device = noise.device
         if self.use_graph:
             # the captured evaluation holds no weight-prepare launch when the images were current at capture time: refresh them here,
@@ -730,7 +826,7 @@ class EDM_Sampler:
             kind = "heun" if self.fused_heun else "dpm"
             if seed is None and (self.s_churn > 0 or (self.solver == "dpmpp_2m_sde" and self.eta > 0)):
                 seed = ops.next_seed()                        # a stochastic stage: one value of the library's stream per call
-            st = self._stage_state(kind, x_next, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, gvec, comp)
+            st = self._stage_state(kind, x_next, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, gvec, comp, tile)
             self._refresh(st, x_next, text_emb, uncond_text_emb, known, um, vm, seed, gvec, comp=comp)
             st["t"].copy_(torch.from_numpy(t_steps))
             st["idx"].fill_(i0)
@@ -742,9 +838,11 @@ class EDM_Sampler:
             return st["x"].clone()
         # host loops: this call's APG momentum (the captured evaluation of use_graph holds its own and zeroes it on the first evaluation)
         mom = torch.zeros(x_next.shape, dtype=torch.float32, device=device) if self._needs_momentum(gvec) and not self.use_graph else None
+        if tile is not None and not self.use_graph:           # this call's tile buffers (the captured evaluation holds its own)
+            tile = self._tile_bufs(tile, x_next)
         if self.solver != "heun":
             return self._dpm_host_loop(x_next, t_steps, i0, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, seed, plan,
-                                       gvec, mom, comp)
+                                       gvec, mom, comp, tile)
         for i in range(i0, N):
             t_cur, t_next = float(t_steps[i]), float(t_steps[i + 1])
             x_cur = x_next
@@ -754,14 +852,15 @@ class EDM_Sampler:
             if gamma > 0:
                 x_hat = ops.axpby(x_cur, self._eps(x_cur, seed, i), 1.0, float(np.sqrt(t_hat ** 2 - t_cur ** 2) * self.s_noise))
             denoised = self._eval(x_hat, t_hat, text_emb, transition_mean, softness, uncond_text_emb, um, vm, plan[i - i0][0], gvec, mom,
-                                  first=i == i0, comp=comp)
+                                  first=i == i0, comp=comp, tile=tile)
             # d_cur = (x_hat - denoised)/t_hat ; x_next = x_hat + (t_next - t_hat) * d_cur
             h = (t_next - t_hat)
             x_next = ops.axpby(x_hat, denoised, 1.0 + h / t_hat, -h / t_hat)
             if known is not None:
                 ops.known_blend_(x_next, *known, t_next)
             if i < self.num_steps - 1:
-                den2 = self._eval(x_next, t_next, text_emb, transition_mean, softness, uncond_text_emb, um, vm, plan[i - i0][1], gvec, mom, comp=comp)
+                den2 = self._eval(x_next, t_next, text_emb, transition_mean, softness, uncond_text_emb, um, vm, plan[i - i0][1], gvec, mom, comp=comp,
+                                  tile=tile)
                 # x_next = x_hat + h * (0.5*d_cur + 0.5*d_prime),  d_prime = (x_next - den2)/t_next
                 d_cur_term = ops.axpby(x_hat, denoised, 1.0 + 0.5 * h / t_hat, -0.5 * h / t_hat)     # x_hat + 0.5 h d_cur
                 d_pr = ops.axpby(x_next, den2, 0.5 * h / t_next, -0.5 * h / t_next)                  # 0.5 h d_prime

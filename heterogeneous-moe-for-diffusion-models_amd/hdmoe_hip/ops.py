@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes
 import functools
 import math
+import numbers
 from typing import Optional, Sequence, Tuple, Union
 
 import torch
@@ -1024,6 +1025,127 @@ def known_blend_(x: Tensor, x0: Tensor, noise: Tensor, mask: Tensor, s: float) -
     assert x0.dtype == noise.dtype == x.dtype and mask.dtype == torch.float32 and x0.numel() == noise.numel() == mask.numel() == x.numel()
     call("hdmoe_known_blend", x, x0, noise, mask, float(s), x.numel(), _dt(x))
     return x
+
+
+# ---- tiled sampling: a latent larger than the model's resolution is evaluated on overlapping model-sized windows (MultiDiffusion) --------
+TILE_MAX_AXIS = 32                        # HDMOE_TILE_MAX_AXIS of include/hdmoe.h: tiles along one axis
+TILE_WINDOWS = ("uniform", "feather")
+
+
+class TilePlan:
+    """Where the (h, w) windows of an (H, W) latent lie and how their outputs blend; built by tile_plan() on the host (numpy only).
+      oy (Ty,), ox (Tx,)       int32 origins along y / x
+      ny (Ty, H), nx (Tx, W)   float32 normalised 1-D window weights: ny[k, y] = w1(y - oy[k]) / sum_k' w1(y - oy[k']) where tile k covers
+                               row y, 0 elsewhere (computed in float64, rounded once).  The 2-D weight of tile (ky, kx) is ny[ky, y] nx[kx, x].
+      Ty, Tx, T = Ty Tx        tile counts;  max_cover_y / max_cover_x / max_cover = their product: the most tiles over one position
+    Tile-batch row order is sample-major: r = (b Ty + ky) Tx + kx.  device(dev): the four arrays as tensors on dev (made once per device;
+    ask for them before a stream capture)."""
+
+    def __init__(self, H, W, h, w, overlap, window, oy, ox, ny, nx):
+        self.H, self.W, self.h, self.w, self.overlap, self.window = H, W, h, w, overlap, window
+        self.oy, self.ox, self.ny, self.nx = oy, ox, ny, nx
+        self.Ty, self.Tx = int(oy.shape[0]), int(ox.shape[0])
+        self.T = self.Ty * self.Tx
+        self.max_cover_y = int((ny > 0).sum(0).max())
+        self.max_cover_x = int((nx > 0).sum(0).max())
+        self.max_cover = self.max_cover_y * self.max_cover_x
+        self._dev = {}
+
+    def device(self, dev):
+        dev = torch.device(dev)
+        if dev not in self._dev:
+            self._dev[dev] = tuple(torch.from_numpy(a).to(dev) for a in (self.oy, self.ox, self.ny, self.nx))
+        return self._dev[dev]
+
+    def __repr__(self):
+        return (f"TilePlan({self.H}x{self.W} in {self.Ty}x{self.Tx} tiles of {self.h}x{self.w}, overlap={self.overlap}, "
+                f"window={self.window!r}, max_cover={self.max_cover})")
+
+
+def _tile_axis(L: int, n: int, o: int, window: str, axis: str):
+    """Origins (int32) and the normalised weight table (T, L) float32 of one axis: stride s = n - o, 1 + ceil((L - n) / s) tiles, origin k
+    = min(k s, L - n) (the last tile is clamped to the edge)."""
+    import numpy as np
+    if L < n:
+        raise ValueError(f"tile_plan: the latent's {axis} ({L}) is smaller than the tile's ({n})")
+    if not 0 <= o < n:
+        raise ValueError(f"tile_plan: overlap along {axis} must lie in [0, {n}), got {o}")
+    s = n - o
+    T = 1 if L == n else 1 + -(-(L - n) // s)
+    if T > TILE_MAX_AXIS:
+        raise ValueError(f"tile_plan: {T} tiles along {axis} ({L} in tiles of {n}, overlap {o}); the limit is {TILE_MAX_AXIS}")
+    org = np.minimum(np.arange(T, dtype=np.int64) * s, L - n)
+    i = np.arange(L, dtype=np.int64)[None, :] - org[:, None]                  # tile-local index of every position, (T, L)
+    inside = (i >= 0) & (i < n)
+    if window == "uniform":
+        w1 = np.ones(i.shape, dtype=np.float64)
+    else:
+        r = max(o, 1)
+        w1 = np.minimum(np.minimum(i + 1, n - i), r).astype(np.float64) / r
+    w1 = np.where(inside, w1, 0.0)
+    return org.astype(np.int32), (w1 / w1.sum(0, keepdims=True)).astype(np.float32)
+
+
+def tile_plan(H: int, W: int, h: int, w: int, overlap=0, window: str = "feather") -> TilePlan:
+    """The plan of (h, w) tiles over an (H, W) latent.  overlap: an int or (oy, ox), 0 <= overlap < tile; window: "uniform" (w1 = 1) or
+    "feather" (w1(i) = min(i + 1, n - i, r) / r, r = max(overlap, 1)).  ValueError: a latent smaller than the tile, an overlap outside
+    [0, n), more than 32 tiles on an axis, an unknown window.  Pure host arithmetic."""
+    if window not in TILE_WINDOWS:
+        raise ValueError(f"tile_plan: window must be one of {', '.join(map(repr, TILE_WINDOWS))}, got {window!r}")
+    try:
+        ov = (int(overlap),) * 2 if isinstance(overlap, numbers.Integral) else tuple(int(v) for v in overlap)
+        dims = tuple(int(v) for v in (H, W, h, w))
+    except (TypeError, ValueError):
+        raise ValueError(f"tile_plan: sizes must be ints and overlap an int or a pair (oy, ox), got {(H, W, h, w)!r}, {overlap!r}") from None
+    if len(ov) != 2 or min(dims) < 1:
+        raise ValueError(f"tile_plan: sizes must be positive and overlap an int or a pair (oy, ox), got {(H, W, h, w)!r}, {overlap!r}")
+    H, W, h, w = dims
+    oy, ny = _tile_axis(H, h, ov[0], window, "H")
+    ox, nx = _tile_axis(W, w, ov[1], window, "W")
+    return TilePlan(H, W, h, w, ov, window, oy, ox, ny, nx)
+
+
+def _tile_check(who: str, t: Tensor, shape, what: str) -> Tensor:
+    if not isinstance(t, Tensor) or t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_cuda or not t.is_contiguous():
+        raise ValueError(f"{who}: {what} must be a contiguous float32 CUDA tensor of shape {tuple(shape)}, got "
+                         f"{tuple(getattr(t, 'shape', ())) or type(t).__name__} {getattr(t, 'dtype', '')}")
+    return t.detach()
+
+
+def tile_gather(x: Tensor, plan: TilePlan, row0: int = 0, rows: Optional[int] = None, out: Optional[Tensor] = None) -> Tensor:
+    """Rows row0 .. row0 + rows - 1 (default: all B T) of the tile batch of x (B, C, H, W), float32: (rows, C, h, w), an exact copy of the
+    windows in the plan's sample-major order.  out: a preallocated result (a captured launch).  Inference only."""
+    if not isinstance(x, Tensor) or x.ndim != 4 or tuple(x.shape[2:]) != (plan.H, plan.W):
+        raise ValueError(f"tile_gather: x must be (B, C, {plan.H}, {plan.W}), got {tuple(getattr(x, 'shape', ())) or type(x).__name__}")
+    x = _tile_check("tile_gather", x, x.shape, "x")
+    B, C = int(x.shape[0]), int(x.shape[1])
+    total = B * plan.T
+    rows = total - int(row0) if rows is None else int(rows)
+    row0 = int(row0)
+    if row0 < 0 or rows < 1 or row0 + rows > total:
+        raise ValueError(f"tile_gather: rows [{row0}, {row0 + rows}) do not lie in the tile batch of {total} rows")
+    shape = (rows, C, plan.h, plan.w)
+    out = torch.empty(shape, dtype=torch.float32, device=x.device) if out is None else _tile_check("tile_gather", out, shape, "out")
+    oy, ox, _, _ = plan.device(x.device)
+    call("hdmoe_tile_gather", out, x, oy, ox, B, C, plan.H, plan.W, plan.h, plan.w, plan.Ty, plan.Tx, row0, rows)
+    return out
+
+
+def tile_blend(tiles: Tensor, plan: TilePlan, B: int, out: Optional[Tensor] = None) -> Tensor:
+    """The (B, C, H, W) blend of the tile batch tiles (B T, C, h, w), float32:
+    out[b, c, y, x] = sum_ky sum_kx (ny[ky, y] nx[kx, x]) tiles[(b Ty + ky) Tx + kx, c, y - oy[ky], x - ox[kx]] over the covering tiles,
+    fp32 fma in that order, every element written once (deterministic).  out: a preallocated result.  Inference only."""
+    B = int(B)
+    if not isinstance(tiles, Tensor) or tiles.ndim != 4 or B < 1 or tuple(tiles.shape) != (B * plan.T, tiles.shape[1], plan.h, plan.w):
+        raise ValueError(f"tile_blend: tiles must be (B T = {B * plan.T}, C, {plan.h}, {plan.w}), got "
+                         f"{tuple(getattr(tiles, 'shape', ())) or type(tiles).__name__}")
+    tiles = _tile_check("tile_blend", tiles, tiles.shape, "tiles")
+    C = int(tiles.shape[1])
+    shape = (B, C, plan.H, plan.W)
+    out = torch.empty(shape, dtype=torch.float32, device=tiles.device) if out is None else _tile_check("tile_blend", out, shape, "out")
+    oy, ox, ny, nx = plan.device(tiles.device)
+    call("hdmoe_tile_blend", out, tiles, oy, ox, ny, nx, B, C, plan.H, plan.W, plan.h, plan.w, plan.Ty, plan.Tx)
+    return out
 
 
 def mp_sum(a: Tensor, b: Tensor, t: float = 0.5) -> Tensor:

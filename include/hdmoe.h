@@ -298,6 +298,26 @@ int hdmoe_heun_correct_hat(float* out, const float* xh, const float* den, const 
 int hdmoe_dpm2m_sde_step(float* x_out, const float* x, const float* den, float* den_prev, const double* t, const int* idx, const int* i0, long n,
                          const float* x0, const float* noise, const float* mask, float eta, float s_noise, const unsigned long long* seed,
                          HS stream);
+/* Tiled sampling (csrc/tiles.hip): a (B, C, H, W) latent larger than the model's (h, w) is evaluated on Ty x Tx overlapping model-sized
+ * windows and the outputs are blended back.  All tensors fp32 NCHW.  oy[Ty] / ox[Tx]: int32 DEVICE arrays of the tile origins along y / x
+ * (0 <= origin <= H - h / W - w; the kernels clamp an origin into that range, so no access leaves a tensor whatever the arrays hold).
+ * Tile-batch row r = (b Ty + ky) Tx + kx is tile (ky, kx) of sample b.
+ * tile_gather: tiles[0 .. rows) <- rows row0 .. row0 + rows - 1 of the tile batch, cropped out of x: tiles[r - row0][c][i][j] =
+ * x[b][c][oy[ky] + i][ox[kx] + j], an exact copy.
+ * tile_blend: ny[Ty][H] / nx[Tx][W]: fp32 DEVICE tables of the normalised 1-D window weights, zero where the tile does not cover the
+ * position.  out[b][c][y][x] = sum over ky ascending, kx ascending within it, of fl(ny[ky][y] nx[kx][x]) tiles[(b Ty + ky) Tx + kx][c][y - oy[ky]][x - ox[kx]]:
+ * one fp32 product for the weight, then fma accumulation in that order from -0 (so one covering tile of weight 1 returns its value bit for
+ * bit).  Tiles that do not cover the position and terms of weight zero are skipped.  Every output element is written once, by one lane:
+ * no atomics, no zero-fill, deterministic.
+ * 16-byte accesses when W, w and every x origin are multiples of 4 and the pointers are aligned (four consecutive x then lie wholly inside
+ * or outside any tile; the origins are read on the device, the kernel picks the arm), else element by element.
+ * HDMOE_EINVAL, nothing launched: a NULL pointer, a size < 1, h > H or w > W, Ty or Tx outside [1, HDMOE_TILE_MAX_AXIS]; tile_gather also
+ * row0 < 0, rows < 1, row0 + rows > B Ty Tx. */
+#define HDMOE_TILE_MAX_AXIS 32
+int hdmoe_tile_gather(float* tiles, const float* x, const int* oy, const int* ox, int B, int C, int H, int W, int h, int w, int Ty, int Tx,
+                      long row0, long rows, HS stream);
+int hdmoe_tile_blend(float* out, const float* tiles, const int* oy, const int* ox, const float* ny, const float* nx, int B, int C, int H, int W,
+                     int h, int w, int Ty, int Tx, HS stream);
 /* Measurement aid: `blocks` x 256 threads, 8 x `iters` dependent v_exp_f32 per thread (out: blocks * 256 floats).  bench.py times it to state the
  * transcendental issue rate the attention kernels (reference models/model_internals.py:374-404: one exp per score) are bounded by. */
 int hdmoe_exp_rate(float* out, int blocks, int iters, HS stream);
