@@ -19,6 +19,7 @@ namespace {
 
 struct LwgArgs {
   const void* x; const void* dy; float* G[HDMOE_MAX_GROUPS]; const int* seg;
+  const void* dy2; float* G2;   // DUAL only (below)
   int ngroups, N, I, O, upw;
   long HW;
 };
@@ -38,8 +39,9 @@ DEVI bool lwg_slot(const LwgArgs& a, int slot, int& g, long& p0, long& p1, long&
   return false;
 }
 
-template <int OT, int IT>
-DEVI void lwg_flush(f32x16 (&acc)[OT][IT], float* red, float* G, int o0, int i0, int I, int tid) {
+// DUAL: output tile t = 1 is the second layer's: rows o0 .. of its own slab G2
+template <int OT, int IT, bool DUAL = false>
+DEVI void lwg_flush(f32x16 (&acc)[OT][IT], float* red, float* G, int o0, int i0, int I, int tid, float* G2 = nullptr) {
   // red: [4 waves][OT * IT][16 regs][64 lanes] floats; lane-major so that both the write and the summing read are conflict-free
   const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
@@ -58,13 +60,17 @@ DEVI void lwg_flush(f32x16 (&acc)[OT][IT], float* red, float* G, int o0, int i0,
     float v = 0.f;
 #pragma unroll
     for (int w = 0; w < 4; ++w) v += red[((w * OT * IT + tu) * 16 + reg) * 64 + l];
-    const int o = o0 + 32 * (tu / IT) + acc_row(reg, l), i = i0 + 32 * (tu % IT) + (l & 31);
-    atomicAdd(&G[(long)o * I + i], v);
+    const int o = o0 + (DUAL ? 0 : 32 * (tu / IT)) + acc_row(reg, l), i = i0 + 32 * (tu % IT) + (l & 31);
+    atomicAdd(&((DUAL && tu / IT) ? G2 : G)[(long)o * I + i], v);
   }
 }
 
-template <int OT, int IT>
+// DUAL (hdmoe_lwgrad2): two layers with 32 outputs each over the SAME x -- the dy sub-tile t = 0 is read from dy, t = 1 from dy2 (both
+// [P][32]) and the tiles flush into G / G2; x is read once.  Slices, waves and the order in which a workgroup sums are those of each
+// layer's own OT = 1 launch.
+template <int OT, int IT, bool DUAL = false>
 __global__ __launch_bounds__(256) void lwg_bf16_kernel(LwgArgs a) {
+  static_assert(!DUAL || OT == 2, "two layers = two output tiles");
   // per wave: dy sub-tiles [OT][64 positions][64 B], x sub-tiles [IT][64][64 B]; reused for the cross-wave reduction at the end
   constexpr int WB = (OT + IT) * 4096;
   extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
@@ -74,6 +80,7 @@ __global__ __launch_bounds__(256) void lwg_bf16_kernel(LwgArgs a) {
   if (!lwg_slot(a, blockIdx.z, g, p0, p1, u0, u1)) return;
   const bf16* X = (const bf16*)a.x;
   const bf16* DY = (const bf16*)a.dy;
+  const bf16* DY2 = (const bf16*)a.dy2;
   unsigned char* mine = lds + wave * WB;
   uint4 sdy[4 * OT], sx[4 * IT];
   auto load = [&](long u) {
@@ -82,7 +89,8 @@ __global__ __launch_bounds__(256) void lwg_bf16_kernel(LwgArgs a) {
     for (int k = 0; k < 4 * OT; ++k) {
       const int e = lane + 64 * k, q = e / (4 * OT), pc = e % (4 * OT);
       const long p = pb + q;
-      sdy[k] = *reinterpret_cast<const uint4*>(DY + (p < p1 ? p : p0) * a.O + o0 + pc * 8);
+      if constexpr (DUAL) sdy[k] = *reinterpret_cast<const uint4*>((pc < 4 ? DY : DY2) + (p < p1 ? p : p0) * 32 + (pc & 3) * 8);
+      else sdy[k] = *reinterpret_cast<const uint4*>(DY + (p < p1 ? p : p0) * a.O + o0 + pc * 8);
     }
 #pragma unroll
     for (int k = 0; k < 4 * IT; ++k) {
@@ -153,7 +161,7 @@ __global__ __launch_bounds__(256) void lwg_bf16_kernel(LwgArgs a) {
     }
   }
   __syncthreads();                                            // every wave is done with its sub-tiles: the flush re-uses the whole buffer
-  lwg_flush<OT, IT>(acc, reinterpret_cast<float*>(lds), a.G[g], o0, i0, a.I, tid);
+  lwg_flush<OT, IT, DUAL>(acc, reinterpret_cast<float*>(lds), a.G[g], o0, i0, a.I, tid, a.G2);
 }
 
 template <int OT, int IT>
@@ -450,7 +458,7 @@ int lwg_try_launch(const void* x, const void* dy, float* const* G, const int* se
   if (Cin % 32 || Cout % 32 || (dtype != HDMOE_BF16 && dtype != HDMOE_F32)) return 1;
   if (((uintptr_t)x | (uintptr_t)dy) & 15) return 1;
   LwgArgs a;
-  a.x = x; a.dy = dy; a.seg = seg; a.ngroups = ngroups; a.N = N; a.HW = HW; a.I = Cin; a.O = Cout;
+  a.x = x; a.dy = dy; a.seg = seg; a.ngroups = ngroups; a.N = N; a.HW = HW; a.I = Cin; a.O = Cout; a.dy2 = nullptr; a.G2 = nullptr;
   for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) a.G[g] = G[g < ngroups ? g : 0];
   const int OT = Cout % 64 == 0 ? 2 : 1, IT = Cin % 64 == 0 ? 2 : 1;
   const long ib = Cin / (32 * IT), ob = Cout / (32 * OT);
@@ -470,5 +478,29 @@ int lwg_try_launch(const void* x, const void* dy, float* const* G, const int* se
     if (dtype == HDMOE_BF16) hipLaunchKernelGGL((lwg_bf16_kernel<O, I>), grid, dim3(256), stage > red ? stage : red, stream, a);
     else hipLaunchKernelGGL((lwg_f32_kernel<O, I>), grid, dim3(256), red, stream, a);
   }); });
+  return hdmoe_launch_status();
+}
+
+// Weight gradients of two pointwise bf16 layers with 32 outputs each over the same x [P][Cin] in one launch: G1 ([32][Cin] fp32) +=
+// dy1^T x, G2 += dy2^T x.  The grid is the one a single such layer gets (lwg_try_launch), so every workgroup forms for each slab the
+// partial sum it would form there.  Domain: bf16, Cin % 64 == 0, 16-byte aligned tensors; 1 outside it, nothing launched.
+extern "C" int hdmoe_lwgrad2(const void* x, const void* dy1, const void* dy2, float* G1, float* G2, long P, int Cin, int dtype,
+                             hipStream_t stream) {
+  if (dtype != HDMOE_BF16 || Cin % 64 || Cin < 64) return 1;
+  if (!x || !dy1 || !dy2 || !G1 || !G2 || P < 0) return HDMOE_EINVAL;
+  if ((((uintptr_t)x | (uintptr_t)dy1 | (uintptr_t)dy2) & 15) || (((uintptr_t)G1 | (uintptr_t)G2) & 3) || P >= (1l << 40)) return 1;
+  if (P == 0) return HDMOE_OK;
+  LwgArgs a;
+  a.x = x; a.dy = dy1; a.dy2 = dy2; a.seg = nullptr; a.ngroups = 1; a.N = 1; a.HW = P; a.I = Cin; a.O = 32; a.G2 = G2;
+  for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) a.G[g] = G1;
+  const long ib = Cin / 64;
+  const long units = (P + 63) / 64 + 1;                                  // as lwg_try_launch counts them for one group, OT = 1, IT = 2
+  long upw = (units * ib + 511) / 512;
+  if (upw < 4) upw = 4;
+  if (upw > 4096) upw = 4096;
+  a.upw = (int)upw;
+  const long slots = units / upw + 2;
+  if (slots > 65535) return 1;
+  hipLaunchKernelGGL((lwg_bf16_kernel<2, 2, true>), dim3((unsigned)ib, 1, (unsigned)slots), dim3(256), (size_t)4 * 2 * 2 * 4096, stream, a);
   return hdmoe_launch_status();
 }

@@ -1873,8 +1873,9 @@ FUSION_FUSED = True                                     # False: always the unfu
 
 class _FusionInFn(torch.autograd.Function):
     """(query, ctx, q, k, v) = hdmoe_fusion_in_fwd(fu, fv, sw) with the prepared images of the weight-bank entries ``ents`` (q, k, v
-    projection); without ``sw`` query and ctx are fu and fv themselves.  The backward is one hdmoe_fusion_in_bwd launch for dfu, dfv
-    and dsw -- the gradient fan-in of query and ctx included -- and one weight-only launch per projection into the bank's slabs."""
+    projection); without ``sw`` query and ctx are fu and fv themselves.  The backward is ONE launch: hdmoe_fusion_in_bwd_wg for dfu, dfv
+    and dsw -- the gradient fan-in of query and ctx included -- and the three projections' weight gradients, contracted from the rows the
+    kernel holds (query and ctx recomputed from fu, fv, sw) straight into the bank's slabs; hdmoe_fusion_in_bwd when no weight wants one."""
 
     @staticmethod
     def forward(ctx, fu, fv, sw, ents, S, *weights):
@@ -1886,25 +1887,28 @@ class _FusionInFn(torch.autograd.Function):
                 ents[0].alpha, ents[1].alpha, ents[2].alpha, BF16) != 0:
             raise RuntimeError("hdmoe_fusion_in_fwd declined a call that ops.fusion_in admitted")
         ctx.ents, ctx.bank, ctx.S, ctx.pool_ok = ents, _bank.ACTIVE, S, sw is not None and not sw.is_leaf
-        ctx.save_for_backward(fu, fv, *(() if sw is None else (sw, query, cx)))
+        ctx.save_for_backward(fu, fv, *(() if sw is None else (sw,)))     # (the backward recomputes query and ctx from these)
         STATS["fusion_in"] += 1
         return (fu, fv, q, k, v) if sw is None else (query, cx, q, k, v)
 
     @staticmethod
     def backward(ctx, gquery, gctx, gq, gk, gv):
         fu, fv, *rest = ctx.saved_tensors
-        sw, query, cx = rest if rest else (None, fu, fv)
+        sw = rest[0] if rest else None
         ents, rows = ctx.ents, fu.numel() // 32
         gq, gk, gv = (torch.zeros_like(fu) if g is None else _c(g) for g in (gq, gk, gv))
         dfu, dfv = torch.empty_like(fu), torch.empty_like(fv)
         dsw = None if sw is None else _zeros(sw.shape, torch.float32, sw.device, ctx.pool_ok)
-        if call("hdmoe_fusion_in_bwd", gq, gk, gv, _c(gquery), _c(gctx), fu, fv, sw, ents[0].wd, ents[1].wd, ents[2].wd, dfu, dfv, dsw,
-                rows, ctx.S, 32, ents[0].alpha, ents[1].alpha, ents[2].alpha, BF16) != 0:
-            raise RuntimeError("hdmoe_fusion_in_bwd declined a call whose forward ran fused")
+        head = (gq, gk, gv, _c(gquery), _c(gctx), fu, fv, sw, ents[0].wd, ents[1].wd, ents[2].wd, dfu, dfv, dsw)
+        tail = (rows, ctx.S, 32, ents[0].alpha, ents[1].alpha, ents[2].alpha, BF16)
         if any(ctx.needs_input_grad[5:]):
-            # weight gradients on the weight-only kernel, straight into the bank's slabs (finished with every other layer's)
-            for ent, x, dy in zip(ents, (query, cx, cx), (gq, gk, gv)):
-                _bank_wgrad(ctx.bank, ent, x, dy, rows, 32, 32)
+            # with the weight gradients, straight into the bank's slabs (finished with every other layer's)
+            if call("hdmoe_fusion_in_bwd_wg", *head, ents[0].G[0], ents[1].G[0], ents[2].G[0], 0, *tail) != 0:
+                raise RuntimeError("hdmoe_fusion_in_bwd_wg declined a call whose forward ran fused")
+            for ent in ents:
+                ctx.bank.note_backward(ent)
+        elif call("hdmoe_fusion_in_bwd", *head, *tail) != 0:
+            raise RuntimeError("hdmoe_fusion_in_bwd declined a call whose forward ran fused")
         return (dfu, dfv, dsw, None, None) + (None,) * len(ents)
 
 
@@ -1929,55 +1933,52 @@ def fusion_in(fu: Tensor, fv: Tensor, sw: Optional[Tensor], projs, gain: float =
     return _FusionInFn.apply(fu, fv, sw, ents, int(fu.shape[1]), *ws)
 
 
-def _bank_wgrad(bank, ent, x, dy, rows: int, I: int, O: int) -> None:
-    """Weight gradient of pointwise bank layer ``ent`` on the weight-only kernel, from x (rows, I) and dy (rows, O), into the bank's slab."""
-    _timed("conv_wgrad", lambda: _conv_record(x, None, 1, rows, O, I, [1], [1], wgrad_name="towg_bf16_kernel" if O <= 4 else "lwg_bf16_kernel"),
-           "hdmoe_conv_wgrad", x, dy, list(ent.G), None, 1, 1, 1, rows, 1, rows, I, I, O, 1, 0, [1], [1], [0], [0], BF16)
-    bank.note_backward(ent)
-
-
 class _FusionOutFn(torch.autograd.Function):
     """(mixed, gate) = hdmoe_fusion_out_fwd(o2, a, U): out_proj of the text cross-attention with its residual, lerp_param, mp_cat, gate1,
     mp_silu, gate2 and gate_mix.  ``ents``: the bank entries of out_proj, gate1, gate2; ``k`` = (alpha_o, beta_o, wa, wb).  The backward
-    is one hdmoe_fusion_out_bwd launch (do2, da, dU, dalpha) and one weight-only launch per layer."""
+    is ONE launch: hdmoe_fusion_out_bwd_wg (do2, da, dU, dalpha and the three layers' weight gradients into the bank's slabs; their dy
+    never leave the kernel and their x, cat and s, are recomputed from U, a2, g1 -- so the forward saves a2 and g1 alone);
+    hdmoe_fusion_out_bwd when no weight wants a gradient."""
 
     @staticmethod
     def forward(ctx, o2, a, U, alpha_txt, ents, k, *weights):
         ctx.set_materialize_grads(False)
         rows = o2.numel() // 32
         mixed = torch.empty_like(U)
-        a2 = g1 = s = cat = None
+        a2 = g1 = None
         if any(ctx.needs_input_grad):                          # (else: inference, nothing is saved)
-            a2, g1, s = (torch.empty_like(U) for _ in range(3))
-            cat = torch.empty((rows, 64), dtype=U.dtype, device=U.device)
+            a2, g1 = torch.empty_like(U), torch.empty_like(U)
         gate = torch.empty((*U.shape[:-1], 2), dtype=torch.float32, device=U.device)
         consts = (*k, ents[1].alpha, ents[2].alpha)
-        if call("hdmoe_fusion_out_fwd", o2, a, U, alpha_txt, ents[0].wf, ents[1].wf, ents[2].wf, mixed, gate, a2, g1, cat, s, rows, 32,
+        if call("hdmoe_fusion_out_fwd", o2, a, U, alpha_txt, ents[0].wf, ents[1].wf, ents[2].wf, mixed, gate, a2, g1, None, None, rows, 32,
                 *consts, BF16) != 0:
             raise RuntimeError("hdmoe_fusion_out_fwd declined a call that ops.fusion_out admitted")
         ctx.ents, ctx.bank, ctx.consts = ents, _bank.ACTIVE, consts
         if a2 is not None:
-            ctx.save_for_backward(o2, a, U, alpha_txt, a2, g1, cat, s, gate)
+            ctx.save_for_backward(o2, a, U, alpha_txt, a2, g1, gate)
         STATS["fusion_out"] += 1
         return mixed, gate
 
     @staticmethod
     def backward(ctx, dmixed, dgate):
-        o2, a, U, alpha_txt, a2, g1, cat, s, gate = ctx.saved_tensors
+        o2, a, U, alpha_txt, a2, g1, gate = ctx.saved_tensors
         ents, rows = ctx.ents, o2.numel() // 32
         dmixed = torch.zeros_like(U) if dmixed is None else _c(dmixed)
         dgate = None if dgate is None else _f32(dgate)
-        do2, da, dU, dat, dg1 = torch.empty_like(o2), torch.empty_like(a), torch.empty_like(U), torch.empty_like(o2), torch.empty_like(o2)
-        dl = torch.empty((rows, 2), dtype=U.dtype, device=U.device)
+        do2, da, dU = torch.empty_like(o2), torch.empty_like(a), torch.empty_like(U)
         direct = _direct(alpha_txt)
         dal = alpha_txt.grad if direct else torch.zeros_like(alpha_txt)
-        if call("hdmoe_fusion_out_bwd", dmixed, dgate, gate, U, a2, g1, o2, a, alpha_txt, ents[0].wf, ents[0].wd, ents[1].wd, ents[2].wd,
-                do2, da, dU, dat, dg1, dl, dal, rows, 32, *ctx.consts, BF16) != 0:
-            raise RuntimeError("hdmoe_fusion_out_bwd declined a call whose forward ran fused")
+        head = (dmixed, dgate, gate, U, a2, g1, o2, a, alpha_txt, ents[0].wf, ents[0].wd, ents[1].wd, ents[2].wd, do2, da, dU)
         if any(ctx.needs_input_grad[6:]):
-            _bank_wgrad(ctx.bank, ents[2], s, dl, rows, 32, 2)
-            _bank_wgrad(ctx.bank, ents[1], cat, dg1, rows, 64, 32)
-            _bank_wgrad(ctx.bank, ents[0], o2, dat, rows, 32, 32)
+            if call("hdmoe_fusion_out_bwd_wg", *head, dal, ents[0].G[0], ents[1].G[0], ents[2].G[0], 0, rows, 32, *ctx.consts, BF16) != 0:
+                raise RuntimeError("hdmoe_fusion_out_bwd_wg declined a call whose forward ran fused")
+            for ent in ents:
+                ctx.bank.note_backward(ent)
+        else:
+            dat, dg1 = torch.empty_like(o2), torch.empty_like(o2)       # (the dy of weight gradients nobody asked for)
+            dl = torch.empty((rows, 2), dtype=U.dtype, device=U.device)
+            if call("hdmoe_fusion_out_bwd", *head, dat, dg1, dl, dal, rows, 32, *ctx.consts, BF16) != 0:
+                raise RuntimeError("hdmoe_fusion_out_bwd declined a call whose forward ran fused")
         return (do2, da, dU, None if direct else dal, None, None) + (None,) * len(ents)
 
 
@@ -2002,6 +2003,102 @@ def fusion_out(o2: Tensor, a: Tensor, U: Tensor, alpha_txt: Tensor, w_out: Tenso
     c = math.sqrt(64 / 0.5)                                  # mp_cat(U, a2, 0.5) of two 32-channel tensors
     k = (float(alpha), float(beta), c * 0.5 / math.sqrt(32), c * 0.5 / math.sqrt(32))
     return _FusionOutFn.apply(o2, a, U, alpha_txt, ents, k, *ws)
+
+
+class _FusionMidFn(torch.autograd.Function):
+    """(a, q2) = hdmoe_fusion_mid_fwd(o1, query): out_proj of the first cross-attention with its residual, then q_proj of the text
+    attention.  ``ents``: their bank entries; ``k`` = (alpha_o, beta_o).  The backward is one hdmoe_fusion_mid_bwd launch: the gradient
+    fan-in of a (no ATen add), do1, the residual's share of query's gradient and both weight gradients into the bank's slabs."""
+
+    @staticmethod
+    def forward(ctx, o1, query, ents, k, *weights):
+        ctx.set_materialize_grads(False)
+        rows = o1.numel() // 32
+        a, q2 = torch.empty_like(query), torch.empty_like(query)
+        if call("hdmoe_fusion_mid_fwd", o1, query, ents[0].wf, ents[1].wf, a, q2, rows, 32, *k, ents[1].alpha, BF16) != 0:
+            raise RuntimeError("hdmoe_fusion_mid_fwd declined a call that ops.fusion_mid admitted")
+        ctx.ents, ctx.bank, ctx.k = ents, _bank.ACTIVE, k
+        ctx.save_for_backward(o1, a)
+        STATS["fusion_mid"] += 1
+        return a, q2
+
+    @staticmethod
+    def backward(ctx, da, dq2):
+        o1, a = ctx.saved_tensors
+        ents, rows = ctx.ents, o1.numel() // 32
+        da, dq2 = (torch.zeros_like(a) if g is None else _c(g) for g in (da, dq2))
+        do1, dres = torch.empty_like(o1), torch.empty_like(a)
+        wg = any(ctx.needs_input_grad[4:])
+        if call("hdmoe_fusion_mid_bwd", da, dq2, a, o1, ents[0].wd, ents[1].wd, do1, dres, ents[0].G[0] if wg else None,
+                ents[1].G[0] if wg else None, 0, rows, 32, *ctx.k, ents[1].alpha, BF16) != 0:
+            raise RuntimeError("hdmoe_fusion_mid_bwd declined a call whose forward ran fused")
+        if wg:
+            for ent in ents:
+                ctx.bank.note_backward(ent)
+        return (do1, dres, None, None) + (None,) * len(ents)
+
+
+def fusion_mid(o1: Tensor, query: Tensor, w_out: Tensor, alpha: float, beta: float, w_q: Tensor, gain: float = 1.0):
+    """Between the fusion stage's two attention cores in one launch: a = out_proj(o1) mixed with the residual ``query`` (alpha, beta as
+    MP_Attention passes them to mp_conv), q2 = q_proj(a) of the text attention.  o1, query: (B, S, 32).  Returns (a, q2), or None outside
+    the fused kernel's domain (as ops.fusion_in): the caller then runs the two layers."""
+    bank = _bank.ACTIVE
+    if not (FUSION_FUSED and _prof_ok() and bank is not None and o1.is_cuda and o1.ndim == 3 and o1.shape == query.shape and o1.shape[-1] == 32
+            and o1.dtype == query.dtype == torch.bfloat16 and o1.is_contiguous() and query.is_contiguous()
+            and o1.data_ptr() % 16 == 0 and query.data_ptr() % 16 == 0 and o1.numel() > 0):
+        return None
+    ws = f32_params([w_out, w_q])
+    if not all(w.shape[0] == 32 and w.shape[1] == 32 and _kernel_hw(w) == (1, 1) for w in ws) or ws[0].requires_grad != ws[1].requires_grad:
+        return None
+    ents = [bank.lookup([ws[0]], torch.bfloat16, float(gain), float(alpha), True), bank.lookup([ws[1]], torch.bfloat16, float(gain), 1.0, True)]
+    if any(e is None for e in ents):
+        return None
+    return _FusionMidFn.apply(o1, query, ents, (float(alpha), float(beta)), *ws)
+
+
+class _KVProjFn(torch.autograd.Function):
+    """(k, v) = hdmoe_kgemm2_fwd(x): two 32-output pointwise layers (bank entries ``ents``) over the same wide input, x read once; the
+    backward is one hdmoe_lwgrad2 launch into both slabs.  x gets no gradient (ops.kv_proj admits only inputs that want none)."""
+
+    @staticmethod
+    def forward(ctx, x, ents, *weights):
+        ctx.set_materialize_grads(False)
+        rows, K = x.numel() // x.shape[-1], int(x.shape[-1])
+        k, v = (torch.empty((*x.shape[:-1], 32), dtype=x.dtype, device=x.device) for _ in range(2))
+        if call("hdmoe_kgemm2_fwd", x, ents[0].wf, ents[1].wf, k, v, rows, K, ents[0].alpha, ents[1].alpha, BF16) != 0:
+            raise RuntimeError("hdmoe_kgemm2_fwd declined a call that ops.kv_proj admitted")
+        ctx.ents, ctx.bank = ents, _bank.ACTIVE
+        ctx.save_for_backward(x)
+        return k, v
+
+    @staticmethod
+    def backward(ctx, gk, gv):
+        (x,) = ctx.saved_tensors
+        ents, rows, K = ctx.ents, x.numel() // x.shape[-1], int(x.shape[-1])
+        if any(ctx.needs_input_grad[2:]):
+            gk, gv = (torch.zeros((rows, 32), dtype=x.dtype, device=x.device) if g is None else _c(g) for g in (gk, gv))
+            if call("hdmoe_lwgrad2", x, gk, gv, ents[0].G[0], ents[1].G[0], rows, K, BF16) != 0:
+                raise RuntimeError("hdmoe_lwgrad2 declined a call whose forward ran fused")
+            for ent in ents:
+                ctx.bank.note_backward(ent)
+        return (None, None) + (None,) * len(ents)
+
+
+def kv_proj(x: Tensor, w_k: Tensor, w_v: Tensor, gain: float = 1.0):
+    """k, v = two pointwise projections (weight tensors, plain ``gain``) of the same x (..., C) in one launch per direction.  Returns (k, v),
+    or None outside the domain -- bf16 x that wants no gradient, C % 64 == 0 and >= 512 (the long-contraction kernel's), 32 outputs each,
+    both projections ready weight-bank entries: the caller then runs the two layers on their own."""
+    bank = _bank.ACTIVE
+    if not (FUSION_FUSED and _prof_ok() and bank is not None and x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous()
+            and not x.requires_grad and x.numel() > 0 and x.shape[-1] % 64 == 0 and x.shape[-1] >= 512 and x.data_ptr() % 16 == 0):
+        return None
+    ws = f32_params([w_k, w_v])
+    if not all(w.shape[0] == 32 and w.shape[1] == x.shape[-1] and _kernel_hw(w) == (1, 1) for w in ws) or ws[0].requires_grad != ws[1].requires_grad:
+        return None
+    ents = [bank.lookup([w], torch.bfloat16, float(gain), 1.0, True) for w in ws]      # (the key ops.mp_conv registers the layer under)
+    if any(e is None for e in ents):
+        return None
+    return _KVProjFn.apply(x, ents, *ws)
 
 
 class _SoftmaxRowsFn(torch.autograd.Function):

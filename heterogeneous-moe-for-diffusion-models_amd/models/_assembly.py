@@ -319,13 +319,22 @@ class _HDMOEMBase(nn.Module):
         ca = self.cross_attn
         # fusion inputs + the q / k / v projections in one launch (csrc/fusion.hip); None outside its domain: the op chain
         head = None if ca.time_dependent else ops.fusion_in(fu, fv, sw, (ca.q_proj.weights, ca.k_proj.weights, ca.v_proj.weights), 1.0)
+        cat = self.cross_attn_text
+        mid = None
         if head is not None:
-            a = ca._attend(*head, gain_s=1.0)
+            o1 = ca._attend(*head, gain_s=1.0, core_only=True)
+            # out_proj with its residual and the text attention's q_proj in one launch (csrc/fusion.hip); None outside its domain
+            if not cat.time_dependent and text_c is not None:
+                mid = ops.fusion_mid(o1, head[0], ca.out_proj.weights, *ca._out_mix(), cat.q_proj.weights, 1.0)
+            a = mid[0] if mid is not None else ca._project_out(o1, head[0], 1.0)
         else:
             q, ctx = self._fusion_inputs(fu, fv, sw)
             a = ca(query=q, context=ctx, gain_s=1.0, gain_t=1.0)
-        cat = self.cross_attn_text
-        o2 = cat(query=a, context=text_c, gain_s=1.0, gain_t=1.0, core_only=True)
+        if mid is not None:
+            tctx = ops.cast(text_c, a.dtype)
+            o2 = cat._attend(a, tctx, mid[1], *cat._project_kv(tctx, 1.0, True), 1.0, core_only=True)
+        else:
+            o2 = cat(query=a, context=text_c, gain_s=1.0, gain_t=1.0, core_only=True, paired_kv=True)
         # everything behind the text attention in one launch (csrc/fusion.hip); None outside its domain: the op chain
         tail = ops.fusion_out(o2, a, out_u, self.alpha_txt, cat.out_proj.weights, *cat._out_mix(), self.gate1.weights, self.gate2.weights, 1.0)
         if tail is not None:

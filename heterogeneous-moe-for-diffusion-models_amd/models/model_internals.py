@@ -199,14 +199,14 @@ class MP_Attention(nn.Module):
         self.out_proj = MP_Conv(emb_dim, emb_dim, kernel=(1, 1))
 
     def forward(self, query: Tensor, gain_s: float, gain_t: float, context: Optional[Tensor] = None,
-                time_embedding: Optional[Tensor] = None, core_only: bool = False) -> Tensor:
+                time_embedding: Optional[Tensor] = None, core_only: bool = False, paired_kv: bool = False) -> Tensor:
+        """paired_kv: k_proj and v_proj in one launch per direction where ops.kv_proj takes them (the fusion stage's text attention)."""
         batch_size, seq_len, emb_dim = query.shape
         assert emb_dim == self.emb_dim
         dt = query.dtype
         ctx = query if context is None else ops.cast(context, dt)
         q = self.q_proj._fwd(query, gain_s)
-        k = self.k_proj._fwd(ctx, gain_s)
-        v = self.v_proj._fwd(ctx, gain_s)
+        k, v = self._project_kv(ctx, gain_s, paired_kv)
         if self.time_dependent and time_embedding is not None:
             te = ops.cast(time_embedding.reshape(batch_size, -1), torch.float32)
             q = ops.seq_bcast_add(q, self.q_time._fwd(te, gain_t))
@@ -214,6 +214,11 @@ class MP_Attention(nn.Module):
                 k = ops.seq_bcast_add(k, self.k_time._fwd(te, gain_t))
                 v = ops.seq_bcast_add(v, self.v_time._fwd(te, gain_t))
         return self._attend(query, ctx, q, k, v, gain_s, core_only)
+
+    def _project_kv(self, ctx: Tensor, gain_s: float, paired: bool):
+        """k_proj(ctx), v_proj(ctx); paired: the context is read once for both (ops.kv_proj), outside that launch's domain the two layers."""
+        kv = ops.kv_proj(ctx, self.k_proj.weights, self.v_proj.weights, gain_s) if paired and ctx.ndim == 3 else None
+        return kv if kv is not None else (self.k_proj._fwd(ctx, gain_s), self.v_proj._fwd(ctx, gain_s))
 
     def _attend(self, query: Tensor, ctx: Tensor, q: Tensor, k: Tensor, v: Tensor, gain_s: float, core_only: bool = False) -> Tensor:
         """Attention core + out_proj with the residual, from projections already made (forward, or the fused head of the fusion stage).

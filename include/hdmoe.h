@@ -98,6 +98,15 @@ int hdmoe_conv_bwd6_film(const void* x, const void* dy, const void* wd, void* dx
  * (Cin / 32) * (Cout / 32) <= 8.  Returns 1 without launching outside it; the caller then uses hdmoe_conv_fwd + hdmoe_conv_wgrad. */
 int hdmoe_pw_bwd(const void* x, const void* dy, const void* wd, void* dx, float* const* G, const int* seg, int ngroups,
                  long wd_stride, int N, long HW, int Cin, int Cout, float alpha, int dtype, HS stream);
+/* Two pointwise bf16 layers with 32 outputs each over the SAME input (the k / v projections of a cross-attention over a wide context),
+ * one launch per direction, x read once (csrc/kgemm.hip, csrc/lwgrad.hip).  x [M][K]; w1 / w2 the prepared forward images [32][K].
+ *   hdmoe_kgemm2_fwd: y1 = alpha1 x w1^T, y2 = alpha2 x w2^T ([M][32]), each bit-equal to hdmoe_conv_fwd of its layer (the long-
+ *     contraction kernel: K % 64 == 0, K >= 512).
+ *   hdmoe_lwgrad2: G1 ([32][K] fp32) += dy1^T x, G2 += dy2^T x, each workgroup's partial sums those of hdmoe_conv_wgrad of the layer.
+ * Return 1 without launching outside the domain (bf16, K as above, 16-byte aligned x, images and dy). */
+int hdmoe_kgemm2_fwd(const void* x, const void* w1, const void* w2, void* y1, void* y2, long M, int K, float alpha1, float alpha2,
+                     int dtype, HS stream);
+int hdmoe_lwgrad2(const void* x, const void* dy1, const void* dy2, float* G1, float* G2, long P, int Cin, int dtype, HS stream);
 /* Fusion stage, the token-local chain in front of the first attention call in one launch per direction (csrc/fusion.hip).  All tensors
  * [rows][32] bf16, contiguous, 16-byte aligned; sw [rows / S] fp32 per-sample swap weights or NULL; wq / wk / wv the prepared FORWARD
  * images ([32][32]) of the three projections, wdq / wdk / wdv their flipped images, alpha_* the layers' output scales.
@@ -114,13 +123,23 @@ int hdmoe_fusion_in_fwd(const void* fu, const void* fv, const float* sw, const v
 int hdmoe_fusion_in_bwd(const void* dq, const void* dk, const void* dv, const void* gquery, const void* gctx, const void* fu,
                         const void* fv, const float* sw, const void* wdq, const void* wdk, const void* wdv, void* dfu, void* dfv,
                         float* dsw, long rows, long S, int C, float alpha_q, float alpha_k, float alpha_v, int dtype, HS stream);
+/* hdmoe_fusion_in_bwd with the three projections' weight gradients contracted in the same launch: Gq, Gk, Gv ([32][32] fp32, the
+ * bank's [O][I] slab of a 1x1 layer as hdmoe_conv_wgrad fills it) += dq^T query, dk^T ctx, dv^T ctx, with query / ctx recomputed from
+ * fu, fv, sw as the forward rounds them -- fu and fv are therefore read with and without sw.  dfu, dfv are bit-equal to
+ * hdmoe_fusion_in_bwd's; the slabs (and dsw) are fp32 sums in another order (accumulated per wave over its tiles, the four waves of a
+ * workgroup met in wave order, one float-atomic flush per workgroup).  max_wg: cap of the persistent grid, 0 = the default (512). */
+int hdmoe_fusion_in_bwd_wg(const void* dq, const void* dk, const void* dv, const void* gquery, const void* gctx, const void* fu,
+                           const void* fv, const float* sw, const void* wdq, const void* wdk, const void* wdv, void* dfu, void* dfv,
+                           float* dsw, float* Gq, float* Gk, float* Gv, int max_wg, long rows, long S, int C, float alpha_q,
+                           float alpha_k, float alpha_v, int dtype, HS stream);
 /* The chain behind the text attention of the fusion stage, down to the gate, in one launch per direction (csrc/fusion.hip).  Row tensors
  * [rows][32] bf16 unless noted; alpha_txt the device scalar of lerp_param; wo / w1 / w2 the forward images of cross_attn_text.out_proj
  * ([32][32], output scale alpha_o, residual weight beta_o), gate1 ([32][64], alpha_1) and gate2 ([2][32], alpha_2), wdo / wd1 / wd2
  * their flipped images ([32][32], [64][32], [32][16]); wa, wb the weights of mp_cat.
  *   fwd: at = alpha_o Wo o2 + beta_o a; a2 = a + alpha_txt (at - a); cat = [wa U | wb a2] ([rows][64]); g1 = alpha_1 W1 cat;
  *        s = mp_silu(g1); gate = softmax(alpha_2 W2 s) ([rows][2] fp32); mixed = hdmoe_gate_mix_fwd(logits, U, a2).
- *        a2, g1, cat, s are what the backward and the weight gradients read; all four NULL: not written (inference).
+ *        a2, g1 are what the backward reads, cat, s the x of hdmoe_conv_wgrad for gate1, gate2; all four NULL: not written
+ *        (inference); cat and s alone NULL: those two not written (hdmoe_fusion_out_bwd_wg recomputes them).
  *   bwd: from dmixed and dgate (or NULL): do2, da (the lerp's and the residual's share, summed), dU (gate_mix's and mp_cat's share,
  *        summed), dalpha += (fp32, one atomic per workgroup), and dat, dg1, dl ([rows][2]): the dy of the three weight gradients
  *        (hdmoe_conv_wgrad with x = o2, cat, s).
@@ -132,6 +151,30 @@ int hdmoe_fusion_out_bwd(const void* dmixed, const float* dgate, const float* ga
                          const void* o2, const void* a, const float* alpha_txt, const void* wo, const void* wdo, const void* wd1,
                          const void* wd2, void* do2, void* da, void* dU, void* dat, void* dg1, void* dl, float* dalpha, long rows,
                          int C, float alpha_o, float beta_o, float wa, float wb, float alpha_1, float alpha_2, int dtype, HS stream);
+/* hdmoe_fusion_out_bwd with the three layers' weight gradients contracted in the same launch: Go ([32][32] fp32), G1 ([32][64]),
+ * G2 ([2][32]), the bank's [O][I] slabs, += dat^T o2, dg1^T cat, dl^T s.  dat, dg1, dl are rounded to bf16 where hdmoe_fusion_out_bwd
+ * stores them and are not written; cat and s are recomputed from U, a2, g1 with the forward's formula and rounding.  do2, da, dU are
+ * bit-equal to hdmoe_fusion_out_bwd's; the slabs (and dalpha) are fp32 sums in another order, flushed as in hdmoe_fusion_in_bwd_wg.
+ * max_wg: cap of the persistent grid, 0 = the default (512). */
+int hdmoe_fusion_out_bwd_wg(const void* dmixed, const float* dgate, const float* gate, const void* U, const void* a2, const void* g1,
+                            const void* o2, const void* a, const float* alpha_txt, const void* wo, const void* wdo, const void* wd1,
+                            const void* wd2, void* do2, void* da, void* dU, float* dalpha, float* Go, float* G1, float* G2, int max_wg,
+                            long rows, int C, float alpha_o, float beta_o, float wa, float wb, float alpha_1, float alpha_2, int dtype,
+                            HS stream);
+/* The chain between the fusion stage's two attention cores in one launch per direction (csrc/fusion.hip).  Row tensors [rows][32] bf16;
+ * wo / wq the forward images of cross_attn.out_proj (output scale alpha_o, residual weight beta_o) and cross_attn_text.q_proj (alpha_q),
+ * wdo / wdq their flipped images.
+ *   fwd: a = alpha_o Wo o1 + beta_o query (rounded as hdmoe_conv_fwd's residual epilogue rounds it); q2 = alpha_q Wq a.
+ *   bwd: da_t = da + alpha_q Wq^T dq2 (the gradient fan-in of a); do1 = alpha_o Wo^T da_t; dres = beta_o da_t (the residual's share of
+ *        query's gradient); with Go, Gq ([32][32] fp32 slabs; both or neither): Go += da_t^T o1, Gq += dq2^T a, accumulated and flushed as
+ *        in hdmoe_fusion_in_bwd_wg (max_wg likewise); a and o1 are read only then.
+ * bf16 rounding wherever hdmoe_conv_fwd, hdmoe_pw_bwd, the bf16 sum of two gradients and hdmoe_axpby store a tensor: every bf16 output
+ * is bit-equal to theirs.  Returns 1 without launching outside the domain (bf16, C == 32, aligned). */
+int hdmoe_fusion_mid_fwd(const void* o1, const void* query, const void* wo, const void* wq, void* a, void* q2, long rows, int C,
+                         float alpha_o, float beta_o, float alpha_q, int dtype, HS stream);
+int hdmoe_fusion_mid_bwd(const void* da, const void* dq2, const void* a, const void* o1, const void* wdo, const void* wdq, void* do1,
+                         void* dres, float* Go, float* Gq, int max_wg, long rows, int C, float alpha_o, float beta_o, float alpha_q,
+                         int dtype, HS stream);
 int hdmoe_conv_bwd6s(const void* x, const void* dy, const void* wd, void* dx, float* const* G, const int* seg, int ngroups,
                      long wd_stride, long wd_plane, int N, int H, int W, int Cin, int Cout, const int* kh, const int* kw,
                      const int* pt, const int* pl, float alpha, void* ws, long ws_bytes, const float* in_scale, const float* in_shift,
@@ -200,7 +243,9 @@ enum {
   HDMOE_SEL_ATTN_BWD_MERGED = 29,  /* hdmoe_attn_bwd: the merged MFMA backward (Sq <= 1024) */
   HDMOE_SEL_ATTN_BWD_PAIR = 30,    /* hdmoe_attn_bwd: the MFMA dq + dk / dv pair (Sq > 1024) */
   HDMOE_SEL_ATTN_GENERIC = 31,     /* hdmoe_attn_fwd / hdmoe_attn_bwd: the one-row-per-thread kernels (one count per call) */
-  HDMOE_SEL_COUNT = 32
+  HDMOE_SEL_FUSION_MID = 32,       /* hdmoe_fusion_mid_fwd: cross_attn.out_proj with its residual + cross_attn_text.q_proj in one launch */
+  HDMOE_SEL_FUSION_MID_BWD = 33,   /* hdmoe_fusion_mid_bwd: their input gradients, the gradient fan-in of a and both weight gradients */
+  HDMOE_SEL_COUNT = 34
 };
 int hdmoe_kernel_selections(long long* counts, int n, int reset);
 
