@@ -57,6 +57,7 @@ solvers unchanged and only the denoiser evaluation is tiled: ``den_big = blend(m
 (``ops.tile_plan`` / ``ops.tile_gather`` / ``ops.tile_blend``, MultiDiffusion, Bar-Tal et al. 2023).  One method, ``_denoise_tiled``,
 serves the fused and captured stages and the host loops; the text, the router masks and the per-sample scales are repeated per tile row.
 """
+import collections
 import math
 import numbers
 
@@ -68,6 +69,35 @@ from hdmoe_hip import graph as hgraph
 from hdmoe_hip import ops
 
 SOLVERS = ("heun", "dpmpp_2m", "dpmpp_2m_sde")
+
+
+def _each(fn, *vs):
+    """fn over matching fields of _Inputs records: a tensor, or the `known` triple entry by entry; None (and the floats) pass through."""
+    if isinstance(vs[0], tuple):
+        return tuple(fn(*e) for e in zip(*vs))
+    return fn(*vs) if isinstance(vs[0], torch.Tensor) else vs[0]
+
+
+class _Inputs(collections.namedtuple("_Inputs", "text unc um vm g texts cw cm known transition_mean softness")):
+    """The operands of a denoiser evaluation, built once per sample() / denoise() call (EDM_Sampler._inputs) and handed down whole.  Per
+    row (B rows, B T with tiling): text; unc, the unconditional text; um / vm, the (B, E) router masks; g, the (B,) guidance scales.
+    Composed guidance: texts (K, B, ...) with text first, cw (B, K), cm (B, K, H, W).  known: the inpainting triple (x0, noise, mask) of
+    the solver updates.  All but text may be None.  transition_mean, softness: floats.  Whatever has to list the inputs is a method here."""
+    __slots__ = ()
+    PER_ROW = ("text", "unc", "um", "vm", "g")
+
+    def signature(self):                                      # what a capture bakes in: which fields exist, their shapes, the floats (last)
+        return tuple(_each(lambda a: tuple(a.shape), v) for v in self[:-2]) + (float(self.transition_mean), float(self.softness))
+
+    def empty_like(self):                                     # the static buffers of a capture
+        return self._make(_each(torch.empty_like, v) for v in self)
+
+    def copy_from(self, other):                               # refresh of the static buffers; a field they do not hold is skipped
+        for dst, src in zip(self, other):
+            _each(torch.Tensor.copy_, dst, src)
+
+    def per_row(self, fn):                                    # fn over the per-row fields: the tile-row repeat, a chunk of tile rows
+        return self._replace(**{k: _each(fn, getattr(self, k)) for k in self.PER_ROW})
 
 
 class EDM_Sampler:
@@ -142,10 +172,6 @@ class EDM_Sampler:
         evaluation (zero it before the first evaluation of a trajectory).  apg_momentum != 0 needs it; otherwise it is not used.
         compose_text / compose_weights / compose_masks: composed guidance, see sample(); guided=False is then D_c, the composed
         evaluation at scale 1."""
-        comp = self._check_compose(x, text_emb, uncond_text_emb, compose_text, compose_weights, compose_masks)
-        um = self._router_mask(Unet_router_mask, "Unet_router_mask", x.shape[0])
-        vm = self._router_mask(Vit_router_mask, "Vit_router_mask", x.shape[0])
-        g = self._check_guidance(guidance, x.shape[0])
         if self.apg_momentum != 0.0:
             ms = momentum_state
             if not isinstance(ms, torch.Tensor):
@@ -156,58 +182,73 @@ class EDM_Sampler:
                                  f"{tuple(ms.shape)} {ms.dtype} on {ms.device}")
         else:
             momentum_state = None
-        return self._denoise(x, sigma, text_emb, transition_mean, softness, uncond_text_emb, self._dev_mask(um, x), self._dev_mask(vm, x),
-                             bool(guided), self._dev_mask(g, x), momentum_state, self._dev_compose(comp, x, text_emb))
+        inp, _ = self._inputs(x, text_emb, transition_mean, softness, uncond_text_emb, Unet_router_mask=Unet_router_mask,
+                              Vit_router_mask=Vit_router_mask, guidance=guidance, compose_text=compose_text,
+                              compose_weights=compose_weights, compose_masks=compose_masks)
+        return self._denoise(x, sigma, inp, bool(guided), momentum_state)
 
-    def _denoise(self, x, sigma, text_emb, transition_mean, softness, uncond_text_emb, um=None, vm=None, guided=True, g=None, mom=None,
-                 comp=None):
-        """denoise() on validated device masks (or None) and a validated (B,) float32 device vector of scales g (or None: self.guide): no
-        host read, so it can run under stream capture.  guided False, or a float scale of 1: one plain conditional call.
+    def _denoise(self, x, sigma, inp, guided=True, mom=None):
+        """denoise() on the validated operands inp (_Inputs): no host read, so it can run under stream capture.  inp.g None: the scale
+        is self.guide.  guided False, or a float scale of 1: one plain conditional call.
         With guidance rescale / APG (combine_params()) the blend of a guided evaluation is the combine kernel; mom: its momentum buffer
         (apg_momentum != 0), read and written by guided evaluations only.
-        comp: None, or the device operands (texts (K, B, ...), weights (B, K), masks (B, K, H, W) or None) of composed guidance; text_emb
-        is then texts[0] and is not read."""
-        bs = x.shape[0]
-        num_experts = self.model.num_experts
-        Unet_router_mask = torch.ones((bs, num_experts), device=x.device) if um is None else um
-        vit_router_mask = torch.ones((bs, num_experts), device=x.device) if vm is None else vm
-        kw = dict(x=x, sigma=sigma, Unet_router_mask=Unet_router_mask, Vit_router_mask=vit_router_mask, zeta=0,
-                  transition_point=transition_mean, softness=softness)
-        active = guided and (g is not None or self.guide != 1.0)
+        inp.texts: composed guidance; inp.text is then texts[0] and is not read."""
+        um, vm = (torch.ones((x.shape[0], self.model.num_experts), device=x.device) if m is None else m for m in (inp.um, inp.vm))
+        kw = dict(x=x, sigma=sigma, Unet_router_mask=um, Vit_router_mask=vm, zeta=0, transition_point=inp.transition_mean,
+                  softness=inp.softness)
+        # the guidance decision, once: the scale the kernels get and the combine record (eta, norm_threshold, momentum, rescale, state)
+        # or None; the exits below only choose a callee
+        active = guided and (inp.g is not None or self.guide != 1.0)
+        scale = (self.guide if inp.g is None else inp.g) if active else 1.0
         comb = self.combine_params() if active else None
-        if comp is not None:
+        rec = None if comb is None else comb + (mom,)
+        # no record: the keyword defaults of ops.guide_* are the identity scalars
+        ckw = {} if rec is None else dict(zip(("eta", "norm_threshold", "momentum", "rescale", "state"), rec))
+        if inp.texts is not None:
             # composed guidance: D_c of the K conditions takes the conditional output's place.  Not active (the interval, guided=False,
             # a float scale of 1): the same evaluation at scale 1 with the identity scalars, out = D_c, the momentum untouched
-            texts, cw, cm = comp
-            gd = (self.guide if g is None else g) if active else 1.0
-            eta, r, beta, phi = comb if comb is not None else (1.0, float("inf"), 0.0, 0.0)
             if self.shared_guidance:
                 self._check_shared(composed=True)
-                return self.model.forward_composed(text_embs=texts, uncond_text_emb=uncond_text_emb, weights=cw, masks=cm, guidance=gd,
-                                                   guide_combine=None if comb is None else comb + (mom,), **kw)["denoised"].to(self.dtype)
-            ds = [self.model(text_emb=texts[k], **kw)["denoised"].to(self.dtype) for k in range(texts.shape[0])]
-            ref_D_x = self.gnet(text_emb=uncond_text_emb, **kw)["denoised"].to(self.dtype)
-            return ops.guide_compose(ref_D_x, ds, cw, cm, gd, eta=eta, norm_threshold=r, momentum=beta, rescale=phi, state=mom)
+                return self.model.forward_composed(text_embs=inp.texts, uncond_text_emb=inp.unc, weights=inp.cw, masks=inp.cm,
+                                                   guidance=scale, guide_combine=rec, **kw)["denoised"].to(self.dtype)
+            ds = [self.model(text_emb=inp.texts[k], **kw)["denoised"].to(self.dtype) for k in range(inp.texts.shape[0])]
+            ref_D_x = self.gnet(text_emb=inp.unc, **kw)["denoised"].to(self.dtype)
+            return ops.guide_compose(ref_D_x, ds, inp.cw, inp.cm, scale, **ckw)
         if self.shared_guidance and active:
             # one pass: routing (and so the router masks) once, both text variants through the banks and the tail, the lerp in the egress
             self._check_shared()
-            if comb is not None:                              # the egress is the combine kernel
-                kw["guide_combine"] = comb + (mom,)
-            return self.model.forward_guided(text_emb=text_emb, uncond_text_emb=uncond_text_emb, guidance=self.guide if g is None else g,
-                                             **kw)["denoised"].to(self.dtype)
-        D_x = self.model(text_emb=text_emb, **kw)["denoised"].to(self.dtype)
+            if rec is not None:                               # the egress is the combine kernel
+                kw["guide_combine"] = rec
+            return self.model.forward_guided(text_emb=inp.text, uncond_text_emb=inp.unc, guidance=scale, **kw)["denoised"].to(self.dtype)
+        D_x = self.model(text_emb=inp.text, **kw)["denoised"].to(self.dtype)
         if not active:
             return D_x
-        emb_for_guide = uncond_text_emb if uncond_text_emb is not None else text_emb
-        ref_D_x = self.gnet(text_emb=emb_for_guide, **kw)["denoised"].to(self.dtype)
-        if comb is not None:
-            eta, r, beta, phi = comb
-            return ops.guide_combine(ref_D_x, D_x, self.guide if g is None else g, eta=eta, norm_threshold=r, momentum=beta, rescale=phi,
-                                     state=mom)
+        ref_D_x = self.gnet(text_emb=inp.unc if inp.unc is not None else inp.text, **kw)["denoised"].to(self.dtype)
+        if rec is not None:
+            return ops.guide_combine(ref_D_x, D_x, scale, **ckw)
         # ref.lerp(D, g) = (1-g)*ref + g*D
-        if g is not None:
-            return ops.lerp_rows(ref_D_x, D_x, g)
-        return ops.axpby(ref_D_x, D_x, 1.0 - self.guide, self.guide)
+        if inp.g is not None:
+            return ops.lerp_rows(ref_D_x, D_x, scale)
+        return ops.axpby(ref_D_x, D_x, 1.0 - scale, scale)
+
+    def _inputs(self, x, text_emb, transition_mean, softness, uncond_text_emb=None, tile=None, *, Unet_router_mask=None,
+                Vit_router_mask=None, guidance=None, compose_text=None, compose_weights=None, compose_masks=None):
+        """The one constructor of _Inputs, from the public arguments of sample() / denoise() under their public names; tile: None, or
+        sample()'s (tile, tile_overlap, tile_window, tile_batch).  Every check first (ValueError naming the argument, host work only),
+        then the tile-row repeat and the device moves.  Returns (record, _check_tile's record or None)."""
+        bs, dev = x.shape[0], x.device
+        comp = self._check_compose(x, text_emb, uncond_text_emb, compose_text, compose_weights, compose_masks)
+        g = self._check_guidance(guidance, bs)
+        um = self._router_mask(Unet_router_mask, "Unet_router_mask", bs)
+        vm = self._router_mask(Vit_router_mask, "Vit_router_mask", bs)
+        tile = None if tile is None else self._check_tile(x, comp, *tile)
+        put = lambda a: _each(lambda t: t.to(dev).contiguous(), a)
+        extra, cw, cm = comp or (None, None, None)            # composed guidance: the further conditions go behind text_emb
+        texts = None if comp is None else torch.cat([text_emb.detach()[None].to(dev), extra.to(device=dev, dtype=text_emb.dtype)])
+        inp = _Inputs(text_emb, uncond_text_emb, um, vm, g, texts, put(cw), put(cm), None, transition_mean, softness)
+        if tile is not None and tile["plan"].T > 1:           # everything below sample() sees a plain batch of B T rows
+            inp = inp.per_row(lambda a: a.repeat_interleave(tile["plan"].T, 0))
+        return inp._replace(um=put(inp.um), vm=put(inp.vm), g=put(inp.g)), tile
 
     # ---- argument checks of the extensions: ValueError naming the argument, before any device work ------------------------------------
     def _check_shared(self, composed=False):
@@ -328,15 +369,6 @@ class EDM_Sampler:
             m = m.expand((bs, K) + hw)
         return compose_text.detach(), w, m
 
-    @staticmethod
-    def _dev_compose(comp, x, text_emb):
-        """_check_compose's record on x's device as _denoise reads it: (texts (K, B, ...) with text_emb first, weights, masks)."""
-        if comp is None:
-            return None
-        extra, w, m = comp
-        texts = torch.cat([text_emb.detach()[None].to(x.device), extra.to(device=x.device, dtype=text_emb.dtype)])
-        return texts, w.to(x.device).contiguous(), None if m is None else m.to(x.device).contiguous()
-
     def guidance_plan(self, t_steps, i0=0):
         """Which evaluations of sample() lie in guidance_interval: one tuple of bools per stage i = i0 ... N - 1, in the order the stage
         makes its evaluations -- Heun (first, second), its last, Euler-only stage (first,), DPM-Solver++(2M) (its one,).  Pure host
@@ -374,10 +406,6 @@ class EDM_Sampler:
         if bool((h.sum(-1) == 0).any()):
             raise ValueError(f"{name} has a row with no allowed expert")
         return m.detach().to(torch.float32).expand(bs, E)
-
-    @staticmethod
-    def _dev_mask(m, like):
-        return None if m is None else m.to(like.device).contiguous()
 
     @staticmethod
     def _check_seed(seed):
@@ -457,20 +485,18 @@ class EDM_Sampler:
         mk = lambda rows: torch.empty((rows, C, plan.h, plan.w), dtype=torch.float32, device=x.device)
         return dict(tile, xt=mk(tb), buf=mk(B * plan.T) if tb < B * plan.T else None)
 
-    def _denoise_tiled(self, tile, x, sigma, text_emb, transition_mean, softness, uncond_text_emb, um, vm, guided, g):
+    def _denoise_tiled(self, tile, x, sigma, inp, guided):
         """_denoise() of a latent larger than the model: den_big = blend(model(gather(x_big))).  x keeps its B rows; every per-row operand
-        (text, masks, scales) has B T rows, tile-batch order.  Per chunk of tb rows: ops.tile_gather, _denoise, and (more than one chunk)
-        one copy_ into the tile buffer; then ONE ops.tile_blend.  The tile kernels are fp32: other latent dtypes are cast on the way in
-        and out, as _denoise casts the model's output.  No host read: it runs under stream capture like _denoise."""
+        of inp (text, masks, scales) has B T rows, tile-batch order.  Per chunk of tb rows: ops.tile_gather, _denoise, and (more than one
+        chunk) one copy_ into the tile buffer; then ONE ops.tile_blend.  The tile kernels are fp32: other latent dtypes are cast on the
+        way in and out, as _denoise casts the model's output.  No host read: it runs under stream capture like _denoise."""
         plan, tb = tile["plan"], tile["tb"]
         n = x.shape[0] * plan.T
         xf = x.to(torch.float32).contiguous()
-        cut = (lambda a, sl: a) if tb == n else (lambda a, sl: None if a is None else a[sl])
         for r0 in range(0, n, tb):
             sl = slice(r0, r0 + tb)
             xt = ops.tile_gather(xf, plan, r0, tb, out=tile["xt"])
-            d = self._denoise(xt.to(self.dtype), sigma, cut(text_emb, sl), transition_mean, softness, cut(uncond_text_emb, sl), cut(um, sl),
-                              cut(vm, sl), guided, cut(g, sl))
+            d = self._denoise(xt.to(self.dtype), sigma, inp if tb == n else inp.per_row(lambda a: a[sl]), guided)
             if tb == n:
                 tiles = d.to(torch.float32).contiguous()      # one chunk: blended from where the model left it
             else:
@@ -478,8 +504,8 @@ class EDM_Sampler:
                 tiles[sl].copy_(d)
         return ops.tile_blend(tiles, plan, x.shape[0]).to(self.dtype)
 
-    def _stage_state(self, kind, x, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, gvec=None, comp=None, tile=None):
-        """Static buffers, stage functions and (use_graph) captured graphs of one kind:
+    def _stage_state(self, kind, x, inp, tile=None):
+        """Static buffers, stage functions and (use_graph) captured graphs of one kind, for the latents x and the operands inp (_Inputs):
           "eval": one guided evaluation of x at sig into out (the host loops' evaluation with use_graph);
           "heun": a full Heun stage and the last, Euler-only stage; "dpm": one DPM-Solver++(2M) stage (den_prev: the previous stage's
                   denoiser output, read and overwritten element by element by the step kernel; i0: the first stage run).
@@ -487,7 +513,7 @@ class EDM_Sampler:
         the order on the device, so any strength shares one capture.  The SAME stage function runs eagerly and under capture: the two
         trajectories are bit-identical.  The key holds everything a capture bakes in -- shapes, which optional operands exist, and what
         _denoise reads on the host (guide, the two modules), the churn / SDE launch scalars -- never buffer values: every input, the seed of
-        the stochastic stages included (device word "seed") and the per-sample guidance scales ("g"), is refreshed before each run.
+        the stochastic stages included (device word "seed") and the operands (the record "inp"), is refreshed before each run.
         combine_params() -- launch scalars of the combine kernel -- are in the key; the APG momentum ("mom", float32, None without
         apg_momentum) is a buffer value: _refresh zeroes it at the start of a sample() call, every guided evaluation updates it in place.
 
@@ -496,42 +522,35 @@ class EDM_Sampler:
         guidance_plan() to its index in "fns" / "g_<kind>", so the interval's bounds are a host selection and not in the key.  Without an
         interval the lists are the all-guided ones alone: two for "heun" (full, last), one for "dpm" and "eval".
 
-        comp (composed guidance): its texts, weights and masks are static buffers ("texts", "cw", "cm") refreshed like every input; only K
-        and whether there are masks are in the key (its second entry).
-
+        Composed guidance: its texts, weights and masks are static buffers refreshed like every input; K and whether there are masks
+        are the key's second entry.  The "eval" kind reads no known region (the host loops blend it themselves): it drops inp.known.
         tile (tiled sampling, _check_tile's record): every evaluation of the state is _denoise_tiled.  x keeps its B rows, the per-row
         operands come with B T rows; the plan's device arrays and the tile buffers are part of the state ("tile"), and the tile spec --
         (h, w), the overlaps, the window, tile_batch, H, W -- is one more key entry, present only with tiling."""
-        shape = lambda a: None if a is None else tuple(a.shape)
-        variants = self.guidance_interval is not None and (gvec is not None or self.guide != 1.0)
-        key = (kind, None if comp is None else (int(comp[0].shape[0]), comp[2] is not None), self.solver, shape(x), x.dtype) \
+        if kind == "eval":
+            inp = inp._replace(known=None)
+        variants = self.guidance_interval is not None and (inp.g is not None or self.guide != 1.0)
+        key = (kind, None if inp.texts is None else (int(inp.texts.shape[0]), inp.cm is not None), self.solver, tuple(x.shape), x.dtype) \
             + (() if tile is None else (("tile",) + tile["key"],)) + (
-               shape(text_emb), shape(uncond_text_emb), float(transition_mean), float(softness),
-               self.num_steps, bool(self.use_graph), None if known is None else tuple(map(shape, known)), shape(um), shape(vm),
-               float(self.guide), id(self.model), id(self.gnet), float(self.s_churn), float(self.s_min), float(self.s_max), float(self.s_noise),
-               float(self.eta), bool(self.churn_on_device), self.combine_params(), gvec is not None, variants, bool(self.shared_guidance))
+               inp.signature(), self.num_steps, bool(self.use_graph), float(self.guide), id(self.model), id(self.gnet), float(self.s_churn),
+               float(self.s_min), float(self.s_max), float(self.s_noise), float(self.eta), bool(self.churn_on_device), self.combine_params(),
+               inp.g is not None, variants, bool(self.shared_guidance))
         slot = "_graph" if kind == "eval" else "_stage"          # one cached state for the evaluation, one for the solver stage
         st = getattr(self, slot)
         if st is not None and st["key"] == key:
             return st
-        dev = x.device
-        opt = lambda a: None if a is None else torch.empty_like(a)
-        # mods: held so that their ids, in the key, cannot be reused by other modules while this capture lives
-        st = dict(key=key, x=torch.empty_like(x), sig=torch.ones((), dtype=self.dtype, device=dev), text=torch.empty_like(text_emb),
-                  unc=opt(uncond_text_emb), known=None if known is None else tuple(map(torch.empty_like, known)), um=opt(um), vm=opt(vm),
-                  g=opt(gvec), variants=variants, mods=(self.model, self.gnet),
-                  mom=torch.zeros(x.shape, dtype=torch.float32, device=dev) if self._needs_momentum(gvec) else None,
-                  texts=None if comp is None else torch.empty_like(comp[0]), cw=None if comp is None else torch.empty_like(comp[1]),
-                  cm=None if comp is None else opt(comp[2]), tile=None if tile is None else self._tile_bufs(tile, x))
-        self._refresh(st, x, text_emb, uncond_text_emb, known, um, vm, gvec=gvec, comp=comp)
-        st_comp = None if comp is None else (st["texts"], st["cw"], st["cm"])
+        dev, static = x.device, inp.empty_like()
+        # the record's fields under their own names too ("known": the stage functions read it).  mods: held so that their ids, in the
+        # key, cannot be reused by other modules while this capture lives
+        st = dict(static._asdict(), key=key, x=torch.empty_like(x), sig=torch.ones((), dtype=self.dtype, device=dev), inp=static,
+                  variants=variants, mods=(self.model, self.gnet),
+                  mom=torch.zeros(x.shape, dtype=torch.float32, device=dev) if self._needs_momentum(inp.g) else None,
+                  tile=None if tile is None else self._tile_bufs(tile, x))
+        self._refresh(st, x, inp)
 
         def den(x_, guided):
-            if st["tile"] is not None:
-                return self._denoise_tiled(st["tile"], x_, st["sig"], st["text"], transition_mean, softness, st["unc"], st["um"], st["vm"],
-                                           guided, st["g"])
-            return self._denoise(x_, st["sig"], st["text"], transition_mean, softness, st["unc"], st["um"], st["vm"], guided, st["g"],
-                                 st["mom"], st_comp)
+            return (self._denoise(x_, st["sig"], static, guided, st["mom"]) if st["tile"] is None else
+                    self._denoise_tiled(st["tile"], x_, st["sig"], static, guided))
 
         def pick(j):                                          # sig = t[idx + j]
             ops.call("hdmoe_sched_pick", st["sig"], st["t"], st["idx"], j)
@@ -615,7 +634,7 @@ class EDM_Sampler:
         return graphs
 
     @staticmethod
-    def _refresh(st, x, text_emb, uncond_text_emb, known, um, vm, seed=None, gvec=None, reset_momentum=True, comp=None):
+    def _refresh(st, x, inp, seed=None, reset_momentum=True):
         """Every input into the static buffers: a later sample() with another prompt of the same shape must not see the captured one.
         seed: the 64-bit seed of this call's stochastic stages (a buffer value like the others, never part of the capture key).
         reset_momentum: zero the APG momentum -- the start of a sample() call (the warm-up runs of a capture have written it too); the
@@ -625,15 +644,7 @@ class EDM_Sampler:
         if seed is not None:
             st["seed"].fill_(seed - (1 << 64) if seed >= 1 << 63 else seed)
         st["x"].copy_(x)
-        st["text"].copy_(text_emb)
-        for name, src in (("unc", uncond_text_emb), ("um", um), ("vm", vm), ("g", gvec)):
-            if st[name] is not None:
-                st[name].copy_(src)
-        for buf, src in zip(st["known"] or (), known or ()):
-            buf.copy_(src)
-        for name, src in zip(("texts", "cw", "cm"), comp or ()):      # composed guidance: (texts, weights, masks or None)
-            if st[name] is not None:
-                st[name].copy_(src)
+        st["inp"].copy_from(inp)
 
     @staticmethod
     def _eps(x, seed, stage):
@@ -641,17 +652,15 @@ class EDM_Sampler:
         eps = ops.randn_like(x, 1.0) if seed is None else ops.randn_keyed(x, seed, stage)
         return eps.to(x.dtype)
 
-    def _dpm_host_loop(self, x, t_steps, i0, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, seed=None, plan=None,
-                       gvec=None, mom=None, comp=None, tile=None):
+    def _dpm_host_loop(self, x, t_steps, inp, seed, plan, mom, tile):
         """solver="dpmpp_2m" / "dpmpp_2m_sde" for latents the fused stage does not take (non-fp32 dtype): the rule of sample() with host
-        coefficients."""
-        N = self.num_steps
+        coefficients.  plan: guidance_plan() of the stages run, i0 ... N - 1."""
+        N, known, i0 = self.num_steps, inp.known, self.num_steps - len(plan)
         sde = self.solver == "dpmpp_2m_sde"
         den_prev = None
         for i in range(i0, N):
             t_cur, t_next = float(t_steps[i]), float(t_steps[i + 1])
-            den = self._eval(x, t_cur, text_emb, transition_mean, softness, uncond_text_emb, um, vm,
-                             True if plan is None else plan[i - i0][0], gvec, mom, first=i == i0, comp=comp, tile=tile)
+            den = self._eval(x, t_cur, inp, plan[i - i0][0], mom, i == i0, tile)
             e = math.exp(-self.eta * math.log(t_cur / t_next)) if sde and t_next > 0 else 1.0
             a = t_next / t_cur * e
             if t_next == 0:
@@ -668,18 +677,42 @@ class EDM_Sampler:
             den_prev = den
         return x
 
-    def _eval(self, x, t, text_emb, transition_mean, softness, uncond_text_emb, um=None, vm=None, guided=True, gvec=None, mom=None,
-              first=False, comp=None, tile=None):
+    def _heun_host_loop(self, x_next, t_steps, inp, seed, plan, mom, tile):
+        """solver="heun" for what the fused stage does not take (host churn, non-fp32 latents): the reference's loop (:90-107), every
+        latent update a fused launch.  plan: guidance_plan() of the stages run, i0 ... N - 1."""
+        N, known, i0 = self.num_steps, inp.known, self.num_steps - len(plan)
+        for i in range(i0, N):
+            t_cur, t_next = float(t_steps[i]), float(t_steps[i + 1])
+            gamma = min(self.s_churn / self.num_steps, np.sqrt(2) - 1) if (self.s_churn > 0 and self.s_min <= t_cur <= self.s_max) else 0
+            t_hat = t_cur + gamma * t_cur
+            x_hat = x_next
+            if gamma > 0:
+                x_hat = ops.axpby(x_next, self._eps(x_next, seed, i), 1.0, float(np.sqrt(t_hat ** 2 - t_cur ** 2) * self.s_noise))
+            denoised = self._eval(x_hat, t_hat, inp, plan[i - i0][0], mom, i == i0, tile)
+            # d_cur = (x_hat - denoised)/t_hat ; x_next = x_hat + (t_next - t_hat) * d_cur
+            h = (t_next - t_hat)
+            x_next = ops.axpby(x_hat, denoised, 1.0 + h / t_hat, -h / t_hat)
+            if known is not None:
+                ops.known_blend_(x_next, *known, t_next)
+            if i < self.num_steps - 1:
+                den2 = self._eval(x_next, t_next, inp, plan[i - i0][1], mom, False, tile)
+                # x_next = x_hat + h * (0.5*d_cur + 0.5*d_prime),  d_prime = (x_next - den2)/t_next
+                d_cur_term = ops.axpby(x_hat, denoised, 1.0 + 0.5 * h / t_hat, -0.5 * h / t_hat)     # x_hat + 0.5 h d_cur
+                d_pr = ops.axpby(x_next, den2, 0.5 * h / t_next, -0.5 * h / t_next)                  # 0.5 h d_prime
+                x_next = ops.axpby(d_cur_term, d_pr, 1.0, 1.0)
+                if known is not None:
+                    ops.known_blend_(x_next, *known, t_next)
+        return x_next
+
+    def _eval(self, x, t, inp, guided, mom, first, tile):
         """One evaluation at sigma t of the host loops; guided: the solver's guidance-interval decision for it.  mom: the call's APG
         momentum buffer (eager); the captured evaluation carries its own, zeroed on the first evaluation of a call.  tile: the tile
         record of a tiled call (eager: with this call's buffers, _tile_bufs); the evaluation is then _denoise_tiled."""
         if not self.use_graph:
             sig = torch.tensor(t, dtype=self.dtype, device=x.device)
-            if tile is not None:
-                return self._denoise_tiled(tile, x, sig, text_emb, transition_mean, softness, uncond_text_emb, um, vm, guided, gvec)
-            return self._denoise(x, sig, text_emb, transition_mean, softness, uncond_text_emb, um, vm, guided, gvec, mom, comp)
-        st = self._stage_state("eval", x, text_emb, transition_mean, softness, uncond_text_emb, None, um, vm, gvec, comp, tile)
-        self._refresh(st, x, text_emb, uncond_text_emb, None, um, vm, gvec=gvec, reset_momentum=first, comp=comp)
+            return self._denoise(x, sig, inp, guided, mom) if tile is None else self._denoise_tiled(tile, x, sig, inp, guided)
+        st = self._stage_state("eval", x, inp, tile)
+        self._refresh(st, x, inp, reset_momentum=first)
         st["sig"].fill_(float(t))
         guided = bool(guided) or not st["variants"]
         st["g_eval"][st["sel"][(guided,)]].replay()
@@ -778,18 +811,11 @@ class EDM_Sampler:
         replays the same graphs.  Refused (ValueError naming tile): composed guidance (its spatial masks would have to be tiled too),
         guidance_rescale and apg_* (their per-sample statistics and momentum would become per-tile ones).
         Argument errors raise ValueError (naming the argument) before any device work."""
-        comp = self._check_compose(noise, text_emb, uncond_text_emb, compose_text, compose_weights, compose_masks)
         strength = self._check_conditioning(noise, init_latents, strength, inpaint_mask)
         seed = self._check_seed(seed)
-        bs = noise.shape[0]
-        gvec = self._check_guidance(guidance, bs)
-        um = self._router_mask(Unet_router_mask, "Unet_router_mask", bs)
-        vm = self._router_mask(Vit_router_mask, "Vit_router_mask", bs)
-        tile = self._check_tile(noise, comp, tile, tile_overlap, tile_window, tile_batch)
-        if tile is not None and tile["plan"].T > 1:
-            # per-row operands: from here on _stage_state, _refresh, the static buffers and _denoise see a plain batch of B T rows
-            rep = lambda a: None if a is None else a.repeat_interleave(tile["plan"].T, 0)
-            text_emb, uncond_text_emb, um, vm, gvec = rep(text_emb), rep(uncond_text_emb), rep(um), rep(vm), rep(gvec)
+        inp, tile = self._inputs(noise, text_emb, transition_mean, softness, uncond_text_emb, (tile, tile_overlap, tile_window, tile_batch),
+                                 Unet_router_mask=Unet_router_mask, Vit_router_mask=Vit_router_mask, guidance=guidance,
+                                 compose_text=compose_text, compose_weights=compose_weights, compose_masks=compose_masks)
         device = noise.device
         if self.use_graph:
             # the captured evaluation holds no weight-prepare launch when the images were current at capture time: refresh them here,
@@ -798,17 +824,12 @@ class EDM_Sampler:
             for m_ in {id(self.model): self.model, id(self.gnet): self.gnet}.values():
                 if isinstance(m_, nn.Module) and getattr(m_, "_hdmoe_bank", None) is not None:
                     m_._hdmoe_bank.refresh_eval()
-        N = self.num_steps
-        i0 = N - math.ceil(strength * N)
+        i0 = self.num_steps - math.ceil(strength * self.num_steps)
         t_steps = self.t_schedule(device)
-        um, vm, gvec = self._dev_mask(um, noise), self._dev_mask(vm, noise), self._dev_mask(gvec, noise)
-        comp = self._dev_compose(comp, noise, text_emb)
         # the guidance-interval decision of every evaluation, taken here, on the host, from the float64 sigmas: denoise() never reads sigma
         plan = self.guidance_plan(t_steps, i0)
-        n_eval = sum(map(len, plan))
-        n_guided = sum(map(sum, plan)) if (gvec is not None or self.guide != 1.0) else 0
-        self.last_evaluations = {"guided": n_guided, "plain": n_eval - n_guided}
-        known = None
+        n_guided = sum(map(sum, plan)) if (inp.g is not None or self.guide != 1.0) else 0
+        self.last_evaluations = {"guided": n_guided, "plain": sum(map(len, plan)) - n_guided}
         if init_latents is None:
             x_next = ops.axpby(noise.to(self.dtype), None, float(t_steps[i0]), 0.0)
         else:
@@ -816,7 +837,7 @@ class EDM_Sampler:
             x0 = init_latents.to(device=device, dtype=self.dtype).contiguous()
             x_next = ops.axpby(x0, lat, 1.0, float(t_steps[i0]))
             if inpaint_mask is not None:                      # expanded once per call: the kernels read a mask of the latents' size
-                known = (x0, lat, inpaint_mask.to(device).expand(noise.shape).contiguous())
+                inp = inp._replace(known=(x0, lat, inpaint_mask.to(device).expand(noise.shape).contiguous()))
         fused = bool((self.s_churn <= 0 or self.churn_on_device) and self.dtype == torch.float32 and noise.is_cuda and self.num_steps >= 2)
         self.fused_heun = fused and self.solver == "heun"
         self.fused_dpm = fused and self.solver != "heun"
@@ -826,8 +847,8 @@ class EDM_Sampler:
             kind = "heun" if self.fused_heun else "dpm"
             if seed is None and (self.s_churn > 0 or (self.solver == "dpmpp_2m_sde" and self.eta > 0)):
                 seed = ops.next_seed()                        # a stochastic stage: one value of the library's stream per call
-            st = self._stage_state(kind, x_next, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, gvec, comp, tile)
-            self._refresh(st, x_next, text_emb, uncond_text_emb, known, um, vm, seed, gvec, comp=comp)
+            st = self._stage_state(kind, x_next, inp, tile)
+            self._refresh(st, x_next, inp, seed)
             st["t"].copy_(torch.from_numpy(t_steps))
             st["idx"].fill_(i0)
             if self.fused_dpm:
@@ -837,34 +858,8 @@ class EDM_Sampler:
                 runs[st["sel"][flags if st["variants"] else (True,) * len(flags)]]()
             return st["x"].clone()
         # host loops: this call's APG momentum (the captured evaluation of use_graph holds its own and zeroes it on the first evaluation)
-        mom = torch.zeros(x_next.shape, dtype=torch.float32, device=device) if self._needs_momentum(gvec) and not self.use_graph else None
+        mom = torch.zeros(x_next.shape, dtype=torch.float32, device=device) if self._needs_momentum(inp.g) and not self.use_graph else None
         if tile is not None and not self.use_graph:           # this call's tile buffers (the captured evaluation holds its own)
             tile = self._tile_bufs(tile, x_next)
-        if self.solver != "heun":
-            return self._dpm_host_loop(x_next, t_steps, i0, text_emb, transition_mean, softness, uncond_text_emb, known, um, vm, seed, plan,
-                                       gvec, mom, comp, tile)
-        for i in range(i0, N):
-            t_cur, t_next = float(t_steps[i]), float(t_steps[i + 1])
-            x_cur = x_next
-            gamma = min(self.s_churn / self.num_steps, np.sqrt(2) - 1) if (self.s_churn > 0 and self.s_min <= t_cur <= self.s_max) else 0
-            t_hat = t_cur + gamma * t_cur
-            x_hat = x_cur
-            if gamma > 0:
-                x_hat = ops.axpby(x_cur, self._eps(x_cur, seed, i), 1.0, float(np.sqrt(t_hat ** 2 - t_cur ** 2) * self.s_noise))
-            denoised = self._eval(x_hat, t_hat, text_emb, transition_mean, softness, uncond_text_emb, um, vm, plan[i - i0][0], gvec, mom,
-                                  first=i == i0, comp=comp, tile=tile)
-            # d_cur = (x_hat - denoised)/t_hat ; x_next = x_hat + (t_next - t_hat) * d_cur
-            h = (t_next - t_hat)
-            x_next = ops.axpby(x_hat, denoised, 1.0 + h / t_hat, -h / t_hat)
-            if known is not None:
-                ops.known_blend_(x_next, *known, t_next)
-            if i < self.num_steps - 1:
-                den2 = self._eval(x_next, t_next, text_emb, transition_mean, softness, uncond_text_emb, um, vm, plan[i - i0][1], gvec, mom, comp=comp,
-                                  tile=tile)
-                # x_next = x_hat + h * (0.5*d_cur + 0.5*d_prime),  d_prime = (x_next - den2)/t_next
-                d_cur_term = ops.axpby(x_hat, denoised, 1.0 + 0.5 * h / t_hat, -0.5 * h / t_hat)     # x_hat + 0.5 h d_cur
-                d_pr = ops.axpby(x_next, den2, 0.5 * h / t_next, -0.5 * h / t_next)                  # 0.5 h d_prime
-                x_next = ops.axpby(d_cur_term, d_pr, 1.0, 1.0)
-                if known is not None:
-                    ops.known_blend_(x_next, *known, t_next)
-        return x_next
+        loop = self._heun_host_loop if self.solver == "heun" else self._dpm_host_loop
+        return loop(x_next, t_steps, inp, seed, plan, mom, tile)

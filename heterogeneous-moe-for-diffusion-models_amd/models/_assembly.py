@@ -423,75 +423,39 @@ class _PrecondBase(nn.Module):
         finally:
             wbank.deactivate()
 
-    def _forward_guided(self, x: Tensor, sigma: Tensor, text_emb: Tensor, uncond_text_emb: Optional[Tensor], guidance: Union[float, Tensor],
-                        Unet_router_mask: Tensor, Vit_router_mask: Tensor, zeta, guide_combine=None, **kw):
-        """The classifier-free-guidance evaluation (1 - g) D(x; uncond) + g D(x; text) as ONE pass with shared routing (inference only):
-        net._fwd_guided on the pair-stacked batch, the guided D_x formed by the egress kernel.  uncond_text_emb None: the unconditional
-        branch is the conditional one (the reference's ref.lerp(D, g) with ref = D), i.e. the plain evaluation.
+    def _forward_shared(self, x: Tensor, sigma: Tensor, text_embs: Tensor, uncond_text_emb: Optional[Tensor], guidance: Union[float, Tensor],
+                        Unet_router_mask: Tensor, Vit_router_mask: Tensor, zeta, guide_combine=None, compose=None, **kw):
+        """A guided evaluation as ONE pass with shared routing (inference only), behind forward_guided (compose None) and forward_composed
+        (compose = (weights, masks)): net._fwd_guided on the variant-stacked batch [condition 1 ; ... ; condition K ; unconditional] of
+        text_embs (K, B, ...), 1 <= K <= ops.COMPOSE_MAX, the guided D_x formed by the egress kernel.
+        forward_guided (K = 1): (1 - g) D(x; uncond) + g D(x; text).  uncond_text_emb None: the unconditional branch is the conditional
+        one (the reference's ref.lerp(D, g) with ref = D), i.e. the plain evaluation: a record changes nothing, its buffer is untouched.
+        forward_composed: the egress ops.nhwc_to_nchw_compose forms D_c = D_u + sum_k weights[n, k] masks[n, k, p] (D_k - D_u) in
+        registers and applies the guidance combine to (D_c, D_u).  uncond_text_emb (B, ...) is required; weights: (B, K) float32; masks:
+        None or (B, K, H, W) float32 in [0, 1] (values are the caller's to check: nothing is read from the device).
         guidance: a float, or a (B,) tensor of per-sample scales; only the egress reads it, nothing else in the pass depends on it.
-        guide_combine: None, or the record (eta, norm_threshold, momentum, rescale, state) of ops.nhwc_to_nchw_guide_combine: the egress
-        is then that kernel (projected guidance and rescale of the two outputs, state = the (B, C, H, W) float32 momentum buffer or None).
-        With uncond_text_emb None the two outputs coincide and the record changes nothing: the plain evaluation, the buffer untouched."""
-        if isinstance(guidance, Tensor) and (tuple(guidance.shape) != (x.shape[0],) or not guidance.is_floating_point()):
-            raise ValueError(f"guidance must be a float or a floating-point tensor of shape ({x.shape[0]},), got {tuple(guidance.shape)} "
-                             f"{guidance.dtype}")
-        tensors = [t for t in (x, sigma, text_emb, uncond_text_emb) if isinstance(t, Tensor)]
-        if torch.is_grad_enabled() and (any(t.requires_grad for t in tensors) or any(p.requires_grad for p in self.parameters())):
-            raise RuntimeError("forward_guided is inference only: call it under torch.no_grad() (gradients take forward())")
-        if hgraph.current() is not None:
-            raise RuntimeError("forward_guided is inference only: not inside a staged training step")
-        if uncond_text_emb is None:
-            return self._forward(x, sigma, text_emb, Unet_router_mask, Vit_router_mask, zeta, False, **kw)
-        if not isinstance(uncond_text_emb, Tensor) or tuple(uncond_text_emb.shape) != tuple(text_emb.shape):
-            raise ValueError(f"uncond_text_emb must have the shape of text_emb {tuple(text_emb.shape)}, got "
-                             f"{tuple(getattr(uncond_text_emb, 'shape', ())) or type(uncond_text_emb).__name__}")
-        B = x.shape[0]
-        wbank.bank_for(self).begin_step(self.training)
-        try:
-            coef = ops.edm_coeffs(sigma, self.sigma_data, B)                # rows: c_skip, c_out, c_in, c_noise
-            c_skip, c_out, c_in, c_noise = coef[0], coef[1], coef[2], coef[3]
-            x32 = ops.cast(x, torch.float32)
-            xs = ops.to_nhwc(x32, scale=c_in, dtype=torch.float32)
-            out, p_u, raw_u, p_v, raw_v, scaling = self.net._fwd_guided(xs, c_noise, text_emb, uncond_text_emb.to(text_emb.dtype),
-                                                                         Unet_router_mask, Vit_router_mask, zeta, **kw)
-            if isinstance(guidance, Tensor):
-                guidance = guidance.detach().to(device=x32.device, dtype=torch.float32)
-            if guide_combine is None:
-                D_x = ops.nhwc_to_nchw_guided(out, c_out, x32, ops.mul(c_skip, c_in), guidance)
-            else:
-                eta, r, beta, phi, state = guide_combine
-                D_x = ops.nhwc_to_nchw_guide_combine(out, c_out, x32, ops.mul(c_skip, c_in), guidance, eta=eta, norm_threshold=r,
-                                                     momentum=beta, rescale=phi, state=state)
-        finally:
-            wbank.deactivate()
-        return {"denoised": D_x, "Unet_router_loss": p_u, "Unet_raw": raw_u, "vit_router_loss": p_v, "vit_raw": raw_v,
-                "scaling_net_out": scaling}
-
-    def _forward_composed(self, x: Tensor, sigma: Tensor, text_embs: Tensor, uncond_text_emb: Tensor, weights: Tensor,
-                          masks: Optional[Tensor], guidance: Union[float, Tensor], Unet_router_mask: Tensor, Vit_router_mask: Tensor, zeta,
-                          guide_combine=None, **kw):
-        """Composed guidance over K conditions as ONE pass with shared routing (inference only): net._fwd_guided on the variant-stacked
-        batch [condition 1 ; ... ; condition K ; unconditional], then the egress ops.nhwc_to_nchw_compose, which forms
-        D_c = D_u + sum_k weights[n, k] masks[n, k, p] (D_k - D_u) in registers and applies the guidance combine to (D_c, D_u).
-        text_embs: (K, B, ...), 1 <= K <= ops.COMPOSE_MAX; uncond_text_emb: (B, ...), required; weights: (B, K) float32; masks: None or
-        (B, K, H, W) float32 in [0, 1] (values are the caller's to check: nothing is read from the device).
-        guidance / guide_combine: as in forward_guided; without a record the egress gets the identity scalars, i.e.
-        (1 - g) D_u + g D_c."""
+        guide_combine: None, or the record (eta, norm_threshold, momentum, rescale, state) of the egress: projected guidance and rescale
+        of the two outputs, state = the (B, C, H, W) float32 momentum buffer or None.  Without a record the egress is the plain blend
+        (1 - g) D_u + g D_c; for composition that is the compose egress at its keyword defaults, the identity scalars."""
+        who = "forward_guided" if compose is None else "forward_composed"
         B = x.shape[0]
         if isinstance(guidance, Tensor) and (tuple(guidance.shape) != (B,) or not guidance.is_floating_point()):
             raise ValueError(f"guidance must be a float or a floating-point tensor of shape ({B},), got {tuple(guidance.shape)} "
                              f"{guidance.dtype}")
-        tensors = [t for t in (x, sigma, text_embs, uncond_text_emb, weights, masks) if isinstance(t, Tensor)]
+        tensors = [t for t in (x, sigma, text_embs, uncond_text_emb, *(compose or ())) if isinstance(t, Tensor)]
         if torch.is_grad_enabled() and (any(t.requires_grad for t in tensors) or any(p.requires_grad for p in self.parameters())):
-            raise RuntimeError("forward_composed is inference only: call it under torch.no_grad() (gradients take forward())")
+            raise RuntimeError(f"{who} is inference only: call it under torch.no_grad() (gradients take forward())")
         if hgraph.current() is not None:
-            raise RuntimeError("forward_composed is inference only: not inside a staged training step")
-        if not isinstance(text_embs, Tensor) or text_embs.ndim < 3 or text_embs.shape[1] != B or not 1 <= text_embs.shape[0] <= ops.COMPOSE_MAX:
+            raise RuntimeError(f"{who} is inference only: not inside a staged training step")
+        if compose is None and uncond_text_emb is None:
+            return self._forward(x, sigma, text_embs[0], Unet_router_mask, Vit_router_mask, zeta, False, **kw)
+        if compose is not None and (not isinstance(text_embs, Tensor) or text_embs.ndim < 3 or text_embs.shape[1] != B
+                                    or not 1 <= text_embs.shape[0] <= ops.COMPOSE_MAX):
             raise ValueError(f"text_embs must be a (K, {B}, ...) tensor with 1 <= K <= {ops.COMPOSE_MAX}, got "
                              f"{tuple(getattr(text_embs, 'shape', ())) or type(text_embs).__name__}")
-        K = text_embs.shape[0]
         if not isinstance(uncond_text_emb, Tensor) or tuple(uncond_text_emb.shape) != tuple(text_embs.shape[1:]):
-            raise ValueError(f"uncond_text_emb is required and must have the shape of one condition {tuple(text_embs.shape[1:])}, got "
+            what = "must have the shape of text_emb" if compose is None else "is required and must have the shape of one condition"
+            raise ValueError(f"uncond_text_emb {what} {tuple(text_embs.shape[1:])}, got "
                              f"{tuple(getattr(uncond_text_emb, 'shape', ())) or type(uncond_text_emb).__name__}")
         wbank.bank_for(self).begin_step(self.training)
         try:
@@ -504,9 +468,14 @@ class _PrecondBase(nn.Module):
                                                                          more_text=tuple(text_embs[1:].unbind(0)), **kw)
             if isinstance(guidance, Tensor):
                 guidance = guidance.detach().to(device=x32.device, dtype=torch.float32)
-            eta, r, beta, phi, state = (1.0, float("inf"), 0.0, 0.0, None) if guide_combine is None else guide_combine
-            D_x = ops.nhwc_to_nchw_compose(out, c_out, x32, ops.mul(c_skip, c_in), K, weights, masks, guidance, eta=eta, norm_threshold=r,
-                                           momentum=beta, rescale=phi, state=state)
+            ckw = {} if guide_combine is None else dict(zip(("eta", "norm_threshold", "momentum", "rescale", "state"), guide_combine))
+            sx = ops.mul(c_skip, c_in)
+            if compose is not None:
+                D_x = ops.nhwc_to_nchw_compose(out, c_out, x32, sx, text_embs.shape[0], *compose, guidance, **ckw)
+            elif guide_combine is not None:
+                D_x = ops.nhwc_to_nchw_guide_combine(out, c_out, x32, sx, guidance, **ckw)
+            else:
+                D_x = ops.nhwc_to_nchw_guided(out, c_out, x32, sx, guidance)
         finally:
             wbank.deactivate()
         return {"denoised": D_x, "Unet_router_loss": p_u, "Unet_raw": raw_u, "vit_router_loss": p_v, "vit_raw": raw_v,

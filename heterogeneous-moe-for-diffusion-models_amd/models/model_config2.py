@@ -70,7 +70,7 @@ class preconditioned_HDMOEM(_PrecondBase):
         guidance: a float, or a (B,) tensor of per-sample scales (read on the device by the egress kernel).
         guide_combine: None, or (eta, norm_threshold, momentum, rescale, state): projected guidance and rescale in the egress
         (ops.nhwc_to_nchw_guide_combine) instead of the plain blend."""
-        return self._forward_guided(x, sigma, text_emb, uncond_text_emb, guidance, Unet_router_mask, Vit_router_mask, zeta,
+        return self._forward_shared(x, sigma, text_emb[None], uncond_text_emb, guidance, Unet_router_mask, Vit_router_mask, zeta,
                                     guide_combine=guide_combine, transition_point=transition_point, softness=softness)
 
     def forward_composed(self, x: Tensor, sigma: Tensor, text_embs: Tensor, uncond_text_emb: Tensor, weights: Tensor,
@@ -80,5 +80,6 @@ class preconditioned_HDMOEM(_PrecondBase):
         With D_c = D_u + sum_k weights[n, k] masks[n, k, p] (D_k - D_u): (1 - guidance) D_u + guidance D_c, or, with the record
         guide_combine = (eta, norm_threshold, momentum, rescale, state), projected guidance and rescale of (D_c, D_u).
         weights: (B, K) float32; masks: None or (B, K, H, W) float32 in [0, 1]; uncond_text_emb is required."""
-        return self._forward_composed(x, sigma, text_embs, uncond_text_emb, weights, masks, guidance, Unet_router_mask, Vit_router_mask, zeta,
-                                      guide_combine=guide_combine, transition_point=transition_point, softness=softness)
+        return self._forward_shared(x, sigma, text_embs, uncond_text_emb, guidance, Unet_router_mask, Vit_router_mask, zeta,
+                                    guide_combine=guide_combine, compose=(weights, masks), transition_point=transition_point,
+                                    softness=softness)

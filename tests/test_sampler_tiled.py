@@ -364,14 +364,15 @@ def test_real_model_one_tiled_evaluation(real_model, shared):
     sig = torch.tensor(1.3, device=DEV)
     with torch.no_grad():
         s = EDM_Sampler(model, model, num_solve_steps=3, guidance=2.0, shared_guidance=shared, use_graph=True)
-        tile = s._check_tile(noise, None, (R, R), R // 2, "feather", 2)
+        inp, tile = s._inputs(x, text, TP, SOFT, unc, ((R, R), R // 2, "feather", 2))
         plan = tile["plan"]
         text_r, unc_r = text.repeat_interleave(plan.T, 0), unc.repeat_interleave(plan.T, 0)
         sl = slices(x, plan)
         tiles = torch.cat([s.denoise(sl[r:r + 2].contiguous(), sig, text_r[r:r + 2], TP, SOFT, unc_r[r:r + 2]) for r in range(0, 4, 2)])
         ref = blend64(tiles, plan, 2)
-        eager = s._denoise_tiled(s._tile_bufs(tile, x), x, sig, text_r, TP, SOFT, unc_r, None, None, True, None)
-        st = s._stage_state("eval", x, text_r, TP, SOFT, unc_r, None, None, None, None, None, tile)
+        assert torch.equal(inp.text, text_r) and torch.equal(inp.unc, unc_r)
+        eager = s._denoise_tiled(s._tile_bufs(tile, x), x, sig, inp, True)
+        st = s._stage_state("eval", x, inp, tile)
         st["sig"].fill_(1.3)
         st["g_eval"][0].replay()
         replayed = st["out"].clone()

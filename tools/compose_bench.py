@@ -62,8 +62,7 @@ def compose_kw(K):
 
 def captured(s, ckw):
     """The captured evaluation of sampler s (its "eval" stage state) on x at sigma 1.3: (graph, output getter)."""
-    comp = s._dev_compose(s._check_compose(x, text, unc, ckw.get("compose_text"), ckw.get("compose_weights"), ckw.get("compose_masks")), x, text)
-    st = s._stage_state("eval", x, text, TP, SOFT, unc, None, None, None, None, comp)
+    st = s._stage_state("eval", x, s._inputs(x, text, TP, SOFT, unc, **ckw)[0])
     st["sig"].fill_(1.3)
     return st["g_eval"][0], (lambda: st["out"])
 

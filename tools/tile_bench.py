@@ -185,8 +185,7 @@ def evaluation(args):
     with torch.no_grad():
         for name, spec in (("untiled", None), ("tiled_T1", (R, R))):
             s = EDM_Sampler(model, Guide_net=model, num_solve_steps=40, guidance=1.0, use_graph=True)
-            tile = s._check_tile(x, None, spec, 0, "feather", None)
-            st = s._stage_state("eval", x, text, -1.2, 1.2, None, None, None, None, None, None, tile)
+            st = s._stage_state("eval", x, *s._inputs(x, text, -1.2, 1.2, None, (spec, 0, "feather", None)))
             st["sig"].fill_(1.3)
             sides[name] = (lambda i, gr=st["g_eval"][0]: gr.replay())
             outs[name] = st
