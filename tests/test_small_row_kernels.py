@@ -20,6 +20,7 @@ import pytest
 import torch
 
 import test_norm_kernels as TN
+from test_weight_finish_kernels import SPLIT_REL
 
 pytestmark = pytest.mark.gpu
 
@@ -277,7 +278,7 @@ def _bf16_ulp(r):
 def test_bank_prepare_images(call, dt, normalize, mutate):
     """Every (fan-in, taps, O) tensor in ONE launch.  The forward image [tap][O][Ipad] and the flipped image [tap'][I][Opad] must hold the
     same bits at corresponding indices (any relayout error shows without a reference); the rows must match the fp64 normalisation to
-    4 * 2^-24 relative (fp32 images) or one bf16 ulp (bf16 images and the hi plane of split); a mutating prepare must leave w_raw rows
+    4 * 2^-24 relative (fp32 images) or one bf16 ulp (bf16 images and the hi plane of split), hi + lo of split to SPLIT_REL; a mutating prepare must leave w_raw rows
     of the fp64 computation's norm to 1e-6, and its images are held to the fp64 normalisation of the rows it stored -- the parameter is
     the forward's input, as in the reference; measured from the rows BEFORE the mutation instead, the stored rows' own fp32 rounding adds
     to the error and the worst fp32 element came out at 4.17 * 2^-24.
@@ -346,6 +347,13 @@ def test_bank_prepare_images(call, dt, normalize, mutate):
             ratio = float(((got - ref).abs() / _bf16_ulp(ref)).max())
         worst = max(worst, ratio)
         assert ratio <= 1.0, f"{tag}: |err| / bound = {ratio:.3f}"
+        if dt == "split":
+            # the lo plane against the reference: two roundings to nearest leave at most 2^-17 |v| of the fp32 value v (attained), and v is
+            # within 4 * 2^-24 of the reference -- the derivation stands at SPLIT_REL in tests/test_weight_finish_kernels.py.  (The flipped
+            # image's lo plane is tied to this one bit for bit above.)
+            lo = f[1, :, first:, :I].double()
+            r_lo = float(((got + lo - ref).abs() / (SPLIT_REL * ref.abs()).clamp_min(1e-300)).max())
+            assert r_lo <= 1.0, f"{tag}: |hi + lo - ref| / (SPLIT_REL |ref|) = {r_lo:.3f}"
     print(f"bank prepare {dt} normalize={normalize} mutate={mutate}: worst |err| / bound = {worst:.3f}")
 
 
