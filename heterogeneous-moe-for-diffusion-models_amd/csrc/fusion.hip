@@ -26,6 +26,7 @@
 // Streaming kernels: the floor is bytes / HBM rate (forward reads 2 and writes 5 tensors, backward reads 6 and writes 2 with sw).
 #include "common.h"
 #include "conv_args.h"
+#include "pw_stream.h"
 #include "hdmoe.h"
 
 namespace {
@@ -101,14 +102,13 @@ DEVI Row32 scaled(const Row32& a, float s) {
 }
 
 // ---- weight gradients inside the backward kernels (hdmoe_fusion_in_bwd_wg / hdmoe_fusion_out_bwd_wg) ------------------------------------
-// dW[o][i] = sum over rows of dy[row][o] x[row][i] contracts over what the row layout puts ACROSS lanes, so both operands take the route
-// of lwgrad.hip's lwg_bf16_kernel: the wave writes its 32 bf16 rows to a wave-private LDS tile ([32 rows][64 B], 16-byte stores) and
-// fetches the MFMA fragments back with the transposing read (8 consecutive rows of channel lane & 31), two 32x32x16 steps per 32 x 32
-// weight tile and row tile.  The 16-byte chunk c of row r sits at chunk c ^ ((r >> 1) & 3): unswizzled, the row-per-lane stores of eight
-// consecutive lanes would share two 16-byte bank slots; the transposing read takes an address per lane, so it follows the swizzle and
-// still covers whole 64-byte rows (conflict-free either way).  The fp32 accumulators stay in registers over the wave's tiles.
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((address_space(3))) s16x4* lds_p4;
+// dW[o][i] = sum over rows of dy[row][o] x[row][i] contracts over what the row layout puts ACROSS lanes, so both operands take the
+// LDS-transpose route of pw_stream.h: the wave writes its 32 bf16 rows to a wave-private LDS tile ([32 rows][64 B], 16-byte stores) and
+// fetches the MFMA fragments back with the transposing read (pws_tr8: 8 consecutive rows of channel lane & 31), two 32x32x16 steps per
+// 32 x 32 weight tile and row tile; a hand-over of the tile is a pws_fence.  The 16-byte chunk c of row r sits at chunk c ^ ((r >> 1) & 3):
+// unswizzled, the row-per-lane stores of eight consecutive lanes would share two 16-byte bank slots; the transposing read takes an address
+// per lane, so it follows the swizzle and still covers whole 64-byte rows (conflict-free either way).  The fp32 accumulators stay in
+// registers over the wave's tiles.
 constexpr int WG_TILE = 2048;                                 // bytes of one operand tile
 constexpr int WG_WGS = 512;                                   // default persistent grid of the _wg kernels: two workgroups per CU
 
@@ -118,21 +118,13 @@ DEVI void wg_put(unsigned char* tile, int r, int h, const Row32& x) {
   *reinterpret_cast<bf16x8*>(tile + wg_off(r, h)) = x.f[0];
   *reinterpret_cast<bf16x8*>(tile + wg_off(r, 2 + h)) = x.f[1];
 }
-// the tile is wave-private and the LDS keeps one wave's accesses in order: a hand-over needs a compiler fence, no workgroup barrier
-DEVI void wg_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 DEVI WgFrag wg_get(const unsigned char* tile, int lane) {
-  const int h = lane >> 5, q4 = (lane & 15) >> 2, c8 = ((lane & 16) >> 2) + (lane & 3);   // 8-byte chunk: channels 4 c8 .. 4 c8 + 3
+  const int c8 = pws_tr_col(lane) >> 3;                       // 8-byte chunk: channels 4 c8 .. 4 c8 + 3
   WgFrag f;
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
-    const int row = 16 * ks + 8 * h + q4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p4)(tile + wg_off(row, c8 >> 1) + 8 * (c8 & 1)));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p4)(tile + wg_off(row + 4, c8 >> 1) + 8 * (c8 & 1)));
-    f.k[ks] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+    const int row = 16 * ks + pws_tr_row(lane);
+    f.k[ks] = pws_tr8(tile + wg_off(row, c8 >> 1) + 8 * (c8 & 1), tile + wg_off(row + 4, c8 >> 1) + 8 * (c8 & 1));
   }
   return f;
 }
@@ -149,22 +141,15 @@ DEVI Row32 wg_keep(const Row32& x, bool ok) {
 }
 // End of the kernel: the four waves' accumulators of one weight tile meet in LDS in wave order (red: [4][16 regs][64 lanes] floats) and
 // the workgroup adds rows o < O of the tile into G (row stride ld) once, with float atomics.  Every workgroup adds to the same words:
-// each starts at another quarter (lwg_flush).  All threads of the workgroup must call it.
+// each starts at another quarter (pw_stream.h pws_flush).  All threads of the workgroup must call it.
 DEVI void wg_flush(const f32x16& acc, float* red, float* G, int O, int ld, int tid, unsigned rot) {
-  const int lane = tid & 63, wave = tid >> 6;
   __syncthreads();                                            // red is free: the operand tiles, or the previous tile's sums, are done with
-#pragma unroll
-  for (int reg = 0; reg < 16; ++reg) red[(wave * 16 + reg) * 64 + lane] = acc[reg];
+  pws_put<1>(red, tid >> 6, tid & 63, &acc);
   __syncthreads();
-  for (int e0 = tid; e0 < 1024; e0 += 256) {
-    const int e = (e0 + 256 * (int)(rot & 3)) & 1023;
-    const int l = e & 63, reg = e >> 6;
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) v += red[(w * 16 + reg) * 64 + l];
+  pws_flush<4, 1>(red, tid, 256, 256 * (int)(rot & 3), [&](int, int reg, int l) -> float* {
     const int o = acc_row(reg, l);
-    if (o < O) atomicAdd(&G[o * ld + (l & 31)], v);
-  }
+    return o < O ? &G[o * ld + (l & 31)] : nullptr;
+  });
 }
 
 struct FinArgs {
@@ -251,10 +236,10 @@ __global__ __launch_bounds__(256, WG ? 2 : 1) void fusion_in_bwd_kernel(FinBwdAr
           xc = addsub(cx, d, -1.f);
         }
         unsigned char* mine = wg_lds + w * 5 * WG_TILE;
-        wg_fence();                                            // (the previous tile's reads)
+        pws_fence();                                            // (the previous tile's reads)
         wg_put(mine, r, h, wg_keep(dq, ok)); wg_put(mine + WG_TILE, r, h, wg_keep(dk, ok)); wg_put(mine + 2 * WG_TILE, r, h, wg_keep(dv, ok));
         wg_put(mine + 3 * WG_TILE, r, h, xq); wg_put(mine + 4 * WG_TILE, r, h, xc);
-        wg_fence();
+        pws_fence();
         const WgFrag fq = wg_get(mine + 3 * WG_TILE, lane), fc = wg_get(mine + 4 * WG_TILE, lane);
         wg_mma(gacc[0], wg_get(mine, lane), fq);
         wg_mma(gacc[1], wg_get(mine + WG_TILE, lane), fc);
@@ -464,7 +449,7 @@ __global__ __launch_bounds__(256, WG ? 2 : 1) void fusion_out_bwd_kernel(FoutBwd
           cu.f[k][j] = (bf16)((float)U.f[k][j] * a.wa);                                                         // cat2_fwd_kernel
           ca.f[k][j] = (bf16)((float)a2.f[k][j] * a.wb);
         }
-      wg_fence();                                              // (the previous tile's reads)
+      pws_fence();                                              // (the previous tile's reads)
       wg_put(mine + 3 * WG_TILE, r, h, cu); wg_put(mine + 4 * WG_TILE, r, h, ca);
     }
     // gate_mix_bwd_vec_kernel
@@ -507,7 +492,7 @@ __global__ __launch_bounds__(256, WG ? 2 : 1) void fusion_out_bwd_kernel(FoutBwd
         *reinterpret_cast<bf16x2*>(mine + 5 * WG_TILE + wg_off(r, 0)) = d;
       }
       wg_put(mine + 6 * WG_TILE, r, h, s);
-      wg_fence();
+      pws_fence();
       const WgFrag fg = wg_get(mine + 2 * WG_TILE, lane);
       wg_mma(gacc[1], fg, wg_get(mine + 3 * WG_TILE, lane));
       wg_mma(gacc[2], fg, wg_get(mine + 4 * WG_TILE, lane));
@@ -537,7 +522,7 @@ __global__ __launch_bounds__(256, WG ? 2 : 1) void fusion_out_bwd_kernel(FoutBwd
       }
     if constexpr (WG) {
       wg_put(mine, r, h, wg_keep(dat, ok)); wg_put(mine + WG_TILE, r, h, o2);
-      wg_fence();
+      pws_fence();
       wg_mma(gacc[0], wg_get(mine, lane), wg_get(mine + WG_TILE, lane));
     }
     const Row32 do2 = proj(wdo, dat, a.ao, h);
@@ -630,7 +615,7 @@ __global__ __launch_bounds__(256, WG ? 2 : 1) void fusion_mid_bwd_kernel(FmidBwd
       if constexpr (WG) { nav = ld_row(a.a, nr, h); no1 = ld_row(a.o1, nr, h); }
     }
     if constexpr (WG) {
-      wg_fence();                                              // (the previous tile's reads)
+      pws_fence();                                              // (the previous tile's reads)
       wg_put(mine, r, h, wg_keep(dq2, ok)); wg_put(mine + WG_TILE, r, h, av);
       wg_put(mine + 3 * WG_TILE, r, h, o1);
     }
@@ -639,7 +624,7 @@ __global__ __launch_bounds__(256, WG ? 2 : 1) void fusion_mid_bwd_kernel(FmidBwd
     if (ok) { st_row(a.do1, row, h, do1); st_row(a.dres, row, h, dres); }
     if constexpr (WG) {
       wg_put(mine + 2 * WG_TILE, r, h, wg_keep(dat, ok));
-      wg_fence();
+      pws_fence();
       wg_mma(gacc[0], wg_get(mine, lane), wg_get(mine + WG_TILE, lane));
       wg_mma(gacc[1], wg_get(mine + 2 * WG_TILE, lane), wg_get(mine + 3 * WG_TILE, lane));
     }

@@ -5,11 +5,12 @@
 // (285 us for a 33 MB read).  Here both operands are K-contiguous in memory, so MFMA fragments are plain 16-byte global loads (no
 // LDS): a workgroup owns 32 rows, its eight waves split K in 64-element chunks (a lane reads 64 contiguous bytes of its row per
 // chunk = four k-steps; the k <-> MFMA-slot assignment is arbitrary as long as both operands use the same one), and the partial
-// sums meet in LDS in a fixed order (deterministic forward).
+// sums meet in LDS in wave order (pw_stream.h pws_put / pws_sum: deterministic forward).
 // DUAL (hdmoe_kgemm2_fwd): two 32-output layers over the SAME x in one launch -- tile 0 is layer 1 (w, y, alpha), tile 1 is layer 2 (w2,
 // y2, alpha2); x is read once.  Each output's products, chunk split and meeting order are those of its own NT = 1 launch: bit-equal.
 #include "common.h"
 #include "conv_args.h"
+#include "pw_stream.h"
 #include "hdmoe.h"
 
 namespace {
@@ -70,16 +71,11 @@ __global__ __launch_bounds__(512) void kgemm_kernel(KArgs a) {
       mma(1);
     }
   }
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) red[((wave * NT + t) * 16 + reg) * 64 + lane] = acc[t][reg];
+  pws_put<NT>(red, wave, lane, acc);
   __syncthreads();
   for (int e = tid; e < NT * 1024; e += 512) {
     const int l = e & 63, reg = (e >> 6) & 15, t = e >> 10;
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) v += red[((w * NT + t) * 16 + reg) * 64 + l];
+    float v = pws_sum<8, NT>(red, e);
     const long m = m0 + (l & 31);
     const int o = (DUAL ? 0 : 32 * t) + acc_row(reg, l);
     if (m < me) {

@@ -9,10 +9,13 @@
 //   fp32: no LDS at all -- for v_mfma_f32_32x32x2_f32 a lane supplies ONE element A[row = lane & 31][k = lane >> 5], which for
 //         position-major tensors is exactly a coalesced 128-byte row load per half-wave (exact fp32 products; these layers are tiny).
 // The four waves of a workgroup split the workgroup's slice range, add their accumulators through LDS and flush one [32*OT][32*IT]
-// tile with float atomics (the slab is shared with the other position partitions, as in conv_wgrad2).
+// tile with float atomics (the slab is shared with the other position partitions, as in conv_wgrad2).  The slot decode, the bf16 slice
+// pipeline, the hand-over of the accumulators, the flush and the launch plan are pw_stream.h's, shared with pbwd.hip, kgemm.hip and
+// fusion.hip.
 // Domain: Cin % 32 == 0, Cout % 32 == 0, no constant-one input channel; everything else stays with conv.hip.
 #include "common.h"
 #include "conv_args.h"
+#include "pw_stream.h"
 #include "hdmoe.h"
 
 namespace {
@@ -23,142 +26,54 @@ struct LwgArgs {
   int ngroups, N, I, O, upw;
   long HW;
 };
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((address_space(3))) s16x4* lds_p4;
 
-// partition slot -> (expert, slice range): experts take ceil(slices / upw) consecutive slots each
-DEVI bool lwg_slot(const LwgArgs& a, int slot, int& g, long& p0, long& p1, long& u0, long& u1) {
-  for (g = 0; g < a.ngroups; ++g) {
-    const long r0 = a.seg ? a.seg[g] : 0, r1 = a.seg ? a.seg[g + 1] : a.N;
-    p0 = r0 * a.HW; p1 = r1 * a.HW;
-    const long units = (p1 - p0 + 63) >> 6;
-    const long nch = (units + a.upw - 1) / a.upw;
-    if (slot < nch) { u0 = (long)slot * a.upw; u1 = u0 + a.upw < units ? u0 + a.upw : units; return true; }
-    slot -= (int)nch;
-  }
-  return false;
-}
-
-// DUAL: output tile t = 1 is the second layer's: rows o0 .. of its own slab G2
+// the four waves' tiles meet in LDS (red: [4 waves][OT * IT] tiles, pw_stream.h) and go into the slab with float atomics (it is shared with the
+// other position partitions).  DUAL: output tile t = 1 is the second layer's: rows o0 .. of its own slab G2
 template <int OT, int IT, bool DUAL = false>
 DEVI void lwg_flush(f32x16 (&acc)[OT][IT], float* red, float* G, int o0, int i0, int I, int tid, float* G2 = nullptr) {
-  // red: [4 waves][OT * IT][16 regs][64 lanes] floats; lane-major so that both the write and the summing read are conflict-free
-  const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
-  for (int t = 0; t < OT; ++t)
-#pragma unroll
-    for (int u = 0; u < IT; ++u)
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) red[((wave * OT * IT + t * IT + u) * 16 + reg) * 64 + lane] = acc[t][u][reg];
+  for (int t = 0; t < OT; ++t) pws_put<IT>(red, (tid >> 6) * OT + t, tid & 63, acc[t]);
   __syncthreads();
-  // every workgroup of the launch adds into the same [32*OT][32*IT] tile: start each one at a different element so that they do
-  // not all queue on the same addresses at the same time
   const int rot = (int)((blockIdx.z * 131u + blockIdx.x * 17u) % (unsigned)(OT * IT * 4)) * 256;
-  for (int e0 = tid; e0 < OT * IT * 1024; e0 += 256) {
-    const int e = (e0 + rot) % (OT * IT * 1024);
-    const int l = e & 63, reg = (e >> 6) & 15, tu = e >> 10;
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) v += red[((w * OT * IT + tu) * 16 + reg) * 64 + l];
+  pws_flush<4, OT * IT>(red, tid, 256, rot, [&](int tu, int reg, int l) -> float* {
     const int o = o0 + (DUAL ? 0 : 32 * (tu / IT)) + acc_row(reg, l), i = i0 + 32 * (tu % IT) + (l & 31);
-    atomicAdd(&((DUAL && tu / IT) ? G2 : G)[(long)o * I + i], v);
-  }
+    return &((DUAL && tu / IT) ? G2 : G)[(long)o * I + i];
+  });
 }
 
+// A wave streams its slices through PwsSlice (pw_stream.h): the next slice's loads are in flight while this one's MFMAs run.
 // DUAL (hdmoe_lwgrad2): two layers with 32 outputs each over the SAME x -- the dy sub-tile t = 0 is read from dy, t = 1 from dy2 (both
 // [P][32]) and the tiles flush into G / G2; x is read once.  Slices, waves and the order in which a workgroup sums are those of each
 // layer's own OT = 1 launch.
 template <int OT, int IT, bool DUAL = false>
 __global__ __launch_bounds__(256) void lwg_bf16_kernel(LwgArgs a) {
-  static_assert(!DUAL || OT == 2, "two layers = two output tiles");
   // per wave: dy sub-tiles [OT][64 positions][64 B], x sub-tiles [IT][64][64 B]; reused for the cross-wave reduction at the end
   constexpr int WB = (OT + IT) * 4096;
   extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int i0 = blockIdx.x * 32 * IT, o0 = blockIdx.y * 32 * OT;
   int g; long p0, p1, u0, u1;
-  if (!lwg_slot(a, blockIdx.z, g, p0, p1, u0, u1)) return;
-  const bf16* X = (const bf16*)a.x;
-  const bf16* DY = (const bf16*)a.dy;
-  const bf16* DY2 = (const bf16*)a.dy2;
+  if (!pws_slot(a.seg, a.ngroups, a.N, a.HW, a.upw, blockIdx.z, g, p0, p1, u0, u1)) return;
   unsigned char* mine = lds + wave * WB;
-  uint4 sdy[4 * OT], sx[4 * IT];
+  PwsSlice<OT, IT> s;
   auto load = [&](long u) {
-    const long pb = p0 + (u << 6);
-#pragma unroll
-    for (int k = 0; k < 4 * OT; ++k) {
-      const int e = lane + 64 * k, q = e / (4 * OT), pc = e % (4 * OT);
-      const long p = pb + q;
-      if constexpr (DUAL) sdy[k] = *reinterpret_cast<const uint4*>((pc < 4 ? DY : DY2) + (p < p1 ? p : p0) * 32 + (pc & 3) * 8);
-      else sdy[k] = *reinterpret_cast<const uint4*>(DY + (p < p1 ? p : p0) * a.O + o0 + pc * 8);
-    }
-#pragma unroll
-    for (int k = 0; k < 4 * IT; ++k) {
-      const int e = lane + 64 * k, q = e / (4 * IT), pc = e % (4 * IT);
-      const long p = pb + q;
-      sx[k] = *reinterpret_cast<const uint4*>(X + (p < p1 ? p : p0) * a.I + i0 + pc * 8);
-    }
-    // (positions past the range were read from the range's first position; they are zeroed here, after all loads were issued)
-#pragma unroll
-    for (int k = 0; k < 4 * OT; ++k) if (pb + (lane + 64 * k) / (4 * OT) >= p1) sdy[k] = make_uint4(0, 0, 0, 0);
-#pragma unroll
-    for (int k = 0; k < 4 * IT; ++k) if (pb + (lane + 64 * k) / (4 * IT) >= p1) sx[k] = make_uint4(0, 0, 0, 0);
-  };
-  auto store = [&]() {
-#pragma unroll
-    for (int k = 0; k < 4 * OT; ++k) {
-      const int e = lane + 64 * k, q = e / (4 * OT), pc = e % (4 * OT);
-      *reinterpret_cast<uint4*>(mine + (pc >> 2) * 4096 + q * 64 + (pc & 3) * 16) = sdy[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 4 * IT; ++k) {
-      const int e = lane + 64 * k, q = e / (4 * IT), pc = e % (4 * IT);
-      *reinterpret_cast<uint4*>(mine + OT * 4096 + (pc >> 2) * 4096 + q * 64 + (pc & 3) * 16) = sx[k];
-    }
-  };
-  // transposing-read lane address inside a [rows][64 B] sub-tile: fragment = 8 consecutive positions (k) of channel lane & 31
-  const int h = lane >> 5, q4 = (lane & 15) >> 2, col4 = (lane & 16) + 4 * (lane & 3);
-  const int tlane = (8 * h + q4) * 64 + col4 * 2;
-  auto tr2 = [&](const unsigned char* base) -> bf16x8 {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p4)(base));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p4)(base + 4 * 64));
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+    s.template load<DUAL>((const bf16*)a.dy, (const bf16*)a.dy2, (const bf16*)a.x, a.O, a.I, o0, i0, p0 + (u << 6), p0, p1, lane);
   };
   f32x16 acc[OT][IT];
 #pragma unroll
   for (int t = 0; t < OT; ++t)
 #pragma unroll
     for (int u = 0; u < IT; ++u) acc[t][u] = (f32x16)(0.f);
-  // the sub-tiles are WAVE-PRIVATE: the LDS keeps one wave's writes and reads in order, so a slice hand-over needs a compiler fence, not a
-  // workgroup barrier (two per slice marched the four waves in lockstep until round 3); the one barrier is in front of the shared flush
-  auto wfence = [&]() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
   const long iters = (u1 - u0 + 3) >> 2;
   if (u0 + wave < u1) load(u0 + wave);
   for (long it = 0; it < iters; ++it) {
     const long u = u0 + wave + 4 * it;
     const bool valid = u < u1;
-    wfence();
-    if (valid) store();
-    wfence();
+    pws_fence();
+    if (valid) s.store(mine, lane);
+    pws_fence();
     if (u + 4 < u1) load(u + 4);
-    if (valid) {
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        bf16x8 fdy[OT], fx[IT];
-#pragma unroll
-        for (int t = 0; t < OT; ++t) fdy[t] = tr2(mine + t * 4096 + ks * 1024 + tlane);
-#pragma unroll
-        for (int v = 0; v < IT; ++v) fx[v] = tr2(mine + (OT + v) * 4096 + ks * 1024 + tlane);
-#pragma unroll
-        for (int t = 0; t < OT; ++t)
-#pragma unroll
-          for (int v = 0; v < IT; ++v) acc[t][v] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fdy[t], fx[v], acc[t][v], 0, 0, 0);
-      }
-    }
+    if (valid) s.mma(mine, lane, acc);
   }
   __syncthreads();                                            // every wave is done with its sub-tiles: the flush re-uses the whole buffer
   lwg_flush<OT, IT, DUAL>(acc, reinterpret_cast<float*>(lds), a.G[g], o0, i0, a.I, tid, a.G2);
@@ -170,7 +85,7 @@ __global__ __launch_bounds__(256) void lwg_f32_kernel(LwgArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int i0 = blockIdx.x * 32 * IT, o0 = blockIdx.y * 32 * OT;
   int g; long p0, p1, u0, u1;
-  if (!lwg_slot(a, blockIdx.z, g, p0, p1, u0, u1)) return;
+  if (!pws_slot(a.seg, a.ngroups, a.N, a.HW, a.upw, blockIdx.z, g, p0, p1, u0, u1)) return;
   const float* X = (const float*)a.x;
   const float* DY = (const float*)a.dy;
   const int r = lane & 31, h = lane >> 5;
@@ -281,24 +196,15 @@ __global__ __launch_bounds__(64 * NW) void swg_f32_kernel(SwgArgs a) {
 #pragma unroll
       for (int b = 0; b < NBLK; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(dv[st], xv[st][b], acc[b], 0, 0, 0);
   }
-#pragma unroll
-  for (int b = 0; b < NBLK; ++b)
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) red[((wave * NBLK + b) * 16 + reg) * 64 + lane] = acc[b][reg];
+  pws_put<NBLK>(red, wave, lane, acc);
   __syncthreads();
-  const int rot = (int)((blockIdx.x * 37u) % (unsigned)(NBLK * 4)) * 256;      // stagger the workgroups' atomic flushes (see lwg_flush)
-  for (int e0 = tid; e0 < NBLK * 1024; e0 += 64 * NW) {
-    const int e = (e0 + rot) % (NBLK * 1024);
-    const int l = e & 63, reg = (e >> 6) & 15, b = e >> 10;
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) v += red[((w * NBLK + b) * 16 + reg) * 64 + l];
+  const int rot = (int)((blockIdx.x * 37u) % (unsigned)(NBLK * 4)) * 256;
+  pws_flush<NW, NBLK>(red, tid, 64 * NW, rot, [&](int b, int reg, int l) -> float* {
     const int o = o0 + acc_row(reg, l), n = 32 * b + (l & 31);
-    if (n < ncols) {
-      const int tap = n / a.Cin, i = n - tap * a.Cin;
-      atomicAdd(&a.G[((long)tap * a.Cout + o) * a.Cin + i], v);
-    }
-  }
+    if (n >= ncols) return nullptr;
+    const int tap = n / a.Cin, i = n - tap * a.Cin;
+    return &a.G[((long)tap * a.Cout + o) * a.Cin + i];
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -461,22 +367,14 @@ int lwg_try_launch(const void* x, const void* dy, float* const* G, const int* se
   a.x = x; a.dy = dy; a.seg = seg; a.ngroups = ngroups; a.N = N; a.HW = HW; a.I = Cin; a.O = Cout; a.dy2 = nullptr; a.G2 = nullptr;
   for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) a.G[g] = G[g < ngroups ? g : 0];
   const int OT = Cout % 64 == 0 ? 2 : 1, IT = Cin % 64 == 0 ? 2 : 1;
-  const long ib = Cin / (32 * IT), ob = Cout / (32 * OT);
-  const long units = ((long)N * HW + 63) / 64 + ngroups;               // 64-position slices (upper bound over the experts' ragged ends)
-  long upw = (units * ib * ob + 511) / 512;                              // ~512 workgroups per launch
-  if (upw < 4) upw = 4;                                                  // at least one slice per wave
-  if (upw > 4096) upw = 4096;
-  a.upw = (int)upw;
-  const long slots = units / upw + ngroups + 1;
-  if (slots > 65535 || ob > 65535) return 1;
-  dim3 grid((unsigned)ib, (unsigned)ob, (unsigned)slots);
-  const size_t red = (size_t)4 * OT * IT * 4096;
+  PwsPlan p;
+  if (!pws_plan(p, (long)N * HW, ngroups, Cin / (32 * IT), Cout / (32 * OT), OT, IT, dtype == HDMOE_BF16)) return 1;
+  a.upw = p.upw;
   if (dry_run) return HDMOE_OK;
-  const size_t stage = (size_t)4 * (OT + IT) * 4096;                     // (bf16: the staged operands share the buffer with the reduction)
   conv_pick<2, 1>(OT, [&](auto Ot) { conv_pick<2, 1>(IT, [&](auto It) {
     constexpr int O = decltype(Ot)::value, I = decltype(It)::value;
-    if (dtype == HDMOE_BF16) hipLaunchKernelGGL((lwg_bf16_kernel<O, I>), grid, dim3(256), stage > red ? stage : red, stream, a);
-    else hipLaunchKernelGGL((lwg_f32_kernel<O, I>), grid, dim3(256), red, stream, a);
+    if (dtype == HDMOE_BF16) hipLaunchKernelGGL((lwg_bf16_kernel<O, I>), p.grid, dim3(256), p.lds, stream, a);
+    else hipLaunchKernelGGL((lwg_f32_kernel<O, I>), p.grid, dim3(256), p.lds, stream, a);
   }); });
   return hdmoe_launch_status();
 }
@@ -493,14 +391,9 @@ extern "C" int hdmoe_lwgrad2(const void* x, const void* dy1, const void* dy2, fl
   LwgArgs a;
   a.x = x; a.dy = dy1; a.dy2 = dy2; a.seg = nullptr; a.ngroups = 1; a.N = 1; a.HW = P; a.I = Cin; a.O = 32; a.G2 = G2;
   for (int g = 0; g < HDMOE_MAX_GROUPS; ++g) a.G[g] = G1;
-  const long ib = Cin / 64;
-  const long units = (P + 63) / 64 + 1;                                  // as lwg_try_launch counts them for one group, OT = 1, IT = 2
-  long upw = (units * ib + 511) / 512;
-  if (upw < 4) upw = 4;
-  if (upw > 4096) upw = 4096;
-  a.upw = (int)upw;
-  const long slots = units / upw + 2;
-  if (slots > 65535) return 1;
-  hipLaunchKernelGGL((lwg_bf16_kernel<2, 2, true>), dim3((unsigned)ib, 1, (unsigned)slots), dim3(256), (size_t)4 * 2 * 2 * 4096, stream, a);
+  PwsPlan p;                                                             // the grid of ONE such layer (OT = 1, IT = 2), both layers' tiles in LDS
+  if (!pws_plan(p, P, 1, Cin / 64, 1, 2, 2, true)) return 1;
+  a.upw = p.upw;
+  hipLaunchKernelGGL((lwg_bf16_kernel<2, 2, true>), p.grid, dim3(256), p.lds, stream, a);
   return hdmoe_launch_status();
 }

@@ -4,7 +4,7 @@
 // Until round 6 a layer paid two launches for this (the general conv kernel on wd, then lwg_bf16_kernel), each reading all of dy.  The
 // weights are at most 128 x 64, so the layer is pure streaming: its floor is one read of dy, one of x and one write of dx.
 //
-// A wave streams 64-position slices exactly as lwg_bf16_kernel does: 16-byte loads -> wave-private LDS sub-tiles [64 positions][64 B].
+// A wave streams 64-position slices through pw_stream.h's PwsSlice: 16-byte loads -> wave-private LDS sub-tiles [64 positions][64 B].
 // The staged dy slice feeds BOTH products:
 //   dW: ds_read_b64_tr_b16 of dy and x (8 consecutive positions of one channel per lane), 32x32x16 MFMAs contracting over positions;
 //   dx: plain 16-byte reads of dy (8 consecutive channels o of one position per lane) as the B operand, the group's wd tile -- held in
@@ -12,11 +12,13 @@
 //       4 consecutive channels i of one position, so the result goes back into the (now free) x sub-tiles with 8-byte writes and
 //       leaves for HBM with the same coalesced 16-byte row pattern the loads use.
 // Persistent grid: one or two workgroups per CU, each a contiguous range of slices inside ONE expert group (so the wd tile never
-// changes), one flush of the dW tiles per workgroup: the four waves meet pairwise through LDS, then float atomics with a staggered start.
+// changes; pws_slot), one flush of the dW tiles per workgroup: the four waves meet pairwise through LDS (pws_put's layout), then float
+// atomics with a staggered start.
 // Domain: bf16; Cin % 32 == 0, Cout % 32 == 0, both <= 128, (Cin / 32) * (Cout / 32) <= 8 (the dW accumulators of a larger layer no
 // longer fit the register file next to the staging registers: 128 x 128, 128 x 96 and 96 x 96 stay on the two-launch path).
 #include "common.h"
 #include "conv_args.h"
+#include "pw_stream.h"
 #include "hdmoe.h"
 
 namespace {
@@ -27,21 +29,6 @@ struct PbwArgs {
   long HW, wdstride;
   float alpha;
 };
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((address_space(3))) s16x4* lds_p4;
-
-// partition slot -> (expert, slice range): experts take ceil(slices / upw) consecutive slots each (an expert without rows takes none)
-DEVI bool pbw_slot(const PbwArgs& a, int slot, int& g, long& p0, long& p1, long& u0, long& u1) {
-  for (g = 0; g < a.ngroups; ++g) {
-    const long r0 = a.seg ? a.seg[g] : 0, r1 = a.seg ? a.seg[g + 1] : a.N;
-    p0 = r0 * a.HW; p1 = r1 * a.HW;
-    const long units = p1 > p0 ? (p1 - p0 + 63) >> 6 : 0;
-    const long nch = (units + a.upw - 1) / a.upw;
-    if (slot < nch) { u0 = (long)slot * a.upw; u1 = u0 + a.upw < units ? u0 + a.upw : units; return true; }
-    slot -= (int)nch;
-  }
-  return false;
-}
 
 template <int OT, int IT>
 __global__ __launch_bounds__(256) void pw_bwd_kernel(PbwArgs a) {
@@ -51,9 +38,7 @@ __global__ __launch_bounds__(256) void pw_bwd_kernel(PbwArgs a) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int g; long p0, p1, u0, u1;
-  if (!pbw_slot(a, blockIdx.x, g, p0, p1, u0, u1)) return;
-  const bf16* X = a.x;
-  const bf16* DY = a.dy;
+  if (!pws_slot(a.seg, a.ngroups, a.N, a.HW, a.upw, blockIdx.x, g, p0, p1, u0, u1)) return;
   bf16* DX = a.dx;
   unsigned char* mine = lds + wave * WB;
   const int r = lane & 31, h = lane >> 5;
@@ -68,82 +53,26 @@ __global__ __launch_bounds__(256) void pw_bwd_kernel(PbwArgs a) {
 #pragma unroll
         for (int k2 = 0; k2 < 2; ++k2) wfr[u][t][k2] = *reinterpret_cast<const bf16x8*>(WD + (long)(32 * u + r) * a.O + 32 * t + 16 * k2 + 8 * h);
   }
-  uint4 sdy[4 * OT], sx[4 * IT];
-  auto load = [&](long u) {
-    const long pb = p0 + (u << 6);
-#pragma unroll
-    for (int k = 0; k < 4 * OT; ++k) {
-      const int e = lane + 64 * k, q = e / (4 * OT), pc = e % (4 * OT);
-      const long p = pb + q;
-      sdy[k] = *reinterpret_cast<const uint4*>(DY + (p < p1 ? p : p0) * a.O + pc * 8);
-    }
-#pragma unroll
-    for (int k = 0; k < 4 * IT; ++k) {
-      const int e = lane + 64 * k, q = e / (4 * IT), pc = e % (4 * IT);
-      const long p = pb + q;
-      sx[k] = *reinterpret_cast<const uint4*>(X + (p < p1 ? p : p0) * a.I + pc * 8);
-    }
-    // (positions past the range were read from the range's first position; they are zeroed here, after all loads were issued)
-#pragma unroll
-    for (int k = 0; k < 4 * OT; ++k) if (pb + (lane + 64 * k) / (4 * OT) >= p1) sdy[k] = make_uint4(0, 0, 0, 0);
-#pragma unroll
-    for (int k = 0; k < 4 * IT; ++k) if (pb + (lane + 64 * k) / (4 * IT) >= p1) sx[k] = make_uint4(0, 0, 0, 0);
-  };
-  auto store = [&]() {
-#pragma unroll
-    for (int k = 0; k < 4 * OT; ++k) {
-      const int e = lane + 64 * k, q = e / (4 * OT), pc = e % (4 * OT);
-      *reinterpret_cast<uint4*>(mine + (pc >> 2) * 4096 + q * 64 + (pc & 3) * 16) = sdy[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 4 * IT; ++k) {
-      const int e = lane + 64 * k, q = e / (4 * IT), pc = e % (4 * IT);
-      *reinterpret_cast<uint4*>(mine + OT * 4096 + (pc >> 2) * 4096 + q * 64 + (pc & 3) * 16) = sx[k];
-    }
-  };
-  // transposing-read lane address inside a [rows][64 B] sub-tile: fragment = 8 consecutive positions (k) of channel lane & 31
-  const int q4 = (lane & 15) >> 2, col4 = (lane & 16) + 4 * (lane & 3);
-  const int tlane = (8 * h + q4) * 64 + col4 * 2;
-  auto tr2 = [&](const unsigned char* base) -> bf16x8 {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p4)(base));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p4)(base + 4 * 64));
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-  };
+  PwsSlice<OT, IT> s;                                          // (whole rows of dy and x: no column offsets)
+  auto load = [&](long u) { s.load(a.dy, nullptr, a.x, a.O, a.I, 0, 0, p0 + (u << 6), p0, p1, lane); };
   f32x16 acc[OT][IT];
 #pragma unroll
   for (int t = 0; t < OT; ++t)
 #pragma unroll
     for (int u = 0; u < IT; ++u) acc[t][u] = (f32x16)(0.f);
-  // the sub-tiles are WAVE-PRIVATE: the LDS keeps one wave's writes and reads in order, so a hand-over needs a compiler fence only
-  auto wfence = [&]() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
   const long iters = (u1 - u0 + 3) >> 2;
   if (u0 + wave < u1) load(u0 + wave);
   for (long it = 0; it < iters; ++it) {
     const long u = u0 + wave + 4 * it;
     const bool valid = u < u1;
-    wfence();
-    if (valid) store();
-    wfence();
+    pws_fence();
+    if (valid) s.store(mine, lane);
+    pws_fence();
     if (u + 4 < u1) load(u + 4);
     if (valid) {
       // dW += dy^T x over the slice's 64 positions
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        bf16x8 fdy[OT], fx[IT];
-#pragma unroll
-        for (int t = 0; t < OT; ++t) fdy[t] = tr2(mine + t * 4096 + ks * 1024 + tlane);
-#pragma unroll
-        for (int v = 0; v < IT; ++v) fx[v] = tr2(mine + (OT + v) * 4096 + ks * 1024 + tlane);
-#pragma unroll
-        for (int t = 0; t < OT; ++t)
-#pragma unroll
-          for (int v = 0; v < IT; ++v) acc[t][v] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fdy[t], fx[v], acc[t][v], 0, 0, 0);
-      }
-      wfence();                                                // x has been consumed: its sub-tiles take dx
+      s.mma(mine, lane, acc);
+      pws_fence();                                                // x has been consumed: its sub-tiles take dx
       // dx^T[i][p] = sum_o wd[i][o] dy[p][o], 32 positions at a time
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh) {
@@ -169,7 +98,7 @@ __global__ __launch_bounds__(256) void pw_bwd_kernel(PbwArgs a) {
             *reinterpret_cast<bf16x4*>(mine + (OT + v) * 4096 + (32 * hh + r) * 64 + (8 * q + 4 * h) * 2) = o4;
           }
       }
-      wfence();
+      pws_fence();
       const long pb = p0 + (u << 6);
 #pragma unroll
       for (int k = 0; k < 4 * IT; ++k) {
@@ -181,13 +110,9 @@ __global__ __launch_bounds__(256) void pw_bwd_kernel(PbwArgs a) {
   }
   // ---- one flush per workgroup: waves 2, 3 hand their tiles to waves 0, 1 through LDS, those two meet in the atomic pass
   float* red = reinterpret_cast<float*>(lds);                  // [2][T][16 regs][64 lanes]: lane-major, conflict-free both ways
-  auto put = [&](int s) {
+  auto put = [&](int slot) {
 #pragma unroll
-    for (int t = 0; t < OT; ++t)
-#pragma unroll
-      for (int v = 0; v < IT; ++v)
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) red[((s * T + t * IT + v) * 16 + reg) * 64 + lane] = acc[t][v][reg];
+    for (int t = 0; t < OT; ++t) pws_put<IT>(red, slot * OT + t, lane, acc[t]);
   };
   __syncthreads();                                             // every wave is done with its sub-tiles
   if (wave >= 2) put(wave - 2);
